@@ -12,10 +12,15 @@ the timed region when it falls there.  With the driver's `--warmup 5 --steps 20`
 registration 1 and rounds 1-5 of registration 2: each of the reference's 20 rounds exactly once.  `regimes` splits the timed
 rounds by whether the LM solve still moved the poses.
 
-    python bench.py [--gpus N --steps K --warmup W] [--workload cfg2|cfg3|cfg4|cfg5|tiny|shard8|shard8_cfg5]
+    python bench.py [--gpus N --steps K --warmup W] [--workload cfg2|cfg3|cfg4|cfg5|tiny|shard8|shard8_cfg5] [--dump-outputs DIR] [--full]
 
 N > 1: launched by torch.distributed.run, one rank per GPU; edges are sharded across ranks and the per-edge normal-equation
 blocks are summed with an RCCL all-reduce per LM evaluation (strong scaling: the problem is fixed).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times exactly K rounds (one fenced window, no profiling scopes), writes the last timed round's outputs
+when --dump-outputs is given, and prints the line.  --full adds everything else: the timed window repeated until the timed region lasts
+2 s (value = the median window), live HIP-event scopes and the rooflines, the untimed census replay pass, the drop-in leg, the CPU
+reference legs and the full record in --detail-file.
 """
 import argparse
 import hashlib
@@ -254,6 +259,33 @@ def synth_pose_diff(A, B):
     return synth.pose_diff(A, B)
 
 
+DUMP_CORR_SAMPLE = 1 << 20    # correspondence triples --dump-outputs keeps (a fixed, seeded sample when the round found more)
+
+
+def dump_outputs(eng, rb, dirname):
+    """--dump-outputs: what the last timed round handed its caller, one .npy per array — the poses mvicp_optimize returned (K x 4 x 4,
+    row-major), its summary, the per-edge counts / weights of mvicp_correspond and a seeded sample of the correspondence lists in the
+    reference's layout (edge, first, second, dist).  Inputs are seeded, so two builds can be compared file by file."""
+    from mvicp import lib as L
+    os.makedirs(dirname, exist_ok=True)
+    sm = rb["sm"]
+    arrays = {
+        "poses": L.poses_from_c(rb["P"]),
+        "lm_summary": np.array([sm.initial_cost, sm.final_cost, sm.iterations, sm.successful_steps, sm.termination, sm.evaluations], dtype=np.float64),
+        "counts": rb["counts"].astype(np.float64),
+        "weights": rb["weights"].astype(np.float32),
+    }
+    triples, off = eng.map_correspondences(copy=False)
+    pos = np.arange(len(triples))
+    if len(pos) > DUMP_CORR_SAMPLE:
+        pos = np.sort(np.random.Generator(np.random.PCG64(0)).choice(len(triples), DUMP_CORR_SAMPLE, replace=False))
+    arrays["corr_edge"] = (np.searchsorted(off, pos, side="right") - 1).astype(np.float64)
+    for f in ("first", "second", "dist"):
+        arrays["corr_" + f] = triples[f][pos].astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -268,11 +300,17 @@ def main():
     ap.add_argument("--grid-target", type=float, default=None)
     ap.add_argument("--opt", action="append", default=[], help="library option name=value (mvicp_set_option), repeatable; tuning / A-B runs")
     ap.add_argument("--windows", type=int, default=0, help="the timed window of --steps rounds is repeated this many times; value = the MEDIAN window (all in window_values).  "
-                    "0 (default) = at least 5 and as many as make the whole timed region >= 2 s (sized from the first window)")
-    ap.add_argument("--detail-file", default=os.path.join(ROOT, "bench_detail.json"), help="where rank 0 writes the full record (windows, regimes, every kernel's roofline, the drop-in "
-                    "and CPU legs); the printed line stays compact and names this file")
+                    "0 (default) = one window in a plain run; with --full at least 5 and as many as make the whole timed region >= 2 s (sized from the first window)")
+    ap.add_argument("--detail-file", default=None, help="where rank 0 writes the full record (windows, regimes, every kernel's roofline, the drop-in "
+                    "and CPU legs); the printed line stays compact and names this file.  Default: bench_detail.json with --full, none in a plain run")
     ap.add_argument("--no-dropin", action="store_true", help="skip the drop-in leg (bin/multiview on the same problem written to disk, with and without copy-back)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: repeated windows, live kernel scopes and rooflines, the census replay pass, "
+                    "the drop-in leg and the CPU reference legs (--no-replay / --no-dropin / --no-cpu-baseline / --cpu-rounds select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed round computed (poses, LM summary, per-edge counts and weights, "
+                    "a seeded sample of the correspondence lists) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.full and args.detail_file is None:
+        args.detail_file = os.path.join(ROOT, "bench_detail.json")
     if args.gpus < 1 or args.steps < 1 or args.warmup < 0 or args.windows < 0:
         print("[bench] --gpus and --steps must be >= 1, --windows and --warmup >= 0", file=sys.stderr)
         sys.exit(2)
@@ -421,11 +459,13 @@ def main():
 
     for _ in range(args.warmup):
         step()
-    eng.profile(2)   # live HIP-event scopes around the roofline kernels only (one scope per NN kernel, "linearize") + the collective; everything else: replay pass below
-    eng.profile_reset()
+    if args.full:
+        eng.profile(2)   # live HIP-event scopes around the roofline kernels only (one scope per NN kernel, "linearize") + the collective; everything else: replay pass below
+        eng.profile_reset()
     # R back-to-back windows of exactly --steps rounds, each bracketed by barrier + synchronize on both sides and reduced with MAX over
-    # ranks; `value` is the MEDIAN window (a 20-round window is ~20 ms: one window alone is at the mercy of a single slow launch)
-    R = args.windows if args.windows > 0 else 5
+    # ranks; `value` is the MEDIAN window (a 20-round window is ~20 ms: one window alone is at the mercy of a single slow launch).
+    # A plain run times ONE window: --steps is the number of timed rounds.
+    R = args.windows if args.windows > 0 else (5 if args.full else 1)
     window_s, window_local_s = [], []
     w = 0
     while w < R:
@@ -441,7 +481,7 @@ def main():
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt = float(tt.item())
         window_s.append(dt)
-        if w == 0 and args.windows == 0:
+        if w == 0 and args.windows == 0 and args.full:
             # size the timed region from the first window: >= 2 s in total (the driver's 5-second GPU-activity sampler then sees it), at most 400 windows;
             # every rank takes the same decision (dt is the MAX over ranks)
             R = int(min(400, max(5, np.ceil(2.0 / max(dt, 1e-6)))))
@@ -456,11 +496,14 @@ def main():
     raw.clear()
 
     NN_SCOPES = ("nn_mfma", "nn_tile", "nn_grid", "nn_brute")   # one HIP-event scope per NN kernel; "nn_far" = the grid stage's second phase; "nn" = all together
-    timed = {k: eng.profile_get(k) for k in ("nn", "linearize", "comm", "nn_far") + NN_SCOPES}
-    spec_hits = eng.profile_get("spec.hit")[1] / R
-    host = {k: eng.profile_get(k)[0] / NSTEPS for k in ("host.correspond", "host.corr.setup", "host.corr.nn_launch", "host.corr.post_launch", "host.corr.wait",
-                                                          "host.corr.finish", "host.optimize", "host.evaluate")}
-    eng.profile(False)
+    if args.full:
+        timed = {k: eng.profile_get(k) for k in ("nn", "linearize", "comm", "nn_far") + NN_SCOPES}
+        spec_hits = eng.profile_get("spec.hit")[1] / R
+        host = {k: eng.profile_get(k)[0] / NSTEPS for k in ("host.correspond", "host.corr.setup", "host.corr.nn_launch", "host.corr.post_launch", "host.corr.wait",
+                                                              "host.corr.finish", "host.optimize", "host.evaluate")}
+        eng.profile(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, rb, args.dump_outputs)   # (the state the timed rounds left, before any untimed pass below)
     timed_log = list(log)
     final_poses = L.poses_from_c(Pc)
     g_end = state["g"]
@@ -472,7 +515,7 @@ def main():
     replay = None
     census = None
     replay_identical = None
-    if not args.no_replay:
+    if args.full and not args.no_replay:
         eng.reset_history()
         np.copyto(Pc, init_c)
         state["g"] = 0
@@ -494,7 +537,7 @@ def main():
     # registration 1 beyond the rounds the loop walked (untimed): the CPU-path comparison needs its first rounds
     cpu_rounds = args.cpu_rounds if args.cpu_rounds is not None else (8 if 2.0 * K * N <= 3e7 else 2)
     cpu_rounds = max(1, min(cpu_rounds, ROUNDS_PER_REGISTRATION))
-    if world == 1 and not args.no_cpu_baseline and max(poses_after, default=0) < cpu_rounds:
+    if args.full and world == 1 and not args.no_cpu_baseline and max(poses_after, default=0) < cpu_rounds:
         eng.reset_history()
         np.copyto(Pc, init_c)
         state["g"] = 0
@@ -509,19 +552,21 @@ def main():
     #   nn         per launch 24 N_src (queries) + 12 N_src (index + distance) + 24 x candidate points FETCHED FROM MEMORY + 8 x cells / boxes
     #              looked up, from the replay's exact census (hash-slot reads of the per-lane kernel are not counted: conservative).
     #              `compulsory` = the structure-independent bound 60 B per query the survey quotes next to it.
-    # one entry per kernel: (timed ms, timed launches, SURVEY bytes over those launches, compulsory bytes, library-model bytes)
-    prof = {"linearize": (timed["linearize"][0], timed["linearize"][1], timed["linearize"][2], None, None)}
-    for k in ("nn",) + NN_SCOPES:
-        ms_k, n_k, _ = timed[k]
-        if n_k == 0:
-            continue
-        alg = comp = model = float("nan")
-        # the replay pass repeats exactly the rounds under the live scopes (all R windows): same launches, now with the census on
-        if replay is not None and replay_ex[k]["launches"] == n_k:
-            alg = replay_ex[k]["survey_bytes"]
-            comp = 60.0 * replay_ex[k]["queries"]
-            model = replay_ex[k]["model_bytes"]
-        prof[k] = (ms_k, n_k, alg, comp, model)
+    # one entry per kernel: (timed ms, timed launches, SURVEY bytes over those launches, compulsory bytes, library-model bytes); --full only
+    prof = {}
+    if args.full:
+        prof["linearize"] = (timed["linearize"][0], timed["linearize"][1], timed["linearize"][2], None, None)
+        for k in ("nn",) + NN_SCOPES:
+            ms_k, n_k, _ = timed[k]
+            if n_k == 0:
+                continue
+            alg = comp = model = float("nan")
+            # the replay pass repeats exactly the rounds under the live scopes (all R windows): same launches, now with the census on
+            if replay is not None and replay_ex[k]["launches"] == n_k:
+                alg = replay_ex[k]["survey_bytes"]
+                comp = 60.0 * replay_ex[k]["queries"]
+                model = replay_ex[k]["model_bytes"]
+            prof[k] = (ms_k, n_k, alg, comp, model)
 
     sha = source_sha16()
 
@@ -572,7 +617,7 @@ def main():
         return r
 
     # the dominant KERNEL: largest total time under the live scopes among the individual kernels ("nn" is a scope over several kernels, never the headline)
-    dominant = max([k for k in prof if k != "nn"], key=lambda k: prof[k][0])
+    dominant = max([k for k in prof if k != "nn"], key=lambda k: prof[k][0], default=None)
     err_t = max(synth.pose_diff(final_poses[k], pb["gt"][k])[0] for k in range(K))
     err_r = max(synth.pose_diff(final_poses[k], pb["gt"][k])[1] for k in range(K))
 
@@ -586,7 +631,7 @@ def main():
                 "device_evaluations": float(np.mean([l["evals"] for l in rows]))}
 
     per_rank = None
-    if world > 1:
+    if world > 1 and args.full:
         # per-rank phase times (ms per step) so that a first real multi-GPU run is diagnosable: who waits for whom
         mine = torch.tensor([local_elapsed / args.steps * 1e3, float(np.mean([l["nn_ms"] for l in log])), float(np.mean([l["lm_ms"] for l in log])),
                              timed["nn"][0] / NSTEPS, timed["linearize"][0] / NSTEPS, timed["comm"][0] / NSTEPS, host["host.corr.wait"], host["host.evaluate"]],
@@ -626,12 +671,14 @@ def main():
                                   "lm_iterations": float(np.mean([l["lm_iters"] for l in log])), "device_evaluations": float(np.mean([l["evals"] for l in log])),
                                   "correspondences": float(np.mean([l["corr"] for l in log]))},
             "lm_step_economy": {"lm_iterations": int(sum(l["lm_iters"] for l in log)), "rejected_or_terminal_steps": int(rejected),
-                                "evaluations": int(sum(l["evals"] for l in log)), "first_evaluations_served_by_the_queued_launch": int(spec_hits)},
-            "kernel_ms_per_step": {**{k: timed[k][0] / NSTEPS for k in ("nn", "linearize", "nn_far") + NN_SCOPES if timed[k][1] > 0}},
-            "host_ms_per_step": host,
+                                "evaluations": int(sum(l["evals"] for l in log))},
             "pose_error_vs_gt": {"max_translation_m": err_t, "max_rotation_rad": err_r},
             "source_sha16": sha,
         }
+        if args.full:
+            out["lm_step_economy"]["first_evaluations_served_by_the_queued_launch"] = int(spec_hits)
+            out["kernel_ms_per_step"] = {k: timed[k][0] / NSTEPS for k in ("nn", "linearize", "nn_far") + NN_SCOPES if timed[k][1] > 0}
+            out["host_ms_per_step"] = host
         if replay is not None:
             out["kernel_ms_per_step"].update({k: replay[k][0] / NSTEPS for k in ("compact", "gather", "select", "reduce")})   # secondary scopes: replay pass
             out["replay_pass"] = {"identical_poses": replay_identical, "nn_ms_per_step": replay["nn"][0] / NSTEPS,
@@ -641,11 +688,12 @@ def main():
                                           "cells_or_boxes": census["nodes"] / q, "tree_fallback_fraction": census["far"] / q,
                                           "temporal_cache_hit_fraction": census["hits"] / q}
         if world > 1:
-            out["comm_ms_per_step"] = timed["comm"][0] / NSTEPS
-            out["comm_launches_per_step"] = timed["comm"][1] / NSTEPS
             out["rccl_nranks"] = eng.comm_nranks() if "rccl" in exchange else None
-            out["per_rank"] = per_rank
-        if world == 1 and not args.no_dropin and float(K) * N <= 8e6:   # (the leg writes the clouds to a temporary directory: not for the 64 x 1 M problem)
+            if args.full:
+                out["comm_ms_per_step"] = timed["comm"][0] / NSTEPS
+                out["comm_launches_per_step"] = timed["comm"][1] / NSTEPS
+                out["per_rank"] = per_rank
+        if args.full and world == 1 and not args.no_dropin and float(K) * N <= 8e6:   # (the leg writes the clouds to a temporary directory: not for the 64 x 1 M problem)
             # the literal drop-in route (bin/multiview: Frame / Session / ICP_Ceres mirror over the C ABI) on the same problem, after the clock stopped
             try:
                 sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -654,7 +702,7 @@ def main():
                 out["dropin"] = dropin_bench.run(pb, param, plane, cutoff, ROUNDS_PER_REGISTRATION)
             except Exception as ex:
                 out["dropin"] = {"error": repr(ex)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 moved_by_round = [bool(np.any(poses_after[r] != (pb["init"] if r == 1 else poses_after[r - 1]))) for r in sorted(poses_after)]
                 legs = cpu_reference_legs(pb, plane, param, [poses_after[r] for r in range(1, cpu_rounds + 1)], [iters_of[r] for r in range(1, cpu_rounds + 1)],
@@ -666,15 +714,16 @@ def main():
             except Exception as ex:  # the baseline is a reported extra, never the measurement
                 out["cpu_baseline"] = {"error": repr(ex)}
         detail = args.detail_file
-        try:
-            os.makedirs(os.path.dirname(os.path.abspath(detail)), exist_ok=True)
-            with open(detail, "w") as f:
-                json.dump(out, f)
-                f.write("\n")
-            detail = os.path.relpath(detail, ROOT)
-        except OSError as ex:   # a read-only checkout still gets its line
-            detail = None
-            print(f"[bench] could not write {args.detail_file}: {ex}", file=sys.stderr)
+        if detail:
+            try:
+                os.makedirs(os.path.dirname(os.path.abspath(detail)), exist_ok=True)
+                with open(detail, "w") as f:
+                    json.dump(out, f)
+                    f.write("\n")
+                detail = os.path.relpath(detail, ROOT)
+            except OSError as ex:   # a read-only checkout still gets its line
+                detail = None
+                print(f"[bench] could not write {args.detail_file}: {ex}", file=sys.stderr)
         sys.stdout.flush()
         print(compact_line(out, detail), flush=True)
     eng.close()

@@ -107,3 +107,46 @@ def test_compact_line_fits_the_driver_tail_and_round_trips():
     # a pathological record (long strings everywhere) still fits: optional blocks are dropped before the limit is broken
     full["dropin"] = {"copyback": {"it_per_s_after_first_round": 1.0, "first_round_ms": 2.0}, "device_only": {"it_per_s_after_first_round": 1.0, "first_round_ms": 2.0}, "fixed_point_note": "x" * 5000}
     assert len(bench.compact_line(full, "d.json")) <= bench.COMPACT_LIMIT
+
+
+def test_dump_outputs_writes_the_last_round_as_float_arrays(tmp_path):
+    """--dump-outputs: the last timed round's poses (row-major 4x4), LM summary, per-edge counts / weights and a seeded, sorted sample of
+    the correspondence lists, each a float32 / float64 .npy; the sample is the same from run to run and the files stay under 64 MB."""
+    from mvicp import lib as L
+
+    class StubEngine:   # what bench.dump_outputs reads from mvicp.Engine, without a GPU
+        def __init__(self, triples, off):
+            self.t, self.off = triples, off
+
+        def map_correspondences(self, copy=True):
+            return self.t, self.off
+
+    K, E = 3, 4
+    poses = np.array([np.eye(4) + 0.01 * k for k in range(K)])
+    sm = L.Summary(0.5, 0.25, 7, 5, 3, 9)
+    lens = [0, bench.DUMP_CORR_SAMPLE, 3, bench.DUMP_CORR_SAMPLE // 2]
+    off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    t = np.zeros(off[-1], dtype=L.Engine.CORR_DTYPE)
+    t["first"] = np.arange(off[-1]) % 1000
+    t["second"] = np.arange(off[-1]) // 7
+    t["dist"] = np.arange(off[-1]) * 1e-6
+    rb = {"P": L.poses_to_c(poses), "sm": sm, "counts": np.array(lens, dtype=np.int32), "weights": np.array([0, 0.1, 0.2, 0.3], dtype=np.float32)}
+    for d in ("a", "b"):
+        bench.dump_outputs(StubEngine(t, off), rb, str(tmp_path / d))
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(os.listdir(tmp_path / "b"))
+    assert {"poses.npy", "lm_summary.npy", "counts.npy", "weights.npy", "corr_edge.npy", "corr_first.npy", "corr_second.npy", "corr_dist.npy"} == set(files)
+    total = 0
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
+        total += os.path.getsize(tmp_path / "a" / f)
+    assert total <= 64 << 20
+    assert np.array_equal(np.load(tmp_path / "a" / "poses.npy"), poses)
+    assert list(np.load(tmp_path / "a" / "lm_summary.npy")) == [0.5, 0.25, 7, 5, 3, 9]
+    assert np.array_equal(np.load(tmp_path / "a" / "weights.npy"), rb["weights"])
+    e, first, second, dist = (np.load(tmp_path / "a" / f"corr_{k}.npy") for k in ("edge", "first", "second", "dist"))
+    assert len(first) == bench.DUMP_CORR_SAMPLE and np.all(np.diff(e) >= 0) and set(np.unique(e)) <= {1, 2, 3}
+    pos = np.rint(dist * 1e6).astype(np.int64)                                  # the sampled triples are whole records of their edge
+    assert np.all(np.diff(pos) > 0) and np.array_equal(first, pos % 1000) and np.array_equal(second, pos // 7)
+    assert np.array_equal(e, np.searchsorted(off, pos, side="right") - 1)

@@ -2,7 +2,7 @@
 side: the product's tie rule (mv-lm-icp_amd/csrc/kdvisit.h — nanoflann's split structure restated + "the child on the query's side is
 visited first") must reproduce the REAL nanoflann's 10-NN lists element for element, order included, on every row of
 samples/Bunny_RealData/cloudXYZ_0.xyz (golden: tests/golden/bunny_knn_full.npz, 1185 of 16 264 points have a tie at the 10th place),
-and on a synthetic lattice with duplicate points when oracle/_ref is available.  The device kernel uses the same header
+and on a synthetic lattice with duplicate points (golden: tests/golden/nanoflann_synthetic.npz, checked live where oracle/_ref is built).  The device kernel uses the same header
 (tests/test_gpu_parity.py::test_recompute_normals_full_cloud_matches_nanoflann_lists)."""
 import ctypes as C
 import os
@@ -45,12 +45,30 @@ def test_tie_order_reproduces_nanoflann_lists_on_the_bunny_lattice(harness):
     assert 0.005 < differ < 0.1, differ
 
 
-def test_tie_order_on_a_lattice_with_duplicate_points(harness, refnn):
-    if refnn is None:
-        pytest.skip("oracle/_ref not built")
+def lattice_points():
     rng = np.random.default_rng(1)
-    pts = np.round(rng.uniform(0, 1, (4000, 3)) * 20) / 20.0             # 21^3 lattice sites for 4000 points: duplicates and ties everywhere
-    gi, _ = refnn.knn_self(pts, 10)
+    return np.round(rng.uniform(0, 1, (4000, 3)) * 20) / 20.0              # 21^3 lattice sites for 4000 points: duplicates and ties everywhere
+
+
+def degenerate_points():
+    x = 2.0 ** np.arange(-450, 450, dtype=np.float64)                     # (squared distances stay finite)
+    pts = np.stack([x, np.zeros_like(x), np.zeros_like(x)], 1)
+    return np.vstack([pts, pts[::7]])                                   # + duplicates
+
+
+def nanoflann_lists(refnn, name, pts):
+    """The real nanoflann's 10-NN lists of `pts`: recorded in tests/golden/nanoflann_synthetic.npz (tests/golden/make_synthetic_nn.py);
+    where oracle/_ref is built, a live run must reproduce the recording."""
+    want = np.load(os.path.join(GOLD, "nanoflann_synthetic.npz"))[name]
+    if refnn is not None:
+        gi, _ = refnn.knn_self(pts, 10)
+        assert np.array_equal(gi, want)
+    return want
+
+
+def test_tie_order_on_a_lattice_with_duplicate_points(harness, refnn):
+    pts = lattice_points()
+    gi = nanoflann_lists(refnn, "lattice_knn_idx", pts)
     got, _ = knn(harness, pts, 10)
     assert np.array_equal(got, gi)
 
@@ -59,12 +77,8 @@ def test_degenerate_depth_is_not_a_recursion_depth(harness, refnn):
     """A cloud whose coordinates form a geometric progression: every middle split (nanoflann.hpp:1034-1078) peels ONE point off, so the
     tree is as deep as it has points (900 levels here; the exponent range of a double allows ~2000).  The product's builder walks it with an explicit
     stack (kdvisit.h divide) and must still agree with the real nanoflann (which recurses that deep), ties and all."""
-    if refnn is None:
-        pytest.skip("oracle/_ref not built")
-    x = 2.0 ** np.arange(-450, 450, dtype=np.float64)                     # (squared distances stay finite)
-    pts = np.stack([x, np.zeros_like(x), np.zeros_like(x)], 1)
-    pts = np.vstack([pts, pts[::7]])                                    # + duplicates
-    gi, _ = refnn.knn_self(pts, 10)
+    pts = degenerate_points()
+    gi = nanoflann_lists(refnn, "degenerate_knn_idx", pts)
     got, nodes = knn(harness, pts, 10)
     assert nodes == 2 * len(pts) - 1
     assert np.array_equal(got, gi)
