@@ -69,6 +69,26 @@ int mvicp_destroy(mvicp_ctx* ctx);
 int mvicp_set_num_frames(mvicp_ctx* ctx, int n_frames);
 int mvicp_set_frame(mvicp_ctx* ctx, int frame, const double* xyz, const double* nrm, int n);
 
+/* The same upload from DEVICE memory: a cloud that already lives in HBM (a torch tensor of a GPU pre-processing step, a depth-fusion
+ * result) is built into the same structures without a trip through host memory.  d_xyz / d_nrm: n x 3 row-major doubles in device memory
+ * of the context's device (d_nrm may be NULL); a host pointer or another device's pointer is MVICP_ERR_ARG.  The arrays must be fully
+ * written when the call is made (the caller synchronises the stream that produced them); the call copies them device-to-device into
+ * library-owned buffers before it returns, so the caller may free or overwrite them afterwards.  Everything else is mvicp_set_frame's:
+ * before mvicp_set_graph, a non-finite coordinate is MVICP_ERR_ARG reported by this call, option "async_build" moves the rest of the
+ * build behind the call (a failed build is reported, sticky, by the next entry point that needs the structures).  The structures are
+ * built on the GPU and are byte-identical to the ones mvicp_set_frame builds on the host for the same cloud and options. */
+int mvicp_set_frame_device(mvicp_ctx* ctx, int frame, const double* d_xyz, const double* d_nrm, int n);
+
+/* Read-back seam of the per-cloud structures (tests, diagnosis).  Waits for pending builds, then copies the named array of `frame` into
+ * out (host memory, cap_bytes long) or, with out NULL, only reports its size.  RETURNS THE BYTE COUNT (>= 0) or a negative mvicp_status.
+ * Names: "spts" "sidx" "srec" "crec" "inv" "snor" "table" "oct" "wide" "mf_ops" "mf_blk" "bricks" "celltab" (device arrays; absent
+ * ones are 0 bytes), "h_order" "h_inv" (the host copies of the order), "scalars" and "build_ms".
+ * "scalars" is one fp64 vector in this fixed order: dims[3], origin[3], cell, inv_cell, n_cells, table_mask, table_shift, oct_leaf,
+ * oct_first_leaf, wide_levels, wide_cnt[6], wide_off[6], maxabs, struct_bytes, max_norm, bdims[3] (32 values).
+ * "build_ms" is two doubles of the slot's last build: host wall milliseconds without the upload, device milliseconds of the device
+ * build's kernels (-1 for a host build). */
+long long mvicp_get_structure(mvicp_ctx* ctx, int frame, const char* name, void* out, long long cap_bytes);
+
 /* Replaces Frame::recomputeNormals() (include/frame.h:49, src/internal/frame.cpp:244-255; on by default in the reference,
  * main_multiview.cpp:49,68-70): normal of every point = eigenvector of the smallest eigenvalue of the covariance of its
  * k nearest points INCLUDING itself (reference k = 10), flipped so n_z <= 0 (include/common.h:331-346).  Overwrites the

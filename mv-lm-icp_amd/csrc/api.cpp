@@ -307,11 +307,25 @@ static int upload_sorted_normals(FrameDev& f, const double* nrm) {
   return MVICP_OK;
 }
 
+static bool injected_build_failure(mvicp_ctx* c) {
+  if (c->fault_inject_build.load() > 0 && c->fault_inject_build.fetch_sub(1) == 1) { set_error("injected structure-build failure (option fault_inject_build)"); return true; }
+  return false;
+}
+
 static int build_frame_structures(mvicp_ctx* c, FrameDev& f, const double* xyz, const double* nrm) {
-  if (c->fault_inject_build.load() > 0 && c->fault_inject_build.fetch_sub(1) == 1) { set_error("injected structure-build failure (option fault_inject_build)"); return MVICP_ERR_INTERNAL; }
+  if (injected_build_failure(c)) return MVICP_ERR_INTERNAL;
+  const auto t0 = std::chrono::steady_clock::now();
   MV_CHECK(build_grid(c, f, xyz));
   if (nrm) MV_CHECK(upload_sorted_normals(f, nrm));
+  f.build_ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  f.build_ms[1] = -1.0;
   return MVICP_OK;
+}
+
+// the device build of a cloud that mvicp_set_frame_device has copied to f.pts / f.nor (build.hip); the sorted normals are gathered there
+static int build_frame_structures_device(mvicp_ctx* c, FrameDev& f, const DevBounds& b, int grid_curve, double grid_target) {
+  if (injected_build_failure(c)) return MVICP_ERR_INTERNAL;
+  return build_grid_device(c, f, b, grid_curve, grid_target);
 }
 
 int finish_builds(mvicp_ctx* c) {
@@ -538,6 +552,130 @@ int mvicp_set_frame(mvicp_ctx* c, int frame, const double* xyz, const double* nr
   });
   f.job = job;
   return MVICP_OK;
+} MVICP_GUARD_ABI
+
+// a device pointer of this context's device (hipPointerGetAttributes), else MVICP_ERR_ARG
+static int check_device_pointer(mvicp_ctx* c, const void* p, const char* what) {
+  hipPointerAttribute_t at;
+  std::memset(&at, 0, sizeof(at));
+  const hipError_t e = hipPointerGetAttributes(&at, p);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();   // (the failed query leaves its error behind; the next launch check must not report it)
+    set_error("%s is not a device pointer (%s)", what, hipGetErrorString(e));
+    return MVICP_ERR_ARG;
+  }
+  if (at.type != hipMemoryTypeDevice) { set_error("%s is not device memory (memory type %d)", what, (int)at.type); return MVICP_ERR_ARG; }
+  if (at.device != c->device) { set_error("%s lives on device %d, the context on device %d", what, at.device, c->device); return MVICP_ERR_ARG; }
+  return MVICP_OK;
+}
+
+int mvicp_set_frame_device(mvicp_ctx* c, int frame, const double* d_xyz, const double* d_nrm, int n) try {
+  MV_CHECK(bind(c));
+  if (frame < 0 || frame >= c->n_frames) { set_error("frame %d out of range [0,%d)", frame, c->n_frames); return MVICP_ERR_ARG; }
+  if (n < 0 || (n > 0 && !d_xyz)) { set_error("bad cloud (n=%d)", n); return MVICP_ERR_ARG; }
+  if (c->E) { set_error("set frames before mvicp_set_graph"); return MVICP_ERR_STATE; }
+  if (n > 0) {
+    MV_CHECK(check_device_pointer(c, d_xyz, "xyz"));
+    if (d_nrm) MV_CHECK(check_device_pointer(c, d_nrm, "nrm"));
+  }
+  FrameDev& f = c->frames[frame];
+  if (f.job) { try { (void)f.job->fut.get(); } catch (...) {} f.job.reset(); }   // a build of the cloud this call replaces
+  dev_free(f.pts); dev_free(f.nor); free_grid(f.grid); free_tie(f);
+  f.has_grid = false; f.build_error.clear();
+  f.n = n;
+  f.max_norm = 0.0;
+  // library-owned copies (the caller may reuse its buffers once this call returns), then the one reduction the call itself needs:
+  // finiteness (reported by this call), max_norm, the bounding box and max |coordinate| of the build
+  MV_CHECK(dev_alloc(&f.pts, 3 * (size_t)n));
+  if (n) MV_HIP(hipMemcpyAsync(f.pts, d_xyz, sizeof(double) * 3 * (size_t)n, hipMemcpyDeviceToDevice, c->stream));
+  if (d_nrm) {
+    MV_CHECK(dev_alloc(&f.nor, 3 * (size_t)n));
+    if (n) MV_HIP(hipMemcpyAsync(f.nor, d_nrm, sizeof(double) * 3 * (size_t)n, hipMemcpyDeviceToDevice, c->stream));
+  }
+  if (n == 0) { MV_HIP(hipStreamSynchronize(c->stream)); return MVICP_OK; }
+  const auto t0 = std::chrono::steady_clock::now();
+  DevBounds b;
+  MV_CHECK(device_bounds(c->stream, f.pts, n, &b));
+  b.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (b.nonfinite) { set_error("non-finite coordinate in cloud"); return MVICP_ERR_ARG; }
+  f.max_norm = b.max_norm;
+  const int curve = c->grid_curve;
+  const double target = c->grid_target;
+  if (!c->async_build) {
+    const int st = build_frame_structures_device(c, f, b, curve, target);
+    if (st != MVICP_OK) { f.build_error = g_err; free_grid(f.grid); f.has_grid = false; }
+    return st;
+  }
+  // the rest of the build runs behind the call, as mvicp_set_frame's does, on a stream of its own; no host copy of the cloud is held
+  throttle_builds(c);
+  std::shared_ptr<BuildJob> job = std::make_shared<BuildJob>();
+  FrameDev* fp = &f;
+  BuildJob* jp = job.get();
+  job->fut = std::async(std::launch::async, [c, fp, jp, b, curve, target]() -> int {
+    build_slots().acquire();
+    int st = MVICP_ERR_INTERNAL;
+    try {
+      st = hipSetDevice(c->device) == hipSuccess ? build_frame_structures_device(c, *fp, b, curve, target) : MVICP_ERR_HIP;
+      if (st != MVICP_OK) jp->err = g_err;
+    } catch (const std::exception& e) { jp->err = std::string("structure build: ") + e.what(); }
+    catch (...) { jp->err = "structure build threw"; }
+    build_slots().release();
+    return st;
+  });
+  f.job = job;
+  return MVICP_OK;
+} MVICP_GUARD_ABI
+
+long long mvicp_get_structure(mvicp_ctx* c, int frame, const char* name, void* out, long long cap_bytes) try {
+  MV_CHECK(bind(c));
+  if (frame < 0 || frame >= c->n_frames || !name) { set_error("frame %d out of range [0,%d) or no name", frame, c->n_frames); return MVICP_ERR_ARG; }
+  MV_CHECK(finish_builds(c));
+  const FrameDev& f = c->frames[frame];
+  if (!f.has_grid) { set_error("frame %d has no structures (n = %d)", frame, f.n); return MVICP_ERR_STATE; }
+  const GridDev& G = f.grid;
+  const size_t n = (size_t)f.n;
+  const void* dsrc = nullptr; const void* hsrc = nullptr; size_t bytes = 0;
+  std::vector<double> sc;
+  const int tiles = (f.n + 31) / 32, blocks = (tiles + 63) / 64;
+  if (!std::strcmp(name, "spts")) { dsrc = G.spts; bytes = 24 * n; }
+  else if (!std::strcmp(name, "sidx")) { dsrc = G.sidx; bytes = 4 * n; }
+  else if (!std::strcmp(name, "srec")) { dsrc = G.srec; bytes = sizeof(PointRec) * n; }
+  else if (!std::strcmp(name, "crec")) { dsrc = G.crec; bytes = sizeof(PointRec) * n; }
+  else if (!std::strcmp(name, "inv")) { dsrc = G.inv; bytes = 4 * n; }
+  else if (!std::strcmp(name, "snor")) { dsrc = G.snor; bytes = G.snor ? 24 * n : 0; }
+  else if (!std::strcmp(name, "table")) { dsrc = G.table; bytes = 16 * ((size_t)G.table_mask + 1); }
+  else if (!std::strcmp(name, "oct")) { dsrc = G.oct; bytes = 32 * (size_t)(8 * G.oct_first_leaf + 1); }
+  else if (!std::strcmp(name, "wide")) { dsrc = G.wide; bytes = 4 * (size_t)(G.wide_off[G.wide_levels - 1] + 6ll * G.wide_cnt[G.wide_levels - 1]); }
+  else if (!std::strcmp(name, "mf_ops")) { dsrc = G.mf_ops; bytes = (size_t)std::max(tiles, 1) * 64 * 16; }
+  else if (!std::strcmp(name, "mf_blk")) { dsrc = G.mf_blk; bytes = (size_t)std::max(blocks, 1) * 48; }
+  else if (!std::strcmp(name, "bricks")) { dsrc = G.bricks; bytes = G.bricks ? 16 * (size_t)G.bdims[0] * G.bdims[1] * G.bdims[2] : 0; }
+  else if (!std::strcmp(name, "celltab")) { dsrc = G.celltab; bytes = G.celltab ? G.celltab_bytes : 0; }
+  else if (!std::strcmp(name, "h_order")) { hsrc = G.h_order.data(); bytes = 4 * G.h_order.size(); }
+  else if (!std::strcmp(name, "h_inv")) { hsrc = G.h_inv.data(); bytes = 4 * G.h_inv.size(); }
+  else if (!std::strcmp(name, "scalars") || !std::strcmp(name, "build_ms")) {
+    if (name[0] == 's') {
+      for (int a = 0; a < 3; ++a) sc.push_back(G.dims[a]);
+      for (int a = 0; a < 3; ++a) sc.push_back(G.origin[a]);
+      sc.push_back(G.cell); sc.push_back(G.inv_cell); sc.push_back(G.n_cells); sc.push_back(G.table_mask); sc.push_back(G.table_shift);
+      sc.push_back(G.oct_leaf); sc.push_back((double)G.oct_first_leaf); sc.push_back(G.wide_levels);
+      for (int l = 0; l < 6; ++l) sc.push_back(G.wide_cnt[l]);
+      for (int l = 0; l < 6; ++l) sc.push_back((double)G.wide_off[l]);
+      sc.push_back(G.maxabs); sc.push_back(G.struct_bytes); sc.push_back(f.max_norm);
+      for (int a = 0; a < 3; ++a) sc.push_back(G.bdims[a]);
+    } else {
+      sc.push_back(f.build_ms[0]); sc.push_back(f.build_ms[1]);
+    }
+    hsrc = sc.data(); bytes = sizeof(double) * sc.size();
+  } else { set_error("unknown structure name \"%s\"", name); return MVICP_ERR_ARG; }
+  if (!out) return (long long)bytes;
+  if (cap_bytes < (long long)bytes) { set_error("%s: %zu bytes do not fit in %lld", name, bytes, cap_bytes); return MVICP_ERR_ARG; }
+  if (bytes == 0) return 0;
+  if (hsrc) std::memcpy(out, hsrc, bytes);
+  else {
+    MV_HIP(hipStreamSynchronize(c->stream));   // (mvicp_recompute_normals rewrites snor on the context's stream)
+    MV_HIP(hipMemcpy(out, dsrc, bytes, hipMemcpyDeviceToHost));
+  }
+  return (long long)bytes;
 } MVICP_GUARD_ABI
 
 int mvicp_recompute_normals(mvicp_ctx* c, int frame, int k, double* nrm_out, int* knn_out) try {

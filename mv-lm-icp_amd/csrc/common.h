@@ -73,6 +73,7 @@ struct GridDev {
   // dense brick map over the cells (nn_grid.hip, nn_cell_kernel): brick = 4x4x4 cells -> {occupancy mask, row of the cell table};
   // cell table row = 64 x {start, count} of the cell runs in the sorted array.  Null when the grid is too large for a dense map.
   void* bricks = nullptr; void* celltab = nullptr; int bdims[3] = {0, 0, 0};
+  size_t celltab_bytes = 0;    // bytes of the cell table in use
 };
 
 struct PointRec { double x, y, z; long long idx; };  // 32-B aligned sorted point + original index
@@ -81,6 +82,9 @@ struct PointRec { double x, y, z; long long idx; };  // 32-B aligned sorted poin
 // on the device, the k-d order / box hierarchy / matrix-pipe operands / hash are built behind it, one cloud beside the other, and every
 // entry point that needs a structure waits for the pending builds first (finish_builds).
 struct BuildJob { std::future<int> fut; std::string err; std::vector<double> xyz, nrm; };
+
+// What the device build needs from the one reduction mvicp_set_frame_device runs before it returns (build.hip device_bounds)
+struct DevBounds { double lo[3], hi[3], max_norm, maxabs, wall_ms; int nonfinite, pad; };
 
 struct FrameDev {
   std::shared_ptr<BuildJob> job;   // pending structure build (null: none)
@@ -92,6 +96,7 @@ struct FrameDev {
   GridDev grid;
   bool has_grid = false;
   double max_norm = 0.0;   // max |p| over the cloud (bounds how far a pose change can move a query)
+  double build_ms[2] = {0.0, -1.0};   // the last structure build of this slot: host wall ms (upload excluded), device ms of the device build (-1: host build)
   // the reference's own tree over this cloud (kdvisit.h: split structure of nanoflann's buildIndex, leaf_max_size 1): decides exact distance
   // ties the way the reference does (nn_tie.hip) and orders the k-NN lists of the normals (normals.hip); built on first use
   void* tie_nodes = nullptr; int* tie_ord = nullptr; int* tie_slot = nullptr; double tie_box[6] = {0, 0, 0, 0, 0, 0}; bool has_tie = false;
@@ -316,6 +321,8 @@ int warm_nn_tile(mvicp_ctx* c); int warm_nn_grid(mvicp_ctx* c);                 
 int build_wide(FrameDev& f, const double* sorted_pts);                                 // nn_tile.hip (host, called by build_grid)
 int launch_nn_grid_queries(mvicp_ctx* c, const FrameDev& f, const double* d_q, int n, int* d_idx, double* d_d2);
 int build_grid(mvicp_ctx* c, FrameDev& f, const double* h_xyz);
+int device_bounds(hipStream_t stream, const double* d_xyz, int n, DevBounds* out);   // build.hip: the validate + bbox reduction (waits for it)
+int build_grid_device(mvicp_ctx* c, FrameDev& f, const DevBounds& b, int grid_curve, double grid_target);   // build.hip: same arrays as build_grid, from f.pts
 int finish_builds(mvicp_ctx* c);   // api.cpp: wait for every pending structure build of this context; first failure wins
 void free_grid(GridDev& g);
 void free_tie(FrameDev& f);                                                            // nn_tie.hip

@@ -36,6 +36,7 @@
 #include <thread>
 #include <unordered_set>
 
+#include "build_common.h"
 #include "common.h"
 #include "nn_list.h"
 #include "nn_tie.h"
@@ -49,10 +50,6 @@ namespace {
 #endif
 constexpr int NT = MVICP_GRID_THREADS;
 constexpr unsigned long long EMPTY = ~0ull;
-
-struct HashEntry { unsigned long long key; unsigned int start, count; };
-
-struct BrickEntry { unsigned long long mask; unsigned int tab; unsigned int pad; };   // 4x4x4 cells: bit (x&3) | (y&3)<<2 | (z&3)<<4
 
 struct GridView {  // device view of one cloud's structure
   const double* spts; const int* sidx; const PointRec* srec; int n;   // canonical (sorted-position) order
@@ -78,13 +75,6 @@ struct GridJob {
   int seed;            // out_idx still holds last round's neighbours (from any kernel): a starting candidate for far queries
   TieRef tie;          // where queries whose best distance was met by more than one target are reported (nn_tie.h)
 };
-
-__host__ __device__ __forceinline__ unsigned long long cell_key(int ix, int iy, int iz) {
-  return (unsigned long long)ix | ((unsigned long long)iy << 21) | ((unsigned long long)iz << 42);
-}
-__host__ __device__ __forceinline__ unsigned int hash_slot(unsigned long long k, int shift) {
-  return (unsigned int)((k * 0x9E3779B97F4A7C15ull) >> shift);
-}
 
 __device__ __forceinline__ void xf_point(const double* __restrict__ x, double p0, double p1, double p2, double& q0, double& q1, double& q2) {
   double g[3], u[3];
@@ -806,66 +796,12 @@ __global__ __launch_bounds__(256) void census_sum_kernel(const unsigned long lon
 }
 
 // ---------------------------------------------------------------------------------------- host build
-inline unsigned long long morton3(unsigned int x, unsigned int y, unsigned int z) {
-  auto spread = [](unsigned long long v) {
-    v &= 0x1fffffull;
-    v = (v | v << 32) & 0x1f00000000ffffull;
-    v = (v | v << 16) & 0x1f0000ff0000ffull;
-    v = (v | v << 8) & 0x100f00f00f00f00full;
-    v = (v | v << 4) & 0x10c30c30c30c30c3ull;
-    v = (v | v << 2) & 0x1249249249249249ull;
-    return v;
-  };
-  return spread(x) | (spread(y) << 1) | (spread(z) << 2);
-}
-
-// 3-D Hilbert index of a cell (Skilling's transpose algorithm, `bits` per axis).  Consecutive runs of a Hilbert-sorted
-// surface are compact patches without the long jumps of the Z-order curve at power-of-two boundaries, so the boxes of the
-// 32-point tiles / 8-ary tree nodes built over the sorted array are tighter and fewer of them overlap a query patch.
-inline unsigned long long hilbert3(unsigned int x, unsigned int y, unsigned int z, int bits) {
-  unsigned int X[3] = {x, y, z};
-  const unsigned int M = 1u << (bits - 1);
-  for (unsigned int Q = M; Q > 1; Q >>= 1) {
-    const unsigned int P = Q - 1;
-    for (int i = 0; i < 3; ++i) {
-      if (X[i] & Q) X[0] ^= P;
-      else { const unsigned int t = (X[0] ^ X[i]) & P; X[0] ^= t; X[i] ^= t; }
-    }
-  }
-  for (int i = 1; i < 3; ++i) X[i] ^= X[i - 1];
-  unsigned int t = 0;
-  for (unsigned int Q = M; Q > 1; Q >>= 1) if (X[2] & Q) t ^= Q - 1;
-  for (int i = 0; i < 3; ++i) X[i] ^= t;
-  return morton3(X[2], X[1], X[0]);   // interleave, X[0] most significant in every bit triple
-}
-
-struct HostGrid {
-  double o[3], h, inv_h;
-  int d[3];
-};
-
-inline void cell_of(const HostGrid& g, const double* p, int* c) {
-  for (int a = 0; a < 3; ++a) {
-    int v = (int)std::floor((p[a] - g.o[a]) * g.inv_h);
-    c[a] = std::min(std::max(v, 0), g.d[a] - 1);
-  }
-}
-
 size_t occupied_cells(const HostGrid& g, const double* xyz, int n, int stride) {
   std::unordered_set<unsigned long long> s;
   s.reserve((size_t)n / stride + 16);
   int c[3];
   for (int i = 0; i < n; i += stride) { cell_of(g, xyz + 3 * (size_t)i, c); s.insert(cell_key(c[0], c[1], c[2])); }
   return s.size();
-}
-
-void make_grid(HostGrid& g, const double* lo, const double* hi, double h) {
-  g.h = h; g.inv_h = 1.0 / h;
-  for (int a = 0; a < 3; ++a) {
-    g.o[a] = lo[a] - 0.01 * h;
-    g.d[a] = std::max(1, (int)std::ceil((hi[a] - g.o[a]) * g.inv_h + 0.01) + 1);
-    g.d[a] = std::min(g.d[a], (1 << 21) - 1);
-  }
 }
 
 
@@ -936,38 +872,13 @@ int build_grid(mvicp_ctx* c, FrameDev& f, const double* xyz) {
     for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], xyz[3 * (size_t)i + a]); hi[a] = std::max(hi[a], xyz[3 * (size_t)i + a]); }
   for (int i = 0; i < 3 * n; ++i)
     if (!std::isfinite(xyz[i])) { set_error("non-finite coordinate in cloud"); return MVICP_ERR_ARG; }
-  double ext = std::max(std::max(hi[0] - lo[0], hi[1] - lo[1]), hi[2] - lo[2]);
-  if (!(ext > 0.0)) ext = 1.0;
-  // cell edge: aim at ~6 points per occupied cell.  Measure occupancy at two resolutions (the cloud is a surface,
-  // so occupied(h) ~ h^-dim with dim ~ 2), extrapolate, verify once.
-  const double target = c->grid_target;
-  double h = ext / std::max(2.0, std::cbrt((double)n));
   HostGrid g;
-  if (n > 64) {
-    make_grid(g, lo, hi, h);
-    const double occ1 = (double)occupied_cells(g, xyz, n, 1);
-    make_grid(g, lo, hi, 2.0 * h);
-    const double occ2 = (double)occupied_cells(g, xyz, n, 1);
-    double dim = std::log(std::max(occ1, 1.0) / std::max(occ2, 1.0)) / std::log(2.0);
-    dim = std::min(3.0, std::max(1.0, dim));
-    const double want = (double)n / target;
-    h = h * std::pow(std::max(occ1, 1.0) / want, 1.0 / dim);
-    h = std::min(std::max(h, ext * 1e-6), ext);
-    for (int it = 0; it < 3; ++it) {
-      make_grid(g, lo, hi, h);
-      const double per = (double)n / (double)occupied_cells(g, xyz, n, 1);
-      if (per < 0.6 * target) h *= std::pow(target / per, 1.0 / dim);
-      else if (per > 1.8 * target) h *= std::pow(target / per, 1.0 / dim);
-      else break;
-    }
-  }
-  make_grid(g, lo, hi, h);
+  (void)choose_grid(g, n, lo, hi, c->grid_target, [&](const HostGrid& gg) { return (long long)occupied_cells(gg, xyz, n, 1); });
 
   // sort by (space-filling-curve index of the cell, original index)
   std::vector<unsigned long long> mkey(n), ckey(n);
   int cc[3];
-  int hbits = 1;
-  while ((1 << hbits) < std::max(g.d[0], std::max(g.d[1], g.d[2]))) ++hbits;
+  const int hbits = curve_bits(g);
   for (int i = 0; i < n; ++i) {
     cell_of(g, xyz + 3 * (size_t)i, cc);
     mkey[i] = c->grid_curve == 0 ? morton3((unsigned)cc[0], (unsigned)cc[1], (unsigned)cc[2])
@@ -994,60 +905,30 @@ int build_grid(mvicp_ctx* c, FrameDev& f, const double* xyz) {
     runs.push_back(HashEntry{ckey[corder[i]], (unsigned)i, (unsigned)(j - i)});
     i = j;
   }
-  int log2size = 4;
-  while ((1ull << log2size) < 2 * runs.size() + 2) ++log2size;
-  const unsigned int tsize = 1u << log2size, mask = tsize - 1;
-  const int shift = 64 - log2size;
-  std::vector<HashEntry> table(tsize, HashEntry{EMPTY, 0u, 0u});
-  for (const HashEntry& r : runs) {
-    unsigned int s = hash_slot(r.key, shift);
-    while (table[s].key != EMPTY) s = (s + 1) & mask;
-    table[s] = r;
-  }
+  std::vector<HashEntry> table;
+  unsigned int mask = 0; int shift = 0;
+  hash_runs(runs, table, mask, shift);
+  const unsigned int tsize = mask + 1;
 
-  // dense brick map (nn_cell_kernel): 4x4x4-cell bricks -> occupancy mask + row of the cell table; cell table = {start, count} of
-  // every cell run.  Only built when the dense array stays small (a surface scan at a few points per cell: ~1e5..1e6 bricks).
   {
-    const long long bd[3] = {(g.d[0] + 3) / 4, (g.d[1] + 3) / 4, (g.d[2] + 3) / 4};
-    const long long nb = bd[0] * bd[1] * bd[2];
-    const bool capped = g.d[0] >= (1 << 21) - 1 || g.d[1] >= (1 << 21) - 1 || g.d[2] >= (1 << 21) - 1;
-    if (!split_orders && !capped && nb <= (1ll << 24) && n < (1 << 30)) {   // nn_cell_kernel stages runs of the CANONICAL arrays
-      std::vector<BrickEntry> bricks((size_t)nb, BrickEntry{0ull, 0xffffffffu, 0u});
-      std::vector<uint2> celltab;
-      unsigned int n_tab = 0;
-      for (const HashEntry& r : runs) {
-        const int ix = (int)(r.key & 0x1fffffull), iy = (int)((r.key >> 21) & 0x1fffffull), iz = (int)((r.key >> 42) & 0x1fffffull);
-        BrickEntry& be = bricks[(size_t)(((long long)(iz >> 2) * bd[1] + (iy >> 2)) * bd[0] + (ix >> 2))];
-        if (be.tab == 0xffffffffu) { be.tab = n_tab++; celltab.resize((size_t)n_tab * 64, make_uint2(0u, 0u)); }
-        const int bit = (ix & 3) | ((iy & 3) << 2) | ((iz & 3) << 4);
-        be.mask |= 1ull << bit;
-        celltab[(size_t)be.tab * 64 + bit] = make_uint2(r.start, r.count);
-      }
-      MV_HIP(hipMalloc((void**)&G.bricks, sizeof(BrickEntry) * (size_t)nb));
-      MV_HIP(hipMemcpy(G.bricks, bricks.data(), sizeof(BrickEntry) * (size_t)nb, hipMemcpyHostToDevice));
+    std::vector<BrickEntry> bricks;
+    std::vector<uint2> celltab;
+    if (brick_map(runs, g, n, split_orders, bricks, celltab, G.bdims)) {
+      MV_HIP(hipMalloc((void**)&G.bricks, sizeof(BrickEntry) * bricks.size()));
+      MV_HIP(hipMemcpy(G.bricks, bricks.data(), sizeof(BrickEntry) * bricks.size(), hipMemcpyHostToDevice));
       MV_HIP(hipMalloc((void**)&G.celltab, sizeof(uint2) * std::max<size_t>(celltab.size(), 1)));
       MV_HIP(hipMemcpy(G.celltab, celltab.data(), sizeof(uint2) * celltab.size(), hipMemcpyHostToDevice));
-      G.bdims[0] = (int)bd[0]; G.bdims[1] = (int)bd[1]; G.bdims[2] = (int)bd[2];
+      G.celltab_bytes = sizeof(uint2) * celltab.size();
     }
   }
 
   const float finf = std::numeric_limits<float>::infinity();
-  auto down = [](double v) { float f = (float)v; if ((double)f > v) f = std::nextafterf(f, -std::numeric_limits<float>::infinity()); return f; };
-  auto up = [](double v) { float f = (float)v; if ((double)f < v) f = std::nextafterf(f, std::numeric_limits<float>::infinity()); return f; };
   // implicit complete 8-ary box tree over the sorted array (phase 2 of the grid kernel): 32-B boxes {lo.xyz, hi.xyz, pad}
   // leaves are ALIGNED runs of 8, 16 or 32 sorted points (whole k-d subtrees in the default order, so are all their ancestors' runs);
   // of the (depth, leaf size) pairs that cover n the one with the fewest empty leaves is taken; empty leaves keep inverted boxes
   // (lower bound +inf: never opened)
   int D8 = 0, L8 = 8;
-  {
-    long long best_cap = -1;
-    for (int d = 0; d <= 7; ++d)      // OCT_STACK holds 7 entries per level + 1
-      for (int l8 = 8; l8 <= 32; l8 *= 2) {
-        const long long cap = (1ll << (3 * d)) * l8;
-        if (cap >= std::max(n, 1) && (best_cap < 0 || cap < best_cap)) { best_cap = cap; D8 = d; L8 = l8; }
-      }
-    if (best_cap < 0) { D8 = 7; L8 = 64; while ((1ll << 21) * L8 < n) L8 *= 2; }   // > 67 M points: longer leaves
-  }
+  oct_shape(n, D8, L8);
   const long long leaves8 = 1ll << (3 * D8);
   const long long first_leaf8 = (leaves8 - 1) / 7;
   const long long nodes8 = first_leaf8 + leaves8;
@@ -1057,7 +938,7 @@ int build_grid(mvicp_ctx* c, FrameDev& f, const double* xyz) {
     float* bx = &oct[8 * (size_t)(first_leaf8 + j)];
     bx[0] = bx[1] = bx[2] = finf; bx[3] = bx[4] = bx[5] = -finf;
     for (int k = a; k < b; ++k)
-      for (int ax = 0; ax < 3; ++ax) { bx[ax] = std::min(bx[ax], down(spts[3 * (size_t)k + ax])); bx[3 + ax] = std::max(bx[3 + ax], up(spts[3 * (size_t)k + ax])); }
+      for (int ax = 0; ax < 3; ++ax) { bx[ax] = std::min(bx[ax], f32_down(spts[3 * (size_t)k + ax])); bx[3 + ax] = std::max(bx[3 + ax], f32_up(spts[3 * (size_t)k + ax])); }
   }
   for (long long id = first_leaf8 - 1; id >= 0; --id) {
     float* bx = &oct[8 * (size_t)id];

@@ -20,6 +20,7 @@
 // screen.  No LDS staging, no per-lane box tests below the block level (except in launches without any seed: the LBT build, scan_block),
 // confirmations read the 32-B sorted records straight from memory.  Levels >= 1 of the hierarchy are walked exactly as in nn_tile.hip.
 // Workgroups are 128 threads: the waves share nothing but the edge transform.
+#include "build_common.h"
 #include "nn_tile_common.h"
 
 namespace mvicp {
@@ -612,27 +613,6 @@ __global__ __launch_bounds__(MT, WPE) void nn_mfma_kernel(const TileJob* __restr
   }
 }
 
-// ---- host: f16 pieces of the targets (exact arithmetic, so the error terms in the block records are maxima, not estimates) ----
-unsigned short f16_bits(double x) {   // round to nearest even; |x| < 65520 (anything else, NaN included: the largest finite value)
-  if (x == 0.0) return 0;
-  if (!(std::fabs(x) < 65520.0)) return (unsigned short)((x < 0 ? 0x8000 : 0) | 0x7bff);
-  const unsigned short sign = x < 0 ? 0x8000 : 0;
-  const double a = std::fabs(x);
-  int e;
-  (void)std::frexp(a, &e);
-  int E = e - 1;
-  if (E < -14) return sign | (unsigned short)std::nearbyint(std::ldexp(a, 24));   // subnormal: multiples of 2^-24 (1024 -> the smallest normal)
-  double k = std::nearbyint(std::ldexp(a, 10 - E));
-  if (k == 2048.0) { k = 1024.0; ++E; }
-  if (E > 15) return sign | 0x7bff;
-  return sign | (unsigned short)(((E + 15) << 10) | ((int)k - 1024));
-}
-double f16_value(unsigned short h) {
-  const int e = (h >> 10) & 31, f = h & 1023;
-  const double v = e == 0 ? std::ldexp((double)f, -24) : std::ldexp((double)(1024 + f), e - 25);
-  return (h & 0x8000) ? -v : v;
-}
-
 __global__ void mfma_warm_kernel() {}
 
 }  // namespace
@@ -661,35 +641,18 @@ int build_mfma(FrameDev& f, const double* spts) {
     for (int t = b * FAN; t < std::min(tiles, (b + 1) * FAN); ++t)
       for (int i = 0; i < LEAF; ++i) {
         const int k = t * LEAF + i;
-        unsigned short lo8[8] = {0, 0, 0, 0, 0, 0, 0, 0}, hi8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        hi8[4] = f16_bits(4096.0); hi8[5] = hi8[6] = f16_bits(1.0);
-        if (k < n) {
-          double bt[3], res2 = 0.0, nn = 0.0;
-          for (int a = 0; a < 3; ++a) {
-            const double beta = (spts[3 * (size_t)k + a] - c[a]) * scale;
-            const unsigned short h = f16_bits(beta);
-            const unsigned short l = f16_bits(beta - f16_value(h));
-            bt[a] = f16_value(h) + f16_value(l);
-            res2 += (beta - bt[a]) * (beta - bt[a]);
-            nn += bt[a] * bt[a];
-            lo8[a] = hi8[a] = f16_bits(-2.0 * f16_value(h));
-            lo8[3 + a] = f16_bits(-2.0 * f16_value(l));
-          }
-          const unsigned short n1 = f16_bits(nn), n2 = f16_bits(nn - f16_value(n1)), n3 = f16_bits(nn - f16_value(n1) - f16_value(n2));
-          lo8[6] = n1; lo8[7] = n2; hi8[3] = n3;
-          en = std::max(en, std::fabs(nn - f16_value(n1) - f16_value(n2) - f16_value(n3)) + nn * 1e-15);
-          db = std::max(db, std::sqrt(res2));
-        } else {
-          lo8[6] = 0x7bff;   // padding: |b|^2 = 65504, never below a finite threshold (and k < n is re-checked before a confirmation)
-        }
+        unsigned short lo8[8], hi8[8];
+        double res, e;
+        mf_point(k < n ? spts + 3 * (size_t)k : nullptr, c, scale, lo8, hi8, res, e);
+        if (k < n) { en = std::max(en, e); db = std::max(db, res); }
         std::memcpy(&ops[((size_t)t * 64 + i) * 8], lo8, 16);
         std::memcpy(&ops[((size_t)t * 64 + 32 + i) * 8], hi8, 16);
       }
     MfBlock& B = blk[b];
     B.cx = c[0]; B.cy = c[1]; B.cz = c[2]; B.scale = scale;
     // + the fp64 rounding of (p - c) * scale on the host
-    B.db = (float)((db + (cloud_max + std::fabs(c[0]) + std::fabs(c[1]) + std::fabs(c[2])) * scale * 4.5e-16) * 1.000001 + 1e-30);
-    B.en = (float)(en * 1.000001 + 1e-30);
+    B.db = mf_block_db(db, cloud_max, c, scale);
+    B.en = mf_block_en(en);
     B.pad0 = B.pad1 = 0.f;
   }
   MV_HIP(hipMalloc((void**)&G.mf_ops, ops.size() * sizeof(unsigned short)));

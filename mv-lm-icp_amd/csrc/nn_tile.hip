@@ -32,6 +32,7 @@
 // The kernel is VALU-issue bound (not memory bound): its design minimises wave instructions per opened tile.
 // No per-lane pointer chasing, no divergence between "near" and "far" queries: the first-round regime
 // (centimetre misalignment) and the converged regime run the same code, the former just opens more leaves.
+#include "build_common.h"
 #include "nn_tile_common.h"
 
 namespace mvicp {
@@ -492,8 +493,6 @@ int build_wide(FrameDev& f, const double* spts) {
   GridDev& G = f.grid;
   const int n = f.n;
   const float finf = std::numeric_limits<float>::infinity();
-  auto down = [](double v) { float x = (float)v; if ((double)x > v) x = std::nextafterf(x, -std::numeric_limits<float>::infinity()); return x; };
-  auto up = [](double v) { float x = (float)v; if ((double)x < v) x = std::nextafterf(x, std::numeric_limits<float>::infinity()); return x; };
   std::vector<std::vector<float>> lv;  // per level: 6 x cnt SoA
   std::vector<int> cnts;
   int cnt = (n + LEAF - 1) / LEAF;
@@ -502,7 +501,7 @@ int build_wide(FrameDev& f, const double* spts) {
     for (int j = 0; j < cnt; ++j) {
       float lo[3] = {finf, finf, finf}, hi[3] = {-finf, -finf, -finf};
       for (int k = j * LEAF; k < std::min(n, (j + 1) * LEAF); ++k)
-        for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], down(spts[3 * (size_t)k + a])); hi[a] = std::max(hi[a], up(spts[3 * (size_t)k + a])); }
+        for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], f32_down(spts[3 * (size_t)k + a])); hi[a] = std::max(hi[a], f32_up(spts[3 * (size_t)k + a])); }
       for (int a = 0; a < 3; ++a) { b[(size_t)a * cnt + j] = lo[a]; b[(size_t)(3 + a) * cnt + j] = hi[a]; }
     }
     lv.push_back(b); cnts.push_back(cnt);

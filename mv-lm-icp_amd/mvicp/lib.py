@@ -16,8 +16,12 @@ SYMBOLS = [
     "mvicp_recompute_normals", "mvicp_set_graph", "mvicp_set_shard", "mvicp_edge_owner", "mvicp_comm_unique_id", "mvicp_comm_init", "mvicp_comm_nranks", "mvicp_comm_set_callback", "mvicp_correspond",
     "mvicp_get_correspondences", "mvicp_map_correspondences", "mvicp_map_correspondences_async", "mvicp_wait_correspondences", "mvicp_correspondence_epochs", "mvicp_set_correspondences", "mvicp_nn_query", "mvicp_linearize", "mvicp_optimize",
     "mvicp_lm_solve", "mvicp_set_option", "mvicp_nn_census", "mvicp_nn_census_ex", "mvicp_reset_history", "mvicp_profile_enable", "mvicp_profile_reset", "mvicp_profile_get", "mvicp_profile_get_ex", "mvicp_stream", "mvicp_sync",
-    "mvicp_closedform_point_to_point", "mvicp_closedform_point_to_plane",
+    "mvicp_closedform_point_to_point", "mvicp_closedform_point_to_plane", "mvicp_set_frame_device", "mvicp_get_structure",
 ]
+
+# names of mvicp_get_structure (include/mvicp.h)
+STRUCTURE_NAMES = ("spts", "sidx", "srec", "crec", "inv", "snor", "table", "oct", "wide", "mf_ops", "mf_blk", "bricks", "celltab",
+                   "h_order", "h_inv", "scalars")
 
 
 class MvicpError(RuntimeError):
@@ -86,6 +90,9 @@ def load_library(path=None):
     lib.mvicp_sync.argtypes = [vp]
     lib.mvicp_closedform_point_to_point.argtypes = [dp, dp, C.c_int, dp]
     lib.mvicp_closedform_point_to_plane.argtypes = [dp, dp, dp, C.c_int, dp]
+    lib.mvicp_set_frame_device.argtypes = [vp, C.c_int, vp, vp, C.c_int]
+    lib.mvicp_get_structure.argtypes = [vp, C.c_int, C.c_char_p, vp, C.c_longlong]
+    lib.mvicp_get_structure.restype = C.c_longlong
     if path is None:
         _lib = lib
     return lib
@@ -97,6 +104,27 @@ def _dp(a):
 
 def _ip(a):
     return a.ctypes.data_as(C.POINTER(C.c_int))
+
+
+def check_device_cloud(t, device, n=None, name="xyz"):
+    """The checks of a device cloud for Engine.set_frame_device, before any library call: a torch tensor, float64, shape (n, 3),
+    contiguous, on the GPU `device` (an index).  Raises TypeError / ValueError; returns the number of points."""
+    import torch
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch tensor, got {type(t).__name__}")
+    if t.dtype != torch.float64:
+        raise TypeError(f"{name} must be float64, got {t.dtype}")
+    if t.dim() != 2 or t.shape[1] != 3:
+        raise ValueError(f"{name} must have shape (n, 3), got {tuple(t.shape)}")
+    if n is not None and t.shape[0] != n:
+        raise ValueError(f"{name} has {t.shape[0]} rows, the cloud {n}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+    if not t.is_cuda:
+        raise TypeError(f"{name} must be a GPU (HIP) tensor, got device {t.device}")
+    if t.device.index != device:
+        raise ValueError(f"{name} is on cuda:{t.device.index}, the engine on cuda:{device}")
+    return int(t.shape[0])
 
 
 def _check(lib, st):
@@ -176,6 +204,7 @@ class Engine:
     def __init__(self, device=0, rank=0, world=1):
         self.lib = load_library()
         h = C.c_void_p()
+        self.device = device
         _check(self.lib, self.lib.mvicp_create(device, C.byref(h)))
         self.h = h
         self.n_frames = 0
@@ -212,6 +241,37 @@ class Engine:
         n = None if nor is None else np.ascontiguousarray(nor, dtype=np.float64)
         _check(self.lib, self.lib.mvicp_set_frame(self.h, frame, _dp(p), _dp(n) if n is not None else None, len(p)))
         self.npts[frame] = len(p)
+
+    def set_frame_device(self, frame, xyz, nor=None):
+        """Upload ONE cloud that is already on the GPU (torch tensors, n x 3 float64): mvicp_set_frame_device.  The structures are
+        built on the GPU; the tensors may be reused once this returns."""
+        n = check_device_cloud(xyz, self.device)
+        if nor is not None:
+            check_device_cloud(nor, self.device, n, "nor")
+        import torch
+        torch.cuda.current_stream(xyz.device).synchronize()   # the call's contract: the arrays are fully written
+        p = C.c_void_p(xyz.data_ptr()) if n else None
+        q = C.c_void_p(nor.data_ptr()) if nor is not None and n else None
+        _check(self.lib, self.lib.mvicp_set_frame_device(self.h, frame, p, q, n))
+        self.npts[frame] = n
+
+    def set_frames_device(self, xyz_list, nor_list=None):
+        for i, t in enumerate(xyz_list):   # (every tensor is checked before the frames are reset)
+            check_device_cloud(t, self.device)
+            if nor_list is not None and nor_list[i] is not None:
+                check_device_cloud(nor_list[i], self.device, int(t.shape[0]), "nor")
+        self.n_frames = len(xyz_list)
+        _check(self.lib, self.lib.mvicp_set_num_frames(self.h, self.n_frames))
+        self.npts = [0] * self.n_frames
+        for i, t in enumerate(xyz_list):
+            self.set_frame_device(i, t, None if nor_list is None else nor_list[i])
+
+    def get_structure(self, frame, name):
+        """One per-cloud structure array as bytes (np.uint8), "scalars" / "build_ms" as float64: mvicp_get_structure."""
+        nb = _check(self.lib, self.lib.mvicp_get_structure(self.h, frame, name.encode(), None, 0))
+        buf = np.zeros(nb, dtype=np.uint8)
+        _check(self.lib, self.lib.mvicp_get_structure(self.h, frame, name.encode(), buf.ctypes.data_as(C.c_void_p), nb))
+        return buf.view(np.float64) if name in ("scalars", "build_ms") else buf
 
     def recompute_normals(self, frame, k=10, want_knn=False):
         n = self.npts[frame]
