@@ -101,6 +101,39 @@ int mvicp_recompute_normals(mvicp_ctx* ctx, int frame, int k, double* nrm_out, i
  * 104-117).  Edge order is the reference's loop order: src ascending, then neighbour order. */
 int mvicp_set_graph(mvicp_ctx* ctx, int n_edges, const int* src, const int* dst);
 
+/* ---- overlap census and the pose graph made from it ----------------------------------------------------
+ * The reference offers one rule for the pose graph: the k frames whose camera centres are nearest (Frame::computePoseNeighboursKnn,
+ * frame.cpp:67-89; main_multiview.cpp:104-117).  mvicp_overlap measures instead how much surface two clouds share at the given poses,
+ * for ALL ordered frame pairs at once.  For i != j:
+ *   hits[i*K+j] = #{ p in S_i : sqrt(d2(p)) < (double)thresh }   -- the predicate of frame.cpp:156
+ *   sumq[i*K+j] = sum over those p of floor(d2(p) * 2^q_exp)      -- exact integers, order-independent
+ * d2(p) = squared distance, in the reference metric (frame.h:70-76, no fma), from the query R_j^-1 ((R_i p + t_i) - t_j) -- the SAME
+ * rounded operations as mvicp_correspond's query transform -- to the nearest point of cloud j.  hits[i*K+i] = samples[i], sumq[i*K+i] = 0.
+ * S_i: s_i = n_i if max_samples <= 0 or max_samples >= n_i, else max_samples; its t-th member is the point with ORIGINAL index
+ * floor(t * n_i / s_i) (64-bit), t = 0 .. s_i-1.  samples[i] = s_i.
+ * q_exp: the integer with 2^30 <= B2 * 2^q_exp < 2^31, B2 = the smallest double whose correctly rounded sqrt is >= thresh
+ * (sqrt(d2) < thresh <=> d2 < B2), so every term is < 2^31 and exact.  A frame with n_i = 0 has samples[i] = 0 and zero hits in its row
+ * and its column.
+ *   poses : n_frames x 16;  samples: K ints;  hits: K*K ints;  sumq: K*K long long (may be NULL);  q_exp: one int (may be NULL).
+ * Needs every frame uploaded (mvicp_set_frame / mvicp_set_frame_device; waits for pending structure builds and reports a failed one like
+ * mvicp_nn_query) and NO graph: it may be called before or after mvicp_set_graph and between rounds, and it is HISTORY-NEUTRAL — it reads
+ * clouds and structures only and leaves the temporal cache, seeds, lists, epochs, medians, the AUTO state and any queued evaluation
+ * alone, so a registration with census calls in between is bit-identical to one without.  With several ranks every rank computes the
+ * whole census locally (the clouds are replicated): identical arrays, no communication.
+ * Errors: thresh not finite or <= 0, a non-finite pose entry, NULL poses / samples / hits -> MVICP_ERR_ARG; mvicp_set_num_frames not
+ * called or a frame never uploaded -> MVICP_ERR_STATE. */
+int mvicp_overlap(mvicp_ctx* ctx, const double* poses, float thresh, int max_samples, int* samples, int* hits, long long* sumq, int* q_exp);
+
+/* The graph rule on top of the census (pure host function, no context).  Frame i keeps the knn frames j != i with the most hits, among
+ * those with hits[i*K+j] > 0 and hits[i*K+j] >= min_fraction * samples[i]; equal hits: the smaller sumq first (within one row that is
+ * the smaller mean distance: an exact integer comparison, no division), then the lower j.  sumq NULL: hits, then lower j.  Edges are
+ * written src ascending, neighbours best first (the reference's order, main_multiview.cpp:104-117); skip_frame0 != 0 omits the edges
+ * OUT OF frame 0 (never searched: frame.cpp:93).  *n_components (may be NULL) = connected components of the undirected graph over all
+ * K frames, edges out of frame 0 included whether or not they are written.  A graph with more than one component is reported, not
+ * repaired.  RETURNS THE NUMBER OF EDGES (>= 0); more than cap is MVICP_ERR_ARG. */
+int mvicp_graph_from_overlap(int n_frames, const int* samples, const int* hits, const long long* sumq, int knn, double min_fraction,
+                             int skip_frame0, int cap, int* src, int* dst, int* n_components);
+
 /* Multi-GPU: this rank owns a contiguous chunk of the edge list (balanced by N_src).  Call before
  * mvicp_set_graph.  Default rank 0 of 1. */
 int mvicp_set_shard(mvicp_ctx* ctx, int rank, int world);

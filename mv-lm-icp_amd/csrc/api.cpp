@@ -197,6 +197,16 @@ void inverse3(const double* m, double* r) {
 #undef M
 }
 
+// The query transform of a directed pair src -> dst (frame.cpp:117-118,131,136), the first 24 doubles of an edge's kEdgeXf:
+// Rs(9) ts(3) Rd^-1(9) td(3), column-major.  mvicp_correspond and mvicp_overlap both build theirs here.
+void fill_query_xf(const double* Ps, const double* Pd, double* x) {
+  double Rd[9];
+  for (int j = 0; j < 3; ++j)
+    for (int i = 0; i < 3; ++i) { x[i + 3 * j] = Ps[i + 4 * j]; Rd[i + 3 * j] = Pd[i + 4 * j]; }
+  for (int i = 0; i < 3; ++i) { x[9 + i] = Ps[12 + i]; x[21 + i] = Pd[12 + i]; }
+  inverse3(Rd, x + 12);
+}
+
 int ensure_pin(mvicp_ctx* c, size_t doubles) {
   if (doubles <= c->h_pin_doubles) return MVICP_OK;
   if (c->h_pin) MV_HIP(hipHostFree(c->h_pin));
@@ -472,6 +482,7 @@ int mvicp_destroy(mvicp_ctx* c) try {
   free_graph(c);
   for (FrameDev& f : c->frames) { dev_free(f.pts); dev_free(f.nor); free_grid(f.grid); free_tie(f); }
   dev_free(c->d_split_idx); dev_free(c->d_split_d2); dev_free(c->d_scratch);
+  free_overlap(c);
   for (auto& kv : c->tables) if (kv.second.d) (void)hipFree(kv.second.d);
   if (c->d_census) (void)hipFree(c->d_census);
   if (c->h_census) (void)hipHostFree(c->h_census);
@@ -736,6 +747,68 @@ int mvicp_edge_owner(int n_edges, const int* n_src, int world, int* owner) try {
   return MVICP_OK;
 } MVICP_GUARD_ABI
 
+int mvicp_overlap(mvicp_ctx* c, const double* poses, float thresh, int max_samples, int* samples, int* hits, long long* sumq, int* q_exp) try {
+  MV_CHECK(bind(c));
+  if (!poses || !samples || !hits) { set_error("poses / samples / hits is null"); return MVICP_ERR_ARG; }
+  if (!std::isfinite(thresh) || !(thresh > 0.f)) { set_error("thresh must be finite and > 0"); return MVICP_ERR_ARG; }
+  const int K = c->n_frames;
+  if (K <= 0) { set_error("no frames: call mvicp_set_num_frames first"); return MVICP_ERR_STATE; }
+  for (size_t k = 0; k < 16 * (size_t)K; ++k)
+    if (!std::isfinite(poses[k])) { set_error("non-finite pose entry (frame %d)", (int)(k / 16)); return MVICP_ERR_ARG; }
+  for (int i = 0; i < K; ++i)
+    if (!c->frames[i].pts) { set_error("frame %d was never uploaded", i); return MVICP_ERR_STATE; }
+  MV_CHECK(finish_builds(c));
+  // sqrt(d2) < thresh <=> d2 < B2; every term floor(d2 * 2^q) of sumq is then below B2 * 2^q < 2^31
+  const double B2 = sqrt_bound((double)thresh);
+  int ex = 0;
+  (void)std::frexp(B2, &ex);   // B2 = m 2^ex, m in [0.5, 1)
+  const int q = 31 - ex;
+  if (q_exp) *q_exp = q;
+  std::vector<double> xf(24 * (size_t)K * K, 0.0);
+  for (int i = 0; i < K; ++i)
+    for (int j = 0; j < K; ++j)
+      if (i != j) fill_query_xf(poses + 16 * (size_t)i, poses + 16 * (size_t)j, &xf[24 * ((size_t)i * K + j)]);
+  return overlap_census(c, xf.data(), B2, std::ldexp(1.0, q), max_samples, samples, hits, sumq);
+} MVICP_GUARD_ABI
+
+int mvicp_graph_from_overlap(int n_frames, const int* samples, const int* hits, const long long* sumq, int knn, double min_fraction,
+                             int skip_frame0, int cap, int* src, int* dst, int* n_components) try {
+  const int K = n_frames;
+  if (K < 0 || knn < 0 || cap < 0 || (K > 0 && (!samples || !hits)) || !(min_fraction == min_fraction)) { set_error("bad arguments"); return MVICP_ERR_ARG; }
+  std::vector<int> parent((size_t)K);
+  for (int i = 0; i < K; ++i) parent[i] = i;
+  auto root = [&](int a) { while (parent[a] != a) { parent[a] = parent[parent[a]]; a = parent[a]; } return a; };
+  int n_edges = 0;
+  std::vector<int> cand;
+  for (int i = 0; i < K; ++i) {
+    cand.clear();
+    const int* h = hits + (size_t)i * K;
+    const long long* sq = sumq ? sumq + (size_t)i * K : nullptr;
+    for (int j = 0; j < K; ++j)
+      if (j != i && h[j] > 0 && (double)h[j] >= min_fraction * (double)samples[i]) cand.push_back(j);
+    // most hits first; equal hits: the smaller sumq (the smaller mean: an exact integer comparison), then the lower j
+    std::sort(cand.begin(), cand.end(), [&](int a, int b) {
+      if (h[a] != h[b]) return h[a] > h[b];
+      if (sq && sq[a] != sq[b]) return sq[a] < sq[b];
+      return a < b;
+    });
+    const int take = std::min<int>(knn, (int)cand.size());
+    for (int k = 0; k < take; ++k) {
+      parent[root(i)] = root(cand[k]);
+      if (i == 0 && skip_frame0) continue;
+      if (n_edges >= cap) { set_error("more than cap = %d edges (frame %d of %d, knn = %d)", cap, i, K, knn); return MVICP_ERR_ARG; }
+      if (!src || !dst) { set_error("src / dst is null"); return MVICP_ERR_ARG; }
+      src[n_edges] = i; dst[n_edges] = cand[k]; ++n_edges;
+    }
+  }
+  if (n_components) {
+    int comps = 0;
+    for (int i = 0; i < K; ++i) comps += root(i) == i ? 1 : 0;
+    *n_components = comps;
+  }
+  return n_edges;
+} MVICP_GUARD_ABI
+
 int mvicp_set_graph(mvicp_ctx* c, int n_edges, const int* src, const int* dst) try {
   MV_CHECK(bind(c));
   if (n_edges < 0 || (n_edges > 0 && (!src || !dst))) { set_error("bad edge list"); return MVICP_ERR_ARG; }
@@ -987,11 +1060,7 @@ static int correspond_once(mvicp_ctx* c, const double* poses, const unsigned cha
     const double* Ps = poses + 16 * (size_t)c->esrc[e];
     const double* Pd = poses + 16 * (size_t)c->edst[e];
     double* x = hx + (size_t)e * kEdgeXf;
-    double Rd[9];
-    for (int j = 0; j < 3; ++j)
-      for (int i = 0; i < 3; ++i) { x[i + 3 * j] = Ps[i + 4 * j]; Rd[i + 3 * j] = Pd[i + 4 * j]; }
-    for (int i = 0; i < 3; ++i) { x[9 + i] = Ps[12 + i]; x[21 + i] = Pd[12 + i]; }
-    inverse3(Rd, x + 12);
+    fill_query_xf(Ps, Pd, x);
     // temporal cache: q = M p + v with M = Rd^-1 Rs, v = Rd^-1 (ts - td).  Between two searches every query of the edge
     // moves by at most ||dM||_F max|p| + |dv|  (+ a rounding allowance far above the 1e-16-relative error of the fp64 map).
     double Mq[12];

@@ -74,6 +74,9 @@ struct GridDev {
   // cell table row = 64 x {start, count} of the cell runs in the sorted array.  Null when the grid is too large for a dense map.
   void* bricks = nullptr; void* celltab = nullptr; int bdims[3] = {0, 0, 0};
   size_t celltab_bytes = 0;    // bytes of the cell table in use
+  // overlap census (overlap.hip): the sorted positions of the cloud's `ov_samp_s` sample points, ascending; built on first use for
+  // a given max_samples and kept until it changes (null: none yet, or every point is a sample)
+  int* ov_samp = nullptr; int ov_samp_s = 0;
 };
 
 struct PointRec { double x, y, z; long long idx; };  // 32-B aligned sorted point + original index
@@ -227,6 +230,10 @@ struct mvicp_ctx {
   // brute-force split scratch
   int* d_split_idx = nullptr; double* d_split_d2 = nullptr; size_t split_cap = 0;
 
+  // overlap census (overlap.hip): buffers of its own — [jobs | item offsets | hits | sumq] on the device and the same in pinned host
+  // memory — so that mvicp_overlap touches nothing a search, a queued evaluation or the shared control block uses
+  char* ov_dev = nullptr; char* ov_pin = nullptr; size_t ov_bytes = 0;
+
   // cached small tables
   struct CachedTable { std::vector<char> bytes; void* d = nullptr; size_t cap = 0; };
   std::map<std::string, CachedTable> tables;
@@ -326,6 +333,10 @@ int build_grid_device(mvicp_ctx* c, FrameDev& f, const DevBounds& b, int grid_cu
 int finish_builds(mvicp_ctx* c);   // api.cpp: wait for every pending structure build of this context; first failure wins
 void free_grid(GridDev& g);
 void free_tie(FrameDev& f);                                                            // nn_tie.hip
+// overlap.hip: census of all ordered pairs.  xf: K x K x 24 query transforms (pair i -> j at [i * K + j]); B2 = squared cutoff bound,
+// scale = 2^q_exp; samples K, hits K x K, sumq K x K or null (host arrays).  Waits for the stream; history-neutral.
+int overlap_census(mvicp_ctx* c, const double* xf, double B2, double scale, int max_samples, int* samples, int* hits, long long* sumq);
+void free_overlap(mvicp_ctx* c);
 int launch_compact(mvicp_ctx* c, double d2_bound);                                    // corr.hip
 int launch_gather_stream(mvicp_ctx* c);
 int launch_select_median(mvicp_ctx* c);

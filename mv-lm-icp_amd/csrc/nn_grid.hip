@@ -39,6 +39,7 @@
 #include "build_common.h"
 #include "common.h"
 #include "nn_list.h"
+#include "nn_metric.h"
 #include "nn_tie.h"
 
 namespace mvicp {
@@ -75,23 +76,6 @@ struct GridJob {
   int seed;            // out_idx still holds last round's neighbours (from any kernel): a starting candidate for far queries
   TieRef tie;          // where queries whose best distance was met by more than one target are reported (nn_tie.h)
 };
-
-__device__ __forceinline__ void xf_point(const double* __restrict__ x, double p0, double p1, double p2, double& q0, double& q1, double& q2) {
-  double g[3], u[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-    g[i] = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(x[i], p0), __dmul_rn(x[i + 3], p1)), __dmul_rn(x[i + 6], p2)), x[9 + i]);
-#pragma unroll
-  for (int i = 0; i < 3; ++i) u[i] = __dsub_rn(g[i], x[21 + i]);
-  q0 = __dadd_rn(__dadd_rn(__dmul_rn(x[12 + 0], u[0]), __dmul_rn(x[12 + 3], u[1])), __dmul_rn(x[12 + 6], u[2]));
-  q1 = __dadd_rn(__dadd_rn(__dmul_rn(x[12 + 1], u[0]), __dmul_rn(x[12 + 4], u[1])), __dmul_rn(x[12 + 7], u[2]));
-  q2 = __dadd_rn(__dadd_rn(__dmul_rn(x[12 + 2], u[0]), __dmul_rn(x[12 + 5], u[1])), __dmul_rn(x[12 + 8], u[2]));
-}
-
-__device__ __forceinline__ double dist2(double qx, double qy, double qz, double x, double y, double z) {
-  const double d0 = __dsub_rn(qx, x), d1 = __dsub_rn(qy, y), d2 = __dsub_rn(qz, z);
-  return __dadd_rn(__dadd_rn(__dmul_rn(d0, d0), __dmul_rn(d1, d1)), __dmul_rn(d2, d2));
-}
 
 // sum over the ACTIVE lanes of the wave (lanes may have exited early)
 __device__ __forceinline__ unsigned long long __reduce_add_u64(unsigned long long v) {
@@ -647,16 +631,6 @@ __global__ __launch_bounds__(NT, 5) void nn_cell_kernel(const GridJob* __restric
 // points at a time with an octet arg-min.  Compared with one lane per query this divides the number of dependent
 // memory round trips per query by ~3 (8-ary instead of binary), keeps the loads of an octet contiguous, and only the 8
 // octets of a wave can diverge from each other.  Persistent grid-stride launch: the far count lives on the device.
-constexpr int OCT_STACK = 56;  // >= 7 * max depth + 1 (build_grid keeps the depth <= 7)
-
-__device__ __forceinline__ double oct_box_lb(double qx, double qy, double qz, const float4 a, const float4 b) {
-  // box = {lo.xyz = a.xyz, hi.xyz = (a.w, b.x, b.y)}
-  const double g0 = fmax(fmax(__dsub_rn((double)a.x, qx), __dsub_rn(qx, (double)a.w)), 0.0);
-  const double g1 = fmax(fmax(__dsub_rn((double)a.y, qy), __dsub_rn(qy, (double)b.x)), 0.0);
-  const double g2 = fmax(fmax(__dsub_rn((double)a.z, qz), __dsub_rn(qz, (double)b.y)), 0.0);
-  return __dadd_rn(__dadd_rn(__dmul_rn(g0, g0), __dmul_rn(g1, g1)), __dmul_rn(g2, g2));
-}
-
 __global__ __launch_bounds__(NT) void nn_far_kernel(const GridJob* __restrict__ jobs, const int2* __restrict__ far_list, double bound,
                                                     const unsigned int* __restrict__ far_count, unsigned int* __restrict__ next_far_count,
                                                     unsigned long long* __restrict__ stats, size_t stats_slots, unsigned int* __restrict__ seen) {
@@ -1002,6 +976,7 @@ void free_grid(GridDev& g) {
   if (g.oct) (void)hipFree(g.oct);
   if (g.bricks) (void)hipFree(g.bricks);
   if (g.celltab) (void)hipFree(g.celltab);
+  if (g.ov_samp) (void)hipFree(g.ov_samp);
   g = GridDev();
 }
 

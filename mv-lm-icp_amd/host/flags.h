@@ -1,5 +1,7 @@
 // Tiny gflags-compatible command line parser for the headless drivers (gflags is not installed): --name=value,
 // --name value, --name / --noname for booleans; same flag names and defaults as the reference's DEFINE_* lines.
+// Flags the reference does not have (--rounds, --trace, --graph overlap with --overlap_cutoff / --overlap_samples / --overlap_min ...)
+// are listed at the top of each driver.
 #pragma once
 #include <cstdlib>
 #include <iostream>

@@ -29,6 +29,7 @@ void Session::reset() {
   frames_key = nullptr;
   frame_keys.clear();
   last_poses.clear();
+  graph_bound = false;
 }
 
 void Session::invalidate() {
@@ -44,17 +45,16 @@ int Session::frame_index(const Frame* f) const {
   return -1;
 }
 
-void Session::bind(std::vector<std::shared_ptr<Frame>>& frames) {
-  // graph in the reference's loop order: src ascending, neighbour order (main_multiview.cpp:119-127)
-  std::vector<int> s, d;
-  for (size_t i = 0; i < frames.size(); ++i)
-    for (const OutgoingEdge& e : frames[i]->neighbours) { s.push_back((int)i); d.push_back(e.neighbourIdx); }
-  std::vector<FrameKey> keys(frames.size());
+static std::vector<Session::FrameKey> frame_keys_of(const std::vector<std::shared_ptr<Frame>>& frames) {
+  std::vector<Session::FrameKey> keys(frames.size());
   for (size_t i = 0; i < frames.size(); ++i) {
     const Frame& f = *frames[i];
-    keys[i] = FrameKey{&f, f.pts.empty() ? nullptr : (const void*)f.pts[0].data(), f.pts.size(), f.nor.empty() ? nullptr : (const void*)f.nor[0].data(), f.version};
+    keys[i] = Session::FrameKey{&f, f.pts.empty() ? nullptr : (const void*)f.pts[0].data(), f.pts.size(), f.nor.empty() ? nullptr : (const void*)f.nor[0].data(), f.version};
   }
-  if (ctx && frames_key == (const void*)&frames && s == esrc && d == edst && keys == frame_keys) return;
+  return keys;
+}
+
+void Session::upload(std::vector<std::shared_ptr<Frame>>& frames) {
   if (!ctx) check(mvicp_create(device, &ctx));
   check(mvicp_set_num_frames(ctx, (int)frames.size()));
   for (size_t i = 0; i < frames.size(); ++i) {
@@ -62,13 +62,51 @@ void Session::bind(std::vector<std::shared_ptr<Frame>>& frames) {
     const double* nrm = f.nor.size() == f.pts.size() && !f.nor.empty() ? f.nor[0].data() : nullptr;
     check(mvicp_set_frame(ctx, (int)i, f.pts.empty() ? nullptr : f.pts[0].data(), nrm, (int)f.pts.size()));
   }
+}
+
+void Session::bind(std::vector<std::shared_ptr<Frame>>& frames) {
+  // graph in the reference's loop order: src ascending, neighbour order (main_multiview.cpp:119-127)
+  std::vector<int> s, d;
+  for (size_t i = 0; i < frames.size(); ++i)
+    for (const OutgoingEdge& e : frames[i]->neighbours) { s.push_back((int)i); d.push_back(e.neighbourIdx); }
+  const std::vector<FrameKey> keys = frame_keys_of(frames);
+  const bool same_frames = ctx && frames_key == (const void*)&frames && keys == frame_keys;
+  if (same_frames && graph_bound && s == esrc && d == edst) return;
+  if (!(same_frames && !graph_bound)) upload(frames);   // (clouds that computeOverlapNeighbours has just uploaded are not uploaded again)
   check(mvicp_set_graph(ctx, (int)s.size(), s.data(), d.data()));
   esrc = s; edst = d;
+  graph_bound = true;
   frames_key = (const void*)&frames;
   frame_keys = keys;
   last_poses.clear();
   held.assign(esrc.size(), Held());
   epochs = nullptr;
+}
+
+int Session::computeOverlapNeighbours(std::vector<std::shared_ptr<Frame>>& frames, int knn, float thresh, int max_samples, double min_fraction) {
+  const int K = (int)frames.size();
+  const std::vector<FrameKey> keys = frame_keys_of(frames);
+  if (!(ctx && frames_key == (const void*)&frames && keys == frame_keys)) {
+    upload(frames);
+    frames_key = (const void*)&frames; frame_keys = keys;
+    graph_bound = false; esrc.clear(); edst.clear();
+    last_poses.clear(); held.clear(); epochs = nullptr; corr = nullptr; corr_off = nullptr;
+  }
+  std::vector<double> P(16 * (size_t)K);
+  for (int i = 0; i < K; ++i) std::memcpy(&P[16 * (size_t)i], frames[i]->pose.data(), 128);
+  std::vector<int> samples(K), hits((size_t)K * K), src((size_t)K * K), dst((size_t)K * K);
+  std::vector<long long> sumq((size_t)K * K);
+  check(mvicp_overlap(ctx, P.data(), thresh, max_samples, samples.data(), hits.data(), sumq.data(), nullptr));
+  int comps = 0;
+  const int E = mvicp_graph_from_overlap(K, samples.data(), hits.data(), sumq.data(), knn, min_fraction, 0, K * K, src.data(), dst.data(), &comps);
+  check(E);
+  for (auto& f : frames) f->neighbours.clear();
+  for (int e = 0; e < E; ++e) {
+    const int i = src[e], j = dst[e];
+    const float fraction = (float)((double)hits[(size_t)i * K + j] / (double)samples[i]);
+    frames[i]->neighbours.push_back(OutgoingEdge{j, 1.f - fraction, {}});   // "smaller is nearer" holds until the first search overwrites it
+  }
+  return comps;
 }
 
 void Session::correspond(std::vector<std::shared_ptr<Frame>>& frames, float thresh) {

@@ -97,7 +97,14 @@ struct Session {
   void invalidate();                       // forget the device copy (forces re-upload + fresh search); for in-place edits of pts/nor data
   std::vector<int> counts;
   std::vector<float> weights;
+  bool graph_bound = false;                                   // the context holds the graph of esrc / edst (false: clouds only)
+  void upload(std::vector<std::shared_ptr<Frame>>& frames);    // the clouds alone (no graph)
   void bind(std::vector<std::shared_ptr<Frame>>& frames);      // upload + graph (idempotent)
+  // Pose graph from the overlap census (mvicp_overlap + mvicp_graph_from_overlap) in place of the computePoseNeighboursKnn loop
+  // (main_multiview.cpp:104-117): fills EVERY Frame::neighbours with the frame's knn best-overlapping frames at the current poses
+  // (weight = 1 - fraction of the frame's samples with a counterpart within thresh) and returns the number of connected components.
+  // More than one component is reported, not repaired: frames cut off from frame 0 make the solve singular.
+  int computeOverlapNeighbours(std::vector<std::shared_ptr<Frame>>& frames, int knn, float thresh, int max_samples = 4096, double min_fraction = 0.0);
   void correspond(std::vector<std::shared_ptr<Frame>>& frames, float thresh);
   void optimize(std::vector<std::shared_ptr<Frame>>& frames, int param, bool pointToPlane, bool robust, mvicp_summary* sm = nullptr);
   void reset();

@@ -13,6 +13,10 @@
 // frame K's translation moves by 1e-4 m), --copy_stats (one line `copyback: round r copied X skipped Y` per round): the copy-back bookkeeping of
 // host/frame.h under test; --dump_corr also writes the poses of the last search (search_pose_<i>.txt); --dump_knn FILE [--knn_k 10]: Frame::getNeighbours
 // (frame.cpp:208-231) of EVERY point of frame 0, asked one by one like frame.cpp:249, as raw doubles (n x k x 3), then exit.
+// --graph pose|overlap (default pose = computePoseNeighboursKnn, :104-117): overlap builds the pose graph from the overlap census of the
+// initial poses instead (Session::computeOverlapNeighbours: every frame keeps the --knn frames it shares most surface with) and prints one
+// more line, `overlap graph: C component(s)`; --overlap_cutoff X (default --cutoff), --overlap_samples N (4096; 0 = every point),
+// --overlap_min F (0: smallest share of a frame's samples that makes a candidate).
 #include <chrono>
 #include <cstring>
 #include <fstream>
@@ -75,7 +79,14 @@ int main(int argc, char** argv) {
     return 0;
   }
   frames[0]->fixed = true;
-  for (int i = 0; i < (int)frames.size(); ++i) frames[i]->computePoseNeighboursKnn(&frames, i, knn);
+  const bool overlap_graph = F.s("graph", "pose") == "overlap";
+  int components = 0;
+  try {
+    if (overlap_graph)
+      components = Session::get().computeOverlapNeighbours(frames, knn, (float)F.f("overlap_cutoff", cutoff), F.i("overlap_samples", 4096), F.f("overlap_min", 0.0));
+    else
+      for (int i = 0; i < (int)frames.size(); ++i) frames[i]->computePoseNeighboursKnn(&frames, i, knn);
+  } catch (const std::exception& ex) { std::cerr << ex.what() << std::endl; return 2; }
   if (!quiet) {
     std::cout << "graph adjacency matrix == block structure" << std::endl;
     for (size_t i = 0; i < frames.size(); ++i) {
@@ -84,6 +95,7 @@ int main(int argc, char** argv) {
       for (int v : row) std::cout << v << " ";
       std::cout << std::endl;
     }
+    if (overlap_graph) std::cout << "overlap graph: " << components << " component(s)" << std::endl;
   }
   double wall_search = 0.0, wall_solve = 0.0;
   std::ofstream trace;

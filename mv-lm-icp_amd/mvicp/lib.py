@@ -17,6 +17,7 @@ SYMBOLS = [
     "mvicp_get_correspondences", "mvicp_map_correspondences", "mvicp_map_correspondences_async", "mvicp_wait_correspondences", "mvicp_correspondence_epochs", "mvicp_set_correspondences", "mvicp_nn_query", "mvicp_linearize", "mvicp_optimize",
     "mvicp_lm_solve", "mvicp_set_option", "mvicp_nn_census", "mvicp_nn_census_ex", "mvicp_reset_history", "mvicp_profile_enable", "mvicp_profile_reset", "mvicp_profile_get", "mvicp_profile_get_ex", "mvicp_stream", "mvicp_sync",
     "mvicp_closedform_point_to_point", "mvicp_closedform_point_to_plane", "mvicp_set_frame_device", "mvicp_get_structure",
+    "mvicp_overlap", "mvicp_graph_from_overlap",
 ]
 
 # names of mvicp_get_structure (include/mvicp.h)
@@ -93,6 +94,9 @@ def load_library(path=None):
     lib.mvicp_set_frame_device.argtypes = [vp, C.c_int, vp, vp, C.c_int]
     lib.mvicp_get_structure.argtypes = [vp, C.c_int, C.c_char_p, vp, C.c_longlong]
     lib.mvicp_get_structure.restype = C.c_longlong
+    llp = C.POINTER(C.c_longlong)
+    lib.mvicp_overlap.argtypes = [vp, dp, C.c_float, C.c_int, ip, ip, llp, ip]
+    lib.mvicp_graph_from_overlap.argtypes = [C.c_int, ip, ip, llp, C.c_int, C.c_double, C.c_int, C.c_int, ip, ip, ip]
     if path is None:
         _lib = lib
     return lib
@@ -149,6 +153,34 @@ def edge_owner(n_src, world):
     owner = np.zeros(len(n_src), dtype=np.int32)
     _check(lib, lib.mvicp_edge_owner(len(n_src), _ip(n_src), world, _ip(owner)))
     return owner
+
+
+def overlap_sample_indices(n, max_samples):
+    """The sample rule of mvicp_overlap: ORIGINAL indices of the s sample points of a cloud of n points, s = n if max_samples <= 0 or
+    max_samples >= n else max_samples; the t-th is floor(t * n / s) in 64-bit integers."""
+    n = int(n)
+    s = n if max_samples <= 0 or max_samples >= n else int(max_samples)
+    if s == 0:
+        return np.zeros(0, dtype=np.int64)
+    return (np.arange(s, dtype=np.int64) * n) // s
+
+
+def graph_from_overlap(samples, hits, sumq=None, knn=2, min_fraction=0.0, skip_fixed0=True, cap=None):
+    """mvicp_graph_from_overlap: frame i keeps the knn frames with the most hits (ties: smaller sumq, then lower index) among those with
+    hits > 0 and hits >= min_fraction * samples[i].  -> (src, dst, n_components); edges src ascending, neighbours best first;
+    skip_fixed0 omits the edges out of frame 0.  cap (default K * min(knn, K - 1)): capacity of the edge arrays; more edges raise."""
+    lib = load_library()
+    samples = np.ascontiguousarray(samples, dtype=np.int32)
+    K = len(samples)
+    hits = np.ascontiguousarray(hits, dtype=np.int32).reshape(K, K)
+    sq = None if sumq is None else np.ascontiguousarray(sumq, dtype=np.int64).reshape(K, K)
+    if cap is None:
+        cap = K * max(min(int(knn), K - 1), 0)
+    src = np.zeros(max(cap, 1), dtype=np.int32); dst = np.zeros(max(cap, 1), dtype=np.int32)
+    nc = C.c_int(0)
+    n = _check(lib, lib.mvicp_graph_from_overlap(K, _ip(samples), _ip(hits), sq.ctypes.data_as(C.POINTER(C.c_longlong)) if sq is not None else None,
+                                                 int(knn), float(min_fraction), int(bool(skip_fixed0)), int(cap), _ip(src), _ip(dst), C.byref(nc)))
+    return src[:n].copy(), dst[:n].copy(), int(nc.value)
 
 
 def closedform_point_to_point(src, dst):
@@ -406,6 +438,19 @@ class Engine:
         first = np.ascontiguousarray(first, dtype=np.int32)
         second = np.ascontiguousarray(second, dtype=np.int32)
         _check(self.lib, self.lib.mvicp_set_correspondences(self.h, edge, len(first), _ip(first), _ip(second), np.float32(weight)))
+
+    def overlap(self, poses, thresh, max_samples=4096):
+        """mvicp_overlap: census of ALL ordered frame pairs at `poses` -> dict(samples (K), hits (K,K), sumq (K,K) int64, q_exp,
+        fraction = hits / samples[:, None], mean_d2 = sumq / max(hits, 1) * 2^-q_exp).  Needs no graph; history-neutral."""
+        P = poses_to_c(poses)
+        K = len(P)
+        samples = np.zeros(K, dtype=np.int32); hits = np.zeros((K, K), dtype=np.int32); sumq = np.zeros((K, K), dtype=np.int64)
+        q = C.c_int(0)
+        _check(self.lib, self.lib.mvicp_overlap(self.h, _dp(P), np.float32(thresh), int(max_samples), _ip(samples), _ip(hits),
+                                                sumq.ctypes.data_as(C.POINTER(C.c_longlong)), C.byref(q)))
+        fraction = hits / np.maximum(samples, 1)[:, None].astype(np.float64)
+        mean_d2 = np.ldexp(sumq / np.maximum(hits, 1).astype(np.float64), -q.value)
+        return {"samples": samples, "hits": hits, "sumq": sumq, "q_exp": int(q.value), "fraction": fraction, "mean_d2": mean_d2}
 
     def nn_query(self, frame, queries, nn_method=NN_AUTO):
         q = np.ascontiguousarray(queries, dtype=np.float64)
