@@ -210,6 +210,11 @@ int mvicp_nn_query(mvicp_ctx* ctx, int frame, const double* queries, int n, int 
  * (icp-ceres.cpp:284,374,449).  out: n_edges x 91 = [78 upper-triangular row-major H | 12 g | cost]. */
 #define MVICP_EDGE_BLOCK 91
 int mvicp_linearize(mvicp_ctx* ctx, const double* poses, int point_to_plane, int robust, double* out);
+/* Two evaluations on the SAME correspondences and scales: out_a = what mvicp_linearize gives at poses_a, out_b = what it gives at poses_b,
+ * bit for bit.  On a single rank both come from one kernel that reads the operand stream once (the kernel is bandwidth-bound, so the pair
+ * costs little more than one evaluation); with an exchange configured (N > 1 ranks) it is two ordinary evaluations.  The single-rank path does
+ * not touch the evaluations mvicp_correspond queued ahead, nor their buffers.  Profile scope: "linearize_pair". */
+int mvicp_linearize_pair(mvicp_ctx* ctx, const double* poses_a, const double* poses_b, int point_to_plane, int robust, double* out_a, double* out_b);
 
 /* ---- S2: the LM solve ----------------------------------------------------------------------------
  * Replaces ICP_Ceres::ceresOptimizer / _ceresAngleAxis / _sophusSE3 (frames, pointToPlane, robust)
@@ -270,7 +275,8 @@ int mvicp_closedform_point_to_plane(const double* src, const double* dst, const 
  * once it has settled; "spec_eval" (0/1, default 1): mvicp_correspond queues the first linearization of the following
  * mvicp_optimize (same poses, previous solve's flags) behind its own kernels so the round waits once, not twice; "spec2_eval" (0/1, default 1; single rank): when a
  * search's poses are bit-identical to the last search's (a converged registration), the candidate evaluation of the last solve is queued as well — the fixed-point
- * round's solve then needs no further device launch and no second wait (used only if the solve asks for exactly those poses); "lin_share_p"
+ * round's solve then needs no further device launch and no second wait (used only if the solve asks for exactly those poses); "lin_pair" (0/1, default 1): those
+ * two queued evaluations go as ONE paired launch that reads the operand stream once (see mvicp_linearize_pair; 0: two launches with a copy between them); "lin_share_p"
  * (0/1, default 1): the linearization reads the source points of an all-accepted edge from the shared sorted cloud; "lin_interleave" (0/1, default 1; read at
  * mvicp_set_graph): the linearization's workgroups of the edges that share a source cloud are launched interleaved in groups of 8, so that the second reader of a
  * piece of the cloud runs on the XCD whose L2 still holds it; "nn_cell"
@@ -299,7 +305,7 @@ int mvicp_nn_census(mvicp_ctx* ctx, double* out5);              /* the first fiv
 int mvicp_nn_census_ex(mvicp_ctx* ctx, double* out, int cap);
 
 /* ---- profiling (HIP events on the library's own stream) ------------------------------------------ */
-/* on = 0: off; 1: every scope below; 2: only the NN kernels, "linearize" and "comm" (fewer event packets between the kernels of
+/* on = 0: off; 1: every scope below; 2: only the NN kernels, "linearize", "linearize_pair" and "comm" (fewer event packets between the kernels of
  * a timed run). */
 int mvicp_profile_enable(mvicp_ctx* ctx, int on);
 int mvicp_profile_reset(mvicp_ctx* ctx);

@@ -83,7 +83,7 @@ int scratch_upload(mvicp_ctx* c, const void* src, size_t bytes, void** dptr) {
 
 ProfScope::ProfScope(mvicp_ctx* ctx, const char* nm, double bytes) : c(ctx), name(nm), on(ctx->profile) {
   // level 2: only the two roofline scopes (every event pair is two extra queue packets between kernels)
-  if (on && ctx->profile_level >= 2 && ((std::strncmp(nm, "nn_", 3) != 0 && std::strcmp(nm, "linearize") != 0 && std::strcmp(nm, "comm") != 0) ||
+  if (on && ctx->profile_level >= 2 && ((std::strncmp(nm, "nn_", 3) != 0 && std::strncmp(nm, "linearize", 9) != 0 && std::strcmp(nm, "comm") != 0) ||
                                         std::strcmp(nm, "nn_tie") == 0)) on = false;   // (the tie fix-up is a few microseconds per moving round: not worth two packets)
   if (!on) return;
   ProfEntry& pe = c->prof[name];
@@ -151,7 +151,7 @@ template <typename T> void dev_free(T*& p) {
 
 void free_graph(mvicp_ctx* c) {
   dev_free(c->d_esrc); dev_free(c->d_edst); dev_free(c->d_cap_off); dev_free(c->d_count);
-  dev_free(c->d_ctl); c->d_nsrc = nullptr; c->d_a = nullptr; c->d_xf = nullptr; c->d_rel = nullptr; c->d_dirty = nullptr;
+  dev_free(c->d_ctl); c->d_nsrc = nullptr; c->d_a = nullptr; c->d_xf = nullptr; c->d_rel = nullptr; c->d_rel2 = nullptr; c->d_dirty = nullptr;
   dev_free(c->d_nn_idx); dev_free(c->d_nn_d2); dev_free(c->d_nn_lb); dev_free(c->d_first); dev_free(c->d_second);
   dev_free(c->d_sblock_off); dev_free(c->d_sel_keys1); dev_free(c->d_sel_keys2); c->n_sblocks = 0;
   dev_free(c->d_cd2); dev_free(c->d_qpos); dev_free(c->d_dirty_slots); dev_free(c->d_dslot_off); dev_free(c->d_stream); dev_free(c->d_cblock_off); dev_free(c->d_cblock_cnt); if (c->d_sel_state) (void)hipFree(c->d_sel_state);
@@ -375,7 +375,7 @@ static void throttle_builds(mvicp_ctx* c) {
 }
 
 // One device evaluation of all per-edge blocks at `poses` -> host `out` (E x 91), all-reduced over ranks.
-int evaluate_blocks(mvicp_ctx* c, const double* poses, int plane, int robust, double* out) {
+static int check_evaluable(mvicp_ctx* c, int plane) {
   if (!c->have_corr) { set_error("no correspondences: call mvicp_correspond or mvicp_set_correspondences first"); return MVICP_ERR_STATE; }
   if (plane) {
     for (int e = 0; e < c->E; ++e)
@@ -384,6 +384,28 @@ int evaluate_blocks(mvicp_ctx* c, const double* poses, int plane, int robust, do
         return MVICP_ERR_STATE;
       }
   }
+  return MVICP_OK;
+}
+
+// Single rank: the blocks at poses_a and at poses_b from ONE paired launch (linearize.hip), each what evaluate_blocks gives for its poses bit for bit.  The
+// queued evaluations of the last search, their buffers and the candidate-pose prediction are left alone.
+int evaluate_pair(mvicp_ctx* c, const double* poses_a, const double* poses_b, int plane, int robust, double* out_a, double* out_b) {
+  MV_CHECK(check_evaluable(c, plane));
+  HostScope hs(c, "host.evaluate");
+  const size_t n = (size_t)c->E * MVICP_EDGE_BLOCK;
+  fill_rel_into(c, poses_b, c->h_pin + c->ctl_rel2_off);
+  fill_rel(c, poses_a);
+  // rel2 | rel | a are adjacent in the control block: one upload
+  MV_HIP(hipMemcpyAsync(c->d_rel2, c->h_pin + c->ctl_rel2_off, sizeof(double) * ((size_t)c->E * kEdgeRel + c->ctl_r2), hipMemcpyHostToDevice, c->stream));
+  MV_CHECK(launch_linearize_pair(c, plane, robust, c->d_blocks_host, c->d_blocks2_host));
+  MV_CHECK(stream_wait(c));
+  std::memcpy(out_a, c->h_pin + c->pin_blocks_off, sizeof(double) * n);
+  std::memcpy(out_b, c->h_pin + c->pin_blocks2_off, sizeof(double) * n);
+  return MVICP_OK;
+}
+
+int evaluate_blocks(mvicp_ctx* c, const double* poses, int plane, int robust, double* out) {
+  MV_CHECK(check_evaluable(c, plane));
   HostScope hs(c, "host.evaluate");
   const size_t n = (size_t)c->E * MVICP_EDGE_BLOCK;
   if (c->spec_ready) {
@@ -880,16 +902,17 @@ int mvicp_set_graph(mvicp_ctx* c, int n_edges, const int* src, const int* dst) t
   const size_t cap = (size_t)c->total_cap;
   MV_CHECK(dev_alloc(&c->d_esrc, E)); MV_CHECK(dev_alloc(&c->d_edst, E)); MV_CHECK(dev_alloc(&c->d_cap_off, E + 1));
   MV_CHECK(dev_alloc(&c->d_count, E));
-  // control block (see common.h): region 1 = xf | nsrc | dirty, region 2 = rel | a
+  // control block (see common.h): region 1 = xf | nsrc | dirty, rel2 (second pose set of a paired evaluation), region 2 = rel | a
   c->ctl_r1 = (size_t)E * kEdgeXf + (size_t)E + 2 * (size_t)E;  // xf | 2E ints = E doubles | select brackets (lo, hi) per edge
-  c->ctl_r2_off = (c->ctl_r1 + 1) & ~(size_t)1;                // 16-B aligned
+  c->ctl_rel2_off = (c->ctl_r1 + 1) & ~(size_t)1;              // 16-B aligned
+  c->ctl_r2_off = c->ctl_rel2_off + (size_t)E * kEdgeRel;      // (E x 12 doubles: still 16-B aligned)
   c->ctl_r2 = (size_t)E * (kEdgeRel + 1);
   MV_CHECK(dev_alloc(&c->d_ctl, c->ctl_r2_off + c->ctl_r2));
   MV_HIP(hipMemset(c->d_ctl, 0, sizeof(double) * std::max<size_t>(c->ctl_r2_off + c->ctl_r2, 1)));
   c->d_xf = c->d_ctl; c->d_nsrc = reinterpret_cast<int*>(c->d_ctl + (size_t)E * kEdgeXf); c->d_dirty = c->d_nsrc + E;
   c->d_sel_lohi = c->d_ctl + (size_t)E * (kEdgeXf + 1);
   c->sel_med1.assign(E, -1.0); c->sel_med2.assign(E, -1.0);
-  c->d_rel = c->d_ctl + c->ctl_r2_off; c->d_a = c->d_rel + (size_t)E * kEdgeRel;
+  c->d_rel = c->d_ctl + c->ctl_r2_off; c->d_a = c->d_rel + (size_t)E * kEdgeRel; c->d_rel2 = c->d_ctl + c->ctl_rel2_off;
   MV_CHECK(dev_alloc(&c->d_nn_idx, cap)); MV_CHECK(dev_alloc(&c->d_nn_d2, cap)); MV_CHECK(dev_alloc(&c->d_nn_lb, cap));
   c->nn_cache_valid = false; c->prev_q.assign((size_t)E * 12, 0.0); c->nn_cache_edge.assign(E, 0);
   c->auto_prev_dist = 0.0; c->auto_last_method = -1; c->corr_tie_seen = c->corr_far_seen = 1u;
@@ -931,7 +954,7 @@ int mvicp_set_graph(mvicp_ctx* c, int n_edges, const int* src, const int* dst) t
   MV_CHECK(dev_alloc(&c->d_median, E));
   MV_CHECK(dev_alloc(&c->d_chunk_edge, (size_t)c->n_chunks)); MV_CHECK(dev_alloc(&c->d_chunk_start, (size_t)c->n_chunks));
   MV_CHECK(dev_alloc(&c->d_chunk_first, E + 1));
-  MV_CHECK(dev_alloc(&c->d_partials, (size_t)c->n_chunks * kLinPartial));
+  MV_CHECK(dev_alloc(&c->d_partials, 2 * (size_t)c->n_chunks * kLinPartial));   // (second half: the second pose set of a paired launch)
   MV_CHECK(dev_alloc(&c->d_out, (size_t)E * (MVICP_EDGE_BLOCK + 3) + 2));   // blocks | (count, median d2) x E | armed | a x E  (see common.h)
   MV_HIP(hipMemset(c->d_out, 0, sizeof(double) * ((size_t)E * (MVICP_EDGE_BLOCK + 3) + 2)));
   if (E) {
@@ -955,7 +978,8 @@ int mvicp_set_graph(mvicp_ctx* c, int n_edges, const int* src, const int* dst) t
   if (c->h_pin) { MV_HIP(hipHostFree(c->h_pin)); c->h_pin = nullptr; c->h_pin_doubles = 0; }
   c->pin_spec2_off = (c->pin_adev_off + (size_t)E + 8 + 1) & ~(size_t)1;                 // blocks of the second queued evaluation (16-B aligned)
   c->pin_rel2_off = c->pin_spec2_off + (size_t)E * MVICP_EDGE_BLOCK + ((size_t)E * MVICP_EDGE_BLOCK & 1);   // its relative transforms (E x 12), copied into d_rel in stream order
-  MV_CHECK(ensure_pin(c, c->pin_rel2_off + (size_t)E * kEdgeRel + 8));
+  c->pin_blocks2_off = (c->pin_rel2_off + (size_t)E * kEdgeRel + 1) & ~(size_t)1;         // second block set of mvicp_linearize_pair (16-B aligned)
+  MV_CHECK(ensure_pin(c, c->pin_blocks2_off + (size_t)E * MVICP_EDGE_BLOCK + 8));
   {
     void* dp = nullptr;
     MV_HIP(hipHostGetDevicePointer(&dp, c->h_pin, 0));
@@ -964,6 +988,7 @@ int mvicp_set_graph(mvicp_ctx* c, int n_edges, const int* src, const int* dst) t
     c->d_spec_host = (double*)dp + c->pin_spec_off;
     c->d_adev_host = (double*)dp + c->pin_adev_off;
     c->d_spec2_host = (double*)dp + c->pin_spec2_off;
+    c->d_blocks2_host = (double*)dp + c->pin_blocks2_off;
   }
   c->spec_ready = false; c->spec_arm = false; c->bracket_counters_clean = false;
   c->spec2_ready = false; c->spec2_armed = false; c->last_cand_poses.clear();
@@ -1221,6 +1246,7 @@ static int correspond_once(mvicp_ctx* c, const double* poses, const unsigned cha
   c->d_res_target = exchange ? c->d_out + nb : nullptr;
   c->d_a_check = exchange ? c->d_out + nb + 2 * (size_t)E + 1 : c->d_adev_host;   // where the select kernels copy the scales they derive
   size_t upload_doubles = c->ctl_r1;
+  bool spec2_plan = false;
   if (c->spec_arm) {
     // the solve evaluates at x_to_pose(pose_to_x(P)) (host/lm.cpp): the same round trip here, so the poses match bit for bit.  The
     // relative transforms of that evaluation ride on the control-block upload (region 2 follows region 1; the SoftLOne scales
@@ -1231,6 +1257,11 @@ static int correspond_once(mvicp_ctx* c, const double* poses, const unsigned cha
     fill_rel(c, c->spec_poses.data());
     c->spec_q_plane = c->spec_plane; c->spec_q_robust = c->spec_robust;
     upload_doubles = c->ctl_r2_off + (size_t)E * kEdgeRel;
+    // second queued evaluation: this search's poses are last search's bit for bit, so the solve that follows will ask for last solve's candidate again
+    spec2_plan = !exchange && c->spec2_enable && all_same && same_active_set && c->have_corr && c->last_cand_poses.size() == 16 * (size_t)c->n_frames &&
+                 c->last_cand_plane == c->spec_q_plane && c->last_cand_robust == c->spec_q_robust;
+    // paired launch (option lin_pair): its relative transforms lie between region 1 and rel, so they ride on the same upload
+    if (spec2_plan && c->lin_pair) fill_rel_into(c, c->last_cand_poses.data(), hx + c->ctl_rel2_off);
   }
   if (method != MVICP_NN_BRUTE && method != MVICP_NN_GRID && method != MVICP_NN_TILE) { set_error("unknown nn_method %d", nn_method); return MVICP_ERR_ARG; }   // (an argument error: the same on every rank)
   bool all_unchanged = true;
@@ -1303,13 +1334,16 @@ static int correspond_once(mvicp_ctx* c, const double* poses, const unsigned cha
     if (st_q == MVICP_OK && hipMemcpyAsync(c->h_pin + c->pin_spec_off, c->d_out, sizeof(double) * (nb + ntail), hipMemcpyDeviceToHost, c->stream) != hipSuccess) {
       set_error("hipMemcpyAsync of the exchanged buffer failed"); st_q = MVICP_ERR_HIP;
     }
+  } else if (c->spec_arm && spec2_plan && c->lin_pair) {
+    // both queued evaluations in one pass over the operand stream: first blocks -> d_spec_host, second -> d_spec2_host
+    c->spec2_armed = false;
+    st_q = launch_linearize_pair(c, c->spec_q_plane, c->spec_q_robust, c->d_spec_host, c->d_spec2_host);
+    if (st_q == MVICP_OK) { c->spec2_armed = true; c->spec2_poses = c->last_cand_poses; c->spec2_plane = c->spec_q_plane; c->spec2_robust = c->spec_q_robust; }
   } else if (c->spec_arm) {
     c->lin_out = c->d_spec_host;
     st_q = launch_linearize(c, c->spec_q_plane, c->spec_q_robust);
-    // second queued evaluation: this search's poses are last search's bit for bit, so the solve that follows will ask for last solve's candidate again
     c->spec2_armed = false;
-    if (st_q == MVICP_OK && c->spec2_enable && all_same && same_active_set && c->have_corr && c->last_cand_poses.size() == 16 * (size_t)c->n_frames &&
-        c->last_cand_plane == c->spec_q_plane && c->last_cand_robust == c->spec_q_robust) {
+    if (st_q == MVICP_OK && spec2_plan) {
       fill_rel_into(c, c->last_cand_poses.data(), c->h_pin + c->pin_rel2_off);
       if (hipMemcpyAsync(c->d_rel, c->h_pin + c->pin_rel2_off, sizeof(double) * (size_t)E * kEdgeRel, hipMemcpyHostToDevice, c->stream) == hipSuccess) {
         c->lin_out = c->d_spec2_host;
@@ -1593,6 +1627,21 @@ int mvicp_linearize(mvicp_ctx* c, const double* poses, int point_to_plane, int r
   return MVICP_OK;
 } MVICP_GUARD_ABI
 
+// Two evaluations on the current correspondences in one pass over the operand stream (single rank); see include/mvicp.h
+int mvicp_linearize_pair(mvicp_ctx* c, const double* poses_a, const double* poses_b, int point_to_plane, int robust, double* out_a, double* out_b) try {
+  MV_CHECK(bind(c));
+  if (!poses_a || !poses_b || !out_a || !out_b) { set_error("null argument"); return MVICP_ERR_ARG; }
+  if (c->E == 0) { set_error("no graph"); return MVICP_ERR_STATE; }
+  if (c->comm || c->ar_fn) {   // an exchange is configured: two ordinary evaluations (one collective each)
+    MV_CHECK(evaluate_blocks(c, poses_a, point_to_plane, robust, out_a));
+    MV_CHECK(evaluate_blocks(c, poses_b, point_to_plane, robust, out_b));
+  } else {
+    MV_CHECK(evaluate_pair(c, poses_a, poses_b, point_to_plane, robust, out_a, out_b));
+  }
+  if (c->profile) prof_collect_lazy(c);
+  return MVICP_OK;
+} MVICP_GUARD_ABI
+
 int mvicp_set_option(mvicp_ctx* c, const char* name, double value) try {
   MV_CHECK(bind(c));
   if (!name) { set_error("null option name"); return MVICP_ERR_ARG; }
@@ -1604,6 +1653,7 @@ int mvicp_set_option(mvicp_ctx* c, const char* name, double value) try {
   if (std::strcmp(name, "list_reuse") == 0) { c->list_reuse = value != 0.0; return MVICP_OK; }
   if (std::strcmp(name, "lin_interleave") == 0) { c->lin_interleave = value != 0.0; return MVICP_OK; }   // takes effect at the next mvicp_set_graph
   if (std::strcmp(name, "lin_share_p") == 0) { c->lin_share_p = value != 0.0; return MVICP_OK; }
+  if (std::strcmp(name, "lin_pair") == 0) { c->lin_pair = value != 0.0; return MVICP_OK; }   // 0: the two queued evaluations of a fixed-point round as two launches
   if (std::strcmp(name, "nn_census") == 0) { c->nn_census = value != 0.0; return MVICP_OK; }
   if (std::strcmp(name, "nn_skip_far") == 0) { c->nn_skip_far = value != 0.0; return MVICP_OK; }
   if (std::strcmp(name, "sel_bracket") == 0) { c->sel_bracket = value != 0.0; return MVICP_OK; }

@@ -139,7 +139,9 @@ struct mvicp_ctx {
   // device per-edge tables.  d_xf / d_nsrc / d_dirty and d_rel / d_a are views into ONE control block (d_ctl) mirrored in
   // pinned host memory, so a round costs one upload before the NN stage and one per LM evaluation:
   //   region 1 (correspond): xf [E x kEdgeXf] | nsrc [E int] | dirty [E int]        region 2 (evaluate): rel [E x kEdgeRel] | a [E]
-  double* d_ctl = nullptr; size_t ctl_r1 = 0, ctl_r2_off = 0, ctl_r2 = 0;   // sizes / offset in doubles
+  // Between the two lies rel2 [E x kEdgeRel], the second pose set of a paired evaluation (linearize.hip): a search that queues evaluations uploads
+  // region 1 | rel2 | rel in one copy (the scales `a` behind them are written on the device).
+  double* d_ctl = nullptr; size_t ctl_r1 = 0, ctl_rel2_off = 0, ctl_r2_off = 0, ctl_r2 = 0;   // sizes / offsets in doubles
   int* d_esrc = nullptr; int* d_edst = nullptr;
   long long* d_cap_off = nullptr;   // E+1
   int* d_nsrc = nullptr;            // E: N_src if owned and active else 0
@@ -147,6 +149,7 @@ struct mvicp_ctx {
   double* d_a = nullptr;            // E: SoftLOne scale (double)(float)weight
   double* d_xf = nullptr;           // E x kEdgeXf
   double* d_rel = nullptr;          // E x kEdgeRel
+  double* d_rel2 = nullptr;         // E x kEdgeRel: relative transforms of the second pose set of a paired launch
   // per-query (total_cap)
   int* d_nn_idx = nullptr; double* d_nn_d2 = nullptr;
   float* d_nn_lb = nullptr;         // fp32, rounded down: lower bound on the DISTANCE from the query to every target other than nn_idx (temporal cache)
@@ -194,7 +197,8 @@ struct mvicp_ctx {
   int n_chunks = 0;
   std::vector<int> chunk_first;     // E+1
   int* d_chunk_edge = nullptr; int* d_chunk_start = nullptr; int* d_chunk_first = nullptr;
-  double* d_partials = nullptr;     // n_chunks x kLinPartial
+  double* d_partials = nullptr;     // 2 x n_chunks x kLinPartial (second half: the second pose set of a paired launch)
+  bool lin_pair = true;             // option "lin_pair": two queued evaluations of a fixed-point round go as ONE paired launch (0: two launches, a copy between them)
   double* d_out = nullptr;          // E x 91 blocks | E x 2 (count, median d2) | 1 "armed" slot: ONE buffer, so that with N > 1 ranks a round's
                                     // counts / medians / use-the-queued-evaluation decision travel in the same all-reduce as the queued blocks
   double* d_res_target = nullptr;   // where the select kernels put (count, median d2): null = mapped host memory (single rank), else d_out's tail
@@ -216,13 +220,15 @@ struct mvicp_ctx {
   // Second queued evaluation (round 6, single rank).  At the fixed point of a registration every round's solve is: first evaluation (queued, above) -> one LM
   // iteration -> candidate evaluation -> function-tolerance stop, and the candidate poses are last round's bit for bit (same inputs).  When this search's poses
   // are bit-identical to the last search's, the candidate evaluation of the LAST solve is queued right behind the first one (relative transforms from a second
-  // pinned slice, copied into d_rel in stream order between the two), so the round waits ONCE for both.  Used only if the solve really asks for exactly those
+  // pinned slice, copied into d_rel in stream order between the two — or, option lin_pair, both in ONE paired launch that reads the operand stream once, with
+  // the second set of relative transforms riding on the control-block upload), so the round waits ONCE for both.  Used only if the solve really asks for exactly those
   // poses; nothing is skipped — the work is queued earlier.
   bool spec2_enable = true, spec2_armed = false, spec2_ready = false; int spec2_plane = 0, spec2_robust = 0;
   std::vector<double> spec2_poses;       // poses the second queued evaluation was made at
   std::vector<double> last_cand_poses;   // poses of the last evaluation a solve asked for beyond its first (the prediction for the next solve's candidate)
   int last_cand_plane = -1, last_cand_robust = -1;
   size_t pin_spec2_off = 0, pin_rel2_off = 0; double* d_spec2_host = nullptr;
+  size_t pin_blocks2_off = 0; double* d_blocks2_host = nullptr;   // second block set of mvicp_linearize_pair (device view of its pinned region)
   double* d_a_check = nullptr;      // where this search's select kernels copy the SoftLOne scales they derive: mapped host memory (single rank) or d_out's tail
   bool spin_wait = false;           // poll the stream instead of a blocking wait (measured: no gain, HIP's own wait already spins)
   unsigned long long* h_census = nullptr;   // pinned: 8 counters of the last NN launch, resolved after the round's own sync
@@ -343,6 +349,7 @@ int launch_select_median(mvicp_ctx* c);
 int launch_export(mvicp_ctx* c);           // export.hip: every exportable edge's list -> reference-order triples in pinned memory (async; caller waits)
 int launch_select_bracket(mvicp_ctx* c);   // one-pass select around last round's medians (d_sel_lohi); flags edges it cannot answer
 int launch_linearize(mvicp_ctx* c, int plane, int robust);                            // linearize.hip
+int launch_linearize_pair(mvicp_ctx* c, int plane, int robust, double* out_a, double* out_b);   // linearize.hip: d_rel -> out_a, d_rel2 -> out_b, one pass
 int launch_normals(mvicp_ctx* c, FrameDev& f, int k, int* d_knn);                      // normals.hip
 int stream_wait(mvicp_ctx* c);      // api.cpp: wait for the context's stream (spin-polls first)
 void census_resolve(mvicp_ctx* c);  // api.cpp: fold the counters of the last NN launch into the profile (after a sync)

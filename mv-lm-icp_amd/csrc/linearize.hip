@@ -77,8 +77,10 @@ __device__ __forceinline__ void accumulate(double (&acc)[NACC], const double* __
     for (int i = 0; i < 6; ++i) {
       const double wu = w * u[i];
 #pragma unroll
-      for (int j = i; j < 6; ++j) acc[o++] += wu * u[j];
-      acc[21 + i] += wu * r;
+      // (explicit fma: what the compiler contracts these to anyway; spelled out so that the two-pose build, where n_i n_j is common to both pose sets
+      // when w = 1, cannot keep the shared product as a separate rounded multiply)
+      for (int j = i; j < 6; ++j) { acc[o] = __builtin_fma(wu, u[j], acc[o]); ++o; }
+      acc[21 + i] = __builtin_fma(wu, r, acc[21 + i]);
     }
   } else {
     const double f0 = x0 - q0, f1 = x1 - q1, f2 = x2 - q2;
@@ -104,13 +106,21 @@ __device__ __forceinline__ void accumulate(double (&acc)[NACC], const double* __
   }
 }
 
-template <bool PLANE, bool ROBUST>
+// Extra kernel arguments of the two-pose builds (empty for one pose set, so the one-pose kernels keep their argument layout).
+template <int NP> struct PairArgs {};
+template <> struct PairArgs<2> { const double* rel2; size_t partials2_off; double* out2; };
+
+// NP = 1 or 2 pose sets.  NP = 2 (the paired launch) reads the operand stream ONCE and accumulates the moments of two sets of relative transforms (rel, x.rel2)
+// side by side: same loads, same chunk order, every expression of a set exactly the one-pose build's, each set reduced through LDS in the same fixed order ->
+// partials bit-identical to two one-pose launches.  The second set's partials follow the first's at x.partials2_off doubles.  2 x 28 / 29 fp64 accumulators
+// per lane: 2 waves per SIMD instead of 3, no spills.
+template <bool PLANE, bool ROBUST, int NP>
 __global__ __launch_bounds__(NT) void linearize_kernel(const int* __restrict__ chunk_edge, const int* __restrict__ chunk_start, int chunk,
                                                        const int* __restrict__ count, const long long* __restrict__ cap_off, long long total_cap,
                                                        const double* __restrict__ rel, const double* __restrict__ a_scale,
                                                        const double* __restrict__ stream, double* __restrict__ partials,
                                                        const double* const* __restrict__ src_pts, const int* __restrict__ nsrc,
-                                                       const int* __restrict__ chunk_first) {
+                                                       const int* __restrict__ chunk_first, PairArgs<NP> x) {
   const int e = chunk_edge[blockIdx.x];
   const int start = chunk_start[blockIdx.x];
   // the partial's slot is the chunk's place in ITS EDGE's run (chunk_first[e] + k), whatever the launch order of the workgroups (api.cpp interleaves the chunks
@@ -120,21 +130,27 @@ __global__ __launch_bounds__(NT) void linearize_kernel(const int* __restrict__ c
   const int cnt = count[e];
   if (start >= cnt) return;
   const int end = min(cnt, start + chunk);
-  __shared__ double srel[kEdgeRel];
+  __shared__ double srel[NP][kEdgeRel];
   __shared__ double red[NACC / 2][NT + 1];
-  if (threadIdx.x < kEdgeRel) srel[threadIdx.x] = rel[(size_t)e * kEdgeRel + threadIdx.x];
+  if (threadIdx.x < kEdgeRel) srel[0][threadIdx.x] = rel[(size_t)e * kEdgeRel + threadIdx.x];
+  if constexpr (NP > 1) { if (threadIdx.x >= 32 && threadIdx.x < 32 + kEdgeRel) srel[1][threadIdx.x - 32] = x.rel2[(size_t)e * kEdgeRel + threadIdx.x - 32]; }
   __syncthreads();
-  double A[9], t[3];
+  double A[NP][9], t[NP][3];
 #pragma unroll
-  for (int i = 0; i < 9; ++i) A[i] = srel[i];
+  for (int k = 0; k < NP; ++k) {
 #pragma unroll
-  for (int i = 0; i < 3; ++i) t[i] = srel[9 + i];
+    for (int i = 0; i < 9; ++i) A[k][i] = srel[k][i];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) t[k][i] = srel[k][9 + i];
+  }
   double a2 = 1.0, inv_a2 = 1.0;
   if (ROBUST) { const double a = a_scale[e]; a2 = a * a; inv_a2 = 1.0 / a2; }
 
-  double acc[NACC];
+  double acc[NP][NACC];
 #pragma unroll
-  for (int i = 0; i < NACC; ++i) acc[i] = 0.0;
+  for (int k = 0; k < NP; ++k)
+#pragma unroll
+    for (int i = 0; i < NACC; ++i) acc[k][i] = 0.0;
 
   const size_t base = (size_t)cap_off[e];  // multiple of 64 -> 16-B aligned double2 loads
   const double* __restrict__ s0 = stream + base;
@@ -179,15 +195,20 @@ __global__ __launch_bounds__(NT) void linearize_kernel(const int* __restrict__ c
     const int npos = pos + 2 * NT;
     load(nxt, npos);
     // slots: plane 0-2 p, 3-5 n, 6 c;  point 0-2 p, 3-5 q
-    if (PLANE) {
-      accumulate<PLANE, ROBUST>(acc, A, t, inv_a2, a2, cur[0].x, cur[1].x, cur[2].x, cur[6].x, 0.0, 0.0, cur[3].x, cur[4].x, cur[5].x);
-      if (pos + 1 < end)
-        accumulate<PLANE, ROBUST>(acc, A, t, inv_a2, a2, cur[0].y, cur[1].y, cur[2].y, cur[6].y, 0.0, 0.0, cur[3].y, cur[4].y, cur[5].y);
-    } else {
-      accumulate<PLANE, ROBUST>(acc, A, t, inv_a2, a2, cur[0].x, cur[1].x, cur[2].x, cur[3].x, cur[4].x, cur[5].x, 0.0, 0.0, 0.0);
-      if (pos + 1 < end)
-        accumulate<PLANE, ROBUST>(acc, A, t, inv_a2, a2, cur[0].y, cur[1].y, cur[2].y, cur[3].y, cur[4].y, cur[5].y, 0.0, 0.0, 0.0);
+    // (pose set k of NP; spelled out rather than looped: a loop here, even of one trip, changes the schedule of the one-pose build)
+#define MVICP_LIN_STEP(k)                                                                                                                                   \
+    if (PLANE) {                                                                                                                                            \
+      accumulate<PLANE, ROBUST>(acc[k], A[k], t[k], inv_a2, a2, cur[0].x, cur[1].x, cur[2].x, cur[6].x, 0.0, 0.0, cur[3].x, cur[4].x, cur[5].x);             \
+      if (pos + 1 < end)                                                                                                                                    \
+        accumulate<PLANE, ROBUST>(acc[k], A[k], t[k], inv_a2, a2, cur[0].y, cur[1].y, cur[2].y, cur[6].y, 0.0, 0.0, cur[3].y, cur[4].y, cur[5].y);           \
+    } else {                                                                                                                                                \
+      accumulate<PLANE, ROBUST>(acc[k], A[k], t[k], inv_a2, a2, cur[0].x, cur[1].x, cur[2].x, cur[3].x, cur[4].x, cur[5].x, 0.0, 0.0, 0.0);                  \
+      if (pos + 1 < end)                                                                                                                                    \
+        accumulate<PLANE, ROBUST>(acc[k], A[k], t[k], inv_a2, a2, cur[0].y, cur[1].y, cur[2].y, cur[3].y, cur[4].y, cur[5].y, 0.0, 0.0, 0.0);                \
     }
+    MVICP_LIN_STEP(0)
+    if constexpr (NP > 1) { MVICP_LIN_STEP(NP - 1) }
+#undef MVICP_LIN_STEP
 #pragma unroll
     for (int j = 0; j < 9; ++j) cur[j] = nxt[j];
     pos = npos;
@@ -197,20 +218,25 @@ __global__ __launch_bounds__(NT) void linearize_kernel(const int* __restrict__ c
   // conflict-free ds_write_b64), then 16 threads per row add 16 columns each and finish with a 4-step xor-shuffle
   // inside their lane group (two passes of 16 rows keep the LDS footprint at 33 KB).  Fixed association order -> deterministic.
 #pragma unroll
-  for (int pass = 0; pass < 2; ++pass) {
-    if (pass) __syncthreads();
+  for (int k = 0; k < NP; ++k) {
+    double* __restrict__ pk = partials;
+    if constexpr (NP > 1) { if (k) pk = partials + x.partials2_off; }
 #pragma unroll
-    for (int j = 0; j < NACC / 2; ++j) red[j][threadIdx.x] = acc[pass * (NACC / 2) + j];
-    __syncthreads();
-    const int row = threadIdx.x >> 4, part = threadIdx.x & 15;  // 16 rows x 16 parts
-    double sum = 0.0;
+    for (int pass = 0; pass < 2; ++pass) {
+      if (pass || k) __syncthreads();
+#pragma unroll
+      for (int j = 0; j < NACC / 2; ++j) red[j][threadIdx.x] = acc[k][pass * (NACC / 2) + j];
+      __syncthreads();
+      const int row = threadIdx.x >> 4, part = threadIdx.x & 15;  // 16 rows x 16 parts
+      double sum = 0.0;
 #pragma unroll 8
-    for (int k = 0; k < NT / 16; ++k) sum += red[row][part + 16 * k];
-    sum += __shfl_xor(sum, 1, 64);
-    sum += __shfl_xor(sum, 2, 64);
-    sum += __shfl_xor(sum, 4, 64);
-    sum += __shfl_xor(sum, 8, 64);
-    if (part == 0) partials[(size_t)c * NACC + pass * (NACC / 2) + row] = sum;
+      for (int i = 0; i < NT / 16; ++i) sum += red[row][part + 16 * i];
+      sum += __shfl_xor(sum, 1, 64);
+      sum += __shfl_xor(sum, 2, 64);
+      sum += __shfl_xor(sum, 4, 64);
+      sum += __shfl_xor(sum, 8, 64);
+      if (part == 0) pk[(size_t)c * NACC + pass * (NACC / 2) + row] = sum;
+    }
   }
 }
 
@@ -221,10 +247,14 @@ __device__ __forceinline__ void cross_mat(const double* a, double* M) {  // row-
   M[6] = -a[1]; M[7] = a[0]; M[8] = 0;
 }
 
-template <bool PLANE>
+// NP = 2: blockIdx.y picks the pose set of a paired launch (its relative transforms, partials and output); per set the same arithmetic
+template <bool PLANE, int NP>
 __global__ __launch_bounds__(256) void reduce_expand_kernel(const int* __restrict__ chunk_first, int chunk, const int* __restrict__ count,
                                                            const double* __restrict__ rel, const double* __restrict__ partials,
-                                                           double* __restrict__ out) {
+                                                           double* __restrict__ out, PairArgs<NP> x) {
+  if constexpr (NP > 1) {
+    if (blockIdx.y) { rel = x.rel2; partials += x.partials2_off; out = x.out2; }
+  }
   const int e = blockIdx.x;
   const int tid = threadIdx.x;
   __shared__ double m[8][NACC];
@@ -342,34 +372,45 @@ __global__ __launch_bounds__(256) void reduce_expand_kernel(const int* __restric
 
 }  // namespace
 
+// algorithmic bytes of one pass over the operand stream: 32 B (plane: n, n.q) / 24 B (point: q) per correspondence + the source point p, 24 B — per correspondence
+// when the edge reads its private copy from the stream, ONCE PER SOURCE POINT for the edges of one source cloud that read the shared sorted cloud side by side
+// (identity lists, lin_share_p + lin_interleave: the second edge's read is an L2 hit by construction; PMC: 0.695 -> 0.551 GB per launch at cfg4)
+static double stream_pass_bytes(mvicp_ctx* c, int plane) {
+  double bytes = 0;
+  std::vector<char> src_counted((size_t)c->n_frames, 0);
+  for (int e = 0; e < c->E; ++e) {
+    if (!c->owned[e]) continue;
+    const double cnt = c->h_count[e];
+    const int s = c->esrc[e];
+    bytes += (plane ? 32.0 : 24.0) * cnt;
+    if (c->lin_share_p && c->lin_interleave && c->h_count[e] == c->frames[s].n) { if (!src_counted[s]) { bytes += 24.0 * cnt; src_counted[s] = 1; } }
+    else bytes += 24.0 * cnt;
+  }
+  return bytes;
+}
+
+// per-edge sorted source clouds (identity-list fast path of the kernel); table cached by content
+static int source_table(mvicp_ctx* c, const double* const** d_src) {
+  *d_src = nullptr;
+  if (c->lin_share_p) {
+    std::vector<const double*> tab((size_t)c->E, nullptr);
+    for (int e = 0; e < c->E; ++e) if (c->owned[e]) tab[e] = c->frames[c->esrc[e]].grid.spts;
+    MV_CHECK(cached_upload(c, "lin_src", tab.data(), sizeof(void*) * tab.size(), (void**)d_src));
+  }
+  return MVICP_OK;
+}
+
 int launch_linearize(mvicp_ctx* c, int plane, int robust) {
   if (c->E == 0) return MVICP_OK;
   const int chunk = c->lin_chunk;
   if (c->n_chunks > 0) {
-    // algorithmic bytes of the launch: 32 B (plane: n, n.q) / 24 B (point: q) per correspondence + the source point p, 24 B — per correspondence when the edge
-    // reads its private copy from the stream, ONCE PER SOURCE POINT for the edges of one source cloud that read the shared sorted cloud side by side (identity
-    // lists, lin_share_p + lin_interleave: the second edge's read is an L2 hit by construction; PMC: 0.695 -> 0.551 GB per launch at cfg4)
-    double bytes = 0;
-    std::vector<char> src_counted((size_t)c->n_frames, 0);
-    for (int e = 0; e < c->E; ++e) {
-      if (!c->owned[e]) continue;
-      const double cnt = c->h_count[e];
-      const int s = c->esrc[e];
-      bytes += (plane ? 32.0 : 24.0) * cnt;
-      if (c->lin_share_p && c->lin_interleave && c->h_count[e] == c->frames[s].n) { if (!src_counted[s]) { bytes += 24.0 * cnt; src_counted[s] = 1; } }
-      else bytes += 24.0 * cnt;
-    }
-    // per-edge sorted source clouds (identity-list fast path of the kernel); table cached by content
+    const double bytes = stream_pass_bytes(c, plane);
     const double* const* d_src = nullptr;
-    if (c->lin_share_p) {
-      std::vector<const double*> tab((size_t)c->E, nullptr);
-      for (int e = 0; e < c->E; ++e) if (c->owned[e]) tab[e] = c->frames[c->esrc[e]].grid.spts;
-      MV_CHECK(cached_upload(c, "lin_src", tab.data(), sizeof(void*) * tab.size(), (void**)&d_src));
-    }
+    MV_CHECK(source_table(c, &d_src));
     ProfScope ps(c, "linearize", bytes);
 #define LAUNCH(P, R)                                                                                                                           \
-  hipLaunchKernelGGL((linearize_kernel<P, R>), dim3(c->n_chunks), dim3(NT), 0, c->stream, c->d_chunk_edge, c->d_chunk_start, chunk, c->d_count, \
-                     c->d_cap_off, c->total_cap, c->d_rel, c->d_a, c->d_stream, c->d_partials, d_src, (const int*)c->d_nsrc, (const int*)c->d_chunk_first)
+  hipLaunchKernelGGL((linearize_kernel<P, R, 1>), dim3(c->n_chunks), dim3(NT), 0, c->stream, c->d_chunk_edge, c->d_chunk_start, chunk, c->d_count, \
+                     c->d_cap_off, c->total_cap, c->d_rel, c->d_a, c->d_stream, c->d_partials, d_src, (const int*)c->d_nsrc, (const int*)c->d_chunk_first, PairArgs<1>{})
     if (plane && robust) LAUNCH(true, true);
     else if (plane) LAUNCH(true, false);
     else if (robust) LAUNCH(false, true);
@@ -379,9 +420,41 @@ int launch_linearize(mvicp_ctx* c, int plane, int robust) {
   {
     ProfScope ps(c, "reduce", 0.0);
     if (plane)
-      hipLaunchKernelGGL((reduce_expand_kernel<true>), dim3(c->E), dim3(256), 0, c->stream, c->d_chunk_first, chunk, c->d_count, c->d_rel, c->d_partials, c->lin_out ? c->lin_out : c->d_out);
+      hipLaunchKernelGGL((reduce_expand_kernel<true, 1>), dim3(c->E), dim3(256), 0, c->stream, c->d_chunk_first, chunk, c->d_count, c->d_rel, c->d_partials, c->lin_out ? c->lin_out : c->d_out, PairArgs<1>{});
     else
-      hipLaunchKernelGGL((reduce_expand_kernel<false>), dim3(c->E), dim3(256), 0, c->stream, c->d_chunk_first, chunk, c->d_count, c->d_rel, c->d_partials, c->lin_out ? c->lin_out : c->d_out);
+      hipLaunchKernelGGL((reduce_expand_kernel<false, 1>), dim3(c->E), dim3(256), 0, c->stream, c->d_chunk_first, chunk, c->d_count, c->d_rel, c->d_partials, c->lin_out ? c->lin_out : c->d_out, PairArgs<1>{});
+  }
+  MV_HIP(hipGetLastError());
+  return MVICP_OK;
+}
+
+// Two evaluations on the same correspondences and scales in ONE pass over the stream: the blocks at the relative transforms in d_rel go to out_a, those at
+// d_rel2 to out_b — what launch_linearize would give for each, bit for bit.  The profile scope is its own ("linearize_pair", bytes of one pass).
+int launch_linearize_pair(mvicp_ctx* c, int plane, int robust, double* out_a, double* out_b) {
+  if (c->E == 0) return MVICP_OK;
+  const int chunk = c->lin_chunk;
+  PairArgs<2> x;
+  x.rel2 = c->d_rel2; x.partials2_off = (size_t)c->n_chunks * kLinPartial; x.out2 = out_b;
+  if (c->n_chunks > 0) {
+    const double bytes = stream_pass_bytes(c, plane);
+    const double* const* d_src = nullptr;
+    MV_CHECK(source_table(c, &d_src));
+    ProfScope ps(c, "linearize_pair", bytes);
+#define LAUNCH(P, R)                                                                                                                              \
+  hipLaunchKernelGGL((linearize_kernel<P, R, 2>), dim3(c->n_chunks), dim3(NT), 0, c->stream, c->d_chunk_edge, c->d_chunk_start, chunk, c->d_count, \
+                     c->d_cap_off, c->total_cap, c->d_rel, c->d_a, c->d_stream, c->d_partials, d_src, (const int*)c->d_nsrc, (const int*)c->d_chunk_first, x)
+    if (plane && robust) LAUNCH(true, true);
+    else if (plane) LAUNCH(true, false);
+    else if (robust) LAUNCH(false, true);
+    else LAUNCH(false, false);
+#undef LAUNCH
+  }
+  {
+    ProfScope ps(c, "reduce", 0.0);
+    if (plane)
+      hipLaunchKernelGGL((reduce_expand_kernel<true, 2>), dim3(c->E, 2), dim3(256), 0, c->stream, c->d_chunk_first, chunk, c->d_count, c->d_rel, c->d_partials, out_a, x);
+    else
+      hipLaunchKernelGGL((reduce_expand_kernel<false, 2>), dim3(c->E, 2), dim3(256), 0, c->stream, c->d_chunk_first, chunk, c->d_count, c->d_rel, c->d_partials, out_a, x);
   }
   MV_HIP(hipGetLastError());
   return MVICP_OK;

@@ -14,7 +14,7 @@ EDGE_BLOCK = 91
 SYMBOLS = [
     "mvicp_last_error", "mvicp_version", "mvicp_create", "mvicp_destroy", "mvicp_set_num_frames", "mvicp_set_frame",
     "mvicp_recompute_normals", "mvicp_set_graph", "mvicp_set_shard", "mvicp_edge_owner", "mvicp_comm_unique_id", "mvicp_comm_init", "mvicp_comm_nranks", "mvicp_comm_set_callback", "mvicp_correspond",
-    "mvicp_get_correspondences", "mvicp_map_correspondences", "mvicp_map_correspondences_async", "mvicp_wait_correspondences", "mvicp_correspondence_epochs", "mvicp_set_correspondences", "mvicp_nn_query", "mvicp_linearize", "mvicp_optimize",
+    "mvicp_get_correspondences", "mvicp_map_correspondences", "mvicp_map_correspondences_async", "mvicp_wait_correspondences", "mvicp_correspondence_epochs", "mvicp_set_correspondences", "mvicp_nn_query", "mvicp_linearize", "mvicp_linearize_pair", "mvicp_optimize",
     "mvicp_lm_solve", "mvicp_set_option", "mvicp_nn_census", "mvicp_nn_census_ex", "mvicp_reset_history", "mvicp_profile_enable", "mvicp_profile_reset", "mvicp_profile_get", "mvicp_profile_get_ex", "mvicp_stream", "mvicp_sync",
     "mvicp_closedform_point_to_point", "mvicp_closedform_point_to_plane", "mvicp_set_frame_device", "mvicp_get_structure",
     "mvicp_overlap", "mvicp_graph_from_overlap",
@@ -76,6 +76,7 @@ def load_library(path=None):
     lib.mvicp_set_correspondences.argtypes = [vp, C.c_int, C.c_int, ip, ip, C.c_float]
     lib.mvicp_nn_query.argtypes = [vp, C.c_int, dp, C.c_int, C.c_int, ip, dp]
     lib.mvicp_linearize.argtypes = [vp, dp, C.c_int, C.c_int, dp]
+    lib.mvicp_linearize_pair.argtypes = [vp, dp, dp, C.c_int, C.c_int, dp, dp]
     lib.mvicp_optimize.argtypes = [vp, dp, u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Summary)]
     lib.mvicp_lm_solve.argtypes = [C.c_int, C.c_int, ip, ip, dp, u8p, C.c_int, C.c_int, EVAL_FN, vp, C.POINTER(Summary)]
     lib.mvicp_set_option.argtypes = [vp, C.c_char_p, C.c_double]
@@ -466,6 +467,14 @@ class Engine:
         _check(self.lib, self.lib.mvicp_linearize(self.h, _dp(P), int(point_to_plane), int(robust), _dp(out)))
         return out
 
+    def linearize_pair(self, poses_a, poses_b, point_to_plane, robust):
+        """linearize(poses_a), linearize(poses_b) from one pass over the operand stream (bit-identical to the two calls)."""
+        Pa, Pb = poses_to_c(poses_a), poses_to_c(poses_b)
+        out_a = np.zeros((self.E, EDGE_BLOCK), dtype=np.float64)
+        out_b = np.zeros((self.E, EDGE_BLOCK), dtype=np.float64)
+        _check(self.lib, self.lib.mvicp_linearize_pair(self.h, _dp(Pa), _dp(Pb), int(point_to_plane), int(robust), _dp(out_a), _dp(out_b)))
+        return out_a, out_b
+
     def optimize(self, poses, fixed, param=PARAM_SOPHUS_SE3, point_to_plane=True, robust=True, max_iterations=50):
         b = self._round_buffers(len(poses))
         np.copyto(b["P44"], np.transpose(np.asarray(poses, dtype=np.float64), (0, 2, 1)))
@@ -484,7 +493,7 @@ class Engine:
 
     # ---- profiling
     def profile(self, on=True):
-        """on: False/0 off, True/1 every scope, 2 only the roofline scopes "nn" and "linearize"."""
+        """on: False/0 off, True/1 every scope, 2 only the roofline scopes "nn", "linearize" and "linearize_pair"."""
         _check(self.lib, self.lib.mvicp_profile_enable(self.h, int(on)))
 
     def profile_reset(self):
