@@ -5,8 +5,10 @@
 // Operand stream (SoA, `total_cap` doubles per array, written once per round by the gather kernel, corr.hip):
 //   arrays 0-2 p (source point, src frame) | 3-5 n (dst normal) | 6 c = n . q | 7-9 q (dst point).
 // Point-to-plane needs q only through the scalar c:  r = n . (p~ - q) = n . p~ - c,  so it reads 7 arrays instead
-// of 9 (-22 % bytes on the kernel that dominates the LM phase).  The two forms of r differ by the rounding of two
-// O(|p~|) dot products, ~3e-16 absolute, i.e. ~1e-14 relative in the assembled g: far inside the 1e-11 block tolerance.
+// of 9 (-22 % bytes on the kernel that dominates the LM phase).  The two forms of r differ by the rounding of O(|p~|)-sized dot products: an absolute
+// error of a few eps |p~| per residual, which the assembled g carries as ~eps |p~| / |r| RELATIVE — 1e-14 for unit-scale clouds with mm residuals, but
+// growing in proportion to the distance of the data from the dst frame's origin (1e-10 at |p~| = 1e4).  An fp64 evaluation of the reference's own
+// functors rounds p~ the same way and loses the same digits (families "t" and "W"); H and the cost are not affected.
 //
 // Replaces what Ceres does with one AutoDiffCostFunction + SoftLOneLoss per correspondence
 // (src/internal/icp-ceres.cpp:270-292,360-378,435-453 on the functors of include/icp-ceres.h:49-316):
@@ -20,14 +22,20 @@
 // that lives in the dst frame:
 //   point-to-plane  r = n . (p~ - q),  u = [n ; p~ x n],           J = [ Ad^T u ; -u ]
 //   point-to-point  r = p~ - q,        u_k = [e_k ; p~ x e_k],     J_k = [ Ad^T u_k ; -u_k + [0 ; r x e_k] ]
-// so instead of 78 + 12 + 1 running sums per lane only the weighted 6x6 moment block is accumulated:
-//   plane (28 sums):  U = sum w u u^T (21), v = sum w r u (6), cost
-//   point (29 sums):  sum w {1, p~ (3), p~ p~^T (6), r (3), p~ r^T (9), r r^T (6)}, cost
-// with w = rho'(|r|^2) = 1/sqrt(1 + |r|^2 / a^2), cost = sum rho/2, rho = 2 a^2 (sqrt(1 + s/a^2) - 1)
-// (ceres::SoftLOneLoss(a = edge.weight) [upstream]), and the 12x12 block is expanded ONCE per edge:
-//   H_ss = Ad^T S Ad, H_sd = -Ad^T (S - X), H_dd = S - X - X^T + Y, g = [Ad^T v ; -v]
-//   (plane: S = U, X = Y = 0; point: S = sum w [[I, -[p~]x],[[p~]x, -[p~]x^2]], X = sum w [[0,-[r]x],[0,-[p~]x[r]x]],
-//    Y = sum w [[0,0],[0,-[r]x^2]], v = sum w [r ; p~ x r]).
+// so instead of 78 + 12 + 1 running sums per lane only a weighted 6x6 moment block is accumulated.
+//
+// CENTRED MOMENTS.  Moments of u itself are of size |p~|^2, while the source-side Jacobian [A^T n ; p x A^T n] is of size |p|: when t is large
+// against the spread of the source cloud (views expressed in displaced sensor frames), Ad^T U Ad cancels and H_ss loses (|t| / spread)^2 eps.
+// So the moments are taken about t:  x' = A p (rotated, not translated),  u' = [n ; x' x n]  resp.  u'_k = [e_k ; x' x e_k].  Then
+//   u = L u',  L = [[I, 0], [[t]x, I]],  and  Ad^T L = diag(A^T, A^T) =: R6^T,  L [0 ; z] = [0 ; z],
+// and nothing in the expansion cancels.  Accumulated per lane:
+//   plane (28 sums):  U = sum w u' u'^T (21), v = sum w r u' (6), cost
+//   point (29 sums):  sum w {1, x' (3), x' x'^T (6), r (3), x' r^T (9), r r^T (6)}, cost
+// with r from p~ = x' + t (plane: r = n . x' + (n . t - c)), w = rho'(|r|^2) = 1/sqrt(1 + |r|^2 / a^2), cost = sum rho/2,
+// rho = 2 a^2 (sqrt(1 + s/a^2) - 1) (ceres::SoftLOneLoss(a = edge.weight) [upstream]; evaluated as 2 s w / (1 + w), half_rho below), and the 12x12 block is expanded ONCE per edge:
+//   H_ss = R6^T S R6, H_sd = -R6^T (S - X) L^T, H_dd = L (S - X - X^T + Y) L^T, g = [R6^T v ; -L v]
+//   (plane: S = U, X = Y = 0; point: S = sum w [[I, -[x']x],[[x']x, -[x']x^2]], X = sum w [[0,-[r]x],[0,-[x']x[r]x]],
+//    Y = sum w [[0,0],[0,-[r]x^2]], v = sum w [r ; x' x r]).
 //
 // Mapping: one 256-thread workgroup per chunk of `chunk` correspondences of ONE edge; ~60 accumulator
 // VGPRs per lane leave room to keep the next correspondences' loads in flight; transposed LDS block
@@ -43,6 +51,17 @@ constexpr int NT = kLinThreads;
 constexpr int NB = MVICP_EDGE_BLOCK;  // 91
 constexpr int NACC = kLinPartial;     // padded partial width (28 plane / 29 point)
 
+// rho / 2 = a^2 (sqrt(y) - 1) with y = 1 + s / a^2, written as s w / (1 + w) with w = 1 / sqrt(y): the textbook form cancels for a >> |r| (y -> 1: every term
+// is rounded to an ulp of 1, 1e-4 relative at a = 1e6 |r|), this one is good to a few ulp of the term at every a and is exactly 0 for s = 0.
+// 1 / (1 + w), 1 + w in (1, 2]: v_rcp_f64 seed + two Newton steps.
+__device__ __forceinline__ double half_rho(double s, double w) {
+  const double d = 1.0 + w;
+  double r = __builtin_amdgcn_rcp(d);
+  r = __builtin_fma(__builtin_fma(-d, r, 1.0), r, r);
+  r = __builtin_fma(__builtin_fma(-d, r, 1.0), r, r);
+  return (s * w) * r;
+}
+
 __device__ __forceinline__ double fast_rsqrt(double y) {
   // y in [1, huge): v_rsq_f64 seed + two Newton steps (each squares the error) -> ~1 ulp
   double r = __builtin_amdgcn_rsq(y);
@@ -52,14 +71,18 @@ __device__ __forceinline__ double fast_rsqrt(double y) {
 }
 
 template <bool PLANE, bool ROBUST>
-__device__ __forceinline__ void accumulate(double (&acc)[NACC], const double* __restrict__ A, const double* __restrict__ t, double inv_a2, double a2,
+__device__ __forceinline__ void accumulate(double (&acc)[NACC], const double* __restrict__ A, const double* __restrict__ t, double inv_a2,
                                            double p0, double p1, double p2, double q0, double q1, double q2, double n0, double n1, double n2) {
   // PLANE: (q0, q1, q2) = (c, -, -) with c = n . q;  POINT: (n0, n1, n2) unused
-  const double x0 = A[0] * p0 + A[3] * p1 + A[6] * p2 + t[0];
-  const double x1 = A[1] * p0 + A[4] * p1 + A[7] * p2 + t[1];
-  const double x2 = A[2] * p0 + A[5] * p1 + A[8] * p2 + t[2];
+  // x' = A p: the source point rotated into the dst frame but NOT translated — the moments are taken about the relative translation t (see the header);
+  // only the residual sees p~ = x' + t.  Explicit fma throughout: one rounding sequence whatever the build (one or two pose sets).
+  const double x0 = __builtin_fma(A[6], p2, __builtin_fma(A[3], p1, A[0] * p0));
+  const double x1 = __builtin_fma(A[7], p2, __builtin_fma(A[4], p1, A[1] * p0));
+  const double x2 = __builtin_fma(A[8], p2, __builtin_fma(A[5], p1, A[2] * p0));
   if (PLANE) {
-    const double r = (n0 * x0 + n1 * x1 + n2 * x2) - q0;
+    // r = n . x' + (n . t - c)
+    const double nt_c = __builtin_fma(n2, t[2], __builtin_fma(n1, t[1], __builtin_fma(n0, t[0], -q0)));
+    const double r = __builtin_fma(n2, x2, __builtin_fma(n1, x1, n0 * x0)) + nt_c;
     double u[6];
     u[0] = n0; u[1] = n1; u[2] = n2;
     u[3] = x1 * n2 - x2 * n1; u[4] = x2 * n0 - x0 * n2; u[5] = x0 * n1 - x1 * n0;
@@ -68,7 +91,7 @@ __device__ __forceinline__ void accumulate(double (&acc)[NACC], const double* __
     if (ROBUST) {
       const double y = 1.0 + s * inv_a2;
       w = fast_rsqrt(y);
-      acc[27] += a2 * (y * w - 1.0);
+      acc[27] += half_rho(s, w);
     } else {
       acc[27] += 0.5 * s;
     }
@@ -83,13 +106,13 @@ __device__ __forceinline__ void accumulate(double (&acc)[NACC], const double* __
       acc[21 + i] = __builtin_fma(wu, r, acc[21 + i]);
     }
   } else {
-    const double f0 = x0 - q0, f1 = x1 - q1, f2 = x2 - q2;
+    const double f0 = (x0 + t[0]) - q0, f1 = (x1 + t[1]) - q1, f2 = (x2 + t[2]) - q2;   // r = p~ - q, p~ = x' + t
     const double s = f0 * f0 + f1 * f1 + f2 * f2;
     double w = 1.0;
     if (ROBUST) {
       const double y = 1.0 + s * inv_a2;
       w = fast_rsqrt(y);
-      acc[28] += a2 * (y * w - 1.0);
+      acc[28] += half_rho(s, w);
     } else {
       acc[28] += 0.5 * s;
     }
@@ -143,8 +166,8 @@ __global__ __launch_bounds__(NT) void linearize_kernel(const int* __restrict__ c
 #pragma unroll
     for (int i = 0; i < 3; ++i) t[k][i] = srel[k][9 + i];
   }
-  double a2 = 1.0, inv_a2 = 1.0;
-  if (ROBUST) { const double a = a_scale[e]; a2 = a * a; inv_a2 = 1.0 / a2; }
+  double inv_a2 = 1.0;
+  if (ROBUST) { const double a = a_scale[e]; inv_a2 = 1.0 / (a * a); }
 
   double acc[NP][NACC];
 #pragma unroll
@@ -198,13 +221,13 @@ __global__ __launch_bounds__(NT) void linearize_kernel(const int* __restrict__ c
     // (pose set k of NP; spelled out rather than looped: a loop here, even of one trip, changes the schedule of the one-pose build)
 #define MVICP_LIN_STEP(k)                                                                                                                                   \
     if (PLANE) {                                                                                                                                            \
-      accumulate<PLANE, ROBUST>(acc[k], A[k], t[k], inv_a2, a2, cur[0].x, cur[1].x, cur[2].x, cur[6].x, 0.0, 0.0, cur[3].x, cur[4].x, cur[5].x);             \
+      accumulate<PLANE, ROBUST>(acc[k], A[k], t[k], inv_a2, cur[0].x, cur[1].x, cur[2].x, cur[6].x, 0.0, 0.0, cur[3].x, cur[4].x, cur[5].x);             \
       if (pos + 1 < end)                                                                                                                                    \
-        accumulate<PLANE, ROBUST>(acc[k], A[k], t[k], inv_a2, a2, cur[0].y, cur[1].y, cur[2].y, cur[6].y, 0.0, 0.0, cur[3].y, cur[4].y, cur[5].y);           \
+        accumulate<PLANE, ROBUST>(acc[k], A[k], t[k], inv_a2, cur[0].y, cur[1].y, cur[2].y, cur[6].y, 0.0, 0.0, cur[3].y, cur[4].y, cur[5].y);           \
     } else {                                                                                                                                                \
-      accumulate<PLANE, ROBUST>(acc[k], A[k], t[k], inv_a2, a2, cur[0].x, cur[1].x, cur[2].x, cur[3].x, cur[4].x, cur[5].x, 0.0, 0.0, 0.0);                  \
+      accumulate<PLANE, ROBUST>(acc[k], A[k], t[k], inv_a2, cur[0].x, cur[1].x, cur[2].x, cur[3].x, cur[4].x, cur[5].x, 0.0, 0.0, 0.0);                  \
       if (pos + 1 < end)                                                                                                                                    \
-        accumulate<PLANE, ROBUST>(acc[k], A[k], t[k], inv_a2, a2, cur[0].y, cur[1].y, cur[2].y, cur[3].y, cur[4].y, cur[5].y, 0.0, 0.0, 0.0);                \
+        accumulate<PLANE, ROBUST>(acc[k], A[k], t[k], inv_a2, cur[0].y, cur[1].y, cur[2].y, cur[3].y, cur[4].y, cur[5].y, 0.0, 0.0, 0.0);                \
     }
     MVICP_LIN_STEP(0)
     if constexpr (NP > 1) { MVICP_LIN_STEP(NP - 1) }
@@ -258,7 +281,7 @@ __global__ __launch_bounds__(256) void reduce_expand_kernel(const int* __restric
   const int e = blockIdx.x;
   const int tid = threadIdx.x;
   __shared__ double m[8][NACC];
-  __shared__ double S[36], X[36], Y[36], Ad[36], T1[36], T2[36], H[144], v[6];
+  __shared__ double S[36], X[36], Y[36], R6[36], Lm[36], T1[36], T2[36], T3[36], H[144], v[6];
   const int c0 = chunk_first[e];
   const int nchunks = min(chunk_first[e + 1] - c0, (count[e] + chunk - 1) / chunk);
   {
@@ -268,7 +291,7 @@ __global__ __launch_bounds__(256) void reduce_expand_kernel(const int* __restric
     for (int c = part; c < nchunks; c += 8) s += partials[(size_t)(c0 + c) * NACC + val];
     m[part][val] = s;
   }
-  if (tid < 36) { S[tid] = 0.0; X[tid] = 0.0; Y[tid] = 0.0; Ad[tid] = 0.0; }
+  if (tid < 36) { S[tid] = 0.0; X[tid] = 0.0; Y[tid] = 0.0; R6[tid] = 0.0; Lm[tid] = (tid / 6 == tid % 6) ? 1.0 : 0.0; }
   __syncthreads();
   if (tid < NACC) {
     double s = m[0][tid];
@@ -281,40 +304,40 @@ __global__ __launch_bounds__(256) void reduce_expand_kernel(const int* __restric
   const double* A = rel + (size_t)e * kEdgeRel;  // column-major 3x3
   const double* t = A + 9;
   if (tid < 9) {
-    // Ad = [[A, [t]x A],[0, A]]   (row-major 6x6)
+    // R6 = diag(A, A),  L = [[I, 0],[[t]x, I]]   (row-major 6x6)
     const int i = tid / 3, j = tid % 3;
     double tx[9];
     cross_mat(t, tx);
     const double a = A[i + 3 * j];
-    Ad[i * 6 + j] = a;
-    Ad[(3 + i) * 6 + 3 + j] = a;
-    Ad[i * 6 + 3 + j] = tx[i * 3 + 0] * A[0 + 3 * j] + tx[i * 3 + 1] * A[1 + 3 * j] + tx[i * 3 + 2] * A[2 + 3 * j];
+    R6[i * 6 + j] = a;
+    R6[(3 + i) * 6 + 3 + j] = a;
+    Lm[(3 + i) * 6 + j] = tx[i * 3 + j];
     if (PLANE) {
       if (tid < 6) v[tid] = mm[21 + tid];
     } else {
       const double w = mm[0];
       const double px[3] = {mm[1], mm[2], mm[3]};
-      const double P[9] = {mm[4], mm[5], mm[6], mm[5], mm[7], mm[8], mm[6], mm[8], mm[9]};            // sum w p p^T
+      const double P[9] = {mm[4], mm[5], mm[6], mm[5], mm[7], mm[8], mm[6], mm[8], mm[9]};            // sum w x' x'^T
       const double rr[3] = {mm[10], mm[11], mm[12]};
-      const double PR[9] = {mm[13], mm[14], mm[15], mm[16], mm[17], mm[18], mm[19], mm[20], mm[21]};  // sum w p r^T (row-major)
+      const double PR[9] = {mm[13], mm[14], mm[15], mm[16], mm[17], mm[18], mm[19], mm[20], mm[21]};  // sum w x' r^T (row-major)
       const double RR[9] = {mm[22], mm[23], mm[24], mm[23], mm[25], mm[26], mm[24], mm[26], mm[27]};
       double pxm[9], rxm[9];
       cross_mat(px, pxm);
       cross_mat(rr, rxm);
       const double trP = P[0] + P[4] + P[8], trRR = RR[0] + RR[4] + RR[8], trPR = PR[0] + PR[4] + PR[8];
       const double I = i == j ? 1.0 : 0.0;
-      // S = sum w [[I, -[p]x],[[p]x, |p|^2 I - p p^T]]
+      // (x' = A p throughout)  S = sum w [[I, -[x']x],[[x']x, |x'|^2 I - x' x'^T]]
       S[i * 6 + j] = w * I;
       S[i * 6 + 3 + j] = -pxm[i * 3 + j];
       S[(3 + i) * 6 + j] = pxm[i * 3 + j];
       S[(3 + i) * 6 + 3 + j] = trP * I - P[i * 3 + j];
-      // X = sum w [[0, -[r]x],[0, -[p]x[r]x]],  [p]x[r]x = r p^T - (p.r) I
+      // X = sum w [[0, -[r]x],[0, -[x']x[r]x]],  [x']x[r]x = r x'^T - (x'.r) I
       X[i * 6 + 3 + j] = -rxm[i * 3 + j];
       X[(3 + i) * 6 + 3 + j] = -(PR[j * 3 + i] - trPR * I);
       // Y = sum w [[0,0],[0, |r|^2 I - r r^T]]
       Y[(3 + i) * 6 + 3 + j] = trRR * I - RR[i * 3 + j];
       if (tid == 0) {
-        // v = sum w [r ; p x r],  (p x r) from the antisymmetric part of p r^T
+        // v = sum w [r ; x' x r],  (x' x r) from the antisymmetric part of x' r^T
         v[0] = rr[0]; v[1] = rr[1]; v[2] = rr[2];
         v[3] = PR[1 * 3 + 2] - PR[2 * 3 + 1];
         v[4] = PR[2 * 3 + 0] - PR[0 * 3 + 2];
@@ -336,27 +359,37 @@ __global__ __launch_bounds__(256) void reduce_expand_kernel(const int* __restric
     const int i = tid / 6, j = tid % 6;
     double s = 0.0;
 #pragma unroll
-    for (int k = 0; k < 6; ++k) s += S[i * 6 + k] * Ad[k * 6 + j];
-    T1[tid] = s;                 // S Ad
-    T2[tid] = S[tid] - X[tid];   // S - X
+    for (int k = 0; k < 6; ++k) s += S[i * 6 + k] * R6[k * 6 + j];
+    T1[tid] = s;                                                    // S R6
+    T2[tid] = S[tid] - X[tid];                                      // Z = S - X
+    T3[tid] = S[tid] - X[tid] - X[j * 6 + i] + Y[tid];              // D = S - X - X^T + Y
   }
+  __syncthreads();
+  double zl = 0.0, dl = 0.0;
+  if (tid < 36) {
+    const int i = tid / 6, j = tid % 6;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) { zl += T2[i * 6 + k] * Lm[j * 6 + k]; dl += T3[i * 6 + k] * Lm[j * 6 + k]; }
+  }
+  __syncthreads();
+  if (tid < 36) { T2[tid] = zl; T3[tid] = dl; }                     // Z L^T, D L^T
   __syncthreads();
   double* o = out + (size_t)e * NB;
   if (tid < 36) {
     const int i = tid / 6, j = tid % 6;
-    double hss = 0.0, hsd = 0.0;
+    double hss = 0.0, hsd = 0.0, hdd = 0.0;
 #pragma unroll
-    for (int k = 0; k < 6; ++k) { hss += Ad[k * 6 + i] * T1[k * 6 + j]; hsd += Ad[k * 6 + i] * T2[k * 6 + j]; }
-    H[i * 12 + j] = hss;                                                             // H_ss = Ad^T S Ad
-    H[i * 12 + 6 + j] = -hsd;                                                        // H_sd = -Ad^T (S - X)
-    H[(6 + i) * 12 + 6 + j] = S[i * 6 + j] - X[i * 6 + j] - X[j * 6 + i] + Y[i * 6 + j];  // H_dd
+    for (int k = 0; k < 6; ++k) { hss += R6[k * 6 + i] * T1[k * 6 + j]; hsd += R6[k * 6 + i] * T2[k * 6 + j]; hdd += Lm[i * 6 + k] * T3[k * 6 + j]; }
+    H[i * 12 + j] = hss;                       // H_ss = R6^T S R6
+    H[i * 12 + 6 + j] = -hsd;                  // H_sd = -R6^T (S - X) L^T
+    H[(6 + i) * 12 + 6 + j] = hdd;             // H_dd = L (S - X - X^T + Y) L^T
   } else if (tid < 42) {
     const int i = tid - 36;
-    double s = 0.0;
+    double s = 0.0, l = 0.0;
 #pragma unroll
-    for (int k = 0; k < 6; ++k) s += Ad[k * 6 + i] * v[k];
-    o[78 + i] = s;           // g_s = Ad^T v
-    o[84 + i] = -v[i];       // g_d = -v
+    for (int k = 0; k < 6; ++k) { s += R6[k * 6 + i] * v[k]; l += Lm[i * 6 + k] * v[k]; }
+    o[78 + i] = s;           // g_s = R6^T v
+    o[84 + i] = -l;          // g_d = -L v
   } else if (tid == 42) {
     o[90] = count[e] > 0 ? mm[PLANE ? 27 : 28] : 0.0;
   }

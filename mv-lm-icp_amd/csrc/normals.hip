@@ -149,19 +149,21 @@ __global__ __launch_bounds__(NT) void normals_kernel(NormJob job) {
     const bool full = bj(K - 1) >= 0;
     if ((full && m > 0.0 && bd(K - 1) < m * m) || r >= rmax) break;
   }
-  // PCA of the neighbours (common.h:331-346)
+  // PCA of the neighbours (common.h:331-346).  Coordinates are taken relative to the point itself before the centroid is formed: the covariance is
+  // the same, but a coordinate that all neighbours share (a range image's constant depth, an axis-aligned wall) then cancels EXACTLY — the mean of the
+  // raw coordinates need not reproduce it (ten times 0.1 is not 1) and would leave a ~1e-17 residue that tilts the normal of an exact plane off the axis.
   double mx = 0, my = 0, mz = 0;
   int kk = 0;
 #pragma unroll
   for (int t = 0; t < KMAX; ++t)
-    if (t < K && bj(t) >= 0) { const PointRec p = job.srec[bj(t)]; mx += p.x; my += p.y; mz += p.z; ++kk; }
+    if (t < K && bj(t) >= 0) { const PointRec p = job.srec[bj(t)]; mx += p.x - me.x; my += p.y - me.y; mz += p.z - me.z; ++kk; }
   mx /= kk; my /= kk; mz /= kk;
   double c00 = 0, c01 = 0, c02 = 0, c11 = 0, c12 = 0, c22 = 0;
 #pragma unroll
   for (int t = 0; t < KMAX; ++t)
     if (t < K && bj(t) >= 0) {
       const PointRec p = job.srec[bj(t)];
-      const double x = p.x - mx, y = p.y - my, z = p.z - mz;
+      const double x = (p.x - me.x) - mx, y = (p.y - me.y) - my, z = (p.z - me.z) - mz;
       c00 += x * x; c01 += x * y; c02 += x * z; c11 += y * y; c12 += y * z; c22 += z * z;
     }
   double nv[3];

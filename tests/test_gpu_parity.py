@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import mvicp
+import normcheck
 import orclib
 from mvicp import lib as L
 from mvicp import synth
@@ -1188,7 +1189,8 @@ def test_random_graphs_costs_and_parameterizations(eng, orc, seed):
 def test_random_shapes_knn_lists_equal_nanoflann(eng, refnn, seed):
     """Row f1 beyond the Bunny lattice: k-NN lists of random clouds — blobs, jittered and exact lattices (ties at every place), planes,
     clusters, duplicated points; 12..3000 points, k = 3 / 10 / 16 — element for element against the real nanoflann's knnSearch
-    (tie order = the order its tree visits the leaves, csrc/kdvisit.h)."""
+    (tie order = the order its tree visits the leaves, csrc/kdvisit.h).  The normals computed from those lists are judged on every point by
+    their Rayleigh residual on the long-double covariance of the set (bar: 32 x numpy's fp64 route, tests/normcheck.py)."""
     if refnn is None:
         pytest.skip("oracle/_ref was not built")
     rng = np.random.default_rng(900 + seed)
@@ -1207,6 +1209,8 @@ def test_random_shapes_knn_lists_equal_nanoflann(eng, refnn, seed):
     myd = (e[:, :, 0] * e[:, :, 0] + e[:, :, 1] * e[:, :, 1]) + e[:, :, 2] * e[:, :, 2]
     assert np.array_equal(myd, gd), seed
     assert np.array_equal(knn, gi), (seed, int((~np.all(knn == gi, axis=1)).sum()))
+    # ... and the normals of those sets: every point, degenerate neighbourhoods included, by the Rayleigh residual (tests/normcheck.py)
+    normcheck.check(pts, knn, nrm, "random shapes seed %d (%s, k = %d)" % (seed, kind, k))
 
 
 @pytest.mark.parametrize("factor", [0.0, 1.0, 4.0])
