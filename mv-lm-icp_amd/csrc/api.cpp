@@ -153,9 +153,9 @@ void free_graph(mvicp_ctx* c) {
   dev_free(c->d_esrc); dev_free(c->d_edst); dev_free(c->d_cap_off); dev_free(c->d_count);
   dev_free(c->d_ctl); c->d_nsrc = nullptr; c->d_a = nullptr; c->d_xf = nullptr; c->d_rel = nullptr; c->d_rel2 = nullptr; c->d_dirty = nullptr;
   dev_free(c->d_nn_idx); dev_free(c->d_nn_d2); dev_free(c->d_nn_lb); dev_free(c->d_first); dev_free(c->d_second);
-  dev_free(c->d_sblock_off); dev_free(c->d_sel_keys1); dev_free(c->d_sel_keys2); c->n_sblocks = 0;
-  dev_free(c->d_cd2); dev_free(c->d_qpos); dev_free(c->d_dirty_slots); dev_free(c->d_dslot_off); dev_free(c->d_stream); dev_free(c->d_cblock_off); dev_free(c->d_cblock_cnt); if (c->d_sel_state) (void)hipFree(c->d_sel_state);
-  c->d_sel_state = nullptr; dev_free(c->d_sel_hist); dev_free(c->d_median); dev_free(c->d_chunk_edge); dev_free(c->d_chunk_start);
+  dev_free(c->d_sblock_off); dev_free(c->d_sel_keys1); c->n_sblocks = 0;
+  dev_free(c->d_cd2); dev_free(c->d_qpos); dev_free(c->d_dirty_slots); dev_free(c->d_dslot_off); dev_free(c->d_stream); dev_free(c->d_cblock_off); dev_free(c->d_cblock_cnt);
+  dev_free(c->d_sel_hist); dev_free(c->d_median); dev_free(c->d_chunk_edge); dev_free(c->d_chunk_start);
   dev_free(c->d_chunk_first); dev_free(c->d_partials); dev_free(c->d_out);
   if (c->h_pin) (void)hipHostFree(c->h_pin);
   c->h_pin = nullptr; c->h_pin_doubles = 0; c->d_res_host = nullptr; c->d_blocks_host = nullptr; c->lin_out = nullptr;
@@ -930,13 +930,15 @@ int mvicp_set_graph(mvicp_ctx* c, int n_edges, const int* src, const int* dst) t
   MV_HIP(hipMemset(c->d_dirty_slots, 0, sizeof(int) * std::max<size_t>((size_t)c->n_dslots, 1)));   // dirty_reduce_kernel re-zeroes what it reads
   MV_HIP(hipMemcpy(c->d_dslot_off, c->dslot_off.data(), sizeof(int) * (E + 1), hipMemcpyHostToDevice));
   MV_CHECK(dev_alloc(&c->d_cblock_off, E + 1)); MV_CHECK(dev_alloc(&c->d_cblock_cnt, (size_t)c->n_cblocks));
-  MV_HIP(hipMalloc(&c->d_sel_state, 16 * 3 * (size_t)std::max(E, 1))); MV_CHECK(dev_alloc(&c->d_sel_hist, (size_t)E * (3 * 2048 + 5)));
+  MV_CHECK(dev_alloc(&c->d_sel_hist, (size_t)E * (2048 + 2)));   // cnt_lt [E] | cnt_mid [E] | hist [E][2048] (corr.hip); zeroed here, kept zero by the select kernels
+  MV_HIP(hipMemset(c->d_sel_hist, 0, sizeof(unsigned int) * std::max<size_t>((size_t)E * (2048 + 2), 1)));
+  c->sel_scratch_clean = true; c->sel_result_valid = false; c->sel_result_armed = false;
   c->sblock_off.assign(E + 1, 0);
   for (int e = 0; e < E; ++e) c->sblock_off[e + 1] = c->sblock_off[e] + (int)(((c->owned[e] ? c->frames[src[e]].n : 0) + kSelBlock - 1) / kSelBlock);
   c->n_sblocks = c->sblock_off[E];
   MV_CHECK(dev_alloc(&c->d_sblock_off, (size_t)E + 1));
   MV_HIP(hipMemcpy(c->d_sblock_off, c->sblock_off.data(), sizeof(int) * (E + 1), hipMemcpyHostToDevice));
-  MV_CHECK(dev_alloc(&c->d_sel_keys1, cap)); MV_CHECK(dev_alloc(&c->d_sel_keys2, cap));
+  MV_CHECK(dev_alloc(&c->d_sel_keys1, cap));
   // the grid kernel's far-query list (worst case every query): allocated here, not lazily inside the first grid launch — a
   // 100 MB hipMalloc in the middle of an ICP loop costs milliseconds
   if (cap > c->far_cap) {
@@ -990,7 +992,7 @@ int mvicp_set_graph(mvicp_ctx* c, int n_edges, const int* src, const int* dst) t
     c->d_spec2_host = (double*)dp + c->pin_spec2_off;
     c->d_blocks2_host = (double*)dp + c->pin_blocks2_off;
   }
-  c->spec_ready = false; c->spec_arm = false; c->bracket_counters_clean = false;
+  c->spec_ready = false; c->spec_arm = false;
   c->spec2_ready = false; c->spec2_armed = false; c->last_cand_poses.clear();
   c->prev_xf.assign((size_t)E * 24, 0.0);
   if (!c->h_census) MV_HIP(hipHostMalloc((void**)&c->h_census, 8 * sizeof(unsigned long long), hipHostMallocDefault));
@@ -1010,6 +1012,7 @@ static void forget_history(mvicp_ctx* c) {
   c->qpos_valid.assign(E, 0);
   for (int e = 0; e < E; ++e) c->corr_epoch[e] = ++c->epoch_counter;
   c->sel_med1.assign(E, -1.0); c->sel_med2.assign(E, -1.0);
+  c->sel_result_valid = false;
   c->spec_ready = false; c->spec_arm = false; c->spec_flags_valid = false;
   c->spec2_ready = false; c->spec2_armed = false; c->last_cand_poses.clear();
   c->have_corr = false;
@@ -1033,6 +1036,7 @@ int mvicp_reset_history(mvicp_ctx* c) try {
 //   prev_q / prev_xf[e]           the per-edge loop below                  dM, dv of the temporal cache; bit-identical transform  every search rewrites them
 //   list_valid[e], explicit_list  end of the NN stage / set_correspondences  the edge's compacted list may be maintained in place  set_correspondences, recompute_normals (dst), reset
 //   sel_med1/2[e]                 after the wait below                     one-pass bracket select once the median has settled   inactive edge, set_correspondences, reset
+//   sel_result_valid, _armed      this call's end (single rank)            no select launch in a search in which no list can change   any search that does not return OK, set_graph, set_correspondences, reset
 //   auto_prev_dist, auto_last_method   the AUTO policy block               hand-over tile -> grid, "already handed over"          set_graph, reset
 //   corr_tie_seen, corr_far_seen  after the wait below (own launches only) tie fix-up / far launch may be skipped at a fixed point  any search that is not bit-identical; reset
 //   prev_grid_kernel              end of the NN stage                      corr_far_seen describes the last search                every search rewrites it
@@ -1063,7 +1067,18 @@ int mvicp_correspond(mvicp_ctx* c, const double* poses, const unsigned char* fix
   return MVICP_OK;
 } MVICP_GUARD_ABI
 
+static int correspond_body(mvicp_ctx* c, const double* poses, const unsigned char* fixed, float thresh, int nn_method, int* counts, float* weights, bool* tie_unresolved);
+
 static int correspond_once(mvicp_ctx* c, const double* poses, const unsigned char* fixed, float thresh, int nn_method, int* counts, float* weights, bool* tie_unresolved) {
+  // whatever way a search ends other than OK (an error status, an exception): the next one neither reuses its select result nor trusts the
+  // self-cleaning select scratch (a kernel that never ran has not re-zeroed what its predecessor filled)
+  struct Guard { mvicp_ctx* c; bool ok = false; ~Guard() { if (!ok) { c->sel_result_valid = false; c->sel_scratch_clean = false; } } } guard{c};
+  const int st = correspond_body(c, poses, fixed, thresh, nn_method, counts, weights, tie_unresolved);
+  guard.ok = st == MVICP_OK;
+  return st;
+}
+
+static int correspond_body(mvicp_ctx* c, const double* poses, const unsigned char* fixed, float thresh, int nn_method, int* counts, float* weights, bool* tie_unresolved) {
   if (!poses) { set_error("poses is null"); return MVICP_ERR_ARG; }
   if (c->E == 0) { set_error("no graph: call mvicp_set_graph first"); return MVICP_ERR_STATE; }
   const int E = c->E;
@@ -1208,7 +1223,7 @@ static int correspond_once(mvicp_ctx* c, const double* poses, const unsigned cha
       for (int e = 0; e < E; ++e) if (c->active[e] && c->list_valid[e]) dirty[e] = 0;
     std::memcpy(hd, dirty.data(), sizeof(int) * E);
   }
-  // One-pass bracket select (corr.hip) instead of the 3-pass radix select: only when EVERY active edge of this rank has a
+  // One-pass bracket select (corr.hip) instead of the two-pass anchored select: only when EVERY active edge of this rank has a
   // median that has settled (last two rounds within 0.1 %); the bracket is +-0.6 % in d2 around the last one.
   bool use_bracket = c->sel_bracket && c->have_corr;
   {
@@ -1263,6 +1278,11 @@ static int correspond_once(mvicp_ctx* c, const double* poses, const unsigned cha
     // paired launch (option lin_pair): its relative transforms lie between region 1 and rel, so they ride on the same upload
     if (spec2_plan && c->lin_pair) fill_rel_into(c, c->last_cand_poses.data(), hx + c->ctl_rel2_off);
   }
+  // ... and the median select neither (single rank): the median of an edge is a function of its d2 list and its count, nothing rewrites either in such
+  // a search, and the last search's select finished — d_median, d_a (the select's own values, or the host's bit-identical mirror uploaded by an
+  // evaluation since) and the mapped (count, median d2) pairs ARE this search's result.  Only the "armed" slot is this search's own: the host writes
+  // it.  With N > 1 ranks that tail lives in the exchanged buffer and is summed in place, so it is rewritten every search.
+  const bool sel_skip = !exchange && c->sel_reuse && nothing_can_change && c->sel_result_valid && (!c->spec_arm || c->sel_result_armed);
   if (method != MVICP_NN_BRUTE && method != MVICP_NN_GRID && method != MVICP_NN_TILE) { set_error("unknown nn_method %d", nn_method); return MVICP_ERR_ARG; }   // (an argument error: the same on every rank)
   bool all_unchanged = true;
   for (int e = 0; e < E; ++e) { if (!unchanged[e]) all_unchanged = false; if (c->active[e]) c->qpos_valid[e] = 0; }   // (set again once the NN stage is queued)
@@ -1302,7 +1322,8 @@ static int correspond_once(mvicp_ctx* c, const double* poses, const unsigned cha
     MV_CHECK(launch_compact(c, bound));
     MV_CHECK(launch_gather_stream(c));
   }
-  return use_bracket ? launch_select_bracket(c) : launch_select_median(c);
+  if (sel_skip) { c->h_pin[c->pin_res_off + 2 * (size_t)E] = c->spec_arm ? 1.0 : 0.0; return MVICP_OK; }   // (nothing on the device writes the mapped results in this search)
+  return use_bracket ? launch_select_bracket(c) : launch_select_median(c, bound);
   };   // local_search
   if (st_local == MVICP_OK) st_local = local_search();
   if (st_local != MVICP_OK && !exchange) { c->spec_flags_valid = false; return st_local; }
@@ -1353,7 +1374,7 @@ static int correspond_once(mvicp_ctx* c, const double* poses, const unsigned cha
     }
   }
   mark("host.corr.post_launch");
-  // (count, median d2) per edge arrive in mapped host memory, written by select_final_kernel (single rank), or summed over ranks
+  // (count, median d2) per edge arrive in mapped host memory, written by bracket_final_kernel (single rank), or summed over ranks
   // behind the blocks; weight = (float)(1.5 * sqrt(median d2))  (frame.cpp:168-176)
   if (st_q == MVICP_OK) st_q = stream_wait(c);
   if (st_q != MVICP_OK) { c->spec_flags_valid = false; c->spec_arm = false; return st_q; }
@@ -1382,7 +1403,7 @@ static int correspond_once(mvicp_ctx* c, const double* poses, const unsigned cha
     for (int e = 0; e < E; ++e) if (hr[2 * e + 1] < 0.0) redo = true;
     if (redo) {
       spec_bad = true;   // the queued evaluation used the scales of the failed select
-      int st_r = launch_select_median(c);
+      int st_r = launch_select_median(c, bound);
       if (exchange) {
         int st_x = MVICP_OK;
         if (st_r != MVICP_OK) {   // same protocol as above: the second (tail-only) collective is entered with a poisoned armed slot
@@ -1429,6 +1450,8 @@ static int correspond_once(mvicp_ctx* c, const double* poses, const unsigned cha
   c->spec_ready = c->spec_arm && !spec_bad;
   c->spec2_ready = c->spec_ready && c->spec2_armed;   // (same scales, same lists: valid whenever the first one is)
   c->spec2_armed = false;
+  if (!sel_skip) c->sel_result_armed = c->spec_arm;   // (a skipped select leaves d_a and its mapped copy as they were)
+  c->sel_result_valid = !exchange;
   c->spec_arm = false;
   double* ha = c->h_pin + c->ctl_r2_off + (size_t)E * kEdgeRel;   // `a` slice of region 2: uploaded with rel by the next evaluation
   for (int e = 0; e < E; ++e) {
@@ -1569,6 +1592,7 @@ int mvicp_set_correspondences(mvicp_ctx* c, int edge, int n, const int* first, c
   c->list_valid[edge] = 0; c->explicit_list[edge] = 1; c->export_valid = false;
   c->qpos_valid[edge] = 0; c->corr_epoch[edge] = ++c->epoch_counter;
   c->sel_med1[edge] = c->sel_med2[edge] = -1.0;
+  c->sel_result_valid = false;   // d_count, d_cd2 and d_a of this edge are no longer the last select's
   const double a = (double)weight;
   MV_HIP(hipMemcpy(c->d_count + edge, &n, sizeof(int), hipMemcpyHostToDevice));
   {   // an explicit list is arbitrary (repeats, any order): never the identity list the linearize kernel may shortcut
@@ -1657,6 +1681,7 @@ int mvicp_set_option(mvicp_ctx* c, const char* name, double value) try {
   if (std::strcmp(name, "nn_census") == 0) { c->nn_census = value != 0.0; return MVICP_OK; }
   if (std::strcmp(name, "nn_skip_far") == 0) { c->nn_skip_far = value != 0.0; return MVICP_OK; }
   if (std::strcmp(name, "sel_bracket") == 0) { c->sel_bracket = value != 0.0; return MVICP_OK; }
+  if (std::strcmp(name, "sel_reuse") == 0) { c->sel_reuse = value != 0.0; return MVICP_OK; }   // 0: launch the median select in every search
   if (std::strcmp(name, "prune_rho") == 0) { c->prune_rho = value; return MVICP_OK; }
   if (std::strcmp(name, "grid_curve") == 0) { c->grid_curve = (int)value; return MVICP_OK; }   // takes effect at the next mvicp_set_frame
   if (std::strcmp(name, "auto_settle") == 0) { c->auto_settle = value; return MVICP_OK; }

@@ -182,13 +182,17 @@ struct mvicp_ctx {
   std::vector<int> cblock_off;      // E+1
   int* d_cblock_off = nullptr; int* d_cblock_cnt = nullptr;
   // select scratch
-  void* d_sel_state = nullptr; unsigned int* d_sel_hist = nullptr; double* d_median = nullptr;
+  unsigned int* d_sel_hist = nullptr;   // cnt_lt [E] | cnt_mid [E] | hist [E][2048]: every kernel re-zeroes what it used (no memset in a search)
+  double* d_median = nullptr;
   int n_sblocks = 0; std::vector<int> sblock_off; int* d_sblock_off = nullptr;   // kSelBlock keys per workgroup
   double* d_sel_lohi = nullptr;      // view into the control block: per edge the bracket [lo, hi] (d2) of the one-pass select
   std::vector<double> sel_med1, sel_med2;   // per owned edge: median d2 of the last / the one-before-last round (< 0: unknown)
   bool sel_bracket = true;           // option: use the one-pass bracket select once the medians have settled
-  bool bracket_counters_clean = false;   // the bracket pass's two per-edge counters are zero on the device (left so by bracket_final_kernel)
-  double* d_sel_keys1 = nullptr; double* d_sel_keys2 = nullptr;                  // compact key buffers of passes B and C (total_cap each)
+  bool sel_scratch_clean = false;    // d_sel_hist is all zero on the device: after mvicp_set_graph's memset and after every search that returned OK
+  bool sel_reuse = true;             // option "sel_reuse": no select launch in a single-rank search in which no list can change (0: launch it every search)
+  bool sel_result_valid = false;     // the last search on this context finished its select: d_median, d_a and the mapped (count, median d2) pairs are that select's
+  bool sel_result_armed = false;     // ... and that select also wrote the SoftLOne scales (d_a and their mapped copy)
+  double* d_sel_keys1 = nullptr;     // compact key buffer of the bracket pass (total_cap)
   // linearize chunks
   bool lin_interleave = true;       // launch order of the linearize workgroups: chunks of the edges that share a source cloud interleaved in groups of 8 (api.cpp mvicp_set_graph)
   bool lin_share_p = true;          // linearize reads p from the sorted source cloud when an edge's list is the identity (option "lin_share_p")
@@ -205,7 +209,7 @@ struct mvicp_ctx {
   // pinned (device-mapped) host staging: [control-block mirror | blocks E x 91 | results E x 2 | misc]
   double* h_pin = nullptr; size_t h_pin_doubles = 0;
   size_t pin_blocks_off = 0, pin_res_off = 0, pin_misc_off = 0;
-  double* d_res_host = nullptr;     // device view of the results region: (count, median d2) per edge, written by select_final_kernel
+  double* d_res_host = nullptr;     // device view of the results region: (count, median d2) per edge, written by bracket_final_kernel
   double* d_blocks_host = nullptr;  // device view of the blocks region: single-rank evaluations write the E x 91 blocks straight to the host
   double* lin_out = nullptr;        // where the next launch_linearize puts the E x 91 blocks (d_out or d_blocks_host)
   // Speculative first evaluation: mvicp_correspond queues the linearization the NEXT mvicp_optimize will ask for first (same poses,
@@ -345,7 +349,7 @@ int overlap_census(mvicp_ctx* c, const double* xf, double B2, double scale, int 
 void free_overlap(mvicp_ctx* c);
 int launch_compact(mvicp_ctx* c, double d2_bound);                                    // corr.hip
 int launch_gather_stream(mvicp_ctx* c);
-int launch_select_median(mvicp_ctx* c);
+int launch_select_median(mvicp_ctx* c, double d2_bound);   // two-pass select anchored at the acceptance bound: any key set, exact
 int launch_export(mvicp_ctx* c);           // export.hip: every exportable edge's list -> reference-order triples in pinned memory (async; caller waits)
 int launch_select_bracket(mvicp_ctx* c);   // one-pass select around last round's medians (d_sel_lohi); flags edges it cannot answer
 int launch_linearize(mvicp_ctx* c, int plane, int robust);                            // linearize.hip

@@ -1,8 +1,8 @@
-// K3/K4 — cutoff filter + stable compaction, packed-stream gather, exact median (compacting radix select / bracket select).
+// K3/K4 — cutoff filter + stable compaction, packed-stream gather, exact median (anchored two-pass select / bracket select).
 //
 // Replaces the tail of Frame::computeClosestPointsToNeighbours (src/internal/frame.cpp:156-176):
 //   if (sqrt(d2) < thresh) push {k, idx, dist}        -> flag / exclusive scan / scatter, ascending k
-//   nth_element(dists, size/2); weight = 1.5 * median -> radix select on the fp64 bit pattern of d2
+//   nth_element(dists, size/2); weight = 1.5 * median -> select on the fp64 bit pattern of d2
 // The acceptance test is evaluated as `d2 < bound` where the host has computed `bound` = the smallest
 // double whose correctly rounded sqrt is >= (double)thresh, so the decision is bit-identical to the
 // reference's `sqrt(d2) < thresh` without a device sqrt.  sqrt is monotone, so the median of the
@@ -12,6 +12,8 @@
 // LM evaluations re-read up to ~100 times: SoA p (3) | n (3) | c = n . q | q (3), 10 arrays, of which point-to-plane
 // streams 7 (56 B per correspondence) and point-to-point 6 — instead of 2-3 random 24-B gathers per evaluation.
 #include "common.h"
+
+#include <cstring>
 
 namespace mvicp {
 
@@ -180,18 +182,24 @@ __global__ __launch_bounds__(NT) void gather_kernel(const int* __restrict__ cblo
   }
 }
 
-// ---- radix select over the fp64 patterns of the accepted d2: 3 streaming passes x 11 bits + an in-LDS finish ------------
-// d2 >= 0, so bit 63 is clear and the unsigned pattern is monotone in the value.  Digits, MSB first:
-//   A = bits 62..52 (the exponent), B = bits 51..41, C = bits 40..30, then 30 low bits resolved by one workgroup per edge.
-// Pass A histograms every key.  Pass B histograms the keys whose exponent is the picked one AND appends them to a
-// compact buffer (10-30 % of the list); pass C reads only that buffer, histograms the keys matching the 22-bit prefix and
-// appends those (a few dozen per edge) to a second buffer, which the finishing workgroup resolves with three 10-bit
-// passes in LDS.  Two full reads of the list instead of eight; every step is exact for any input (all-equal keys just
-// make the compact buffers as long as the list).  The digit of a pass is picked by a one-workgroup-per-edge kernel between
-// the passes (a "last workgroup picks" ticket scheme needs an agent-scope fence per workgroup, which on the 8-XCD part
-// writes back / invalidates L2 and made the select 4x slower).
+// ---- exact median of the accepted d2 of an edge: select on the fp64 bit pattern, two streaming passes ---------------------
+// d2 >= 0, so bit 63 is clear and the unsigned pattern is monotone in the value.  Every accepted key lies below the acceptance
+// bound, so the first digit is anchored there instead of spending 11 bits on an exponent field that hardly varies:
+//   bin(key) = clamp(2047 - ((kb >> SH) - (key >> SH)), 0, 2047),   kb = pattern of the bound, SH = 46: a bin is 1/64 octave of d2,
+// 2048 bins reach 32 octaves below the bound; whatever lies further down shares bin 0, whatever lies at or above the bound bin 2047.
+// The function is monotone non-decreasing in the key — all exactness needs.  select_hist_kernel histograms every key (one read),
+// select_pick_kernel (one workgroup per edge; a "last workgroup picks" ticket scheme needs an agent-scope fence per workgroup, which
+// on the 8-XCD part writes back / invalidates L2 and made the select 4x slower) finds the bin that holds rank size/2 and writes the
+// bin's smallest and largest pattern as the edge's bracket; bracket_pass_kernel / bracket_final_kernel (below) then count the keys
+// under the bracket, compact the bin (a second read) and select inside it — by construction the rank is inside.  Exact for any
+// input: all-equal keys or a cutoff far above every key only make the compacted bin as long as the list.
 constexpr int kSelBins = 2048;
-struct SelState { unsigned long long prefix; int k; int pad; };
+constexpr int kSelShift = 46;
+
+__device__ __forceinline__ unsigned int sel_bin(unsigned long long key, long long kbq) {
+  const long long d = kbq - (long long)(key >> kSelShift);
+  return d <= 0 ? (unsigned int)(kSelBins - 1) : d >= kSelBins - 1 ? 0u : (unsigned int)(kSelBins - 1 - d);
+}
 
 // Workgroup-wide: which of `nbins` bins (nbins = NT * PER) holds rank k, and how many keys sit in the bins below it.
 // `get(bin)` returns the count of a bin.  All NT threads must call; result valid in every thread.
@@ -218,110 +226,66 @@ __device__ __forceinline__ void pick_bin(F get, unsigned int k, int* __restrict_
   __syncthreads();
 }
 
-// PASS 0: keys = cd2 (count[e]), no filter, no output.   PASS 1: keys = cd2, filter on digit A, output -> out_keys/out_cnt.
-// PASS 2: keys = in_keys (in_cnt[e]), filter on digits A,B, output -> out_keys/out_cnt.
-template <int PASS>
-__global__ __launch_bounds__(NT) void select_pass_kernel(const int* __restrict__ sblock_off, int E, const int* __restrict__ count,
-                                                         const long long* __restrict__ cap_off, const double* __restrict__ in_keys,
-                                                         const unsigned int* __restrict__ in_cnt, unsigned int* __restrict__ hist,
-                                                         const SelState* __restrict__ state,
-                                                         double* __restrict__ out_keys, unsigned int* __restrict__ out_cnt) {
-  constexpr int SPT = kSelBlock / NT;                       // keys per thread
-  constexpr int SHIFT = PASS == 0 ? 52 : PASS == 1 ? 41 : 30;
+// histogram of the anchored first digit: one streaming read of the keys (16 B per lane per load), counted in LDS, one global atomic
+// per non-empty bin and workgroup.  (The keys of a wave spread over many bins — hundreds are populated on a registration's d2 — so
+// the interleaved LDS copies the exponent digit needed are gone.)
+__global__ __launch_bounds__(NT) void select_hist_kernel(const int* __restrict__ sblock_off, int E, const int* __restrict__ count,
+                                                         const long long* __restrict__ cap_off, const double* __restrict__ keys,
+                                                         long long kbq, unsigned int* __restrict__ hist) {
+  constexpr int SPT = kSelBlock / NT;   // keys per thread, two per step
   __shared__ unsigned int lh[kSelBins];
-  __shared__ int wave_tot[NT / 64];
-  __shared__ unsigned int sh_base;
   const int b = blockIdx.x;
   const int e = find_edge(sblock_off, E, b);
   const int lb = b - sblock_off[e];
   const int cnt = count[e];
-  const int n_in = PASS == 2 ? (cnt > 0 ? (int)in_cnt[e] : 0) : cnt;
-  if ((long long)lb * kSelBlock >= n_in) return;
-  SelState st;
-  st.prefix = 0ull; st.k = cnt / 2; st.pad = 0;              // dists.begin() + size()/2  (frame.cpp:166)
-  if (PASS > 0) st = state[(size_t)(PASS - 1) * E + e];
+  if ((long long)lb * kSelBlock >= cnt) return;
   for (int i = threadIdx.x; i < kSelBins; i += NT) lh[i] = 0u;
   __syncthreads();
-  const long long base = cap_off[e];
-  unsigned long long keys[SPT];
-  int nmatch = 0;
+  const long long base = cap_off[e];   // multiple of 64 keys: 16-B aligned pairs
 #pragma unroll
-  for (int i = 0; i < SPT; ++i) {
-    const int pos = lb * kSelBlock + i * NT + threadIdx.x;
-    bool match = pos < n_in;
-    unsigned long long key = 0ull;
-    if (match) {
-      key = (unsigned long long)__double_as_longlong(__builtin_nontemporal_load(&in_keys[base + pos]));
-      if (PASS > 0) match = (key >> (SHIFT + 11)) == (st.prefix >> (SHIFT + 11));
+  for (int i = 0; i < SPT / 2; ++i) {
+    const int pos = lb * kSelBlock + 2 * (i * NT + threadIdx.x);
+    if (pos + 1 < cnt) {
+      typedef double d2v __attribute__((ext_vector_type(2)));
+      const d2v v = __builtin_nontemporal_load(reinterpret_cast<const d2v*>(keys + base + pos));
+      atomicAdd(&lh[sel_bin((unsigned long long)__double_as_longlong(v.x), kbq)], 1u);
+      atomicAdd(&lh[sel_bin((unsigned long long)__double_as_longlong(v.y), kbq)], 1u);
+    } else if (pos < cnt) {
+      atomicAdd(&lh[sel_bin((unsigned long long)__double_as_longlong(keys[base + pos]), kbq)], 1u);
     }
-    const unsigned int bin = (unsigned int)(key >> SHIFT) & (kSelBins - 1);
-    if (PASS == 0) {
-      // exponent digit: the 64 keys of a wave share a handful of exponents, so plain LDS atomics would serialise on a few
-      // addresses.  Exponent fields 768..1023 (values in [2^-255, 2): every realistic squared distance) are counted in
-      // EIGHT interleaved copies of a 256-bin window, picked by the lane number; anything else (exact zeros, huge cutoffs)
-      // is rare and goes straight to the global histogram, one atomic per distinct value per wave.
-      const int lane = threadIdx.x & 63;
-      const bool inwin = match && bin >= 768u && bin < 1024u;
-      if (inwin) atomicAdd(&lh[(bin & 255u) | ((unsigned int)(lane & 7) << 8)], 1u);
-      unsigned long long todo = __ballot(match && !inwin);
-      while (todo) {
-        const int leader = __ffsll((long long)todo) - 1;
-        const unsigned int lbin = (unsigned int)__builtin_amdgcn_readlane((int)bin, leader);
-        const unsigned long long same = __ballot(match && !inwin && bin == lbin) & todo;
-        if (lane == leader) atomicAdd(&hist[((size_t)PASS * E + e) * kSelBins + lbin], (unsigned int)__popcll(same));
-        todo &= ~same;
-      }
-    } else if (match) {
-      atomicAdd(&lh[bin], 1u);
-    }
-    keys[i] = key;
-    if (PASS > 0 && match) { keys[i] |= 1ull << 63; ++nmatch; }   // bit 63 is free (d2 >= 0): mark the keys to keep
-  }
-  if (PASS > 0) {
-    int total;
-    int off = block_exclusive_scan(nmatch, wave_tot, &total);
-    if (threadIdx.x == 0) sh_base = total ? atomicAdd(&out_cnt[e], (unsigned int)total) : 0u;
-    __syncthreads();
-    off += (int)sh_base;
-#pragma unroll
-    for (int i = 0; i < SPT; ++i)
-      if (keys[i] >> 63) out_keys[base + off++] = __longlong_as_double((long long)(keys[i] & ~(1ull << 63)));
   }
   __syncthreads();
-  if (PASS == 0) {
-    unsigned int v = 0;   // fold the 8 copies of the exponent window
-#pragma unroll
-    for (int cpy = 0; cpy < 8; ++cpy) v += lh[cpy * 256 + threadIdx.x];
-    if (v) atomicAdd(&hist[((size_t)PASS * E + e) * kSelBins + 768 + threadIdx.x], v);
-  } else {
-    for (int i = threadIdx.x; i < kSelBins; i += NT) {
-      const unsigned int v = lh[i];
-      if (v) atomicAdd(&hist[((size_t)PASS * E + e) * kSelBins + i], v);
-    }
+  for (int i = threadIdx.x; i < kSelBins; i += NT) {
+    const unsigned int v = lh[i];
+    if (v) atomicAdd(&hist[(size_t)e * kSelBins + i], v);
   }
 }
 
-// digit pick of pass PASS (0 = A, 1 = B): one workgroup per edge over the finished histogram
-template <int PASS>
-__global__ __launch_bounds__(NT) void select_pick_kernel(int E, const int* __restrict__ count, const unsigned int* __restrict__ hist,
-                                                         SelState* __restrict__ state) {
-  constexpr int SHIFT = PASS == 0 ? 52 : 41;
+// one workgroup per edge over the finished histogram: the bin of rank size/2 (dists.begin() + size()/2, frame.cpp:166) becomes the
+// edge's bracket [smallest, largest pattern of the bin]; the row is left zeroed for the next search.
+__global__ __launch_bounds__(NT) void select_pick_kernel(int E, const int* __restrict__ count, unsigned int* __restrict__ hist, long long kbq,
+                                                         double* __restrict__ lohi) {
   __shared__ int wave_tot[NT / 64];
   __shared__ int sh_pick[2];
   const int e = blockIdx.x;
   const int cnt = count[e];
-  if (cnt <= 0) return;
-  SelState st;
-  st.prefix = 0ull; st.k = cnt / 2; st.pad = 0;              // dists.begin() + size()/2  (frame.cpp:166)
-  if (PASS > 0) st = state[(size_t)(PASS - 1) * E + e];
-  const unsigned int* hp = hist + ((size_t)PASS * E + e) * kSelBins;
+  if (cnt <= 0) {   // (no workgroup of the histogram pass touched the row)
+    if (threadIdx.x == 0) { lohi[2 * e] = 0.0; lohi[2 * e + 1] = 0.0; }
+    return;
+  }
+  unsigned int* hp = hist + (size_t)e * kSelBins;
   int bin; unsigned int below;
-  pick_bin<kSelBins / NT>([&](int i) { return hp[i]; }, (unsigned int)st.k, wave_tot, sh_pick, bin, below);
+  pick_bin<kSelBins / NT>([&](int i) { return hp[i]; }, (unsigned int)(cnt / 2), wave_tot, sh_pick, bin, below);
+#pragma unroll
+  for (int i = 0; i < kSelBins / NT; ++i) hp[threadIdx.x * (kSelBins / NT) + i] = 0u;
   if (threadIdx.x == 0) {
-    SelState o;
-    o.prefix = st.prefix | ((unsigned long long)bin << SHIFT);
-    o.k = st.k - (int)below; o.pad = 0;
-    state[(size_t)PASS * E + e] = o;
+    const long long q = kbq - (long long)(kSelBins - 1 - bin);   // key >> SH of the bin's keys (bins 1..2046); a non-empty bin has q >= 0
+    const unsigned long long low_mask = (1ull << kSelShift) - 1ull;
+    unsigned long long lo = 0ull, hi = 0ull;
+    if (bin == kSelBins - 1) { lo = (unsigned long long)(kbq > 0 ? kbq : 0) << kSelShift; hi = 0x7FFFFFFFFFFFFFFFull; }
+    else if (bin == 0) { lo = 0ull; hi = q >= 0 ? (((unsigned long long)q << kSelShift) | low_mask) : 0ull; }
+    else if (q >= 0) { lo = (unsigned long long)q << kSelShift; hi = lo | low_mask; }
+    lohi[2 * e] = __longlong_as_double((long long)lo); lohi[2 * e + 1] = __longlong_as_double((long long)hi);
   }
 }
 
@@ -335,59 +299,12 @@ __device__ __forceinline__ void write_a_scale(int cnt, double med, int e, double
   if (a_host) a_host[e] = a;
 }
 
-// one workgroup per edge: pick digit C, then the keys matching the 33-bit prefix (out of the second compact buffer) ->
-// 3 x 10-bit passes in LDS.  Also hands (count, median d2) to the host through the mapped result buffer.
-__global__ __launch_bounds__(NT) void select_final_kernel(int E, const int* __restrict__ count, const long long* __restrict__ cap_off,
-                                                          const double* __restrict__ keys2, const unsigned int* __restrict__ cnt2,
-                                                          const unsigned int* __restrict__ hist, const SelState* __restrict__ state,
-                                                          double* __restrict__ median, double* __restrict__ host_res,
-                                                          double* __restrict__ a_dev, double* __restrict__ a_host, double armed) {
-  __shared__ unsigned int lh[1024];
-  __shared__ int wave_tot[NT / 64];
-  __shared__ int sh_pick[2];
-  const int e = blockIdx.x;
-  const int cnt = count[e];
-  double med = 0.0;
-  if (cnt > 0) {
-    SelState st = state[(size_t)1 * E + e];
-    {
-      const unsigned int* hp = hist + ((size_t)2 * E + e) * kSelBins;
-      int bin; unsigned int below;
-      pick_bin<kSelBins / NT>([&](int i) { return hp[i]; }, (unsigned int)st.k, wave_tot, sh_pick, bin, below);
-      st.prefix |= (unsigned long long)bin << 30;
-      st.k -= (int)below;
-    }
-    const int n2 = (int)cnt2[e];
-    const long long base = cap_off[e];
-    for (int shift = 20; shift >= 0; shift -= 10) {
-      for (int i = threadIdx.x; i < 1024; i += NT) lh[i] = 0u;
-      __syncthreads();
-      for (int pos = threadIdx.x; pos < n2; pos += NT) {
-        const unsigned long long key = (unsigned long long)__double_as_longlong(keys2[base + pos]);
-        if ((key >> (shift + 10)) == (st.prefix >> (shift + 10))) atomicAdd(&lh[(key >> shift) & 1023ull], 1u);
-      }
-      __syncthreads();
-      int bin; unsigned int below;
-      pick_bin<1024 / NT>([&](int i) { return lh[i]; }, (unsigned int)st.k, wave_tot, sh_pick, bin, below);
-      st.prefix |= (unsigned long long)bin << shift;
-      st.k -= (int)below;
-    }
-    med = __longlong_as_double((long long)st.prefix);
-  }
-  if (threadIdx.x == 0) {
-    median[e] = med;
-    if (host_res) {
-      host_res[2 * e] = (double)(cnt > 0 ? cnt : 0); host_res[2 * e + 1] = med;
-      if (e == 0) host_res[2 * E] = armed;   // slot behind the E pairs: 1 if this rank queued the speculative evaluation (summed over ranks)
-    }
-    write_a_scale(cnt, med, e, a_dev, a_host);
-  }
-}
-
 // ---- bracket select: when the registration has settled, the median of an edge barely moves between rounds.  ONE pass
 // over the keys counts those below a bracket [lo, hi] around last round's median and compacts the few per cent inside it;
 // one workgroup per edge then selects the wanted rank among the compacted keys in LDS.  Exact whenever the rank falls inside
-// the bracket; otherwise the edge's result slot is flagged (median = -1) and the host runs the full radix select.
+// the bracket; otherwise the edge's result slot is flagged (median = -1) and the host runs the full select (launch_select_median),
+// which puts the very same two kernels behind a device-made bracket that cannot miss.  Also hands (count, median d2) to the host
+// through the mapped result buffer.
 __global__ __launch_bounds__(NT) void bracket_pass_kernel(const int* __restrict__ sblock_off, int E, const int* __restrict__ count,
                                                           const long long* __restrict__ cap_off, const double* __restrict__ keys,
                                                           const double* __restrict__ lohi, unsigned int* __restrict__ cnt_lt,
@@ -551,53 +468,57 @@ int launch_gather_stream(mvicp_ctx* c) {
   return MVICP_OK;
 }
 
+// cnt_lt [E] | cnt_mid [E] | hist [E][2048]; zeroed once (mvicp_set_graph, or here after a failed search), kept zero by the kernels
+static int select_scratch(mvicp_ctx* c, unsigned int** cnt_lt, unsigned int** cnt_mid, unsigned int** hist) {
+  const size_t E = (size_t)c->E;
+  *cnt_lt = c->d_sel_hist; *cnt_mid = *cnt_lt + E; *hist = *cnt_mid + E;
+  if (!c->sel_scratch_clean) {
+    MV_HIP(hipMemsetAsync(c->d_sel_hist, 0, sizeof(unsigned int) * E * (kSelBins + 2), c->stream));
+    c->sel_scratch_clean = true;   // (a search that does not return OK clears it again)
+  }
+  return MVICP_OK;
+}
+
+static void launch_bracket_final(mvicp_ctx* c, unsigned int* cnt_lt, unsigned int* cnt_mid) {
+  hipLaunchKernelGGL(bracket_final_kernel, dim3(c->E), dim3(NT), 0, c->stream, c->E, c->d_count, c->d_cap_off, c->d_sel_keys1, cnt_lt,
+                     cnt_mid, c->d_median, c->d_res_target ? c->d_res_target : c->d_res_host, c->spec_arm ? c->d_a : (double*)nullptr,
+                     c->spec_arm ? c->d_a_check : (double*)nullptr, c->spec_arm ? 1.0 : 0.0);
+}
+
 int launch_select_bracket(mvicp_ctx* c) {
   if (c->E == 0) return MVICP_OK;
   double bytes = 0;
   for (int e = 0; e < c->E; ++e) if (c->owned[e]) bytes += 8.0 * c->h_count[e];   // one full read of the key list
   ProfScope ps(c, "select", bytes);
-  const size_t E = (size_t)c->E;
-  unsigned int* cnt_lt = c->d_sel_hist;   // reuses the histogram scratch: cnt_lt [E] | cnt_mid [E]
-  unsigned int* cnt_mid = cnt_lt + E;
-  if (c->n_sblocks) {
-    if (!c->bracket_counters_clean) MV_HIP(hipMemsetAsync(cnt_lt, 0, sizeof(unsigned int) * 2 * E, c->stream));
-    c->bracket_counters_clean = true;   // bracket_final_kernel re-zeroes what it used
+  unsigned int *cnt_lt, *cnt_mid, *hist;
+  MV_CHECK(select_scratch(c, &cnt_lt, &cnt_mid, &hist));
+  if (c->n_sblocks)
     hipLaunchKernelGGL(bracket_pass_kernel, dim3(c->n_sblocks), dim3(NT), 0, c->stream, c->d_sblock_off, c->E, c->d_count, c->d_cap_off, c->d_cd2,
                        (const double*)c->d_sel_lohi, cnt_lt, c->d_sel_keys1, cnt_mid);
-  }
-  hipLaunchKernelGGL(bracket_final_kernel, dim3(c->E), dim3(NT), 0, c->stream, c->E, c->d_count, c->d_cap_off, c->d_sel_keys1, cnt_lt,
-                     cnt_mid, c->d_median, c->d_res_target ? c->d_res_target : c->d_res_host, c->spec_arm ? c->d_a : (double*)nullptr,
-                     c->spec_arm ? c->d_a_check : (double*)nullptr, c->spec_arm ? 1.0 : 0.0);
+  launch_bracket_final(c, cnt_lt, cnt_mid);
   MV_HIP(hipGetLastError());
   return MVICP_OK;
 }
 
-int launch_select_median(mvicp_ctx* c) {
+int launch_select_median(mvicp_ctx* c, double d2_bound) {
   if (c->E == 0) return MVICP_OK;
   double bytes = 0;
   for (int e = 0; e < c->E; ++e) if (c->owned[e]) bytes += 16.0 * c->h_count[e];   // two full reads of the key list (last round's length)
   ProfScope ps(c, "select", bytes);
-  const size_t E = (size_t)c->E;
-  unsigned int* hist = c->d_sel_hist;                 // [3][E][2048] | cnt1 [E] | cnt2 [E]  (one memset)
-  unsigned int* cnt1 = hist + 3 * E * kSelBins;
-  unsigned int* cnt2 = cnt1 + E;
-  SelState* st = (SelState*)c->d_sel_state;
-  c->bracket_counters_clean = false;   // the radix passes use the same scratch
+  unsigned int *cnt_lt, *cnt_mid, *hist;
+  MV_CHECK(select_scratch(c, &cnt_lt, &cnt_mid, &hist));
   if (c->n_sblocks) {
-    MV_HIP(hipMemsetAsync(hist, 0, sizeof(unsigned int) * (3 * E * kSelBins + 2 * E), c->stream));
+    long long kb;
+    std::memcpy(&kb, &d2_bound, sizeof(kb));
+    const long long kbq = kb > 0 ? kb >> kSelShift : 0;   // (a bound that is not a positive number anchors at 0: still monotone)
     const dim3 grid(c->n_sblocks), blk(NT);
-    hipLaunchKernelGGL((select_pass_kernel<0>), grid, blk, 0, c->stream, c->d_sblock_off, c->E, c->d_count, c->d_cap_off, c->d_cd2, (const unsigned int*)nullptr,
-                       hist, (const SelState*)st, (double*)nullptr, (unsigned int*)nullptr);
-    hipLaunchKernelGGL((select_pick_kernel<0>), dim3(c->E), blk, 0, c->stream, c->E, c->d_count, (const unsigned int*)hist, st);
-    hipLaunchKernelGGL((select_pass_kernel<1>), grid, blk, 0, c->stream, c->d_sblock_off, c->E, c->d_count, c->d_cap_off, c->d_cd2, (const unsigned int*)nullptr,
-                       hist, (const SelState*)st, c->d_sel_keys1, cnt1);
-    hipLaunchKernelGGL((select_pick_kernel<1>), dim3(c->E), blk, 0, c->stream, c->E, c->d_count, (const unsigned int*)hist, st);
-    hipLaunchKernelGGL((select_pass_kernel<2>), grid, blk, 0, c->stream, c->d_sblock_off, c->E, c->d_count, c->d_cap_off, c->d_sel_keys1, (const unsigned int*)cnt1,
-                       hist, (const SelState*)st, c->d_sel_keys2, cnt2);
+    // (d_sel_lohi: the control-block upload of this search, which carries the host-predicted brackets, is earlier in the stream)
+    hipLaunchKernelGGL(select_hist_kernel, grid, blk, 0, c->stream, c->d_sblock_off, c->E, c->d_count, c->d_cap_off, c->d_cd2, kbq, hist);
+    hipLaunchKernelGGL(select_pick_kernel, dim3(c->E), blk, 0, c->stream, c->E, c->d_count, hist, kbq, c->d_sel_lohi);
+    hipLaunchKernelGGL(bracket_pass_kernel, grid, blk, 0, c->stream, c->d_sblock_off, c->E, c->d_count, c->d_cap_off, c->d_cd2,
+                       (const double*)c->d_sel_lohi, cnt_lt, c->d_sel_keys1, cnt_mid);
   }
-  hipLaunchKernelGGL(select_final_kernel, dim3(c->E), dim3(NT), 0, c->stream, c->E, c->d_count, c->d_cap_off, c->d_sel_keys2, (const unsigned int*)cnt2,
-                     (const unsigned int*)hist, (const SelState*)st, c->d_median, c->d_res_target ? c->d_res_target : c->d_res_host,
-                     c->spec_arm ? c->d_a : (double*)nullptr, c->spec_arm ? c->d_a_check : (double*)nullptr, c->spec_arm ? 1.0 : 0.0);
+  launch_bracket_final(c, cnt_lt, cnt_mid);
   MV_HIP(hipGetLastError());
   return MVICP_OK;
 }
