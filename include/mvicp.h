@@ -124,6 +124,42 @@ int mvicp_set_graph(mvicp_ctx* ctx, int n_edges, const int* src, const int* dst)
  * called or a frame never uploaded -> MVICP_ERR_STATE. */
 int mvicp_overlap(mvicp_ctx* ctx, const double* poses, float thresh, int max_samples, int* samples, int* hits, long long* sumq, int* q_exp);
 
+/* ---- voxel-grid reduction: downsampled levels and the fused model -------------------------------------------
+ * Reduces the points of one or several frames, at given poses, to ONE POINT PER OCCUPIED VOXEL: a coarser copy of a cloud (one frame, no
+ * poses) or the merged model of a registration (all frames at the final poses).  The result is a pure function of the inputs, bit for bit
+ * (tests/voxelref.py is the same definition in numpy):
+ *   Inputs   frames[]: n_sel DISTINCT frame indices (NULL = all frames 0 .. K-1, n_sel ignored); poses: n_frames x 16 or NULL; voxel: the cell edge.
+ *   Sequence the selected frames in the order of frames[], inside a frame the points in ascending ORIGINAL index; the position in it is `seq`.
+ *   World    poses == NULL: w = p, m = n (the stored bytes, no arithmetic).  Otherwise, for c = 0..2, every operation rounded on its own, no fma
+ *            (the first line of xf_point, csrc/nn_metric.h):  w_c = ((R[c,0] p0 + R[c,1] p1) + R[c,2] p2) + t_c,
+ *            m_c = (R[c,0] n0 + R[c,1] n1) + R[c,2] n2.  R and t are used as given; they are not orthonormalised.
+ *   Cell     c_a = floor(w_a / voxel) per axis, the IEEE double division (NOT a multiplication by 1 / voxel: that lands in another cell for
+ *            points on cell faces).  Any |w_a / voxel| >= 2^31, or a non-finite quotient, is MVICP_ERR_ARG.
+ *   Key      cmin_a and d_a = cmax_a - cmin_a + 1 over the whole sequence; key = ((c_z - cmin_z) d_y + (c_y - cmin_y)) d_x + (c_x - cmin_x);
+ *            d_x d_y d_z >= 2^62 is MVICP_ERR_ARG (voxel too small for the extent).
+ *   Output   one row per distinct key, rows in ASCENDING key (z-major, then y, then x).  Row v:
+ *            cnt[v] (int32) = number of input points with that key;
+ *            xyz[v]: per component s = +0.0; for the voxel's points in ascending seq: s = s + w_c; then s / (double)cnt (IEEE division);
+ *            nrm[v]: the same sequential sums S of m, then S / sqrt((S0 S0 + S1 S1) + S2 S2) (no fma, IEEE sqrt and division), (0,0,0) when that
+ *            norm is 0 or not finite; produced iff every selected frame with at least one point has normals (*has_normals).
+ *   Empty    an empty selection, or one whose frames are all empty, gives m = 0 (*has_normals = 1) and is not an error.
+ * The summation order is part of the contract, so a voxel is summed by one GPU lane: a voxel that holds thousands of points (a cell larger
+ * than the cloud) is reduced sequentially -- correct, not fast.
+ * Needs the selected frames uploaded (mvicp_set_frame / mvicp_set_frame_device), NO graph and no search structure; HISTORY-NEUTRAL like
+ * mvicp_overlap: it reads the stored clouds only and leaves caches, seeds, lists, epochs, medians, the AUTO state and queued evaluations
+ * alone.  With several ranks every rank computes it locally.  The call returns when the result is complete; the result lives in
+ * library-owned device memory until the next mvicp_voxel_grid, mvicp_set_num_frames or mvicp_destroy.
+ * RETURNS THE NUMBER OF VOXELS m (>= 0) or a negative mvicp_status; has_normals may be NULL.
+ * Errors: NULL context, voxel not finite or <= 0, n_sel < 0, a non-finite pose entry, a frame index out of range or listed twice, the range
+ * errors above, >= 2^31 input points -> MVICP_ERR_ARG (those that need no GPU are decided before the context is touched);
+ * mvicp_set_num_frames not called or a selected frame never uploaded -> MVICP_ERR_STATE. */
+long long mvicp_voxel_grid(mvicp_ctx* ctx, int n_sel, const int* frames, const double* poses, double voxel, int* has_normals);
+/* Copies the last result: xyz / nrm (m x 3 doubles), cnt (m ints); each may be NULL; each may be a HOST pointer or a DEVICE pointer of the
+ * context's device (decided per pointer like mvicp_set_frame_device decides; another device's memory is MVICP_ERR_ARG), so a device
+ * result goes straight back into mvicp_set_frame_device of this or another context.  cap = rows each destination holds.
+ * Errors: cap < m -> MVICP_ERR_ARG; no mvicp_voxel_grid before, or nrm != NULL when has_normals == 0 -> MVICP_ERR_STATE. */
+int mvicp_voxel_fetch(mvicp_ctx* ctx, long long cap, double* xyz, double* nrm, int* cnt);
+
 /* The graph rule on top of the census (pure host function, no context).  Frame i keeps the knn frames j != i with the most hits, among
  * those with hits[i*K+j] > 0 and hits[i*K+j] >= min_fraction * samples[i]; equal hits: the smaller sumq first (within one row that is
  * the smaller mean distance: an exact integer comparison, no division), then the lower j.  sumq NULL: hits, then lower j.  Edges are
@@ -260,6 +296,8 @@ int mvicp_closedform_point_to_plane(const double* src, const double* dst, const 
  * "nn_cache" (0/1, default 1): temporal cache of the grid kernel — a query whose previous neighbour is provably still
  * nearest after the pose update skips the search (results are bit-identical either way).
  * "nn_census" (0/1): count candidates / boxes / cache hits per launch while profiling (feeds the algorithmic-byte model).
+ * "voxel_permute" (0/1, default 1): mvicp_voxel_grid lays the transformed points out in sorted order before it sums them (0: the
+ * sum re-gathers them through the sorted sequence; the result is the same bytes).
  * "spin_wait" (0/1, default 0): poll the stream for up to 2 ms before blocking on the per-evaluation / per-round waits.
  * "tile_seed" (0/1, default 1): the tile kernel starts from last round's neighbours; "tile_waves" (0 = auto, 4..8):
  * occupancy variant of the tile kernel; "tile_mfma" (0/1/2, default 1): the tile method screens an opened tile on the matrix pipe

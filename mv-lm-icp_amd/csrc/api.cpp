@@ -505,6 +505,7 @@ int mvicp_destroy(mvicp_ctx* c) try {
   for (FrameDev& f : c->frames) { dev_free(f.pts); dev_free(f.nor); free_grid(f.grid); free_tie(f); }
   dev_free(c->d_split_idx); dev_free(c->d_split_d2); dev_free(c->d_scratch);
   free_overlap(c);
+  free_voxel(c);
   for (auto& kv : c->tables) if (kv.second.d) (void)hipFree(kv.second.d);
   if (c->d_census) (void)hipFree(c->d_census);
   if (c->h_census) (void)hipHostFree(c->h_census);
@@ -528,6 +529,7 @@ int mvicp_set_num_frames(mvicp_ctx* c, int n_frames) try {
   if (n_frames < 0) { set_error("n_frames < 0"); return MVICP_ERR_ARG; }
   (void)finish_builds(c);   // (builds of clouds that are dropped right here: their outcome no longer matters)
   if (c->E) free_graph(c);
+  free_voxel(c);   // (the last voxel-grid result ends here; every voxel call waits for its own work)
   for (FrameDev& f : c->frames) { dev_free(f.pts); dev_free(f.nor); free_grid(f.grid); free_tie(f); }
   c->frames.assign(n_frames, FrameDev());
   c->n_frames = n_frames;
@@ -791,6 +793,70 @@ int mvicp_overlap(mvicp_ctx* c, const double* poses, float thresh, int max_sampl
     for (int j = 0; j < K; ++j)
       if (i != j) fill_query_xf(poses + 16 * (size_t)i, poses + 16 * (size_t)j, &xf[24 * ((size_t)i * K + j)]);
   return overlap_census(c, xf.data(), B2, std::ldexp(1.0, q), max_samples, samples, hits, sumq);
+} MVICP_GUARD_ABI
+
+long long mvicp_voxel_grid(mvicp_ctx* c, int n_sel, const int* frames, const double* poses, double voxel, int* has_normals) try {
+  // every argument error that needs no GPU first: nothing of the context has been touched when one of them is reported
+  if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
+  if (!std::isfinite(voxel) || !(voxel > 0.0)) { set_error("voxel must be finite and > 0"); return MVICP_ERR_ARG; }
+  if (n_sel < 0) { set_error("n_sel < 0"); return MVICP_ERR_ARG; }
+  const int K = c->n_frames;
+  if (K <= 0) { set_error("no frames: call mvicp_set_num_frames first"); return MVICP_ERR_STATE; }
+  std::vector<int> sel;
+  if (!frames) { sel.resize((size_t)K); for (int i = 0; i < K; ++i) sel[i] = i; }
+  else {
+    std::vector<char> seen((size_t)K, 0);
+    for (int k = 0; k < n_sel; ++k) {
+      const int i = frames[k];
+      if (i < 0 || i >= K) { set_error("frames[%d] = %d out of range [0,%d)", k, i, K); return MVICP_ERR_ARG; }
+      if (seen[i]) { set_error("frame %d is listed twice", i); return MVICP_ERR_ARG; }
+      seen[i] = 1;
+      sel.push_back(i);
+    }
+  }
+  if (poses)
+    for (size_t k = 0; k < 16 * (size_t)K; ++k)
+      if (!std::isfinite(poses[k])) { set_error("non-finite pose entry (frame %d)", (int)(k / 16)); return MVICP_ERR_ARG; }
+  long long total = 0;
+  for (int i : sel) {
+    if (!c->frames[i].pts) { set_error("frame %d was never uploaded", i); return MVICP_ERR_STATE; }
+    total += c->frames[i].n;
+  }
+  if (total >= (1ll << 31)) { set_error("%lld input points: the voxel grid takes fewer than 2^31", total); return MVICP_ERR_ARG; }
+  MV_CHECK(bind(c));
+  return voxel_reduce(c, (int)sel.size(), sel.data(), poses, voxel, has_normals);
+} MVICP_GUARD_ABI
+
+// where a destination of mvicp_voxel_fetch lives: 1 = device memory of the context's device, 0 = host memory; another device's memory is MVICP_ERR_ARG
+static int destination_kind(mvicp_ctx* c, const void* p, const char* what) {
+  hipPointerAttribute_t at;
+  std::memset(&at, 0, sizeof(at));
+  const hipError_t e = hipPointerGetAttributes(&at, p);
+  if (e != hipSuccess) { (void)hipGetLastError(); return 0; }   // (a pointer the runtime does not know: plain host memory)
+  if (at.type != hipMemoryTypeDevice) return 0;
+  if (at.device != c->device) { set_error("%s lives on device %d, the context on device %d", what, at.device, c->device); return MVICP_ERR_ARG; }
+  return 1;
+}
+
+int mvicp_voxel_fetch(mvicp_ctx* c, long long cap, double* xyz, double* nrm, int* cnt) try {
+  if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
+  if (c->vox_m < 0) { set_error("no voxel grid: call mvicp_voxel_grid first"); return MVICP_ERR_STATE; }
+  if (cap < c->vox_m) { set_error("cap %lld < %lld voxels", cap, c->vox_m); return MVICP_ERR_ARG; }
+  if (nrm && !c->vox_has_normals) { set_error("the voxel grid has no normals"); return MVICP_ERR_STATE; }
+  const size_t m = (size_t)c->vox_m;
+  if (m == 0) return MVICP_OK;
+  MV_CHECK(bind(c));
+  const void* src[3] = {c->vox_xyz, c->vox_nrm, c->vox_cnt};
+  void* dst[3] = {xyz, nrm, cnt};
+  const size_t bytes[3] = {24 * m, 24 * m, 4 * m};
+  const char* names[3] = {"xyz", "nrm", "cnt"};
+  int kind[3] = {0, 0, 0};
+  for (int k = 0; k < 3; ++k)
+    if (dst[k]) { kind[k] = destination_kind(c, dst[k], names[k]); if (kind[k] < 0) return kind[k]; }
+  for (int k = 0; k < 3; ++k)
+    if (dst[k]) MV_HIP(hipMemcpyAsync(dst[k], src[k], bytes[k], kind[k] ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+  MV_HIP(hipStreamSynchronize(c->stream));
+  return MVICP_OK;
 } MVICP_GUARD_ABI
 
 int mvicp_graph_from_overlap(int n_frames, const int* samples, const int* hits, const long long* sumq, int knn, double min_fraction,
@@ -1703,6 +1769,7 @@ int mvicp_set_option(mvicp_ctx* c, const char* name, double value) try {
   if (std::strcmp(name, "reject_cache") == 0) { c->reject_cache = value != 0.0; return MVICP_OK; }
   if (std::strcmp(name, "tile_miss") == 0) { if (!(value >= 0.0 && value <= 64.0)) { set_error("tile_miss outside [0, 64]"); return MVICP_ERR_ARG; } c->tile_miss = (int)value; return MVICP_OK; }
   if (std::strcmp(name, "tile_cache") == 0) { c->tile_cache = (int)value; return MVICP_OK; }
+  if (std::strcmp(name, "voxel_permute") == 0) { c->voxel_permute = value != 0.0; return MVICP_OK; }
   if (std::strcmp(name, "spin_wait") == 0) { c->spin_wait = value != 0.0; return MVICP_OK; }
   if (std::strcmp(name, "fault_inject") == 0) { c->fault_inject = (int)value; return MVICP_OK; }            // tests: the value-th mvicp_correspond from now fails locally before its exchange
   if (std::strcmp(name, "fault_inject_build") == 0) { c->fault_inject_build.store((int)value); return MVICP_OK; }      // tests: the value-th structure build from now fails

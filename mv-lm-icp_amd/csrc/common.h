@@ -244,6 +244,13 @@ struct mvicp_ctx {
   // memory — so that mvicp_overlap touches nothing a search, a queued evaluation or the shared control block uses
   char* ov_dev = nullptr; char* ov_pin = nullptr; size_t ov_bytes = 0;
 
+  // voxel-grid reduction (voxel.hip): the last result, library-owned until the next mvicp_voxel_grid / mvicp_set_num_frames / mvicp_destroy
+  // (vox_m < 0: none), and buffers of its own — scratch, rocprim storage, a pinned control block — kept between calls and grown on demand,
+  // so that mvicp_voxel_grid touches nothing a search, a queued evaluation or the census uses
+  double* vox_xyz = nullptr; double* vox_nrm = nullptr; int* vox_cnt = nullptr; long long vox_m = -1; int vox_has_normals = 0;
+  char* vox_scratch = nullptr; char* vox_tmp = nullptr; char* vox_pin = nullptr; size_t vox_scratch_bytes = 0, vox_tmp_bytes = 0, vox_pin_bytes = 0;
+  int voxel_permute = 1;           // option "voxel_permute": lay w / R n out in sorted order before the reduction (0: the reduction re-gathers through seq)
+
   // cached small tables
   struct CachedTable { std::vector<char> bytes; void* d = nullptr; size_t cap = 0; };
   std::map<std::string, CachedTable> tables;
@@ -347,6 +354,10 @@ void free_tie(FrameDev& f);                                                     
 // scale = 2^q_exp; samples K, hits K x K, sumq K x K or null (host arrays).  Waits for the stream; history-neutral.
 int overlap_census(mvicp_ctx* c, const double* xf, double B2, double scale, int max_samples, int* samples, int* hits, long long* sumq);
 void free_overlap(mvicp_ctx* c);
+// voxel.hip: the points of the n_sel frames sel[] (valid, distinct, uploaded), at poses (n_frames x 16) or as stored (null), reduced to one
+// point per voxel; the result stays on the context (vox_*).  Returns the number of voxels or a negative status.  Waits for the stream; history-neutral.
+long long voxel_reduce(mvicp_ctx* c, int n_sel, const int* sel, const double* poses, double voxel, int* has_normals);
+void free_voxel(mvicp_ctx* c);     // the result and the buffers
 int launch_compact(mvicp_ctx* c, double d2_bound);                                    // corr.hip
 int launch_gather_stream(mvicp_ctx* c);
 int launch_select_median(mvicp_ctx* c, double d2_bound);   // two-pass select anchored at the acceptance bound: any key set, exact

@@ -83,15 +83,31 @@ void Session::bind(std::vector<std::shared_ptr<Frame>>& frames) {
   epochs = nullptr;
 }
 
+void Session::ensure_uploaded(std::vector<std::shared_ptr<Frame>>& frames) {
+  const std::vector<FrameKey> keys = frame_keys_of(frames);
+  if (ctx && frames_key == (const void*)&frames && keys == frame_keys) return;
+  upload(frames);
+  frames_key = (const void*)&frames; frame_keys = keys;
+  graph_bound = false; esrc.clear(); edst.clear();
+  last_poses.clear(); held.clear(); epochs = nullptr; corr = nullptr; corr_off = nullptr;
+}
+
+long long Session::fusedModel(std::vector<std::shared_ptr<Frame>>& frames, double voxel, std::vector<Vector3d>& pts, std::vector<Vector3d>& nor) {
+  ensure_uploaded(frames);
+  std::vector<double> P(16 * frames.size());
+  for (size_t i = 0; i < frames.size(); ++i) std::memcpy(&P[16 * i], frames[i]->pose.data(), 128);
+  int has_normals = 0;
+  const long long m = mvicp_voxel_grid(ctx, 0, nullptr, P.data(), voxel, &has_normals);
+  if (m < 0) check((int)m);
+  pts.assign((size_t)m, Vector3d());
+  nor.assign(has_normals ? (size_t)m : 0, Vector3d());
+  if (m) check(mvicp_voxel_fetch(ctx, m, pts[0].data(), has_normals ? nor[0].data() : nullptr, nullptr));
+  return m;
+}
+
 int Session::computeOverlapNeighbours(std::vector<std::shared_ptr<Frame>>& frames, int knn, float thresh, int max_samples, double min_fraction) {
   const int K = (int)frames.size();
-  const std::vector<FrameKey> keys = frame_keys_of(frames);
-  if (!(ctx && frames_key == (const void*)&frames && keys == frame_keys)) {
-    upload(frames);
-    frames_key = (const void*)&frames; frame_keys = keys;
-    graph_bound = false; esrc.clear(); edst.clear();
-    last_poses.clear(); held.clear(); epochs = nullptr; corr = nullptr; corr_off = nullptr;
-  }
+  ensure_uploaded(frames);
   std::vector<double> P(16 * (size_t)K);
   for (int i = 0; i < K; ++i) std::memcpy(&P[16 * (size_t)i], frames[i]->pose.data(), 128);
   std::vector<int> samples(K), hits((size_t)K * K), src((size_t)K * K), dst((size_t)K * K);
@@ -294,22 +310,41 @@ std::vector<Vector3d> Frame::getNeighbours(int queryIdx, size_t num_results) {
   return out;
 }
 
-mvicp_ctx* Session::query_context(Frame* f, int* slot) {
+mvicp_ctx* Session::query_context(Frame* f, int* slot, bool with_normals) {
   // frame.cpp:187-206.  The reference builds the frame's KD-tree lazily on first use; here the frame's structure already lives in the
   // bound session (uploaded by computeClosestPointsToNeighbours / ceresOptimizer*), found by frame index.  A frame that is not part
   // of the bound vector gets a one-cloud side context owned by the session (built on first use, like the reference's lazy tree;
   // rebuilt when the cloud changes).
   if (f->pts.empty()) throw std::runtime_error("mvicp: getClosestPoint on an empty cloud (nanoflann throws here: nanoflann.hpp:904)");
   const int fi = ctx ? frame_index(f) : -1;
-  if (fi >= 0 && frame_keys[fi].pts == (const void*)f->pts[0].data() && frame_keys[fi].n == f->pts.size()) { *slot = fi; return ctx; }
-  if (side_owner != f || side_version != f->version || !side_ctx) {
+  const bool has_nor = f->nor.size() == f->pts.size();
+  if (fi >= 0 && frame_keys[fi].pts == (const void*)f->pts[0].data() && frame_keys[fi].n == f->pts.size() &&
+      (!with_normals || (frame_keys[fi].nor == (f->nor.empty() ? nullptr : (const void*)f->nor[0].data()) && frame_keys[fi].version == f->version))) { *slot = fi; return ctx; }
+  const bool want_nor = with_normals && has_nor;
+  if (side_owner != f || side_version != f->version || !side_ctx || (want_nor && !side_nor)) {
     if (!side_ctx) check(mvicp_create(device, &side_ctx));
     check(mvicp_set_num_frames(side_ctx, 1));
-    check(mvicp_set_frame(side_ctx, 0, f->pts[0].data(), nullptr, (int)f->pts.size()));
-    side_owner = f; side_version = f->version;
+    side_owner = nullptr;
+    check(mvicp_set_frame(side_ctx, 0, f->pts[0].data(), want_nor ? f->nor[0].data() : nullptr, (int)f->pts.size()));
+    side_owner = f; side_version = f->version; side_nor = want_nor;
   }
   *slot = 0;
   return side_ctx;
+}
+
+std::shared_ptr<Frame> Frame::voxelDownsample(double voxel) {
+  std::shared_ptr<Frame> out(new Frame());
+  out->fixed = fixed; out->pose = pose; out->poseGroundTruth = poseGroundTruth;
+  for (const OutgoingEdge& e : neighbours) out->neighbours.push_back(OutgoingEdge{e.neighbourIdx, e.weight, {}});
+  if (pts.empty()) return out;
+  int slot = 0, has_normals = 0;
+  mvicp_ctx* c = Session::get().query_context(this, &slot, true);
+  const long long m = mvicp_voxel_grid(c, 1, &slot, nullptr, voxel, &has_normals);
+  if (m < 0) check((int)m);
+  out->pts.assign((size_t)m, Vector3d());
+  out->nor.assign(has_normals && nor.size() == pts.size() ? (size_t)m : 0, Vector3d());
+  if (m) check(mvicp_voxel_fetch(c, m, out->pts[0].data(), out->nor.empty() ? nullptr : out->nor[0].data(), nullptr));
+  return out;
 }
 
 double Frame::getClosestPoint(const Vector3d& q, size_t& ret_index) {

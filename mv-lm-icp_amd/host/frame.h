@@ -56,6 +56,13 @@ class Frame {
   std::vector<Vector3d> getNeighbours(int queryIdx, size_t num_results);
   // the table behind it: pts.size() x num_results original indices, row i = the neighbours of pts[i], nearest (i itself) first
   const std::vector<int>& getNeighbourIndices(size_t num_results);
+  // A coarser copy of this frame (no counterpart in the reference): one point per occupied voxel of edge `voxel` — mvicp_voxel_grid on this
+  // cloud as it is stored, no pose applied: per voxel the mean of its points in ascending index and, if the frame has normals, the
+  // normalised sum of theirs.  The new Frame has the reduced pts / nor and the same pose, poseGroundTruth, fixed and neighbours (index and
+  // weight; the correspondence lists, whose indices refer to the full cloud, start empty).  Runs in the context Session::query_context
+  // finds for this frame.  A driver registers the copies for its first rounds and hands their poses to the full frames (bin/multiview
+  // --coarse_voxel / --coarse_rounds).
+  std::shared_ptr<Frame> voxelDownsample(double voxel);
 
  private:
   std::vector<int> knn_table_; size_t knn_k_ = 0; const void* knn_pts_ = nullptr; size_t knn_n_ = 0;   // cache of getNeighbourIndices
@@ -91,14 +98,21 @@ struct Session {
   std::vector<unsigned char> last_fixed;
   float last_thresh = -1.f;
   mvicp_ctx* side_ctx = nullptr; const Frame* side_owner = nullptr; unsigned long long side_version = 0;  // getClosestPoint on an unbound frame
+  bool side_nor = false;                   // the side context holds the frame's normals too (voxelDownsample asks for them)
   int frame_index(const Frame* f) const;   // position of f in the bound vector, or -1
-  // context + frame slot that hold `f`'s cloud for raw queries: the bound session if f is part of it, else a one-cloud side context
-  mvicp_ctx* query_context(Frame* f, int* slot);
+  // context + frame slot that hold `f`'s cloud for raw queries: the bound session if f is part of it, else a one-cloud side context.
+  // with_normals: the slot must hold the frame's CURRENT normals as well (the bound session only if it was uploaded from them)
+  mvicp_ctx* query_context(Frame* f, int* slot, bool with_normals = false);
   void invalidate();                       // forget the device copy (forces re-upload + fresh search); for in-place edits of pts/nor data
   std::vector<int> counts;
   std::vector<float> weights;
   bool graph_bound = false;                                   // the context holds the graph of esrc / edst (false: clouds only)
   void upload(std::vector<std::shared_ptr<Frame>>& frames);    // the clouds alone (no graph)
+  void ensure_uploaded(std::vector<std::shared_ptr<Frame>>& frames);   // upload unless the session holds exactly these clouds (a new upload drops the graph)
+  // The fused model (no counterpart in the reference, whose end product is the merged cloud in its viewer): the points of ALL frames at their
+  // current poses reduced to one point per voxel of edge `voxel` (mvicp_voxel_grid over every frame, in frame order).  pts / nor receive the
+  // rows in output order; nor stays empty when a non-empty frame has no normals.  Returns the number of voxels.
+  long long fusedModel(std::vector<std::shared_ptr<Frame>>& frames, double voxel, std::vector<Vector3d>& pts, std::vector<Vector3d>& nor);
   void bind(std::vector<std::shared_ptr<Frame>>& frames);      // upload + graph (idempotent)
   // Pose graph from the overlap census (mvicp_overlap + mvicp_graph_from_overlap) in place of the computePoseNeighboursKnn loop
   // (main_multiview.cpp:104-117): fills EVERY Frame::neighbours with the frame's knn best-overlapping frames at the current poses

@@ -17,6 +17,13 @@
 // initial poses instead (Session::computeOverlapNeighbours: every frame keeps the --knn frames it shares most surface with) and prints one
 // more line, `overlap graph: C component(s)`; --overlap_cutoff X (default --cutoff), --overlap_samples N (4096; 0 = every point),
 // --overlap_min F (0: smallest share of a frame's samples that makes a candidate).
+// --coarse_voxel H --coarse_rounds R (default R = 0 = off): coarse to fine — the first R of the --rounds rounds run on Frame::voxelDownsample(H)
+// copies of the frames (one point per voxel of edge H; taken after recomputeNormals, normals are not recomputed on the coarse level), the
+// graph is built once from the full-resolution frames, the poses after round R go to the full-resolution frames, which run the remaining
+// rounds (the session re-binds by itself when the frame vector changes); --trace lines keep their format.
+// --fused_out FILE --fused_voxel H: after the last round the fused model of ALL frames at the final poses (Session::fusedModel: one point per
+// voxel of edge H) is written to FILE in the `.xyz` row format, `x y z nx ny nz` with 17 significant digits (`x y z` when a frame has no
+// normals): exactly one row per voxel, in output order, no count line.
 #include <chrono>
 #include <cstring>
 #include <fstream>
@@ -97,21 +104,36 @@ int main(int argc, char** argv) {
     }
     if (overlap_graph) std::cout << "overlap graph: " << components << " component(s)" << std::endl;
   }
+  const int coarse_rounds = F.i("coarse_rounds", 0);
+  std::vector<std::shared_ptr<Frame>> coarse;   // the frames' voxelDownsample copies (coarse_rounds > 0)
+  if (coarse_rounds > 0) {
+    try {
+      // all clouds into the session first: voxelDownsample then finds every frame there (Session::query_context) instead of uploading the
+      // frames one after the other into a context of their own, each waiting for the previous one's structure build
+      Session::get().ensure_uploaded(frames);
+      for (auto& f : frames) coarse.push_back(f->voxelDownsample(F.f("coarse_voxel", 0.0)));
+    } catch (const std::exception& ex) { std::cerr << ex.what() << std::endl; return 2; }
+    if (!quiet)
+      for (size_t i = 0; i < frames.size(); ++i) std::cout << "coarse frame " << i << ": " << coarse[i]->pts.size() << " of " << frames[i]->pts.size() << " points" << std::endl;
+  }
+  auto poses_to_full = [&]() { for (size_t i = 0; i < coarse.size(); ++i) frames[i]->pose = coarse[i]->pose; };
   double wall_search = 0.0, wall_solve = 0.0;
   std::ofstream trace;
   if (!F.s("trace", "").empty()) { trace.open(F.s("trace", "").c_str()); trace.precision(17); }
   try {
     for (int r = 0; r < rounds; ++r) {
-      if (r == F.i("perturb_round", -1) && F.i("perturb_frame", -1) >= 0 && F.i("perturb_frame", -1) < (int)frames.size())
-        frames[F.i("perturb_frame", -1)]->pose.m[12] += 1e-4;
+      if (r == coarse_rounds && !coarse.empty()) poses_to_full();
+      std::vector<std::shared_ptr<Frame>>& cur = r < coarse_rounds ? coarse : frames;   // this round's level
+      if (r == F.i("perturb_round", -1) && F.i("perturb_frame", -1) >= 0 && F.i("perturb_frame", -1) < (int)cur.size())
+        cur[F.i("perturb_frame", -1)]->pose.m[12] += 1e-4;
       const unsigned long long c0 = Session::get().edges_copied, s0 = Session::get().edges_skipped;
       const auto t0 = std::chrono::steady_clock::now();
-      for (auto& f : frames) f->computeClosestPointsToNeighbours(&frames, cutoff);
+      for (auto& f : cur) f->computeClosestPointsToNeighbours(&cur, cutoff);
       const auto t1 = std::chrono::steady_clock::now();
       if (trace.is_open())
-        for (size_t i = 0; i < frames.size(); ++i)
-          for (size_t j = 0; j < frames[i]->neighbours.size(); ++j) {
-            const OutgoingEdge& e = frames[i]->neighbours[j];
+        for (size_t i = 0; i < cur.size(); ++i)
+          for (size_t j = 0; j < cur[i]->neighbours.size(); ++j) {
+            const OutgoingEdge& e = cur[i]->neighbours[j];
             unsigned int bits;
             std::memcpy(&bits, &e.weight, 4);
             trace << "C " << r << " " << i << " " << j << " " << e.neighbourIdx << " " << e.correspondances.size() << " " << bits << "\n";
@@ -119,10 +141,10 @@ int main(int argc, char** argv) {
       if (F.b("copy_stats", false))
         std::cout << "copyback: round " << r << " copied " << Session::get().edges_copied - c0 << " skipped " << Session::get().edges_skipped - s0 << std::endl;
       if (r == rounds - 1 && !F.s("dump_corr", "").empty()) {
-        for (size_t i = 0; i < frames.size(); ++i) saveMatrix4d(F.s("dump_corr", "") + "/search_pose_" + std::to_string(i) + ".txt", frames[i]->pose);
-        for (size_t i = 0; i < frames.size(); ++i)
-          for (size_t j = 0; j < frames[i]->neighbours.size(); ++j) {
-            const OutgoingEdge& e = frames[i]->neighbours[j];
+        for (size_t i = 0; i < cur.size(); ++i) saveMatrix4d(F.s("dump_corr", "") + "/search_pose_" + std::to_string(i) + ".txt", cur[i]->pose);
+        for (size_t i = 0; i < cur.size(); ++i)
+          for (size_t j = 0; j < cur[i]->neighbours.size(); ++j) {
+            const OutgoingEdge& e = cur[i]->neighbours[j];
             std::ofstream f((F.s("dump_corr", "") + "/corr_" + std::to_string(i) + "_" + std::to_string(j) + ".txt").c_str());
             f.precision(17);
             f << e.neighbourIdx << " " << e.weight << " " << e.correspondances.size() << "\n";
@@ -133,14 +155,14 @@ int main(int argc, char** argv) {
         // S1' through the Frame mirror: q = dst.pose^-1 * (src.pose * p) (frame.cpp:131,136) -> dst.getClosestPoint(q) must give
         // the correspondence's neighbour and distance
         long checked = 0, bad = 0, single = 0;
-        for (size_t i = 0; i < frames.size(); ++i)
-          for (const OutgoingEdge& e : frames[i]->neighbours) {
-            Frame& d = *frames[e.neighbourIdx];
-            const Isometry3d M = d.pose.inverse() * frames[i]->pose;
+        for (size_t i = 0; i < cur.size(); ++i)
+          for (const OutgoingEdge& e : cur[i]->neighbours) {
+            Frame& d = *cur[e.neighbourIdx];
+            const Isometry3d M = d.pose.inverse() * cur[i]->pose;
             const int n = std::min<int>(F.i("check_nn", 0), (int)e.correspondances.size());
             // the batched form (one launch for the edge's queries) ...
             std::vector<Vector3d> qs(n);
-            for (int k = 0; k < n; ++k) qs[k] = M * frames[i]->pts[e.correspondances[k].first];
+            for (int k = 0; k < n; ++k) qs[k] = M * cur[i]->pts[e.correspondances[k].first];
             std::vector<size_t> idxs;
             const std::vector<double> d2s = d.getClosestPoints(qs, idxs);
             for (int k = 0; k < n; ++k) {
@@ -158,14 +180,14 @@ int main(int argc, char** argv) {
         std::cout << "getClosestPoint check: " << checked << " queries, " << bad << " mismatches (" << single << " also asked one by one)" << std::endl;
       }
       if (F.i("freeze_from", 1 << 30) <= r) {}   // (search only: the poses stay bit-identical)
-      else if (sophusSE3) ICP_Ceres::ceresOptimizer_sophusSE3(frames, pointToPlane, robust);
-      else if (angleAxis) ICP_Ceres::ceresOptimizer_ceresAngleAxis(frames, pointToPlane, robust);
-      else ICP_Ceres::ceresOptimizer(frames, pointToPlane, robust);
+      else if (sophusSE3) ICP_Ceres::ceresOptimizer_sophusSE3(cur, pointToPlane, robust);
+      else if (angleAxis) ICP_Ceres::ceresOptimizer_ceresAngleAxis(cur, pointToPlane, robust);
+      else ICP_Ceres::ceresOptimizer(cur, pointToPlane, robust);
       const auto t2 = std::chrono::steady_clock::now();
       if (trace.is_open())
-        for (size_t i = 0; i < frames.size(); ++i) {
+        for (size_t i = 0; i < cur.size(); ++i) {
           trace << "P " << r << " " << i;
-          for (int a = 0; a < 4; ++a) for (int b = 0; b < 4; ++b) trace << " " << frames[i]->pose.m[a + 4 * b];
+          for (int a = 0; a < 4; ++a) for (int b = 0; b < 4; ++b) trace << " " << cur[i]->pose.m[a + 4 * b];
           trace << "\n";
         }
       wall_search += std::chrono::duration<double, std::milli>(t1 - t0).count();
@@ -178,12 +200,27 @@ int main(int argc, char** argv) {
     std::cerr << ex.what() << std::endl;
     return 2;
   }
+  if (coarse_rounds >= rounds && rounds > 0 && !coarse.empty()) poses_to_full();   // (every round ran on the coarse level)
   // whole-loop wall clock of the drop-in route (Frame API + session + copy-back): parsed by bench.py / tools/dropin_bench.py
   std::cout << "loop: rounds " << rounds << " copyback " << (Session::get().copy_back ? 1 : 0) << " closest_pts_ms " << wall_search << " global_ms " << wall_solve
             << " it_per_s " << (rounds > 0 ? 1e3 * rounds / (wall_search + wall_solve) : 0.0) << std::endl;
   for (size_t i = 0; i < frames.size(); ++i) {
     if (!quiet) std::cout << "frame " << i << poseDiff(frames[i]->pose, frames[i]->poseGroundTruth);
     if (!out.empty()) saveMatrix4d(out + "/pose_" + std::to_string(i) + ".txt", frames[i]->pose);
+  }
+  if (!F.s("fused_out", "").empty()) {
+    try {
+      std::vector<Vector3d> fp, fn;
+      const long long m = Session::get().fusedModel(frames, F.f("fused_voxel", 0.0), fp, fn);
+      std::ofstream f(F.s("fused_out", "").c_str());
+      f.precision(17);
+      for (long long v = 0; v < m; ++v) {
+        f << fp[v][0] << " " << fp[v][1] << " " << fp[v][2];
+        if (!fn.empty()) f << " " << fn[v][0] << " " << fn[v][1] << " " << fn[v][2];
+        f << "\n";
+      }
+      if (!quiet) std::cout << "fused model: " << m << " voxels" << std::endl;
+    } catch (const std::exception& ex) { std::cerr << ex.what() << std::endl; return 2; }
   }
   Session::get().reset();
   return 0;

@@ -17,7 +17,7 @@ SYMBOLS = [
     "mvicp_get_correspondences", "mvicp_map_correspondences", "mvicp_map_correspondences_async", "mvicp_wait_correspondences", "mvicp_correspondence_epochs", "mvicp_set_correspondences", "mvicp_nn_query", "mvicp_linearize", "mvicp_linearize_pair", "mvicp_optimize",
     "mvicp_lm_solve", "mvicp_set_option", "mvicp_nn_census", "mvicp_nn_census_ex", "mvicp_reset_history", "mvicp_profile_enable", "mvicp_profile_reset", "mvicp_profile_get", "mvicp_profile_get_ex", "mvicp_stream", "mvicp_sync",
     "mvicp_closedform_point_to_point", "mvicp_closedform_point_to_plane", "mvicp_set_frame_device", "mvicp_get_structure",
-    "mvicp_overlap", "mvicp_graph_from_overlap",
+    "mvicp_overlap", "mvicp_graph_from_overlap", "mvicp_voxel_grid", "mvicp_voxel_fetch",
 ]
 
 # names of mvicp_get_structure (include/mvicp.h)
@@ -98,6 +98,9 @@ def load_library(path=None):
     llp = C.POINTER(C.c_longlong)
     lib.mvicp_overlap.argtypes = [vp, dp, C.c_float, C.c_int, ip, ip, llp, ip]
     lib.mvicp_graph_from_overlap.argtypes = [C.c_int, ip, ip, llp, C.c_int, C.c_double, C.c_int, C.c_int, ip, ip, ip]
+    lib.mvicp_voxel_grid.argtypes = [vp, C.c_int, ip, dp, C.c_double, ip]
+    lib.mvicp_voxel_grid.restype = C.c_longlong
+    lib.mvicp_voxel_fetch.argtypes = [vp, C.c_longlong, vp, vp, vp]
     if path is None:
         _lib = lib
     return lib
@@ -452,6 +455,39 @@ class Engine:
         fraction = hits / np.maximum(samples, 1)[:, None].astype(np.float64)
         mean_d2 = np.ldexp(sumq / np.maximum(hits, 1).astype(np.float64), -q.value)
         return {"samples": samples, "hits": hits, "sumq": sumq, "q_exp": int(q.value), "fraction": fraction, "mean_d2": mean_d2}
+
+    def voxel_grid(self, voxel, frames=None, poses=None, device=False):
+        """mvicp_voxel_grid + mvicp_voxel_fetch: the points of `frames` (a list of distinct frame indices; None = all), at `poses` ((K,4,4);
+        None = as stored), reduced to one point per voxel of edge `voxel` -> dict(xyz (m,3), nrm (m,3) or None, cnt (m,) int32), rows in
+        ascending voxel key.  device=True: torch tensors on the engine's GPU (ready for set_frame_device) instead of numpy arrays.
+        Needs no graph; history-neutral."""
+        if frames is None:
+            n_sel, fp = 0, None
+        else:
+            fr = np.ascontiguousarray(frames, dtype=np.int32).reshape(-1)
+            n_sel = len(fr)
+            fr = np.concatenate([fr, np.zeros(1, dtype=np.int32)])   # (never a NULL pointer for an empty selection: NULL means "all")
+            fp = _ip(fr)
+        P = None if poses is None else poses_to_c(poses)
+        hn = C.c_int(0)
+        st = self.lib.mvicp_voxel_grid(self.h, n_sel, fp, _dp(P) if P is not None else None, float(voxel), C.byref(hn))
+        m = int(_check(self.lib, st))
+        has_nrm = bool(hn.value)
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            xyz = torch.empty((m, 3), dtype=torch.float64, device=dev)
+            nrm = torch.empty((m, 3), dtype=torch.float64, device=dev) if has_nrm else None
+            cnt = torch.empty((m,), dtype=torch.int32, device=dev)
+            torch.cuda.synchronize(dev)   # (the allocations are the caller's; the library fills them on its own stream and waits)
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and m else None
+        else:
+            xyz = np.zeros((m, 3), dtype=np.float64)
+            nrm = np.zeros((m, 3), dtype=np.float64) if has_nrm else None
+            cnt = np.zeros(m, dtype=np.int32)
+            ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and m else None
+        _check(self.lib, self.lib.mvicp_voxel_fetch(self.h, m, ptr(xyz), ptr(nrm), ptr(cnt)))
+        return {"xyz": xyz, "nrm": nrm, "cnt": cnt}
 
     def nn_query(self, frame, queries, nn_method=NN_AUTO):
         q = np.ascontiguousarray(queries, dtype=np.float64)
