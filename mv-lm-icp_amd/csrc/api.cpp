@@ -788,10 +788,10 @@ int mvicp_overlap(mvicp_ctx* c, const double* poses, float thresh, int max_sampl
   (void)std::frexp(B2, &ex);   // B2 = m 2^ex, m in [0.5, 1)
   const int q = 31 - ex;
   if (q_exp) *q_exp = q;
-  std::vector<double> xf(24 * (size_t)K * K, 0.0);
+  std::vector<double> xf(kXfRigid * (size_t)K * K, 0.0);
   for (int i = 0; i < K; ++i)
     for (int j = 0; j < K; ++j)
-      if (i != j) fill_query_xf(poses + 16 * (size_t)i, poses + 16 * (size_t)j, &xf[24 * ((size_t)i * K + j)]);
+      if (i != j) fill_query_xf(poses + 16 * (size_t)i, poses + 16 * (size_t)j, &xf[kXfRigid * ((size_t)i * K + j)]);
   return overlap_census(c, xf.data(), B2, std::ldexp(1.0, q), max_samples, samples, hits, sumq);
 } MVICP_GUARD_ABI
 
@@ -1060,7 +1060,7 @@ int mvicp_set_graph(mvicp_ctx* c, int n_edges, const int* src, const int* dst) t
   }
   c->spec_ready = false; c->spec_arm = false;
   c->spec2_ready = false; c->spec2_armed = false; c->last_cand_poses.clear();
-  c->prev_xf.assign((size_t)E * 24, 0.0);
+  c->prev_xf.assign((size_t)E * kXfRigid, 0.0);
   if (!c->h_census) MV_HIP(hipHostMalloc((void**)&c->h_census, 8 * sizeof(unsigned long long), hipHostMallocDefault));
   return MVICP_OK;
 } MVICP_GUARD_ABI
@@ -1069,7 +1069,7 @@ int mvicp_set_graph(mvicp_ctx* c, int n_edges, const int* src, const int* dst) t
 static void forget_history(mvicp_ctx* c) {
   const int E = c->E;
   c->nn_cache_valid = false; c->nn_cache_thresh = -1.f;
-  c->prev_q.assign((size_t)E * 12, 0.0); c->prev_xf.assign((size_t)E * 24, 0.0);
+  c->prev_q.assign((size_t)E * 12, 0.0); c->prev_xf.assign((size_t)E * kXfRigid, 0.0);
   c->nn_cache_edge.assign(E, 0);                      // no seeds, no temporal cache: d_nn_idx / d_nn_lb are dead until the next search rewrites them
   c->auto_prev_dist = 0.0; c->auto_last_method = -1; c->last_rms = -1.0; c->prev_grid_kernel = false;
   c->corr_tie_seen = c->corr_far_seen = 1u;
@@ -1176,14 +1176,14 @@ static int correspond_body(mvicp_ctx* c, const double* poses, const unsigned cha
     for (int i = 0; i < 3; ++i) Mq[9 + i] = x[12 + i] * dt[0] + x[12 + i + 3] * dt[1] + x[12 + i + 6] * dt[2];
     double* pq = &c->prev_q[(size_t)e * 12];
     double scale = 0.0;
-    for (int k = 0; k < 12; ++k) { x[25 + k] = Mq[k] - pq[k]; scale = std::max(scale, std::fabs(Mq[k])); }
+    for (int k = 0; k < 12; ++k) { x[kXfDM + k] = Mq[k] - pq[k]; scale = std::max(scale, std::fabs(Mq[k])); }
     const double rmax = c->frames[c->esrc[e]].max_norm;
     if (c->active[e]) {
       // how far this edge's queries can have moved since the last search, in units of the bounds-leaving builds' guard band: what decides the
       // temporal-cache hit rate of a cache-aware round before it runs (a hit needs d_new < d_old + mu - eps)
       double fro = 0.0;
-      for (int k = 0; k < 9; ++k) fro += x[25 + k] * x[25 + k];
-      const double eps_e = std::sqrt(fro) * rmax + std::sqrt(x[34] * x[34] + x[35] * x[35] + x[36] * x[36]);
+      for (int k = 0; k < 9; ++k) fro += x[kXfDM + k] * x[kXfDM + k];
+      const double eps_e = std::sqrt(fro) * rmax + std::sqrt(x[kXfDv] * x[kXfDv] + x[kXfDv + 1] * x[kXfDv + 1] + x[kXfDv + 2] * x[kXfDv + 2]);
       const double mu_e = c->tile_mu * c->frames[c->edst[e]].grid.cell;
       eps_ratio.push_back(mu_e > 0.0 ? eps_e / mu_e : 1e300);
     }
@@ -1192,15 +1192,15 @@ static int correspond_body(mvicp_ctx* c, const double* poses, const unsigned cha
     // allowance for the rounding of the fp64 query map itself (both evaluations): ~1e-16 (|M||p| + |v|), taken 1e4 times larger.
     // A transform that is BIT-IDENTICAL to last search's (a converged registration: the LM ends without stepping) reproduces every
     // query bit for bit: no allowance, and dM = dv = 0 below, so the kernel sees eps == 0 and re-verifies without rewriting anything.
-    double* pxf = &c->prev_xf[(size_t)e * 24];
+    double* pxf = &c->prev_xf[(size_t)e * kXfRigid];
     if (!c->owned[e]) unchanged[e] = 1;   // (another rank's edge: nothing of it lives here)
-    else if (c->active[e]) unchanged[e] = hist_ok && c->nn_cache_edge[e] && c->qpos_valid[e] && !c->explicit_list[e] && std::memcmp(pxf, x, sizeof(double) * 24) == 0;
+    else if (c->active[e]) unchanged[e] = hist_ok && c->nn_cache_edge[e] && c->qpos_valid[e] && !c->explicit_list[e] && std::memcmp(pxf, x, sizeof(double) * kXfRigid) == 0;
     else unchanged[e] = hist_ok && !c->nn_cache_edge[e] && !c->explicit_list[e] && c->h_count[e] == 0;   // not searched now, not searched then: stays empty
-    const bool same_xf = cache_on && std::memcmp(pxf, x, sizeof(double) * 24) == 0;
-    x[24] = cache_on ? (same_xf ? 0.0 : 1e-12 * (scale * (rmax + 1.0) + 1.0)) : -1.0;
+    const bool same_xf = cache_on && std::memcmp(pxf, x, sizeof(double) * kXfRigid) == 0;
+    x[kXfCache] = cache_on ? (same_xf ? 0.0 : 1e-12 * (scale * (rmax + 1.0) + 1.0)) : -1.0;
     same_edge[e] = same_xf;
-    std::memcpy(pxf, x, sizeof(double) * 24);
-    for (int k = 37; k < kEdgeXf; ++k) x[k] = 0.0;
+    std::memcpy(pxf, x, sizeof(double) * kXfRigid);
+    for (int k = kXfPad; k < kEdgeXf; ++k) x[k] = 0.0;
     std::memcpy(pq, Mq, sizeof(Mq));
   }
   // region 1 of the control block (xf | nsrc | dirty) goes up in ONE copy once the dirty flags are known (below)

@@ -37,9 +37,12 @@ constexpr int kLinPartial = 32;      // doubles per linearize workgroup partial 
 constexpr int kLinThreads = 256;
 constexpr int kCompactBlock = 1024;  // queries per compaction workgroup
 constexpr int kSelBlock = 8192;      // keys per radix-select workgroup
-constexpr int kEdgeXf = 40;          // Rs(9) ts(3) Rdinv(9) td(3), column-major; [24] = temporal-cache switch (>= 0: on, value =
-                                     // rounding allowance in metres), [25..36] = dM (9, col-major) dv (3): change of the query map
-                                     // q = M p + v since the last search, so a query moved by exactly |dM p + dv|
+constexpr int kEdgeXf = 40;          // doubles per edge of the query-transform block, laid out as:
+constexpr int kXfRigid = 24;         //   [0, 24): Rs(9) ts(3) Rdinv(9) td(3), column-major (what xf_point reads, nn_metric.h)
+constexpr int kXfCache = 24;         //   temporal-cache switch (>= 0: on, value = rounding allowance in metres; < 0: off)
+constexpr int kXfDM = 25;            //   dM (9, column-major) and
+constexpr int kXfDv = 34;            //   dv (3): change of the query map q = M p + v since the last search, so a query moved by exactly |dM p + dv|
+constexpr int kXfPad = 37;           //   [37, kEdgeXf): zero padding
 constexpr int kEdgeRel = 12;         // R_ds(9, column-major) t_ds(3)
 
 // Uniform grid (spatial hash) over one cloud; see nn_grid.hip.

@@ -4,7 +4,7 @@
 // include/nanoflann.hpp:900-911,1199-1247) and the per-query transform of
 // Frame::computeClosestPointsToNeighbours (frame.cpp:117-118,131,136).  Bit-exact contract: the
 // distance is the expression of include/frame.h:70-76 evaluated in fp64, left to right, WITHOUT fma
-// contraction (this TU is built with -ffp-contract=off and uses __dmul_rn/__dadd_rn/__dsub_rn), and
+// contraction (this TU is built with -ffp-contract=off; transform and metric are nn_metric.h's, shared with every NN kernel), and
 // the winner is the lowest index among equal distances (strict '<' over an ascending scan); a query whose best distance was met more
 // than once is REPORTED (nn_tie.h) and re-answered the way the reference's tree decides such ties.
 //
@@ -16,6 +16,7 @@
 #include "common.h"
 #include <cstring>
 
+#include "nn_metric.h"
 #include "nn_tie.h"
 
 namespace mvicp {
@@ -35,19 +36,6 @@ struct BruteJob {
   const int* inv;                // target original index -> sorted position (null: emit original indices)
   TieRef tie;
 };
-
-__device__ __forceinline__ void xf_point(const double* __restrict__ x, double p0, double p1, double p2, double& q0, double& q1, double& q2) {
-  // g_i = ((R(i,0) p0 + R(i,1) p1) + R(i,2) p2) + t_i ; u = g - t_d ; q_i = (Ri(i,0) u0 + Ri(i,1) u1) + Ri(i,2) u2
-  double g[3], u[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-    g[i] = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(x[i], p0), __dmul_rn(x[i + 3], p1)), __dmul_rn(x[i + 6], p2)), x[9 + i]);
-#pragma unroll
-  for (int i = 0; i < 3; ++i) u[i] = __dsub_rn(g[i], x[21 + i]);
-  q0 = __dadd_rn(__dadd_rn(__dmul_rn(x[12 + 0], u[0]), __dmul_rn(x[12 + 3], u[1])), __dmul_rn(x[12 + 6], u[2]));
-  q1 = __dadd_rn(__dadd_rn(__dmul_rn(x[12 + 1], u[0]), __dmul_rn(x[12 + 4], u[1])), __dmul_rn(x[12 + 7], u[2]));
-  q2 = __dadd_rn(__dadd_rn(__dmul_rn(x[12 + 2], u[0]), __dmul_rn(x[12 + 5], u[1])), __dmul_rn(x[12 + 8], u[2]));
-}
 
 __global__ __launch_bounds__(NT) void nn_brute_kernel(const BruteJob* __restrict__ jobs, int n_splits, int* __restrict__ split_idx,
                                                       double* __restrict__ split_d2, const long long* __restrict__ split_off) {
@@ -98,8 +86,7 @@ __global__ __launch_bounds__(NT) void nn_brute_kernel(const BruteJob* __restrict
       const double x = sx[j], y = sy[j], z = sz[j];
 #pragma unroll
       for (int i = 0; i < QPT; ++i) {
-        const double d0 = __dsub_rn(qx[i], x), d1 = __dsub_rn(qy[i], y), d2 = __dsub_rn(qz[i], z);
-        const double d = __dadd_rn(__dadd_rn(__dmul_rn(d0, d0), __dmul_rn(d1, d1)), __dmul_rn(d2, d2));
+        const double d = dist2(qx[i], qy[i], qz[i], x, y, z);
         if (d < best[i]) { best[i] = d; bi[i] = base + j; tie[i] = false; }
         else if (d == best[i]) tie[i] = true;
       }

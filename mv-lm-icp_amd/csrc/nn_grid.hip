@@ -38,6 +38,8 @@
 
 #include "build_common.h"
 #include "common.h"
+#include "nn_cache.h"
+#include "nn_census.h"
 #include "nn_list.h"
 #include "nn_metric.h"
 #include "nn_tie.h"
@@ -69,9 +71,7 @@ struct GridJob {
   int n;
   int* out_idx; double* out_d2;
   const int* inv;      // target original index -> sorted position (null: emit original indices, raw-query API)
-  // "did anything change?" bookkeeping of the edge's compacted list (all null for the raw-query API)
-  const int* qpos; int* second; double* cd2; const int* dirty; int* dirty_slots;  // dirty: host-forced flag; slots: one per NT queries
-  double* stream; long long total_cap; const double* dst_nor;   // the edge's slice of the packed operand stream (linearize.hip) + sorted dst normals
+  ListRef list;        // "did anything change?" bookkeeping of the edge's compacted list (nn_list.h; list.dirty null: none, the raw-query API)
   float* out_lb;       // per query: lower bound on the distance to every target other than out_idx, fp32 ROUNDED DOWN (null: no cache)
   int seed;            // out_idx still holds last round's neighbours (from any kernel): a starting candidate for far queries
   TieRef tie;          // where queries whose best distance was met by more than one target are reported (nn_tie.h)
@@ -91,12 +91,6 @@ __device__ __forceinline__ unsigned long long __reduce_add_u64(unsigned long lon
 __device__ __forceinline__ bool __lane0() {
   const unsigned long long mask = __ballot(1);
   return (int)(threadIdx.x & 63) == __ffsll((long long)mask) - 1;
-}
-
-// list maintenance shared with the tile kernel: nn_list.h
-__device__ __forceinline__ void update_list(const GridJob& job, int i, int idx_new, double d2_new, double bound, bool same_neighbour = false) {
-  const ListRef R{job.qpos, job.second, job.cd2, job.dirty, job.dirty_slots, job.stream, job.total_cap, job.dst_nor, job.dst.srec};
-  update_list_entry(R, i, idx_new, d2_new, bound, same_neighbour);
 }
 
 // Also leaves the slots zeroed for the next round (no memsets in the per-round launch sequence).
@@ -139,11 +133,8 @@ __global__ __launch_bounds__(NT) void nn_grid_kernel(const GridJob* __restrict__
   unsigned int n_cand = 0;
   double second = 1.7976931348623157e308;
 
-  // ---- temporal cache.  Last search left, per query, its neighbour p1 and a lower bound L on the distance to every
-  // OTHER target.  Since then the query moved by at most eps (pose update), so every other target is still >= L - eps
-  // away; if the re-evaluated distance to p1 is strictly below that, p1 is still the unique nearest neighbour and its
-  // exact squared distance (reference arithmetic) is the answer — no search.  Relative 1e-12 slack covers sqrt rounding.
-  const double slack = has_xf ? sxf[24] : -1.0;
+  // ---- temporal cache (nn_cache.h): a query whose old neighbour p1 is provably still nearest keeps it, at its re-evaluated distance — no search.
+  const double slack = has_xf ? sxf[kXfCache] : -1.0;
   // Last round's neighbour p1 (sorted position in out_idx, left there by whichever kernel ran) serves twice:
   //  * temporal cache (needs last round's lower bounds, i.e. a grid round): re-evaluate the distance and stop;
   //  * otherwise its distance bounds the search: the true neighbour lies within |q - p1| of q, so hash cells of the block
@@ -153,9 +144,7 @@ __global__ __launch_bounds__(NT) void nn_grid_kernel(const GridJob* __restrict__
   double rp2 = -1.0;   // < 0: scan the whole block
   if (!TREE_ONLY && job.seed) {
     const int pi = job.out_idx[out];   // sorted position of last round's neighbour
-    if (pi < 0 && slack == 0.0 && job.out_lb != nullptr && job.out_lb[out] == -1.f) {
-      // last search found NO target within the search radius, and the host found this edge's query transform bit-identical to that
-      // search's (slack 0: dM = dv = 0): the same query has the same answer — nothing to search, nothing to write
+    if (pi < 0 && job.out_lb != nullptr && cache_still_none(slack, job.out_lb, out)) {
       if (stats) {
         unsigned long long c1 = __reduce_add_u64(1ull);
         const size_t slot = ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * (NT / 64) + (threadIdx.x >> 6);
@@ -168,22 +157,11 @@ __global__ __launch_bounds__(NT) void nn_grid_kernel(const GridJob* __restrict__
       const double* tp = g.spts + 3 * (size_t)pi;
       const double d = dist2(qx, qy, qz, tp[0], tp[1], tp[2]);
       if (slack >= 0.0 && job.out_lb != nullptr) {
-        // how far THIS query moved since the last search: |dM p + dv| (exactly, up to the rounding allowance)
         const double p0 = job.q[3 * (size_t)i], p1 = job.q[3 * (size_t)i + 1], p2 = job.q[3 * (size_t)i + 2];
-        const double e0 = sxf[25] * p0 + sxf[28] * p1 + sxf[31] * p2 + sxf[34];
-        const double e1 = sxf[26] * p0 + sxf[29] * p1 + sxf[32] * p2 + sxf[35];
-        const double e2 = sxf[27] * p0 + sxf[30] * p1 + sxf[33] * p2 + sxf[36];
-        const double eps = sqrt(e0 * e0 + e1 * e1 + e2 * e2) * (1.0 + 1e-9) + slack;
-        const double nlb = (double)job.out_lb[out] - eps;
-        // eps == 0 only when the host found the edge's query transform bit-identical to last search's (slack 0, dM = dv = 0): the query is
-        // the same bit for bit, so last search's exact answer — whatever its bound — its distance, its bound and its list entry are exactly
-        // what is stored already: nothing to search, nothing to write
-        if (eps == 0.0 || sqrt(d) * (1.0 + 1e-12) < nlb) {
-          if (eps != 0.0) {
-            job.out_d2[out] = d;
-            job.out_lb[out] = __double2float_rd(nlb);
-            if (job.dirty) update_list(job, i, pi, d, bound, true);
-          }
+        const double eps = cache_eps(sxf, p0, p1, p2);
+        const float lb_old = job.out_lb[out];
+        if (cache_hit(eps, lb_old, d, bound, true, false)) {
+          cache_refresh(job, out, pi, d, eps, lb_old, bound);
           if (stats) {
             unsigned long long c1 = __reduce_add_u64(1ull);
             const size_t slot = ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * (NT / 64) + (threadIdx.x >> 6);
@@ -290,7 +268,7 @@ __global__ __launch_bounds__(NT) void nn_grid_kernel(const GridJob* __restrict__
   job.out_d2[out] = best;
   // every other target is either a scanned candidate (>= second) or outside the block (>= m)
   if (job.out_lb != nullptr) job.out_lb[out] = resolved ? __double2float_rd(sqrt(fmin(fmin(second, m2), skipped)) * (1.0 - 1e-12)) : 0.f;
-  if (job.dirty && (resolved || skip_far)) update_list(job, i, bi == 0x7fffffff ? -1 : job.inv[bi], best, bound);
+  if (job.list.dirty && (resolved || skip_far)) update_list_entry(job.list, i, bi == 0x7fffffff ? -1 : job.inv[bi], best, bound, false);
   if (resolved && bi != 0x7fffffff && second == best) tie_report(job.tie, (unsigned int)i);   // another target at exactly the same distance
   if (!resolved && !skip_far) {
     // wave-aggregated append: one atomic per wave
@@ -475,20 +453,12 @@ __global__ __launch_bounds__(NT, 5) void nn_cell_kernel(const GridJob* __restric
     if (pi >= 0 && pi < g.n) {
       const double* tp = g.spts + 3 * (size_t)pi;
       const double d = dist2(L.qx, L.qy, L.qz, tp[0], tp[1], tp[2]);
-      const double slack = sxf[24];
-      if (slack >= 0.0 && job.out_lb != nullptr) {
-        // temporal cache (see nn_grid_kernel): how far THIS query moved since the last search is |dM p + dv|
-        const double e0 = sxf[25] * p0 + sxf[28] * p1 + sxf[31] * p2 + sxf[34];
-        const double e1 = sxf[26] * p0 + sxf[29] * p1 + sxf[32] * p2 + sxf[35];
-        const double e2 = sxf[27] * p0 + sxf[30] * p1 + sxf[33] * p2 + sxf[36];
-        const double eps = sqrt(e0 * e0 + e1 * e1 + e2 * e2) * (1.0 + 1e-9) + slack;
-        const double nlb = (double)job.out_lb[i] - eps;
-        if (sqrt(d) * (1.0 + 1e-12) < nlb) {
-          if (eps != 0.0) {   // (eps == 0: bit-identical query transform, everything stored is already exact — see nn_grid_kernel)
-            job.out_d2[i] = d;
-            job.out_lb[i] = __double2float_rd(nlb);
-            if (job.dirty) update_list(job, i, pi, d, bound, true);
-          }
+      if (sxf[kXfCache] >= 0.0 && job.out_lb != nullptr) {
+        // temporal cache (nn_cache.h), without the bit-identical-query shortcut: a hit is always proven by the distance test
+        const double eps = cache_eps(sxf, p0, p1, p2);
+        const float lb_old = job.out_lb[i];
+        if (cache_hit(eps, lb_old, d, bound, false, false)) {
+          cache_refresh(job, i, pi, d, eps, lb_old, bound);
           hit = true;
         }
       }
@@ -598,7 +568,7 @@ __global__ __launch_bounds__(NT, 5) void nn_cell_kernel(const GridJob* __restric
     // every target that was not scanned is at least R1 away: outside the ball, or in a home cell beyond sqrt(TA2) >= R1
     if (job.out_lb != nullptr) job.out_lb[i] = resolved ? __double2float_rd(sqrt(fmin(L.second, R1 * R1 * (1.0 - 1e-9))) * (1.0 - 1e-12)) : 0.f;
     if (resolved) {
-      if (job.dirty) update_list(job, i, L.bpos, L.best, bound);
+      if (job.list.dirty) update_list_entry(job.list, i, L.bpos, L.best, bound, false);
     } else {
       const unsigned long long mask = __ballot(1);
       const int leader = __ffsll((long long)mask) - 1;
@@ -741,7 +711,7 @@ __global__ __launch_bounds__(NT) void nn_far_kernel(const GridJob* __restrict__ 
       // every other target was scanned (>= second) or sits in a skipped box (>= its lower bound)
       // (-1: no target within the search radius — re-usable as it is while the query does not move at all, see the prologue of phase 1)
       if (job.out_lb != nullptr) job.out_lb[out] = bi == 0x7fffffff ? -1.f : __double2float_rd(sqrt(fmin(second, pruned)) * (1.0 - 1e-12));
-      if (job.dirty) update_list(job, i, bi == 0x7fffffff ? -1 : job.inv[bi], best, bound);
+      if (job.list.dirty) update_list_entry(job.list, i, bi == 0x7fffffff ? -1 : job.inv[bi], best, bound, false);
       if (bi != 0x7fffffff && second == best) tie_report(job.tie, (unsigned int)i);
     }
   }
@@ -751,21 +721,6 @@ __global__ __launch_bounds__(NT) void nn_far_kernel(const GridJob* __restrict__ 
     c = __reduce_add_u64(c); nd = __reduce_add_u64(nd);
     const size_t slot = ((size_t)blockIdx.x * (NT / 64) + (threadIdx.x >> 6)) % stats_slots;
     if (__lane0()) { atomicAdd(&stats[8 * slot], c); atomicAdd(&stats[8 * slot + 1], nd); }
-  }
-}
-
-// sums the per-wave census slots (8 counters each) into out8 (zeroed by the caller); 64 workgroups, 8 atomics each
-__global__ __launch_bounds__(256) void census_sum_kernel(const unsigned long long* __restrict__ stats, size_t slots, unsigned long long* __restrict__ out8) {
-  __shared__ unsigned long long sh[8][256];
-  unsigned long long v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < slots; i += (size_t)gridDim.x * 256)
-    for (int k = 0; k < 8; ++k) v[k] += stats[8 * i + k];
-  for (int k = 0; k < 8; ++k) sh[k][threadIdx.x] = v[k];
-  __syncthreads();
-  if (threadIdx.x < 8) {
-    unsigned long long s = 0;
-    for (int i = 0; i < 256; ++i) s += sh[threadIdx.x][i];
-    atomicAdd(&out8[threadIdx.x], s);
   }
 }
 
@@ -997,7 +952,7 @@ int run(mvicp_ctx* c, std::vector<GridJob>& jobs, double bound, const FrameDev* 
   if (jobs.empty()) return MVICP_OK;
   const double search = search_bound(c, bound);
   std::vector<TieJob> ties;
-  if (!(c->tie_skip && jobs[0].dirty_slots != nullptr)) {
+  if (!(c->tie_skip && jobs[0].list.dirty_slots != nullptr)) {
     double launch_q = 0;
     for (const GridJob& j : jobs) launch_q += j.n;
     const TieRef tref = tie_ref(c, (size_t)launch_q, 0u);
@@ -1007,8 +962,7 @@ int run(mvicp_ctx* c, std::vector<GridJob>& jobs, double bound, const FrameDev* 
       TieJob t;
       std::memset(&t, 0, sizeof(t));
       tie_job_fill(*dst_of[k], t);
-      t.q = j.q; t.xf = j.xf; t.n = j.n; t.out_idx = j.out_idx; t.out_d2 = j.out_d2; t.inv = j.inv;
-      t.list = ListRef{j.qpos, j.second, j.cd2, j.dirty, j.dirty_slots, j.stream, j.total_cap, j.dst_nor, j.dst.srec};
+      t.q = j.q; t.xf = j.xf; t.n = j.n; t.out_idx = j.out_idx; t.out_d2 = j.out_d2; t.inv = j.inv; t.list = j.list;
       ties.push_back(t);
     }
   }
@@ -1020,16 +974,7 @@ int run(mvicp_ctx* c, std::vector<GridJob>& jobs, double bound, const FrameDev* 
   MV_CHECK(cached_upload(c, jobs[0].xf ? "grid_jobs" : "grid_jobs_raw", jobs.data(), sizeof(GridJob) * jobs.size(), (void**)&d_jobs));
   unsigned long long* d_stats = nullptr;
   const size_t slots = (size_t)((max_n + NT - 1) / NT) * jobs.size() * (NT / 64);
-  if (c->profile && c->nn_census) {
-    const size_t need = sizeof(unsigned long long) * 8 * (slots + 1);
-    if (need > c->census_bytes) {
-      if (c->d_census) MV_HIP(hipFree(c->d_census));
-      MV_HIP(hipMalloc((void**)&c->d_census, need));
-      c->census_bytes = need;
-    }
-    d_stats = (unsigned long long*)c->d_census;
-    MV_HIP(hipMemsetAsync(d_stats, 0, need, c->stream));
-  }
+  MV_CHECK(census_scratch(c, slots, &d_stats));
   // far list: (job, query) pairs, worst case every query
   const size_t total_q = (size_t)nq;
   if (total_q > c->far_cap) {
@@ -1037,7 +982,7 @@ int run(mvicp_ctx* c, std::vector<GridJob>& jobs, double bound, const FrameDev* 
     MV_HIP(hipMalloc((void**)&c->d_far_list, sizeof(int2) * total_q));
     c->far_cap = total_q;
   }
-  const bool edge_path = jobs[0].dirty_slots != nullptr;   // dirty_reduce_kernel re-zeroes the counter after phase 2
+  const bool edge_path = jobs[0].list.dirty_slots != nullptr;   // dirty_reduce_kernel re-zeroes the counter after phase 2
   if (!c->d_far_count) {
     MV_HIP(hipMalloc((void**)&c->d_far_count, 2 * sizeof(unsigned int)));
     MV_HIP(hipMemsetAsync(c->d_far_count, 0, 2 * sizeof(unsigned int), c->stream));
@@ -1088,13 +1033,7 @@ int run(mvicp_ctx* c, std::vector<GridJob>& jobs, double bound, const FrameDev* 
       hipLaunchKernelGGL(dirty_reduce_kernel, dim3(c->E), dim3(256), 0, c->stream, c->E, c->d_dslot_off, c->d_dirty_slots, c->d_dirty);
   }
   MV_HIP(hipGetLastError());
-  if (d_stats) {
-    if (!c->h_census) MV_HIP(hipHostMalloc((void**)&c->h_census, 8 * sizeof(unsigned long long), hipHostMallocDefault));
-    // counters -> pinned memory, asynchronously; census_resolve() folds them in after the caller's own wait (no extra sync)
-    hipLaunchKernelGGL(census_sum_kernel, dim3(64), dim3(256), 0, c->stream, d_stats, slots, d_stats + 8 * slots);
-    MV_HIP(hipMemcpyAsync(c->h_census, d_stats + 8 * slots, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    c->census_pending = true; c->census_nq = nq; c->census_kind = c->nn_tree_only ? 1 : (use_cell ? 3 : 0); c->census_scope = "nn_grid";
-  }
+  if (d_stats) MV_CHECK(census_collect(c, d_stats, slots, nq, c->nn_tree_only ? 1 : (use_cell ? 3 : 0), "nn_grid"));
   MV_CHECK(launch_tie_fixup(c, ties, bound));   // exact distance ties: the reference's own descent decides (nn_tie.hip)
   return MVICP_OK;
 }
@@ -1136,9 +1075,8 @@ int launch_nn_grid_edges(mvicp_ctx* c, double d2_bound) {
     j.q = s.grid.spts; j.qidx = nullptr; j.xf = c->d_xf + (size_t)e * kEdgeXf; j.n = s.n;
     j.out_idx = c->d_nn_idx + c->cap_off[e]; j.out_d2 = c->d_nn_d2 + c->cap_off[e];
     j.inv = d.grid.inv; j.out_lb = c->d_nn_lb + c->cap_off[e];
-    j.qpos = c->d_qpos + c->cap_off[e]; j.second = c->d_second + c->cap_off[e]; j.cd2 = c->d_cd2 + c->cap_off[e]; j.dirty = c->d_dirty + e;
-    j.stream = c->d_stream + c->cap_off[e]; j.total_cap = c->total_cap; j.dst_nor = d.grid.snor;
-    j.dirty_slots = c->d_dirty_slots + c->dslot_off[e];
+    j.list = ListRef{c->d_qpos + c->cap_off[e], c->d_second + c->cap_off[e], c->d_cd2 + c->cap_off[e], c->d_dirty + e, c->d_dirty_slots + c->dslot_off[e],
+                     c->d_stream + c->cap_off[e], c->total_cap, d.grid.snor, (const PointRec*)d.grid.srec};
     j.seed = ((int)c->nn_cache_edge.size() == c->E && c->nn_cache_edge[e]) ? 1 : 0;
     jobs.push_back(j); dsts.push_back(&d);
   }
@@ -1152,9 +1090,7 @@ int launch_nn_grid_queries(mvicp_ctx* c, const FrameDev& f, const double* d_q, i
   jobs[0].dst = view_of(f);
   jobs[0].q = d_q; jobs[0].qidx = nullptr; jobs[0].xf = nullptr; jobs[0].n = n;
   jobs[0].out_idx = d_idx; jobs[0].out_d2 = d_d2;
-  jobs[0].inv = nullptr; jobs[0].out_lb = nullptr;
-  jobs[0].qpos = nullptr; jobs[0].second = nullptr; jobs[0].cd2 = nullptr; jobs[0].dirty = nullptr; jobs[0].dirty_slots = nullptr;
-  jobs[0].stream = nullptr; jobs[0].total_cap = 0; jobs[0].dst_nor = nullptr;
+  jobs[0].inv = nullptr; jobs[0].out_lb = nullptr;   // (list stays zeroed: list.dirty null = no list to maintain)
   const FrameDev* dst = &f;
   return run(c, jobs, 1.7976931348623157e308, &dst);
 }

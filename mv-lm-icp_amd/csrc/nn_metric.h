@@ -1,4 +1,4 @@
-// The rounded operations every exact NN kernel shares (nn_grid.hip, overlap.hip): the query transform of
+// The rounded operations every exact NN kernel shares (brute, grid, tile, matrix-pipe, tie fix-up, normals, overlap): the query transform of
 // Frame::computeClosestPointsToNeighbours (frame.cpp:117-118,131,136), the reference metric (frame.h:70-76, no fma) and the lower
 // bound of a query to an outward-rounded float box of the implicit 8-ary tree, evaluated in the SAME rounded operations as the
 // point distance (every rounding is monotone, so lb <= d2 for every point inside the box: DESIGN.md §3.4).
@@ -9,7 +9,8 @@ namespace mvicp {
 
 constexpr int OCT_STACK = 56;  // entries of an octet's descent stack: >= 7 * max depth + 1 (build_grid keeps the depth <= 7)
 
-// x = the first 24 doubles of an edge's kEdgeXf: Rs(9) ts(3) Rd^-1(9) td(3), column-major
+// x = the rigid part of an edge's kEdgeXf (common.h, kXfRigid doubles): Rs(9) ts(3) Rd^-1(9) td(3), column-major
+// g_i = ((R(i,0) p0 + R(i,1) p1) + R(i,2) p2) + t_i ; u = g - t_d ; q_i = (Ri(i,0) u0 + Ri(i,1) u1) + Ri(i,2) u2
 __device__ __forceinline__ void xf_point(const double* __restrict__ x, double p0, double p1, double p2, double& q0, double& q1, double& q2) {
   double g[3], u[3];
 #pragma unroll

@@ -55,10 +55,9 @@ struct LaneM {         // per-lane query state
   float a2, amax, dab;   // |a~|^2, max |alpha coordinate|, delta_a + delta_b (all in the block's scaled units)
   bool inrange;
 };
-struct GroupM {        // wave-uniform patch description
-  float lo[3], hi[3], c[3];
-  float kacc; int trig;   // job tunables
-  float slack, mu, m;  // fp32 box-test guard band (metres), BND extra guard band, largest coordinate magnitude of cloud and patch
+struct GroupM : PatchBox {   // wave-uniform patch description (nn_tile_common.h)
+  float m;               // largest coordinate magnitude of cloud and patch
+  float kacc; int trig;  // job tunables
 };
 
 __device__ __forceinline__ float box_lb32(const LaneM& L, float b0, float b1, float b2, float b3, float b4, float b5) {
@@ -186,8 +185,7 @@ __device__ __forceinline__ bool confirm(const TileView& g, int tile, LaneM& L, u
       const double2* pr = reinterpret_cast<const double2*>(g.srec + k);
       u = pr[0]; v = pr[1];
     }
-    const double d0 = __dsub_rn(L.qx, u.x), d1 = __dsub_rn(L.qy, u.y), d2 = __dsub_rn(L.qz, v.x);
-    const double d = __dadd_rn(__dadd_rn(__dmul_rn(d0, d0), __dmul_rn(d1, d1)), __dmul_rn(d2, d2));
+    const double d = dist2(L.qx, L.qy, L.qz, u.x, u.y, v.x);
     const int oi = (int)__double_as_longlong(v.y);
     // strictly nearer: the new best.  EXACTLY as near as the best (rare): the lower original index keeps the place for now and the query
     // is reported, so that nn_tie.hip lets the reference's own tree decide (nanoflann keeps the target it visits first)
@@ -365,34 +363,12 @@ __device__ void visit(const TileView& g, int first, int nchild, LaneM& L, const 
   if constexpr (LEVEL == 0) { scan_block<BND, CEN, LBT>(g, first, nchild, L, G, C, G.kacc, G.trig, sbox + 2 * 3 * FAN); return; } else {
   const int lane = threadIdx.x & 63;
   const float inf = __int_as_float(0x7f800000);
-  float b0 = inf, b1 = inf, b2 = inf, b3 = -inf, b4 = -inf, b5 = -inf;
-  if (lane < nchild) {
-    const float* base = g.wide + g.off[LEVEL] + first + lane;
-    const long long st = g.cnt[LEVEL];
-    b0 = base[0]; b1 = base[st]; b2 = base[2 * st]; b3 = base[3 * st]; b4 = base[4 * st]; b5 = base[5 * st];
-  }
+  const NodeBoxes B = node_fetch<LEVEL>(g, first, nchild);
   float ddf, key;
-  {
-    const float e0 = fmaxf(fmaxf(b0 - G.hi[0], G.lo[0] - b3), 0.f);
-    const float e1 = fmaxf(fmaxf(b1 - G.hi[1], G.lo[1] - b4), 0.f);
-    const float e2 = fmaxf(fmaxf(b2 - G.hi[2], G.lo[2] - b5), 0.f);
-    ddf = (e0 * e0 + e1 * e1 + e2 * e2) * 0.999999f;
-    const float k0 = fmaxf(fmaxf(b0 - G.c[0], G.c[0] - b3), 0.f);
-    const float k1 = fmaxf(fmaxf(b1 - G.c[1], G.c[1] - b4), 0.f);
-    const float k2 = fmaxf(fmaxf(b2 - G.c[2], G.c[2] - b5), 0.f);
-    key = k0 * k0 + k1 * k1 + k2 * k2;
-  }
+  node_cull(G, B, ddf, key);
   float2* mybox = sbox + (LEVEL > 0 ? (LEVEL - 1) * 3 * FAN : 0);   // levels 1 and 2 park their boxes in wave-private LDS
   constexpr bool IN_LDS = LEVEL == 1 || LEVEL == 2;
-  if (IN_LDS) {
-    __builtin_amdgcn_wave_barrier();
-    mybox[lane] = make_float2(b0, b3);
-    mybox[FAN + lane] = make_float2(b1, b4);
-    mybox[2 * FAN + lane] = make_float2(b2, b5);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  }
+  if (IN_LDS) node_park(mybox, B);
   MV_CEN(C.box += (unsigned)nchild);
   bool pend = lane < nchild;
   const float sm = G.slack + G.mu;
@@ -404,14 +380,8 @@ __device__ void visit(const TileView& g, int first, int nchild, LaneM& L, const 
     const unsigned long long pick = __ballot(pend && key == kmin);
     const int c = __builtin_amdgcn_readfirstlane(__ffsll((long long)pick) - 1);
     if (lane == c) pend = false;
-    float c0, c1, c2, c3, c4, c5;
-    if (IN_LDS) {
-      const float2 u = mybox[c], v = mybox[FAN + c], w = mybox[2 * FAN + c];
-      c0 = u.x; c3 = u.y; c1 = v.x; c4 = v.y; c2 = w.x; c5 = w.y;
-    } else {
-      c0 = bcast(b0, c); c1 = bcast(b1, c); c2 = bcast(b2, c); c3 = bcast(b3, c); c4 = bcast(b4, c); c5 = bcast(b5, c);
-    }
-    const float lb = box_lb32(L, c0, c1, c2, c3, c4, c5);
+    const NodeBoxes Cb = node_child<IN_LDS>(mybox, B, c);
+    const float lb = box_lb32(L, Cb.b0, Cb.b1, Cb.b2, Cb.b3, Cb.b4, Cb.b5);
     if (__ballot(L.active && lb <= box_thr(L.rbest, sm)) == 0ull) continue;
     const int cf = (first + c) * FAN;
     visit<(LEVEL > 0 ? LEVEL - 1 : 0), BND, CEN, LBT>(g, cf, min(FAN, g.cnt[LEVEL > 0 ? LEVEL - 1 : 0] - cf), L, G, sbox, C);
@@ -492,11 +462,7 @@ __global__ __launch_bounds__(MT, WPE) void nn_mfma_kernel(const TileJob* __restr
   L.qx = L.qy = L.qz = 0.0;
   L.a2 = 0.f; L.amax = 0.f; L.dab = 0.f; L.inrange = false;
   double p0 = 0.0, p1 = 0.0, p2 = 0.0;
-  if (L.active) {
-    p0 = job.q[3 * (size_t)i]; p1 = job.q[3 * (size_t)i + 1]; p2 = job.q[3 * (size_t)i + 2];
-    if (has_xf) xf_point(sxf, p0, p1, p2, L.qx, L.qy, L.qz);
-    else { L.qx = p0; L.qy = p1; L.qz = p2; }
-  }
+  load_query(job, sxf, has_xf, i, L, p0, p1, p2);
   // Seed: last round's neighbour is an ordinary candidate; starting from its distance lets the traversal discard almost every tile
   // that does not hold a true neighbour of some lane.  Its slot is masked when its tile is screened (tile_scan).
   int seed_pi = -1;
@@ -506,57 +472,19 @@ __global__ __launch_bounds__(MT, WPE) void nn_mfma_kernel(const TileJob* __restr
     if (pi >= 0 && pi < g.n) {
       const double2* pr = reinterpret_cast<const double2*>(g.srec + pi);
       const double2 u = pr[0], v = pr[1];
-      const double d0 = __dsub_rn(L.qx, u.x), d1 = __dsub_rn(L.qy, u.y), d2 = __dsub_rn(L.qz, v.x);
-      const double d = __dadd_rn(__dadd_rn(__dmul_rn(d0, d0), __dmul_rn(d1, d1)), __dmul_rn(d2, d2));
+      const double d = dist2(L.qx, L.qy, L.qz, u.x, u.y, v.x);
       seed_pi = pi; seed_d = d;
       if (d <= L.best) { L.best = d; L.bi = (int)__double_as_longlong(v.y); L.bpos = pi; }
     }
   }
-  // Temporal cache (BND builds in cache-aware rounds): see nn_tile.hip — a lane whose neighbour provably did not change is finished here.
   unsigned int n_hit = 0;
-  if (BND && job.cache && has_xf && job.seed && L.active && seed_pi < 0 && sxf[24] == 0.0 && job.out_lb[i] == -1.f) {
-    // last search found NO target within the search radius and this edge's query transform is bit-identical to that search's (allowance 0:
-    // dM = dv = 0): the query is the same, so is the answer — nothing to search, nothing to write
-    L.active = false;
-    n_hit = 1;
-  }
-  if (BND && job.cache && has_xf && seed_pi >= 0) {
-    const double cslack = sxf[24];
-    if (cslack >= 0.0) {
-      const double e0 = sxf[25] * p0 + sxf[28] * p1 + sxf[31] * p2 + sxf[34];
-      const double e1 = sxf[26] * p0 + sxf[29] * p1 + sxf[32] * p2 + sxf[35];
-      const double e2 = sxf[27] * p0 + sxf[30] * p1 + sxf[33] * p2 + sxf[36];
-      const double eps = sqrt(e0 * e0 + e1 * e1 + e2 * e2) * (1.0 + 1e-9) + cslack;
-      const double nlb = (double)job.out_lb[i] - eps;
-      // ... or (round 6) the query is provably still REJECTED: its old neighbour is beyond the cutoff now (exact) and every other target was at least
-      // out_lb away, i.e. is at least nlb away now — if that is beyond the cutoff too, no target is inside it, which is all the reference's filter
-      // (frame.cpp:156) asks; the exact neighbour of a rejected query is never output.  out_d2 then holds the distance to the OLD neighbour (>= bound:
-      // the query stays rejected downstream), out_idx keeps it as a seed, the bound is carried on.  These are the lanes with the LARGEST balls (their
-      // thresholds reach the search radius): taking them out of the traversal is what makes a partial-overlap round cheap.
-      const bool still_rejected = eps != 0.0 && seed_d >= bound && nlb > sqrt(bound) * (1.0 + 1e-9);
-      if (eps == 0.0 || sqrt(seed_d) * (1.0 + 1e-12) < nlb || (job.reject_cache && still_rejected)) {   // (eps == 0: the same query bit for bit keeps last search's exact answer)
-        if (eps != 0.0) {   // (eps == 0: bit-identical query transform, everything stored is already exact)
-          job.out_d2[i] = seed_d;
-          job.out_lb[i] = __double2float_rd(nlb);
-          if (job.list.dirty) update_list_entry(job.list, i, seed_pi, seed_d, bound, true);
-        }
-        L.active = false;
-        n_hit = 1;
-      }
-    }
-  }
-  if (BND && job.cache && __ballot(L.active) == 0ull) {
-    if (stats) {   // census (profiling only): all 64 lanes answered by the cache
-      const size_t slot = ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * (MT / 64) + wave;
-      const unsigned long long hits = __popcll(__ballot(n_hit != 0u));
-      if ((threadIdx.x & 63) == 0) stats[8 * slot + 3] = hits;
-    }
-    return;
-  }
+  cache_prologue<BND>(job, sxf, has_xf, i, p0, p1, p2, seed_pi, seed_d, bound, L.active, n_hit);
+  if (cache_all_hit<BND, MT>(job, L.active, n_hit, stats)) return;
   GroupM G;   // wave-uniform: lives in SGPRs
   {
     const float qxf = (float)L.qx, qyf = (float)L.qy, qzf = (float)L.qz;
-    // patch box in fp32, rounded outward (nn_tile.hip)
+    // patch box in fp32, rounded outward: the statements of patch_box (nn_tile_common.h), kept in place — as a call, four builds of this
+    // kernel come out with other register / scratch counts (profiles/nn_shared_rules.txt)
     const float inf = __int_as_float(0x7f800000);
     float lo[3] = {wave_min_any(L.active ? qxf : inf), wave_min_any(L.active ? qyf : inf), wave_min_any(L.active ? qzf : inf)};
     float hi[3] = {wave_max_any(L.active ? qxf : -inf), wave_max_any(L.active ? qyf : -inf), wave_max_any(L.active ? qzf : -inf)};
@@ -586,16 +514,8 @@ __global__ __launch_bounds__(MT, WPE) void nn_mfma_kernel(const TileJob* __restr
     case 3: visit<3, BND, CEN, LBT>(g, 0, g.cnt[3], L, G, sbox, C); break;
     default: visit<4, BND, CEN, LBT>(g, 0, g.cnt[4], L, G, sbox, C); break;
   }
-  if (L.active) {
-    const int out = i;   // sorted order of the source cloud
-    job.out_idx[out] = L.bpos;   // sorted position of the neighbour (-1: none inside the cutoff)
-    job.out_d2[out] = L.best;
-    // every other target was evaluated exactly (>= second) or rejected by a screen (> sqrt(best) + mu away); 1e-9 relative covers the
-    // fp64 roundings of this line.  No neighbour inside the cutoff: 0 forces a full search next round, like the grid kernel does.
-    if (BND) job.out_lb[out] = L.bpos < 0 ? -1.f : __double2float_rd(fmin(sqrt(L.second), sqrt(L.best) + (double)G.mu) * (1.0 - 1e-9));
-    if (job.list.dirty) update_list_entry(job.list, i, L.bpos, L.best, bound, false);
-    if ((BND ? L.second == L.best : L.tie) && L.bpos >= 0) tie_report(job.tie, (unsigned int)i);
-  }
+  if (L.active) store_result<BND, false>(job, i, L.bpos, L.best, L.second, L.tie, G.mu, bound);
+  // census stores: census_slot / census_hits (nn_tile_common.h) written out, for the same reason as the patch box above
   if (CEN && stats && (threadIdx.x & 63) == 0) {
     const size_t slot = ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * (MT / 64) + wave;
     const unsigned long long act = (unsigned long long)min(64, job.n - (i & ~63));
@@ -669,22 +589,7 @@ int warm_nn_mfma(mvicp_ctx* c) {
 }
 
 int launch_nn_mfma_edges(mvicp_ctx* c, double d2_bound, bool with_bounds, bool with_cache, bool with_list) {
-  std::vector<TileJob> jobs;
-  int max_n = 0;
-  double nq = 0;
-  std::vector<TieJob> ties;
-  MV_CHECK(build_tile_jobs(c, with_bounds, with_cache, with_list, jobs, max_n, nq, ties));
-  if (jobs.empty() || max_n == 0) return MVICP_OK;
-  TileJob* d_jobs = nullptr;
-  MV_CHECK(cached_upload(c, jobs[0].xf ? "tile_jobs" : "tile_jobs_raw", jobs.data(), sizeof(TileJob) * jobs.size(), (void**)&d_jobs));
-  unsigned long long* d_stats = nullptr;
-  const size_t slots = (size_t)((max_n + MT - 1) / MT) * jobs.size() * (MT / 64);
-  MV_CHECK(census_scratch(c, slots, &d_stats));
-  {
-    ProfScope ps(c, "nn_mfma", 36.0 * nq);  // query read 24 B + result write 12 B; tile-operand / box bytes come from the census
-    const dim3 grid((max_n + MT - 1) / MT, (unsigned)jobs.size());
-    int top = jobs[0].dst.levels - 1;   // same depth everywhere -> the traversal specialised for it
-    for (const TileJob& j : jobs) if (j.dst.levels - 1 != top) top = -1;
+  return launch_tile_search(c, d2_bound, with_bounds, with_cache, with_list, MT, "nn_mfma", [&](const std::vector<TileJob>& jobs, const TileJob* d_jobs, dim3 grid, int top, unsigned long long* d_stats) {
 #define MVICP_MFMA_L(W, T, B, C, Lb) hipLaunchKernelGGL((nn_mfma_kernel<W, T, B, C, Lb>), grid, dim3(MT), 0, c->stream, d_jobs, d2_bound, search_bound(c, d2_bound), d_stats)
 #define MVICP_MFMA_K(W, T, B) do { if (d_stats) MVICP_MFMA_L(W, T, B, true, false); else MVICP_MFMA_L(W, T, B, false, false); } while (0)
     const int waves = c->tile_waves;
@@ -706,12 +611,7 @@ int launch_nn_mfma_edges(mvicp_ctx* c, double d2_bound, bool with_bounds, bool w
     else MVICP_MFMA_K(5, -1, false);
 #undef MVICP_MFMA_L
 #undef MVICP_MFMA_K
-  }
-  MV_HIP(hipGetLastError());
-  MV_CHECK(launch_tie_fixup(c, ties, d2_bound));     // exact distance ties: the reference's own descent decides (nn_tie.hip); before the lists are read
-  if (with_list) MV_CHECK(launch_dirty_reduce(c));   // per-edge OR of the "list membership changed" slots
-  if (d_stats) MV_CHECK(census_collect(c, d_stats, slots, nq, "nn_mfma"));
-  return MVICP_OK;
+  });
 }
 
 }  // namespace mvicp

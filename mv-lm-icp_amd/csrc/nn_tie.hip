@@ -11,6 +11,7 @@
 #include <thread>
 
 #include "kdvisit.h"
+#include "nn_metric.h"
 #include "nn_tie.h"
 
 namespace mvicp {
@@ -19,18 +20,6 @@ namespace {
 
 constexpr int TIE_STACK = 128;   // pending subtrees: at most one per level of the descent; a balanced tree of 2^30 points has 30 levels, skewed clouds more
                                  // (40 B each, in scratch memory: 5 KB per lane of this small kernel only)
-
-__device__ __forceinline__ void xf_point(const double* __restrict__ x, double p0, double p1, double p2, double& q0, double& q1, double& q2) {
-  double g[3], u[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-    g[i] = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(x[i], p0), __dmul_rn(x[i + 3], p1)), __dmul_rn(x[i + 6], p2)), x[9 + i]);
-#pragma unroll
-  for (int i = 0; i < 3; ++i) u[i] = __dsub_rn(g[i], x[21 + i]);
-  q0 = __dadd_rn(__dadd_rn(__dmul_rn(x[12 + 0], u[0]), __dmul_rn(x[12 + 3], u[1])), __dmul_rn(x[12 + 6], u[2]));
-  q1 = __dadd_rn(__dadd_rn(__dmul_rn(x[12 + 1], u[0]), __dmul_rn(x[12 + 4], u[1])), __dmul_rn(x[12 + 7], u[2]));
-  q2 = __dadd_rn(__dadd_rn(__dmul_rn(x[12 + 2], u[0]), __dmul_rn(x[12 + 5], u[1])), __dmul_rn(x[12 + 8], u[2]));
-}
 
 struct Pending { int node, first; double mind, d0, d1, d2; };   // a subtree still to enter, with the state searchLevel would enter it in
 

@@ -59,11 +59,7 @@ struct Lane {          // per-lane query state
   bool tie;              // another target met at exactly the running best's distance (nn_tie.h)
   double second;         // BND builds only: smallest exact d2 among the fp64-evaluated targets other than the running best
 };
-struct Group {         // wave-uniform patch description
-  float lo[3], hi[3], c[3];   // the patch AABB in fp32, rounded OUTWARD, and its centre (the coarse cull runs in fp32)
-  float slack;         // fp32 screening guard band (metres)
-  float mu;            // BND builds: extra guard band (0 otherwise)
-};
+typedef PatchBox Group;   // wave-uniform patch description (nn_tile_common.h)
 
 // fp32 squared distance from the lane's query to a box.  Same guard-band argument as the point screen in leaf_scan: the
 // nearest point of the box has box coordinates (exact floats) or the query's own, so |sqrt(lb32) - sqrt(true)| <= slack and
@@ -141,8 +137,7 @@ __device__ __forceinline__ void leaf_scan(const TileView& g, int leaf, Lane& L, 
       for (int j = 0; j < 4; ++j) {
         const int k = 4 * k4 + j;
         if (h[j] && k < cnt) {
-          const double d0 = __dsub_rn(L.qx, T->x[k]), d1 = __dsub_rn(L.qy, T->y[k]), d2 = __dsub_rn(L.qz, T->z[k]);
-          const double d = __dadd_rn(__dadd_rn(__dmul_rn(d0, d0), __dmul_rn(d1, d1)), __dmul_rn(d2, d2));
+          const double d = dist2(L.qx, L.qy, L.qz, T->x[k], T->y[k], T->z[k]);
           // strictly nearer: the new best.  EXACTLY as near (rare): the lower original index keeps the place and the query is reported —
           // nn_tie.hip then lets the reference's own tree decide (nanoflann keeps the target it visits first)
           if (d < L.best) {
@@ -227,8 +222,7 @@ __device__ void miss_block(const TileView& g, int first, int nchild, Lane& L, co
         const double2* pr = reinterpret_cast<const double2*>(g.srec + k);
         u = pr[0]; v = pr[1];
       }
-      const double d0 = __dsub_rn(qx, u.x), d1 = __dsub_rn(qy, u.y), d2 = __dsub_rn(qz, v.x);
-      const double d = __dadd_rn(__dadd_rn(__dmul_rn(d0, d0), __dmul_rn(d1, d1)), __dmul_rn(d2, d2));
+      const double d = dist2(qx, qy, qz, u.x, u.y, v.x);
       const int oi = (int)__double_as_longlong(v.y);
       *n_cand += (unsigned)(min(LEAF, g.n - (first + t0) * LEAF) + (t1 >= 0 ? min(LEAF, g.n - (first + t1) * LEAF) : 0));
       unsigned long long pm = __ballot(valid && d <= best);
@@ -261,10 +255,7 @@ __device__ void miss_block(const TileView& g, int first, int nchild, Lane& L, co
 }
 
 // Test the `nchild` boxes [first, first + nchild) of level LEVEL (one per lane) and open what is needed.
-// Register budget: the traversal recurses (level 2 -> 1 -> 0 -> tile scan) and everything a level keeps across the descent
-// is live in all deeper levels.  Levels 1 and 2 therefore park their 64 child boxes in wave-private LDS (32 B each, read
-// back with one uniform-address load per step) and keep only {cull distance, order key, pending} per lane; level 0, the
-// hot one, keeps its boxes in registers and broadcasts them with v_readlane.
+// The node prologue (child-box fetch, coarse cull, LDS parking, read-back) and its register budget: nn_tile_common.h.
 // `miss` (wave-uniform, BND builds only): below the block level the wave runs miss_block instead of the tile loop — a run-time flag, not a template
 // parameter, so that the levels above exist once (two instantiations of the whole traversal cost the regular path 3-4 %: instruction cache)
 template <int LEVEL, bool BND>
@@ -275,36 +266,11 @@ __device__ void visit(const TileView& g, int first, int nchild, Lane& L, const G
   constexpr bool IN_LDS = LEVEL == 1 || LEVEL == 2;
   const int lane = threadIdx.x & 63;
   const float inf = __int_as_float(0x7f800000);
-  float b0 = inf, b1 = inf, b2 = inf, b3 = -inf, b4 = -inf, b5 = -inf;
-  if (lane < nchild) {
-    const float* base = g.wide + g.off[LEVEL] + first + lane;
-    const long long st = g.cnt[LEVEL];
-    b0 = base[0]; b1 = base[st]; b2 = base[2 * st]; b3 = base[3 * st]; b4 = base[4 * st]; b5 = base[5 * st];
-  }
-  // coarse cull: child box vs the patch AABB; valid for every lane because lb_lane >= box-box distance
+  const NodeBoxes B = node_fetch<LEVEL>(g, first, nchild);
   float ddf, key;
-  {
-    // fp32 against the outward-rounded patch box: every operation rounds by <= 2^-24 relative, (1 - 1e-6) more than covers the five of
-    // them, so ddf stays a lower bound of the box-to-patch distance (round 3: was fp64 — 12 conversions + ~20 fp64 operations per node)
-    const float e0 = fmaxf(fmaxf(b0 - G.hi[0], G.lo[0] - b3), 0.f);
-    const float e1 = fmaxf(fmaxf(b1 - G.hi[1], G.lo[1] - b4), 0.f);
-    const float e2 = fmaxf(fmaxf(b2 - G.hi[2], G.lo[2] - b5), 0.f);
-    ddf = (e0 * e0 + e1 * e1 + e2 * e2) * 0.999999f;
-    const float k0 = fmaxf(fmaxf(b0 - G.c[0], G.c[0] - b3), 0.f);
-    const float k1 = fmaxf(fmaxf(b1 - G.c[1], G.c[1] - b4), 0.f);
-    const float k2 = fmaxf(fmaxf(b2 - G.c[2], G.c[2] - b5), 0.f);
-    key = k0 * k0 + k1 * k1 + k2 * k2;   // visiting order only
-  }
+  node_cull(G, B, ddf, key);
   float2* mybox = sbox + (IN_LDS ? (LEVEL - 1) * 3 * FAN : 0);   // [axis][child] -> (lo, hi)
-  if (IN_LDS) {
-    __builtin_amdgcn_wave_barrier();
-    mybox[lane] = make_float2(b0, b3);
-    mybox[FAN + lane] = make_float2(b1, b4);
-    mybox[2 * FAN + lane] = make_float2(b2, b5);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  }
+  if (IN_LDS) node_park(mybox, B);
   *n_box += (unsigned)nchild;
   bool pend = lane < nchild;
   // largest screen threshold of the wave (>= every lane's best): only shrinks, and only when a tile was scanned below ->
@@ -318,14 +284,8 @@ __device__ void visit(const TileView& g, int first, int nchild, Lane& L, const G
     const unsigned long long pick = __ballot(pend && key == kmin);
     const int c = __builtin_amdgcn_readfirstlane(__ffsll((long long)pick) - 1);
     if (lane == c) pend = false;
-    float c0, c1, c2, c3, c4, c5;
-    if (IN_LDS) {
-      const float2 u = mybox[c], v = mybox[FAN + c], w = mybox[2 * FAN + c];
-      c0 = u.x; c3 = u.y; c1 = v.x; c4 = v.y; c2 = w.x; c5 = w.y;
-    } else {
-      c0 = bcast(b0, c); c1 = bcast(b1, c); c2 = bcast(b2, c); c3 = bcast(b3, c); c4 = bcast(b4, c); c5 = bcast(b5, c);
-    }
-    const float lb = box_lb32(L, c0, c1, c2, c3, c4, c5);
+    const NodeBoxes C = node_child<IN_LDS>(mybox, B, c);
+    const float lb = box_lb32(L, C.b0, C.b1, C.b2, C.b3, C.b4, C.b5);
     if (__ballot(L.active && lb <= L.thr) == 0ull) continue;
     const int child = first + c;
     if (LEVEL == 0) {
@@ -362,11 +322,7 @@ __global__ __launch_bounds__(TT, WPE) void nn_tile_kernel(const TileJob* __restr
   L.second = 1.7976931348623157e308;
   L.qx = L.qy = L.qz = 0.0;
   double p0 = 0.0, p1 = 0.0, p2 = 0.0;
-  if (L.active) {
-    p0 = job.q[3 * (size_t)i]; p1 = job.q[3 * (size_t)i + 1]; p2 = job.q[3 * (size_t)i + 2];
-    if (has_xf) xf_point(sxf, p0, p1, p2, L.qx, L.qy, L.qz);
-    else { L.qx = p0; L.qy = p1; L.qz = p2; }
-  }
+  load_query(job, sxf, has_xf, i, L, p0, p1, p2);
   // Seed: last round's neighbour is an ordinary candidate (any target is), but starting from its distance instead of the
   // cutoff bound lets the traversal discard almost every tile that does not hold a true neighbour of some lane.
   int seed_pi = -1;
@@ -375,76 +331,16 @@ __global__ __launch_bounds__(TT, WPE) void nn_tile_kernel(const TileJob* __restr
     const int pi = job.out_idx[i];
     if (pi >= 0 && pi < g.n) {
       const double* p = g.spts + 3 * (size_t)pi;
-      const double d0 = __dsub_rn(L.qx, p[0]), d1 = __dsub_rn(L.qy, p[1]), d2 = __dsub_rn(L.qz, p[2]);
-      const double d = __dadd_rn(__dadd_rn(__dmul_rn(d0, d0), __dmul_rn(d1, d1)), __dmul_rn(d2, d2));
+      const double d = dist2(L.qx, L.qy, L.qz, p[0], p[1], p[2]);
       seed_pi = pi; seed_d = d;
       if (d <= L.best) { L.best = d; L.bi = g.sidx[pi]; }
     }
   }
-  // Temporal cache (BND builds in cache-aware rounds; the same test as nn_grid_kernel's): last search left a lower bound on the distance
-  // to every target OTHER than the neighbour; the query has moved by exactly eps = |dM p + dv| since, so if the re-evaluated distance to
-  // the old neighbour is below (bound - eps) it is still the unique nearest neighbour and its exact d2 is the answer.  Such a lane is
-  // finished here and sits the traversal out: the wave walks the hierarchy for its MISSED lanes only — a patch of a few queries opens
-  // one or two tiles instead of six — and a wave without a miss leaves at once.
   unsigned int n_hit = 0;
-  if (BND && job.cache && has_xf && job.seed && L.active && seed_pi < 0 && sxf[24] == 0.0 && job.out_lb[i] == -1.f) {
-    // last search found NO target within the search radius and this edge's query transform is bit-identical to that search's (allowance 0:
-    // dM = dv = 0): the query is the same, so is the answer — nothing to search, nothing to write
-    L.active = false;
-    n_hit = 1;
-  }
-  if (BND && job.cache && has_xf && seed_pi >= 0) {
-    const double cslack = sxf[24];
-    if (cslack >= 0.0) {
-      const double e0 = sxf[25] * p0 + sxf[28] * p1 + sxf[31] * p2 + sxf[34];
-      const double e1 = sxf[26] * p0 + sxf[29] * p1 + sxf[32] * p2 + sxf[35];
-      const double e2 = sxf[27] * p0 + sxf[30] * p1 + sxf[33] * p2 + sxf[36];
-      const double eps = sqrt(e0 * e0 + e1 * e1 + e2 * e2) * (1.0 + 1e-9) + cslack;
-      const double nlb = (double)job.out_lb[i] - eps;
-      // ... or (round 6) the query is provably still REJECTED: its old neighbour is beyond the cutoff now (exact) and every other target was at least
-      // out_lb away, i.e. is at least nlb away now — if that is beyond the cutoff too, no target is inside it, which is all the reference's filter
-      // (frame.cpp:156) asks; the exact neighbour of a rejected query is never output.  out_d2 then holds the distance to the OLD neighbour (>= bound:
-      // the query stays rejected downstream), out_idx keeps it as a seed, the bound is carried on.  These are the lanes with the LARGEST balls (their
-      // thresholds reach the search radius): taking them out of the traversal is what makes a partial-overlap round cheap.
-      const bool still_rejected = eps != 0.0 && seed_d >= bound && nlb > sqrt(bound) * (1.0 + 1e-9);
-      if (eps == 0.0 || sqrt(seed_d) * (1.0 + 1e-12) < nlb || (job.reject_cache && still_rejected)) {   // (eps == 0: the same query bit for bit keeps last search's exact answer)
-        if (eps != 0.0) {   // (eps == 0: bit-identical query transform, everything stored is already exact)
-          job.out_d2[i] = seed_d;
-          job.out_lb[i] = __double2float_rd(nlb);
-          if (job.list.dirty) update_list_entry(job.list, i, seed_pi, seed_d, bound, true);
-        }
-        L.active = false;
-        n_hit = 1;
-      }
-    }
-  }
-  if (BND && job.cache && __ballot(L.active) == 0ull) {
-    if (stats) {   // census (profiling only): all 64 lanes answered by the cache
-      const size_t slot = ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * (TT / 64) + wave;
-      const unsigned long long hits = __popcll(__ballot(n_hit != 0u));
-      if ((threadIdx.x & 63) == 0) stats[8 * slot + 3] = hits;
-    }
-    return;
-  }
-  Group G;   // wave-uniform: lives in SGPRs
-  {
-    // patch box in fp32, rounded outward: min / max of the lanes' float copies, widened by more than the half ulp a conversion can have
-    // moved a coordinate inwards (six DPP reductions of 7 instructions; round 2 reduced the fp64 coordinates: ~30 instructions each)
-    const float inf = __int_as_float(0x7f800000);
-    const float a = (float)L.qx, b = (float)L.qy, c2 = (float)L.qz;
-    float lo[3] = {wave_min_any(L.active ? a : inf), wave_min_any(L.active ? b : inf), wave_min_any(L.active ? c2 : inf)};
-    float hi[3] = {wave_max_any(L.active ? a : -inf), wave_max_any(L.active ? b : -inf), wave_max_any(L.active ? c2 : -inf)};
-    float m = (float)g.maxabs * 1.000001f;   // largest coordinate magnitude either operand of a difference can have: the cloud's box and the patch
-#pragma unroll
-    for (int ax = 0; ax < 3; ++ax) {
-      lo[ax] -= fabsf(lo[ax]) * 1.2e-7f + 1e-37f; hi[ax] += fabsf(hi[ax]) * 1.2e-7f + 1e-37f;
-      G.lo[ax] = lo[ax]; G.hi[ax] = hi[ax]; G.c[ax] = 0.5f * (lo[ax] + hi[ax]);
-      m = fmaxf(m, fmaxf(fabsf(lo[ax]), fabsf(hi[ax])));
-    }
-    // per axis: |fl32(q) - q| + |fl32(p) - p| + rounding of the fp32 subtraction <= 3 * 2^-24 * m; x sqrt(3) axes, x2 safety
-    G.slack = m * (3.0f * 1.7320508f * 2.0f / 16777216.0f) * 1.00001f + 1e-30f;
-    G.mu = BND ? job.mu : 0.f;
-  }
+  cache_prologue<BND>(job, sxf, has_xf, i, p0, p1, p2, seed_pi, seed_d, bound, L.active, n_hit);
+  if (cache_all_hit<BND, TT>(job, L.active, n_hit, stats)) return;
+  Group G;
+  patch_box<BND>(job, L, G);
   { const float a = (float)L.qx, b = (float)L.qy, c2 = (float)L.qz; L.qx2 = f2v{a, a}; L.qy2 = f2v{b, b}; L.qz2 = f2v{c2, c2}; L.pad_ = 0.0; }
   L.thr = L.active ? thr_of(L.best, G.slack + G.mu) : -1.f;   // a finished / padding lane screens nothing (d32 >= 0 > -1)
   unsigned int n_cand = 0, n_box = 0;
@@ -462,29 +358,14 @@ __global__ __launch_bounds__(TT, WPE) void nn_tile_kernel(const TileJob* __restr
     default: visit<4, BND>(g, 0, g.cnt[4], L, G, T, sbox, &n_cand, &n_box, miss_path); break;
   }
   const unsigned int n_exam = n_cand;
-  if (L.active) {
-    const int out = i;   // sorted order of the source cloud
-    job.out_idx[out] = L.bi == 0x7fffffff ? -1 : (job.inv ? job.inv[L.bi] : L.bi);
-    job.out_d2[out] = L.best;
-    // every other target was evaluated exactly (>= second) or rejected by a screen (> sqrt(best) + mu away); 1e-9 relative covers the
-    // fp64 roundings of this line.  No neighbour inside the cutoff: 0 forces a full search next round, like the grid kernel does.
-    if (BND) job.out_lb[out] = L.bi == 0x7fffffff ? -1.f : __double2float_rd(fmin(sqrt(L.second), sqrt(L.best) + (double)G.mu) * (1.0 - 1e-9));
-    // the edge's compacted list is maintained in place (nn_list.h) whenever the host handed it over (list.dirty != null): a query that
-    // keeps its acceptance patches its own entry and operands, so compaction + gather only run for edges whose MEMBERSHIP changed —
-    // also in the plain seeded rounds, where nearly every neighbour changes but hardly any acceptance does (round 3)
-    if (job.list.dirty) update_list_entry(job.list, i, L.bi == 0x7fffffff ? -1 : job.inv[L.bi], L.best, bound, false);
-    if ((BND ? L.second == L.best : L.tie) && L.bi != 0x7fffffff) tie_report(job.tie, (unsigned int)i);
-  }
+  if (L.active) store_result<BND, true>(job, i, L.bi, L.best, L.second, L.tie, G.mu, bound);
   if (stats && (threadIdx.x & 63) == 0) {
     // wave-uniform counters: candidates examined PER LANE x active lanes, boxes tested per wave
-    const size_t slot = ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * (TT / 64) + wave;
+    const size_t slot = census_slot<TT>();
     const unsigned long long act = (unsigned long long)min(64, job.n - (i & ~63));
     stats[8 * slot] = n_cand; stats[8 * slot + 1] = n_box; stats[8 * slot + 2] = miss_path ? (unsigned long long)n_exam : (unsigned long long)n_cand * act;
   }
-  if (stats && BND && job.cache) {
-    const unsigned long long hits = __popcll(__ballot(n_hit != 0u));
-    if ((threadIdx.x & 63) == 0) stats[8 * (((size_t)blockIdx.y * gridDim.x + blockIdx.x) * (TT / 64) + wave) + 3] = hits;
-  }
+  if (stats && BND && job.cache) census_hits<TT>(stats, n_hit);
 }
 
 }  // namespace
@@ -546,22 +427,7 @@ int launch_nn_tile_edges(mvicp_ctx* c, double d2_bound, bool with_bounds, bool w
   // most lanes finished by the cache the per-lane box tests prune nearly every tile, and the 7-wave occupancy of this build hides the
   // latency of the few that remain (cfg4 rounds 6 / 7: 0.57 / 0.38 ms here against 0.65 / 0.57 ms there)
   if (c->tile_mfma >= 2 || (c->tile_mfma == 1 && (!with_cache || c->cached_on_mfma))) return launch_nn_mfma_edges(c, d2_bound, with_bounds, with_cache, with_list);
-  std::vector<TileJob> jobs;
-  int max_n = 0;
-  double nq = 0;
-  std::vector<TieJob> ties;
-  MV_CHECK(build_tile_jobs(c, with_bounds, with_cache, with_list, jobs, max_n, nq, ties));
-  if (jobs.empty() || max_n == 0) return MVICP_OK;
-  TileJob* d_jobs = nullptr;
-  MV_CHECK(cached_upload(c, jobs[0].xf ? "tile_jobs" : "tile_jobs_raw", jobs.data(), sizeof(TileJob) * jobs.size(), (void**)&d_jobs));
-  unsigned long long* d_stats = nullptr;
-  const size_t slots = (size_t)((max_n + TT - 1) / TT) * jobs.size() * (TT / 64);
-  MV_CHECK(census_scratch(c, slots, &d_stats));
-  {
-    ProfScope ps(c, "nn_tile", 36.0 * nq);  // query read 24 B + result write 12 B; candidate / box bytes come from the census
-    const dim3 grid((max_n + TT - 1) / TT, (unsigned)jobs.size());
-    int top = jobs[0].dst.levels - 1;   // same depth everywhere -> the traversal specialised for it
-    for (const TileJob& j : jobs) if (j.dst.levels - 1 != top) top = -1;
+  return launch_tile_search(c, d2_bound, with_bounds, with_cache, with_list, TT, "nn_tile", [&](const std::vector<TileJob>&, const TileJob* d_jobs, dim3 grid, int top, unsigned long long* d_stats) {
 #define MVICP_TILE_K(W, T, B) hipLaunchKernelGGL((nn_tile_kernel<W, T, B>), grid, dim3(TT), 0, c->stream, d_jobs, d2_bound, search_bound(c, d2_bound), d_stats)
     const int waves = c->tile_waves;   // 0 = pick: 7 waves per SIMD for the depth-3 build, 6 otherwise
     // depth-3 build: 7 waves per SIMD (no spills at 66 VGPRs); 6 and 8 measure 4-10 % slower (profiles/r03_tile_ab.txt)
@@ -575,12 +441,7 @@ int launch_nn_tile_edges(mvicp_ctx* c, double d2_bound, bool with_bounds, bool w
     else if (waves == 8) MVICP_TILE_K(8, -1, false);
     else MVICP_TILE_K(6, -1, false);
 #undef MVICP_TILE_K
-  }
-  MV_HIP(hipGetLastError());
-  MV_CHECK(launch_tie_fixup(c, ties, d2_bound));     // exact distance ties: the reference's own descent decides (nn_tie.hip); before the lists are read
-  if (with_list) MV_CHECK(launch_dirty_reduce(c));   // per-edge OR of the "list membership changed" slots
-  if (d_stats) MV_CHECK(census_collect(c, d_stats, slots, nq, "nn_tile"));
-  return MVICP_OK;
+  });
 }
 
 }  // namespace mvicp

@@ -22,6 +22,7 @@
 
 #include "common.h"
 #include "kdvisit.h"
+#include "nn_metric.h"
 #include "nn_tie.h"
 
 namespace mvicp {
@@ -123,8 +124,7 @@ __global__ __launch_bounds__(NT) void normals_kernel(NormJob job) {
           if (e.key == EMPTY) continue;
           for (unsigned int j = e.start; j < e.start + e.count; ++j) {
             const PointRec p = job.srec[j];
-            const double d0 = __dsub_rn(me.x, p.x), d1 = __dsub_rn(me.y, p.y), d2 = __dsub_rn(me.z, p.z);
-            const double d = __dadd_rn(__dadd_rn(__dmul_rn(d0, d0), __dmul_rn(d1, d1)), __dmul_rn(d2, d2));
+            const double d = dist2(me.x, me.y, me.z, p.x, p.y, p.z);
             // sorted insertion (ascending distance; equal distances in the tree's visit order).  One comparator call site, plain indexed
             // arrays: this kernel runs once per cloud, simplicity beats register residency here.
             int pos = K;

@@ -31,7 +31,7 @@ constexpr int NT = 256;     // threads per workgroup: 4 waves, 32 octets
 constexpr int ITEM_MAX = 256, ITEM_MIN = 8;   // samples per work item (a power of two, chosen per launch)
 
 struct alignas(16) OvJob {
-  double xf[24];                  // Rs ts Rd^-1 td of the pair (the first 24 doubles of an edge's kEdgeXf)
+  double xf[kXfRigid];            // Rs ts Rd^-1 td of the pair (the rigid part of an edge's kEdgeXf)
   const double* q;                // source cloud, sorted order (n x 3)
   const int* samp;                // sorted positions of the samples, ascending (null: every point, position t)
   const double* tpts;             // target cloud, sorted order
@@ -197,7 +197,7 @@ int overlap_census(mvicp_ctx* c, const double* xf, double B2, double scale, int 
       const FrameDev& ft = c->frames[j];
       if (i == j || samples[i] == 0 || ft.n == 0) continue;
       OvJob J;
-      std::memcpy(J.xf, xf + 24 * ((size_t)i * K + j), sizeof(J.xf));
+      std::memcpy(J.xf, xf + kXfRigid * ((size_t)i * K + j), sizeof(J.xf));
       J.q = fs.grid.spts; J.samp = samples[i] == fs.n ? nullptr : fs.grid.ov_samp;
       J.tpts = ft.grid.spts; J.oct = ft.grid.oct; J.first_leaf = ft.grid.oct_first_leaf;
       J.s = samples[i]; J.tn = ft.n; J.oct_leaf = ft.grid.oct_leaf; J.pair = i * K + j;
