@@ -160,6 +160,51 @@ long long mvicp_voxel_grid(mvicp_ctx* ctx, int n_sel, const int* frames, const d
  * Errors: cap < m -> MVICP_ERR_ARG; no mvicp_voxel_grid before, or nrm != NULL when has_normals == 0 -> MVICP_ERR_STATE. */
 int mvicp_voxel_fetch(mvicp_ctx* ctx, long long cap, double* xyz, double* nrm, int* cnt);
 
+/* ---- outlier removal: the statistical and the radius rule over one k-distance search ----------------------------
+ * Cleans one cloud the way every point-cloud toolkit does: a point goes when its k nearest neighbours are unusually far away.  The result is
+ * a pure function of the stored cloud p_0 .. p_{n-1} of `frame` (the stored bytes, no pose), bit for bit (tests/outlierref.py is the same
+ * definition in numpy):
+ *   Per point  D_i[0..k] = the k+1 smallest VALUES, ascending, of the multiset { dist2(p_i, p_j) : j = 0 .. n-1 }, j = i included (D_i[0] = +0);
+ *              dist2 = (d0 d0 + d1 d1) + d2 d2, every operation rounded on its own, no fma (csrc/nn_metric.h).  Only the values enter: which
+ *              of several equidistant points is "the" neighbour is irrelevant, so no tie order is needed or built.
+ *              kd2_i = D_i[k];  mdist_i: s = +0.0; for t = 1 .. k: s = s + sqrt(D_i[t]) (IEEE sqrt, ascending t); then s / (double)k.
+ *   Radius     on iff radius > 0: keep i iff sqrt(kd2_i) < radius (IEEE sqrt) -- at least k other points within the radius.
+ *   Statistic  on iff std_ratio >= 0; order-independent by the device of the census's sumq.  mmax = max_i mdist_i.  mmax == 0: every point
+ *              passes and q_exp = s1 = s2 = T = threshold = 0 (the same zeros are reported while the rule is off).  Otherwise q_exp = the integer
+ *              with 2^30 <= mmax 2^q_exp < 2^31, M_i = floor(mdist_i 2^q_exp) (an exact scaling), S1 = sum M_i, S2 = sum M_i^2 (exact integers;
+ *              S2 = s2_hi 2^64 + s2_lo), T = mvicp_outlier_threshold(n, S1, S2, std_ratio), and i passes iff (double)M_i <= T.
+ *   Both on    kept iff it passes both;  both off: every point is kept (the call is then a k-distance query).
+ *   Output     kept rows in ascending original index: xyz / nrm = the stored bytes (nrm iff the frame has normals), idx = the int32 original
+ *              index; mdist and kd2 have length n, for ALL points.
+ * Needs 1 <= k <= 32 and n > k (n = 0: zero rows, no error); needs the frame's hash structure (waits for pending builds and reports a failed
+ * one, like mvicp_overlap), NO graph, and is HISTORY-NEUTRAL: it does not modify the frame and leaves caches, seeds, lists, epochs, medians, the
+ * AUTO state and queued evaluations alone, so a registration with filter calls in between is bit-identical to one without.  With several
+ * ranks every rank computes it locally.  The call returns when the result is complete; the result lives in library-owned device memory until
+ * the next mvicp_outlier_filter, mvicp_set_num_frames or mvicp_destroy.  Profile scopes: "outlier_knn", "outlier_sum", "outlier_flag",
+ * "outlier_compact".
+ * RETURNS THE NUMBER KEPT (>= 0) or a negative mvicp_status; stats may be NULL.
+ * Errors: NULL context, k outside [1, 32], a non-finite std_ratio or radius, a frame index out of range, 0 < n <= k, a neighbour distance that
+ * overflows -> MVICP_ERR_ARG (those that need no GPU are decided before the context is touched); a frame never uploaded -> MVICP_ERR_STATE. */
+typedef struct mvicp_outlier_stats {
+  long long n, kept;
+  int q_exp;
+  int has_normals;   /* the frame has normals: mvicp_outlier_fetch gives nrm */
+  unsigned long long s1, s2_hi, s2_lo;
+  double T;          /* the threshold in quantised units (compared with (double)M_i) */
+  double threshold;  /* ldexp(T, -q_exp): the same in the cloud's length unit */
+} mvicp_outlier_stats;
+long long mvicp_outlier_filter(mvicp_ctx* ctx, int frame, int k, double std_ratio, double radius, mvicp_outlier_stats* stats);
+/* Copies the last result: xyz / nrm (kept x 3 doubles), idx (kept ints), mdist / kd2 (n doubles); each may be NULL; each may be a HOST pointer
+ * or a DEVICE pointer of the context's device, decided per pointer as mvicp_voxel_fetch decides, so a device result goes straight into
+ * mvicp_set_frame_device.  cap_kept = rows xyz / nrm / idx hold, cap_n = entries mdist / kd2 hold (looked at only when one of the two is given).
+ * Errors: cap_kept < kept, cap_n < n -> MVICP_ERR_ARG; no mvicp_outlier_filter before, or nrm != NULL for a frame without normals -> MVICP_ERR_STATE. */
+int mvicp_outlier_fetch(mvicp_ctx* ctx, long long cap_kept, double* xyz, double* nrm, int* idx, long long cap_n, double* mdist, double* kd2);
+/* The threshold of the statistical rule (pure host function, no context): S2 = s2_hi 2^64 + s2_lo;
+ *   mean = (double)S1 / (double)n;  var = ((double)(n S2 - S1^2) / (double)n) / ((double)n - 1.0);  *T = mean + std_ratio sqrt(var)
+ * -- the 128-bit integer n S2 - S1^2 (>= 0) converted with round-to-nearest-even, every floating-point operation rounded on its own.
+ * Errors: n < 2, NULL T, a non-finite std_ratio, n S2 >= 2^128 or S1^2 > n S2 -> MVICP_ERR_ARG. */
+int mvicp_outlier_threshold(long long n, unsigned long long s1, unsigned long long s2_hi, unsigned long long s2_lo, double std_ratio, double* T);
+
 /* The graph rule on top of the census (pure host function, no context).  Frame i keeps the knn frames j != i with the most hits, among
  * those with hits[i*K+j] > 0 and hits[i*K+j] >= min_fraction * samples[i]; equal hits: the smaller sumq first (within one row that is
  * the smaller mean distance: an exact integer comparison, no division), then the lower j.  sumq NULL: hits, then lower j.  Edges are

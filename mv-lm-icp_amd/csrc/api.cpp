@@ -506,6 +506,7 @@ int mvicp_destroy(mvicp_ctx* c) try {
   dev_free(c->d_split_idx); dev_free(c->d_split_d2); dev_free(c->d_scratch);
   free_overlap(c);
   free_voxel(c);
+  free_outlier(c);
   for (auto& kv : c->tables) if (kv.second.d) (void)hipFree(kv.second.d);
   if (c->d_census) (void)hipFree(c->d_census);
   if (c->h_census) (void)hipHostFree(c->h_census);
@@ -530,6 +531,7 @@ int mvicp_set_num_frames(mvicp_ctx* c, int n_frames) try {
   (void)finish_builds(c);   // (builds of clouds that are dropped right here: their outcome no longer matters)
   if (c->E) free_graph(c);
   free_voxel(c);   // (the last voxel-grid result ends here; every voxel call waits for its own work)
+  free_outlier(c); // (and the last outlier-filter result)
   for (FrameDev& f : c->frames) { dev_free(f.pts); dev_free(f.nor); free_grid(f.grid); free_tie(f); }
   c->frames.assign(n_frames, FrameDev());
   c->n_frames = n_frames;
@@ -856,6 +858,61 @@ int mvicp_voxel_fetch(mvicp_ctx* c, long long cap, double* xyz, double* nrm, int
   for (int k = 0; k < 3; ++k)
     if (dst[k]) MV_HIP(hipMemcpyAsync(dst[k], src[k], bytes[k], kind[k] ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
   MV_HIP(hipStreamSynchronize(c->stream));
+  return MVICP_OK;
+} MVICP_GUARD_ABI
+
+long long mvicp_outlier_filter(mvicp_ctx* c, int frame, int k, double std_ratio, double radius, mvicp_outlier_stats* stats) try {
+  // every argument error that needs no GPU first: nothing of the context has been touched when one of them is reported
+  if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
+  if (k < 1 || k > 32) { set_error("k = %d outside [1, 32]", k); return MVICP_ERR_ARG; }
+  if (!std::isfinite(std_ratio)) { set_error("std_ratio must be finite (negative: statistical rule off)"); return MVICP_ERR_ARG; }
+  if (!std::isfinite(radius)) { set_error("radius must be finite (<= 0: radius rule off)"); return MVICP_ERR_ARG; }
+  if (frame < 0 || frame >= c->n_frames) { set_error("frame %d out of range [0,%d)", frame, c->n_frames); return MVICP_ERR_ARG; }
+  if (!c->frames[frame].pts) { set_error("frame %d was never uploaded", frame); return MVICP_ERR_STATE; }
+  const int n = c->frames[frame].n;
+  if (n > 0 && n <= k) { set_error("frame %d has %d points: k = %d needs more than k", frame, n, k); return MVICP_ERR_ARG; }
+  MV_CHECK(bind(c));
+  MV_CHECK(finish_builds(c));
+  const long long kept = outlier_filter(c, c->frames[frame], k, std_ratio, radius, stats);
+  if (c->profile) prof_collect_lazy(c);
+  return kept;
+} MVICP_GUARD_ABI
+
+int mvicp_outlier_fetch(mvicp_ctx* c, long long cap_kept, double* xyz, double* nrm, int* idx, long long cap_n, double* mdist, double* kd2) try {
+  if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
+  if (c->out_n < 0) { set_error("no outlier result: call mvicp_outlier_filter first"); return MVICP_ERR_STATE; }
+  if (cap_kept < c->out_kept) { set_error("cap_kept %lld < %lld kept rows", cap_kept, c->out_kept); return MVICP_ERR_ARG; }
+  if ((mdist || kd2) && cap_n < c->out_n) { set_error("cap_n %lld < %lld points", cap_n, c->out_n); return MVICP_ERR_ARG; }
+  if (nrm && !c->out_has_normals) { set_error("the filtered frame has no normals"); return MVICP_ERR_STATE; }
+  if (c->out_n == 0) return MVICP_OK;
+  MV_CHECK(bind(c));
+  const size_t m = (size_t)c->out_kept, n = (size_t)c->out_n;
+  const void* src[5] = {c->out_xyz, c->out_nrm, c->out_idx, c->out_mdist, c->out_kd2};
+  void* dst[5] = {xyz, nrm, idx, mdist, kd2};
+  const size_t bytes[5] = {24 * m, 24 * m, 4 * m, 8 * n, 8 * n};
+  const char* names[5] = {"xyz", "nrm", "idx", "mdist", "kd2"};
+  int kind[5] = {0, 0, 0, 0, 0};
+  for (int t = 0; t < 5; ++t)
+    if (dst[t] && bytes[t]) { kind[t] = destination_kind(c, dst[t], names[t]); if (kind[t] < 0) return kind[t]; }
+  for (int t = 0; t < 5; ++t)
+    if (dst[t] && bytes[t]) MV_HIP(hipMemcpyAsync(dst[t], src[t], bytes[t], kind[t] ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+  MV_HIP(hipStreamSynchronize(c->stream));
+  return MVICP_OK;
+} MVICP_GUARD_ABI
+
+int mvicp_outlier_threshold(long long n, unsigned long long s1, unsigned long long s2_hi, unsigned long long s2_lo, double std_ratio, double* T) try {
+  if (n < 2 || !T || !std::isfinite(std_ratio)) { set_error("outlier threshold: needs n >= 2, a finite std_ratio and T"); return MVICP_ERR_ARG; }
+  typedef unsigned __int128 u128;
+  const u128 s2 = ((u128)s2_hi << 64) | s2_lo, nn = (u128)(unsigned long long)n;
+  if (s2 > ~(u128)0 / nn) { set_error("outlier threshold: n S2 does not fit 128 bits"); return MVICP_ERR_ARG; }
+  const u128 a = nn * s2, b = (u128)s1 * s1;
+  if (b > a) { set_error("outlier threshold: S1^2 > n S2 (not the sums of one set)"); return MVICP_ERR_ARG; }
+  // every operation rounded on its own (this TU is built without fma contraction); the 128-bit integer converts with round-to-nearest-even
+  const double dn = (double)n;
+  const double mean = (double)s1 / dn;
+  const double var = ((double)(a - b) / dn) / (dn - 1.0);
+  const double spread = std_ratio * std::sqrt(var);
+  *T = mean + spread;
   return MVICP_OK;
 } MVICP_GUARD_ABI
 

@@ -254,6 +254,13 @@ struct mvicp_ctx {
   char* vox_scratch = nullptr; char* vox_tmp = nullptr; char* vox_pin = nullptr; size_t vox_scratch_bytes = 0, vox_tmp_bytes = 0, vox_pin_bytes = 0;
   int voxel_permute = 1;           // option "voxel_permute": lay w / R n out in sorted order before the reduction (0: the reduction re-gathers through seq)
 
+  // outlier filter (outlier.hip): the last result, library-owned until the next mvicp_outlier_filter / mvicp_set_num_frames / mvicp_destroy
+  // (out_n < 0: none).  One device arena (the result arrays are views into it), rocprim storage and a pinned control block of its own, kept
+  // between calls and grown on demand: mvicp_outlier_filter touches nothing a search, a queued evaluation, the census or the voxel grid uses
+  char* out_dev = nullptr; char* out_tmp = nullptr; char* out_pin = nullptr; size_t out_dev_bytes = 0, out_tmp_bytes = 0;
+  double* out_xyz = nullptr; double* out_nrm = nullptr; double* out_mdist = nullptr; double* out_kd2 = nullptr; int* out_idx = nullptr;
+  long long out_n = -1, out_kept = -1; int out_has_normals = 0;
+
   // cached small tables
   struct CachedTable { std::vector<char> bytes; void* d = nullptr; size_t cap = 0; };
   std::map<std::string, CachedTable> tables;
@@ -361,6 +368,11 @@ void free_overlap(mvicp_ctx* c);
 // point per voxel; the result stays on the context (vox_*).  Returns the number of voxels or a negative status.  Waits for the stream; history-neutral.
 long long voxel_reduce(mvicp_ctx* c, int n_sel, const int* sel, const double* poses, double voxel, int* has_normals);
 void free_voxel(mvicp_ctx* c);     // the result and the buffers
+// outlier.hip: k-distance search over frame f's hash (valid, uploaded, structures built; 1 <= k <= 32, n == 0 or n > k), the statistical
+// (std_ratio >= 0) and the radius (radius > 0) rule; the result stays on the context (out_*).  Returns the number kept or a negative
+// status.  Waits for the stream; history-neutral.
+long long outlier_filter(mvicp_ctx* c, const FrameDev& f, int k, double std_ratio, double radius, mvicp_outlier_stats* stats);
+void free_outlier(mvicp_ctx* c);   // the result and the buffers
 int launch_compact(mvicp_ctx* c, double d2_bound);                                    // corr.hip
 int launch_gather_stream(mvicp_ctx* c);
 int launch_select_median(mvicp_ctx* c, double d2_bound);   // two-pass select anchored at the acceptance bound: any key set, exact

@@ -1,0 +1,315 @@
+// Statistical and radius outlier removal (mvicp_outlier_filter): per point the k+1 smallest squared distances to the points of its own
+// cloud (itself included), from them the k-th distance and the mean distance to the k nearest, and the two classic rules on top.  The
+// result is a pure function of the stored cloud, bit for bit (the contract is stated in include/mvicp.h; tests/outlierref.py is its
+// numpy form).  DESIGN.md §3.8.
+//
+// Passes, all on the context's stream:
+//   1  knn      one lane per point in hash-CELL order (GridDev::crec): the growing cell block of normals_kernel with its exactness test
+//               (the k+1-th value lies inside the scanned block's faces, or the block covers the grid), VALUES ONLY: no index, no tie
+//               order, no PCA.  Writes kd2 and mdist in original order; one atomic max per wave on the bit pattern of mdist (>= 0).
+//      -- host wait (statistical rule only): mmax; the host chooses q_exp --
+//   2  sum      M = floor(mdist 2^q_exp) < 2^31; S1 = sum M and the two 32-bit halves of M^2 summed apart (each sum < 2^63 for
+//               n < 2^31): wave reduction, then three 64-bit integer atomics per workgroup.  Integer sums: order-independent.
+//      -- host wait: the sums; T = mvicp_outlier_threshold --
+//   3  flag     keep = ((double)M <= T) and (sqrt(kd2) < radius), each rule only when it is on
+//   4  compact  exclusive scan of the flags (rocprim), then one lane per point stores its row at its rank: ascending original index
+//      -- host wait: the number kept --
+// What the knn kernel does differently from normals_kernel, and why (this kernel is the whole feature, that one runs once per cloud):
+//   * the list capacity is a template parameter (9 / 17 / 33 doubles per lane, one LDS column per lane): 9 / 17 / 33 KiB per 128-lane
+//     workgroup, so k <= 8 still runs at the 32-waves-per-CU cap, k <= 16 at 18 waves and only k > 16 at 8 (160 KiB of LDS per CU);
+//   * the current k+1-th value stays in a register: a candidate that cannot enter the list costs one comparison and no LDS access
+//     (after the first cell nearly every candidate);
+//   * a grown block scans only the SHELL of new cells — the list holds values only, so what the smaller block found stays valid;
+//   * a lane whose block would exceed 2 n cells (a point far from everything in a sparse grid) scans the cloud itself instead: O(n),
+//     exact by construction, where the growing block would look up O(r^3) empty cells.
+// Consecutive cell-order lanes read the same few cells, so the candidate loads of a wave are mostly one address (a broadcast from L1).
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include <rocprim/rocprim.hpp>
+
+#include "common.h"
+#include "nn_metric.h"
+
+namespace mvicp {
+
+namespace {
+
+constexpr int NT = 128;   // lanes per workgroup of the knn kernel
+constexpr int VT = 256;   // of the streaming passes
+constexpr unsigned long long EMPTY = ~0ull;
+
+struct HashEntry { unsigned long long key; unsigned int start, count; };
+
+__device__ __forceinline__ unsigned long long cell_key(int ix, int iy, int iz) {
+  return (unsigned long long)ix | ((unsigned long long)iy << 21) | ((unsigned long long)iz << 42);
+}
+__device__ __forceinline__ unsigned int hash_slot(unsigned long long k, int shift) { return (unsigned int)((k * 0x9E3779B97F4A7C15ull) >> shift); }
+
+struct KnnJob {
+  const PointRec* crec; int n;   // records in hash-CELL order
+  const HashEntry* table; unsigned int mask; int shift;
+  double ox, oy, oz, h, inv_h;
+  int dx, dy, dz;
+  int k;
+  double* mdist; double* kd2;    // n each, original order
+  unsigned long long* mmax;      // bit pattern of the largest mdist
+};
+
+struct OutCtl { unsigned long long mmax, s1, s2lo, s2hi; int kept, pad; };
+
+template <int KCAP>
+__global__ __launch_bounds__(NT) void outlier_knn_kernel(KnnJob job) {
+  // the lane's k+1 smallest values so far, ascending, +inf where there is none yet: one LDS column per lane (consecutive lanes,
+  // consecutive 8-byte words: conflict-free), indexed at run time by the insertion
+  __shared__ double s_d[KCAP][NT];
+#define LD(t) s_d[t][threadIdx.x]
+  const int i = blockIdx.x * NT + threadIdx.x;   // position in cell order
+  const bool active = i < job.n;
+  double md = 0.0;
+  if (active) {
+    const PointRec me = job.crec[i];
+    const int L = job.k + 1;
+    for (int t = 0; t < L; ++t) LD(t) = INFINITY;
+    double worst = INFINITY;   // = LD(L - 1)
+    auto offer = [&](double d) {
+      if (!(d < worst)) return;   // (an equal value changes nothing: only the values enter)
+      int pos = L - 1;
+      while (pos > 0) {
+        const double e = LD(pos - 1);
+        if (!(e > d)) break;
+        LD(pos) = e;
+        --pos;
+      }
+      LD(pos) = d;
+      worst = LD(L - 1);
+    };
+    auto scan_run = [&](unsigned int a, unsigned int b) {
+      for (unsigned int j = a; j < b; ++j) {
+        const PointRec* p = job.crec + j;
+        offer(dist2(me.x, me.y, me.z, p->x, p->y, p->z));
+      }
+    };
+    auto scan_cells = [&](int x0, int x1, int iy, int iz) {
+      for (int ix = x0; ix <= x1; ++ix) {
+        const unsigned long long key = cell_key(ix, iy, iz);
+        unsigned int slot = hash_slot(key, job.shift) & job.mask;
+        HashEntry e = job.table[slot];
+        while (e.key != key && e.key != EMPTY) { slot = (slot + 1) & job.mask; e = job.table[slot]; }
+        if (e.key != EMPTY) scan_run(e.start, e.start + e.count);
+      }
+    };
+    const int cx = min(max((int)floor((me.x - job.ox) * job.inv_h), 0), job.dx - 1);
+    const int cy = min(max((int)floor((me.y - job.oy) * job.inv_h), 0), job.dy - 1);
+    const int cz = min(max((int)floor((me.z - job.oz) * job.inv_h), 0), job.dz - 1);
+    const int rmax = max(job.dx, max(job.dy, job.dz));
+    int rprev = -1;   // the cells within this Chebyshev distance of (cx, cy, cz) are scanned
+    for (int r = 1;; ++r) {
+      const int x0 = max(cx - r, 0), x1 = min(cx + r, job.dx - 1), y0 = max(cy - r, 0), y1 = min(cy + r, job.dy - 1);
+      const int z0 = max(cz - r, 0), z1 = min(cz + r, job.dz - 1);
+      if (r > 1 && (long long)(x1 - x0 + 1) * (y1 - y0 + 1) * (z1 - z0 + 1) > 2ll * job.n) {
+        // far from everything in a sparse grid: the cloud itself is the smaller scan
+        for (int t = 0; t < L; ++t) LD(t) = INFINITY;
+        worst = INFINITY;
+        scan_run(0u, (unsigned int)job.n);
+        break;
+      }
+      for (int iz = z0; iz <= z1; ++iz)
+        for (int iy = y0; iy <= y1; ++iy) {
+          if (max(abs(iz - cz), abs(iy - cy)) > rprev) scan_cells(x0, x1, iy, iz);
+          else {   // only the cells of this row that the smaller block did not hold
+            scan_cells(x0, min(cx - rprev - 1, x1), iy, iz);
+            scan_cells(max(cx + rprev + 1, x0), x1, iy, iz);
+          }
+        }
+      rprev = r;
+      // exact iff the k+1-th value is inside the scanned block: every unscanned point is >= m away along some axis (normals.hip)
+      const double fx = job.ox + (cx - r) * job.h, fy = job.oy + (cy - r) * job.h, fz = job.oz + (cz - r) * job.h;
+      const double w = (2 * r + 1) * job.h;
+      double m = fmin(fmin(me.x - fx, fx + w - me.x), fmin(fmin(me.y - fy, fy + w - me.y), fmin(me.z - fz, fz + w - me.z)));
+      m *= 0.999;
+      if ((m > 0.0 && worst < m * m) || r >= rmax) break;   // (worst < m m implies a full list: +inf is not below it)
+    }
+    double s = 0.0;
+    for (int t = 1; t < L; ++t) s = __dadd_rn(s, __dsqrt_rn(LD(t)));
+    md = __ddiv_rn(s, (double)job.k);
+    job.kd2[me.idx] = worst;
+    job.mdist[me.idx] = md;
+  }
+#undef LD
+  unsigned long long b = (unsigned long long)__double_as_longlong(md);   // md >= +0: the bit patterns order like the values
+#pragma unroll
+  for (int x = 1; x < 64; x <<= 1) { const unsigned long long o = __shfl_xor(b, x, 64); b = o > b ? o : b; }
+  if ((threadIdx.x & 63) == 0 && b != 0ull) atomicMax(job.mmax, b);
+}
+
+__device__ __forceinline__ unsigned long long quantise(double md, int q) { return (unsigned long long)floor(ldexp(md, q)); }
+
+__global__ __launch_bounds__(VT) void outlier_sum_kernel(const double* __restrict__ mdist, int n, int q, OutCtl* __restrict__ ctl) {
+  __shared__ unsigned long long s_p[VT / 64][3];
+  const int i = blockIdx.x * VT + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const unsigned long long M = i < n ? quantise(mdist[i], q) : 0ull, M2 = M * M;   // M < 2^31
+  unsigned long long v[3] = {M, M2 & 0xffffffffull, M2 >> 32};
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int x = 1; x < 64; x <<= 1) v[a] += __shfl_xor(v[a], x, 64);
+  if (lane == 0)
+    for (int a = 0; a < 3; ++a) s_p[wave][a] = v[a];
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    const int a = threadIdx.x;
+    unsigned long long t = s_p[0][a];
+    for (int w = 1; w < VT / 64; ++w) t += s_p[w][a];
+    if (t) atomicAdd(a == 0 ? &ctl->s1 : a == 1 ? &ctl->s2lo : &ctl->s2hi, t);
+  }
+}
+
+__global__ __launch_bounds__(VT) void outlier_flag_kernel(const double* __restrict__ mdist, const double* __restrict__ kd2, int n, int stat, int q, double T,
+                                                          int rad, double radius, int* __restrict__ flag) {
+  const int i = blockIdx.x * VT + threadIdx.x;
+  if (i >= n) return;
+  bool keep = true;
+  if (stat) keep = (double)quantise(mdist[i], q) <= T;
+  if (rad) keep = keep && __dsqrt_rn(kd2[i]) < radius;
+  flag[i] = keep ? 1 : 0;
+}
+
+template <bool NRM>
+__global__ __launch_bounds__(VT) void outlier_compact_kernel(const double* __restrict__ pts, const double* __restrict__ nor, const int* __restrict__ flag,
+                                                             const int* __restrict__ pos, int n, double* __restrict__ xyz, double* __restrict__ nrm,
+                                                             int* __restrict__ idx, OutCtl* __restrict__ ctl) {
+  const int i = blockIdx.x * VT + threadIdx.x;
+  if (i >= n) return;
+  const int f = flag[i], o = pos[i];   // o <= i < n: inside the n-row destinations
+  if (f) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) xyz[3 * (size_t)o + a] = pts[3 * (size_t)i + a];
+    if (NRM) {
+#pragma unroll
+      for (int a = 0; a < 3; ++a) nrm[3 * (size_t)o + a] = nor[3 * (size_t)i + a];
+    }
+    idx[o] = i;
+  }
+  if (i == n - 1) ctl->kept = o + f;
+}
+
+size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+int grid_of(long long n, int t) { return (int)((n + t - 1) / t); }
+
+int ensure_dev(char** p, size_t* have, size_t need) {
+  if (need <= *have) return MVICP_OK;
+  if (*p) MV_HIP(hipFree(*p));
+  *p = nullptr; *have = 0;
+  MV_HIP(hipMalloc((void**)p, need));
+  *have = need;
+  return MVICP_OK;
+}
+
+}  // namespace
+
+void free_outlier(mvicp_ctx* c) {
+  if (c->out_dev) (void)hipFree(c->out_dev);
+  if (c->out_tmp) (void)hipFree(c->out_tmp);
+  if (c->out_pin) (void)hipHostFree(c->out_pin);
+  c->out_dev = nullptr; c->out_tmp = nullptr; c->out_pin = nullptr; c->out_dev_bytes = 0; c->out_tmp_bytes = 0;
+  c->out_xyz = nullptr; c->out_nrm = nullptr; c->out_mdist = nullptr; c->out_kd2 = nullptr; c->out_idx = nullptr;
+  c->out_n = -1; c->out_kept = -1; c->out_has_normals = 0;
+}
+
+long long outlier_filter(mvicp_ctx* c, const FrameDev& f, int k, double std_ratio, double radius, mvicp_outlier_stats* stats) {
+  c->out_n = -1; c->out_kept = -1;   // (the last result ends here; a failed call leaves none behind)
+  mvicp_outlier_stats S;
+  std::memset(&S, 0, sizeof(S));
+  S.n = f.n; S.has_normals = f.nor ? 1 : 0;
+  c->out_has_normals = f.nor ? 1 : 0;
+  if (f.n == 0) { c->out_n = 0; c->out_kept = 0; if (stats) *stats = S; return 0; }
+  if (!f.has_grid) { set_error("the outlier filter needs the per-cloud hash structure"); return MVICP_ERR_STATE; }
+  const int n = f.n;
+  const size_t NN = (size_t)n;
+  const bool normals = f.nor != nullptr, stat_on = std_ratio >= 0.0, rad_on = radius > 0.0;
+  hipStream_t st = c->stream;
+
+  // one arena: [control | mdist | kd2 | flag | rank | xyz | nrm | idx]; the results are views into it
+  const size_t off_md = 256, off_kd = off_md + align256(8 * NN), off_fl = off_kd + align256(8 * NN), off_ps = off_fl + align256(4 * NN);
+  const size_t off_x = off_ps + align256(4 * NN), off_nr = off_x + align256(24 * NN), off_ix = off_nr + (normals ? align256(24 * NN) : 0);
+  const size_t bytes = off_ix + align256(4 * NN);
+  MV_CHECK(ensure_dev(&c->out_dev, &c->out_dev_bytes, bytes));
+  if (!c->out_pin) MV_HIP(hipHostMalloc((void**)&c->out_pin, 256, hipHostMallocDefault));
+  char* D = c->out_dev;
+  OutCtl* d_ctl = reinterpret_cast<OutCtl*>(D);
+  OutCtl* h_ctl = reinterpret_cast<OutCtl*>(c->out_pin);
+  c->out_mdist = reinterpret_cast<double*>(D + off_md); c->out_kd2 = reinterpret_cast<double*>(D + off_kd);
+  int* flag = reinterpret_cast<int*>(D + off_fl); int* pos = reinterpret_cast<int*>(D + off_ps);
+  c->out_xyz = reinterpret_cast<double*>(D + off_x); c->out_nrm = normals ? reinterpret_cast<double*>(D + off_nr) : nullptr;
+  c->out_idx = reinterpret_cast<int*>(D + off_ix);
+  size_t scan_bytes = 0;
+  MV_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, flag, pos, 0, NN, rocprim::plus<int>(), st));
+  MV_CHECK(ensure_dev(&c->out_tmp, &c->out_tmp_bytes, std::max<size_t>(scan_bytes, 256)));
+
+  MV_HIP(hipMemsetAsync(d_ctl, 0, sizeof(OutCtl), st));
+  KnnJob j;
+  const GridDev& g = f.grid;
+  j.crec = (const PointRec*)g.crec; j.n = n;
+  j.table = (const HashEntry*)g.table; j.mask = g.table_mask; j.shift = g.table_shift;
+  j.ox = g.origin[0]; j.oy = g.origin[1]; j.oz = g.origin[2]; j.h = g.cell; j.inv_h = g.inv_cell;
+  j.dx = g.dims[0]; j.dy = g.dims[1]; j.dz = g.dims[2];
+  j.k = k; j.mdist = c->out_mdist; j.kd2 = c->out_kd2; j.mmax = &d_ctl->mmax;
+  {
+    ProfScope ps(c, "outlier_knn", 0.0);
+    if (k <= 8) hipLaunchKernelGGL(outlier_knn_kernel<9>, dim3(grid_of(n, NT)), dim3(NT), 0, st, j);
+    else if (k <= 16) hipLaunchKernelGGL(outlier_knn_kernel<17>, dim3(grid_of(n, NT)), dim3(NT), 0, st, j);
+    else hipLaunchKernelGGL(outlier_knn_kernel<33>, dim3(grid_of(n, NT)), dim3(NT), 0, st, j);
+  }
+  MV_HIP(hipGetLastError());
+
+  int stat = 0, q = 0;
+  double T = 0.0;
+  if (stat_on) {
+    MV_HIP(hipMemcpyAsync(h_ctl, d_ctl, sizeof(OutCtl), hipMemcpyDeviceToHost, st));
+    MV_HIP(hipStreamSynchronize(st));
+    double mmax;
+    std::memcpy(&mmax, &h_ctl->mmax, 8);
+    if (!std::isfinite(mmax)) { set_error("outlier filter: a neighbour distance is not finite (coordinates too large)"); return MVICP_ERR_ARG; }
+    if (mmax > 0.0) {
+      int ex = 0;
+      (void)std::frexp(mmax, &ex);   // mmax = m 2^ex, m in [0.5, 1): mmax 2^(31 - ex) in [2^30, 2^31)
+      q = 31 - ex; stat = 1;
+      {
+        ProfScope ps(c, "outlier_sum", 8.0 * n);
+        hipLaunchKernelGGL(outlier_sum_kernel, dim3(grid_of(n, VT)), dim3(VT), 0, st, c->out_mdist, n, q, d_ctl);
+      }
+      MV_HIP(hipGetLastError());
+      MV_HIP(hipMemcpyAsync(h_ctl, d_ctl, sizeof(OutCtl), hipMemcpyDeviceToHost, st));
+      MV_HIP(hipStreamSynchronize(st));
+      const unsigned __int128 s2 = ((unsigned __int128)h_ctl->s2hi << 32) + h_ctl->s2lo;
+      S.q_exp = q; S.s1 = h_ctl->s1; S.s2_hi = (unsigned long long)(s2 >> 64); S.s2_lo = (unsigned long long)s2;
+      MV_CHECK(mvicp_outlier_threshold(n, S.s1, S.s2_hi, S.s2_lo, std_ratio, &T));
+      S.T = T; S.threshold = std::ldexp(T, -q);
+    }
+  }
+  {
+    ProfScope ps(c, "outlier_flag", 20.0 * n);
+    hipLaunchKernelGGL(outlier_flag_kernel, dim3(grid_of(n, VT)), dim3(VT), 0, st, c->out_mdist, c->out_kd2, n, stat, q, T, rad_on ? 1 : 0, radius, flag);
+  }
+  MV_HIP(hipGetLastError());
+  {
+    ProfScope ps(c, "outlier_compact", (normals ? 108.0 : 60.0) * n);
+    size_t tb = scan_bytes;
+    MV_HIP(rocprim::exclusive_scan(c->out_tmp, tb, flag, pos, 0, NN, rocprim::plus<int>(), st));
+    if (normals) hipLaunchKernelGGL(outlier_compact_kernel<true>, dim3(grid_of(n, VT)), dim3(VT), 0, st, f.pts, f.nor, flag, pos, n, c->out_xyz, c->out_nrm, c->out_idx, d_ctl);
+    else hipLaunchKernelGGL(outlier_compact_kernel<false>, dim3(grid_of(n, VT)), dim3(VT), 0, st, f.pts, f.nor, flag, pos, n, c->out_xyz, c->out_nrm, c->out_idx, d_ctl);
+  }
+  MV_HIP(hipGetLastError());
+  MV_HIP(hipMemcpyAsync(h_ctl, d_ctl, sizeof(OutCtl), hipMemcpyDeviceToHost, st));
+  MV_HIP(hipStreamSynchronize(st));
+  const int kept = h_ctl->kept;
+  if (kept < 0 || kept > n) { set_error("outlier filter: %d kept of %d", kept, n); return MVICP_ERR_INTERNAL; }
+  S.kept = kept;
+  if (stats) *stats = S;
+  c->out_n = n; c->out_kept = kept;
+  return kept;
+}
+
+}  // namespace mvicp

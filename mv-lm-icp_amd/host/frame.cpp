@@ -347,6 +347,22 @@ std::shared_ptr<Frame> Frame::voxelDownsample(double voxel) {
   return out;
 }
 
+std::shared_ptr<Frame> Frame::removeOutliers(int k, double std_ratio, double radius) {
+  std::shared_ptr<Frame> out(new Frame());
+  out->fixed = fixed; out->pose = pose; out->poseGroundTruth = poseGroundTruth;
+  for (const OutgoingEdge& e : neighbours) out->neighbours.push_back(OutgoingEdge{e.neighbourIdx, e.weight, {}});
+  if (pts.empty()) return out;
+  int slot = 0;
+  mvicp_ctx* c = Session::get().query_context(this, &slot, true);
+  mvicp_outlier_stats st;
+  const long long m = mvicp_outlier_filter(c, slot, k, std_ratio, radius, &st);
+  if (m < 0) check((int)m);
+  out->pts.assign((size_t)m, Vector3d());
+  out->nor.assign(st.has_normals && nor.size() == pts.size() ? (size_t)m : 0, Vector3d());
+  if (m) check(mvicp_outlier_fetch(c, m, out->pts[0].data(), out->nor.empty() ? nullptr : out->nor[0].data(), nullptr, 0, nullptr, nullptr));
+  return out;
+}
+
 double Frame::getClosestPoint(const Vector3d& q, size_t& ret_index) {
   int slot = 0, idx = -1;
   double d2 = 0.0;

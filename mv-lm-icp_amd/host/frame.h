@@ -63,6 +63,12 @@ class Frame {
   // finds for this frame.  A driver registers the copies for its first rounds and hands their poses to the full frames (bin/multiview
   // --coarse_voxel / --coarse_rounds).
   std::shared_ptr<Frame> voxelDownsample(double voxel);
+  // A cleaned copy of this frame (no counterpart in the reference): mvicp_outlier_filter on this cloud as it is stored -- the statistical
+  // rule (mean distance to the k nearest neighbours against mean + std_ratio sigma over the cloud; std_ratio < 0: off) and the radius rule
+  // (at least k neighbours within `radius`; radius <= 0: off).  The new Frame has the kept pts / nor in their original order and the same
+  // pose, poseGroundTruth, fixed and neighbours (index and weight; the correspondence lists start empty).  Runs in the context
+  // Session::query_context finds for this frame (bin/multiview --sor_k / --sor_ratio / --ror_radius).
+  std::shared_ptr<Frame> removeOutliers(int k, double std_ratio, double radius);
 
  private:
   std::vector<int> knn_table_; size_t knn_k_ = 0; const void* knn_pts_ = nullptr; size_t knn_n_ = 0;   // cache of getNeighbourIndices

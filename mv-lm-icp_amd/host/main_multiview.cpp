@@ -24,6 +24,10 @@
 // --fused_out FILE --fused_voxel H: after the last round the fused model of ALL frames at the final poses (Session::fusedModel: one point per
 // voxel of edge H) is written to FILE in the `.xyz` row format, `x y z nx ny nz` with 17 significant digits (`x y z` when a frame has no
 // normals): exactly one row per voxel, in output order, no count line.
+// --sor_k K --sor_ratio A --ror_radius R (default K = 0 = off): every frame is cleaned after loading, before recomputeNormals and before any
+// coarse level, by Frame::removeOutliers(K, A, R): the statistical rule over the K nearest neighbours (A < 0, the default without --sor_ratio
+// when only a radius is given: off; --sor_ratio alone defaults to 2) and / or the radius rule (at least K neighbours within R; R <= 0: off).
+// One line per frame, `outlier filter: frame i kept a of b` (printed with --quiet too).
 #include <chrono>
 #include <cstring>
 #include <fstream>
@@ -47,6 +51,13 @@ static void loadFrames(const Flags& F, std::vector<std::shared_ptr<Frame>>& fram
     std::shared_ptr<Frame> f(new Frame());
     const int j = F.b("fake", false) ? 0 : i;
     loadXYZ(clouds[j], f->pts, f->nor, !F.b("drop_phantom_row", false));
+    if (F.i("sor_k", 0) > 0) {
+      const double radius = F.f("ror_radius", 0.0);
+      const size_t before = f->pts.size();
+      std::shared_ptr<Frame> kept = f->removeOutliers(F.i("sor_k", 0), F.f("sor_ratio", radius > 0.0 ? -1.0 : 2.0), radius);
+      f->pts.swap(kept->pts); f->nor.swap(kept->nor); ++f->version;   // (a context that holds the old cloud re-uploads)
+      std::cout << "outlier filter: frame " << frames.size() << " kept " << f->pts.size() << " of " << before << std::endl;
+    }
     if (F.b("recomputeNormals", true)) f->recomputeNormals();  // main_multiview.cpp:49,68-70 (default on)
     if (groundtruth.size() == clouds.size()) {
       f->pose = loadMatrix4d(poses[i]);
@@ -72,7 +83,9 @@ int main(int argc, char** argv) {
   noiseStream() = F.s("noise_stream", "libstdc++") == "libc++" ? 1 : F.s("noise_stream", "libstdc++") == "g++" ? 2 : 0;
 
   std::vector<std::shared_ptr<Frame>> frames;
-  loadFrames(F, frames, dir);
+  try {
+    loadFrames(F, frames, dir);
+  } catch (const std::exception& ex) { std::cerr << ex.what() << std::endl; return 2; }
   if (frames.empty()) { std::cerr << "no frames loaded from " << dir << std::endl; return 1; }
   if (!F.s("dump_knn", "").empty()) {
     try {

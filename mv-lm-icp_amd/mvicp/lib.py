@@ -18,6 +18,7 @@ SYMBOLS = [
     "mvicp_lm_solve", "mvicp_set_option", "mvicp_nn_census", "mvicp_nn_census_ex", "mvicp_reset_history", "mvicp_profile_enable", "mvicp_profile_reset", "mvicp_profile_get", "mvicp_profile_get_ex", "mvicp_stream", "mvicp_sync",
     "mvicp_closedform_point_to_point", "mvicp_closedform_point_to_plane", "mvicp_set_frame_device", "mvicp_get_structure",
     "mvicp_overlap", "mvicp_graph_from_overlap", "mvicp_voxel_grid", "mvicp_voxel_fetch",
+    "mvicp_outlier_filter", "mvicp_outlier_fetch", "mvicp_outlier_threshold",
 ]
 
 # names of mvicp_get_structure (include/mvicp.h)
@@ -35,6 +36,16 @@ class Summary(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class OutlierStats(C.Structure):
+    _fields_ = [("n", C.c_longlong), ("kept", C.c_longlong), ("q_exp", C.c_int), ("has_normals", C.c_int), ("s1", C.c_ulonglong),
+                ("s2_hi", C.c_ulonglong), ("s2_lo", C.c_ulonglong), ("T", C.c_double), ("threshold", C.c_double)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["s2"] = (d["s2_hi"] << 64) | d["s2_lo"]
+        return d
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_size_t)
@@ -101,6 +112,10 @@ def load_library(path=None):
     lib.mvicp_voxel_grid.argtypes = [vp, C.c_int, ip, dp, C.c_double, ip]
     lib.mvicp_voxel_grid.restype = C.c_longlong
     lib.mvicp_voxel_fetch.argtypes = [vp, C.c_longlong, vp, vp, vp]
+    lib.mvicp_outlier_filter.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(OutlierStats)]
+    lib.mvicp_outlier_filter.restype = C.c_longlong
+    lib.mvicp_outlier_fetch.argtypes = [vp, C.c_longlong, vp, vp, vp, C.c_longlong, vp, vp]
+    lib.mvicp_outlier_threshold.argtypes = [C.c_longlong, C.c_ulonglong, C.c_ulonglong, C.c_ulonglong, C.c_double, dp]
     if path is None:
         _lib = lib
     return lib
@@ -185,6 +200,18 @@ def graph_from_overlap(samples, hits, sumq=None, knn=2, min_fraction=0.0, skip_f
     n = _check(lib, lib.mvicp_graph_from_overlap(K, _ip(samples), _ip(hits), sq.ctypes.data_as(C.POINTER(C.c_longlong)) if sq is not None else None,
                                                  int(knn), float(min_fraction), int(bool(skip_fixed0)), int(cap), _ip(src), _ip(dst), C.byref(nc)))
     return src[:n].copy(), dst[:n].copy(), int(nc.value)
+
+
+def outlier_threshold(n, s1, s2, std_ratio):
+    """mvicp_outlier_threshold: the threshold T (quantised units) of the statistical outlier rule from the exact integer sums
+    S1 = sum M_i and S2 = sum M_i^2 (Python integers; S2 up to 128 bits) over n points.  Host only."""
+    lib = load_library()
+    s1, s2 = int(s1), int(s2)
+    if not (0 <= s1 < 1 << 64 and 0 <= s2 < 1 << 128):
+        raise ValueError("s1 must fit 64 bits and s2 128 bits")
+    T = C.c_double(0.0)
+    _check(lib, lib.mvicp_outlier_threshold(int(n), s1, s2 >> 64, s2 & ((1 << 64) - 1), float(std_ratio), C.byref(T)))
+    return T.value
 
 
 def closedform_point_to_point(src, dst):
@@ -488,6 +515,33 @@ class Engine:
             ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and m else None
         _check(self.lib, self.lib.mvicp_voxel_fetch(self.h, m, ptr(xyz), ptr(nrm), ptr(cnt)))
         return {"xyz": xyz, "nrm": nrm, "cnt": cnt}
+
+    def outlier_filter(self, frame, k=16, std_ratio=2.0, radius=0.0, device=False):
+        """mvicp_outlier_filter + mvicp_outlier_fetch on the stored cloud of `frame`: the statistical rule (mean distance to the k nearest
+        neighbours against mean + std_ratio * sigma over the cloud; std_ratio < 0: off) and the radius rule (at least k neighbours within
+        `radius`; radius <= 0: off) -> dict(xyz (kept,3), nrm (kept,3) or None, idx (kept,) int32 original indices ascending, mdist (n,),
+        kd2 (n,), stats).  device=True: torch tensors on the engine's GPU (xyz / nrm ready for set_frame_device) instead of numpy arrays.
+        Needs no graph; history-neutral."""
+        S = OutlierStats()
+        kept = int(_check(self.lib, self.lib.mvicp_outlier_filter(self.h, int(frame), int(k), float(std_ratio), float(radius), C.byref(S))))
+        n = int(S.n)
+        has_nrm = bool(S.has_normals)
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+            f64, i32 = torch.float64, torch.int32
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+        else:
+            mk = lambda shape, dt: np.zeros(shape, dtype=dt)
+            f64, i32 = np.float64, np.int32
+            ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+        xyz, nrm, idx = mk((kept, 3), f64), (mk((kept, 3), f64) if has_nrm else None), mk((kept,), i32)
+        mdist, kd2 = mk((n,), f64), mk((n,), f64)
+        if device:
+            torch.cuda.synchronize(dev)   # (the allocations are the caller's; the library fills them on its own stream and waits)
+        _check(self.lib, self.lib.mvicp_outlier_fetch(self.h, kept, ptr(xyz), ptr(nrm), ptr(idx), n, ptr(mdist), ptr(kd2)))
+        return {"xyz": xyz, "nrm": nrm, "idx": idx, "mdist": mdist, "kd2": kd2, "stats": S.as_dict()}
 
     def nn_query(self, frame, queries, nn_method=NN_AUTO):
         q = np.ascontiguousarray(queries, dtype=np.float64)
