@@ -205,6 +205,17 @@ int mvicp_outlier_fetch(mvicp_ctx* ctx, long long cap_kept, double* xyz, double*
  * Errors: n < 2, NULL T, a non-finite std_ratio, n S2 >= 2^128 or S1^2 > n S2 -> MVICP_ERR_ARG. */
 int mvicp_outlier_threshold(long long n, unsigned long long s1, unsigned long long s2_hi, unsigned long long s2_lo, double std_ratio, double* T);
 
+/* The rounding allowance of the temporal cache (pure host function, no context): what mvicp_correspond adds to the displacement |dM p + dv|
+ * of an edge's queries between the search at (pose_src_old, pose_dst_old) and the one at (pose_src, pose_dst), poses as 16 column-major
+ * doubles, max_norm >= max |p| over the source cloud.  With x = (Rs, ts, Rd^-1, td) the query transform of a pose pair (Rd^-1 as
+ * mvicp_correspond computes it) and B(x) = ||Rd^-1||_F (|ts| + 16 ||Rs||_F max_norm + 13 |ts - td|):
+ *   *out = 2^-52 (B(x_old) + B(x_new)), and 0 iff the two transforms are bit-identical (then every query is, too).
+ * It bounds the rounding of both evaluations of the fp64 query map (which rounds R p + ts at the size of ts, not of ts - td) and of
+ * dM, dv themselves; the derivation is at cache_allowance_xf in csrc/api.cpp and in DESIGN.md section 3.4.
+ * Errors: a NULL pointer, max_norm < 0 or NaN -> MVICP_ERR_ARG. */
+int mvicp_cache_allowance(const double* pose_src_old, const double* pose_dst_old, const double* pose_src, const double* pose_dst,
+                          double max_norm, double* out);
+
 /* The graph rule on top of the census (pure host function, no context).  Frame i keeps the knn frames j != i with the most hits, among
  * those with hits[i*K+j] > 0 and hits[i*K+j] >= min_fraction * samples[i]; equal hits: the smaller sumq first (within one row that is
  * the smaller mean distance: an exact integer comparison, no division), then the lower j.  sumq NULL: hits, then lower j.  Edges are

@@ -8,6 +8,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <exception>
+#include <limits>
 #include <mutex>
 #include <new>
 #include <thread>
@@ -205,6 +206,52 @@ void fill_query_xf(const double* Ps, const double* Pd, double* x) {
     for (int i = 0; i < 3; ++i) { x[i + 3 * j] = Ps[i + 4 * j]; Rd[i + 3 * j] = Pd[i + 4 * j]; }
   for (int i = 0; i < 3; ++i) { x[9 + i] = Ps[12 + i]; x[21 + i] = Pd[12 + i]; }
   inverse3(Rd, x + 12);
+}
+
+// The affine form of a query transform block x (fill_query_xf): q = M p + v with M = Rd^-1 Rs (9, column-major), v = Rd^-1 (ts - td) (3).
+// The kernels never evaluate it (they run xf_point); its change between two searches is the displacement cache_eps reads.
+void query_affine(const double* x, double* Mq) {
+  for (int j = 0; j < 3; ++j)
+    for (int i = 0; i < 3; ++i) Mq[i + 3 * j] = x[12 + i] * x[0 + 3 * j] + x[12 + i + 3] * x[1 + 3 * j] + x[12 + i + 6] * x[2 + 3 * j];
+  const double dt[3] = {x[9] - x[21], x[10] - x[22], x[11] - x[23]};
+  for (int i = 0; i < 3; ++i) Mq[9 + i] = x[12 + i] * dt[0] + x[12 + i + 3] * dt[1] + x[12 + i + 6] * dt[2];
+}
+
+// The rounding allowance of the temporal cache (nn_cache.h: cache_eps adds it to |dM p + dv|): a bound on everything that separates the
+// displacement the kernel computes from the distance between the two queries the kernels really searched with.
+//
+// u = 2^-53; bounds to first order in u (the result is doubled at the end).  A block x = (R, ts, Ri, td) and a point |p| <= r define the
+// exact query q(x) = Ri (R p + ts - td) and the affine pair M(x) = Ri R, v(x) = Ri (ts - td) over the reals.  Norms of vectors are
+// Euclidean, of matrices Frobenius (|| |A| y || <= ||A||_F |y|), s_i = sum_j |R_ij||p_j|, so |s| <= ||R||_F r.
+//  (a) xf_point (nn_metric.h), per component.  The three products and two sums of R p: error <= 3 u s_i.  The sum with ts_i rounds
+//      at the size of its RESULT: u |g_i| <= u (|ts_i| + s_i).  u^_i = fl(g^_i - td_i) rounds at the size of ITS result (exact when g^_i
+//      and td_i are close, Sterbenz): u |u_i| <= u (s_i + |ts_i - td_i|).  Together |u^ - u| <= u (|ts| + 5 ||R||_F r + |ts - td|).
+//      q^ = fl(Ri u^), three products and two sums: 3 u |Ri||u^|, |u^| <= ||R||_F r + |ts - td|.  So
+//          |q^ - q| <= u ||Ri||_F (|ts| + 8 ||R||_F r + 4 |ts - td|).
+//      The leading term lives at the size of ts, NOT of v: two poses that share a large world translation (georeferenced scans) have
+//      a small v and still round g = R p + ts at |ts| — 4e-10 m at a UTM northing of 4e6 m.
+//  (b) query_affine: |M^ - M| <= 3 u |Ri||R| and |v^ - v| <= 4 u |Ri||ts - td| entrywise (the difference ts - td is rounded once, at
+//      its own size), so |(M^ - M) p + (v^ - v)| <= u ||Ri||_F (3 ||R||_F r + 4 |ts - td|).
+//  (c) the kernel's e^ = fl(dM p + dv) with dM = fl(M^_new - M^_old), dv likewise: one rounding for the difference, four through the
+//      sum, each relative to the terms and not to the (possibly cancelling) result: |e^ - e| <= 5 u (|dM||p| + |dv|) <=
+//      5 u sum over both blocks of ||Ri||_F (||R||_F r + |ts - td|).  (The norm's own roundings are relative to |e^|: cache_eps'
+//      factor 1 + 1e-9.)
+// Both searches count, each with its own block:
+//     |q^_new - q^_old| <= |e^| (1 + 1e-9) + u sum over both blocks of ||Ri||_F (|ts| + 16 ||R||_F r + 13 |ts - td|).
+// The allowance is that sum with 2 u = 2^-52: the spare factor covers the second-order terms and the roundings of the norms, of r
+// (max_norm, a rounded norm) and of this sum.  Contracted multiply-adds only remove roundings.  Blocks that are bit-identical give the
+// same queries bit for bit: 0, which the kernels read as "nothing moved"; any other pair gives a positive value.
+double cache_allowance_xf(const double* x_old, const double* x_new, double r) {
+  if (std::memcmp(x_old, x_new, sizeof(double) * kXfRigid) == 0) return 0.0;
+  double b = 0.0;
+  for (const double* x : {x_old, x_new}) {
+    double fr = 0.0, fi = 0.0;
+    for (int k = 0; k < 9; ++k) { fr += x[k] * x[k]; fi += x[12 + k] * x[12 + k]; }
+    const double dt[3] = {x[9] - x[21], x[10] - x[22], x[11] - x[23]};
+    const double ts = std::sqrt(x[9] * x[9] + x[10] * x[10] + x[11] * x[11]), dtn = std::sqrt(dt[0] * dt[0] + dt[1] * dt[1] + dt[2] * dt[2]);
+    b += std::sqrt(fi) * (ts + 16.0 * std::sqrt(fr) * r + 13.0 * dtn);
+  }
+  return std::max(0x1p-52 * b, std::numeric_limits<double>::min());
 }
 
 int ensure_pin(mvicp_ctx* c, size_t doubles) {
@@ -916,6 +963,15 @@ int mvicp_outlier_threshold(long long n, unsigned long long s1, unsigned long lo
   return MVICP_OK;
 } MVICP_GUARD_ABI
 
+int mvicp_cache_allowance(const double* pose_src_old, const double* pose_dst_old, const double* pose_src, const double* pose_dst, double max_norm, double* out) try {
+  if (!pose_src_old || !pose_dst_old || !pose_src || !pose_dst || !out || !(max_norm >= 0.0)) { set_error("cache allowance: needs four poses, max_norm >= 0 and out"); return MVICP_ERR_ARG; }
+  double xo[kXfRigid], xn[kXfRigid];
+  fill_query_xf(pose_src_old, pose_dst_old, xo);
+  fill_query_xf(pose_src, pose_dst, xn);
+  *out = cache_allowance_xf(xo, xn, max_norm);
+  return MVICP_OK;
+} MVICP_GUARD_ABI
+
 int mvicp_graph_from_overlap(int n_frames, const int* samples, const int* hits, const long long* sumq, int knn, double min_fraction,
                              int skip_frame0, int cap, int* src, int* dst, int* n_components) try {
   const int K = n_frames;
@@ -1225,15 +1281,11 @@ static int correspond_body(mvicp_ctx* c, const double* poses, const unsigned cha
     double* x = hx + (size_t)e * kEdgeXf;
     fill_query_xf(Ps, Pd, x);
     // temporal cache: q = M p + v with M = Rd^-1 Rs, v = Rd^-1 (ts - td).  Between two searches every query of the edge
-    // moves by at most ||dM||_F max|p| + |dv|  (+ a rounding allowance far above the 1e-16-relative error of the fp64 map).
+    // moves by at most ||dM||_F max|p| + |dv|  (+ the rounding allowance of cache_allowance_xf).
     double Mq[12];
-    for (int j = 0; j < 3; ++j)
-      for (int i = 0; i < 3; ++i) Mq[i + 3 * j] = x[12 + i] * x[0 + 3 * j] + x[12 + i + 3] * x[1 + 3 * j] + x[12 + i + 6] * x[2 + 3 * j];
-    const double dt[3] = {x[9] - x[21], x[10] - x[22], x[11] - x[23]};
-    for (int i = 0; i < 3; ++i) Mq[9 + i] = x[12 + i] * dt[0] + x[12 + i + 3] * dt[1] + x[12 + i + 6] * dt[2];
+    query_affine(x, Mq);
     double* pq = &c->prev_q[(size_t)e * 12];
-    double scale = 0.0;
-    for (int k = 0; k < 12; ++k) { x[kXfDM + k] = Mq[k] - pq[k]; scale = std::max(scale, std::fabs(Mq[k])); }
+    for (int k = 0; k < 12; ++k) x[kXfDM + k] = Mq[k] - pq[k];
     const double rmax = c->frames[c->esrc[e]].max_norm;
     if (c->active[e]) {
       // how far this edge's queries can have moved since the last search, in units of the bounds-leaving builds' guard band: what decides the
@@ -1246,7 +1298,7 @@ static int correspond_body(mvicp_ctx* c, const double* poses, const unsigned cha
     }
     const bool cache_on = c->nn_cache_valid && c->nn_cache_enable && c->active[e] && (int)c->nn_cache_edge.size() == E && c->nn_cache_edge[e] &&
                           c->nn_cache_thresh == thresh;
-    // allowance for the rounding of the fp64 query map itself (both evaluations): ~1e-16 (|M||p| + |v|), taken 1e4 times larger.
+    // allowance for the rounding of the fp64 query map itself (both evaluations) and of dM, dv: cache_allowance_xf.
     // A transform that is BIT-IDENTICAL to last search's (a converged registration: the LM ends without stepping) reproduces every
     // query bit for bit: no allowance, and dM = dv = 0 below, so the kernel sees eps == 0 and re-verifies without rewriting anything.
     double* pxf = &c->prev_xf[(size_t)e * kXfRigid];
@@ -1254,7 +1306,7 @@ static int correspond_body(mvicp_ctx* c, const double* poses, const unsigned cha
     else if (c->active[e]) unchanged[e] = hist_ok && c->nn_cache_edge[e] && c->qpos_valid[e] && !c->explicit_list[e] && std::memcmp(pxf, x, sizeof(double) * kXfRigid) == 0;
     else unchanged[e] = hist_ok && !c->nn_cache_edge[e] && !c->explicit_list[e] && c->h_count[e] == 0;   // not searched now, not searched then: stays empty
     const bool same_xf = cache_on && std::memcmp(pxf, x, sizeof(double) * kXfRigid) == 0;
-    x[kXfCache] = cache_on ? (same_xf ? 0.0 : 1e-12 * (scale * (rmax + 1.0) + 1.0)) : -1.0;
+    x[kXfCache] = cache_on ? cache_allowance_xf(pxf, x, rmax) : -1.0;
     same_edge[e] = same_xf;
     std::memcpy(pxf, x, sizeof(double) * kXfRigid);
     for (int k = kXfPad; k < kEdgeXf; ++k) x[k] = 0.0;

@@ -1,7 +1,8 @@
 // The temporal-cache rule of the exact NN kernels (nn_grid_kernel, nn_cell_kernel, nn_tile_kernel, nn_mfma_kernel).
 //
 // Last search left, per query, its neighbour and a lower bound L on the distance to every OTHER target (out_lb, fp32 rounded down).  Since
-// then the query moved by exactly eps = |dM p + dv| (pose update; the edge's kEdgeXf block carries dM, dv and a rounding allowance), so every
+// then the query moved by at most eps = |dM p + dv| (1 + 1e-9) + allowance (pose update; the edge's kEdgeXf block carries dM, dv and the rounding
+// allowance of api.cpp:cache_allowance_xf, which bounds what separates that figure from the distance between the two ROUNDED queries), so every
 // other target is still >= L - eps away: if the re-evaluated distance to the old neighbour is strictly below that, it is still the unique
 // nearest neighbour and its exact squared distance (reference arithmetic) is the answer — no search.
 #pragma once
@@ -10,7 +11,8 @@
 
 namespace mvicp {
 
-// how far THIS query (source point p) moved since the last search: |dM p + dv| (exactly, up to the rounding allowance sxf[kXfCache] >= 0).
+// how far THIS query (source point p) moved since the last search, at most: |dM p + dv| plus the rounding allowance sxf[kXfCache] >= 0; the factor
+// 1 + 1e-9 covers the roundings of the norm itself, which are relative to it (those of dM p + dv are not: they are in the allowance).
 // 0 only when the host found the edge's query transform bit-identical to last search's (allowance 0, dM = dv = 0).
 __device__ __forceinline__ double cache_eps(const double* sxf, double p0, double p1, double p2) {
   const double e0 = sxf[kXfDM] * p0 + sxf[kXfDM + 3] * p1 + sxf[kXfDM + 6] * p2 + sxf[kXfDv];

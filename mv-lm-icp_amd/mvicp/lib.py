@@ -18,7 +18,7 @@ SYMBOLS = [
     "mvicp_lm_solve", "mvicp_set_option", "mvicp_nn_census", "mvicp_nn_census_ex", "mvicp_reset_history", "mvicp_profile_enable", "mvicp_profile_reset", "mvicp_profile_get", "mvicp_profile_get_ex", "mvicp_stream", "mvicp_sync",
     "mvicp_closedform_point_to_point", "mvicp_closedform_point_to_plane", "mvicp_set_frame_device", "mvicp_get_structure",
     "mvicp_overlap", "mvicp_graph_from_overlap", "mvicp_voxel_grid", "mvicp_voxel_fetch",
-    "mvicp_outlier_filter", "mvicp_outlier_fetch", "mvicp_outlier_threshold",
+    "mvicp_outlier_filter", "mvicp_outlier_fetch", "mvicp_outlier_threshold", "mvicp_cache_allowance",
 ]
 
 # names of mvicp_get_structure (include/mvicp.h)
@@ -116,6 +116,7 @@ def load_library(path=None):
     lib.mvicp_outlier_filter.restype = C.c_longlong
     lib.mvicp_outlier_fetch.argtypes = [vp, C.c_longlong, vp, vp, vp, C.c_longlong, vp, vp]
     lib.mvicp_outlier_threshold.argtypes = [C.c_longlong, C.c_ulonglong, C.c_ulonglong, C.c_ulonglong, C.c_double, dp]
+    lib.mvicp_cache_allowance.argtypes = [dp, dp, dp, dp, C.c_double, dp]
     if path is None:
         _lib = lib
     return lib
@@ -212,6 +213,16 @@ def outlier_threshold(n, s1, s2, std_ratio):
     T = C.c_double(0.0)
     _check(lib, lib.mvicp_outlier_threshold(int(n), s1, s2 >> 64, s2 & ((1 << 64) - 1), float(std_ratio), C.byref(T)))
     return T.value
+
+
+def cache_allowance(pose_src_old, pose_dst_old, pose_src, pose_dst, max_norm):
+    """mvicp_cache_allowance: the rounding allowance the temporal cache adds to an edge's query displacement between the search at
+    the old pose pair and the one at the new pair (4x4 matrices), for a source cloud with max |p| <= max_norm.  Host only."""
+    lib = load_library()
+    P = poses_to_c(np.stack([np.asarray(a, dtype=np.float64).reshape(4, 4) for a in (pose_src_old, pose_dst_old, pose_src, pose_dst)]))
+    out = C.c_double(0.0)
+    _check(lib, lib.mvicp_cache_allowance(_dp(P[0]), _dp(P[1]), _dp(P[2]), _dp(P[3]), float(max_norm), C.byref(out)))
+    return out.value
 
 
 def closedform_point_to_point(src, dst):
