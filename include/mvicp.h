@@ -205,6 +205,48 @@ int mvicp_outlier_fetch(mvicp_ctx* ctx, long long cap_kept, double* xyz, double*
  * Errors: n < 2, NULL T, a non-finite std_ratio, n S2 >= 2^128 or S1^2 > n S2 -> MVICP_ERR_ARG. */
 int mvicp_outlier_threshold(long long n, unsigned long long s1, unsigned long long s2_hi, unsigned long long s2_lo, double std_ratio, double* T);
 
+/* ---- neighbour search: the k nearest and / or all points within a radius, for arbitrary queries, with indices ------------
+ * The search primitive of every point-cloud toolkit (search_knn, search_radius, the hybrid of the two) over one stored cloud.  The result
+ * is a pure function of the inputs, bit for bit (tests/knnref.py is the same definition in numpy):
+ *   Inputs     the stored cloud p_0 .. p_{n-1} of `frame` (the stored bytes, no pose); queries: m x 3 doubles in the frame's local
+ *              coordinates, like mvicp_nn_query.  `queries` may be a HOST pointer or a DEVICE pointer of the context's device, decided per
+ *              pointer as mvicp_voxel_fetch decides (another device's memory is MVICP_ERR_ARG); a device array must be fully written when
+ *              the call is made.  queries == NULL is SELF MODE: m is ignored, row i is the neighbourhood of p_i, i an ORIGINAL index, and
+ *              the point itself is an ordinary candidate with d2 = +0.
+ *   Metric     dist2 of csrc/nn_metric.h: (d0 d0 + d1 d1) + d2 d2 with d = q - p, every operation rounded on its own, no fma.
+ *   Radius     on iff radius > 0: j is a candidate of query i iff sqrt(dist2(q_i, p_j)) < radius (IEEE sqrt, strict) -- the predicate of
+ *              mvicp_outlier_filter; equivalently dist2 < B2, B2 as defined at mvicp_overlap.  Radius off: every j is a candidate.
+ *   Order      the candidates of a query are ordered by (dist2 ascending, ORIGINAL index j ascending).  This is deliberately NOT the
+ *              nanoflann visiting order of mvicp_recompute_normals' knn_out: that order exists to reproduce the reference and needs the
+ *              reference's own tree over the cloud; this one is a pure function of the cloud, no tie tree is built or needed, and among
+ *              equidistant points the lowest original indices win.
+ *   k mode     1 <= k <= 64: cnt[i] = min(k, number of candidates); row i of idx / d2 (dense m x k) holds the first cnt[i] candidates, the
+ *              rest of the row is padded with idx = -1, d2 = +inf; off, if asked for, gets the m + 1 entries i k.
+ *   All mode   k == 0 (needs radius > 0): every candidate, in CSR form: off[0] = 0, off[i+1] = off[i] + cnt[i]; idx / d2 have off[m]
+ *              entries.  A row is put in order by one GPU wave in O(len^2 / 64): rows of thousands of entries (a radius as large as the
+ *              cloud) are correct, not fast.
+ *   Empty      an empty frame (n = 0) gives every cnt[i] = 0 and is not an error; m = 0 gives an empty result.
+ *   Anywhere   queries may lie anywhere, far outside the cloud included; those in empty space are exact, not fast.
+ * Needs the frame's hash structure (waits for pending builds and reports a failed one, like mvicp_overlap), NO graph, and is
+ * HISTORY-NEUTRAL: it leaves caches, seeds, lists, epochs, medians, the AUTO state, queued evaluations and tie_skip alone and builds no tie
+ * tree, so a registration with searches in between is bit-identical to one without.  With several ranks every rank computes it locally.
+ * The call returns when the result is complete; the result lives in library-owned device memory until the next mvicp_knn_search,
+ * mvicp_set_num_frames or mvicp_destroy.  Option "knn_order" (default 1; 0 = answer the queries in the order given instead of the order of
+ * their hash cells) changes the speed only: the result is the same bytes.  Profile scopes: "knn_key", "knn_search", "knn_count",
+ * "knn_fill", "knn_order".
+ * RETURNS THE NUMBER OF ENTRIES sum cnt[i] (>= 0) or a negative mvicp_status.
+ * Errors: NULL context, k outside [0, 64], a non-finite radius, k == 0 with radius <= 0, m < 0 or m >= 2^31 with queries given, a frame
+ * index out of range -> MVICP_ERR_ARG, decided before the context is touched; a frame never uploaded -> MVICP_ERR_STATE; a non-finite query
+ * coordinate, a stored neighbour distance that overflowed to +inf, an all-mode total >= 2^31 -> MVICP_ERR_ARG, reported by this call, and
+ * no result is left behind.  An argument error of the first kind leaves the previous result alone. */
+long long mvicp_knn_search(mvicp_ctx* ctx, int frame, const double* queries, long long m, int k, double radius);
+/* Copies the last result: cnt (m ints), off (m + 1 long long), idx (ints) / d2 (doubles) with m k entries (k mode) or off[m] (all mode);
+ * each may be NULL; each may be a HOST pointer or a DEVICE pointer of the context's device, decided per pointer as mvicp_voxel_fetch
+ * decides.  cap_rows = rows cnt holds (off holds one more), looked at only when cnt or off is given; cap_entries = entries idx / d2 hold,
+ * looked at only when one of the two is given.
+ * Errors: NULL context, cap_rows < m, cap_entries too small -> MVICP_ERR_ARG; no mvicp_knn_search before -> MVICP_ERR_STATE. */
+int mvicp_knn_fetch(mvicp_ctx* ctx, long long cap_rows, long long cap_entries, int* cnt, long long* off, int* idx, double* d2);
+
 /* The rounding allowance of the temporal cache (pure host function, no context): what mvicp_correspond adds to the displacement |dM p + dv|
  * of an edge's queries between the search at (pose_src_old, pose_dst_old) and the one at (pose_src, pose_dst), poses as 16 column-major
  * doubles, max_norm >= max |p| over the source cloud.  With x = (Rs, ts, Rd^-1, td) the query transform of a pose pair (Rd^-1 as

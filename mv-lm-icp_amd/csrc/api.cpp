@@ -554,6 +554,7 @@ int mvicp_destroy(mvicp_ctx* c) try {
   free_overlap(c);
   free_voxel(c);
   free_outlier(c);
+  free_knn(c);
   for (auto& kv : c->tables) if (kv.second.d) (void)hipFree(kv.second.d);
   if (c->d_census) (void)hipFree(c->d_census);
   if (c->h_census) (void)hipHostFree(c->h_census);
@@ -579,6 +580,7 @@ int mvicp_set_num_frames(mvicp_ctx* c, int n_frames) try {
   if (c->E) free_graph(c);
   free_voxel(c);   // (the last voxel-grid result ends here; every voxel call waits for its own work)
   free_outlier(c); // (and the last outlier-filter result)
+  free_knn(c);     // (and the last neighbour-search result)
   for (FrameDev& f : c->frames) { dev_free(f.pts); dev_free(f.nor); free_grid(f.grid); free_tie(f); }
   c->frames.assign(n_frames, FrameDev());
   c->n_frames = n_frames;
@@ -942,6 +944,45 @@ int mvicp_outlier_fetch(mvicp_ctx* c, long long cap_kept, double* xyz, double* n
   for (int t = 0; t < 5; ++t)
     if (dst[t] && bytes[t]) { kind[t] = destination_kind(c, dst[t], names[t]); if (kind[t] < 0) return kind[t]; }
   for (int t = 0; t < 5; ++t)
+    if (dst[t] && bytes[t]) MV_HIP(hipMemcpyAsync(dst[t], src[t], bytes[t], kind[t] ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+  MV_HIP(hipStreamSynchronize(c->stream));
+  return MVICP_OK;
+} MVICP_GUARD_ABI
+
+long long mvicp_knn_search(mvicp_ctx* c, int frame, const double* queries, long long m, int k, double radius) try {
+  // every argument error that needs no GPU first: nothing of the context has been touched when one of them is reported
+  if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
+  if (k < 0 || k > 64) { set_error("k = %d outside [0, 64]", k); return MVICP_ERR_ARG; }
+  if (!std::isfinite(radius)) { set_error("radius must be finite (<= 0: no radius)"); return MVICP_ERR_ARG; }
+  if (k == 0 && !(radius > 0.0)) { set_error("k = 0 (every neighbour within the radius) needs radius > 0"); return MVICP_ERR_ARG; }
+  if (queries && (m < 0 || m >= (1ll << 31))) { set_error("m = %lld outside [0, 2^31)", m); return MVICP_ERR_ARG; }
+  if (frame < 0 || frame >= c->n_frames) { set_error("frame %d out of range [0,%d)", frame, c->n_frames); return MVICP_ERR_ARG; }
+  if (!c->frames[frame].pts) { set_error("frame %d was never uploaded", frame); return MVICP_ERR_STATE; }
+  MV_CHECK(bind(c));
+  int on_device = 0;
+  if (queries && m > 0) { on_device = destination_kind(c, queries, "queries"); if (on_device < 0) return on_device; }
+  MV_CHECK(finish_builds(c));
+  const long long total = knn_search(c, c->frames[frame], queries, on_device, m, k, radius, radius > 0.0 ? sqrt_bound(radius) : 0.0);
+  if (c->profile) prof_collect_lazy(c);
+  return total;
+} MVICP_GUARD_ABI
+
+int mvicp_knn_fetch(mvicp_ctx* c, long long cap_rows, long long cap_entries, int* cnt, long long* off, int* idx, double* d2) try {
+  if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
+  if (c->knn_m < 0) { set_error("no neighbour search result: call mvicp_knn_search first"); return MVICP_ERR_STATE; }
+  const long long entries = c->knn_k ? c->knn_m * c->knn_k : c->knn_total;
+  if ((cnt || off) && cap_rows < c->knn_m) { set_error("cap_rows %lld < %lld rows", cap_rows, c->knn_m); return MVICP_ERR_ARG; }
+  if ((idx || d2) && cap_entries < entries) { set_error("cap_entries %lld < %lld entries", cap_entries, entries); return MVICP_ERR_ARG; }
+  MV_CHECK(bind(c));
+  const size_t m = (size_t)c->knn_m, e = (size_t)entries;
+  const void* src[4] = {c->knn_cnt, c->knn_off, c->knn_idx, c->knn_d2};
+  void* dst[4] = {cnt, off, idx, d2};
+  const size_t bytes[4] = {4 * m, 8 * (m + 1), 4 * e, 8 * e};
+  const char* names[4] = {"cnt", "off", "idx", "d2"};
+  int kind[4] = {0, 0, 0, 0};
+  for (int t = 0; t < 4; ++t)
+    if (dst[t] && bytes[t]) { kind[t] = destination_kind(c, dst[t], names[t]); if (kind[t] < 0) return kind[t]; }
+  for (int t = 0; t < 4; ++t)
     if (dst[t] && bytes[t]) MV_HIP(hipMemcpyAsync(dst[t], src[t], bytes[t], kind[t] ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
   MV_HIP(hipStreamSynchronize(c->stream));
   return MVICP_OK;
@@ -1879,6 +1920,7 @@ int mvicp_set_option(mvicp_ctx* c, const char* name, double value) try {
   if (std::strcmp(name, "tile_miss") == 0) { if (!(value >= 0.0 && value <= 64.0)) { set_error("tile_miss outside [0, 64]"); return MVICP_ERR_ARG; } c->tile_miss = (int)value; return MVICP_OK; }
   if (std::strcmp(name, "tile_cache") == 0) { c->tile_cache = (int)value; return MVICP_OK; }
   if (std::strcmp(name, "voxel_permute") == 0) { c->voxel_permute = value != 0.0; return MVICP_OK; }
+  if (std::strcmp(name, "knn_order") == 0) { c->knn_order = value != 0.0; return MVICP_OK; }
   if (std::strcmp(name, "spin_wait") == 0) { c->spin_wait = value != 0.0; return MVICP_OK; }
   if (std::strcmp(name, "fault_inject") == 0) { c->fault_inject = (int)value; return MVICP_OK; }            // tests: the value-th mvicp_correspond from now fails locally before its exchange
   if (std::strcmp(name, "fault_inject_build") == 0) { c->fault_inject_build.store((int)value); return MVICP_OK; }      // tests: the value-th structure build from now fails

@@ -261,6 +261,16 @@ struct mvicp_ctx {
   double* out_xyz = nullptr; double* out_nrm = nullptr; double* out_mdist = nullptr; double* out_kd2 = nullptr; int* out_idx = nullptr;
   long long out_n = -1, out_kept = -1; int out_has_normals = 0;
 
+  // neighbour search (knn.hip): the last result, library-owned until the next mvicp_knn_search / mvicp_set_num_frames / mvicp_destroy
+  // (knn_m < 0: none).  knn_dev holds [control | cnt | off], knn_ent the entries [idx | d2] (all mode: behind them the same in visiting
+  // order), knn_tmp the scratch (staged host queries, sort keys, rocprim storage); a pinned control block of its own.  Kept between calls
+  // and grown on demand: mvicp_knn_search touches nothing a search, a queued evaluation, the census, the voxel grid or the filter uses
+  char* knn_dev = nullptr; char* knn_ent = nullptr; char* knn_tmp = nullptr; char* knn_pin = nullptr;
+  size_t knn_dev_bytes = 0, knn_ent_bytes = 0, knn_tmp_bytes = 0;
+  int* knn_cnt = nullptr; long long* knn_off = nullptr; int* knn_idx = nullptr; double* knn_d2 = nullptr;
+  long long knn_m = -1, knn_total = 0; int knn_k = 0;   // rows, entries over all rows, the k of the call (0: all mode, CSR)
+  int knn_order = 1;               // option "knn_order": queries are answered in the order of their home cells (0: as given); the result is the same bytes
+
   // cached small tables
   struct CachedTable { std::vector<char> bytes; void* d = nullptr; size_t cap = 0; };
   std::map<std::string, CachedTable> tables;
@@ -373,6 +383,11 @@ void free_voxel(mvicp_ctx* c);     // the result and the buffers
 // status.  Waits for the stream; history-neutral.
 long long outlier_filter(mvicp_ctx* c, const FrameDev& f, int k, double std_ratio, double radius, mvicp_outlier_stats* stats);
 void free_outlier(mvicp_ctx* c);   // the result and the buffers
+// knn.hip: the neighbourhoods of m queries (host or device memory, as `queries_on_device` says) or, queries == null, of the cloud's own
+// points, in frame f (valid, uploaded, structures built); 0 <= k <= 64, k == 0 needs radius > 0; B2 = sqrt_bound(radius) when radius > 0.
+// The result stays on the context (knn_*).  Returns the number of entries or a negative status.  Waits for the stream; history-neutral.
+long long knn_search(mvicp_ctx* c, const FrameDev& f, const double* queries, int queries_on_device, long long m, int k, double radius, double B2);
+void free_knn(mvicp_ctx* c);       // the result and the buffers
 int launch_compact(mvicp_ctx* c, double d2_bound);                                    // corr.hip
 int launch_gather_stream(mvicp_ctx* c);
 int launch_select_median(mvicp_ctx* c, double d2_bound);   // two-pass select anchored at the acceptance bound: any key set, exact

@@ -19,6 +19,7 @@ SYMBOLS = [
     "mvicp_closedform_point_to_point", "mvicp_closedform_point_to_plane", "mvicp_set_frame_device", "mvicp_get_structure",
     "mvicp_overlap", "mvicp_graph_from_overlap", "mvicp_voxel_grid", "mvicp_voxel_fetch",
     "mvicp_outlier_filter", "mvicp_outlier_fetch", "mvicp_outlier_threshold", "mvicp_cache_allowance",
+    "mvicp_knn_search", "mvicp_knn_fetch",
 ]
 
 # names of mvicp_get_structure (include/mvicp.h)
@@ -117,6 +118,9 @@ def load_library(path=None):
     lib.mvicp_outlier_fetch.argtypes = [vp, C.c_longlong, vp, vp, vp, C.c_longlong, vp, vp]
     lib.mvicp_outlier_threshold.argtypes = [C.c_longlong, C.c_ulonglong, C.c_ulonglong, C.c_ulonglong, C.c_double, dp]
     lib.mvicp_cache_allowance.argtypes = [dp, dp, dp, dp, C.c_double, dp]
+    lib.mvicp_knn_search.argtypes = [vp, C.c_int, vp, C.c_longlong, C.c_int, C.c_double]
+    lib.mvicp_knn_search.restype = C.c_longlong
+    lib.mvicp_knn_fetch.argtypes = [vp, C.c_longlong, C.c_longlong, vp, vp, vp, vp]
     if path is None:
         _lib = lib
     return lib
@@ -553,6 +557,51 @@ class Engine:
             torch.cuda.synchronize(dev)   # (the allocations are the caller's; the library fills them on its own stream and waits)
         _check(self.lib, self.lib.mvicp_outlier_fetch(self.h, kept, ptr(xyz), ptr(nrm), ptr(idx), n, ptr(mdist), ptr(kd2)))
         return {"xyz": xyz, "nrm": nrm, "idx": idx, "mdist": mdist, "kd2": kd2, "stats": S.as_dict()}
+
+    def knn_search(self, frame, queries=None, k=8, radius=0.0, device=False):
+        """mvicp_knn_search + mvicp_knn_fetch on the stored cloud of `frame`: per query the candidates (every point, or with radius > 0 the
+        points with sqrt(d2) < radius) in the order (d2, original index).  1 <= k <= 64: the first k of them -> dict(cnt (m,) int32,
+        off (m+1,) int64 = i k, idx (m,k) int32 padded with -1, d2 (m,k) padded with +inf, total).  k = 0 (needs radius > 0): all of them in
+        CSR form -> idx / d2 flat with off[m] entries.  queries: (m,3) numpy array, a float64 torch tensor on the engine's GPU, or None =
+        the cloud's own points (row i = point i).  device=True: torch tensors on the engine's GPU instead of numpy arrays.
+        Needs no graph; history-neutral."""
+        keep = None
+        if queries is None:
+            qp, m = None, 0
+        elif isinstance(queries, np.ndarray) or not hasattr(queries, "data_ptr"):
+            keep = np.ascontiguousarray(queries, dtype=np.float64).reshape(-1, 3)
+            m = len(keep)
+            qp = keep.ctypes.data_as(C.c_void_p) if m else C.cast(C.create_string_buffer(24), C.c_void_p)   # (never NULL: NULL means self mode)
+        else:
+            import torch
+            if not queries.is_cuda or queries.dtype != torch.float64 or (queries.device.index or 0) != self.device:
+                raise MvicpError("knn_search: a torch `queries` must be a float64 tensor on the engine's GPU")
+            keep = queries.contiguous().reshape(-1, 3)
+            m = keep.shape[0]
+            torch.cuda.synchronize(keep.device)   # (a device array must be fully written when the call is made)
+            qp = C.c_void_p(keep.data_ptr()) if m else C.cast(C.create_string_buffer(24), C.c_void_p)
+        total = int(_check(self.lib, self.lib.mvicp_knn_search(self.h, int(frame), qp, m, int(k), float(radius))))
+        if queries is None:
+            m = self.npts[int(frame)]
+        k = int(k)
+        entries = m * k if k else total
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+            f64, i32, i64 = torch.float64, torch.int32, torch.int64
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if t.numel() else None
+        else:
+            mk = lambda shape, dt: np.zeros(shape, dtype=dt)
+            f64, i32, i64 = np.float64, np.int32, np.int64
+            ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
+        cnt, off, idx, d2 = mk((m,), i32), mk((m + 1,), i64), mk((entries,), i32), mk((entries,), f64)
+        if device:
+            torch.cuda.synchronize(dev)   # (the allocations are the caller's; the library fills them on its own stream and waits)
+        _check(self.lib, self.lib.mvicp_knn_fetch(self.h, m, entries, ptr(cnt), ptr(off), ptr(idx), ptr(d2)))
+        if k:
+            idx, d2 = idx.reshape(m, k), d2.reshape(m, k)
+        return {"cnt": cnt, "off": off, "idx": idx, "d2": d2, "total": total}
 
     def nn_query(self, frame, queries, nn_method=NN_AUTO):
         q = np.ascontiguousarray(queries, dtype=np.float64)
