@@ -247,6 +247,45 @@ long long mvicp_knn_search(mvicp_ctx* ctx, int frame, const double* queries, lon
  * Errors: NULL context, cap_rows < m, cap_entries too small -> MVICP_ERR_ARG; no mvicp_knn_search before -> MVICP_ERR_STATE. */
 int mvicp_knn_fetch(mvicp_ctx* ctx, long long cap_rows, long long cap_entries, int* cnt, long long* off, int* idx, double* d2);
 
+/* ---- FPFH surface descriptors (Rusu 2009), exactly specified ----------------------------------------------------------------
+ * The 33-bin Fast Point Feature Histogram of every point of one stored cloud with normals: the link between "downsample + normals" and
+ * "match + coarse pose" of every registration pipeline.  The result is a pure function of the stored bytes, bit for bit
+ * (tests/fpfhref.py is the same definition in numpy and as a scalar loop).  The textbook formulas use atan2 and acos, which no library
+ * rounds correctly; the contract states the same geometry with + - x / sqrt, comparisons and floor only, in fp64, every operation rounded
+ * on its own, no fma:
+ *   Inputs     the stored cloud p_0 .. p_{n-1} and normals n_0 .. n_{n-1} of `frame` (the stored bytes, no pose; the normals are used as
+ *              given, they are not normalised), radius > 0, 2 <= max_nn <= 64.
+ *   N(i)       row i of mvicp_knn_search(frame, NULL, max_nn, radius) -- self mode, the max_nn nearest within the radius, in the order
+ *              (dist2, original index) -- without its entries with d2 == 0 (the point itself and exact duplicates, whose pair frame is
+ *              undefined); m_i = |N(i)| <= 63.
+ *   Pair       j in N(i): d = p_j - p_i, dist = sqrt(d2) with the row's d2; dot products (x0 y0 + x1 y1) + x2 y2, cross products
+ *              componentwise x1 y2 - x2 y1, ...; a1 = n_i . d, a2 = n_j . d.  |a1| < |a2| (ties do not swap): s = n_j, t = n_i, e = -d,
+ *              f3 = (-a2) / dist; otherwise s = n_i, t = n_j, e = d, f3 = a1 / dist.  v = e x s, vn = sqrt(v . v); vn == 0: the pair's
+ *              three bins are (5, 5, 5); otherwise v = v / vn, w = s x v, f2 = v . t, y = w . t, x = s . t.
+ *   Bins       11 each.  f2, f3: min(10, max(0, floor((f + 1.0) * 5.5))).  theta = the angle of (x, y) in (-pi, pi]: its bin is the number
+ *              of inner edges phi_k = -pi + 2 pi k / 11, k = 1 .. 10, it has passed, decided with the doubles (c_k, s_k) nearest to
+ *              (cos phi_k, sin phi_k) and cr_k = c_k * y - s_k * x: an edge k <= 5 is passed iff y >= 0 or cr_k >= 0, an edge k >= 6 iff
+ *              (y > 0 and cr_k >= 0) or (y == 0 and x < 0).
+ *   SPFH       integer counts c_i[33] over N(i): theta bins 0-10, f2 bins 11-21, f3 bins 22-32; r_i = 100.0 / (double)m_i, 0 if m_i == 0.
+ *   FPFH       acc[b] = +0.0; over N(i) IN ROW ORDER: g = r_j / d2, acc[b] = acc[b] + (double)c_j[b] * g.  Per sub-histogram S = the
+ *              sequential sum of its 11 acc in ascending b, scale = 100.0 / S if S != 0 else 0;
+ *              desc[i][b] = acc[b] * scale + (double)c_i[b] * r_i.  A point with m_i == 0 gets the all-zero row.
+ * desc is n x 33 doubles and used holds m_i, row i the ORIGINAL index i; n = 0 gives zero rows and is not an error.
+ * The call performs mvicp_knn_search(frame, NULL, max_nn, radius) internally and AFTERWARDS THAT SEARCH IS THE CONTEXT'S LAST
+ * NEIGHBOUR-SEARCH RESULT: mvicp_knn_fetch returns the neighbourhoods the descriptors were computed over, at no extra cost, and the
+ * previous search result is gone.  Otherwise the call is HISTORY-NEUTRAL like mvicp_knn_search, needs the frame's hash structure (waits
+ * for pending builds and reports a failed one the same way) and NO graph; with several ranks every rank computes it locally.  It returns
+ * when the result is complete; the result lives in library-owned device memory until the next mvicp_fpfh, mvicp_set_num_frames or
+ * mvicp_destroy.  Profile scopes: those of the search, "fpfh_spfh", "fpfh_sum".
+ * RETURNS THE NUMBER OF ROWS n (>= 0) or a negative mvicp_status.
+ * Errors: NULL context, max_nn outside [2, 64], a radius that is not finite or <= 0, a frame index out of range -> MVICP_ERR_ARG, decided
+ * before the context is touched (earlier results stay); a frame never uploaded, or uploaded without normals -> MVICP_ERR_STATE. */
+long long mvicp_fpfh(mvicp_ctx* ctx, int frame, double radius, int max_nn);
+/* Copies the last result: desc (n x 33 doubles), used (n ints: m_i); each may be NULL; each may be a HOST pointer or a DEVICE pointer of the
+ * context's device, decided per pointer as mvicp_voxel_fetch decides.  cap_rows = rows the destinations hold.
+ * Errors: NULL context, cap_rows < n -> MVICP_ERR_ARG; no mvicp_fpfh before -> MVICP_ERR_STATE. */
+int mvicp_fpfh_fetch(mvicp_ctx* ctx, long long cap_rows, double* desc, int* used);
+
 /* The rounding allowance of the temporal cache (pure host function, no context): what mvicp_correspond adds to the displacement |dM p + dv|
  * of an edge's queries between the search at (pose_src_old, pose_dst_old) and the one at (pose_src, pose_dst), poses as 16 column-major
  * doubles, max_norm >= max |p| over the source cloud.  With x = (Rs, ts, Rd^-1, td) the query transform of a pose pair (Rd^-1 as

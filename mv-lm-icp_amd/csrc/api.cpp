@@ -555,6 +555,7 @@ int mvicp_destroy(mvicp_ctx* c) try {
   free_voxel(c);
   free_outlier(c);
   free_knn(c);
+  free_fpfh(c);
   for (auto& kv : c->tables) if (kv.second.d) (void)hipFree(kv.second.d);
   if (c->d_census) (void)hipFree(c->d_census);
   if (c->h_census) (void)hipHostFree(c->h_census);
@@ -581,6 +582,7 @@ int mvicp_set_num_frames(mvicp_ctx* c, int n_frames) try {
   free_voxel(c);   // (the last voxel-grid result ends here; every voxel call waits for its own work)
   free_outlier(c); // (and the last outlier-filter result)
   free_knn(c);     // (and the last neighbour-search result)
+  free_fpfh(c);    // (and the last descriptors)
   for (FrameDev& f : c->frames) { dev_free(f.pts); dev_free(f.nor); free_grid(f.grid); free_tie(f); }
   c->frames.assign(n_frames, FrameDev());
   c->n_frames = n_frames;
@@ -984,6 +986,42 @@ int mvicp_knn_fetch(mvicp_ctx* c, long long cap_rows, long long cap_entries, int
     if (dst[t] && bytes[t]) { kind[t] = destination_kind(c, dst[t], names[t]); if (kind[t] < 0) return kind[t]; }
   for (int t = 0; t < 4; ++t)
     if (dst[t] && bytes[t]) MV_HIP(hipMemcpyAsync(dst[t], src[t], bytes[t], kind[t] ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+  MV_HIP(hipStreamSynchronize(c->stream));
+  return MVICP_OK;
+} MVICP_GUARD_ABI
+
+long long mvicp_fpfh(mvicp_ctx* c, int frame, double radius, int max_nn) try {
+  // every argument error that needs no GPU first: nothing of the context has been touched when one of them is reported
+  if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
+  if (max_nn < 2 || max_nn > 64) { set_error("max_nn = %d outside [2, 64]", max_nn); return MVICP_ERR_ARG; }
+  if (!std::isfinite(radius) || !(radius > 0.0)) { set_error("radius must be finite and > 0"); return MVICP_ERR_ARG; }
+  if (frame < 0 || frame >= c->n_frames) { set_error("frame %d out of range [0,%d)", frame, c->n_frames); return MVICP_ERR_ARG; }
+  const FrameDev& f = c->frames[frame];
+  if (!f.pts) { set_error("frame %d was never uploaded", frame); return MVICP_ERR_STATE; }
+  if (f.n > 0 && !f.nor) { set_error("frame %d has no normals: the descriptors need them", frame); return MVICP_ERR_STATE; }
+  MV_CHECK(bind(c));
+  MV_CHECK(finish_builds(c));
+  const long long rows = fpfh_compute(c, f, max_nn, radius, sqrt_bound(radius));
+  if (c->profile) prof_collect_lazy(c);
+  return rows;
+} MVICP_GUARD_ABI
+
+int mvicp_fpfh_fetch(mvicp_ctx* c, long long cap_rows, double* desc, int* used) try {
+  if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
+  if (c->fpfh_rows < 0) { set_error("no descriptors: call mvicp_fpfh first"); return MVICP_ERR_STATE; }
+  if (cap_rows < c->fpfh_rows) { set_error("cap_rows %lld < %lld rows", cap_rows, c->fpfh_rows); return MVICP_ERR_ARG; }
+  if (c->fpfh_rows == 0) return MVICP_OK;
+  MV_CHECK(bind(c));
+  const size_t n = (size_t)c->fpfh_rows;
+  const void* src[2] = {c->fpfh_desc, c->fpfh_used};
+  void* dst[2] = {desc, used};
+  const size_t bytes[2] = {33 * 8 * n, 4 * n};
+  const char* names[2] = {"desc", "used"};
+  int kind[2] = {0, 0};
+  for (int t = 0; t < 2; ++t)
+    if (dst[t]) { kind[t] = destination_kind(c, dst[t], names[t]); if (kind[t] < 0) return kind[t]; }
+  for (int t = 0; t < 2; ++t)
+    if (dst[t]) MV_HIP(hipMemcpyAsync(dst[t], src[t], bytes[t], kind[t] ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
   MV_HIP(hipStreamSynchronize(c->stream));
   return MVICP_OK;
 } MVICP_GUARD_ABI

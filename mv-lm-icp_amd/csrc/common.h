@@ -271,6 +271,13 @@ struct mvicp_ctx {
   long long knn_m = -1, knn_total = 0; int knn_k = 0;   // rows, entries over all rows, the k of the call (0: all mode, CSR)
   int knn_order = 1;               // option "knn_order": queries are answered in the order of their home cells (0: as given); the result is the same bytes
 
+  // FPFH descriptors (fpfh.hip): the last result, library-owned until the next mvicp_fpfh / mvicp_set_num_frames / mvicp_destroy
+  // (fpfh_rows < 0: none).  One device arena, grown on demand: [desc n x 33 doubles | used n ints | SPFH records n x 48 B]; the
+  // neighbourhoods are the knn_* result of the search the call runs, so there is no second set of search buffers
+  char* fpfh_dev = nullptr; size_t fpfh_dev_bytes = 0;
+  double* fpfh_desc = nullptr; int* fpfh_used = nullptr;
+  long long fpfh_rows = -1;
+
   // cached small tables
   struct CachedTable { std::vector<char> bytes; void* d = nullptr; size_t cap = 0; };
   std::map<std::string, CachedTable> tables;
@@ -388,6 +395,11 @@ void free_outlier(mvicp_ctx* c);   // the result and the buffers
 // The result stays on the context (knn_*).  Returns the number of entries or a negative status.  Waits for the stream; history-neutral.
 long long knn_search(mvicp_ctx* c, const FrameDev& f, const double* queries, int queries_on_device, long long m, int k, double radius, double B2);
 void free_knn(mvicp_ctx* c);       // the result and the buffers
+// fpfh.hip: knn_search(c, f, null, 0, 0, max_nn, radius, B2) and the two descriptor passes over its rows, for frame f (valid, uploaded,
+// with normals unless empty, structures built; 2 <= max_nn <= 64, radius > 0, B2 = sqrt_bound(radius)); the result stays on the context
+// (fpfh_*), the search's as knn_*.  Returns the number of rows or a negative status.  Waits for the stream; history-neutral.
+long long fpfh_compute(mvicp_ctx* c, const FrameDev& f, int max_nn, double radius, double B2);
+void free_fpfh(mvicp_ctx* c);      // the result and the buffer
 int launch_compact(mvicp_ctx* c, double d2_bound);                                    // corr.hip
 int launch_gather_stream(mvicp_ctx* c);
 int launch_select_median(mvicp_ctx* c, double d2_bound);   // two-pass select anchored at the acceptance bound: any key set, exact

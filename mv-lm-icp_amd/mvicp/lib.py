@@ -19,7 +19,7 @@ SYMBOLS = [
     "mvicp_closedform_point_to_point", "mvicp_closedform_point_to_plane", "mvicp_set_frame_device", "mvicp_get_structure",
     "mvicp_overlap", "mvicp_graph_from_overlap", "mvicp_voxel_grid", "mvicp_voxel_fetch",
     "mvicp_outlier_filter", "mvicp_outlier_fetch", "mvicp_outlier_threshold", "mvicp_cache_allowance",
-    "mvicp_knn_search", "mvicp_knn_fetch",
+    "mvicp_knn_search", "mvicp_knn_fetch", "mvicp_fpfh", "mvicp_fpfh_fetch",
 ]
 
 # names of mvicp_get_structure (include/mvicp.h)
@@ -121,6 +121,9 @@ def load_library(path=None):
     lib.mvicp_knn_search.argtypes = [vp, C.c_int, vp, C.c_longlong, C.c_int, C.c_double]
     lib.mvicp_knn_search.restype = C.c_longlong
     lib.mvicp_knn_fetch.argtypes = [vp, C.c_longlong, C.c_longlong, vp, vp, vp, vp]
+    lib.mvicp_fpfh.argtypes = [vp, C.c_int, C.c_double, C.c_int]
+    lib.mvicp_fpfh.restype = C.c_longlong
+    lib.mvicp_fpfh_fetch.argtypes = [vp, C.c_longlong, vp, vp]
     if path is None:
         _lib = lib
     return lib
@@ -602,6 +605,24 @@ class Engine:
         if k:
             idx, d2 = idx.reshape(m, k), d2.reshape(m, k)
         return {"cnt": cnt, "off": off, "idx": idx, "d2": d2, "total": total}
+
+    def fpfh(self, frame, radius, max_nn=64, device=False):
+        """mvicp_fpfh + mvicp_fpfh_fetch on the stored cloud and normals of `frame`: the 33-bin FPFH descriptor of every point over its
+        max_nn nearest neighbours within `radius` -> dict(desc (n,33) float64, used (n,) int32 = neighbours that entered).  device=True:
+        torch tensors on the engine's GPU instead of numpy arrays.  Afterwards the engine's last neighbour-search result is
+        knn_search(frame, None, max_nn, radius).  Needs no graph; history-neutral."""
+        n = int(_check(self.lib, self.lib.mvicp_fpfh(self.h, int(frame), float(radius), int(max_nn))))
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            desc, used = torch.empty((n, 33), dtype=torch.float64, device=dev), torch.empty((n,), dtype=torch.int32, device=dev)
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if t.numel() else None
+            torch.cuda.synchronize(dev)   # (the allocations are the caller's; the library fills them on its own stream and waits)
+        else:
+            desc, used = np.zeros((n, 33), dtype=np.float64), np.zeros((n,), dtype=np.int32)
+            ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
+        _check(self.lib, self.lib.mvicp_fpfh_fetch(self.h, n, ptr(desc), ptr(used)))
+        return {"desc": desc, "used": used}
 
     def nn_query(self, frame, queries, nn_method=NN_AUTO):
         q = np.ascontiguousarray(queries, dtype=np.float64)
