@@ -286,6 +286,71 @@ long long mvicp_fpfh(mvicp_ctx* ctx, int frame, double radius, int max_nn);
  * Errors: NULL context, cap_rows < n -> MVICP_ERR_ARG; no mvicp_fpfh before -> MVICP_ERR_STATE. */
 int mvicp_fpfh_fetch(mvicp_ctx* ctx, long long cap_rows, double* desc, int* used);
 
+/* ---- Descriptor matching and a consensus coarse pose, exactly specified -------------------------------------------------------
+ * The stage that turns two sets of descriptors into a coarse pose: two device stages, one host rule between them.  Each result is a
+ * pure function of the input bytes, bit for bit (tests/matchref.py is the same definition in numpy and as a scalar loop).  All
+ * floating-point work is fp64, every operation rounded on its own, no fma; only + - x / sqrt and comparisons occur; comparisons are
+ * IEEE as written, so NaN compares false.  Both device calls are HISTORY-NEUTRAL in the sense of
+ * mvicp_knn_search, need NO graph and NO frame; with several ranks every rank computes locally.  Results live in library-owned device
+ * memory until the next call of the same kind, mvicp_set_num_frames or mvicp_destroy.  Input and destination pointers may be HOST or
+ * DEVICE pointers of the context's device, decided per pointer as mvicp_voxel_fetch decides (a device array must be fully written when
+ * the call is made).  Argument errors are decided before the context is touched and leave earlier results alone.
+ *
+ * mvicp_feature_match: a has m rows, b has n rows, both row-major doubles with `dim` columns, 1 <= dim <= 64 (FPFH: 33), every value
+ * finite, 0 <= m, n < 2^31.
+ *   dist(a, b) s = +0.0; for c = 0 .. dim-1 in ascending order: t = a[c] - b[c]; s = s + t * t.  (a - b) and (b - a) are exact negatives,
+ *              so dist is symmetric bit for bit.
+ *   Forward    for each row i of a, the rows of b ordered by (dist, j): fwd_idx[i][0..1] and fwd_d2[i][0..1] are the first two entries;
+ *              a missing entry is padded with idx -1 and d2 +inf.
+ *   Backward   the same for each row j of b over the rows of a: bwd_idx (n x 2), bwd_d2 (n x 2).
+ * Option "match_chunk" (default 2048) sets the rows of the other operand per chunk of the brute-force kernel; it changes the speed only,
+ * the result is the same bytes.  Profile scopes: "match_fwd", "match_bwd", "match_merge".
+ * RETURNS m (>= 0; m = 0 or n = 0 is not an error) or a negative mvicp_status.
+ * Errors: NULL context, dim outside [1, 64], m or n outside [0, 2^31), a NULL operand with rows -> MVICP_ERR_ARG; a non-finite descriptor
+ * value -> MVICP_ERR_ARG, reported by this call, and no result is left behind. */
+long long mvicp_feature_match(mvicp_ctx* ctx, const double* a, long long m, const double* b, long long n, int dim);
+/* Copies the last result: fwd_idx (m x 2 ints), fwd_d2 (m x 2 doubles), bwd_idx (n x 2 ints), bwd_d2 (n x 2 doubles); each may be NULL.
+ * cap_m / cap_n = rows the forward / backward destinations hold.
+ * Errors: NULL context, cap_m < m, cap_n < n -> MVICP_ERR_ARG; no mvicp_feature_match before -> MVICP_ERR_STATE. */
+int mvicp_feature_match_fetch(mvicp_ctx* ctx, long long cap_m, long long cap_n, int* fwd_idx, double* fwd_d2, int* bwd_idx, double* bwd_d2);
+
+/* The pair rule on top of the fetched arrays (pure host function, no context; host pointers).  Pair (i, j = fwd_idx[i][0]) is kept iff
+ *   j >= 0;  mutual == 0 or bwd_idx[j][0] == i;  ratio >= 1 (ratio test off) or fwd_d2[i][0] <= (ratio * ratio) * fwd_d2[i][1].
+ * Pairs are written to `pairs` (room for m x 2 ints) as (i, j) in ascending i.  RETURNS THE NUMBER OF PAIRS (>= 0).
+ * Errors: a NULL pointer, m or n < 0, a ratio that is NaN or <= 0, an index j >= n -> MVICP_ERR_ARG. */
+long long mvicp_match_pairs(long long m, long long n, const int* fwd_idx, const double* fwd_d2, const int* bwd_idx, int mutual, double ratio,
+                            int* pairs);
+
+/* mvicp_consensus: p, q are n_pairs x 3 doubles, index-aligned pairs from source to destination, all finite, 3 <= n_pairs < 2^31;
+ * 1 <= hypotheses <= 2^24; tau > 0; edge_sim s in [0, 1) (s = 0 makes the edge check vacuous).  With c = n_pairs:
+ *   Forms      dot (x0 y0 + x1 y1) + x2 y2; cross componentwise x1 y2 - x2 y1, ...; a row times a vector (r0 v0 + r1 v1) + r2 v2.
+ *   Sample     hypothesis h, slot t in {0, 1, 2}: z = seed + (3 h + t + 1) * 0x9E3779B97F4A7C15 (mod 2^64);
+ *              z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB; u = z ^ (z >> 31);
+ *              index = ((u >> 32) * c) >> 32.  Rejected if two of the three indices are equal.
+ *   Edges      s2 = s * s; for each of the edges (0,1), (1,2), (2,0): lp = dot(p_a - p_b, p_a - p_b), lq likewise; both
+ *              lp >= s2 * lq and lq >= s2 * lp are needed, rejected otherwise.
+ *   Frame      u1 = p1 - p0, n1 = sqrt(dot(u1, u1)), rejected if n1 == 0, e1 = u1 / n1; w = cross(e1, p2 - p0), nw = sqrt(dot(w, w)),
+ *              rejected if nw == 0, e3 = w / nw; e2 = cross(e3, e1); f1, f2, f3 from the q triangle in the same way.
+ *   Pose       R[r][k] = (f1[r] e1[k] + f2[r] e2[k]) + f3[r] e3[k]; cp = ((p0 + p1) + p2) / 3.0 and cq likewise; t = cq - R cp.
+ *   Score      tau2 = tau * tau; pair i is an inlier iff dot(r, r) <= tau2 with r = (R p_i + t) - q_i; count[h] = the number of inliers,
+ *              or -1 for a rejected hypothesis.
+ *   Winner     the largest count, the lowest h among equals.
+ * *result: best = the winner's index (-1 when nothing was accepted), count = its count, accepted = the number of accepted hypotheses,
+ * pose = 16 column-major doubles.  When every hypothesis is rejected best = -1, count = 0, the pose is the identity and no flag is set;
+ * that is not an error.  Profile scopes: "cons_hyp", "cons_score", "cons_pick".
+ * RETURNS MVICP_OK or a negative mvicp_status.
+ * Errors: NULL context or pointer, n_pairs < 3 or >= 2^31, hypotheses outside [1, 2^24], a tau that is not finite or <= 0, an edge_sim
+ * outside [0, 1) -> MVICP_ERR_ARG; a non-finite coordinate -> MVICP_ERR_ARG, reported by this call, and no result is left behind. */
+typedef struct mvicp_consensus_result {
+  int best, count, accepted, reserved;
+  double pose[16];
+} mvicp_consensus_result;
+int mvicp_consensus(mvicp_ctx* ctx, const double* p, const double* q, long long n_pairs, long long hypotheses, unsigned long long seed,
+                    double tau, double edge_sim, mvicp_consensus_result* result);
+/* Copies the last result: count (hypotheses ints), flags (n_pairs bytes: 1 = an inlier of the winner); each may be NULL.
+ * Errors: NULL context, cap_h < hypotheses, cap_c < n_pairs -> MVICP_ERR_ARG; no mvicp_consensus before -> MVICP_ERR_STATE. */
+int mvicp_consensus_fetch(mvicp_ctx* ctx, long long cap_h, int* count, long long cap_c, unsigned char* flags);
+
 /* The rounding allowance of the temporal cache (pure host function, no context): what mvicp_correspond adds to the displacement |dM p + dv|
  * of an edge's queries between the search at (pose_src_old, pose_dst_old) and the one at (pose_src, pose_dst), poses as 16 column-major
  * doubles, max_norm >= max |p| over the source cloud.  With x = (Rs, ts, Rd^-1, td) the query transform of a pose pair (Rd^-1 as

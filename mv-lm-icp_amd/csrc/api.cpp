@@ -556,6 +556,8 @@ int mvicp_destroy(mvicp_ctx* c) try {
   free_outlier(c);
   free_knn(c);
   free_fpfh(c);
+  free_match(c);
+  free_consensus(c);
   for (auto& kv : c->tables) if (kv.second.d) (void)hipFree(kv.second.d);
   if (c->d_census) (void)hipFree(c->d_census);
   if (c->h_census) (void)hipHostFree(c->h_census);
@@ -583,6 +585,8 @@ int mvicp_set_num_frames(mvicp_ctx* c, int n_frames) try {
   free_outlier(c); // (and the last outlier-filter result)
   free_knn(c);     // (and the last neighbour-search result)
   free_fpfh(c);    // (and the last descriptors)
+  free_match(c);   // (and the last matches)
+  free_consensus(c); // (and the last consensus)
   for (FrameDev& f : c->frames) { dev_free(f.pts); dev_free(f.nor); free_grid(f.grid); free_tie(f); }
   c->frames.assign(n_frames, FrameDev());
   c->n_frames = n_frames;
@@ -1017,6 +1021,96 @@ int mvicp_fpfh_fetch(mvicp_ctx* c, long long cap_rows, double* desc, int* used) 
   void* dst[2] = {desc, used};
   const size_t bytes[2] = {33 * 8 * n, 4 * n};
   const char* names[2] = {"desc", "used"};
+  int kind[2] = {0, 0};
+  for (int t = 0; t < 2; ++t)
+    if (dst[t]) { kind[t] = destination_kind(c, dst[t], names[t]); if (kind[t] < 0) return kind[t]; }
+  for (int t = 0; t < 2; ++t)
+    if (dst[t]) MV_HIP(hipMemcpyAsync(dst[t], src[t], bytes[t], kind[t] ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+  MV_HIP(hipStreamSynchronize(c->stream));
+  return MVICP_OK;
+} MVICP_GUARD_ABI
+
+long long mvicp_feature_match(mvicp_ctx* c, const double* a, long long m, const double* b, long long n, int dim) try {
+  // every argument error that needs no GPU first: nothing of the context has been touched when one of them is reported
+  if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
+  if (dim < 1 || dim > 64) { set_error("dim = %d outside [1, 64]", dim); return MVICP_ERR_ARG; }
+  if (m < 0 || m >= (1ll << 31) || n < 0 || n >= (1ll << 31)) { set_error("m = %lld, n = %lld outside [0, 2^31)", m, n); return MVICP_ERR_ARG; }
+  if ((m > 0 && !a) || (n > 0 && !b)) { set_error("null descriptors"); return MVICP_ERR_ARG; }
+  MV_CHECK(bind(c));
+  int a_dev = 0, b_dev = 0;
+  if (m > 0) { a_dev = destination_kind(c, a, "a"); if (a_dev < 0) return a_dev; }
+  if (n > 0) { b_dev = destination_kind(c, b, "b"); if (b_dev < 0) return b_dev; }
+  const long long rows = feature_match(c, a, a_dev, m, b, b_dev, n, dim);
+  if (c->profile) prof_collect_lazy(c);
+  return rows;
+} MVICP_GUARD_ABI
+
+int mvicp_feature_match_fetch(mvicp_ctx* c, long long cap_m, long long cap_n, int* fwd_idx, double* fwd_d2, int* bwd_idx, double* bwd_d2) try {
+  if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
+  if (c->match_m < 0) { set_error("no matches: call mvicp_feature_match first"); return MVICP_ERR_STATE; }
+  if ((fwd_idx || fwd_d2) && cap_m < c->match_m) { set_error("cap_m %lld < %lld rows", cap_m, c->match_m); return MVICP_ERR_ARG; }
+  if ((bwd_idx || bwd_d2) && cap_n < c->match_n) { set_error("cap_n %lld < %lld rows", cap_n, c->match_n); return MVICP_ERR_ARG; }
+  MV_CHECK(bind(c));
+  const size_t m = (size_t)c->match_m, n = (size_t)c->match_n;
+  const void* src[4] = {c->match_fwd_idx, c->match_fwd_d2, c->match_bwd_idx, c->match_bwd_d2};
+  void* dst[4] = {fwd_idx, fwd_d2, bwd_idx, bwd_d2};
+  const size_t bytes[4] = {8 * m, 16 * m, 8 * n, 16 * n};
+  const char* names[4] = {"fwd_idx", "fwd_d2", "bwd_idx", "bwd_d2"};
+  int kind[4] = {0, 0, 0, 0};
+  for (int t = 0; t < 4; ++t)
+    if (dst[t] && bytes[t]) { kind[t] = destination_kind(c, dst[t], names[t]); if (kind[t] < 0) return kind[t]; }
+  for (int t = 0; t < 4; ++t)
+    if (dst[t] && bytes[t]) MV_HIP(hipMemcpyAsync(dst[t], src[t], bytes[t], kind[t] ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+  MV_HIP(hipStreamSynchronize(c->stream));
+  return MVICP_OK;
+} MVICP_GUARD_ABI
+
+long long mvicp_match_pairs(long long m, long long n, const int* fwd_idx, const double* fwd_d2, const int* bwd_idx, int mutual, double ratio,
+                            int* pairs) try {
+  if (m < 0 || n < 0 || !fwd_idx || !fwd_d2 || !bwd_idx || !pairs) { set_error("match pairs: needs m, n >= 0 and four arrays"); return MVICP_ERR_ARG; }
+  if (!(ratio > 0.0)) { set_error("match pairs: ratio must be > 0"); return MVICP_ERR_ARG; }
+  // (this TU is built without fma contraction: the product of the ratio test is rounded on its own)
+  const double r2 = ratio * ratio;
+  long long k = 0;
+  for (long long i = 0; i < m; ++i) {
+    const long long j = fwd_idx[2 * i];
+    if (j < 0) continue;
+    if (j >= n) { set_error("match pairs: fwd_idx[%lld][0] = %lld with n = %lld", i, j, n); return MVICP_ERR_ARG; }
+    if (mutual && (long long)bwd_idx[2 * j] != i) continue;
+    if (!(ratio >= 1.0) && !(fwd_d2[2 * i] <= r2 * fwd_d2[2 * i + 1])) continue;
+    pairs[2 * k] = (int)i; pairs[2 * k + 1] = (int)j;
+    ++k;
+  }
+  return k;
+} MVICP_GUARD_ABI
+
+int mvicp_consensus(mvicp_ctx* c, const double* p, const double* q, long long n_pairs, long long hypotheses, unsigned long long seed, double tau,
+                    double edge_sim, mvicp_consensus_result* result) try {
+  // every argument error that needs no GPU first: nothing of the context has been touched when one of them is reported
+  if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
+  if (n_pairs < 3 || n_pairs >= (1ll << 31)) { set_error("%lld pairs outside [3, 2^31)", n_pairs); return MVICP_ERR_ARG; }
+  if (hypotheses < 1 || hypotheses > (1ll << 24)) { set_error("%lld hypotheses outside [1, 2^24]", hypotheses); return MVICP_ERR_ARG; }
+  if (!std::isfinite(tau) || !(tau > 0.0)) { set_error("tau must be finite and > 0"); return MVICP_ERR_ARG; }
+  if (!(edge_sim >= 0.0 && edge_sim < 1.0)) { set_error("edge_sim must be in [0, 1)"); return MVICP_ERR_ARG; }
+  if (!p || !q) { set_error("null pairs"); return MVICP_ERR_ARG; }
+  MV_CHECK(bind(c));
+  const int p_dev = destination_kind(c, p, "p"); if (p_dev < 0) return p_dev;
+  const int q_dev = destination_kind(c, q, "q"); if (q_dev < 0) return q_dev;
+  const int st = consensus(c, p, p_dev, q, q_dev, n_pairs, hypotheses, seed, tau, edge_sim, result);
+  if (c->profile) prof_collect_lazy(c);
+  return st;
+} MVICP_GUARD_ABI
+
+int mvicp_consensus_fetch(mvicp_ctx* c, long long cap_h, int* count, long long cap_c, unsigned char* flags) try {
+  if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
+  if (c->cons_H < 0) { set_error("no consensus: call mvicp_consensus first"); return MVICP_ERR_STATE; }
+  if (count && cap_h < c->cons_H) { set_error("cap_h %lld < %lld hypotheses", cap_h, c->cons_H); return MVICP_ERR_ARG; }
+  if (flags && cap_c < c->cons_c) { set_error("cap_c %lld < %lld pairs", cap_c, c->cons_c); return MVICP_ERR_ARG; }
+  MV_CHECK(bind(c));
+  const void* src[2] = {c->cons_count, c->cons_flags};
+  void* dst[2] = {count, flags};
+  const size_t bytes[2] = {4 * (size_t)c->cons_H, (size_t)c->cons_c};
+  const char* names[2] = {"count", "flags"};
   int kind[2] = {0, 0};
   for (int t = 0; t < 2; ++t)
     if (dst[t]) { kind[t] = destination_kind(c, dst[t], names[t]); if (kind[t] < 0) return kind[t]; }
@@ -1959,6 +2053,10 @@ int mvicp_set_option(mvicp_ctx* c, const char* name, double value) try {
   if (std::strcmp(name, "tile_cache") == 0) { c->tile_cache = (int)value; return MVICP_OK; }
   if (std::strcmp(name, "voxel_permute") == 0) { c->voxel_permute = value != 0.0; return MVICP_OK; }
   if (std::strcmp(name, "knn_order") == 0) { c->knn_order = value != 0.0; return MVICP_OK; }
+  if (std::strcmp(name, "match_chunk") == 0) {
+    if (!(value >= 1.0 && value < 2147483648.0)) { set_error("match_chunk must be in [1, 2^31)"); return MVICP_ERR_ARG; }
+    c->match_chunk = (int)value; return MVICP_OK;
+  }
   if (std::strcmp(name, "spin_wait") == 0) { c->spin_wait = value != 0.0; return MVICP_OK; }
   if (std::strcmp(name, "fault_inject") == 0) { c->fault_inject = (int)value; return MVICP_OK; }            // tests: the value-th mvicp_correspond from now fails locally before its exchange
   if (std::strcmp(name, "fault_inject_build") == 0) { c->fault_inject_build.store((int)value); return MVICP_OK; }      // tests: the value-th structure build from now fails

@@ -278,6 +278,20 @@ struct mvicp_ctx {
   double* fpfh_desc = nullptr; int* fpfh_used = nullptr;
   long long fpfh_rows = -1;
 
+  // descriptor matching (match.hip): the last result, library-owned until the next mvicp_feature_match / mvicp_set_num_frames /
+  // mvicp_destroy (match_m < 0: none).  match_dev holds [fwd_idx | fwd_d2 | bwd_idx | bwd_d2 | flag], match_tmp the scratch (staged host
+  // operands, the per-chunk partial lists); both kept between calls and grown on demand
+  char* match_dev = nullptr; char* match_tmp = nullptr; size_t match_dev_bytes = 0, match_tmp_bytes = 0;
+  int* match_fwd_idx = nullptr; int* match_bwd_idx = nullptr; double* match_fwd_d2 = nullptr; double* match_bwd_d2 = nullptr;
+  long long match_m = -1, match_n = -1;
+  int match_chunk = 2048;          // option "match_chunk": rows of the right operand per blockIdx.y chunk; the result is the same bytes
+
+  // consensus (consensus.hip): the last result, library-owned until the next mvicp_consensus / mvicp_set_num_frames / mvicp_destroy
+  // (cons_H < 0: none).  One device arena, grown on demand: [control | count H ints | accepted h | flags c bytes | staged host pairs]
+  char* cons_dev = nullptr; size_t cons_dev_bytes = 0;
+  int* cons_count = nullptr; unsigned char* cons_flags = nullptr;
+  long long cons_H = -1, cons_c = -1;
+
   // cached small tables
   struct CachedTable { std::vector<char> bytes; void* d = nullptr; size_t cap = 0; };
   std::map<std::string, CachedTable> tables;
@@ -400,6 +414,17 @@ void free_knn(mvicp_ctx* c);       // the result and the buffers
 // (fpfh_*), the search's as knn_*.  Returns the number of rows or a negative status.  Waits for the stream; history-neutral.
 long long fpfh_compute(mvicp_ctx* c, const FrameDev& f, int max_nn, double radius, double B2);
 void free_fpfh(mvicp_ctx* c);      // the result and the buffer
+// match.hip: the two nearest rows of B (n x dim) for every row of A (m x dim) and the reverse; 0 <= m, n < 2^31, 1 <= dim <= 64; each
+// operand in host or device memory as its `_on_device` says.  The result stays on the context (match_*).  Returns m or a negative
+// status (a non-finite value: MVICP_ERR_ARG, no result).  Waits for the stream; history-neutral.
+long long feature_match(mvicp_ctx* c, const double* A, int a_on_device, long long m, const double* B, int b_on_device, long long n, int dim);
+void free_match(mvicp_ctx* c);     // the result and the buffers
+// consensus.hip: H hypotheses over the n_pairs index-aligned pairs (P, Q) (host or device memory); 3 <= n_pairs < 2^31, 1 <= H <= 2^24,
+// tau > 0, 0 <= edge_sim < 1.  count / flags stay on the context (cons_*), the record goes to `out`.  Returns a status (a non-finite
+// coordinate: MVICP_ERR_ARG, no result).  Waits for the stream; history-neutral.
+int consensus(mvicp_ctx* c, const double* P, int p_on_device, const double* Q, int q_on_device, long long n_pairs, long long H, unsigned long long seed,
+              double tau, double edge_sim, mvicp_consensus_result* out);
+void free_consensus(mvicp_ctx* c); // the result and the buffer
 int launch_compact(mvicp_ctx* c, double d2_bound);                                    // corr.hip
 int launch_gather_stream(mvicp_ctx* c);
 int launch_select_median(mvicp_ctx* c, double d2_bound);   // two-pass select anchored at the acceptance bound: any key set, exact

@@ -1,0 +1,233 @@
+// Descriptor matching (mvicp_feature_match): for every row of A the two nearest rows of B, and for every row of B the two nearest rows
+// of A, under the squared Euclidean distance in `dim` dimensions, as a pure function of the input bytes, bit for bit.  The contract is
+// stated in include/mvicp.h; tests/matchref.py is its numpy form and its scalar-loop form.  DESIGN.md §3.11.
+//
+//   dist(a, b)   s = +0.0; for c = 0 .. dim-1 ascending: t = a[c] - b[c]; s = s + t * t      (fp64, every operation rounded on its own)
+//
+// Brute force, no search structure: one direction is one launch of the same kernel, the other the same launch with the operands swapped
+// ((a - b) and (b - a) are exact negatives, so the distance is the same bits in both).
+//   1  match_kernel<33>      a lane owns one row of the left operand in registers; a tile of 64 rows of the right operand is staged in LDS
+//                            and every lane reads the same address (a broadcast: no bank conflicts); each lane keeps its best two (d2, j).
+//                            The right operand is split over blockIdx.y into chunks, so that few left rows still fill the device.  The
+//                            partial sums of non-negative terms only grow under rounded addition, so a candidate whose running sum
+//                            already exceeds the lane's second best cannot enter: checked after each 11-bin sub-histogram, skipped
+//                            only when the whole wave agrees.
+//      match_generic_kernel  any 1 <= dim <= 64: 64 left rows per workgroup, transposed in LDS (lane-contiguous: no bank conflicts)
+//   2  match_merge_kernel    per left row the best two over its chunks in (d2, j) order.  Tiling cannot change a pair's dist, and the
+//                            chunks are visited in ascending j, so the merge is exact.
+#include "common.h"
+
+namespace mvicp {
+
+namespace {
+
+constexpr int kThreads = 256;   // left rows per workgroup of match_kernel
+constexpr int kTile = 64;       // right rows per LDS tile
+constexpr int kGenRows = 64;    // left rows per workgroup of match_generic_kernel
+constexpr int kGenTile = 32;    // its right rows per LDS tile
+constexpr int kMaxDim = 64;
+constexpr int kMaxChunks = 65535;
+
+struct Best2 { double d0, d1; int j0, j1; };   // the first two of a row in (d2, j) order; j < 0: the slot is empty (d = +inf)
+static_assert(sizeof(Best2) == 24, "Best2 is 24 bytes");
+
+// candidates arrive in ascending j (or chunk by chunk in ascending j, each chunk's own two in order): a strict comparison keeps the lower j
+__device__ __forceinline__ void offer(double d, int j, double& d0, int& j0, double& d1, int& j1) {
+  const bool first = j0 < 0 || d < d0, second = !first && (j1 < 0 || d < d1);   // (selects: the four values stay in registers)
+  d1 = first ? d0 : second ? d : d1; j1 = first ? j0 : second ? j : j1;
+  d0 = first ? d : d0; j0 = first ? j : j0;
+}
+
+template <int DIM>
+__global__ __launch_bounds__(kThreads) void match_kernel(const double* __restrict__ A, int m, const double* __restrict__ B, int n, int chunk,
+                                                         Best2* __restrict__ part) {
+  constexpr int LD = DIM + (DIM & 1);   // (an even row length keeps every row 16-byte aligned)
+  constexpr int SEG = 11;               // the early-exit check follows each sub-histogram
+  static_assert(DIM % SEG == 0, "the row is a whole number of segments");
+  __shared__ double Bs[kTile * LD];
+  const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
+  const bool live = i < m;
+  double a[DIM];
+#pragma unroll
+  for (int c = 0; c < DIM; ++c) a[c] = live ? A[(size_t)i * DIM + c] : 0.0;
+  const long long lo = (long long)blockIdx.y * chunk;
+  const long long hi = lo + chunk < (long long)n ? lo + chunk : (long long)n;
+  double d0 = INFINITY, d1 = INFINITY; int j0 = -1, j1 = -1;
+  for (long long base = lo; base < hi; base += kTile) {
+    const int rows = (int)(hi - base < kTile ? hi - base : kTile);
+    __syncthreads();   // (the last tile has been read by every wave)
+    for (int e = threadIdx.x; e < rows * DIM; e += kThreads) {
+      const int r = e / DIM, c = e - r * DIM;
+      Bs[r * LD + c] = B[(size_t)base * DIM + e];
+    }
+    __syncthreads();
+    for (int r = 0; r < rows; ++r) {
+      const double* b = Bs + r * LD;
+      double s = 0.0;
+      bool skip = false;
+#pragma unroll
+      for (int g = 0; g < DIM / SEG; ++g) {
+#pragma unroll
+        for (int c = g * SEG; c < (g + 1) * SEG; ++c) {
+          const double t = __dsub_rn(a[c], b[c]);
+          s = __dadd_rn(s, __dmul_rn(t, t));
+        }
+        // s only grows from here: above the second best (never above an empty slot's +inf) it cannot enter
+        if (g + 1 < DIM / SEG && __all(!live || s > d1)) { skip = true; break; }
+      }
+      if (!skip) offer(s, (int)(base + r), d0, j0, d1, j1);
+    }
+  }
+  if (live) { Best2* o = part + ((size_t)blockIdx.y * m + i); o->d0 = d0; o->d1 = d1; o->j0 = j0; o->j1 = j1; }
+}
+
+__global__ __launch_bounds__(kGenRows) void match_generic_kernel(const double* __restrict__ A, int m, const double* __restrict__ B, int n, int dim,
+                                                                 int chunk, Best2* __restrict__ part) {
+  __shared__ double As[kMaxDim * kGenRows];   // [c][row]
+  __shared__ double Bs[kGenTile * kMaxDim];   // [row][c]
+  const long long i0 = (long long)blockIdx.x * kGenRows;
+  const long long i = i0 + threadIdx.x;
+  const bool live = i < m;
+  const int rows_a = (int)((long long)m - i0 < kGenRows ? (long long)m - i0 : kGenRows);
+  for (int e = threadIdx.x; e < kGenRows * dim; e += kGenRows) {
+    const int r = e / dim, c = e - r * dim;
+    As[c * kGenRows + r] = r < rows_a ? A[(size_t)i0 * dim + e] : 0.0;
+  }
+  const long long lo = (long long)blockIdx.y * chunk;
+  const long long hi = lo + chunk < (long long)n ? lo + chunk : (long long)n;
+  double d0 = INFINITY, d1 = INFINITY; int j0 = -1, j1 = -1;
+  for (long long base = lo; base < hi; base += kGenTile) {
+    const int rows = (int)(hi - base < kGenTile ? hi - base : kGenTile);
+    __syncthreads();
+    for (int e = threadIdx.x; e < rows * dim; e += kGenRows) Bs[e] = B[(size_t)base * dim + e];
+    __syncthreads();
+    for (int r = 0; r < rows; ++r) {
+      const double* b = Bs + r * dim;
+      double s = 0.0;
+      for (int c = 0; c < dim; ++c) {
+        const double t = __dsub_rn(As[c * kGenRows + threadIdx.x], b[c]);
+        s = __dadd_rn(s, __dmul_rn(t, t));
+      }
+      offer(s, (int)(base + r), d0, j0, d1, j1);
+    }
+  }
+  if (live) { Best2* o = part + ((size_t)blockIdx.y * m + i); o->d0 = d0; o->d1 = d1; o->j0 = j0; o->j1 = j1; }
+}
+
+// rows x 2 results from the rows x chunks partial lists (chunks == 0: the padding alone)
+__global__ __launch_bounds__(kThreads) void match_merge_kernel(const Best2* __restrict__ part, int rows, int chunks, int* __restrict__ idx,
+                                                               double* __restrict__ d2) {
+  const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
+  if (i >= rows) return;
+  double d0 = INFINITY, d1 = INFINITY; int j0 = -1, j1 = -1;
+  for (int y = 0; y < chunks; ++y) {
+    const Best2* p = part + ((size_t)y * rows + i);
+    const double pd0 = p->d0, pd1 = p->d1; const int pj0 = p->j0, pj1 = p->j1;
+    if (pj0 >= 0) offer(pd0, pj0, d0, j0, d1, j1);
+    if (pj1 >= 0) offer(pd1, pj1, d0, j0, d1, j1);
+  }
+  idx[2 * i] = j0; idx[2 * i + 1] = j1;
+  d2[2 * i] = d0; d2[2 * i + 1] = d1;
+}
+
+__global__ __launch_bounds__(kThreads) void match_finite_kernel(const double* __restrict__ v, size_t count, int* __restrict__ flag) {
+  bool bad = false;
+  for (size_t e = (size_t)blockIdx.x * kThreads + threadIdx.x; e < count; e += (size_t)gridDim.x * kThreads) bad |= !isfinite(v[e]);
+  if (bad) atomicOr(flag, 1);
+}
+
+size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+int grow(char** buf, size_t* have, size_t need) {
+  if (need <= *have) return MVICP_OK;
+  if (*buf) MV_HIP(hipFree(*buf));
+  *buf = nullptr; *have = 0;
+  MV_HIP(hipMalloc((void**)buf, need));
+  *have = need;
+  return MVICP_OK;
+}
+
+// rows of the right operand per chunk and the number of chunks for `right` rows
+void chunking(const mvicp_ctx* c, long long right, int* chunk, int* chunks) {
+  long long ch = c->match_chunk > 0 ? c->match_chunk : 1;
+  if ((right + ch - 1) / ch > kMaxChunks) ch = (right + kMaxChunks - 1) / kMaxChunks;
+  if (ch > right) ch = right > 0 ? right : 1;
+  *chunk = (int)ch;
+  *chunks = (int)((right + ch - 1) / ch);
+}
+
+int launch_direction(mvicp_ctx* c, const char* scope, const double* L, int rows, const double* Rt, int right, int dim, int chunk, int chunks, Best2* part) {
+  // the left rows once, the right rows once per workgroup of left rows, the partial lists
+  const double wgs = dim == 33 ? (rows + kThreads - 1) / kThreads : (rows + kGenRows - 1) / kGenRows;
+  ProfScope ps(c, scope, 8.0 * dim * ((double)rows * chunks + wgs * right) + sizeof(Best2) * (double)rows * chunks);
+  if (dim == 33) {
+    const dim3 grid((unsigned int)((rows + kThreads - 1) / kThreads), (unsigned int)chunks);
+    hipLaunchKernelGGL(match_kernel<33>, grid, dim3(kThreads), 0, c->stream, L, rows, Rt, right, chunk, part);
+  } else {
+    const dim3 grid((unsigned int)((rows + kGenRows - 1) / kGenRows), (unsigned int)chunks);
+    hipLaunchKernelGGL(match_generic_kernel, grid, dim3(kGenRows), 0, c->stream, L, rows, Rt, right, dim, chunk, part);
+  }
+  MV_HIP(hipGetLastError());
+  return MVICP_OK;
+}
+
+}  // namespace
+
+void free_match(mvicp_ctx* c) {
+  if (c->match_dev) (void)hipFree(c->match_dev);
+  if (c->match_tmp) (void)hipFree(c->match_tmp);
+  c->match_dev = nullptr; c->match_tmp = nullptr; c->match_dev_bytes = 0; c->match_tmp_bytes = 0;
+  c->match_fwd_idx = nullptr; c->match_bwd_idx = nullptr; c->match_fwd_d2 = nullptr; c->match_bwd_d2 = nullptr;
+  c->match_m = -1; c->match_n = -1;
+}
+
+long long feature_match(mvicp_ctx* c, const double* A, int a_on_device, long long m, const double* B, int b_on_device, long long n, int dim) {
+  c->match_m = -1; c->match_n = -1;   // (the last result ends here; a failed call leaves none behind)
+  hipStream_t st = c->stream;
+  const size_t M = (size_t)m, N = (size_t)n, a_bytes = 8 * M * dim, b_bytes = 8 * N * dim;
+  int chunk_f = 1, chunks_f = 0, chunk_b = 1, chunks_b = 0;
+  if (m > 0 && n > 0) { chunking(c, n, &chunk_f, &chunks_f); chunking(c, m, &chunk_b, &chunks_b); }
+  // results: [fwd_idx | fwd_d2 | bwd_idx | bwd_d2 | flag]
+  const size_t off_fd = align256(8 * M), off_bi = off_fd + align256(16 * M), off_bd = off_bi + align256(8 * N), off_flag = off_bd + align256(16 * N);
+  MV_CHECK(grow(&c->match_dev, &c->match_dev_bytes, off_flag + 256));
+  // scratch: [A staged | B staged | forward partial lists | backward partial lists]
+  const size_t off_b = a_on_device ? 0 : align256(a_bytes), off_pf = off_b + (b_on_device ? 0 : align256(b_bytes));
+  const size_t off_pb = off_pf + align256(sizeof(Best2) * M * chunks_f), tmp_need = off_pb + align256(sizeof(Best2) * N * chunks_b);
+  MV_CHECK(grow(&c->match_tmp, &c->match_tmp_bytes, tmp_need + 256));
+  c->match_fwd_idx = reinterpret_cast<int*>(c->match_dev); c->match_fwd_d2 = reinterpret_cast<double*>(c->match_dev + off_fd);
+  c->match_bwd_idx = reinterpret_cast<int*>(c->match_dev + off_bi); c->match_bwd_d2 = reinterpret_cast<double*>(c->match_dev + off_bd);
+  int* flag = reinterpret_cast<int*>(c->match_dev + off_flag);
+  const double* dA = A; const double* dB = B;
+  if (!a_on_device && a_bytes) { MV_HIP(hipMemcpyAsync(c->match_tmp, A, a_bytes, hipMemcpyHostToDevice, st)); dA = reinterpret_cast<const double*>(c->match_tmp); }
+  if (!b_on_device && b_bytes) { MV_HIP(hipMemcpyAsync(c->match_tmp + off_b, B, b_bytes, hipMemcpyHostToDevice, st)); dB = reinterpret_cast<const double*>(c->match_tmp + off_b); }
+  MV_HIP(hipMemsetAsync(flag, 0, sizeof(int), st));
+  const double* checked[2] = {dA, dB};
+  const size_t counts[2] = {M * dim, N * dim};
+  for (int t = 0; t < 2; ++t)
+    if (counts[t]) {
+      const size_t wgs = (counts[t] + kThreads - 1) / kThreads;
+      hipLaunchKernelGGL(match_finite_kernel, dim3((unsigned int)(wgs < 4096 ? wgs : 4096)), dim3(kThreads), 0, st, checked[t], counts[t], flag);
+      MV_HIP(hipGetLastError());
+    }
+  int h_flag = 0;
+  MV_HIP(hipMemcpyAsync(&h_flag, flag, sizeof(int), hipMemcpyDeviceToHost, st));
+  MV_HIP(hipStreamSynchronize(st));
+  if (h_flag) { set_error("a descriptor value is not finite"); return MVICP_ERR_ARG; }
+  Best2* part_f = reinterpret_cast<Best2*>(c->match_tmp + off_pf);
+  Best2* part_b = reinterpret_cast<Best2*>(c->match_tmp + off_pb);
+  if (chunks_f) {
+    MV_CHECK(launch_direction(c, "match_fwd", dA, (int)m, dB, (int)n, dim, chunk_f, chunks_f, part_f));
+    MV_CHECK(launch_direction(c, "match_bwd", dB, (int)n, dA, (int)m, dim, chunk_b, chunks_b, part_b));
+  }
+  {
+    ProfScope ps(c, "match_merge", (sizeof(Best2) * (double)chunks_f + 24.0) * m + (sizeof(Best2) * (double)chunks_b + 24.0) * n);
+    if (m) hipLaunchKernelGGL(match_merge_kernel, dim3((unsigned int)((M + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, part_f, (int)m, chunks_f, c->match_fwd_idx, c->match_fwd_d2);
+    if (n) hipLaunchKernelGGL(match_merge_kernel, dim3((unsigned int)((N + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, part_b, (int)n, chunks_b, c->match_bwd_idx, c->match_bwd_d2);
+    MV_HIP(hipGetLastError());
+  }
+  MV_HIP(hipStreamSynchronize(st));
+  c->match_m = m; c->match_n = n;
+  return m;
+}
+
+}  // namespace mvicp

@@ -20,6 +20,7 @@ SYMBOLS = [
     "mvicp_overlap", "mvicp_graph_from_overlap", "mvicp_voxel_grid", "mvicp_voxel_fetch",
     "mvicp_outlier_filter", "mvicp_outlier_fetch", "mvicp_outlier_threshold", "mvicp_cache_allowance",
     "mvicp_knn_search", "mvicp_knn_fetch", "mvicp_fpfh", "mvicp_fpfh_fetch",
+    "mvicp_feature_match", "mvicp_feature_match_fetch", "mvicp_match_pairs", "mvicp_consensus", "mvicp_consensus_fetch",
 ]
 
 # names of mvicp_get_structure (include/mvicp.h)
@@ -47,6 +48,10 @@ class OutlierStats(C.Structure):
         d = {k: getattr(self, k) for k, _ in self._fields_}
         d["s2"] = (d["s2_hi"] << 64) | d["s2_lo"]
         return d
+
+
+class ConsensusResult(C.Structure):
+    _fields_ = [("best", C.c_int), ("count", C.c_int), ("accepted", C.c_int), ("reserved", C.c_int), ("pose", C.c_double * 16)]
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_size_t)
@@ -124,6 +129,13 @@ def load_library(path=None):
     lib.mvicp_fpfh.argtypes = [vp, C.c_int, C.c_double, C.c_int]
     lib.mvicp_fpfh.restype = C.c_longlong
     lib.mvicp_fpfh_fetch.argtypes = [vp, C.c_longlong, vp, vp]
+    lib.mvicp_feature_match.argtypes = [vp, vp, C.c_longlong, vp, C.c_longlong, C.c_int]
+    lib.mvicp_feature_match.restype = C.c_longlong
+    lib.mvicp_feature_match_fetch.argtypes = [vp, C.c_longlong, C.c_longlong, vp, vp, vp, vp]
+    lib.mvicp_match_pairs.argtypes = [C.c_longlong, C.c_longlong, vp, vp, vp, C.c_int, C.c_double, vp]
+    lib.mvicp_match_pairs.restype = C.c_longlong
+    lib.mvicp_consensus.argtypes = [vp, vp, vp, C.c_longlong, C.c_longlong, C.c_ulonglong, C.c_double, C.c_double, C.POINTER(ConsensusResult)]
+    lib.mvicp_consensus_fetch.argtypes = [vp, C.c_longlong, vp, C.c_longlong, vp]
     if path is None:
         _lib = lib
     return lib
@@ -248,6 +260,53 @@ def closedform_point_to_plane(src, dst, nor):
     out = np.zeros(16)
     _check(lib, lib.mvicp_closedform_point_to_plane(_dp(a), _dp(b), _dp(c), len(a), _dp(out)))
     return poses_from_c(out)[0]
+
+
+def match_pairs(fwd_idx, fwd_d2, bwd_idx, mutual=True, ratio=1.0):
+    """mvicp_match_pairs on the fetched arrays of Engine.feature_match: pair (i, j = fwd_idx[i][0]) is kept iff j >= 0, (not mutual or
+    bwd_idx[j][0] == i) and (ratio >= 1 or fwd_d2[i][0] <= ratio^2 fwd_d2[i][1]) -> (k, 2) int32, ascending i.  Host only."""
+    lib = load_library()
+    fi = np.ascontiguousarray(fwd_idx, dtype=np.int32).reshape(-1, 2)
+    fd = np.ascontiguousarray(fwd_d2, dtype=np.float64).reshape(-1, 2)
+    bi = np.ascontiguousarray(bwd_idx, dtype=np.int32).reshape(-1, 2)
+    if len(fd) != len(fi):
+        raise ValueError("fwd_idx and fwd_d2 differ in length")
+    m, n = len(fi), len(bi)
+    pairs = np.zeros((max(m, 1), 2), dtype=np.int32)
+    spare = np.zeros(2)   # (an empty array still gets a pointer that is not NULL)
+    ptr = lambda a: (a if a.size else spare).ctypes.data_as(C.c_void_p)
+    k = _check(lib, lib.mvicp_match_pairs(m, n, ptr(fi), ptr(fd), ptr(bi), int(bool(mutual)), float(ratio), ptr(pairs)))
+    return pairs[:k].copy()
+
+
+def coarse_align(eng, src_frame, dst_frame, src_xyz, dst_xyz, radius, max_nn=64, hypotheses=10000, seed=0, tau=None, edge_sim=0.9,
+                 mutual=True, ratio=1.0):
+    """A coarse pose src -> dst from the clouds alone: Engine.fpfh of both frames (device results) -> Engine.feature_match ->
+    match_pairs -> Engine.consensus -> closedform_point_to_point over the winner's inliers in ascending pair order (when there are at
+    least 3).  src_xyz / dst_xyz: the stored clouds of the two frames as numpy arrays; tau: the inlier distance of the consensus.
+    -> dict(pose (4,4) = the consensus pose, refined (4,4), pairs (k,2), inliers (k,) uint8, counts = dict(pairs, accepted, inliers,
+    best)).  Fewer than 3 pairs, or no accepted hypothesis: both poses are the identity and best = -1."""
+    if tau is None:
+        raise ValueError("coarse_align needs tau, the inlier distance of the consensus")
+    src_xyz = np.ascontiguousarray(src_xyz, dtype=np.float64).reshape(-1, 3)
+    dst_xyz = np.ascontiguousarray(dst_xyz, dtype=np.float64).reshape(-1, 3)
+    da = eng.fpfh(src_frame, radius, max_nn, device=True)["desc"]
+    db = eng.fpfh(dst_frame, radius, max_nn, device=True)["desc"]
+    if da.shape[0] != len(src_xyz) or db.shape[0] != len(dst_xyz):
+        raise ValueError("src_xyz / dst_xyz are not the clouds of the two frames")
+    mt = eng.feature_match(da, db)
+    pairs = match_pairs(mt["fwd_idx"], mt["fwd_d2"], mt["bwd_idx"], mutual, ratio)
+    out = {"pose": np.eye(4), "refined": np.eye(4), "pairs": pairs, "inliers": np.zeros(len(pairs), dtype=np.uint8),
+           "counts": {"pairs": len(pairs), "accepted": 0, "inliers": 0, "best": -1}}
+    if len(pairs) < 3:
+        return out
+    P, Q = np.ascontiguousarray(src_xyz[pairs[:, 0]]), np.ascontiguousarray(dst_xyz[pairs[:, 1]])
+    cons = eng.consensus(P, Q, hypotheses, seed, tau, edge_sim)
+    out["pose"], out["inliers"] = cons["pose"], cons["flags"]
+    out["counts"].update(accepted=cons["accepted"], inliers=cons["count"], best=cons["best"])
+    keep = cons["flags"] != 0
+    out["refined"] = closedform_point_to_point(P[keep], Q[keep]) if cons["count"] >= 3 else cons["pose"].copy()
+    return out
 
 
 def lm_solve_host(n_frames, src, dst, poses, fixed, param, eval_callback, max_iterations=50):
@@ -623,6 +682,67 @@ class Engine:
             ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
         _check(self.lib, self.lib.mvicp_fpfh_fetch(self.h, n, ptr(desc), ptr(used)))
         return {"desc": desc, "used": used}
+
+    def _rows_operand(self, x, cols, what):
+        """-> (the array kept alive, its pointer or None when empty, rows) for a (rows, cols) float64 numpy array or torch tensor on the engine's GPU"""
+        if isinstance(x, np.ndarray) or not hasattr(x, "data_ptr"):
+            keep = np.ascontiguousarray(x, dtype=np.float64)
+            keep = keep.reshape(-1, cols) if cols else keep
+            if keep.ndim != 2:
+                raise MvicpError(f"{what} must be a matrix")
+            return keep, (keep.ctypes.data_as(C.c_void_p) if keep.size else None), keep.shape[0]
+        import torch
+        if not x.is_cuda or x.dtype != torch.float64 or (x.device.index or 0) != self.device:
+            raise MvicpError(f"a torch `{what}` must be a float64 tensor on the engine's GPU")
+        keep = x.contiguous()
+        keep = keep.reshape(-1, cols) if cols else keep
+        if keep.dim() != 2:
+            raise MvicpError(f"{what} must be a matrix")
+        torch.cuda.synchronize(keep.device)   # (a device array must be fully written when the call is made)
+        return keep, (C.c_void_p(keep.data_ptr()) if keep.numel() else None), int(keep.shape[0])
+
+    def feature_match(self, a, b, device=False):
+        """mvicp_feature_match + mvicp_feature_match_fetch: a (m, dim), b (n, dim), 1 <= dim <= 64, numpy arrays or float64 torch tensors
+        on the engine's GPU.  Per row of a the two nearest rows of b in the order (dist, j), dist = the sequential fp64 sum of squared
+        differences, and the reverse -> dict(fwd_idx (m,2) int32, fwd_d2 (m,2), bwd_idx (n,2) int32, bwd_d2 (n,2)), a missing entry
+        padded with (-1, +inf).  device=True: torch tensors on the engine's GPU.  Needs no frame and no graph; history-neutral."""
+        ka, pa, m = self._rows_operand(a, 0, "a")
+        kb, pb, n = self._rows_operand(b, 0, "b")
+        if ka.shape[1] != kb.shape[1]:
+            raise MvicpError(f"a has {ka.shape[1]} columns, b {kb.shape[1]}")
+        got = int(_check(self.lib, self.lib.mvicp_feature_match(self.h, pa, m, pb, n, int(ka.shape[1]))))
+        assert got == m
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+            f64, i32 = torch.float64, torch.int32
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if t.numel() else None
+        else:
+            mk = lambda shape, dt: np.zeros(shape, dtype=dt)
+            f64, i32 = np.float64, np.int32
+            ptr = lambda t: t.ctypes.data_as(C.c_void_p) if t.size else None
+        fi, fd, bi, bd = mk((m, 2), i32), mk((m, 2), f64), mk((n, 2), i32), mk((n, 2), f64)
+        if device:
+            torch.cuda.synchronize(dev)   # (the allocations are the caller's; the library fills them on its own stream and waits)
+        _check(self.lib, self.lib.mvicp_feature_match_fetch(self.h, m, n, ptr(fi), ptr(fd), ptr(bi), ptr(bd)))
+        return {"fwd_idx": fi, "fwd_d2": fd, "bwd_idx": bi, "bwd_d2": bd}
+
+    def consensus(self, P, Q, hypotheses, seed, tau, edge_sim=0.9):
+        """mvicp_consensus + mvicp_consensus_fetch: P, Q (c, 3) index-aligned pairs src -> dst (numpy arrays or float64 torch tensors on
+        the engine's GPU), `hypotheses` triangle-frame poses drawn from `seed`, each scored by its pairs within tau; edge_sim rejects
+        triangles whose edge lengths differ by more than that factor -> dict(best, count, accepted, pose (4,4), counts (H,) int32 with
+        -1 = rejected, flags (c,) uint8 = the winner's inliers).  Needs no frame and no graph; history-neutral."""
+        kp, pp, c = self._rows_operand(P, 3, "P")
+        kq, pq, cq = self._rows_operand(Q, 3, "Q")
+        if c != cq:
+            raise MvicpError(f"P has {c} rows, Q {cq}")
+        res = ConsensusResult()
+        _check(self.lib, self.lib.mvicp_consensus(self.h, pp, pq, c, int(hypotheses), int(seed) & (2 ** 64 - 1), float(tau), float(edge_sim), C.byref(res)))
+        counts, flags = np.zeros(int(hypotheses), dtype=np.int32), np.zeros(c, dtype=np.uint8)
+        _check(self.lib, self.lib.mvicp_consensus_fetch(self.h, len(counts), counts.ctypes.data_as(C.c_void_p), c, flags.ctypes.data_as(C.c_void_p)))
+        return {"best": int(res.best), "count": int(res.count), "accepted": int(res.accepted), "pose": poses_from_c(np.array(res.pose[:]))[0],
+                "counts": counts, "flags": flags}
 
     def nn_query(self, frame, queries, nn_method=NN_AUTO):
         q = np.ascontiguousarray(queries, dtype=np.float64)
