@@ -9,6 +9,7 @@ import pytest
 
 import mvicp
 import outlierref
+import pathcases
 from mvicp import synth
 
 pytestmark = pytest.mark.gpu
@@ -60,11 +61,13 @@ def sheet_ref(n, k, std_ratio, radius, normals=True):
     return outlierref.outlier_filter(p, nr if normals else None, k, std_ratio, radius)
 
 
-@pytest.mark.parametrize("k", [1, 8, 32])
+@pytest.mark.parametrize("k", pathcases.OUTLIER_SWEEP_K)
 @pytest.mark.parametrize("n", ["k+1", 63, 64, 65, 257, 5000])
 def test_size_sweep(eng, n, k):
-    """n = k + 1 makes every list the whole cloud; 63 / 64 / 65 straddle a wave, 257 two workgroups of the knn kernel; k = 1 / 8 / 32 run
-    the three list capacities."""
+    """n = k + 1 makes every list the whole cloud; 63 / 64 / 65 straddle a wave, 257 two workgroups of the knn kernel.  The knn kernel has
+    three list capacities: k <= 8 runs <9>, 9 <= k <= 16 runs <17>, k >= 17 runs <33>; k = 1, 8 | 9, 16 | 17, 32 are the ends of the three
+    ranges, so both sides of each boundary run (tests/test_paths_cpu.py holds the list against the dispatch in csrc/outlier.hip)."""
+    assert pathcases.OUTLIER_SWEEP_K == pathcases.outlier_boundary_ks()
     n = k + 1 if n == "k+1" else n
     p, nr, planted = sheet(n)
     want = sheet_ref(n, k, 2.0, 0.0)
@@ -74,6 +77,17 @@ def test_size_sweep(eng, n, k):
         assert len(removed & set(planted.tolist())) >= 0.85 * len(planted)
     eng.set_frames([p], [nr])
     assert_same(eng.outlier_filter(0, k, 2.0, 0.0), want, (n, k))
+
+
+@pytest.mark.parametrize("k,std_ratio,radius", pathcases.O1_PARAMS)
+def test_far_from_the_origin(eng, k, std_ratio, radius):
+    """O1: a cloud of 1 mm extent at UTM coordinates (|p| > 4e6, the spacing of the doubles there is a nanometre), one case per list
+    capacity, the statistical rule, both rules and the radius rule alone."""
+    want = pathcases.check_outlier_far(k, std_ratio, radius)
+    p, nr = pathcases.outlier_far_cloud()
+    eng.set_frames([p], [nr])
+    assert_same(eng.outlier_filter(0, k, std_ratio, radius), want, ("far", k, std_ratio, radius))
+    assert_same(eng.outlier_filter(0, k, std_ratio, radius, device=True), want, ("far, device fetch", k, std_ratio, radius))
 
 
 def test_lattice_ties_and_a_far_cluster(eng):

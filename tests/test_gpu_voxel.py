@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import mvicp
+import pathcases
 import voxelref
 from mvicp import lib as L
 from mvicp import synth
@@ -117,6 +118,48 @@ def test_several_frames_with_poses(eng):
     assert a["xyz"].tobytes() != b["xyz"].tobytes() or a["nrm"].tobytes() != b["nrm"].tobytes()
     # poses given but frames stored as they are: NULL poses is "no arithmetic", not the identity's
     assert_same(eng.voxel_grid(h, [1]), voxelref.voxel_grid(pb["pts"], pb["nor"], h, [1]), "stored")
+
+
+@pytest.mark.parametrize("h", pathcases.V1_VOXELS)
+def test_wide_keys(eng, h):
+    """V1: two clusters 1000 (then 1200) apart on every axis at a millimetre voxel: a million cells per axis, negative and positive, and a
+    sort over 60 (then 61) key bits, the widest below the refusal; further apart the cell count passes 2^62, which is refused and leaves
+    the context usable."""
+    for shift in (pathcases.V1_SHIFT, pathcases.V1_SHIFT_WIDER):
+        bits, want = pathcases.check_voxel_v1(shift, h)
+        p, nr = pathcases.voxel_two_clusters(shift)
+        eng.set_frames([p], [nr])
+        for permute in (1, 0):
+            eng.set_option("voxel_permute", permute)
+            assert_same(eng.voxel_grid(h), want, ("wide keys", shift, h, bits, permute))
+        eng.set_option("voxel_permute", 1)
+    p, nr = pathcases.voxel_two_clusters(pathcases.V1_SHIFT_REFUSED)
+    assert pathcases.voxel_key_bits(p, h)[1] >= 2 ** 62
+    with pytest.raises(ValueError, match="too small for the extent"):
+        voxelref.voxel_grid([p], [nr], h)
+    eng.set_frames([p], [nr])
+    for permute in (1, 0):
+        eng.set_option("voxel_permute", permute)
+        with pytest.raises(mvicp.MvicpError, match="too small for the extent"):
+            eng.voxel_grid(h)
+        assert_same(eng.voxel_grid(0.04), voxelref.voxel_grid([p], [nr], 0.04), ("after the refusal", h, permute))
+    eng.set_option("voxel_permute", 1)
+
+
+def test_georeferenced_and_fused(eng):
+    """V2: three frames with poses at UTM coordinates, fused at a centimetre voxel (quotients above 4e8); a millimetre voxel there passes
+    2^31 cells from the origin, which is an argument error that leaves the context usable."""
+    want = pathcases.check_voxel_v2()
+    pts, nor, poses = pathcases.voxel_v2_problem()
+    eng.set_frames(pts, nor)
+    for permute in (1, 0):
+        eng.set_option("voxel_permute", permute)
+        assert_same(eng.voxel_grid(pathcases.V2_VOXEL, None, poses), want, ("utm", permute))
+        with pytest.raises(mvicp.MvicpError, match="status -1"):
+            eng.voxel_grid(pathcases.V2_VOXEL_REFUSED, None, poses)
+        assert b"2^31" in eng.lib.mvicp_last_error()
+        assert_same(eng.voxel_grid(pathcases.V2_VOXEL, None, poses), want, ("utm, after the refusal", permute))
+    eng.set_option("voxel_permute", 1)
 
 
 def test_normals_empty_frames_and_empty_selections(eng):
