@@ -351,6 +351,58 @@ int mvicp_consensus(mvicp_ctx* ctx, const double* p, const double* q, long long 
  * Errors: NULL context, cap_h < hypotheses, cap_c < n_pairs -> MVICP_ERR_ARG; no mvicp_consensus before -> MVICP_ERR_STATE. */
 int mvicp_consensus_fetch(mvicp_ctx* ctx, long long cap_h, int* count, long long cap_c, unsigned char* flags);
 
+/* ---- Batched coarse poses over an edge list, and initial poses from them ---------------------------------------------------------
+ * mvicp_coarse_pairs: desc (total x dim doubles) and xyz (total x 3 doubles) are the concatenated descriptors and points of n_sets
+ * sets; set s owns rows offsets[s] .. offsets[s+1] (offsets: n_sets + 1 non-decreasing host values starting at 0; empty sets are
+ * allowed).  desc, xyz and the fetch destinations may each be a HOST or a DEVICE pointer, decided per pointer as mvicp_voxel_fetch
+ * decides; offsets, src, dst, seeds and results are host pointers.
+ * CONTRACT, by reduction: for edge e with a = src[e], b = dst[e], m_a and m_b their rows, results[e] and the fetched arrays equal, byte
+ * for byte, the chain
+ *   1  mvicp_feature_match(desc_a, m_a, desc_b, m_b, dim)
+ *   2  mvicp_match_pairs(..., mutual, ratio): c pairs in ascending i
+ *   3  P = xyz_a[pairs[:,0]], Q = xyz_b[pairs[:,1]]
+ *   4  mvicp_consensus(P, Q, c, hypotheses, seeds[e], tau, edge_sim) when c >= 3; otherwise best = -1, count = 0, accepted = 0, the
+ *      identity pose and no flag set.
+ * results[e].pairs = c.  Each distinct ordered set pair is matched once, whatever the edge list repeats or reverses.  Option
+ * "match_chunk" changes the speed only.  HISTORY-NEUTRAL, needs NO graph and NO frame; the result lives in storage of its own (the last
+ * results of mvicp_feature_match, mvicp_consensus, mvicp_fpfh and mvicp_knn_search are left untouched) until the next mvicp_coarse_pairs,
+ * mvicp_set_num_frames or mvicp_destroy; a failed call leaves none behind.  The host waits for the device twice per call, however many
+ * edges.  Profile scopes: "coarse_match", "coarse_merge", "coarse_rule", "coarse_hyp", "coarse_score", "coarse_pick".
+ * RETURNS n_edges (n_edges = 0 is not an error) or a negative mvicp_status.
+ * Errors (MVICP_ERR_ARG, decided before the context is touched): NULL context or pointer, dim outside [1, 64], n_sets < 1, n_edges
+ * outside [0, 65535], an edge index out of range or src[e] == dst[e], offsets that do not start at 0 or decrease, a total >= 2^31,
+ * hypotheses outside [1, 2^24], n_edges x hypotheses > 2^28, a ratio that is NaN or <= 0, a tau that is not finite or <= 0, an edge_sim
+ * outside [0, 1); a non-finite descriptor or coordinate -> MVICP_ERR_ARG, reported by this call, and no result is left behind. */
+typedef struct mvicp_coarse_edge {
+  int pairs, best, count, accepted;
+  double pose[16];
+} mvicp_coarse_edge;
+long long mvicp_coarse_pairs(mvicp_ctx* ctx, const double* desc, const double* xyz, const long long* offsets, int n_sets, int dim, int n_edges,
+                             const int* src, const int* dst, const unsigned long long* seeds, int mutual, double ratio, long long hypotheses,
+                             double tau, double edge_sim, mvicp_coarse_edge* results);
+/* Copies edge `edge` of the last result: pairs (c x 2 ints, (i, j) in ascending i), flags (c bytes: 1 = an inlier of the winner); each
+ * may be NULL.  cap_pairs = pairs the destinations hold.
+ * Errors: NULL context, an edge out of range, cap_pairs < c -> MVICP_ERR_ARG; no mvicp_coarse_pairs before -> MVICP_ERR_STATE. */
+int mvicp_coarse_pairs_fetch(mvicp_ctx* ctx, int edge, long long cap_pairs, int* pairs, unsigned char* flags);
+
+/* Initial poses from pairwise poses (pure host function, no context; host pointers).  pose[e] (16 column-major doubles) maps coordinates
+ * of frame src[e] into those of frame dst[e], as mvicp_consensus returns it; the poses written map frame to world.  Edge e is usable
+ * iff count[e] >= min_count.
+ *   Rule         a maximum spanning forest, Prim, deterministic: the reached set starts as {root}; among the usable edges with exactly
+ *                one endpoint reached take the largest count, the lowest e among equals; repeat until none is left.  If frames remain,
+ *                the lowest unreached index starts the next component: its pose is the identity, its parent and parent_edge -1.
+ *                component[i] numbers the components in the order they start (the root's is 0).  More than one component is reported,
+ *                not repaired.
+ *   Composition  fp64, every operation rounded on its own, no fma.  With T = pose[e]: the new frame is dst[e]: pose_child = pose_parent
+ *                T^-1, T^-1 = [R^T | -(R^T t)]; the new frame is src[e]: pose_child = pose_parent T.  A product has R = Ra Rb, each
+ *                entry (a0 b0 + a1 b1) + a2 b2, t = (Ra tb) + ta with a row times a vector as (r0 v0 + r1 v1) + r2 v2, and the bottom
+ *                row 0 0 0 1.  The root's pose is root_pose as given (NULL: the identity).
+ * parent, parent_edge and component may be NULL.  RETURNS THE NUMBER OF COMPONENTS (>= 1).
+ * Errors (MVICP_ERR_ARG): poses_out NULL, src / dst / count / pose NULL with n_edges > 0, n_frames < 1, n_edges < 0, root out of range,
+ * an edge index out of range or src[e] == dst[e], min_count < 0. */
+int mvicp_poses_from_pairs(int n_frames, int n_edges, const int* src, const int* dst, const int* count, const double* pose, int min_count,
+                           int root, const double* root_pose, double* poses_out, int* parent, int* parent_edge, int* component);
+
 /* The rounding allowance of the temporal cache (pure host function, no context): what mvicp_correspond adds to the displacement |dM p + dv|
  * of an edge's queries between the search at (pose_src_old, pose_dst_old) and the one at (pose_src, pose_dst), poses as 16 column-major
  * doubles, max_norm >= max |p| over the source cloud.  With x = (Rs, ts, Rd^-1, td) the query transform of a pose pair (Rd^-1 as

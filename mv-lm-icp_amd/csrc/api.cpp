@@ -558,6 +558,7 @@ int mvicp_destroy(mvicp_ctx* c) try {
   free_fpfh(c);
   free_match(c);
   free_consensus(c);
+  free_coarse(c);
   for (auto& kv : c->tables) if (kv.second.d) (void)hipFree(kv.second.d);
   if (c->d_census) (void)hipFree(c->d_census);
   if (c->h_census) (void)hipHostFree(c->h_census);
@@ -587,6 +588,7 @@ int mvicp_set_num_frames(mvicp_ctx* c, int n_frames) try {
   free_fpfh(c);    // (and the last descriptors)
   free_match(c);   // (and the last matches)
   free_consensus(c); // (and the last consensus)
+  free_coarse(c);    // (and the last batched coarse poses)
   for (FrameDev& f : c->frames) { dev_free(f.pts); dev_free(f.nor); free_grid(f.grid); free_tie(f); }
   c->frames.assign(n_frames, FrameDev());
   c->n_frames = n_frames;
@@ -1118,6 +1120,127 @@ int mvicp_consensus_fetch(mvicp_ctx* c, long long cap_h, int* count, long long c
     if (dst[t]) MV_HIP(hipMemcpyAsync(dst[t], src[t], bytes[t], kind[t] ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
   MV_HIP(hipStreamSynchronize(c->stream));
   return MVICP_OK;
+} MVICP_GUARD_ABI
+
+long long mvicp_coarse_pairs(mvicp_ctx* c, const double* desc, const double* xyz, const long long* offsets, int n_sets, int dim, int n_edges,
+                             const int* src, const int* dst, const unsigned long long* seeds, int mutual, double ratio, long long hypotheses,
+                             double tau, double edge_sim, mvicp_coarse_edge* results) try {
+  // every argument error that needs no GPU first: nothing of the context has been touched when one of them is reported
+  if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
+  if (dim < 1 || dim > 64) { set_error("dim = %d outside [1, 64]", dim); return MVICP_ERR_ARG; }
+  if (n_sets < 1) { set_error("n_sets = %d < 1", n_sets); return MVICP_ERR_ARG; }
+  if (n_edges < 0 || n_edges > 65535) { set_error("n_edges = %d outside [0, 65535]", n_edges); return MVICP_ERR_ARG; }
+  if (!offsets) { set_error("null offsets"); return MVICP_ERR_ARG; }
+  if (offsets[0] != 0) { set_error("offsets[0] = %lld, not 0", offsets[0]); return MVICP_ERR_ARG; }
+  for (int s = 0; s < n_sets; ++s)
+    if (offsets[s + 1] < offsets[s]) { set_error("offsets decrease at set %d", s); return MVICP_ERR_ARG; }
+  const long long total = offsets[n_sets];
+  if (total >= (1ll << 31)) { set_error("%lld rows in all, not below 2^31", total); return MVICP_ERR_ARG; }
+  if (total > 0 && (!desc || !xyz)) { set_error("null descriptors or points"); return MVICP_ERR_ARG; }
+  if (n_edges > 0 && (!src || !dst || !seeds || !results)) { set_error("null edge arrays"); return MVICP_ERR_ARG; }
+  for (int e = 0; e < n_edges; ++e)
+    if (src[e] < 0 || src[e] >= n_sets || dst[e] < 0 || dst[e] >= n_sets || src[e] == dst[e]) {
+      set_error("edge %d = (%d, %d) with %d sets", e, src[e], dst[e], n_sets); return MVICP_ERR_ARG;
+    }
+  if (hypotheses < 1 || hypotheses > (1ll << 24)) { set_error("%lld hypotheses outside [1, 2^24]", hypotheses); return MVICP_ERR_ARG; }
+  if ((long long)n_edges * hypotheses > (1ll << 28)) { set_error("n_edges x hypotheses = %lld above 2^28", (long long)n_edges * hypotheses); return MVICP_ERR_ARG; }
+  if (!(ratio > 0.0)) { set_error("ratio must be > 0"); return MVICP_ERR_ARG; }
+  if (!std::isfinite(tau) || !(tau > 0.0)) { set_error("tau must be finite and > 0"); return MVICP_ERR_ARG; }
+  if (!(edge_sim >= 0.0 && edge_sim < 1.0)) { set_error("edge_sim must be in [0, 1)"); return MVICP_ERR_ARG; }
+  MV_CHECK(bind(c));
+  int desc_dev = 0, xyz_dev = 0;
+  if (total > 0) {
+    desc_dev = destination_kind(c, desc, "desc"); if (desc_dev < 0) return desc_dev;
+    xyz_dev = destination_kind(c, xyz, "xyz"); if (xyz_dev < 0) return xyz_dev;
+  }
+  const long long got = coarse_pairs(c, desc, desc_dev, xyz, xyz_dev, offsets, n_sets, dim, n_edges, src, dst, seeds, mutual, ratio, hypotheses, tau, edge_sim, results);
+  if (c->profile) prof_collect_lazy(c);
+  return got;
+} MVICP_GUARD_ABI
+
+int mvicp_coarse_pairs_fetch(mvicp_ctx* c, int edge, long long cap_pairs, int* pairs, unsigned char* flags) try {
+  if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
+  if (c->coarse_edges < 0) { set_error("no coarse pairs: call mvicp_coarse_pairs first"); return MVICP_ERR_STATE; }
+  if (edge < 0 || edge >= c->coarse_edges) { set_error("edge %d out of range [0,%d)", edge, c->coarse_edges); return MVICP_ERR_ARG; }
+  const long long n = c->coarse_cnt[edge];
+  if ((pairs || flags) && cap_pairs < n) { set_error("cap_pairs %lld < %lld pairs", cap_pairs, n); return MVICP_ERR_ARG; }
+  if (n == 0) return MVICP_OK;
+  MV_CHECK(bind(c));
+  const size_t seg = (size_t)c->coarse_seg[edge];
+  const void* from[2] = {c->coarse_pairs + 2 * seg, c->coarse_flags + seg};
+  void* to[2] = {pairs, flags};
+  const size_t bytes[2] = {8 * (size_t)n, (size_t)n};
+  const char* names[2] = {"pairs", "flags"};
+  int kind[2] = {0, 0};
+  for (int t = 0; t < 2; ++t)
+    if (to[t]) { kind[t] = destination_kind(c, to[t], names[t]); if (kind[t] < 0) return kind[t]; }
+  for (int t = 0; t < 2; ++t)
+    if (to[t]) MV_HIP(hipMemcpyAsync(to[t], from[t], bytes[t], kind[t] ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+  MV_HIP(hipStreamSynchronize(c->stream));
+  return MVICP_OK;
+} MVICP_GUARD_ABI
+
+// a (R, t) product of two column-major poses, each operation rounded on its own (this TU is built without fma contraction)
+static void compose_pose(const double* A, const double* B, double* out) {
+  double r[16];
+  for (int row = 0; row < 3; ++row) {
+    const double a0 = A[row], a1 = A[4 + row], a2 = A[8 + row];
+    for (int col = 0; col < 3; ++col) r[4 * col + row] = (a0 * B[4 * col] + a1 * B[4 * col + 1]) + a2 * B[4 * col + 2];
+    r[12 + row] = ((a0 * B[12] + a1 * B[13]) + a2 * B[14]) + A[12 + row];
+  }
+  r[3] = 0.0; r[7] = 0.0; r[11] = 0.0; r[15] = 1.0;
+  std::memcpy(out, r, sizeof(r));
+}
+
+// [R^T | -(R^T t)] of a column-major pose
+static void invert_pose(const double* T, double* out) {
+  for (int row = 0; row < 3; ++row) {   // row `row` of R^T is column `row` of R
+    const double r0 = T[4 * row], r1 = T[4 * row + 1], r2 = T[4 * row + 2];
+    out[row] = r0; out[4 + row] = r1; out[8 + row] = r2;
+    out[12 + row] = -((r0 * T[12] + r1 * T[13]) + r2 * T[14]);
+  }
+  out[3] = 0.0; out[7] = 0.0; out[11] = 0.0; out[15] = 1.0;
+}
+
+int mvicp_poses_from_pairs(int n_frames, int n_edges, const int* src, const int* dst, const int* count, const double* pose, int min_count,
+                           int root, const double* root_pose, double* poses_out, int* parent, int* parent_edge, int* component) try {
+  if (n_frames < 1 || n_edges < 0 || !poses_out) { set_error("poses from pairs: needs n_frames >= 1, n_edges >= 0 and poses_out"); return MVICP_ERR_ARG; }
+  if (n_edges > 0 && (!src || !dst || !count || !pose)) { set_error("poses from pairs: null edge arrays"); return MVICP_ERR_ARG; }
+  if (root < 0 || root >= n_frames) { set_error("poses from pairs: root %d out of range [0,%d)", root, n_frames); return MVICP_ERR_ARG; }
+  if (min_count < 0) { set_error("poses from pairs: min_count < 0"); return MVICP_ERR_ARG; }
+  for (int e = 0; e < n_edges; ++e)
+    if (src[e] < 0 || src[e] >= n_frames || dst[e] < 0 || dst[e] >= n_frames || src[e] == dst[e]) {
+      set_error("poses from pairs: edge %d = (%d, %d) with %d frames", e, src[e], dst[e], n_frames); return MVICP_ERR_ARG;
+    }
+  const double identity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  std::vector<char> reached((size_t)n_frames, 0);
+  std::vector<int> par((size_t)n_frames, -1), pedge((size_t)n_frames, -1), comp((size_t)n_frames, -1);
+  int components = 0, start = root, left = n_frames;
+  while (left > 0) {
+    reached[start] = 1; comp[start] = components; --left;
+    std::memcpy(poses_out + 16 * (size_t)start, components == 0 && root_pose ? root_pose : identity, sizeof(identity));
+    for (;;) {
+      int pick = -1;
+      for (int e = 0; e < n_edges; ++e)
+        if (count[e] >= min_count && reached[src[e]] != reached[dst[e]] && (pick < 0 || count[e] > count[pick])) pick = e;
+      if (pick < 0) break;
+      const bool child_is_dst = reached[src[pick]] != 0;
+      const int child = child_is_dst ? dst[pick] : src[pick], from = child_is_dst ? src[pick] : dst[pick];
+      const double* T = pose + 16 * (size_t)pick;
+      double inv[16];
+      if (child_is_dst) invert_pose(T, inv);
+      compose_pose(poses_out + 16 * (size_t)from, child_is_dst ? inv : T, poses_out + 16 * (size_t)child);
+      reached[child] = 1; par[child] = from; pedge[child] = pick; comp[child] = components; --left;
+    }
+    ++components;
+    for (start = 0; start < n_frames && reached[start]; ++start) {}
+  }
+  for (int i = 0; i < n_frames; ++i) {
+    if (parent) parent[i] = par[i];
+    if (parent_edge) parent_edge[i] = pedge[i];
+    if (component) component[i] = comp[i];
+  }
+  return components;
 } MVICP_GUARD_ABI
 
 int mvicp_outlier_threshold(long long n, unsigned long long s1, unsigned long long s2_hi, unsigned long long s2_lo, double std_ratio, double* T) try {

@@ -292,6 +292,15 @@ struct mvicp_ctx {
   int* cons_count = nullptr; unsigned char* cons_flags = nullptr;
   long long cons_H = -1, cons_c = -1;
 
+  // batched coarse poses (coarse.hip): the last result, library-owned until the next mvicp_coarse_pairs / mvicp_set_num_frames /
+  // mvicp_destroy (coarse_edges < 0: none).  coarse_dev holds [pairs | flags] in per-edge segments (edge e: coarse_seg[e], coarse_cnt[e]
+  // pairs), coarse_tmp the scratch of a call, coarse_work the scoring work table; all kept between calls and grown on demand
+  char* coarse_dev = nullptr; char* coarse_tmp = nullptr; char* coarse_work = nullptr;
+  size_t coarse_dev_bytes = 0, coarse_tmp_bytes = 0, coarse_work_bytes = 0;
+  int* coarse_pairs = nullptr; unsigned char* coarse_flags = nullptr;
+  std::vector<long long> coarse_seg; std::vector<int> coarse_cnt;
+  int coarse_edges = -1;
+
   // cached small tables
   struct CachedTable { std::vector<char> bytes; void* d = nullptr; size_t cap = 0; };
   std::map<std::string, CachedTable> tables;
@@ -425,6 +434,14 @@ void free_match(mvicp_ctx* c);     // the result and the buffers
 int consensus(mvicp_ctx* c, const double* P, int p_on_device, const double* Q, int q_on_device, long long n_pairs, long long H, unsigned long long seed,
               double tau, double edge_sim, mvicp_consensus_result* out);
 void free_consensus(mvicp_ctx* c); // the result and the buffer
+// coarse.hip: the chain feature_match -> match_pairs -> gather -> consensus for every edge (src[e], dst[e]) over n_sets sets whose rows
+// are offsets[s] .. offsets[s+1] of desc (x dim) and xyz (x 3), each in host or device memory; every argument already checked.  pairs /
+// flags stay on the context (coarse_*), the records go to `results`.  Returns n_edges or a negative status (a non-finite value:
+// MVICP_ERR_ARG, no result).  Waits for the stream twice, however many edges; history-neutral.
+long long coarse_pairs(mvicp_ctx* c, const double* desc, int desc_on_device, const double* xyz, int xyz_on_device, const long long* offsets, int n_sets, int dim,
+                       int n_edges, const int* src, const int* dst, const unsigned long long* seeds, int mutual, double ratio, long long H, double tau,
+                       double edge_sim, mvicp_coarse_edge* results);
+void free_coarse(mvicp_ctx* c);    // the result and the buffers
 int launch_compact(mvicp_ctx* c, double d2_bound);                                    // corr.hip
 int launch_gather_stream(mvicp_ctx* c);
 int launch_select_median(mvicp_ctx* c, double d2_bound);   // two-pass select anchored at the acceptance bound: any key set, exact

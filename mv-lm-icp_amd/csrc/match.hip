@@ -16,68 +16,34 @@
 //   2  match_merge_kernel    per left row the best two over its chunks in (d2, j) order.  Tiling cannot change a pair's dist, and the
 //                            chunks are visited in ascending j, so the merge is exact.
 #include "common.h"
+#include "match_tile.h"
 
 namespace mvicp {
 
 namespace {
 
+using match_tile::Best2; using match_tile::RegTile; using match_tile::scan_reg; using match_tile::scan_generic; using match_tile::merge_row;
+
+// the launch arithmetic below is written in these; the tile loops of match_tile.h in their namesakes
 constexpr int kThreads = 256;   // left rows per workgroup of match_kernel
 constexpr int kTile = 64;       // right rows per LDS tile
 constexpr int kGenRows = 64;    // left rows per workgroup of match_generic_kernel
 constexpr int kGenTile = 32;    // its right rows per LDS tile
 constexpr int kMaxDim = 64;
 constexpr int kMaxChunks = 65535;
-
-struct Best2 { double d0, d1; int j0, j1; };   // the first two of a row in (d2, j) order; j < 0: the slot is empty (d = +inf)
-static_assert(sizeof(Best2) == 24, "Best2 is 24 bytes");
-
-// candidates arrive in ascending j (or chunk by chunk in ascending j, each chunk's own two in order): a strict comparison keeps the lower j
-__device__ __forceinline__ void offer(double d, int j, double& d0, int& j0, double& d1, int& j1) {
-  const bool first = j0 < 0 || d < d0, second = !first && (j1 < 0 || d < d1);   // (selects: the four values stay in registers)
-  d1 = first ? d0 : second ? d : d1; j1 = first ? j0 : second ? j : j1;
-  d0 = first ? d : d0; j0 = first ? j : j0;
-}
+static_assert(kThreads == match_tile::kThreads && kTile == match_tile::kTile && kGenRows == match_tile::kGenRows && kGenTile == match_tile::kGenTile &&
+              kMaxDim == match_tile::kMaxDim, "the launches and the tile loops agree on the tiling");
 
 template <int DIM>
 __global__ __launch_bounds__(kThreads) void match_kernel(const double* __restrict__ A, int m, const double* __restrict__ B, int n, int chunk,
                                                          Best2* __restrict__ part) {
-  constexpr int LD = DIM + (DIM & 1);   // (an even row length keeps every row 16-byte aligned)
-  constexpr int SEG = 11;               // the early-exit check follows each sub-histogram
-  static_assert(DIM % SEG == 0, "the row is a whole number of segments");
-  __shared__ double Bs[kTile * LD];
+  __shared__ double Bs[kTile * RegTile<DIM>::LD];
   const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
   const bool live = i < m;
-  double a[DIM];
-#pragma unroll
-  for (int c = 0; c < DIM; ++c) a[c] = live ? A[(size_t)i * DIM + c] : 0.0;
   const long long lo = (long long)blockIdx.y * chunk;
   const long long hi = lo + chunk < (long long)n ? lo + chunk : (long long)n;
   double d0 = INFINITY, d1 = INFINITY; int j0 = -1, j1 = -1;
-  for (long long base = lo; base < hi; base += kTile) {
-    const int rows = (int)(hi - base < kTile ? hi - base : kTile);
-    __syncthreads();   // (the last tile has been read by every wave)
-    for (int e = threadIdx.x; e < rows * DIM; e += kThreads) {
-      const int r = e / DIM, c = e - r * DIM;
-      Bs[r * LD + c] = B[(size_t)base * DIM + e];
-    }
-    __syncthreads();
-    for (int r = 0; r < rows; ++r) {
-      const double* b = Bs + r * LD;
-      double s = 0.0;
-      bool skip = false;
-#pragma unroll
-      for (int g = 0; g < DIM / SEG; ++g) {
-#pragma unroll
-        for (int c = g * SEG; c < (g + 1) * SEG; ++c) {
-          const double t = __dsub_rn(a[c], b[c]);
-          s = __dadd_rn(s, __dmul_rn(t, t));
-        }
-        // s only grows from here: above the second best (never above an empty slot's +inf) it cannot enter
-        if (g + 1 < DIM / SEG && __all(!live || s > d1)) { skip = true; break; }
-      }
-      if (!skip) offer(s, (int)(base + r), d0, j0, d1, j1);
-    }
-  }
+  scan_reg<DIM>(A, i, live, B, lo, hi, Bs, d0, j0, d1, j1);
   if (live) { Best2* o = part + ((size_t)blockIdx.y * m + i); o->d0 = d0; o->d1 = d1; o->j0 = j0; o->j1 = j1; }
 }
 
@@ -88,29 +54,10 @@ __global__ __launch_bounds__(kGenRows) void match_generic_kernel(const double* _
   const long long i0 = (long long)blockIdx.x * kGenRows;
   const long long i = i0 + threadIdx.x;
   const bool live = i < m;
-  const int rows_a = (int)((long long)m - i0 < kGenRows ? (long long)m - i0 : kGenRows);
-  for (int e = threadIdx.x; e < kGenRows * dim; e += kGenRows) {
-    const int r = e / dim, c = e - r * dim;
-    As[c * kGenRows + r] = r < rows_a ? A[(size_t)i0 * dim + e] : 0.0;
-  }
   const long long lo = (long long)blockIdx.y * chunk;
   const long long hi = lo + chunk < (long long)n ? lo + chunk : (long long)n;
   double d0 = INFINITY, d1 = INFINITY; int j0 = -1, j1 = -1;
-  for (long long base = lo; base < hi; base += kGenTile) {
-    const int rows = (int)(hi - base < kGenTile ? hi - base : kGenTile);
-    __syncthreads();
-    for (int e = threadIdx.x; e < rows * dim; e += kGenRows) Bs[e] = B[(size_t)base * dim + e];
-    __syncthreads();
-    for (int r = 0; r < rows; ++r) {
-      const double* b = Bs + r * dim;
-      double s = 0.0;
-      for (int c = 0; c < dim; ++c) {
-        const double t = __dsub_rn(As[c * kGenRows + threadIdx.x], b[c]);
-        s = __dadd_rn(s, __dmul_rn(t, t));
-      }
-      offer(s, (int)(base + r), d0, j0, d1, j1);
-    }
-  }
+  scan_generic(A, m, i0, B, lo, hi, dim, As, Bs, d0, j0, d1, j1);
   if (live) { Best2* o = part + ((size_t)blockIdx.y * m + i); o->d0 = d0; o->d1 = d1; o->j0 = j0; o->j1 = j1; }
 }
 
@@ -120,12 +67,7 @@ __global__ __launch_bounds__(kThreads) void match_merge_kernel(const Best2* __re
   const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
   if (i >= rows) return;
   double d0 = INFINITY, d1 = INFINITY; int j0 = -1, j1 = -1;
-  for (int y = 0; y < chunks; ++y) {
-    const Best2* p = part + ((size_t)y * rows + i);
-    const double pd0 = p->d0, pd1 = p->d1; const int pj0 = p->j0, pj1 = p->j1;
-    if (pj0 >= 0) offer(pd0, pj0, d0, j0, d1, j1);
-    if (pj1 >= 0) offer(pd1, pj1, d0, j0, d1, j1);
-  }
+  merge_row(part, (size_t)rows, (size_t)i, chunks, d0, j0, d1, j1);
   idx[2 * i] = j0; idx[2 * i + 1] = j1;
   d2[2 * i] = d0; d2[2 * i + 1] = d1;
 }

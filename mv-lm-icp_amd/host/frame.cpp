@@ -125,6 +125,69 @@ int Session::computeOverlapNeighbours(std::vector<std::shared_ptr<Frame>>& frame
   return comps;
 }
 
+int Session::initFromFeatures(std::vector<std::shared_ptr<Frame>>& frames, const FeatureInit& o, std::vector<FeatureEdge>* edges_out) {
+  const int K = (int)frames.size();
+  if (edges_out) edges_out->clear();
+  if (K < 1) return 0;
+  // the clouds that carry the features: the frames themselves or their voxel copies
+  std::vector<std::shared_ptr<Frame>> feat;
+  if (o.voxel > 0.0) {
+    ensure_uploaded(frames);   // (voxelDownsample then finds every frame in the session)
+    for (auto& f : frames) feat.push_back(f->voxelDownsample(o.voxel));
+  }
+  std::vector<std::shared_ptr<Frame>>& carry = o.voxel > 0.0 ? feat : frames;
+  ensure_uploaded(carry);
+  std::vector<long long> offsets((size_t)K + 1, 0);
+  for (int i = 0; i < K; ++i) offsets[i + 1] = offsets[i] + (long long)carry[i]->pts.size();
+  const size_t total = (size_t)offsets[K];
+  std::vector<double> desc(33 * total), xyz(3 * total);
+  for (int i = 0; i < K; ++i) {
+    const size_t n = carry[i]->pts.size();
+    if (n) std::memcpy(&xyz[3 * (size_t)offsets[i]], carry[i]->pts[0].data(), 24 * n);
+    const long long got = mvicp_fpfh(ctx, i, o.radius, o.max_nn);
+    if (got < 0) check((int)got);
+    if (n) check(mvicp_fpfh_fetch(ctx, (long long)n, &desc[33 * (size_t)offsets[i]], nullptr));
+  }
+  std::vector<int> src, dst;
+  for (int i = 0; i < K; ++i)
+    for (int j = i + 1; j < K; ++j) { src.push_back(i); dst.push_back(j); }
+  const int E = (int)src.size();
+  std::vector<unsigned long long> seeds((size_t)E);
+  for (int e = 0; e < E; ++e) seeds[e] = o.seed + (unsigned long long)e;
+  std::vector<mvicp_coarse_edge> res((size_t)E);
+  const long long st = mvicp_coarse_pairs(ctx, desc.data(), xyz.data(), offsets.data(), K, 33, E, src.data(), dst.data(), seeds.data(), 1, 1.0, o.hypotheses, o.tau,
+                                          o.edge_sim, res.data());
+  if (st < 0) check((int)st);
+  std::vector<int> count((size_t)E);
+  std::vector<double> pose(16 * (size_t)E);
+  for (int e = 0; e < E; ++e) {
+    count[e] = res[e].count;
+    std::memcpy(&pose[16 * (size_t)e], res[e].pose, 128);
+    if (o.refine && res[e].count >= 3) {
+      const size_t c = (size_t)res[e].pairs;
+      std::vector<int> pairs(2 * c);
+      std::vector<unsigned char> flags(c);
+      check(mvicp_coarse_pairs_fetch(ctx, e, (long long)c, pairs.data(), flags.data()));
+      std::vector<double> P, Q;
+      for (size_t k = 0; k < c; ++k)
+        if (flags[k]) {
+          const double* p = &xyz[3 * ((size_t)offsets[src[e]] + (size_t)pairs[2 * k])];
+          const double* q = &xyz[3 * ((size_t)offsets[dst[e]] + (size_t)pairs[2 * k + 1])];
+          P.insert(P.end(), p, p + 3); Q.insert(Q.end(), q, q + 3);
+        }
+      check(mvicp_closedform_point_to_point(P.data(), Q.data(), (int)(P.size() / 3), &pose[16 * (size_t)e]));
+    }
+    if (edges_out) edges_out->push_back(FeatureEdge{src[e], dst[e], res[e].pairs, res[e].accepted, res[e].count});
+  }
+  std::vector<double> out(16 * (size_t)K);
+  const int comps = mvicp_poses_from_pairs(K, E, src.data(), dst.data(), count.data(), pose.data(), o.min_count, 0, frames[0]->pose.data(), out.data(), nullptr,
+                                           nullptr, nullptr);
+  check(comps);
+  for (int i = 1; i < K; ++i) std::memcpy(frames[i]->pose.data(), &out[16 * (size_t)i], 128);
+  if (o.voxel > 0.0) invalidate();   // (the session holds the copies, which end here: the next bind uploads the frames)
+  return comps;
+}
+
 void Session::correspond(std::vector<std::shared_ptr<Frame>>& frames, float thresh) {
   bind(frames);
   std::vector<double> P(16 * frames.size());

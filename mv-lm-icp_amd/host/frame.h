@@ -125,6 +125,21 @@ struct Session {
   // (weight = 1 - fraction of the frame's samples with a counterpart within thresh) and returns the number of connected components.
   // More than one component is reported, not repaired: frames cut off from frame 0 make the solve singular.
   int computeOverlapNeighbours(std::vector<std::shared_ptr<Frame>>& frames, int knn, float thresh, int max_samples = 4096, double min_fraction = 0.0);
+  // Initial poses from the clouds alone (no counterpart in the reference, which starts from pose files): FPFH descriptors of every frame
+  // (mvicp_fpfh; of its voxelDownsample(voxel) copy when voxel > 0), ONE mvicp_coarse_pairs over all edges i < j with seeds[e] = seed + e,
+  // mutual matches, no ratio test; with `refine` mvicp_closedform_point_to_point over each edge's inliers (when there are at least 3);
+  // mvicp_poses_from_pairs over the inlier counts from root 0 at frames[0]->pose.  Writes frames[i]->pose for i >= 1 and returns the
+  // number of components (more than one is reported, not repaired: a frame no usable edge reaches stands at the identity).  `edges`
+  // receives one record per edge.  The frames need normals.
+  struct FeatureInit {
+    double voxel = 0.0, radius = 0.0, tau = 0.0, edge_sim = 0.9;
+    int max_nn = 64, min_count = 3;
+    long long hypotheses = 10000;
+    unsigned long long seed = 0;
+    bool refine = true;
+  };
+  struct FeatureEdge { int src, dst, pairs, accepted, inliers; };
+  int initFromFeatures(std::vector<std::shared_ptr<Frame>>& frames, const FeatureInit& opts, std::vector<FeatureEdge>* edges = nullptr);
   void correspond(std::vector<std::shared_ptr<Frame>>& frames, float thresh);
   void optimize(std::vector<std::shared_ptr<Frame>>& frames, int param, bool pointToPlane, bool robust, mvicp_summary* sm = nullptr);
   void reset();

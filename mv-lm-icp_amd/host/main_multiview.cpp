@@ -28,7 +28,15 @@
 // coarse level, by Frame::removeOutliers(K, A, R): the statistical rule over the K nearest neighbours (A < 0, the default without --sor_ratio
 // when only a radius is given: off; --sor_ratio alone defaults to 2) and / or the radius rule (at least K neighbours within R; R <= 0: off).
 // One line per frame, `outlier filter: frame i kept a of b` (printed with --quiet too).
+// --init features: the initial poses of frames 1 .. K-1 come from the clouds alone (Session::initFromFeatures, after loadFrames and before the
+// graph is built; frame 0 keeps its loaded pose): FPFH descriptors, one batched matching + consensus over all frame pairs, a spanning tree
+// over the inlier counts.  --feat_voxel H (0 = the full clouds; otherwise Frame::voxelDownsample(H) copies carry the features),
+// --feat_radius (the FPFH radius; default 5 H), --feat_max_nn (64), --feat_tau (the inlier distance; default 1.5 H), --feat_hyp (10000),
+// --feat_edge_sim (0.9), --feat_min_count (3: the fewest inliers that make an edge usable), --feat_seed (0), --feat_refine (default on:
+// each usable pose is refined over its inliers in closed form).  One line per edge, `feature init: edge i j pairs P accepted A inliers C`,
+// and one line `feature init: N component(s)` (printed with --quiet too).
 #include <chrono>
+#include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <iomanip>
@@ -97,6 +105,23 @@ int main(int argc, char** argv) {
       }
     } catch (const std::exception& ex) { std::cerr << ex.what() << std::endl; return 2; }
     return 0;
+  }
+  if (F.s("init", "") == "features") {
+    try {
+      Session::FeatureInit o;
+      o.voxel = F.f("feat_voxel", 0.0);
+      o.radius = F.f("feat_radius", 5.0 * o.voxel); o.tau = F.f("feat_tau", 1.5 * o.voxel);
+      o.max_nn = F.i("feat_max_nn", 64); o.min_count = F.i("feat_min_count", 3);
+      o.hypotheses = std::atoll(F.s("feat_hyp", "10000").c_str());
+      o.edge_sim = F.f("feat_edge_sim", 0.9);
+      o.seed = std::strtoull(F.s("feat_seed", "0").c_str(), nullptr, 10);
+      o.refine = F.b("feat_refine", true);
+      std::vector<Session::FeatureEdge> fe;
+      const int comps = Session::get().initFromFeatures(frames, o, &fe);
+      for (const Session::FeatureEdge& e : fe)
+        std::cout << "feature init: edge " << e.src << " " << e.dst << " pairs " << e.pairs << " accepted " << e.accepted << " inliers " << e.inliers << std::endl;
+      std::cout << "feature init: " << comps << " component(s)" << std::endl;
+    } catch (const std::exception& ex) { std::cerr << ex.what() << std::endl; return 2; }
   }
   frames[0]->fixed = true;
   const bool overlap_graph = F.s("graph", "pose") == "overlap";

@@ -21,6 +21,7 @@ SYMBOLS = [
     "mvicp_outlier_filter", "mvicp_outlier_fetch", "mvicp_outlier_threshold", "mvicp_cache_allowance",
     "mvicp_knn_search", "mvicp_knn_fetch", "mvicp_fpfh", "mvicp_fpfh_fetch",
     "mvicp_feature_match", "mvicp_feature_match_fetch", "mvicp_match_pairs", "mvicp_consensus", "mvicp_consensus_fetch",
+    "mvicp_coarse_pairs", "mvicp_coarse_pairs_fetch", "mvicp_poses_from_pairs",
 ]
 
 # names of mvicp_get_structure (include/mvicp.h)
@@ -52,6 +53,10 @@ class OutlierStats(C.Structure):
 
 class ConsensusResult(C.Structure):
     _fields_ = [("best", C.c_int), ("count", C.c_int), ("accepted", C.c_int), ("reserved", C.c_int), ("pose", C.c_double * 16)]
+
+
+class CoarseEdge(C.Structure):
+    _fields_ = [("pairs", C.c_int), ("best", C.c_int), ("count", C.c_int), ("accepted", C.c_int), ("pose", C.c_double * 16)]
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_size_t)
@@ -136,6 +141,11 @@ def load_library(path=None):
     lib.mvicp_match_pairs.restype = C.c_longlong
     lib.mvicp_consensus.argtypes = [vp, vp, vp, C.c_longlong, C.c_longlong, C.c_ulonglong, C.c_double, C.c_double, C.POINTER(ConsensusResult)]
     lib.mvicp_consensus_fetch.argtypes = [vp, C.c_longlong, vp, C.c_longlong, vp]
+    lib.mvicp_coarse_pairs.argtypes = [vp, vp, vp, llp, C.c_int, C.c_int, C.c_int, ip, ip, C.POINTER(C.c_ulonglong), C.c_int, C.c_double,
+                                       C.c_longlong, C.c_double, C.c_double, C.POINTER(CoarseEdge)]
+    lib.mvicp_coarse_pairs.restype = C.c_longlong
+    lib.mvicp_coarse_pairs_fetch.argtypes = [vp, C.c_int, C.c_longlong, vp, vp]
+    lib.mvicp_poses_from_pairs.argtypes = [C.c_int, C.c_int, ip, ip, ip, dp, C.c_int, C.c_int, dp, dp, ip, ip, ip]
     if path is None:
         _lib = lib
     return lib
@@ -307,6 +317,69 @@ def coarse_align(eng, src_frame, dst_frame, src_xyz, dst_xyz, radius, max_nn=64,
     keep = cons["flags"] != 0
     out["refined"] = closedform_point_to_point(P[keep], Q[keep]) if cons["count"] >= 3 else cons["pose"].copy()
     return out
+
+
+def poses_from_pairs(n_frames, src, dst, count, pose, min_count=0, root=0, root_pose=None):
+    """mvicp_poses_from_pairs: initial poses (frame -> world) from pairwise poses.  pose[e] (4, 4) maps coordinates of frame src[e] into
+    those of dst[e]; edge e is usable iff count[e] >= min_count.  A maximum spanning forest from `root` (Prim: the largest count, the
+    lowest e among equals); a frame no usable edge reaches starts a component of its own at the identity.
+    -> dict(poses (K,4,4), parent (K,), parent_edge (K,), component (K,), components).  Host only."""
+    lib = load_library()
+    src = np.ascontiguousarray(src, dtype=np.int32).reshape(-1); dst = np.ascontiguousarray(dst, dtype=np.int32).reshape(-1)
+    count = np.ascontiguousarray(count, dtype=np.int32).reshape(-1)
+    E = len(src)
+    if len(dst) != E or len(count) != E:
+        raise ValueError("src, dst and count differ in length")
+    T = poses_to_c(np.asarray(pose, dtype=np.float64).reshape(E, 4, 4)) if E else np.zeros((1, 16))
+    K = int(n_frames)
+    out = np.zeros((max(K, 1), 16)); parent = np.zeros(max(K, 1), dtype=np.int32); pedge = np.zeros(max(K, 1), dtype=np.int32)
+    comp = np.zeros(max(K, 1), dtype=np.int32)
+    rp = None if root_pose is None else poses_to_c(np.asarray(root_pose, dtype=np.float64).reshape(1, 4, 4))
+    spare = np.zeros(1, dtype=np.int32)   # (an empty array still gets a pointer that is not NULL)
+    ip = lambda a: _ip(a if a.size else spare)
+    nc = _check(lib, lib.mvicp_poses_from_pairs(K, E, ip(src), ip(dst), ip(count), _dp(T), int(min_count), int(root), None if rp is None else _dp(rp),
+                                                _dp(out), _ip(parent), _ip(pedge), _ip(comp)))
+    return {"poses": poses_from_c(out[:K]), "parent": parent[:K].copy(), "parent_edge": pedge[:K].copy(), "component": comp[:K].copy(),
+            "components": int(nc)}
+
+
+def init_from_clouds(eng, frames, xyz_list, radius, tau, max_nn=64, edges=None, hypotheses=10000, seed=0, edge_sim=0.9, mutual=True, ratio=1.0,
+                     min_count=3, root=0, refine=True):
+    """Initial poses of a multiview problem from the clouds alone: Engine.fpfh(device=True) of every frame of `frames` -> ONE
+    Engine.coarse_pairs over `edges` (pairs (i, j) of positions in `frames`; default: all i < j; seeds[e] = seed + e) -> with `refine`,
+    closedform_point_to_point over each edge's inliers in ascending pair order (when there are at least 3) -> poses_from_pairs over the
+    inlier counts.  xyz_list: the stored clouds of the frames as numpy arrays.
+    -> dict(poses (K,4,4), edges (E,2), records = per edge dict(pairs, accepted, inliers, best, pose, refined), parent, parent_edge,
+    component, components)."""
+    import torch
+    K = len(frames)
+    if len(xyz_list) != K:
+        raise ValueError("xyz_list must hold one cloud per frame")
+    if edges is None:
+        edges = [(i, j) for i in range(K) for j in range(i + 1, K)]
+    edges = np.ascontiguousarray(edges, dtype=np.int32).reshape(-1, 2)
+    clouds = [np.ascontiguousarray(x, dtype=np.float64).reshape(-1, 3) for x in xyz_list]
+    descs = [eng.fpfh(f, radius, max_nn, device=True)["desc"] for f in frames]
+    for d, x in zip(descs, clouds):
+        if d.shape[0] != len(x):
+            raise ValueError("xyz_list does not hold the clouds of the frames")
+    offsets = np.concatenate([[0], np.cumsum([len(x) for x in clouds])]).astype(np.int64)
+    desc = torch.cat(descs, 0) if K else torch.zeros((0, 33), dtype=torch.float64, device=torch.device("cuda", eng.device))
+    xyz = np.ascontiguousarray(np.concatenate(clouds, 0)) if K else np.zeros((0, 3))
+    res = eng.coarse_pairs(desc, xyz, offsets, edges[:, 0], edges[:, 1], seed, mutual=mutual, ratio=ratio, hypotheses=hypotheses, tau=tau, edge_sim=edge_sim)
+    records, used = [], []
+    for e, (i, j) in enumerate(edges):
+        rec = {"pairs": int(res["pairs"][e]), "accepted": int(res["accepted"][e]), "inliers": int(res["count"][e]), "best": int(res["best"][e]),
+               "pose": res["pose"][e].copy(), "refined": res["pose"][e].copy()}
+        if refine and rec["inliers"] >= 3:
+            pr, fl = eng.coarse_pairs_fetch(e)
+            keep = fl != 0
+            rec["refined"] = closedform_point_to_point(clouds[i][pr[keep, 0]], clouds[j][pr[keep, 1]])
+        records.append(rec)
+        used.append(rec["refined"] if refine else rec["pose"])
+    tree = poses_from_pairs(K, edges[:, 0], edges[:, 1], res["count"], np.array(used).reshape(-1, 4, 4), min_count, root)
+    tree.update(edges=edges, records=records)
+    return tree
 
 
 def lm_solve_host(n_frames, src, dst, poses, fixed, param, eval_callback, max_iterations=50):
@@ -743,6 +816,61 @@ class Engine:
         _check(self.lib, self.lib.mvicp_consensus_fetch(self.h, len(counts), counts.ctypes.data_as(C.c_void_p), c, flags.ctypes.data_as(C.c_void_p)))
         return {"best": int(res.best), "count": int(res.count), "accepted": int(res.accepted), "pose": poses_from_c(np.array(res.pose[:]))[0],
                 "counts": counts, "flags": flags}
+
+    def coarse_pairs(self, desc, xyz, offsets, src, dst, seeds=None, mutual=True, ratio=1.0, hypotheses=10000, tau=None, edge_sim=0.9):
+        """mvicp_coarse_pairs: for every edge (src[e], dst[e]) over the sets whose rows are offsets[s] .. offsets[s+1] of desc (total, dim)
+        and xyz (total, 3) the chain feature_match -> match_pairs(mutual, ratio) -> gather -> consensus(hypotheses, seeds[e], tau, edge_sim)
+        in one call, the same bytes as the chain of single calls.  desc / xyz: numpy arrays or float64 torch tensors on the engine's GPU.
+        seeds: one per edge, or None / an int s for seeds[e] = s + e mod 2^64.
+        -> dict(pairs, best, count, accepted: (E,) int32; pose (E,4,4)).  Needs no frame and no graph; history-neutral."""
+        if tau is None:
+            raise ValueError("coarse_pairs needs tau, the inlier distance of the consensus")
+        kd, pd, rows = self._rows_operand(desc, 0, "desc")
+        kx, px, rows_x = self._rows_operand(xyz, 3, "xyz")
+        if rows != rows_x:
+            raise MvicpError(f"desc has {rows} rows, xyz {rows_x}")
+        off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        if len(off) < 2 or int(off[-1]) != rows:
+            raise MvicpError("offsets must hold n_sets + 1 values and end at the number of rows")
+        src = np.ascontiguousarray(src, dtype=np.int32).reshape(-1); dst = np.ascontiguousarray(dst, dtype=np.int32).reshape(-1)
+        E = len(src)
+        if len(dst) != E:
+            raise MvicpError("src and dst differ in length")
+        if seeds is None or isinstance(seeds, (int, np.integer)):
+            s0 = 0 if seeds is None else int(seeds)
+            sd = np.array([(s0 + e) & (2 ** 64 - 1) for e in range(E)], dtype=np.uint64)
+        else:
+            sd = np.array([int(v) & (2 ** 64 - 1) for v in seeds], dtype=np.uint64)
+            if len(sd) != E:
+                raise MvicpError("one seed per edge")
+        res = (CoarseEdge * max(E, 1))()
+        spare = np.zeros(1, dtype=np.int64)   # (an empty array still gets a pointer that is not NULL)
+        ip = lambda a: (a if a.size else spare).ctypes.data_as(C.POINTER(C.c_int))
+        got = int(_check(self.lib, self.lib.mvicp_coarse_pairs(self.h, pd, px, off.ctypes.data_as(C.POINTER(C.c_longlong)), len(off) - 1, int(kd.shape[1]), E,
+                                                               ip(src), ip(dst), (sd if E else spare).ctypes.data_as(C.POINTER(C.c_ulonglong)),
+                                                               int(bool(mutual)), float(ratio), int(hypotheses), float(tau), float(edge_sim), res)))
+        assert got == E
+        self._coarse_counts = [int(res[e].pairs) for e in range(E)]
+        out = {k: np.array([getattr(res[e], k) for e in range(E)], dtype=np.int32) for k in ("pairs", "best", "count", "accepted")}
+        out["pose"] = poses_from_c(np.array([res[e].pose[:] for e in range(E)]).reshape(-1, 16)) if E else np.zeros((0, 4, 4))
+        return out
+
+    def coarse_pairs_fetch(self, edge, device=False):
+        """mvicp_coarse_pairs_fetch: edge `edge` of the last coarse_pairs -> (pairs (c,2) int32 in ascending i, flags (c,) uint8 = the
+        winner's inliers).  device=True: torch tensors on the engine's GPU."""
+        counts = getattr(self, "_coarse_counts", None)
+        c = counts[edge] if counts is not None and 0 <= int(edge) < len(counts) else 0
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            pairs, flags = torch.zeros((c, 2), dtype=torch.int32, device=dev), torch.zeros((c,), dtype=torch.uint8, device=dev)
+            torch.cuda.synchronize(dev)   # (the allocations are the caller's; the library fills them on its own stream and waits)
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if t.numel() else None
+        else:
+            pairs, flags = np.zeros((c, 2), dtype=np.int32), np.zeros(c, dtype=np.uint8)
+            ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
+        _check(self.lib, self.lib.mvicp_coarse_pairs_fetch(self.h, int(edge), c, ptr(pairs), ptr(flags)))
+        return pairs, flags
 
     def nn_query(self, frame, queries, nn_method=NN_AUTO):
         q = np.ascontiguousarray(queries, dtype=np.float64)
