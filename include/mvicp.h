@@ -483,7 +483,8 @@ int mvicp_wait_correspondences(mvicp_ctx* ctx, int edge);
  * refill while (*epochs)[e] == x).  An edge keeps its epoch across an mvicp_correspond iff its list is PROVABLY last search's bit for bit — same
  * cutoff, both poses bit-identical, searched then and now (a search is a pure function of these) — e.g. every edge in the rounds after the
  * registration has converged; then mvicp_map_correspondences returns the buffer it already holds without any device work.  Every other event
- * (a search with different inputs, mvicp_set_correspondences, mvicp_reset_history, a failed search) gives the edge a new, never repeated epoch.
+ * (a search with different inputs, mvicp_set_correspondences, mvicp_reset_history, a change of the "tie_rule" option, a failed search — ANY
+ * mvicp_correspond that does not return MVICP_OK drops the whole cross-round state, as mvicp_reset_history does) gives the edge a new, never repeated epoch.
  * *epochs -> n_edges counters owned by the library, valid until mvicp_set_graph / mvicp_destroy. */
 int mvicp_correspondence_epochs(mvicp_ctx* ctx, const unsigned long long** epochs);
 /* Install an explicit list (pairwise known-correspondence case, main_pairwise.cpp:60-61; tests). */
@@ -561,7 +562,10 @@ int mvicp_closedform_point_to_plane(const double* src, const double* dst, const 
  * tile makes the wave confirm nearest-first and screen the tile again; "mfma_lbt" (0/1, default 1): launches without any seed test a tile's box per
  * lane before screening it; "nn_search_factor" (default 4; 0 = unbounded): the kernels look for a neighbour within this many cutoffs (a query the
  * cutoff rejects keeps a seed and a temporal-cache bound; results are filtered by the cutoff afterwards, like the reference); "tie_rule" (0/1,
- * default 1): exact distance ties are decided the way nanoflann decides them (first visited target; 0 = lowest original index); "tie_lazy" (0/1, default 1;
+ * default 1): exact distance ties are decided the way nanoflann decides them (first visited target; 0 = lowest original index).  The rule is an INPUT of a
+ * search: changing it drops the cross-round state and gives every edge a new epoch, like mvicp_reset_history.  The fix-up walks nanoflann's own tree
+ * over the target, of any depth up to 16384 levels (a cloud whose coordinates form a geometric progression has one level per point; ordinary clouds
+ * have 20-40); a deeper tree makes the call that needs it return MVICP_ERR_ARG — such a cloud can only be searched with "tie_rule" 0; "tie_lazy" (0/1, default 1;
  * single rank only, read at mvicp_set_graph): the reference-equivalent trees that decide ties are built when a search first reports a tie on a target
  * without one — that search is then repeated once — like the reference's own lazily built index (frame.cpp:188-193); 0 = built for every target at mvicp_set_graph; "sel_bracket" (0/1, default 1): one-pass median select around last round's median
  * once it has settled; "sel_reuse" (0/1, default 1; single rank): a search in which no list can change (every transform bit-identical to the last search's, every list

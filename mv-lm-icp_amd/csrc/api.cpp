@@ -564,6 +564,7 @@ int mvicp_destroy(mvicp_ctx* c) try {
   if (c->h_census) (void)hipHostFree(c->h_census);
   if (c->d_tie_list) (void)hipFree(c->d_tie_list);
   if (c->d_tie_count) (void)hipFree(c->d_tie_count);
+  if (c->d_tie_deep) (void)hipFree(c->d_tie_deep);
   if (c->h_tie_seen) (void)hipHostFree(c->h_tie_seen);
   if (c->h_far_seen) (void)hipHostFree(c->h_far_seen);
   if (c->d_far_list) (void)hipFree(c->d_far_list);
@@ -1503,12 +1504,13 @@ int mvicp_reset_history(mvicp_ctx* c) try {
 
 // mvicp_correspond — cross-round state at a glance.  A search is a PURE FUNCTION of (clouds, graph, poses, fixed mask, cutoff): every field below
 // only decides HOW FAST the same answer is found, and tests/test_gpu_parity.py::test_correspond_regime_transitions_match_a_fresh_context checks
-// after every round of randomly perturbed registrations that the answer equals a fresh context's.  mvicp_reset_history / a poisoned exchange
-// (forget_history) drop all of it.
+// after every round of randomly perturbed registrations that the answer equals a fresh context's.  mvicp_reset_history, a search that does not
+// return OK (mvicp_correspond's Forget guard: every error return below, an exception, a poisoned exchange) and a change of the "tie_rule" option
+// (forget_history) drop all of it — "reset" in the last column stands for all three (tests/test_gpu_search_state.py).
 //   field (common.h)              written by                               read by / meaning                                    invalidated by
 //   nn_cache_valid, _thresh       this call's end (grid / BND tile round)  temporal cache may be consulted next search          cutoff change, set_correspondences, options, reset
 //   nn_cache_edge[e]              this call's end (= active mask)          edge e was searched last time: seeds + bounds usable   fixed-mask change (per edge), reset
-//   prev_q / prev_xf[e]           the per-edge loop below                  dM, dv of the temporal cache; bit-identical transform  every search rewrites them
+//   prev_q / prev_xf[e]           the per-edge loop below                  dM, dv of the temporal cache; bit-identical transform  every search rewrites them; a search that does not return OK, reset
 //   list_valid[e], explicit_list  end of the NN stage / set_correspondences  the edge's compacted list may be maintained in place  set_correspondences, recompute_normals (dst), reset
 //   sel_med1/2[e]                 after the wait below                     one-pass bracket select once the median has settled   inactive edge, set_correspondences, reset
 //   sel_result_valid, _armed      this call's end (single rank)            no select launch in a search in which no list can change   any search that does not return OK, set_graph, set_correspondences, reset
@@ -1525,9 +1527,14 @@ static int correspond_once(mvicp_ctx* c, const double* poses, const unsigned cha
 
 int mvicp_correspond(mvicp_ctx* c, const double* poses, const unsigned char* fixed, float thresh, int nn_method, int* counts, float* weights) try {
   MV_CHECK(bind(c));
+  // A search that does not return OK — an argument error, a failed launch, an exception — may have got as far as overwriting prev_xf / prev_q with
+  // transforms that were never searched, while seeds, bounds, lists and the cache flags still describe the last search that succeeded.  Nothing of that
+  // mixture may meet the next search: whatever way this call ends other than OK, the cross-round state is dropped (host bookkeeping, after the stream
+  // has drained) and every edge gets a new epoch — the next search is a first search.
+  struct Forget { mvicp_ctx* c; bool ok = false; ~Forget() { if (!ok) { (void)hipStreamSynchronize(c->stream); forget_history(c); } } } forget{c};
   bool unresolved = false;
   MV_CHECK(correspond_once(c, poses, fixed, thresh, nn_method, counts, weights, &unresolved));
-  if (!unresolved) return MVICP_OK;
+  if (!unresolved) { forget.ok = true; return MVICP_OK; }
   // Lazy tie trees (single rank): the search reported an exact distance tie on a target whose reference-equivalent tree does not exist yet, so that
   // query still carries the kernels' own rule (lowest index).  Build the trees of every searched target now — once per cloud, like the reference's
   // lazily built index — forget what this search left behind and search again: this time the fix-up decides the ties the way nanoflann does.
@@ -1539,6 +1546,7 @@ int mvicp_correspond(mvicp_ctx* c, const double* poses, const unsigned char* fix
   unresolved = false;
   MV_CHECK(correspond_once(c, poses, fixed, thresh, nn_method, counts, weights, &unresolved));
   if (unresolved) { set_error("tie fix-up still without a tree after building them"); return MVICP_ERR_INTERNAL; }
+  forget.ok = true;
   return MVICP_OK;
 } MVICP_GUARD_ABI
 
@@ -1862,6 +1870,7 @@ static int correspond_body(mvicp_ctx* c, const double* poses, const unsigned cha
   // what THIS search's tie fix-up / far launch reported (a skipped launch keeps last search's zero): the next search's skip decisions
   if (tie_launched) c->corr_tie_seen = c->h_tie_seen ? *c->h_tie_seen : 1u;
   if (tie_launched && c->h_tie_seen && c->h_tie_seen[1] != 0u) *tie_unresolved = true;
+  if (tie_launched && c->h_tie_seen && c->h_tie_seen[2] != 0u) { set_error("tie fix-up: a walk ran out of stack (a tree deeper than its recorded levels)"); return MVICP_ERR_INTERNAL; }
   if (far_launched) c->corr_far_seen = c->h_far_seen ? *c->h_far_seen : 1u;
   else if (method != MVICP_NN_GRID) c->corr_far_seen = 1u;
   mark("host.corr.wait");
@@ -2104,6 +2113,7 @@ int mvicp_nn_query(mvicp_ctx* c, int frame, const double* queries, int n, int nn
   if (st == MVICP_OK) {
     hipError_t e1 = hipStreamSynchronize(c->stream);
     if (e1 == hipSuccess) census_resolve(c);
+    if (e1 == hipSuccess && c->tie_rule && c->h_tie_seen && c->h_tie_seen[2] != 0u) { set_error("tie fix-up: a walk ran out of stack (a tree deeper than its recorded levels)"); st = MVICP_ERR_INTERNAL; }
     hipError_t e2 = hipMemcpy(idx, di, sizeof(int) * n, hipMemcpyDeviceToHost);
     hipError_t e3 = hipMemcpy(d2, dd, sizeof(double) * n, hipMemcpyDeviceToHost);
     if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) { set_error("nn_query copy-back failed"); st = MVICP_ERR_HIP; }
@@ -2159,7 +2169,13 @@ int mvicp_set_option(mvicp_ctx* c, const char* name, double value) try {
   if (std::strcmp(name, "auto_switch") == 0) { c->auto_switch = value; return MVICP_OK; }
   if (std::strcmp(name, "nn_cell") == 0) { c->nn_cell = value != 0.0; return MVICP_OK; }
   if (std::strcmp(name, "nn_search_factor") == 0) { if (!(value >= 0.0)) { set_error("nn_search_factor < 0"); return MVICP_ERR_ARG; } c->nn_search_factor = value; c->nn_cache_valid = false; return MVICP_OK; }
-  if (std::strcmp(name, "tie_rule") == 0) { c->tie_rule = value != 0.0; return MVICP_OK; }
+  if (std::strcmp(name, "tie_rule") == 0) {
+    // the rule is an INPUT of every search (which target a tied query gets), not a tuning knob: a change drops what earlier searches left behind —
+    // lists, seeds, the "no tie was reported" memory, the exported copy — and gives every edge a new epoch, like mvicp_reset_history
+    const bool on = value != 0.0;
+    if (on != c->tie_rule) { MV_HIP(hipStreamSynchronize(c->stream)); c->tie_rule = on; forget_history(c); }
+    return MVICP_OK;
+  }
   if (std::strcmp(name, "tie_lazy") == 0) { c->tie_lazy = value != 0.0; return MVICP_OK; }   // takes effect at the next mvicp_set_graph
   if (std::strcmp(name, "tile_seed") == 0) { c->tile_seed = value != 0.0; return MVICP_OK; }
   if (std::strcmp(name, "tile_bounds") == 0) { c->tile_bounds = (int)value; return MVICP_OK; }

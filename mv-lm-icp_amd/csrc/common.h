@@ -105,7 +105,7 @@ struct FrameDev {
   double build_ms[2] = {0.0, -1.0};   // the last structure build of this slot: host wall ms (upload excluded), device ms of the device build (-1: host build)
   // the reference's own tree over this cloud (kdvisit.h: split structure of nanoflann's buildIndex, leaf_max_size 1): decides exact distance
   // ties the way the reference does (nn_tie.hip) and orders the k-NN lists of the normals (normals.hip); built on first use
-  void* tie_nodes = nullptr; int* tie_ord = nullptr; int* tie_slot = nullptr; double tie_box[6] = {0, 0, 0, 0, 0, 0}; bool has_tie = false;
+  void* tie_nodes = nullptr; int* tie_ord = nullptr; int* tie_slot = nullptr; double tie_box[6] = {0, 0, 0, 0, 0, 0}; bool has_tie = false; int tie_levels = 0;   // tie_levels: levels of the tree (build_visit_tree)
 };
 
 struct ProfEntry {
@@ -338,6 +338,7 @@ struct mvicp_ctx {
                                    // the eager build was most of cfg5's set-up time.  N > 1 ranks build them at mvicp_set_graph (a repeated search is a collective)
   bool tie_rule = true;            // exact distance ties are decided as nanoflann decides them (first visited; nn_tie.hip); false: lowest original index
   unsigned long long* d_tie_list = nullptr; size_t tie_cap = 0; unsigned int* d_tie_count = nullptr; int tie_parity = 0;   // queries reported by the NN kernels
+  void* d_tie_deep = nullptr; size_t tie_deep_bytes = 0;   // per-lane walk stacks of nn_tie_deep_kernel (targets whose tree has more levels than the per-lane array)
   unsigned int* h_tie_seen = nullptr; unsigned int* d_tie_seen = nullptr;   // mapped host word: reports of the last fix-up launch (read after the round's wait)
   unsigned int corr_tie_seen = 1u, corr_far_seen = 1u;   // what the LAST mvicp_correspond's own fix-up / far launch reported (read after its wait; 1 = unknown).
                                    // mvicp_nn_query runs the same launches and overwrites the mapped words, so the skip decisions below use these copies

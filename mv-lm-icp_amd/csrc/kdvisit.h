@@ -43,6 +43,7 @@ struct Box3 { double lo[3], hi[3]; };
 
 struct VisitBuilder {
   const double* xyz; std::vector<int> ord; std::vector<VisitNode> nodes;
+  int levels = 0;   // nodes on the longest root-to-leaf path (what divide's own stack reached)
   double at(int slot, int axis) const { return xyz[3 * (size_t)ord[slot] + axis]; }
   void range_of(int first, int count, int axis, double& mn, double& mx) const {
     mn = mx = at(first, axis);
@@ -103,6 +104,7 @@ struct VisitBuilder {
     int root = -1;
     while (!st.empty()) {
       Frame& f = st.back();
+      if ((int)st.size() > levels) levels = (int)st.size();
       if (f.stage == 0) {
         f.me = (int)nodes.size();
         if (root < 0) root = f.me;
@@ -143,6 +145,8 @@ struct VisitBuilder {
 
 }  // namespace kdv_detail
 
+// Returns the number of levels of the tree (nodes on its longest root-to-leaf path; 0 for n = 0): the exact search of tie_walk.h never
+// holds more pending subtrees than that.
 inline int build_visit_tree(const double* xyz, int n, std::vector<VisitNode>& nodes, std::vector<int>& slot) {
   kdv_detail::VisitBuilder B;
   B.xyz = xyz; B.ord.resize(n);
@@ -156,7 +160,7 @@ inline int build_visit_tree(const double* xyz, int n, std::vector<VisitNode>& no
   nodes.swap(B.nodes);
   slot.assign(n, 0);
   for (int s2 = 0; s2 < n; ++s2) slot[B.ord[s2]] = s2;
-  return 0;
+  return B.levels;
 }
 
 

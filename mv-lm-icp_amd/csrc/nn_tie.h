@@ -27,6 +27,7 @@ struct TieJob {
   const void* nodes; const int* ord; double box[6];   // the target's tree: kdvisit.h VisitNode[], slot -> original index, root bounding box
   const double* tpts;                                  // target points, ORIGINAL order
   const double* q; const double* xf; int n;
+  int levels;                                          // of the target's tree: above the per-lane stack of nn_tie_kernel the deep kernel answers
   int* out_idx; const double* out_d2; const int* inv;  // inv: target original index -> what out_idx holds (sorted position); null: original indices
   ListRef list;                                        // list.dirty == null: no list
   long long q_begin;                                   // prefix of n over the launch's jobs (the re-answer-everything mode)

@@ -7,12 +7,18 @@ select, list reuse) are taken per rank from exchanged data, and every rank's rec
 import numpy as np
 
 
-def script(seed, K, rounds=14):
-    """-> list of per-round event dicts (pure function of its arguments)."""
+KINDS = ["none", "none", "cutoff", "fixed", "reset", "method", "option", "hold", "hold"]
+# extended scripts: a search that FAILS before the round's search (an unknown nn_method, or an injected launch failure that every rank
+# meets: all of them enter the exchange poisoned), at poses of its own, and flips of the tie rule
+KINDS_EXTENDED = KINDS + ["fail", "fail", "tie_rule", "tie_rule"]
+
+
+def script(seed, K, rounds=14, extended=False):
+    """-> list of per-round event dicts (pure function of its arguments).  extended=False draws exactly the sequences it always drew."""
     rng = np.random.default_rng(4200 + seed)
     ev = []
     for rnd in range(rounds):
-        kind = str(rng.choice(["none", "none", "cutoff", "fixed", "reset", "method", "option", "hold", "hold"])) if rnd > 0 else "none"
+        kind = str(rng.choice(KINDS_EXTENDED if extended else KINDS)) if rnd > 0 else "none"
         e = {"kind": kind}
         if kind == "cutoff":
             e["cutoff"] = float(rng.choice([0.05, 0.02, 0.008]))
@@ -23,6 +29,9 @@ def script(seed, K, rounds=14):
         elif kind == "option":
             e["name"] = str(rng.choice(["list_reuse", "nn_cache", "sel_bracket", "tile_cache", "tile_seed", "tile_miss", "mfma_entry", "reject_cache"]))
             e["value"] = float(rng.integers(0, 2)) * (8.0 if e["name"] == "tile_miss" else 1.0)
+        elif kind == "fail":
+            e["inject"] = bool(rng.integers(0, 2)); e["frame"] = int(rng.integers(1, K)); e["shift"] = [float(v) for v in rng.normal(0.0, 2e-3, 3)]
+            e["retry_there"] = bool(rng.integers(0, 2))
         e["param"] = int(rng.integers(0, 3)); e["plane"] = int(rng.integers(0, 2)); e["robust"] = bool(rng.integers(0, 2))
         ev.append(e)
     return ev
@@ -32,7 +41,7 @@ def run(eng, pb, events):
     """Replays `events` on an engine that already holds the clouds and the graph.  -> list of (counts, weights-as-bytes, poses) per round."""
     poses = pb["init"].copy()
     fixed = pb["fixed"].copy()
-    cutoff, method = 0.05, 0
+    cutoff, method, rule = 0.05, 0, 1
     out = []
     for e in events:
         k = e["kind"]
@@ -46,8 +55,24 @@ def run(eng, pb, events):
             method = e["method"]
         elif k == "option":
             eng.set_option(e["name"], e["value"])
+        elif k == "tie_rule":
+            rule = 1 - rule
+            eng.set_option("tie_rule", rule)
+        elif k == "fail":
+            Pf = poses.copy()
+            Pf[e["frame"]][:3, 3] += np.array(e["shift"])
+            if e["inject"]:
+                eng.set_option("fault_inject", 1)
+            try:
+                eng.correspond(Pf, fixed, cutoff, method if e["inject"] else 99)
+            except RuntimeError:                              # (mvicp.MvicpError)
+                pass
+            else:
+                raise AssertionError("the scripted failing search did not fail")
+            if e["retry_there"]:
+                poses = Pf
         counts, weights = eng.correspond(poses, fixed, cutoff, method)
-        if k != "hold" and counts.sum() > 0:
+        if k not in ("hold", "fail") and counts.sum() > 0:
             poses, _ = eng.optimize(poses, fixed, e["param"], e["plane"], e["robust"], 50)
         out.append((counts.copy(), weights.tobytes(), poses.copy()))
     return out

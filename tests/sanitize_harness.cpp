@@ -13,6 +13,7 @@
 
 #include "../include/mvicp.h"
 #include "../mv-lm-icp_amd/csrc/kdvisit.h"
+#include "../mv-lm-icp_amd/csrc/tie_walk.h"
 
 // ---- what lm.cpp / closedform.cpp expect from the rest of the library (csrc/api.cpp) — host stand-ins ---------------------------------
 #include "../mv-lm-icp_amd/csrc/common.h"
@@ -200,7 +201,7 @@ static void tree_case(unsigned seed) {
         xyz[3 * (size_t)i + a] = v;
       }
     std::vector<mvicp::VisitNode> nodes; std::vector<int> slot;
-    mvicp::build_visit_tree(xyz.data(), n, nodes, slot);
+    const int levels = mvicp::build_visit_tree(xyz.data(), n, nodes, slot);
     CHECK((int)nodes.size() == 2 * n - 1);
     std::vector<char> seen(n, 0);
     for (int i = 0; i < n; ++i) { CHECK(slot[i] >= 0 && slot[i] < n && !seen[slot[i]]); seen[slot[i]] = 1; }
@@ -212,6 +213,29 @@ static void tree_case(unsigned seed) {
       before += ab;
     }
     std::printf("tree variant %d: %zu nodes, %d of 2000 pairs visited a-first\n", variant, nodes.size(), before);
+    if (variant == 2) {
+      // the 1-NN tie fix-up's walk (csrc/tie_walk.h, host-compiled) on the deep tree, with a stack of exactly the levels the builder reported: every
+      // point queried at itself finds distance 0 at a point with its own coordinates, and no walk runs out of stack
+      CHECK(levels > 128);
+      std::vector<int> ord(n);
+      for (int i = 0; i < n; ++i) ord[slot[i]] = i;
+      double box[6];
+      for (int a = 0; a < 3; ++a) box[a] = box[3 + a] = xyz[a];
+      for (int i = 1; i < n; ++i)
+        for (int a = 0; a < 3; ++a) { const double v = xyz[3 * (size_t)i + a]; if (v < box[a]) box[a] = v; if (v > box[3 + a]) box[3 + a] = v; }
+      const mvicp::TieTree W{nodes.data(), ord.data(), xyz.data(), box};
+      std::vector<mvicp::TiePending> st(levels);
+      int truncated = 0;
+      for (int i = 0; i < n; ++i) {
+        double d2 = -1.0;
+        const int j = mvicp::tie_walk(W, xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2], st.data(), levels, &d2);
+        CHECK(j >= 0 && j < n && d2 == 0.0 && xyz[3 * (size_t)j] == xyz[3 * (size_t)i]);
+        double e2 = -1.0;
+        if (mvicp::tie_walk(W, xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2], st.data(), 128, &e2) == mvicp::TIE_WALK_TRUNCATED) ++truncated;
+      }
+      CHECK(truncated > 0);   // (a 128-entry stack is not enough on this tree, and the walk says so)
+      std::printf("tie walk on variant 2: %d levels, %d of %d self queries would not fit a 128-entry stack\n", levels, truncated, n);
+    }
   }
 }
 

@@ -114,7 +114,7 @@ def _regime_worker(rank, world, port, out, seed, spec):
     eng.set_option("spec_eval", spec)
     eng.set_frames(pb["pts"], pb["nor"]); eng.set_graph(pb["src"], pb["dst"])
     eng.comm_set_callback(allreduce)
-    log = regime_seq.run(eng, pb, regime_seq.script(seed, 5))
+    log = regime_seq.run(eng, pb, regime_seq.script(seed, 5, extended=seed >= 100))
     eng.close()
     regime_seq.save(f"{out}.{rank}.npz", log)
     dist.barrier()
@@ -122,7 +122,7 @@ def _regime_worker(rank, world, port, out, seed, spec):
 
 
 @pytest.mark.timeout(600)
-@pytest.mark.parametrize("seed,spec", [(0, 1), (1, 1), (2, 0), (3, 1)])
+@pytest.mark.parametrize("seed,spec", [(0, 1), (1, 1), (2, 0), (3, 1), (100, 1)])   # seeds >= 100: extended scripts (failed searches, tie-rule flips)
 def test_regime_transitions_sharded_match_single_process(tmp_path, seed, spec):
     """mvicp_correspond's cross-round state (tie_skip / far_skip / spec_arm / bracket select / list reuse / AUTO policy) under a scripted
     registration that changes the cutoff, the fixed mask, the kernel method and options, resets the history and repeats poses — on TWO ranks
@@ -138,10 +138,12 @@ def test_regime_transitions_sharded_match_single_process(tmp_path, seed, spec):
     eng = mvicp.Engine(0)
     eng.set_option("spec_eval", spec)
     eng.set_frames(pb["pts"], pb["nor"]); eng.set_graph(pb["src"], pb["dst"])
-    events = regime_seq.script(seed, 5)
+    events = regime_seq.script(seed, 5, extended=seed >= 100)
     log = regime_seq.run(eng, pb, events)
     eng.close()
     kinds = [e["kind"] for e in events]
+    if seed >= 100:
+        assert "fail" in kinds and "tie_rule" in kinds, kinds
     assert len(set(kinds)) >= 4, kinds                                  # the script really mixes events
     for r in range(2):
         regime_seq.assert_equal(f"{out}.{r}.npz", log, (seed, spec, r, kinds))
