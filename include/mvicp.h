@@ -286,6 +286,54 @@ long long mvicp_fpfh(mvicp_ctx* ctx, int frame, double radius, int max_nn);
  * Errors: NULL context, cap_rows < n -> MVICP_ERR_ARG; no mvicp_fpfh before -> MVICP_ERR_STATE. */
 int mvicp_fpfh_fetch(mvicp_ctx* ctx, long long cap_rows, double* desc, int* used);
 
+/* ---- ISS keypoints (Zhong 2009), exactly specified ---------------------------------------------------------------------------------
+ * Intrinsic Shape Signatures of one stored cloud: the few per cent of its points whose neighbourhood varies in all three directions and
+ * whose smallest variance is a local maximum -- the stage between "normals" and "describe" that lets the descriptor match shrink by the
+ * square of that fraction while the descriptors keep their full-resolution neighbourhoods.  The result is a pure function of the stored
+ * bytes, bit for bit (tests/issref.py is the same definition in numpy and as a scalar loop).  All arithmetic is fp64, every operation
+ * rounded on its own, no fma; only + - x / sqrt, floor, comparisons and integer arithmetic occur:
+ *   Inputs     the stored cloud p_0 .. p_{n-1} of `frame` (the stored bytes, no pose; normals are not needed); both radii finite and in
+ *              [2^-300, 2^300]; gamma21 and gamma32 finite and > 0 (usually 0.975); 1 <= min_neighbors <= 1024.
+ *   N_r(i)     { j : sqrt(dist2(p_i, p_j)) < r }: the candidate set of a self-mode mvicp_knn_search row -- the same metric, the strict
+ *              predicate on the correctly rounded sqrt, the point itself and exact duplicates included.  c_i = |N_salient(i)|,
+ *              n_i = |N_nonmax(i)|.  Any c_i > 1024 -> MVICP_ERR_ARG, reported by this call; no result is left behind.
+ *   Moments    exact integers, so the order in which the neighbours are added is free.  salient_radius = f 2^e with f in [0.5, 1)
+ *              (frexp), q = 20 - e.  Per neighbour and component g = (int64) floor((p_j - p_i) * 2^q): the subtraction rounded, the
+ *              scaling a multiplication by the double 2^q; |g| <= 2^20 + 1.  m_a = sum g_a, S_ab = sum g_a g_b,
+ *              D_ab = c_i S_ab - m_a m_b; every integer stays below 2^62 in magnitude (c_i <= 2^10 gives c_i S_ab < 2^61 and
+ *              |m_a m_b| < 2^62; D is c_i^2 times a covariance, so |D_ab| <= max_a c_i S_aa).
+ *              C_ab = (double)D_ab / (double)(c_i c_i): one round-to-nearest-even conversion, an exact divisor, one division.
+ *   Eigenvalues  A = the full 3 x 3 matrix of C.  Exactly 6 sweeps, no early exit, each over (p, q) = (0,1), (0,2), (1,2) in that order.
+ *              A rotation is skipped iff A[p][q] == 0; otherwise theta = (A[q][q] - A[p][p]) / (2.0 * A[p][q]),
+ *              t = (theta >= 0 ? 1.0 : -1.0) / (|theta| + sqrt(theta * theta + 1.0)), c = 1.0 / sqrt(t * t + 1.0), s = t * c; for r = 0, 1,
+ *              2: (A[r][p], A[r][q]) <- (c * A[r][p] - s * A[r][q], s * A[r][p] + c * A[r][q]); then for r = 0, 1, 2:
+ *              (A[p][r], A[q][r]) <- (c * A[p][r] - s * A[q][r], s * A[p][r] + c * A[q][r]).  l1 >= l2 >= l3 = the diagonal, sorted.
+ *   Saliency   i is salient iff c_i >= min_neighbors, l2 < gamma21 * l1, l3 < gamma32 * l2 and l3 > 0; saliency[i] = l3 * 2^(-2q) (a
+ *              multiplication by that double), +0.0 otherwise.
+ *   Keypoints  i is a keypoint iff saliency[i] > 0, n_i >= min_neighbors and no j in N_nonmax(i) beats it; j beats i iff
+ *              saliency[j] > saliency[i], or saliency[j] == saliency[i] and j < i (the lowest index wins a tie: exact duplicates give
+ *              one keypoint).
+ * idx holds the keypoints as ORIGINAL indices, ascending; saliency, cnt_salient (c_i) and cnt_nms (n_i) have n entries, by original index.
+ * n = 0 gives no keypoint and is not an error.  The call is HISTORY-NEUTRAL like mvicp_knn_search, needs the frame's hash structure (waits
+ * for pending builds and reports a failed one the same way) and NO graph; with several ranks every rank computes it locally.  It returns
+ * when the result is complete; the result lives in library-owned device memory of its own (the last results of mvicp_knn_search,
+ * mvicp_fpfh, mvicp_feature_match, mvicp_consensus and mvicp_coarse_pairs are left untouched) until the next mvicp_iss_keypoints,
+ * mvicp_set_num_frames or mvicp_destroy.  Profile scopes: "iss_moments", "iss_nms", "iss_compact".
+ * RETURNS THE NUMBER OF KEYPOINTS (>= 0) or a negative mvicp_status.
+ * Errors: NULL context, a radius outside [2^-300, 2^300] or not finite, a gamma that is not finite or <= 0, min_neighbors outside
+ * [1, 1024], a frame index out of range -> MVICP_ERR_ARG, decided before the context is touched (earlier results stay); a frame never
+ * uploaded -> MVICP_ERR_STATE. */
+long long mvicp_iss_keypoints(mvicp_ctx* ctx, int frame, double salient_radius, double non_max_radius, double gamma21, double gamma32,
+                              int min_neighbors);
+/* Copies the last result: idx (k ints), xyz and nrm (k x 3 doubles: the stored rows at idx), saliency (n doubles), cnt_salient and cnt_nms
+ * (n ints); each may be NULL; each may be a HOST pointer or a DEVICE pointer of the context's device, decided per pointer as
+ * mvicp_voxel_fetch decides.  cap_keys = keypoints the first three hold, cap_n = points the last three hold; each is looked at only
+ * when one of its destinations is given.
+ * Errors: NULL context, a cap too small -> MVICP_ERR_ARG; no mvicp_iss_keypoints before, nrm asked of a frame without normals ->
+ * MVICP_ERR_STATE. */
+int mvicp_iss_fetch(mvicp_ctx* ctx, long long cap_keys, int* idx, double* xyz, double* nrm, long long cap_n, double* saliency, int* cnt_salient,
+                    int* cnt_nms);
+
 /* ---- Descriptor matching and a consensus coarse pose, exactly specified -------------------------------------------------------
  * The stage that turns two sets of descriptors into a coarse pose: two device stages, one host rule between them.  Each result is a
  * pure function of the input bytes, bit for bit (tests/matchref.py is the same definition in numpy and as a scalar loop).  All

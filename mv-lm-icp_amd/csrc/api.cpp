@@ -559,6 +559,7 @@ int mvicp_destroy(mvicp_ctx* c) try {
   free_match(c);
   free_consensus(c);
   free_coarse(c);
+  free_iss(c);
   for (auto& kv : c->tables) if (kv.second.d) (void)hipFree(kv.second.d);
   if (c->d_census) (void)hipFree(c->d_census);
   if (c->h_census) (void)hipHostFree(c->h_census);
@@ -590,6 +591,7 @@ int mvicp_set_num_frames(mvicp_ctx* c, int n_frames) try {
   free_match(c);   // (and the last matches)
   free_consensus(c); // (and the last consensus)
   free_coarse(c);    // (and the last batched coarse poses)
+  free_iss(c);       // (and the last keypoints)
   for (FrameDev& f : c->frames) { dev_free(f.pts); dev_free(f.nor); free_grid(f.grid); free_tie(f); }
   c->frames.assign(n_frames, FrameDev());
   c->n_frames = n_frames;
@@ -1029,6 +1031,49 @@ int mvicp_fpfh_fetch(mvicp_ctx* c, long long cap_rows, double* desc, int* used) 
     if (dst[t]) { kind[t] = destination_kind(c, dst[t], names[t]); if (kind[t] < 0) return kind[t]; }
   for (int t = 0; t < 2; ++t)
     if (dst[t]) MV_HIP(hipMemcpyAsync(dst[t], src[t], bytes[t], kind[t] ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+  MV_HIP(hipStreamSynchronize(c->stream));
+  return MVICP_OK;
+} MVICP_GUARD_ABI
+
+long long mvicp_iss_keypoints(mvicp_ctx* c, int frame, double salient_radius, double non_max_radius, double gamma21, double gamma32, int min_neighbors) try {
+  // every argument error that needs no GPU first: nothing of the context has been touched when one of them is reported
+  if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
+  const double r_lo = std::ldexp(1.0, -300), r_hi = std::ldexp(1.0, 300);
+  if (!std::isfinite(salient_radius) || !(salient_radius >= r_lo && salient_radius <= r_hi)) { set_error("salient_radius must be finite and lie in [2^-300, 2^300]"); return MVICP_ERR_ARG; }
+  if (!std::isfinite(non_max_radius) || !(non_max_radius >= r_lo && non_max_radius <= r_hi)) { set_error("non_max_radius must be finite and lie in [2^-300, 2^300]"); return MVICP_ERR_ARG; }
+  if (!std::isfinite(gamma21) || !(gamma21 > 0.0)) { set_error("gamma21 must be finite and > 0"); return MVICP_ERR_ARG; }
+  if (!std::isfinite(gamma32) || !(gamma32 > 0.0)) { set_error("gamma32 must be finite and > 0"); return MVICP_ERR_ARG; }
+  if (min_neighbors < 1 || min_neighbors > 1024) { set_error("min_neighbors = %d outside [1, 1024]", min_neighbors); return MVICP_ERR_ARG; }
+  if (frame < 0 || frame >= c->n_frames) { set_error("frame %d out of range [0,%d)", frame, c->n_frames); return MVICP_ERR_ARG; }
+  const FrameDev& f = c->frames[frame];
+  if (!f.pts) { set_error("frame %d was never uploaded", frame); return MVICP_ERR_STATE; }
+  MV_CHECK(bind(c));
+  MV_CHECK(finish_builds(c));
+  int e = 0;
+  (void)std::frexp(salient_radius, &e);   // salient_radius = f 2^e, f in [0.5, 1)
+  const long long k = iss_keypoints(c, f, sqrt_bound(salient_radius), sqrt_bound(non_max_radius), 20 - e, gamma21, gamma32, min_neighbors);
+  if (c->profile) prof_collect_lazy(c);
+  return k;
+} MVICP_GUARD_ABI
+
+int mvicp_iss_fetch(mvicp_ctx* c, long long cap_keys, int* idx, double* xyz, double* nrm, long long cap_n, double* saliency, int* cnt_salient, int* cnt_nms) try {
+  if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
+  if (c->iss_n < 0) { set_error("no keypoints: call mvicp_iss_keypoints first"); return MVICP_ERR_STATE; }
+  if ((idx || xyz || nrm) && cap_keys < c->iss_k) { set_error("cap_keys %lld < %lld keypoints", cap_keys, c->iss_k); return MVICP_ERR_ARG; }
+  if ((saliency || cnt_salient || cnt_nms) && cap_n < c->iss_n) { set_error("cap_n %lld < %lld points", cap_n, c->iss_n); return MVICP_ERR_ARG; }
+  if (nrm && !c->iss_has_normals) { set_error("the frame of the keypoints has no normals"); return MVICP_ERR_STATE; }
+  if (c->iss_n == 0) return MVICP_OK;
+  MV_CHECK(bind(c));
+  const size_t k = (size_t)c->iss_k, n = (size_t)c->iss_n;
+  const void* src[6] = {c->iss_idx, c->iss_xyz, c->iss_nrm, c->iss_sal, c->iss_cnt_s, c->iss_cnt_n};
+  void* dst[6] = {idx, xyz, nrm, saliency, cnt_salient, cnt_nms};
+  const size_t bytes[6] = {4 * k, 24 * k, 24 * k, 8 * n, 4 * n, 4 * n};
+  const char* names[6] = {"idx", "xyz", "nrm", "saliency", "cnt_salient", "cnt_nms"};
+  int kind[6] = {0, 0, 0, 0, 0, 0};
+  for (int t = 0; t < 6; ++t)
+    if (dst[t] && bytes[t]) { kind[t] = destination_kind(c, dst[t], names[t]); if (kind[t] < 0) return kind[t]; }
+  for (int t = 0; t < 6; ++t)
+    if (dst[t] && bytes[t]) MV_HIP(hipMemcpyAsync(dst[t], src[t], bytes[t], kind[t] ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
   MV_HIP(hipStreamSynchronize(c->stream));
   return MVICP_OK;
 } MVICP_GUARD_ABI

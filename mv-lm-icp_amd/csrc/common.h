@@ -301,6 +301,13 @@ struct mvicp_ctx {
   std::vector<long long> coarse_seg; std::vector<int> coarse_cnt;
   int coarse_edges = -1;
 
+  // ISS keypoints (iss.hip): the last result, library-owned until the next mvicp_iss_keypoints / mvicp_set_num_frames / mvicp_destroy
+  // (iss_n < 0: none).  One device arena, grown on demand: [control | saliency | cnt_salient | cnt_nms | idx | xyz | nrm | flags | ranks];
+  // rocprim storage and a pinned control block of its own, so that the call touches nothing another result or a search uses
+  char* iss_dev = nullptr; char* iss_tmp = nullptr; char* iss_pin = nullptr; size_t iss_dev_bytes = 0, iss_tmp_bytes = 0;
+  double* iss_sal = nullptr; int* iss_cnt_s = nullptr; int* iss_cnt_n = nullptr; int* iss_idx = nullptr; double* iss_xyz = nullptr; double* iss_nrm = nullptr;
+  long long iss_n = -1, iss_k = 0; int iss_has_normals = 0;   // points of the frame, keypoints among them
+
   // cached small tables
   struct CachedTable { std::vector<char> bytes; void* d = nullptr; size_t cap = 0; };
   std::map<std::string, CachedTable> tables;
@@ -443,6 +450,11 @@ long long coarse_pairs(mvicp_ctx* c, const double* desc, int desc_on_device, con
                        int n_edges, const int* src, const int* dst, const unsigned long long* seeds, int mutual, double ratio, long long H, double tau,
                        double edge_sim, mvicp_coarse_edge* results);
 void free_coarse(mvicp_ctx* c);    // the result and the buffers
+// iss.hip: the ISS keypoints of frame f (valid, uploaded, structures built) for arguments already checked; B2_* = sqrt_bound of the two
+// radii, q = 20 - the binary exponent of the salient radius.  The result stays on the context (iss_*).  Returns the number of keypoints
+// or a negative status (a salient row of more than 1024 points: MVICP_ERR_ARG, no result).  Waits for the stream once; history-neutral.
+long long iss_keypoints(mvicp_ctx* c, const FrameDev& f, double B2_salient, double B2_nms, int q, double gamma21, double gamma32, int min_neighbors);
+void free_iss(mvicp_ctx* c);       // the result and the buffers
 int launch_compact(mvicp_ctx* c, double d2_bound);                                    // corr.hip
 int launch_gather_stream(mvicp_ctx* c);
 int launch_select_median(mvicp_ctx* c, double d2_bound);   // two-pass select anchored at the acceptance bound: any key set, exact

@@ -1,0 +1,254 @@
+// ISS keypoints (mvicp_iss_keypoints): per point of the stored cloud the eigenvalues l1 >= l2 >= l3 of the covariance of its neighbourhood
+// within salient_radius, the saliency l3 of the points that pass the two ratio tests, and the points no neighbour within non_max_radius
+// beats.  The result is a pure function of the stored bytes (the contract is stated in include/mvicp.h; tests/issref.py is its numpy
+// form).  DESIGN.md §3.13.
+//
+// Passes, all on the context's stream, no host wait before the last one:
+//   1  moments  one lane per point in hash-CELL order (GridDev::crec): the traversal of knn_all_kernel (knn_traverse.h, stop rule B2 <= m m)
+//               whose offer adds the neighbour's count and nine integer sums in registers -- g = floor((p_j - p_i) 2^q) fits an int, so a
+//               product is one 32 x 32 -> 64 multiply-add, and integer sums do not depend on the visiting order: no row is stored and
+//               nothing is sorted.  Then, in the same lane, D = c S - m m^T, C = D / c^2, six Jacobi sweeps and the tests; saliency and
+//               count go to the point's ORIGINAL index.
+//   2  nms      the same traversal at non_max_radius; offer reads the neighbour's saliency by its original index -> flag, count
+//   3  compact  rocprim exclusive scan of the flags; the flagged indices, ascending, and their stored rows (the fetch only copies)
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include <rocprim/rocprim.hpp>
+
+#include "common.h"
+#include "knn_traverse.h"
+#include "nn_metric.h"
+
+namespace mvicp {
+
+namespace {
+
+constexpr int NT = 128;          // lanes per workgroup of the two traversal passes
+constexpr int VT = 256;
+constexpr int kIssCap = 1024;    // neighbours of a salient row; more: MVICP_ERR_ARG
+constexpr int kSweeps = 6;
+constexpr unsigned int kFlagTooMany = 1u;
+
+struct IssCtl { unsigned int flags, pad; };
+constexpr size_t kTreeOffset = 64, kHeadBytes = 256;   // the box-tree view lives in the control block (knn.hip: TreeView)
+
+struct IssJob {
+  GridView g;
+  const TreeView* tree;   // null: no box tree
+  double B2;              // sqrt(d2) < radius  <=>  d2 < B2
+  double scale, unscale;  // 2^q, 2^-2q
+  double g21, g32;
+  int min_nb, pad;
+  double* sal;            // n, original order
+  int* cnt;               // n, original order: this pass's count
+  int* flag;              // n + 1, original order (pass 2; the last entry stays 0)
+  IssCtl* ctl;
+};
+
+__device__ __forceinline__ int scaled_floor(double pj, double pi, double scale) { return (int)floor(__dmul_rn(__dsub_rn(pj, pi), scale)); }
+
+// the diagonal of A after kSweeps sweeps over (0,1), (0,2), (1,2): the rotation of jacobi_min_eigvec (normals.hip) without its exit test
+// and without the vectors
+__device__ __forceinline__ void jacobi_eigenvalues(double (&A)[3][3]) {
+#pragma unroll 1
+  for (int sweep = 0; sweep < kSweeps; ++sweep) {
+#pragma unroll
+    for (int pq = 0; pq < 3; ++pq) {
+      const int p = pq == 2 ? 1 : 0, q = pq == 0 ? 1 : 2;
+      if (A[p][q] == 0.0) continue;
+      const double theta = __ddiv_rn(__dsub_rn(A[q][q], A[p][p]), __dmul_rn(2.0, A[p][q]));
+      const double t = __ddiv_rn(theta >= 0 ? 1.0 : -1.0, __dadd_rn(fabs(theta), __dsqrt_rn(__dadd_rn(__dmul_rn(theta, theta), 1.0))));
+      const double c = __ddiv_rn(1.0, __dsqrt_rn(__dadd_rn(__dmul_rn(t, t), 1.0))), s = __dmul_rn(t, c);
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {  // A <- A J
+        const double arp = A[r][p], arq = A[r][q];
+        A[r][p] = __dsub_rn(__dmul_rn(c, arp), __dmul_rn(s, arq)); A[r][q] = __dadd_rn(__dmul_rn(s, arp), __dmul_rn(c, arq));
+      }
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {  // A <- J^T A
+        const double apr = A[p][r], aqr = A[q][r];
+        A[p][r] = __dsub_rn(__dmul_rn(c, apr), __dmul_rn(s, aqr)); A[q][r] = __dadd_rn(__dmul_rn(s, apr), __dmul_rn(c, aqr));
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(NT) void iss_moments_kernel(IssJob job) {
+  const int i = blockIdx.x * NT + threadIdx.x;   // position in cell order
+  if (i >= job.g.n) return;
+  const PointRec me = job.g.crec[i];
+  const double B2 = job.B2, scale = job.scale;
+  int c = 0;
+  long long m0 = 0, m1 = 0, m2 = 0, s00 = 0, s01 = 0, s02 = 0, s11 = 0, s12 = 0, s22 = 0;
+  auto offer = [&](double d, const PointRec* p) {
+    if (!(d < B2)) return;
+    if (++c > kIssCap) return;   // (reported below; the sums of such a row are not used, and they stay below 2^62)
+    const int g0 = scaled_floor(p->x, me.x, scale), g1 = scaled_floor(p->y, me.y, scale), g2 = scaled_floor(p->z, me.z, scale);
+    m0 += g0; m1 += g1; m2 += g2;
+    s00 += (long long)g0 * g0; s01 += (long long)g0 * g1; s02 += (long long)g0 * g2;
+    s11 += (long long)g1 * g1; s12 += (long long)g1 * g2; s22 += (long long)g2 * g2;
+  };
+  auto reset = [&]() { c = 0; m0 = m1 = m2 = s00 = s01 = s02 = s11 = s12 = s22 = 0; };
+  auto stop = [&](double mm) { return B2 <= mm; };
+  auto open = [&](double lb) { return lb < B2; };
+  auto seed = [&](double) {};
+  traverse(job.g, job.tree, me.x, me.y, me.z, 0, offer, reset, stop, open, seed);
+
+  double sal = 0.0;
+  if (c > kIssCap) atomicOr(&job.ctl->flags, kFlagTooMany);
+  else if (c >= job.min_nb) {   // (c >= 1: the point itself)
+    const long long cc = c;
+    const double den = __ll2double_rn(cc * cc);   // <= 2^20: exact
+    const double c00 = __ddiv_rn(__ll2double_rn(cc * s00 - m0 * m0), den), c01 = __ddiv_rn(__ll2double_rn(cc * s01 - m0 * m1), den);
+    const double c02 = __ddiv_rn(__ll2double_rn(cc * s02 - m0 * m2), den), c11 = __ddiv_rn(__ll2double_rn(cc * s11 - m1 * m1), den);
+    const double c12 = __ddiv_rn(__ll2double_rn(cc * s12 - m1 * m2), den), c22 = __ddiv_rn(__ll2double_rn(cc * s22 - m2 * m2), den);
+    double A[3][3] = {{c00, c01, c02}, {c01, c11, c12}, {c02, c12, c22}};
+    jacobi_eigenvalues(A);
+    const double a = A[0][0], b = A[1][1], e = A[2][2];
+    const double l1 = fmax(fmax(a, b), e), l3 = fmin(fmin(a, b), e);
+    const double l2 = fmax(fmin(a, b), fmin(fmax(a, b), e));   // the median of three
+    if (l2 < __dmul_rn(job.g21, l1) && l3 < __dmul_rn(job.g32, l2) && l3 > 0.0) sal = __dmul_rn(l3, job.unscale);
+  }
+  job.sal[me.idx] = sal;
+  job.cnt[me.idx] = c;
+}
+
+__global__ __launch_bounds__(NT) void iss_nms_kernel(IssJob job) {
+  const int i = blockIdx.x * NT + threadIdx.x;   // position in cell order
+  if (i >= job.g.n) return;
+  const PointRec me = job.g.crec[i];
+  const double B2 = job.B2;
+  const double mine = job.sal[me.idx];
+  const double* __restrict__ sal = job.sal;
+  int c = 0;
+  bool beaten = false;
+  auto offer = [&](double d, const PointRec* p) {
+    if (!(d < B2)) return;
+    ++c;
+    const double s = sal[p->idx];
+    beaten = beaten || s > mine || (s == mine && p->idx < me.idx);
+  };
+  auto reset = [&]() { c = 0; beaten = false; };
+  auto stop = [&](double mm) { return B2 <= mm; };
+  auto open = [&](double lb) { return lb < B2; };
+  auto seed = [&](double) {};
+  traverse(job.g, job.tree, me.x, me.y, me.z, 0, offer, reset, stop, open, seed);
+  job.cnt[me.idx] = c;
+  job.flag[me.idx] = (mine > 0.0 && c >= job.min_nb && !beaten) ? 1 : 0;
+}
+
+// the flagged points at their rank: the original index and the stored rows
+__global__ __launch_bounds__(VT) void iss_scatter_kernel(const int* __restrict__ flag, const int* __restrict__ pos, int n, const double* __restrict__ pts,
+                                                         const double* __restrict__ nor, int* __restrict__ idx, double* __restrict__ xyz, double* __restrict__ nrm) {
+  const int i = blockIdx.x * VT + threadIdx.x;
+  if (i >= n || !flag[i]) return;
+  const size_t t = (size_t)pos[i];   // < the number of flags <= n
+  idx[t] = i;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    xyz[3 * t + a] = pts[3 * (size_t)i + a];
+    if (nor) nrm[3 * t + a] = nor[3 * (size_t)i + a];
+  }
+}
+
+size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+int grid_of(long long n, int t) { return (int)((n + t - 1) / t); }
+
+int ensure_dev(char** p, size_t* have, size_t need) {
+  if (need <= *have) return MVICP_OK;
+  if (*p) MV_HIP(hipFree(*p));
+  *p = nullptr; *have = 0;
+  MV_HIP(hipMalloc((void**)p, need));
+  *have = need;
+  return MVICP_OK;
+}
+
+}  // namespace
+
+void free_iss(mvicp_ctx* c) {
+  if (c->iss_dev) (void)hipFree(c->iss_dev);
+  if (c->iss_tmp) (void)hipFree(c->iss_tmp);
+  if (c->iss_pin) (void)hipHostFree(c->iss_pin);
+  c->iss_dev = nullptr; c->iss_tmp = nullptr; c->iss_pin = nullptr;
+  c->iss_dev_bytes = 0; c->iss_tmp_bytes = 0;
+  c->iss_sal = nullptr; c->iss_cnt_s = nullptr; c->iss_cnt_n = nullptr; c->iss_idx = nullptr; c->iss_xyz = nullptr; c->iss_nrm = nullptr;
+  c->iss_n = -1; c->iss_k = 0; c->iss_has_normals = 0;
+}
+
+long long iss_keypoints(mvicp_ctx* c, const FrameDev& f, double B2_salient, double B2_nms, int q, double gamma21, double gamma32, int min_neighbors) {
+  c->iss_n = -1;   // (the last result ends here; a failed call leaves none behind)
+  const int n = f.n;
+  if (n > 0 && !f.has_grid) { set_error("the keypoints need the per-cloud hash structure%s%s", f.build_error.empty() ? "" : ": ", f.build_error.c_str()); return MVICP_ERR_STATE; }
+  if (n == 0) { c->iss_n = 0; c->iss_k = 0; c->iss_has_normals = 0; return 0; }
+  hipStream_t st = c->stream;
+  const size_t N = (size_t)n;
+
+  // the result and the scratch in one arena: [control | saliency | cnt_salient | cnt_nms | idx | xyz | nrm | flag (n + 1) | rank (n + 1)]
+  const size_t o_sal = kHeadBytes, o_cs = o_sal + align256(8 * N), o_cn = o_cs + align256(4 * N), o_idx = o_cn + align256(4 * N);
+  const size_t o_xyz = o_idx + align256(4 * N), o_nrm = o_xyz + align256(24 * N), o_flag = o_nrm + align256(24 * N), o_pos = o_flag + align256(4 * (N + 1));
+  MV_CHECK(ensure_dev(&c->iss_dev, &c->iss_dev_bytes, o_pos + align256(4 * (N + 1))));
+  size_t scan_bytes = 0;
+  MV_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, (int*)nullptr, (int*)nullptr, 0, N + 1, rocprim::plus<int>(), st));
+  MV_CHECK(ensure_dev(&c->iss_tmp, &c->iss_tmp_bytes, std::max<size_t>(scan_bytes, 256)));
+  if (!c->iss_pin) MV_HIP(hipHostMalloc((void**)&c->iss_pin, 256, hipHostMallocDefault));
+  char* D = c->iss_dev;
+  IssCtl* d_ctl = reinterpret_cast<IssCtl*>(D);
+  c->iss_sal = reinterpret_cast<double*>(D + o_sal); c->iss_cnt_s = reinterpret_cast<int*>(D + o_cs); c->iss_cnt_n = reinterpret_cast<int*>(D + o_cn);
+  c->iss_idx = reinterpret_cast<int*>(D + o_idx); c->iss_xyz = reinterpret_cast<double*>(D + o_xyz); c->iss_nrm = reinterpret_cast<double*>(D + o_nrm);
+  int* d_flag = reinterpret_cast<int*>(D + o_flag); int* d_pos = reinterpret_cast<int*>(D + o_pos);
+  MV_HIP(hipMemsetAsync(d_ctl, 0, sizeof(IssCtl), st));
+  MV_HIP(hipMemsetAsync(d_flag + N, 0, 4, st));
+
+  IssJob j;
+  std::memset(&j, 0, sizeof(j));
+  const GridDev& g = f.grid;
+  j.g.crec = (const PointRec*)g.crec; j.g.n = n;
+  j.g.table = (const HashEntry*)g.table; j.g.mask = g.table_mask; j.g.shift = g.table_shift;
+  j.g.ox = g.origin[0]; j.g.oy = g.origin[1]; j.g.oz = g.origin[2]; j.g.h = g.cell; j.g.inv_h = g.inv_cell;
+  j.g.dx = g.dims[0]; j.g.dy = g.dims[1]; j.g.dz = g.dims[2];
+  // words 0 .. 1 of the pinned block receive the control block, the tree view is staged behind them (the last call's copy has completed:
+  // every call waits for its work)
+  if (g.oct && g.srec) {
+    TreeView* h_tree = reinterpret_cast<TreeView*>(c->iss_pin + kTreeOffset);
+    h_tree->srec = (const PointRec*)g.srec; h_tree->oct = g.oct; h_tree->first_leaf = g.oct_first_leaf; h_tree->leaf = g.oct_leaf; h_tree->pad = 0;
+    MV_HIP(hipMemcpyAsync(D + kTreeOffset, h_tree, sizeof(TreeView), hipMemcpyHostToDevice, st));
+    j.tree = reinterpret_cast<const TreeView*>(D + kTreeOffset);
+  }
+  j.scale = std::ldexp(1.0, q); j.unscale = std::ldexp(1.0, -2 * q);
+  j.g21 = gamma21; j.g32 = gamma32; j.min_nb = min_neighbors;
+  j.sal = c->iss_sal; j.flag = d_flag; j.ctl = d_ctl;
+  {
+    ProfScope ps(c, "iss_moments", 44.0 * n);
+    j.B2 = B2_salient; j.cnt = c->iss_cnt_s;
+    hipLaunchKernelGGL(iss_moments_kernel, dim3(grid_of(n, NT)), dim3(NT), 0, st, j);
+    MV_HIP(hipGetLastError());
+  }
+  {
+    ProfScope ps(c, "iss_nms", 48.0 * n);
+    j.B2 = B2_nms; j.cnt = c->iss_cnt_n;
+    hipLaunchKernelGGL(iss_nms_kernel, dim3(grid_of(n, NT)), dim3(NT), 0, st, j);
+    MV_HIP(hipGetLastError());
+  }
+  {
+    ProfScope ps(c, "iss_compact", 12.0 * n);
+    size_t tb = scan_bytes;
+    MV_HIP(rocprim::exclusive_scan(c->iss_tmp, tb, d_flag, d_pos, 0, N + 1, rocprim::plus<int>(), st));
+    hipLaunchKernelGGL(iss_scatter_kernel, dim3(grid_of(n, VT)), dim3(VT), 0, st, d_flag, d_pos, n, f.pts, f.nor, c->iss_idx, c->iss_xyz, c->iss_nrm);
+    MV_HIP(hipGetLastError());
+  }
+  IssCtl* h_ctl = reinterpret_cast<IssCtl*>(c->iss_pin);
+  int* h_total = reinterpret_cast<int*>(c->iss_pin + 16);
+  MV_HIP(hipMemcpyAsync(h_ctl, d_ctl, sizeof(IssCtl), hipMemcpyDeviceToHost, st));
+  MV_HIP(hipMemcpyAsync(h_total, d_pos + N, 4, hipMemcpyDeviceToHost, st));
+  MV_HIP(hipStreamSynchronize(st));
+  if (h_ctl->flags & kFlagTooMany) {
+    set_error("iss keypoints: a point has more than %d neighbours within the salient radius (smaller radius?)", kIssCap);
+    return MVICP_ERR_ARG;
+  }
+  c->iss_n = n; c->iss_k = *h_total; c->iss_has_normals = f.nor ? 1 : 0;
+  return c->iss_k;
+}
+
+}  // namespace mvicp

@@ -125,9 +125,11 @@ int Session::computeOverlapNeighbours(std::vector<std::shared_ptr<Frame>>& frame
   return comps;
 }
 
-int Session::initFromFeatures(std::vector<std::shared_ptr<Frame>>& frames, const FeatureInit& o, std::vector<FeatureEdge>* edges_out) {
+int Session::initFromFeatures(std::vector<std::shared_ptr<Frame>>& frames, const FeatureInit& o, std::vector<FeatureEdge>* edges_out,
+                              std::vector<FeatureKeypoints>* keypoint_counts) {
   const int K = (int)frames.size();
   if (edges_out) edges_out->clear();
+  if (keypoint_counts) keypoint_counts->clear();
   if (K < 1) return 0;
   // the clouds that carry the features: the frames themselves or their voxel copies
   std::vector<std::shared_ptr<Frame>> feat;
@@ -152,11 +154,39 @@ int Session::initFromFeatures(std::vector<std::shared_ptr<Frame>>& frames, const
   for (int i = 0; i < K; ++i)
     for (int j = i + 1; j < K; ++j) { src.push_back(i); dst.push_back(j); }
   const int E = (int)src.size();
+  int n_sets = K;
+  std::vector<int> set_dst = dst;   // the set an edge's destination rows come from
+  if (o.keypoints) {
+    // the keypoint rows of every frame, gathered in front of (2: the source side only) or instead of (1) the full sets
+    std::vector<long long> k_off((size_t)K + 1, 0);
+    std::vector<double> k_desc, k_xyz;
+    for (int i = 0; i < K; ++i) {
+      const long long k = mvicp_iss_keypoints(ctx, i, o.salient_radius, o.nms_radius, o.gamma21, o.gamma32, o.min_neighbors);
+      if (k < 0) check((int)k);
+      std::vector<int> idx((size_t)k);
+      if (k) check(mvicp_iss_fetch(ctx, k, idx.data(), nullptr, nullptr, 0, nullptr, nullptr, nullptr));
+      for (int r : idx) {
+        const size_t row = (size_t)offsets[i] + (size_t)r;
+        k_desc.insert(k_desc.end(), &desc[33 * row], &desc[33 * row] + 33);
+        k_xyz.insert(k_xyz.end(), &xyz[3 * row], &xyz[3 * row] + 3);
+      }
+      k_off[i + 1] = k_off[i] + k;
+      if (keypoint_counts) keypoint_counts->push_back(FeatureKeypoints{(int)k, (int)carry[i]->pts.size()});
+    }
+    if (o.keypoints == 2) {
+      for (int i = 1; i <= K; ++i) k_off.push_back(k_off[K] + offsets[i]);
+      k_desc.insert(k_desc.end(), desc.begin(), desc.end());
+      k_xyz.insert(k_xyz.end(), xyz.begin(), xyz.end());
+      for (int& d : set_dst) d += K;
+      n_sets = 2 * K;
+    }
+    offsets.swap(k_off); desc.swap(k_desc); xyz.swap(k_xyz);
+  }
   std::vector<unsigned long long> seeds((size_t)E);
   for (int e = 0; e < E; ++e) seeds[e] = o.seed + (unsigned long long)e;
   std::vector<mvicp_coarse_edge> res((size_t)E);
-  const long long st = mvicp_coarse_pairs(ctx, desc.data(), xyz.data(), offsets.data(), K, 33, E, src.data(), dst.data(), seeds.data(), 1, 1.0, o.hypotheses, o.tau,
-                                          o.edge_sim, res.data());
+  const long long st = mvicp_coarse_pairs(ctx, desc.data(), xyz.data(), offsets.data(), n_sets, 33, E, src.data(), set_dst.data(), seeds.data(), 1, 1.0, o.hypotheses,
+                                          o.tau, o.edge_sim, res.data());
   if (st < 0) check((int)st);
   std::vector<int> count((size_t)E);
   std::vector<double> pose(16 * (size_t)E);
@@ -172,7 +202,7 @@ int Session::initFromFeatures(std::vector<std::shared_ptr<Frame>>& frames, const
       for (size_t k = 0; k < c; ++k)
         if (flags[k]) {
           const double* p = &xyz[3 * ((size_t)offsets[src[e]] + (size_t)pairs[2 * k])];
-          const double* q = &xyz[3 * ((size_t)offsets[dst[e]] + (size_t)pairs[2 * k + 1])];
+          const double* q = &xyz[3 * ((size_t)offsets[set_dst[e]] + (size_t)pairs[2 * k + 1])];
           P.insert(P.end(), p, p + 3); Q.insert(Q.end(), q, q + 3);
         }
       check(mvicp_closedform_point_to_point(P.data(), Q.data(), (int)(P.size() / 3), &pose[16 * (size_t)e]));
@@ -424,6 +454,18 @@ std::shared_ptr<Frame> Frame::removeOutliers(int k, double std_ratio, double rad
   out->nor.assign(st.has_normals && nor.size() == pts.size() ? (size_t)m : 0, Vector3d());
   if (m) check(mvicp_outlier_fetch(c, m, out->pts[0].data(), out->nor.empty() ? nullptr : out->nor[0].data(), nullptr, 0, nullptr, nullptr));
   return out;
+}
+
+std::vector<int> Frame::issKeypoints(double salient_radius, double non_max_radius, double gamma21, double gamma32, int min_neighbors) {
+  std::vector<int> idx;
+  if (pts.empty()) return idx;
+  int slot = 0;
+  mvicp_ctx* c = Session::get().query_context(this, &slot);
+  const long long k = mvicp_iss_keypoints(c, slot, salient_radius, non_max_radius, gamma21, gamma32, min_neighbors);
+  if (k < 0) check((int)k);
+  idx.assign((size_t)k, 0);
+  if (k) check(mvicp_iss_fetch(c, k, idx.data(), nullptr, nullptr, 0, nullptr, nullptr, nullptr));
+  return idx;
 }
 
 double Frame::getClosestPoint(const Vector3d& q, size_t& ret_index) {

@@ -69,6 +69,9 @@ class Frame {
   // pose, poseGroundTruth, fixed and neighbours (index and weight; the correspondence lists start empty).  Runs in the context
   // Session::query_context finds for this frame (bin/multiview --sor_k / --sor_ratio / --ror_radius).
   std::shared_ptr<Frame> removeOutliers(int k, double std_ratio, double radius);
+  // The ISS keypoints of this frame (no counterpart in the reference): mvicp_iss_keypoints on this cloud as it is stored -> the indices
+  // of the keypoints, ascending.  Runs in the context Session::query_context finds for this frame (bin/multiview --feat_keypoints).
+  std::vector<int> issKeypoints(double salient_radius, double non_max_radius, double gamma21 = 0.975, double gamma32 = 0.975, int min_neighbors = 5);
 
  private:
   std::vector<int> knn_table_; size_t knn_k_ = 0; const void* knn_pts_ = nullptr; size_t knn_n_ = 0;   // cache of getNeighbourIndices
@@ -131,15 +134,24 @@ struct Session {
   // mvicp_poses_from_pairs over the inlier counts from root 0 at frames[0]->pose.  Writes frames[i]->pose for i >= 1 and returns the
   // number of components (more than one is reported, not repaired: a frame no usable edge reaches stands at the identity).  `edges`
   // receives one record per edge.  The frames need normals.
+  // keypoints = 1 or 2: the descriptors are still computed on the whole cloud that carries the features, mvicp_iss_keypoints selects rows
+  // of every frame (`keypoints` receives how many of how many), and only the selected rows are matched -- 1: the keypoints of both frames of an
+  // edge; 2: the keypoints of the source against every point of the destination (2 K sets: the keypoints, then the clouds; edge (i, j)
+  // becomes (i, K + j)).  The refinement uses the rows that were matched.
   struct FeatureInit {
     double voxel = 0.0, radius = 0.0, tau = 0.0, edge_sim = 0.9;
     int max_nn = 64, min_count = 3;
     long long hypotheses = 10000;
     unsigned long long seed = 0;
     bool refine = true;
+    int keypoints = 0;   // 0: none, 1: both sides, 2: the source side only
+    double salient_radius = 0.0, nms_radius = 0.0, gamma21 = 0.975, gamma32 = 0.975;
+    int min_neighbors = 5;
   };
   struct FeatureEdge { int src, dst, pairs, accepted, inliers; };
-  int initFromFeatures(std::vector<std::shared_ptr<Frame>>& frames, const FeatureInit& opts, std::vector<FeatureEdge>* edges = nullptr);
+  struct FeatureKeypoints { int keypoints, points; };   // of the cloud that carries the frame's features
+  int initFromFeatures(std::vector<std::shared_ptr<Frame>>& frames, const FeatureInit& opts, std::vector<FeatureEdge>* edges = nullptr,
+                       std::vector<FeatureKeypoints>* keypoints = nullptr);
   void correspond(std::vector<std::shared_ptr<Frame>>& frames, float thresh);
   void optimize(std::vector<std::shared_ptr<Frame>>& frames, int param, bool pointToPlane, bool robust, mvicp_summary* sm = nullptr);
   void reset();

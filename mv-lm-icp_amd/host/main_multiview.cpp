@@ -35,6 +35,10 @@
 // --feat_edge_sim (0.9), --feat_min_count (3: the fewest inliers that make an edge usable), --feat_seed (0), --feat_refine (default on:
 // each usable pose is refined over its inliers in closed form).  One line per edge, `feature init: edge i j pairs P accepted A inliers C`,
 // and one line `feature init: N component(s)` (printed with --quiet too).
+// --feat_keypoints none|iss|iss_src (default none): the descriptors are still computed on every point, but only ISS keypoints are matched
+// (iss: on both sides of every edge; iss_src: the keypoints of the source against every point of the destination).  --feat_salient_radius
+// (default --feat_radius), --feat_nms_radius (default 0.3 x salient), --feat_gamma21, --feat_gamma32 (0.975), --feat_min_neighbors (5).
+// One more line per frame, before the edge lines: `feature init: frame i keypoints k of n`.
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
@@ -116,8 +120,16 @@ int main(int argc, char** argv) {
       o.edge_sim = F.f("feat_edge_sim", 0.9);
       o.seed = std::strtoull(F.s("feat_seed", "0").c_str(), nullptr, 10);
       o.refine = F.b("feat_refine", true);
+      const std::string kp = F.s("feat_keypoints", "none");
+      if (kp != "none" && kp != "iss" && kp != "iss_src") { std::cerr << "--feat_keypoints must be none, iss or iss_src" << std::endl; return 1; }
+      o.keypoints = kp == "iss" ? 1 : kp == "iss_src" ? 2 : 0;
+      o.salient_radius = F.f("feat_salient_radius", o.radius); o.nms_radius = F.f("feat_nms_radius", 0.3 * o.salient_radius);
+      o.gamma21 = F.f("feat_gamma21", 0.975); o.gamma32 = F.f("feat_gamma32", 0.975); o.min_neighbors = F.i("feat_min_neighbors", 5);
       std::vector<Session::FeatureEdge> fe;
-      const int comps = Session::get().initFromFeatures(frames, o, &fe);
+      std::vector<Session::FeatureKeypoints> kc;
+      const int comps = Session::get().initFromFeatures(frames, o, &fe, &kc);
+      for (size_t i = 0; i < kc.size(); ++i)
+        std::cout << "feature init: frame " << i << " keypoints " << kc[i].keypoints << " of " << kc[i].points << std::endl;
       for (const Session::FeatureEdge& e : fe)
         std::cout << "feature init: edge " << e.src << " " << e.dst << " pairs " << e.pairs << " accepted " << e.accepted << " inliers " << e.inliers << std::endl;
       std::cout << "feature init: " << comps << " component(s)" << std::endl;

@@ -19,7 +19,7 @@ SYMBOLS = [
     "mvicp_closedform_point_to_point", "mvicp_closedform_point_to_plane", "mvicp_set_frame_device", "mvicp_get_structure",
     "mvicp_overlap", "mvicp_graph_from_overlap", "mvicp_voxel_grid", "mvicp_voxel_fetch",
     "mvicp_outlier_filter", "mvicp_outlier_fetch", "mvicp_outlier_threshold", "mvicp_cache_allowance",
-    "mvicp_knn_search", "mvicp_knn_fetch", "mvicp_fpfh", "mvicp_fpfh_fetch",
+    "mvicp_knn_search", "mvicp_knn_fetch", "mvicp_fpfh", "mvicp_fpfh_fetch", "mvicp_iss_keypoints", "mvicp_iss_fetch",
     "mvicp_feature_match", "mvicp_feature_match_fetch", "mvicp_match_pairs", "mvicp_consensus", "mvicp_consensus_fetch",
     "mvicp_coarse_pairs", "mvicp_coarse_pairs_fetch", "mvicp_poses_from_pairs",
 ]
@@ -134,6 +134,9 @@ def load_library(path=None):
     lib.mvicp_fpfh.argtypes = [vp, C.c_int, C.c_double, C.c_int]
     lib.mvicp_fpfh.restype = C.c_longlong
     lib.mvicp_fpfh_fetch.argtypes = [vp, C.c_longlong, vp, vp]
+    lib.mvicp_iss_keypoints.argtypes = [vp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int]
+    lib.mvicp_iss_keypoints.restype = C.c_longlong
+    lib.mvicp_iss_fetch.argtypes = [vp, C.c_longlong, vp, vp, vp, C.c_longlong, vp, vp, vp]
     lib.mvicp_feature_match.argtypes = [vp, vp, C.c_longlong, vp, C.c_longlong, C.c_int]
     lib.mvicp_feature_match.restype = C.c_longlong
     lib.mvicp_feature_match_fetch.argtypes = [vp, C.c_longlong, C.c_longlong, vp, vp, vp, vp]
@@ -344,13 +347,19 @@ def poses_from_pairs(n_frames, src, dst, count, pose, min_count=0, root=0, root_
 
 
 def init_from_clouds(eng, frames, xyz_list, radius, tau, max_nn=64, edges=None, hypotheses=10000, seed=0, edge_sim=0.9, mutual=True, ratio=1.0,
-                     min_count=3, root=0, refine=True):
+                     min_count=3, root=0, refine=True, keypoints=None):
     """Initial poses of a multiview problem from the clouds alone: Engine.fpfh(device=True) of every frame of `frames` -> ONE
     Engine.coarse_pairs over `edges` (pairs (i, j) of positions in `frames`; default: all i < j; seeds[e] = seed + e) -> with `refine`,
     closedform_point_to_point over each edge's inliers in ascending pair order (when there are at least 3) -> poses_from_pairs over the
     inlier counts.  xyz_list: the stored clouds of the frames as numpy arrays.
+    keypoints: None, or a dict(salient_radius, non_max_radius, gamma21=0.975, gamma32=0.975, min_neighbors=5, mode="both"): the
+    descriptors are still computed on the FULL clouds, Engine.iss_keypoints selects rows of every frame, and only the selected rows are
+    matched.  mode "both": every edge matches the keypoints of its two frames.  mode "src": the keypoints of the source against every
+    point of the destination (2 K sets: the keypoints, then the full clouds; edge (i, j) becomes (i, K + j)), which does not depend on
+    the two views selecting the same points.  The pair indices of coarse_pairs_fetch then refer to the matched rows, and the refinement
+    uses those rows.
     -> dict(poses (K,4,4), edges (E,2), records = per edge dict(pairs, accepted, inliers, best, pose, refined), parent, parent_edge,
-    component, components)."""
+    component, components; with keypoints also keypoints = the index array of every frame)."""
     import torch
     K = len(frames)
     if len(xyz_list) != K:
@@ -363,10 +372,27 @@ def init_from_clouds(eng, frames, xyz_list, radius, tau, max_nn=64, edges=None, 
     for d, x in zip(descs, clouds):
         if d.shape[0] != len(x):
             raise ValueError("xyz_list does not hold the clouds of the frames")
-    offsets = np.concatenate([[0], np.cumsum([len(x) for x in clouds])]).astype(np.int64)
+    kp_idx, set_dst = None, edges[:, 1]
+    src_rows = dst_rows = clouds   # the rows an edge's pair indices refer to, per frame
+    if keypoints is not None:
+        kp = dict(keypoints)
+        mode = kp.pop("mode", "both")
+        if mode not in ("both", "src"):
+            raise ValueError("keypoints['mode'] must be 'both' or 'src'")
+        kp_idx = [eng.iss_keypoints(f, **kp)["idx"] for f in frames]
+        sel = [torch.from_numpy(ix.astype(np.int64)).to(d.device) for ix, d in zip(kp_idx, descs)]
+        kp_descs = [d.index_select(0, t) for d, t in zip(descs, sel)]
+        src_rows = [np.ascontiguousarray(x[ix]) for x, ix in zip(clouds, kp_idx)]
+        if mode == "both":
+            descs, dst_rows, clouds_in = kp_descs, src_rows, src_rows
+        else:
+            descs, clouds_in, set_dst = kp_descs + descs, src_rows + clouds, (edges[:, 1] + K).astype(np.int32)
+    else:
+        clouds_in = clouds
+    offsets = np.concatenate([[0], np.cumsum([len(x) for x in clouds_in])]).astype(np.int64)
     desc = torch.cat(descs, 0) if K else torch.zeros((0, 33), dtype=torch.float64, device=torch.device("cuda", eng.device))
-    xyz = np.ascontiguousarray(np.concatenate(clouds, 0)) if K else np.zeros((0, 3))
-    res = eng.coarse_pairs(desc, xyz, offsets, edges[:, 0], edges[:, 1], seed, mutual=mutual, ratio=ratio, hypotheses=hypotheses, tau=tau, edge_sim=edge_sim)
+    xyz = np.ascontiguousarray(np.concatenate(clouds_in, 0)) if K else np.zeros((0, 3))
+    res = eng.coarse_pairs(desc, xyz, offsets, edges[:, 0], set_dst, seed, mutual=mutual, ratio=ratio, hypotheses=hypotheses, tau=tau, edge_sim=edge_sim)
     records, used = [], []
     for e, (i, j) in enumerate(edges):
         rec = {"pairs": int(res["pairs"][e]), "accepted": int(res["accepted"][e]), "inliers": int(res["count"][e]), "best": int(res["best"][e]),
@@ -374,11 +400,13 @@ def init_from_clouds(eng, frames, xyz_list, radius, tau, max_nn=64, edges=None, 
         if refine and rec["inliers"] >= 3:
             pr, fl = eng.coarse_pairs_fetch(e)
             keep = fl != 0
-            rec["refined"] = closedform_point_to_point(clouds[i][pr[keep, 0]], clouds[j][pr[keep, 1]])
+            rec["refined"] = closedform_point_to_point(src_rows[i][pr[keep, 0]], dst_rows[j][pr[keep, 1]])
         records.append(rec)
         used.append(rec["refined"] if refine else rec["pose"])
     tree = poses_from_pairs(K, edges[:, 0], edges[:, 1], res["count"], np.array(used).reshape(-1, 4, 4), min_count, root)
     tree.update(edges=edges, records=records)
+    if kp_idx is not None:
+        tree["keypoints"] = kp_idx
     return tree
 
 
@@ -755,6 +783,32 @@ class Engine:
             ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
         _check(self.lib, self.lib.mvicp_fpfh_fetch(self.h, n, ptr(desc), ptr(used)))
         return {"desc": desc, "used": used}
+
+    def iss_keypoints(self, frame, salient_radius, non_max_radius, gamma21=0.975, gamma32=0.975, min_neighbors=5, device=False):
+        """mvicp_iss_keypoints + mvicp_iss_fetch on the stored cloud of `frame`: the ISS keypoints (Zhong 2009) -- points whose
+        neighbourhood within `salient_radius` has eigenvalue ratios l2 / l1 < gamma21 and l3 / l2 < gamma32 and at least `min_neighbors`
+        points, and whose l3 no neighbour within `non_max_radius` beats (the lowest index wins a tie) -> dict(idx (k,) int32 original
+        indices ascending, xyz (k,3) the stored rows at idx, saliency (n,), cnt_salient (n,) int32, cnt_nms (n,) int32).  device=True:
+        torch tensors on the engine's GPU instead of numpy arrays.  Needs no graph; history-neutral."""
+        k = int(_check(self.lib, self.lib.mvicp_iss_keypoints(self.h, int(frame), float(salient_radius), float(non_max_radius), float(gamma21),
+                                                              float(gamma32), int(min_neighbors))))
+        n = self.npts[int(frame)]
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+            f64, i32 = torch.float64, torch.int32
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if t.numel() else None
+        else:
+            mk = lambda shape, dt: np.zeros(shape, dtype=dt)
+            f64, i32 = np.float64, np.int32
+            ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
+        idx, xyz = mk((k,), i32), mk((k, 3), f64)
+        sal, cs, cn = mk((n,), f64), mk((n,), i32), mk((n,), i32)
+        if device:
+            torch.cuda.synchronize(dev)   # (the allocations are the caller's; the library fills them on its own stream and waits)
+        _check(self.lib, self.lib.mvicp_iss_fetch(self.h, k, ptr(idx), ptr(xyz), None, n, ptr(sal), ptr(cs), ptr(cn)))
+        return {"idx": idx, "xyz": xyz, "saliency": sal, "cnt_salient": cs, "cnt_nms": cn}
 
     def _rows_operand(self, x, cols, what):
         """-> (the array kept alive, its pointer or None when empty, rows) for a (rows, cols) float64 numpy array or torch tensor on the engine's GPU"""
