@@ -542,6 +542,12 @@ int mvicp_create(int device, mvicp_ctx** out) try {
   return MVICP_OK;
 } MVICP_GUARD_ABI
 
+// the results and the buffers of every stage that keeps its last result on the context (common.h)
+static void release_stages(mvicp_ctx* c) {
+  c->vox.release(); c->out.release(); c->knn.release(); c->fpfh.release();
+  c->match.release(); c->cons.release(); c->coarse.release(); c->iss.release();
+}
+
 int mvicp_destroy(mvicp_ctx* c) try {
   if (!c) return MVICP_OK;
   (void)hipSetDevice(c->device);
@@ -552,14 +558,7 @@ int mvicp_destroy(mvicp_ctx* c) try {
   for (FrameDev& f : c->frames) { dev_free(f.pts); dev_free(f.nor); free_grid(f.grid); free_tie(f); }
   dev_free(c->d_split_idx); dev_free(c->d_split_d2); dev_free(c->d_scratch);
   free_overlap(c);
-  free_voxel(c);
-  free_outlier(c);
-  free_knn(c);
-  free_fpfh(c);
-  free_match(c);
-  free_consensus(c);
-  free_coarse(c);
-  free_iss(c);
+  release_stages(c);
   for (auto& kv : c->tables) if (kv.second.d) (void)hipFree(kv.second.d);
   if (c->d_census) (void)hipFree(c->d_census);
   if (c->h_census) (void)hipHostFree(c->h_census);
@@ -584,14 +583,7 @@ int mvicp_set_num_frames(mvicp_ctx* c, int n_frames) try {
   if (n_frames < 0) { set_error("n_frames < 0"); return MVICP_ERR_ARG; }
   (void)finish_builds(c);   // (builds of clouds that are dropped right here: their outcome no longer matters)
   if (c->E) free_graph(c);
-  free_voxel(c);   // (the last voxel-grid result ends here; every voxel call waits for its own work)
-  free_outlier(c); // (and the last outlier-filter result)
-  free_knn(c);     // (and the last neighbour-search result)
-  free_fpfh(c);    // (and the last descriptors)
-  free_match(c);   // (and the last matches)
-  free_consensus(c); // (and the last consensus)
-  free_coarse(c);    // (and the last batched coarse poses)
-  free_iss(c);       // (and the last keypoints)
+  release_stages(c);   // (the last result of every stage ends here; every stage's call waits for its own work)
   for (FrameDev& f : c->frames) { dev_free(f.pts); dev_free(f.nor); free_grid(f.grid); free_tie(f); }
   c->frames.assign(n_frames, FrameDev());
   c->n_frames = n_frames;
@@ -900,25 +892,35 @@ static int destination_kind(mvicp_ctx* c, const void* p, const char* what) {
   return 1;
 }
 
-int mvicp_voxel_fetch(mvicp_ctx* c, long long cap, double* xyz, double* nrm, int* cnt) try {
-  if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
-  if (c->vox_m < 0) { set_error("no voxel grid: call mvicp_voxel_grid first"); return MVICP_ERR_STATE; }
-  if (cap < c->vox_m) { set_error("cap %lld < %lld voxels", cap, c->vox_m); return MVICP_ERR_ARG; }
-  if (nrm && !c->vox_has_normals) { set_error("the voxel grid has no normals"); return MVICP_ERR_STATE; }
-  const size_t m = (size_t)c->vox_m;
-  if (m == 0) return MVICP_OK;
+// The tail of every fetch: each part with a destination and bytes to copy goes from the library's device memory to where its destination
+// lives.  Every destination is classified before the first copy is queued, so a refused one leaves nothing copied; one wait at the end.
+struct FetchPart { void* dst; const void* src; size_t bytes; const char* name; };
+extern "C++" {
+template <int N>
+static int fetch_parts(mvicp_ctx* c, const FetchPart (&parts)[N]) {
   MV_CHECK(bind(c));
-  const void* src[3] = {c->vox_xyz, c->vox_nrm, c->vox_cnt};
-  void* dst[3] = {xyz, nrm, cnt};
-  const size_t bytes[3] = {24 * m, 24 * m, 4 * m};
-  const char* names[3] = {"xyz", "nrm", "cnt"};
-  int kind[3] = {0, 0, 0};
-  for (int k = 0; k < 3; ++k)
-    if (dst[k]) { kind[k] = destination_kind(c, dst[k], names[k]); if (kind[k] < 0) return kind[k]; }
-  for (int k = 0; k < 3; ++k)
-    if (dst[k]) MV_HIP(hipMemcpyAsync(dst[k], src[k], bytes[k], kind[k] ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+  int kind[N];
+  for (int t = 0; t < N; ++t) {
+    kind[t] = 0;
+    if (parts[t].dst && parts[t].bytes) { kind[t] = destination_kind(c, parts[t].dst, parts[t].name); if (kind[t] < 0) return kind[t]; }
+  }
+  for (int t = 0; t < N; ++t)
+    if (parts[t].dst && parts[t].bytes)
+      MV_HIP(hipMemcpyAsync(parts[t].dst, parts[t].src, parts[t].bytes, kind[t] ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
   MV_HIP(hipStreamSynchronize(c->stream));
   return MVICP_OK;
+}
+}  // extern "C++"
+
+int mvicp_voxel_fetch(mvicp_ctx* c, long long cap, double* xyz, double* nrm, int* cnt) try {
+  if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
+  if (c->vox.m < 0) { set_error("no voxel grid: call mvicp_voxel_grid first"); return MVICP_ERR_STATE; }
+  if (cap < c->vox.m) { set_error("cap %lld < %lld voxels", cap, c->vox.m); return MVICP_ERR_ARG; }
+  if (nrm && !c->vox.has_normals) { set_error("the voxel grid has no normals"); return MVICP_ERR_STATE; }
+  const size_t m = (size_t)c->vox.m;
+  if (m == 0) return MVICP_OK;
+  const FetchPart parts[] = {{xyz, c->vox.xyz, 24 * m, "xyz"}, {nrm, c->vox.nrm, 24 * m, "nrm"}, {cnt, c->vox.cnt, 4 * m, "cnt"}};
+  return fetch_parts(c, parts);
 } MVICP_GUARD_ABI
 
 long long mvicp_outlier_filter(mvicp_ctx* c, int frame, int k, double std_ratio, double radius, mvicp_outlier_stats* stats) try {
@@ -940,24 +942,15 @@ long long mvicp_outlier_filter(mvicp_ctx* c, int frame, int k, double std_ratio,
 
 int mvicp_outlier_fetch(mvicp_ctx* c, long long cap_kept, double* xyz, double* nrm, int* idx, long long cap_n, double* mdist, double* kd2) try {
   if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
-  if (c->out_n < 0) { set_error("no outlier result: call mvicp_outlier_filter first"); return MVICP_ERR_STATE; }
-  if (cap_kept < c->out_kept) { set_error("cap_kept %lld < %lld kept rows", cap_kept, c->out_kept); return MVICP_ERR_ARG; }
-  if ((mdist || kd2) && cap_n < c->out_n) { set_error("cap_n %lld < %lld points", cap_n, c->out_n); return MVICP_ERR_ARG; }
-  if (nrm && !c->out_has_normals) { set_error("the filtered frame has no normals"); return MVICP_ERR_STATE; }
-  if (c->out_n == 0) return MVICP_OK;
-  MV_CHECK(bind(c));
-  const size_t m = (size_t)c->out_kept, n = (size_t)c->out_n;
-  const void* src[5] = {c->out_xyz, c->out_nrm, c->out_idx, c->out_mdist, c->out_kd2};
-  void* dst[5] = {xyz, nrm, idx, mdist, kd2};
-  const size_t bytes[5] = {24 * m, 24 * m, 4 * m, 8 * n, 8 * n};
-  const char* names[5] = {"xyz", "nrm", "idx", "mdist", "kd2"};
-  int kind[5] = {0, 0, 0, 0, 0};
-  for (int t = 0; t < 5; ++t)
-    if (dst[t] && bytes[t]) { kind[t] = destination_kind(c, dst[t], names[t]); if (kind[t] < 0) return kind[t]; }
-  for (int t = 0; t < 5; ++t)
-    if (dst[t] && bytes[t]) MV_HIP(hipMemcpyAsync(dst[t], src[t], bytes[t], kind[t] ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
-  MV_HIP(hipStreamSynchronize(c->stream));
-  return MVICP_OK;
+  if (c->out.n < 0) { set_error("no outlier result: call mvicp_outlier_filter first"); return MVICP_ERR_STATE; }
+  if (cap_kept < c->out.kept) { set_error("cap_kept %lld < %lld kept rows", cap_kept, c->out.kept); return MVICP_ERR_ARG; }
+  if ((mdist || kd2) && cap_n < c->out.n) { set_error("cap_n %lld < %lld points", cap_n, c->out.n); return MVICP_ERR_ARG; }
+  if (nrm && !c->out.has_normals) { set_error("the filtered frame has no normals"); return MVICP_ERR_STATE; }
+  if (c->out.n == 0) return MVICP_OK;
+  const size_t m = (size_t)c->out.kept, n = (size_t)c->out.n;
+  const FetchPart parts[] = {{xyz, c->out.xyz, 24 * m, "xyz"}, {nrm, c->out.nrm, 24 * m, "nrm"}, {idx, c->out.idx, 4 * m, "idx"},
+                             {mdist, c->out.mdist, 8 * n, "mdist"}, {kd2, c->out.kd2, 8 * n, "kd2"}};
+  return fetch_parts(c, parts);
 } MVICP_GUARD_ABI
 
 long long mvicp_knn_search(mvicp_ctx* c, int frame, const double* queries, long long m, int k, double radius) try {
@@ -980,23 +973,13 @@ long long mvicp_knn_search(mvicp_ctx* c, int frame, const double* queries, long 
 
 int mvicp_knn_fetch(mvicp_ctx* c, long long cap_rows, long long cap_entries, int* cnt, long long* off, int* idx, double* d2) try {
   if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
-  if (c->knn_m < 0) { set_error("no neighbour search result: call mvicp_knn_search first"); return MVICP_ERR_STATE; }
-  const long long entries = c->knn_k ? c->knn_m * c->knn_k : c->knn_total;
-  if ((cnt || off) && cap_rows < c->knn_m) { set_error("cap_rows %lld < %lld rows", cap_rows, c->knn_m); return MVICP_ERR_ARG; }
+  if (c->knn.m < 0) { set_error("no neighbour search result: call mvicp_knn_search first"); return MVICP_ERR_STATE; }
+  const long long entries = c->knn.k ? c->knn.m * c->knn.k : c->knn.total;
+  if ((cnt || off) && cap_rows < c->knn.m) { set_error("cap_rows %lld < %lld rows", cap_rows, c->knn.m); return MVICP_ERR_ARG; }
   if ((idx || d2) && cap_entries < entries) { set_error("cap_entries %lld < %lld entries", cap_entries, entries); return MVICP_ERR_ARG; }
-  MV_CHECK(bind(c));
-  const size_t m = (size_t)c->knn_m, e = (size_t)entries;
-  const void* src[4] = {c->knn_cnt, c->knn_off, c->knn_idx, c->knn_d2};
-  void* dst[4] = {cnt, off, idx, d2};
-  const size_t bytes[4] = {4 * m, 8 * (m + 1), 4 * e, 8 * e};
-  const char* names[4] = {"cnt", "off", "idx", "d2"};
-  int kind[4] = {0, 0, 0, 0};
-  for (int t = 0; t < 4; ++t)
-    if (dst[t] && bytes[t]) { kind[t] = destination_kind(c, dst[t], names[t]); if (kind[t] < 0) return kind[t]; }
-  for (int t = 0; t < 4; ++t)
-    if (dst[t] && bytes[t]) MV_HIP(hipMemcpyAsync(dst[t], src[t], bytes[t], kind[t] ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
-  MV_HIP(hipStreamSynchronize(c->stream));
-  return MVICP_OK;
+  const size_t m = (size_t)c->knn.m, e = (size_t)entries;
+  const FetchPart parts[] = {{cnt, c->knn.cnt, 4 * m, "cnt"}, {off, c->knn.off, 8 * (m + 1), "off"}, {idx, c->knn.idx, 4 * e, "idx"}, {d2, c->knn.d2, 8 * e, "d2"}};
+  return fetch_parts(c, parts);
 } MVICP_GUARD_ABI
 
 long long mvicp_fpfh(mvicp_ctx* c, int frame, double radius, int max_nn) try {
@@ -1017,22 +1000,12 @@ long long mvicp_fpfh(mvicp_ctx* c, int frame, double radius, int max_nn) try {
 
 int mvicp_fpfh_fetch(mvicp_ctx* c, long long cap_rows, double* desc, int* used) try {
   if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
-  if (c->fpfh_rows < 0) { set_error("no descriptors: call mvicp_fpfh first"); return MVICP_ERR_STATE; }
-  if (cap_rows < c->fpfh_rows) { set_error("cap_rows %lld < %lld rows", cap_rows, c->fpfh_rows); return MVICP_ERR_ARG; }
-  if (c->fpfh_rows == 0) return MVICP_OK;
-  MV_CHECK(bind(c));
-  const size_t n = (size_t)c->fpfh_rows;
-  const void* src[2] = {c->fpfh_desc, c->fpfh_used};
-  void* dst[2] = {desc, used};
-  const size_t bytes[2] = {33 * 8 * n, 4 * n};
-  const char* names[2] = {"desc", "used"};
-  int kind[2] = {0, 0};
-  for (int t = 0; t < 2; ++t)
-    if (dst[t]) { kind[t] = destination_kind(c, dst[t], names[t]); if (kind[t] < 0) return kind[t]; }
-  for (int t = 0; t < 2; ++t)
-    if (dst[t]) MV_HIP(hipMemcpyAsync(dst[t], src[t], bytes[t], kind[t] ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
-  MV_HIP(hipStreamSynchronize(c->stream));
-  return MVICP_OK;
+  if (c->fpfh.rows < 0) { set_error("no descriptors: call mvicp_fpfh first"); return MVICP_ERR_STATE; }
+  if (cap_rows < c->fpfh.rows) { set_error("cap_rows %lld < %lld rows", cap_rows, c->fpfh.rows); return MVICP_ERR_ARG; }
+  if (c->fpfh.rows == 0) return MVICP_OK;
+  const size_t n = (size_t)c->fpfh.rows;
+  const FetchPart parts[] = {{desc, c->fpfh.desc, 33 * 8 * n, "desc"}, {used, c->fpfh.used, 4 * n, "used"}};
+  return fetch_parts(c, parts);
 } MVICP_GUARD_ABI
 
 long long mvicp_iss_keypoints(mvicp_ctx* c, int frame, double salient_radius, double non_max_radius, double gamma21, double gamma32, int min_neighbors) try {
@@ -1058,24 +1031,15 @@ long long mvicp_iss_keypoints(mvicp_ctx* c, int frame, double salient_radius, do
 
 int mvicp_iss_fetch(mvicp_ctx* c, long long cap_keys, int* idx, double* xyz, double* nrm, long long cap_n, double* saliency, int* cnt_salient, int* cnt_nms) try {
   if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
-  if (c->iss_n < 0) { set_error("no keypoints: call mvicp_iss_keypoints first"); return MVICP_ERR_STATE; }
-  if ((idx || xyz || nrm) && cap_keys < c->iss_k) { set_error("cap_keys %lld < %lld keypoints", cap_keys, c->iss_k); return MVICP_ERR_ARG; }
-  if ((saliency || cnt_salient || cnt_nms) && cap_n < c->iss_n) { set_error("cap_n %lld < %lld points", cap_n, c->iss_n); return MVICP_ERR_ARG; }
-  if (nrm && !c->iss_has_normals) { set_error("the frame of the keypoints has no normals"); return MVICP_ERR_STATE; }
-  if (c->iss_n == 0) return MVICP_OK;
-  MV_CHECK(bind(c));
-  const size_t k = (size_t)c->iss_k, n = (size_t)c->iss_n;
-  const void* src[6] = {c->iss_idx, c->iss_xyz, c->iss_nrm, c->iss_sal, c->iss_cnt_s, c->iss_cnt_n};
-  void* dst[6] = {idx, xyz, nrm, saliency, cnt_salient, cnt_nms};
-  const size_t bytes[6] = {4 * k, 24 * k, 24 * k, 8 * n, 4 * n, 4 * n};
-  const char* names[6] = {"idx", "xyz", "nrm", "saliency", "cnt_salient", "cnt_nms"};
-  int kind[6] = {0, 0, 0, 0, 0, 0};
-  for (int t = 0; t < 6; ++t)
-    if (dst[t] && bytes[t]) { kind[t] = destination_kind(c, dst[t], names[t]); if (kind[t] < 0) return kind[t]; }
-  for (int t = 0; t < 6; ++t)
-    if (dst[t] && bytes[t]) MV_HIP(hipMemcpyAsync(dst[t], src[t], bytes[t], kind[t] ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
-  MV_HIP(hipStreamSynchronize(c->stream));
-  return MVICP_OK;
+  if (c->iss.n < 0) { set_error("no keypoints: call mvicp_iss_keypoints first"); return MVICP_ERR_STATE; }
+  if ((idx || xyz || nrm) && cap_keys < c->iss.k) { set_error("cap_keys %lld < %lld keypoints", cap_keys, c->iss.k); return MVICP_ERR_ARG; }
+  if ((saliency || cnt_salient || cnt_nms) && cap_n < c->iss.n) { set_error("cap_n %lld < %lld points", cap_n, c->iss.n); return MVICP_ERR_ARG; }
+  if (nrm && !c->iss.has_normals) { set_error("the frame of the keypoints has no normals"); return MVICP_ERR_STATE; }
+  if (c->iss.n == 0) return MVICP_OK;
+  const size_t k = (size_t)c->iss.k, n = (size_t)c->iss.n;
+  const FetchPart parts[] = {{idx, c->iss.idx, 4 * k, "idx"}, {xyz, c->iss.xyz, 24 * k, "xyz"}, {nrm, c->iss.nrm, 24 * k, "nrm"},
+                             {saliency, c->iss.sal, 8 * n, "saliency"}, {cnt_salient, c->iss.cnt_s, 4 * n, "cnt_salient"}, {cnt_nms, c->iss.cnt_n, 4 * n, "cnt_nms"}};
+  return fetch_parts(c, parts);
 } MVICP_GUARD_ABI
 
 long long mvicp_feature_match(mvicp_ctx* c, const double* a, long long m, const double* b, long long n, int dim) try {
@@ -1095,22 +1059,13 @@ long long mvicp_feature_match(mvicp_ctx* c, const double* a, long long m, const 
 
 int mvicp_feature_match_fetch(mvicp_ctx* c, long long cap_m, long long cap_n, int* fwd_idx, double* fwd_d2, int* bwd_idx, double* bwd_d2) try {
   if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
-  if (c->match_m < 0) { set_error("no matches: call mvicp_feature_match first"); return MVICP_ERR_STATE; }
-  if ((fwd_idx || fwd_d2) && cap_m < c->match_m) { set_error("cap_m %lld < %lld rows", cap_m, c->match_m); return MVICP_ERR_ARG; }
-  if ((bwd_idx || bwd_d2) && cap_n < c->match_n) { set_error("cap_n %lld < %lld rows", cap_n, c->match_n); return MVICP_ERR_ARG; }
-  MV_CHECK(bind(c));
-  const size_t m = (size_t)c->match_m, n = (size_t)c->match_n;
-  const void* src[4] = {c->match_fwd_idx, c->match_fwd_d2, c->match_bwd_idx, c->match_bwd_d2};
-  void* dst[4] = {fwd_idx, fwd_d2, bwd_idx, bwd_d2};
-  const size_t bytes[4] = {8 * m, 16 * m, 8 * n, 16 * n};
-  const char* names[4] = {"fwd_idx", "fwd_d2", "bwd_idx", "bwd_d2"};
-  int kind[4] = {0, 0, 0, 0};
-  for (int t = 0; t < 4; ++t)
-    if (dst[t] && bytes[t]) { kind[t] = destination_kind(c, dst[t], names[t]); if (kind[t] < 0) return kind[t]; }
-  for (int t = 0; t < 4; ++t)
-    if (dst[t] && bytes[t]) MV_HIP(hipMemcpyAsync(dst[t], src[t], bytes[t], kind[t] ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
-  MV_HIP(hipStreamSynchronize(c->stream));
-  return MVICP_OK;
+  if (c->match.m < 0) { set_error("no matches: call mvicp_feature_match first"); return MVICP_ERR_STATE; }
+  if ((fwd_idx || fwd_d2) && cap_m < c->match.m) { set_error("cap_m %lld < %lld rows", cap_m, c->match.m); return MVICP_ERR_ARG; }
+  if ((bwd_idx || bwd_d2) && cap_n < c->match.n) { set_error("cap_n %lld < %lld rows", cap_n, c->match.n); return MVICP_ERR_ARG; }
+  const size_t m = (size_t)c->match.m, n = (size_t)c->match.n;
+  const FetchPart parts[] = {{fwd_idx, c->match.fwd_idx, 8 * m, "fwd_idx"}, {fwd_d2, c->match.fwd_d2, 16 * m, "fwd_d2"},
+                             {bwd_idx, c->match.bwd_idx, 8 * n, "bwd_idx"}, {bwd_d2, c->match.bwd_d2, 16 * n, "bwd_d2"}};
+  return fetch_parts(c, parts);
 } MVICP_GUARD_ABI
 
 long long mvicp_match_pairs(long long m, long long n, const int* fwd_idx, const double* fwd_d2, const int* bwd_idx, int mutual, double ratio,
@@ -1151,21 +1106,11 @@ int mvicp_consensus(mvicp_ctx* c, const double* p, const double* q, long long n_
 
 int mvicp_consensus_fetch(mvicp_ctx* c, long long cap_h, int* count, long long cap_c, unsigned char* flags) try {
   if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
-  if (c->cons_H < 0) { set_error("no consensus: call mvicp_consensus first"); return MVICP_ERR_STATE; }
-  if (count && cap_h < c->cons_H) { set_error("cap_h %lld < %lld hypotheses", cap_h, c->cons_H); return MVICP_ERR_ARG; }
-  if (flags && cap_c < c->cons_c) { set_error("cap_c %lld < %lld pairs", cap_c, c->cons_c); return MVICP_ERR_ARG; }
-  MV_CHECK(bind(c));
-  const void* src[2] = {c->cons_count, c->cons_flags};
-  void* dst[2] = {count, flags};
-  const size_t bytes[2] = {4 * (size_t)c->cons_H, (size_t)c->cons_c};
-  const char* names[2] = {"count", "flags"};
-  int kind[2] = {0, 0};
-  for (int t = 0; t < 2; ++t)
-    if (dst[t]) { kind[t] = destination_kind(c, dst[t], names[t]); if (kind[t] < 0) return kind[t]; }
-  for (int t = 0; t < 2; ++t)
-    if (dst[t]) MV_HIP(hipMemcpyAsync(dst[t], src[t], bytes[t], kind[t] ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
-  MV_HIP(hipStreamSynchronize(c->stream));
-  return MVICP_OK;
+  if (c->cons.H < 0) { set_error("no consensus: call mvicp_consensus first"); return MVICP_ERR_STATE; }
+  if (count && cap_h < c->cons.H) { set_error("cap_h %lld < %lld hypotheses", cap_h, c->cons.H); return MVICP_ERR_ARG; }
+  if (flags && cap_c < c->cons.c) { set_error("cap_c %lld < %lld pairs", cap_c, c->cons.c); return MVICP_ERR_ARG; }
+  const FetchPart parts[] = {{count, c->cons.count, 4 * (size_t)c->cons.H, "count"}, {flags, c->cons.flags, (size_t)c->cons.c, "flags"}};
+  return fetch_parts(c, parts);
 } MVICP_GUARD_ABI
 
 long long mvicp_coarse_pairs(mvicp_ctx* c, const double* desc, const double* xyz, const long long* offsets, int n_sets, int dim, int n_edges,
@@ -1206,24 +1151,14 @@ long long mvicp_coarse_pairs(mvicp_ctx* c, const double* desc, const double* xyz
 
 int mvicp_coarse_pairs_fetch(mvicp_ctx* c, int edge, long long cap_pairs, int* pairs, unsigned char* flags) try {
   if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
-  if (c->coarse_edges < 0) { set_error("no coarse pairs: call mvicp_coarse_pairs first"); return MVICP_ERR_STATE; }
-  if (edge < 0 || edge >= c->coarse_edges) { set_error("edge %d out of range [0,%d)", edge, c->coarse_edges); return MVICP_ERR_ARG; }
-  const long long n = c->coarse_cnt[edge];
+  if (c->coarse.edges < 0) { set_error("no coarse pairs: call mvicp_coarse_pairs first"); return MVICP_ERR_STATE; }
+  if (edge < 0 || edge >= c->coarse.edges) { set_error("edge %d out of range [0,%d)", edge, c->coarse.edges); return MVICP_ERR_ARG; }
+  const long long n = c->coarse.cnt[edge];
   if ((pairs || flags) && cap_pairs < n) { set_error("cap_pairs %lld < %lld pairs", cap_pairs, n); return MVICP_ERR_ARG; }
   if (n == 0) return MVICP_OK;
-  MV_CHECK(bind(c));
-  const size_t seg = (size_t)c->coarse_seg[edge];
-  const void* from[2] = {c->coarse_pairs + 2 * seg, c->coarse_flags + seg};
-  void* to[2] = {pairs, flags};
-  const size_t bytes[2] = {8 * (size_t)n, (size_t)n};
-  const char* names[2] = {"pairs", "flags"};
-  int kind[2] = {0, 0};
-  for (int t = 0; t < 2; ++t)
-    if (to[t]) { kind[t] = destination_kind(c, to[t], names[t]); if (kind[t] < 0) return kind[t]; }
-  for (int t = 0; t < 2; ++t)
-    if (to[t]) MV_HIP(hipMemcpyAsync(to[t], from[t], bytes[t], kind[t] ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
-  MV_HIP(hipStreamSynchronize(c->stream));
-  return MVICP_OK;
+  const size_t seg = (size_t)c->coarse.seg[edge];
+  const FetchPart parts[] = {{pairs, c->coarse.pairs + 2 * seg, 8 * (size_t)n, "pairs"}, {flags, c->coarse.flags + seg, (size_t)n, "flags"}};
+  return fetch_parts(c, parts);
 } MVICP_GUARD_ABI
 
 // a (R, t) product of two column-major poses, each operation rounded on its own (this TU is built without fma contraction)

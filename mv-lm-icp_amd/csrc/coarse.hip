@@ -216,17 +216,6 @@ __global__ __launch_bounds__(kThreads) void coarse_finite(const double* __restri
   if (bad) atomicOr(flag, 1);
 }
 
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-int grow(char** buf, size_t* have, size_t need) {
-  if (need <= *have) return MVICP_OK;
-  if (*buf) MV_HIP(hipFree(*buf));
-  *buf = nullptr; *have = 0;
-  MV_HIP(hipMalloc((void**)buf, need));
-  *have = need;
-  return MVICP_OK;
-}
-
 // rows of the right operand per chunk and the number of chunks for `right` > 0 rows: the rule of match.hip
 void chunking(const mvicp_ctx* c, long long right, int* chunk, int* chunks) {
   long long ch = c->match_chunk > 0 ? c->match_chunk : 1;
@@ -240,21 +229,10 @@ struct Table { int L, R, chunk, chunks; size_t part, out; };
 
 }  // namespace
 
-void free_coarse(mvicp_ctx* c) {
-  if (c->coarse_dev) (void)hipFree(c->coarse_dev);
-  if (c->coarse_tmp) (void)hipFree(c->coarse_tmp);
-  if (c->coarse_work) (void)hipFree(c->coarse_work);
-  c->coarse_dev = nullptr; c->coarse_tmp = nullptr; c->coarse_work = nullptr;
-  c->coarse_dev_bytes = 0; c->coarse_tmp_bytes = 0; c->coarse_work_bytes = 0;
-  c->coarse_pairs = nullptr; c->coarse_flags = nullptr;
-  c->coarse_seg.clear(); c->coarse_cnt.clear();
-  c->coarse_edges = -1;
-}
-
 long long coarse_pairs(mvicp_ctx* c, const double* desc, int desc_on_device, const double* xyz, int xyz_on_device, const long long* offsets, int n_sets, int dim,
                        int n_edges, const int* src, const int* dst, const unsigned long long* seeds, int mutual, double ratio, long long H, double tau,
                        double edge_sim, mvicp_coarse_edge* results) {
-  c->coarse_edges = -1;   // (the last result ends here; a failed call leaves none behind)
+  c->coarse.edges = -1;   // (the last result ends here; a failed call leaves none behind)
   hipStream_t st = c->stream;
   const size_t E = (size_t)n_edges, NH = (size_t)H, total = (size_t)offsets[n_sets];
   auto rows_of = [&](int s) { return (int)(offsets[s + 1] - offsets[s]); };
@@ -307,9 +285,9 @@ long long coarse_pairs(mvicp_ctx* c, const double* desc, int desc_on_device, con
 
   // the result: [pairs S x 2 ints | flags S bytes]
   const size_t off_flags = align256(8 * S);
-  MV_CHECK(grow(&c->coarse_dev, &c->coarse_dev_bytes, off_flags + align256(S) + 256));
-  c->coarse_pairs = reinterpret_cast<int*>(c->coarse_dev);
-  c->coarse_flags = reinterpret_cast<unsigned char*>(c->coarse_dev + off_flags);
+  MV_CHECK(c->coarse.dev.reserve(off_flags + align256(S) + 256));
+  c->coarse.pairs = reinterpret_cast<int*>(c->coarse.dev.p);
+  c->coarse.flags = reinterpret_cast<unsigned char*>(c->coarse.dev.p + off_flags);
   // scratch: [flag | desc staged | xyz staged | partial lists | table idx | table d2 | P | Q | count E x H | accepted E x H | ctl E | results E |
   //           edges | match work | merge work]
   size_t off = 256;
@@ -318,8 +296,8 @@ long long coarse_pairs(mvicp_ctx* c, const double* desc, int desc_on_device, con
   const size_t o_part = take(sizeof(Best2) * n_part), o_idx = take(8 * n_out), o_d2 = take(16 * n_out), o_P = take(24 * S), o_Q = take(24 * S);
   const size_t o_count = take(4 * E * NH), o_hidx = take(4 * E * NH), o_ctl = take(sizeof(EdgeCtl) * E), o_res = take(sizeof(mvicp_coarse_edge) * E);
   const size_t o_edges = take(sizeof(EdgeRec) * E), o_mwork = take(sizeof(MatchWork) * mwork.size()), o_gwork = take(sizeof(MergeWork) * gwork.size());
-  MV_CHECK(grow(&c->coarse_tmp, &c->coarse_tmp_bytes, off));
-  char* T = c->coarse_tmp;
+  MV_CHECK(c->coarse.tmp.reserve(off));
+  char* T = c->coarse.tmp.p;
   int* flag = reinterpret_cast<int*>(T);
   const double* d_desc = desc; const double* d_xyz = xyz;
   if (!desc_on_device && total) { MV_HIP(hipMemcpyAsync(T + o_desc, desc, 8 * total * dim, hipMemcpyHostToDevice, st)); d_desc = reinterpret_cast<const double*>(T + o_desc); }
@@ -355,8 +333,8 @@ long long coarse_pairs(mvicp_ctx* c, const double* desc, int desc_on_device, con
     MV_HIP(hipMemcpyAsync(&h_flag, flag, sizeof(int), hipMemcpyDeviceToHost, st));
     MV_HIP(hipStreamSynchronize(st));
     if (h_flag) { set_error("a descriptor value or a coordinate is not finite"); return MVICP_ERR_ARG; }
-    c->coarse_seg.assign(1, 0); c->coarse_cnt.clear();
-    c->coarse_edges = 0;
+    c->coarse.seg.assign(1, 0); c->coarse.cnt.clear();
+    c->coarse.edges = 0;
     return 0;
   }
   if (!mwork.empty()) {
@@ -374,7 +352,7 @@ long long coarse_pairs(mvicp_ctx* c, const double* desc, int desc_on_device, con
   const int use_ratio = !(ratio >= 1.0);
   {
     ProfScope ps(c, "coarse_rule", (8.0 + (mutual ? 4.0 : 0.0) + (use_ratio ? 16.0 : 0.0) + 8.0 + 96.0) * (double)S + 64.0 * E);
-    hipLaunchKernelGGL(coarse_rule, dim3((unsigned int)E), dim3(kThreads), 0, st, d_edges, t_idx, t_d2, d_xyz, mutual ? 1 : 0, use_ratio, r2, c->coarse_pairs, P, Q, ctl);
+    hipLaunchKernelGGL(coarse_rule, dim3((unsigned int)E), dim3(kThreads), 0, st, d_edges, t_idx, t_d2, d_xyz, mutual ? 1 : 0, use_ratio, r2, c->coarse.pairs, P, Q, ctl);
     MV_HIP(hipGetLastError());
   }
   const dim3 block(kThreads), grid_h((unsigned int)((NH + kThreads - 1) / kThreads), (unsigned int)E);
@@ -407,10 +385,10 @@ long long coarse_pairs(mvicp_ctx* c, const double* desc, int desc_on_device, con
       score_bytes += 48.0 * ce * ((n_acc + kThreads - 1) / kThreads) + 148.0 * n_acc;
     }
     if (swork.size() > 0x7FFFFFFFull) { set_error("coarse pairs: too many scoring records"); return MVICP_ERR_ARG; }
-    MV_CHECK(grow(&c->coarse_work, &c->coarse_work_bytes, sizeof(ScoreWork) * swork.size()));
-    MV_HIP(hipMemcpyAsync(c->coarse_work, swork.data(), sizeof(ScoreWork) * swork.size(), hipMemcpyHostToDevice, st));
+    MV_CHECK(c->coarse.work.reserve(sizeof(ScoreWork) * swork.size()));
+    MV_HIP(hipMemcpyAsync(c->coarse.work.p, swork.data(), sizeof(ScoreWork) * swork.size(), hipMemcpyHostToDevice, st));
     ProfScope ps(c, "coarse_score", score_bytes + sizeof(ScoreWork) * (double)swork.size());
-    hipLaunchKernelGGL(coarse_score, dim3((unsigned int)swork.size()), block, 0, st, reinterpret_cast<const ScoreWork*>(c->coarse_work), d_edges, P, Q, (int)H, s2, tau2,
+    hipLaunchKernelGGL(coarse_score, dim3((unsigned int)swork.size()), block, 0, st, reinterpret_cast<const ScoreWork*>(c->coarse.work.p), d_edges, P, Q, (int)H, s2, tau2,
                        hidx, ctl, count);
     MV_HIP(hipGetLastError());
   }
@@ -418,16 +396,16 @@ long long coarse_pairs(mvicp_ctx* c, const double* desc, int desc_on_device, con
     ProfScope ps(c, "coarse_pick", 4.0 * NH * E + 49.0 * (double)S + sizeof(mvicp_coarse_edge) * (double)E);
     hipLaunchKernelGGL(coarse_pick, grid_h, block, 0, st, count, (int)H, ctl);
     const unsigned int gx = (unsigned int)(max_c > 0 ? (max_c + kThreads - 1) / kThreads : 1);
-    hipLaunchKernelGGL(coarse_flags, dim3(gx, (unsigned int)E), block, 0, st, d_edges, P, Q, s2, tau2, ctl, c->coarse_flags, d_res);
+    hipLaunchKernelGGL(coarse_flags, dim3(gx, (unsigned int)E), block, 0, st, d_edges, P, Q, s2, tau2, ctl, c->coarse.flags, d_res);
     MV_HIP(hipGetLastError());
   }
   std::vector<mvicp_coarse_edge> h_res(E);
   MV_HIP(hipMemcpyAsync(h_res.data(), d_res, sizeof(mvicp_coarse_edge) * E, hipMemcpyDeviceToHost, st));
   MV_HIP(hipStreamSynchronize(st));
-  c->coarse_seg = seg;
-  c->coarse_cnt.resize(E);
-  for (size_t e = 0; e < E; ++e) { results[e] = h_res[e]; c->coarse_cnt[e] = h_res[e].pairs; }
-  c->coarse_edges = n_edges;
+  c->coarse.seg = seg;
+  c->coarse.cnt.resize(E);
+  for (size_t e = 0; e < E; ++e) { results[e] = h_res[e]; c->coarse.cnt[e] = h_res[e].pairs; }
+  c->coarse.edges = n_edges;
   return n_edges;
 }
 

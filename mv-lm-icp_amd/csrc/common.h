@@ -118,6 +118,113 @@ struct ProfEntry {
   std::vector<hipEvent_t> pool;
 };
 
+// ---- buffers and results a stage of the library owns ---------------------------------------------------------------------------------
+// A stage (voxel grid, outlier filter, neighbour search, FPFH, descriptor matching, consensus, batched coarse poses, ISS keypoints) keeps
+// its LAST result on the context until the caller has fetched it.  Ownership, stated once for all eight: the stage's struct below holds
+// buffers of its own (so that a call touches nothing a search, a queued evaluation, the census or another stage uses), kept between
+// calls and grown on demand, the result arrays as views into them, and the sizes / flags, whose defaults mean "no result".  A call marks
+// its result as gone when it starts (a failed call leaves none behind) and sets it after its last wait; the result then lives until the
+// stage's next call, mvicp_set_num_frames or mvicp_destroy, and the last two release every stage through release_stages (api.cpp):
+// release() frees the buffers and assigns a default-constructed struct, so no view, size or flag can outlive them.
+
+inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+inline int grid_of(long long n, int threads) { return (int)((n + threads - 1) / threads); }
+
+// growable device buffer: reserve keeps a buffer that is large enough, else frees it and allocates exactly `need` (the contents are lost)
+struct DevBuf {
+  char* p = nullptr; size_t cap = 0;
+  int reserve(size_t need) {
+    if (need <= cap) return MVICP_OK;
+    if (p) MV_HIP(hipFree(p));
+    p = nullptr; cap = 0;
+    MV_HIP(hipMalloc((void**)&p, need));
+    cap = need;
+    return MVICP_OK;
+  }
+  void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+};
+// the same in pinned host memory
+struct PinBuf {
+  char* p = nullptr; size_t cap = 0;
+  int reserve(size_t need) {
+    if (need <= cap) return MVICP_OK;
+    if (p) MV_HIP(hipHostFree(p));
+    p = nullptr; cap = 0;
+    MV_HIP(hipHostMalloc((void**)&p, need, hipHostMallocDefault));
+    cap = need;
+    return MVICP_OK;
+  }
+  void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
+};
+
+// voxel.hip.  The result is three allocations of its own, made once the voxel count is known and freed at the start of the next call
+// (drop_result); growable are the scratch, the rocprim storage and the pinned control block
+struct VoxelStage {
+  DevBuf scratch, tmp; PinBuf pin;
+  double* xyz = nullptr; double* nrm = nullptr; int* cnt = nullptr; long long m = -1; int has_normals = 0;   // m < 0: none
+  void drop_result() {
+    if (xyz) (void)hipFree(xyz);
+    if (nrm) (void)hipFree(nrm);
+    if (cnt) (void)hipFree(cnt);
+    xyz = nullptr; nrm = nullptr; cnt = nullptr; m = -1; has_normals = 0;
+  }
+  void release() { drop_result(); scratch.release(); tmp.release(); pin.release(); *this = VoxelStage(); }
+};
+// outlier.hip.  dev: one arena [control | mdist | kd2 | flag | rank | xyz | nrm | idx], tmp: rocprim storage, pin: the control block's host copy
+struct OutlierStage {
+  DevBuf dev, tmp; PinBuf pin;
+  double* xyz = nullptr; double* nrm = nullptr; double* mdist = nullptr; double* kd2 = nullptr; int* idx = nullptr;
+  long long n = -1, kept = -1; int has_normals = 0;   // n < 0: none
+  void release() { dev.release(); tmp.release(); pin.release(); *this = OutlierStage(); }
+};
+// knn.hip.  dev holds [control | cnt | off], ent the entries [idx | d2] (all mode: behind them the same in visiting order), tmp the
+// scratch (staged host queries, sort keys, rocprim storage), pin the control block's host copy
+struct KnnStage {
+  DevBuf dev, ent, tmp; PinBuf pin;
+  int* cnt = nullptr; long long* off = nullptr; int* idx = nullptr; double* d2 = nullptr;
+  long long m = -1, total = 0; int k = 0;   // rows (< 0: none), entries over all rows, the k of the call (0: all mode, CSR)
+  void release() { dev.release(); ent.release(); tmp.release(); pin.release(); *this = KnnStage(); }
+};
+// fpfh.hip.  dev: [desc n x 33 doubles | used n ints | SPFH records n x 48 B]; the neighbourhoods are the KnnStage result of the search
+// the call runs, so there is no second set of search buffers
+struct FpfhStage {
+  DevBuf dev;
+  double* desc = nullptr; int* used = nullptr;
+  long long rows = -1;   // < 0: none
+  void release() { dev.release(); *this = FpfhStage(); }
+};
+// match.hip.  dev holds [fwd_idx | fwd_d2 | bwd_idx | bwd_d2 | flag], tmp the scratch (staged host operands, the per-chunk partial lists)
+struct MatchStage {
+  DevBuf dev, tmp;
+  int* fwd_idx = nullptr; int* bwd_idx = nullptr; double* fwd_d2 = nullptr; double* bwd_d2 = nullptr;
+  long long m = -1, n = -1;   // m < 0: none
+  void release() { dev.release(); tmp.release(); *this = MatchStage(); }
+};
+// consensus.hip.  dev: [control | count H ints | accepted h | flags c bytes | staged host pairs]
+struct ConsensusStage {
+  DevBuf dev;
+  int* count = nullptr; unsigned char* flags = nullptr;
+  long long H = -1, c = -1;   // H < 0: none
+  void release() { dev.release(); *this = ConsensusStage(); }
+};
+// coarse.hip.  dev holds [pairs | flags] in per-edge segments (edge e: seg[e], cnt[e] pairs), tmp the scratch of a call, work the
+// scoring work table
+struct CoarseStage {
+  DevBuf dev, tmp, work;
+  int* pairs = nullptr; unsigned char* flags = nullptr;
+  std::vector<long long> seg; std::vector<int> cnt;
+  int edges = -1;   // < 0: none
+  void release() { dev.release(); tmp.release(); work.release(); *this = CoarseStage(); }
+};
+// iss.hip.  dev: one arena [control | saliency | cnt_salient | cnt_nms | idx | xyz | nrm | flags | ranks], tmp: rocprim storage, pin: the
+// control block's host copy
+struct IssStage {
+  DevBuf dev, tmp; PinBuf pin;
+  double* sal = nullptr; int* cnt_s = nullptr; int* cnt_n = nullptr; int* idx = nullptr; double* xyz = nullptr; double* nrm = nullptr;
+  long long n = -1, k = 0; int has_normals = 0;   // points of the frame (< 0: none), keypoints among them
+  void release() { dev.release(); tmp.release(); pin.release(); *this = IssStage(); }
+};
+
 struct RcclApi;  // comm.cpp
 
 }  // namespace mvicp
@@ -247,66 +354,18 @@ struct mvicp_ctx {
   // memory — so that mvicp_overlap touches nothing a search, a queued evaluation or the shared control block uses
   char* ov_dev = nullptr; char* ov_pin = nullptr; size_t ov_bytes = 0;
 
-  // voxel-grid reduction (voxel.hip): the last result, library-owned until the next mvicp_voxel_grid / mvicp_set_num_frames / mvicp_destroy
-  // (vox_m < 0: none), and buffers of its own — scratch, rocprim storage, a pinned control block — kept between calls and grown on demand,
-  // so that mvicp_voxel_grid touches nothing a search, a queued evaluation or the census uses
-  double* vox_xyz = nullptr; double* vox_nrm = nullptr; int* vox_cnt = nullptr; long long vox_m = -1; int vox_has_normals = 0;
-  char* vox_scratch = nullptr; char* vox_tmp = nullptr; char* vox_pin = nullptr; size_t vox_scratch_bytes = 0, vox_tmp_bytes = 0, vox_pin_bytes = 0;
+  // the library-owned results (the *Stage structs above): one struct per stage; the options that sit between them are settings and outlive a result
+  mvicp::VoxelStage vox;
   int voxel_permute = 1;           // option "voxel_permute": lay w / R n out in sorted order before the reduction (0: the reduction re-gathers through seq)
-
-  // outlier filter (outlier.hip): the last result, library-owned until the next mvicp_outlier_filter / mvicp_set_num_frames / mvicp_destroy
-  // (out_n < 0: none).  One device arena (the result arrays are views into it), rocprim storage and a pinned control block of its own, kept
-  // between calls and grown on demand: mvicp_outlier_filter touches nothing a search, a queued evaluation, the census or the voxel grid uses
-  char* out_dev = nullptr; char* out_tmp = nullptr; char* out_pin = nullptr; size_t out_dev_bytes = 0, out_tmp_bytes = 0;
-  double* out_xyz = nullptr; double* out_nrm = nullptr; double* out_mdist = nullptr; double* out_kd2 = nullptr; int* out_idx = nullptr;
-  long long out_n = -1, out_kept = -1; int out_has_normals = 0;
-
-  // neighbour search (knn.hip): the last result, library-owned until the next mvicp_knn_search / mvicp_set_num_frames / mvicp_destroy
-  // (knn_m < 0: none).  knn_dev holds [control | cnt | off], knn_ent the entries [idx | d2] (all mode: behind them the same in visiting
-  // order), knn_tmp the scratch (staged host queries, sort keys, rocprim storage); a pinned control block of its own.  Kept between calls
-  // and grown on demand: mvicp_knn_search touches nothing a search, a queued evaluation, the census, the voxel grid or the filter uses
-  char* knn_dev = nullptr; char* knn_ent = nullptr; char* knn_tmp = nullptr; char* knn_pin = nullptr;
-  size_t knn_dev_bytes = 0, knn_ent_bytes = 0, knn_tmp_bytes = 0;
-  int* knn_cnt = nullptr; long long* knn_off = nullptr; int* knn_idx = nullptr; double* knn_d2 = nullptr;
-  long long knn_m = -1, knn_total = 0; int knn_k = 0;   // rows, entries over all rows, the k of the call (0: all mode, CSR)
+  mvicp::OutlierStage out;
+  mvicp::KnnStage knn;
   int knn_order = 1;               // option "knn_order": queries are answered in the order of their home cells (0: as given); the result is the same bytes
-
-  // FPFH descriptors (fpfh.hip): the last result, library-owned until the next mvicp_fpfh / mvicp_set_num_frames / mvicp_destroy
-  // (fpfh_rows < 0: none).  One device arena, grown on demand: [desc n x 33 doubles | used n ints | SPFH records n x 48 B]; the
-  // neighbourhoods are the knn_* result of the search the call runs, so there is no second set of search buffers
-  char* fpfh_dev = nullptr; size_t fpfh_dev_bytes = 0;
-  double* fpfh_desc = nullptr; int* fpfh_used = nullptr;
-  long long fpfh_rows = -1;
-
-  // descriptor matching (match.hip): the last result, library-owned until the next mvicp_feature_match / mvicp_set_num_frames /
-  // mvicp_destroy (match_m < 0: none).  match_dev holds [fwd_idx | fwd_d2 | bwd_idx | bwd_d2 | flag], match_tmp the scratch (staged host
-  // operands, the per-chunk partial lists); both kept between calls and grown on demand
-  char* match_dev = nullptr; char* match_tmp = nullptr; size_t match_dev_bytes = 0, match_tmp_bytes = 0;
-  int* match_fwd_idx = nullptr; int* match_bwd_idx = nullptr; double* match_fwd_d2 = nullptr; double* match_bwd_d2 = nullptr;
-  long long match_m = -1, match_n = -1;
+  mvicp::FpfhStage fpfh;
+  mvicp::MatchStage match;
   int match_chunk = 2048;          // option "match_chunk": rows of the right operand per blockIdx.y chunk; the result is the same bytes
-
-  // consensus (consensus.hip): the last result, library-owned until the next mvicp_consensus / mvicp_set_num_frames / mvicp_destroy
-  // (cons_H < 0: none).  One device arena, grown on demand: [control | count H ints | accepted h | flags c bytes | staged host pairs]
-  char* cons_dev = nullptr; size_t cons_dev_bytes = 0;
-  int* cons_count = nullptr; unsigned char* cons_flags = nullptr;
-  long long cons_H = -1, cons_c = -1;
-
-  // batched coarse poses (coarse.hip): the last result, library-owned until the next mvicp_coarse_pairs / mvicp_set_num_frames /
-  // mvicp_destroy (coarse_edges < 0: none).  coarse_dev holds [pairs | flags] in per-edge segments (edge e: coarse_seg[e], coarse_cnt[e]
-  // pairs), coarse_tmp the scratch of a call, coarse_work the scoring work table; all kept between calls and grown on demand
-  char* coarse_dev = nullptr; char* coarse_tmp = nullptr; char* coarse_work = nullptr;
-  size_t coarse_dev_bytes = 0, coarse_tmp_bytes = 0, coarse_work_bytes = 0;
-  int* coarse_pairs = nullptr; unsigned char* coarse_flags = nullptr;
-  std::vector<long long> coarse_seg; std::vector<int> coarse_cnt;
-  int coarse_edges = -1;
-
-  // ISS keypoints (iss.hip): the last result, library-owned until the next mvicp_iss_keypoints / mvicp_set_num_frames / mvicp_destroy
-  // (iss_n < 0: none).  One device arena, grown on demand: [control | saliency | cnt_salient | cnt_nms | idx | xyz | nrm | flags | ranks];
-  // rocprim storage and a pinned control block of its own, so that the call touches nothing another result or a search uses
-  char* iss_dev = nullptr; char* iss_tmp = nullptr; char* iss_pin = nullptr; size_t iss_dev_bytes = 0, iss_tmp_bytes = 0;
-  double* iss_sal = nullptr; int* iss_cnt_s = nullptr; int* iss_cnt_n = nullptr; int* iss_idx = nullptr; double* iss_xyz = nullptr; double* iss_nrm = nullptr;
-  long long iss_n = -1, iss_k = 0; int iss_has_normals = 0;   // points of the frame, keypoints among them
+  mvicp::ConsensusStage cons;
+  mvicp::CoarseStage coarse;
+  mvicp::IssStage iss;
 
   // cached small tables
   struct CachedTable { std::vector<char> bytes; void* d = nullptr; size_t cap = 0; };
@@ -413,48 +472,40 @@ void free_tie(FrameDev& f);                                                     
 int overlap_census(mvicp_ctx* c, const double* xf, double B2, double scale, int max_samples, int* samples, int* hits, long long* sumq);
 void free_overlap(mvicp_ctx* c);
 // voxel.hip: the points of the n_sel frames sel[] (valid, distinct, uploaded), at poses (n_frames x 16) or as stored (null), reduced to one
-// point per voxel; the result stays on the context (vox_*).  Returns the number of voxels or a negative status.  Waits for the stream; history-neutral.
+// point per voxel; the result stays on the context (c->vox).  Returns the number of voxels or a negative status.  Waits for the stream; history-neutral.
 long long voxel_reduce(mvicp_ctx* c, int n_sel, const int* sel, const double* poses, double voxel, int* has_normals);
-void free_voxel(mvicp_ctx* c);     // the result and the buffers
 // outlier.hip: k-distance search over frame f's hash (valid, uploaded, structures built; 1 <= k <= 32, n == 0 or n > k), the statistical
-// (std_ratio >= 0) and the radius (radius > 0) rule; the result stays on the context (out_*).  Returns the number kept or a negative
+// (std_ratio >= 0) and the radius (radius > 0) rule; the result stays on the context (c->out).  Returns the number kept or a negative
 // status.  Waits for the stream; history-neutral.
 long long outlier_filter(mvicp_ctx* c, const FrameDev& f, int k, double std_ratio, double radius, mvicp_outlier_stats* stats);
-void free_outlier(mvicp_ctx* c);   // the result and the buffers
 // knn.hip: the neighbourhoods of m queries (host or device memory, as `queries_on_device` says) or, queries == null, of the cloud's own
 // points, in frame f (valid, uploaded, structures built); 0 <= k <= 64, k == 0 needs radius > 0; B2 = sqrt_bound(radius) when radius > 0.
-// The result stays on the context (knn_*).  Returns the number of entries or a negative status.  Waits for the stream; history-neutral.
+// The result stays on the context (c->knn).  Returns the number of entries or a negative status.  Waits for the stream; history-neutral.
 long long knn_search(mvicp_ctx* c, const FrameDev& f, const double* queries, int queries_on_device, long long m, int k, double radius, double B2);
-void free_knn(mvicp_ctx* c);       // the result and the buffers
 // fpfh.hip: knn_search(c, f, null, 0, 0, max_nn, radius, B2) and the two descriptor passes over its rows, for frame f (valid, uploaded,
 // with normals unless empty, structures built; 2 <= max_nn <= 64, radius > 0, B2 = sqrt_bound(radius)); the result stays on the context
-// (fpfh_*), the search's as knn_*.  Returns the number of rows or a negative status.  Waits for the stream; history-neutral.
+// (c->fpfh), the search's in c->knn.  Returns the number of rows or a negative status.  Waits for the stream; history-neutral.
 long long fpfh_compute(mvicp_ctx* c, const FrameDev& f, int max_nn, double radius, double B2);
-void free_fpfh(mvicp_ctx* c);      // the result and the buffer
 // match.hip: the two nearest rows of B (n x dim) for every row of A (m x dim) and the reverse; 0 <= m, n < 2^31, 1 <= dim <= 64; each
-// operand in host or device memory as its `_on_device` says.  The result stays on the context (match_*).  Returns m or a negative
+// operand in host or device memory as its `_on_device` says.  The result stays on the context (c->match).  Returns m or a negative
 // status (a non-finite value: MVICP_ERR_ARG, no result).  Waits for the stream; history-neutral.
 long long feature_match(mvicp_ctx* c, const double* A, int a_on_device, long long m, const double* B, int b_on_device, long long n, int dim);
-void free_match(mvicp_ctx* c);     // the result and the buffers
 // consensus.hip: H hypotheses over the n_pairs index-aligned pairs (P, Q) (host or device memory); 3 <= n_pairs < 2^31, 1 <= H <= 2^24,
-// tau > 0, 0 <= edge_sim < 1.  count / flags stay on the context (cons_*), the record goes to `out`.  Returns a status (a non-finite
+// tau > 0, 0 <= edge_sim < 1.  count / flags stay on the context (c->cons), the record goes to `out`.  Returns a status (a non-finite
 // coordinate: MVICP_ERR_ARG, no result).  Waits for the stream; history-neutral.
 int consensus(mvicp_ctx* c, const double* P, int p_on_device, const double* Q, int q_on_device, long long n_pairs, long long H, unsigned long long seed,
               double tau, double edge_sim, mvicp_consensus_result* out);
-void free_consensus(mvicp_ctx* c); // the result and the buffer
 // coarse.hip: the chain feature_match -> match_pairs -> gather -> consensus for every edge (src[e], dst[e]) over n_sets sets whose rows
 // are offsets[s] .. offsets[s+1] of desc (x dim) and xyz (x 3), each in host or device memory; every argument already checked.  pairs /
-// flags stay on the context (coarse_*), the records go to `results`.  Returns n_edges or a negative status (a non-finite value:
+// flags stay on the context (c->coarse), the records go to `results`.  Returns n_edges or a negative status (a non-finite value:
 // MVICP_ERR_ARG, no result).  Waits for the stream twice, however many edges; history-neutral.
 long long coarse_pairs(mvicp_ctx* c, const double* desc, int desc_on_device, const double* xyz, int xyz_on_device, const long long* offsets, int n_sets, int dim,
                        int n_edges, const int* src, const int* dst, const unsigned long long* seeds, int mutual, double ratio, long long H, double tau,
                        double edge_sim, mvicp_coarse_edge* results);
-void free_coarse(mvicp_ctx* c);    // the result and the buffers
 // iss.hip: the ISS keypoints of frame f (valid, uploaded, structures built) for arguments already checked; B2_* = sqrt_bound of the two
-// radii, q = 20 - the binary exponent of the salient radius.  The result stays on the context (iss_*).  Returns the number of keypoints
+// radii, q = 20 - the binary exponent of the salient radius.  The result stays on the context (c->iss).  Returns the number of keypoints
 // or a negative status (a salient row of more than 1024 points: MVICP_ERR_ARG, no result).  Waits for the stream once; history-neutral.
 long long iss_keypoints(mvicp_ctx* c, const FrameDev& f, double B2_salient, double B2_nms, int q, double gamma21, double gamma32, int min_neighbors);
-void free_iss(mvicp_ctx* c);       // the result and the buffers
 int launch_compact(mvicp_ctx* c, double d2_bound);                                    // corr.hip
 int launch_gather_stream(mvicp_ctx* c);
 int launch_select_median(mvicp_ctx* c, double d2_bound);   // two-pass select anchored at the acceptance bound: any key set, exact

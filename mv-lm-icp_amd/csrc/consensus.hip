@@ -114,39 +114,25 @@ __global__ __launch_bounds__(kThreads) void cons_finite_kernel(const double* __r
   if (bad) atomicOr(flag, 1);
 }
 
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 }  // namespace
-
-void free_consensus(mvicp_ctx* c) {
-  if (c->cons_dev) (void)hipFree(c->cons_dev);
-  c->cons_dev = nullptr; c->cons_dev_bytes = 0;
-  c->cons_count = nullptr; c->cons_flags = nullptr;
-  c->cons_H = -1; c->cons_c = -1;
-}
 
 int consensus(mvicp_ctx* c, const double* P, int p_on_device, const double* Q, int q_on_device, long long n_pairs, long long H, unsigned long long seed,
               double tau, double edge_sim, mvicp_consensus_result* out) {
-  c->cons_H = -1; c->cons_c = -1;   // (the last result ends here; a failed call leaves none behind)
+  c->cons.H = -1; c->cons.c = -1;   // (the last result ends here; a failed call leaves none behind)
   hipStream_t st = c->stream;
   const size_t C = (size_t)n_pairs, NH = (size_t)H;
   // [ctl | count H | accepted h | flags c | P staged | Q staged]
   const size_t off_count = 256, off_hidx = off_count + align256(4 * NH), off_flags = off_hidx + align256(4 * NH), off_p = off_flags + align256(C);
   const size_t off_q = off_p + (p_on_device ? 0 : align256(24 * C)), need = off_q + (q_on_device ? 0 : align256(24 * C));
   static_assert(sizeof(ConsCtl) <= 256, "the control record fits its slot");
-  if (need > c->cons_dev_bytes) {
-    if (c->cons_dev) MV_HIP(hipFree(c->cons_dev));
-    c->cons_dev = nullptr; c->cons_dev_bytes = 0;
-    MV_HIP(hipMalloc((void**)&c->cons_dev, need));
-    c->cons_dev_bytes = need;
-  }
-  ConsCtl* ctl = reinterpret_cast<ConsCtl*>(c->cons_dev);
-  c->cons_count = reinterpret_cast<int*>(c->cons_dev + off_count);
-  int* hidx = reinterpret_cast<int*>(c->cons_dev + off_hidx);
-  c->cons_flags = reinterpret_cast<unsigned char*>(c->cons_dev + off_flags);
+  MV_CHECK(c->cons.dev.reserve(need));
+  ConsCtl* ctl = reinterpret_cast<ConsCtl*>(c->cons.dev.p);
+  c->cons.count = reinterpret_cast<int*>(c->cons.dev.p + off_count);
+  int* hidx = reinterpret_cast<int*>(c->cons.dev.p + off_hidx);
+  c->cons.flags = reinterpret_cast<unsigned char*>(c->cons.dev.p + off_flags);
   const double* dP = P; const double* dQ = Q;
-  if (!p_on_device) { MV_HIP(hipMemcpyAsync(c->cons_dev + off_p, P, 24 * C, hipMemcpyHostToDevice, st)); dP = reinterpret_cast<const double*>(c->cons_dev + off_p); }
-  if (!q_on_device) { MV_HIP(hipMemcpyAsync(c->cons_dev + off_q, Q, 24 * C, hipMemcpyHostToDevice, st)); dQ = reinterpret_cast<const double*>(c->cons_dev + off_q); }
+  if (!p_on_device) { MV_HIP(hipMemcpyAsync(c->cons.dev.p + off_p, P, 24 * C, hipMemcpyHostToDevice, st)); dP = reinterpret_cast<const double*>(c->cons.dev.p + off_p); }
+  if (!q_on_device) { MV_HIP(hipMemcpyAsync(c->cons.dev.p + off_q, Q, 24 * C, hipMemcpyHostToDevice, st)); dQ = reinterpret_cast<const double*>(c->cons.dev.p + off_q); }
   MV_HIP(hipMemsetAsync(ctl, 0, sizeof(ConsCtl), st));
   const size_t wgs_c = (3 * C + kThreads - 1) / kThreads;
   const dim3 grid_fin((unsigned int)(wgs_c < 4096 ? wgs_c : 4096));
@@ -161,7 +147,7 @@ int consensus(mvicp_ctx* c, const double* P, int p_on_device, const double* Q, i
   const dim3 block(kThreads), grid_h((unsigned int)((NH + kThreads - 1) / kThreads));
   {
     ProfScope ps(c, "cons_hyp", 8.0 * NH + 144.0 * NH);   // count and the accepted list; six points per hypothesis
-    hipLaunchKernelGGL(cons_hyp_kernel, grid_h, block, 0, st, dP, dQ, (int)n_pairs, (int)H, seed, s2, c->cons_count, hidx, ctl);
+    hipLaunchKernelGGL(cons_hyp_kernel, grid_h, block, 0, st, dP, dQ, (int)n_pairs, (int)H, seed, s2, c->cons.count, hidx, ctl);
     MV_HIP(hipGetLastError());
   }
   MV_HIP(hipMemcpyAsync(&h_ctl, ctl, sizeof(ConsCtl), hipMemcpyDeviceToHost, st));
@@ -178,19 +164,19 @@ int consensus(mvicp_ctx* c, const double* P, int p_on_device, const double* Q, i
     const int per_y_i = (int)(per_y < (long long)n_pairs ? per_y : (long long)n_pairs);
     const unsigned int gy_u = (unsigned int)(((long long)n_pairs + per_y_i - 1) / per_y_i);
     ProfScope ps(c, "cons_score", (48.0 * C) * gx + 148.0 * n_acc);   // every workgroup column reads every pair once
-    hipLaunchKernelGGL(cons_score_kernel, dim3((unsigned int)gx, gy_u), block, 0, st, dP, dQ, (int)n_pairs, seed, s2, tau2, hidx, n_acc, per_y_i, c->cons_count);
+    hipLaunchKernelGGL(cons_score_kernel, dim3((unsigned int)gx, gy_u), block, 0, st, dP, dQ, (int)n_pairs, seed, s2, tau2, hidx, n_acc, per_y_i, c->cons.count);
     MV_HIP(hipGetLastError());
   }
   {
     ProfScope ps(c, "cons_pick", 4.0 * NH + 49.0 * C);
-    hipLaunchKernelGGL(cons_pick_kernel, grid_h, block, 0, st, c->cons_count, (int)H, ctl);
-    hipLaunchKernelGGL(cons_flags_kernel, dim3((unsigned int)((C + kThreads - 1) / kThreads)), block, 0, st, dP, dQ, (int)n_pairs, seed, s2, tau2, c->cons_flags, ctl);
+    hipLaunchKernelGGL(cons_pick_kernel, grid_h, block, 0, st, c->cons.count, (int)H, ctl);
+    hipLaunchKernelGGL(cons_flags_kernel, dim3((unsigned int)((C + kThreads - 1) / kThreads)), block, 0, st, dP, dQ, (int)n_pairs, seed, s2, tau2, c->cons.flags, ctl);
     MV_HIP(hipGetLastError());
   }
   MV_HIP(hipMemcpyAsync(&h_ctl, ctl, sizeof(ConsCtl), hipMemcpyDeviceToHost, st));
   MV_HIP(hipStreamSynchronize(st));
   if (out) *out = h_ctl.res;
-  c->cons_H = H; c->cons_c = n_pairs;
+  c->cons.H = H; c->cons.c = n_pairs;
   return MVICP_OK;
 }
 

@@ -154,51 +154,37 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void fpfh_sum_kernel(int n, in
   desc[(size_t)i * kBins + lane] = __dadd_rn(__dmul_rn(acc, scale), own);
 }
 
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 }  // namespace
 
-void free_fpfh(mvicp_ctx* c) {
-  if (c->fpfh_dev) (void)hipFree(c->fpfh_dev);
-  c->fpfh_dev = nullptr; c->fpfh_dev_bytes = 0;
-  c->fpfh_desc = nullptr; c->fpfh_used = nullptr;
-  c->fpfh_rows = -1;
-}
-
 long long fpfh_compute(mvicp_ctx* c, const FrameDev& f, int max_nn, double radius, double B2) {
-  c->fpfh_rows = -1;   // (the last result ends here; a failed call leaves none behind)
+  c->fpfh.rows = -1;   // (the last result ends here; a failed call leaves none behind)
   const long long total = knn_search(c, f, nullptr, 0, 0, max_nn, radius, B2);
   if (total < 0) return total;
   const int n = f.n;
-  if (n == 0) { c->fpfh_rows = 0; return 0; }
+  if (n == 0) { c->fpfh.rows = 0; return 0; }
   hipStream_t st = c->stream;
   const size_t N = (size_t)n;
   const size_t off_used = align256(8 * kBins * N), off_rec = off_used + align256(4 * N), need = off_rec + align256(sizeof(SpfhRec) * N);
-  if (need > c->fpfh_dev_bytes) {
-    if (c->fpfh_dev) MV_HIP(hipFree(c->fpfh_dev));
-    c->fpfh_dev = nullptr; c->fpfh_dev_bytes = 0;
-    MV_HIP(hipMalloc((void**)&c->fpfh_dev, need));
-    c->fpfh_dev_bytes = need;
-  }
-  c->fpfh_desc = reinterpret_cast<double*>(c->fpfh_dev);
-  c->fpfh_used = reinterpret_cast<int*>(c->fpfh_dev + off_used);
-  SpfhRec* rec = reinterpret_cast<SpfhRec*>(c->fpfh_dev + off_rec);
+  MV_CHECK(c->fpfh.dev.reserve(need));
+  c->fpfh.desc = reinterpret_cast<double*>(c->fpfh.dev.p);
+  c->fpfh.used = reinterpret_cast<int*>(c->fpfh.dev.p + off_used);
+  SpfhRec* rec = reinterpret_cast<SpfhRec*>(c->fpfh.dev.p + off_rec);
   const dim3 grid((unsigned int)((N + kWavesPerBlock - 1) / kWavesPerBlock)), block(64 * kWavesPerBlock);
   const double row_bytes = 4.0 + 12.0 * max_nn;   // cnt and the dense row (idx, d2) of a point
   {
     // per point its position, normal, row and record; per neighbour a position and a normal
     ProfScope ps(c, "fpfh_spfh", (48.0 + row_bytes + sizeof(SpfhRec) + 4.0) * n + 48.0 * total);
-    hipLaunchKernelGGL(fpfh_spfh_kernel, grid, block, 0, st, f.pts, f.nor, n, max_nn, c->knn_cnt, c->knn_idx, c->knn_d2, rec, c->fpfh_used);
+    hipLaunchKernelGGL(fpfh_spfh_kernel, grid, block, 0, st, f.pts, f.nor, n, max_nn, c->knn.cnt, c->knn.idx, c->knn.d2, rec, c->fpfh.used);
     MV_HIP(hipGetLastError());
   }
   {
     // per point its row, its own 33 counts and r, the 33 doubles it writes; per neighbour 33 count bytes and r
     ProfScope ps(c, "fpfh_sum", (row_bytes + 41.0 + 8.0 * kBins) * n + 41.0 * total);
-    hipLaunchKernelGGL(fpfh_sum_kernel, grid, block, 0, st, n, max_nn, c->knn_cnt, c->knn_idx, c->knn_d2, rec, c->fpfh_desc);
+    hipLaunchKernelGGL(fpfh_sum_kernel, grid, block, 0, st, n, max_nn, c->knn.cnt, c->knn.idx, c->knn.d2, rec, c->fpfh.desc);
     MV_HIP(hipGetLastError());
   }
   MV_HIP(hipStreamSynchronize(st));
-  c->fpfh_rows = n;
+  c->fpfh.rows = n;
   return n;
 }
 

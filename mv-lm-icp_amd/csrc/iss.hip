@@ -153,50 +153,28 @@ __global__ __launch_bounds__(VT) void iss_scatter_kernel(const int* __restrict__
   }
 }
 
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-int grid_of(long long n, int t) { return (int)((n + t - 1) / t); }
-
-int ensure_dev(char** p, size_t* have, size_t need) {
-  if (need <= *have) return MVICP_OK;
-  if (*p) MV_HIP(hipFree(*p));
-  *p = nullptr; *have = 0;
-  MV_HIP(hipMalloc((void**)p, need));
-  *have = need;
-  return MVICP_OK;
-}
-
 }  // namespace
 
-void free_iss(mvicp_ctx* c) {
-  if (c->iss_dev) (void)hipFree(c->iss_dev);
-  if (c->iss_tmp) (void)hipFree(c->iss_tmp);
-  if (c->iss_pin) (void)hipHostFree(c->iss_pin);
-  c->iss_dev = nullptr; c->iss_tmp = nullptr; c->iss_pin = nullptr;
-  c->iss_dev_bytes = 0; c->iss_tmp_bytes = 0;
-  c->iss_sal = nullptr; c->iss_cnt_s = nullptr; c->iss_cnt_n = nullptr; c->iss_idx = nullptr; c->iss_xyz = nullptr; c->iss_nrm = nullptr;
-  c->iss_n = -1; c->iss_k = 0; c->iss_has_normals = 0;
-}
-
 long long iss_keypoints(mvicp_ctx* c, const FrameDev& f, double B2_salient, double B2_nms, int q, double gamma21, double gamma32, int min_neighbors) {
-  c->iss_n = -1;   // (the last result ends here; a failed call leaves none behind)
+  c->iss.n = -1;   // (the last result ends here; a failed call leaves none behind)
   const int n = f.n;
   if (n > 0 && !f.has_grid) { set_error("the keypoints need the per-cloud hash structure%s%s", f.build_error.empty() ? "" : ": ", f.build_error.c_str()); return MVICP_ERR_STATE; }
-  if (n == 0) { c->iss_n = 0; c->iss_k = 0; c->iss_has_normals = 0; return 0; }
+  if (n == 0) { c->iss.n = 0; c->iss.k = 0; c->iss.has_normals = 0; return 0; }
   hipStream_t st = c->stream;
   const size_t N = (size_t)n;
 
   // the result and the scratch in one arena: [control | saliency | cnt_salient | cnt_nms | idx | xyz | nrm | flag (n + 1) | rank (n + 1)]
   const size_t o_sal = kHeadBytes, o_cs = o_sal + align256(8 * N), o_cn = o_cs + align256(4 * N), o_idx = o_cn + align256(4 * N);
   const size_t o_xyz = o_idx + align256(4 * N), o_nrm = o_xyz + align256(24 * N), o_flag = o_nrm + align256(24 * N), o_pos = o_flag + align256(4 * (N + 1));
-  MV_CHECK(ensure_dev(&c->iss_dev, &c->iss_dev_bytes, o_pos + align256(4 * (N + 1))));
+  MV_CHECK(c->iss.dev.reserve(o_pos + align256(4 * (N + 1))));
   size_t scan_bytes = 0;
   MV_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, (int*)nullptr, (int*)nullptr, 0, N + 1, rocprim::plus<int>(), st));
-  MV_CHECK(ensure_dev(&c->iss_tmp, &c->iss_tmp_bytes, std::max<size_t>(scan_bytes, 256)));
-  if (!c->iss_pin) MV_HIP(hipHostMalloc((void**)&c->iss_pin, 256, hipHostMallocDefault));
-  char* D = c->iss_dev;
+  MV_CHECK(c->iss.tmp.reserve(std::max<size_t>(scan_bytes, 256)));
+  MV_CHECK(c->iss.pin.reserve(256));
+  char* D = c->iss.dev.p;
   IssCtl* d_ctl = reinterpret_cast<IssCtl*>(D);
-  c->iss_sal = reinterpret_cast<double*>(D + o_sal); c->iss_cnt_s = reinterpret_cast<int*>(D + o_cs); c->iss_cnt_n = reinterpret_cast<int*>(D + o_cn);
-  c->iss_idx = reinterpret_cast<int*>(D + o_idx); c->iss_xyz = reinterpret_cast<double*>(D + o_xyz); c->iss_nrm = reinterpret_cast<double*>(D + o_nrm);
+  c->iss.sal = reinterpret_cast<double*>(D + o_sal); c->iss.cnt_s = reinterpret_cast<int*>(D + o_cs); c->iss.cnt_n = reinterpret_cast<int*>(D + o_cn);
+  c->iss.idx = reinterpret_cast<int*>(D + o_idx); c->iss.xyz = reinterpret_cast<double*>(D + o_xyz); c->iss.nrm = reinterpret_cast<double*>(D + o_nrm);
   int* d_flag = reinterpret_cast<int*>(D + o_flag); int* d_pos = reinterpret_cast<int*>(D + o_pos);
   MV_HIP(hipMemsetAsync(d_ctl, 0, sizeof(IssCtl), st));
   MV_HIP(hipMemsetAsync(d_flag + N, 0, 4, st));
@@ -204,42 +182,33 @@ long long iss_keypoints(mvicp_ctx* c, const FrameDev& f, double B2_salient, doub
   IssJob j;
   std::memset(&j, 0, sizeof(j));
   const GridDev& g = f.grid;
-  j.g.crec = (const PointRec*)g.crec; j.g.n = n;
-  j.g.table = (const HashEntry*)g.table; j.g.mask = g.table_mask; j.g.shift = g.table_shift;
-  j.g.ox = g.origin[0]; j.g.oy = g.origin[1]; j.g.oz = g.origin[2]; j.g.h = g.cell; j.g.inv_h = g.inv_cell;
-  j.g.dx = g.dims[0]; j.g.dy = g.dims[1]; j.g.dz = g.dims[2];
-  // words 0 .. 1 of the pinned block receive the control block, the tree view is staged behind them (the last call's copy has completed:
-  // every call waits for its work)
-  if (g.oct && g.srec) {
-    TreeView* h_tree = reinterpret_cast<TreeView*>(c->iss_pin + kTreeOffset);
-    h_tree->srec = (const PointRec*)g.srec; h_tree->oct = g.oct; h_tree->first_leaf = g.oct_first_leaf; h_tree->leaf = g.oct_leaf; h_tree->pad = 0;
-    MV_HIP(hipMemcpyAsync(D + kTreeOffset, h_tree, sizeof(TreeView), hipMemcpyHostToDevice, st));
-    j.tree = reinterpret_cast<const TreeView*>(D + kTreeOffset);
-  }
+  fill_grid_view(&j.g, g, n);
+  // words 0 .. 1 of the pinned block receive the control block, the tree view is staged behind them
+  MV_CHECK(stage_tree_view(g, c->iss.pin.p + kTreeOffset, D + kTreeOffset, st, &j.tree));
   j.scale = std::ldexp(1.0, q); j.unscale = std::ldexp(1.0, -2 * q);
   j.g21 = gamma21; j.g32 = gamma32; j.min_nb = min_neighbors;
-  j.sal = c->iss_sal; j.flag = d_flag; j.ctl = d_ctl;
+  j.sal = c->iss.sal; j.flag = d_flag; j.ctl = d_ctl;
   {
     ProfScope ps(c, "iss_moments", 44.0 * n);
-    j.B2 = B2_salient; j.cnt = c->iss_cnt_s;
+    j.B2 = B2_salient; j.cnt = c->iss.cnt_s;
     hipLaunchKernelGGL(iss_moments_kernel, dim3(grid_of(n, NT)), dim3(NT), 0, st, j);
     MV_HIP(hipGetLastError());
   }
   {
     ProfScope ps(c, "iss_nms", 48.0 * n);
-    j.B2 = B2_nms; j.cnt = c->iss_cnt_n;
+    j.B2 = B2_nms; j.cnt = c->iss.cnt_n;
     hipLaunchKernelGGL(iss_nms_kernel, dim3(grid_of(n, NT)), dim3(NT), 0, st, j);
     MV_HIP(hipGetLastError());
   }
   {
     ProfScope ps(c, "iss_compact", 12.0 * n);
     size_t tb = scan_bytes;
-    MV_HIP(rocprim::exclusive_scan(c->iss_tmp, tb, d_flag, d_pos, 0, N + 1, rocprim::plus<int>(), st));
-    hipLaunchKernelGGL(iss_scatter_kernel, dim3(grid_of(n, VT)), dim3(VT), 0, st, d_flag, d_pos, n, f.pts, f.nor, c->iss_idx, c->iss_xyz, c->iss_nrm);
+    MV_HIP(rocprim::exclusive_scan(c->iss.tmp.p, tb, d_flag, d_pos, 0, N + 1, rocprim::plus<int>(), st));
+    hipLaunchKernelGGL(iss_scatter_kernel, dim3(grid_of(n, VT)), dim3(VT), 0, st, d_flag, d_pos, n, f.pts, f.nor, c->iss.idx, c->iss.xyz, c->iss.nrm);
     MV_HIP(hipGetLastError());
   }
-  IssCtl* h_ctl = reinterpret_cast<IssCtl*>(c->iss_pin);
-  int* h_total = reinterpret_cast<int*>(c->iss_pin + 16);
+  IssCtl* h_ctl = reinterpret_cast<IssCtl*>(c->iss.pin.p);
+  int* h_total = reinterpret_cast<int*>(c->iss.pin.p + 16);
   MV_HIP(hipMemcpyAsync(h_ctl, d_ctl, sizeof(IssCtl), hipMemcpyDeviceToHost, st));
   MV_HIP(hipMemcpyAsync(h_total, d_pos + N, 4, hipMemcpyDeviceToHost, st));
   MV_HIP(hipStreamSynchronize(st));
@@ -247,8 +216,8 @@ long long iss_keypoints(mvicp_ctx* c, const FrameDev& f, double B2_salient, doub
     set_error("iss keypoints: a point has more than %d neighbours within the salient radius (smaller radius?)", kIssCap);
     return MVICP_ERR_ARG;
   }
-  c->iss_n = n; c->iss_k = *h_total; c->iss_has_normals = f.nor ? 1 : 0;
-  return c->iss_k;
+  c->iss.n = n; c->iss.k = *h_total; c->iss.has_normals = f.nor ? 1 : 0;
+  return c->iss.k;
 }
 
 }  // namespace mvicp

@@ -218,18 +218,6 @@ __global__ __launch_bounds__(VT) void knn_rowoff_kernel(long long* __restrict__ 
   if (i <= m) off[i] = (long long)i * k;
 }
 
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-int grid_of(long long n, int t) { return (int)((n + t - 1) / t); }
-
-int ensure_dev(char** p, size_t* have, size_t need) {
-  if (need <= *have) return MVICP_OK;
-  if (*p) MV_HIP(hipFree(*p));
-  *p = nullptr; *have = 0;
-  MV_HIP(hipMalloc((void**)p, need));
-  *have = need;
-  return MVICP_OK;
-}
-
 int launch_search(hipStream_t st, const KnnJob& j) {
   // one LDS column of 12 B entries per lane: 12 / 24 / 48 KiB per 128-lane workgroup at capacity 8 / 16 / 32, 48 KiB per 64-lane workgroup at 64
   if (j.k <= 8) hipLaunchKernelGGL((knn_search_kernel<8, 128>), dim3(grid_of(j.m, 128)), dim3(128), 0, st, j);
@@ -242,19 +230,8 @@ int launch_search(hipStream_t st, const KnnJob& j) {
 
 }  // namespace
 
-void free_knn(mvicp_ctx* c) {
-  if (c->knn_dev) (void)hipFree(c->knn_dev);
-  if (c->knn_ent) (void)hipFree(c->knn_ent);
-  if (c->knn_tmp) (void)hipFree(c->knn_tmp);
-  if (c->knn_pin) (void)hipHostFree(c->knn_pin);
-  c->knn_dev = nullptr; c->knn_ent = nullptr; c->knn_tmp = nullptr; c->knn_pin = nullptr;
-  c->knn_dev_bytes = 0; c->knn_ent_bytes = 0; c->knn_tmp_bytes = 0;
-  c->knn_cnt = nullptr; c->knn_off = nullptr; c->knn_idx = nullptr; c->knn_d2 = nullptr;
-  c->knn_m = -1; c->knn_k = 0; c->knn_total = 0;
-}
-
 long long knn_search(mvicp_ctx* c, const FrameDev& f, const double* queries, int queries_on_device, long long m_in, int k, double radius, double B2) {
-  c->knn_m = -1;   // (the last result ends here; a failed call leaves none behind)
+  c->knn.m = -1;   // (the last result ends here; a failed call leaves none behind)
   const bool self = queries == nullptr, rad_on = radius > 0.0, all = k == 0;
   const int n = f.n;
   const int m = self ? n : (int)m_in;
@@ -264,18 +241,18 @@ long long knn_search(mvicp_ctx* c, const FrameDev& f, const double* queries, int
 
   // the result: [control | cnt | off] in one buffer, the entries [idx | d2] in another (all mode sizes them after the count)
   const size_t off_cnt = 256, off_off = off_cnt + align256(4 * M), head_bytes = off_off + align256(8 * (M + 1));
-  MV_CHECK(ensure_dev(&c->knn_dev, &c->knn_dev_bytes, head_bytes));
-  if (!c->knn_pin) MV_HIP(hipHostMalloc((void**)&c->knn_pin, 256, hipHostMallocDefault));
-  KnnCtl* d_ctl = reinterpret_cast<KnnCtl*>(c->knn_dev);
-  KnnCtl* h_ctl = reinterpret_cast<KnnCtl*>(c->knn_pin);
-  c->knn_cnt = reinterpret_cast<int*>(c->knn_dev + off_cnt);
-  c->knn_off = reinterpret_cast<long long*>(c->knn_dev + off_off);
+  MV_CHECK(c->knn.dev.reserve(head_bytes));
+  MV_CHECK(c->knn.pin.reserve(256));
+  KnnCtl* d_ctl = reinterpret_cast<KnnCtl*>(c->knn.dev.p);
+  KnnCtl* h_ctl = reinterpret_cast<KnnCtl*>(c->knn.pin.p);
+  c->knn.cnt = reinterpret_cast<int*>(c->knn.dev.p + off_cnt);
+  c->knn.off = reinterpret_cast<long long*>(c->knn.dev.p + off_off);
   MV_HIP(hipMemsetAsync(d_ctl, 0, sizeof(KnnCtl), st));
   if (m == 0) {
-    MV_HIP(hipMemsetAsync(c->knn_off, 0, 8, st));
+    MV_HIP(hipMemsetAsync(c->knn.off, 0, 8, st));
     MV_HIP(hipStreamSynchronize(st));
-    c->knn_idx = nullptr; c->knn_d2 = nullptr;
-    c->knn_m = 0; c->knn_k = k; c->knn_total = 0;
+    c->knn.idx = nullptr; c->knn.d2 = nullptr;
+    c->knn.m = 0; c->knn.k = k; c->knn.total = 0;
     return 0;
   }
 
@@ -292,8 +269,8 @@ long long knn_search(mvicp_ctx* c, const FrameDev& f, const double* queries, int
     MV_HIP(rocprim::radix_sort_pairs(nullptr, sort_bytes, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (int*)nullptr, (int*)nullptr, M, 0, bits, st));
   }
   if (all) MV_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, (long long*)nullptr, (long long*)nullptr, 0ll, M + 1, rocprim::plus<long long>(), st));
-  MV_CHECK(ensure_dev(&c->knn_tmp, &c->knn_tmp_bytes, s_rp + std::max<size_t>(std::max(sort_bytes, scan_bytes), 256)));
-  char* T = c->knn_tmp;
+  MV_CHECK(c->knn.tmp.reserve(s_rp + std::max<size_t>(std::max(sort_bytes, scan_bytes), 256)));
+  char* T = c->knn.tmp.p;
   const double* d_q = nullptr;
   if (!self) {
     if (queries_on_device) d_q = queries;
@@ -307,20 +284,11 @@ long long knn_search(mvicp_ctx* c, const FrameDev& f, const double* queries, int
   std::memset(&j, 0, sizeof(j));
   const GridDev& g = f.grid;
   if (n > 0) {
-    j.g.crec = (const PointRec*)g.crec;
-    j.g.table = (const HashEntry*)g.table; j.g.mask = g.table_mask; j.g.shift = g.table_shift;
-    j.g.ox = g.origin[0]; j.g.oy = g.origin[1]; j.g.oz = g.origin[2]; j.g.h = g.cell; j.g.inv_h = g.inv_cell;
-    j.g.dx = g.dims[0]; j.g.dy = g.dims[1]; j.g.dz = g.dims[2];
-  }
-  j.g.n = n;
-  if (n > 0 && g.oct && g.srec) {
-    TreeView* h_tree = reinterpret_cast<TreeView*>(c->knn_pin + kTreeOffset);   // (the last call's copy has completed: every call waits for its work)
-    h_tree->srec = (const PointRec*)g.srec; h_tree->oct = g.oct; h_tree->first_leaf = g.oct_first_leaf; h_tree->leaf = g.oct_leaf; h_tree->pad = 0;
-    MV_HIP(hipMemcpyAsync(c->knn_dev + kTreeOffset, h_tree, sizeof(TreeView), hipMemcpyHostToDevice, st));
-    j.tree = reinterpret_cast<const TreeView*>(c->knn_dev + kTreeOffset);
+    fill_grid_view(&j.g, g, n);
+    MV_CHECK(stage_tree_view(g, c->knn.pin.p + kTreeOffset, c->knn.dev.p + kTreeOffset, st, &j.tree));
   }
   j.q = d_q; j.m = m; j.k = k; j.rad_on = rad_on ? 1 : 0; j.B2 = B2;
-  j.cnt = c->knn_cnt; j.ctl = d_ctl;
+  j.cnt = c->knn.cnt; j.ctl = d_ctl;
   if (order_on) {
     ProfScope ps(c, "knn_key", 44.0 * m);
     unsigned long long* key_a = reinterpret_cast<unsigned long long*>(T + s_ka); unsigned long long* key_b = reinterpret_cast<unsigned long long*>(T + s_kb);
@@ -341,20 +309,20 @@ long long knn_search(mvicp_ctx* c, const FrameDev& f, const double* queries, int
   long long total = 0;
   if (!all) {
     const size_t E = M * (size_t)k, off_d2 = align256(4 * E);
-    MV_CHECK(ensure_dev(&c->knn_ent, &c->knn_ent_bytes, off_d2 + align256(8 * E)));
-    c->knn_idx = reinterpret_cast<int*>(c->knn_ent); c->knn_d2 = reinterpret_cast<double*>(c->knn_ent + off_d2);
-    RowsView* h_rows = reinterpret_cast<RowsView*>(c->knn_pin + kRowsOffset);
-    h_rows->cnt = c->knn_cnt; h_rows->idx = c->knn_idx; h_rows->d2 = c->knn_d2;
-    MV_HIP(hipMemcpyAsync(c->knn_dev + kRowsOffset, h_rows, sizeof(RowsView), hipMemcpyHostToDevice, st));
-    j.rows = reinterpret_cast<const RowsView*>(c->knn_dev + kRowsOffset);
+    MV_CHECK(c->knn.ent.reserve(off_d2 + align256(8 * E)));
+    c->knn.idx = reinterpret_cast<int*>(c->knn.ent.p); c->knn.d2 = reinterpret_cast<double*>(c->knn.ent.p + off_d2);
+    RowsView* h_rows = reinterpret_cast<RowsView*>(c->knn.pin.p + kRowsOffset);
+    h_rows->cnt = c->knn.cnt; h_rows->idx = c->knn.idx; h_rows->d2 = c->knn.d2;
+    MV_HIP(hipMemcpyAsync(c->knn.dev.p + kRowsOffset, h_rows, sizeof(RowsView), hipMemcpyHostToDevice, st));
+    j.rows = reinterpret_cast<const RowsView*>(c->knn.dev.p + kRowsOffset);
     {
       ProfScope ps(c, "knn_search", (36.0 + 12.0 * k) * m);
       if (n > 0) MV_CHECK(launch_search(st, j));
       else {
-        hipLaunchKernelGGL(knn_empty_kernel, dim3(grid_of(m, VT)), dim3(VT), 0, st, d_q, m, k, c->knn_cnt, c->knn_idx, c->knn_d2, c->knn_off, d_ctl);
+        hipLaunchKernelGGL(knn_empty_kernel, dim3(grid_of(m, VT)), dim3(VT), 0, st, d_q, m, k, c->knn.cnt, c->knn.idx, c->knn.d2, c->knn.off, d_ctl);
         MV_HIP(hipGetLastError());
       }
-      hipLaunchKernelGGL(knn_rowoff_kernel, dim3(grid_of((long long)m + 1, VT)), dim3(VT), 0, st, c->knn_off, m, k);
+      hipLaunchKernelGGL(knn_rowoff_kernel, dim3(grid_of((long long)m + 1, VT)), dim3(VT), 0, st, c->knn.off, m, k);
       MV_HIP(hipGetLastError());
     }
     MV_HIP(hipMemcpyAsync(h_ctl, d_ctl, sizeof(KnnCtl), hipMemcpyDeviceToHost, st));
@@ -370,10 +338,10 @@ long long knn_search(mvicp_ctx* c, const FrameDev& f, const double* queries, int
       hipLaunchKernelGGL(knn_all_kernel<false>, dim3(grid_of(m, 128)), dim3(128), 0, st, j);
       MV_HIP(hipGetLastError());
       size_t tb = scan_bytes;
-      MV_HIP(rocprim::exclusive_scan(T + s_rp, tb, cnt64, c->knn_off, 0ll, M + 1, rocprim::plus<long long>(), st));
+      MV_HIP(rocprim::exclusive_scan(T + s_rp, tb, cnt64, c->knn.off, 0ll, M + 1, rocprim::plus<long long>(), st));
     } else {
-      MV_HIP(hipMemsetAsync(c->knn_off + M, 0, 8, st));
-      hipLaunchKernelGGL(knn_empty_kernel, dim3(grid_of(m, VT)), dim3(VT), 0, st, d_q, m, 0, j.cnt, (int*)nullptr, (double*)nullptr, c->knn_off, d_ctl);
+      MV_HIP(hipMemsetAsync(c->knn.off + M, 0, 8, st));
+      hipLaunchKernelGGL(knn_empty_kernel, dim3(grid_of(m, VT)), dim3(VT), 0, st, d_q, m, 0, j.cnt, (int*)nullptr, (double*)nullptr, c->knn.off, d_ctl);
       MV_HIP(hipGetLastError());
     }
     MV_HIP(hipMemcpyAsync(h_ctl, d_ctl, sizeof(KnnCtl), hipMemcpyDeviceToHost, st));
@@ -381,13 +349,13 @@ long long knn_search(mvicp_ctx* c, const FrameDev& f, const double* queries, int
     MV_CHECK(check_flags(h_ctl->flags));
     total = (long long)h_ctl->total;
     if (total >= (1ll << 31)) { set_error("knn search: %lld neighbours in all: all mode returns fewer than 2^31 (smaller radius?)", total); return MVICP_ERR_ARG; }
-    c->knn_idx = nullptr; c->knn_d2 = nullptr;
+    c->knn.idx = nullptr; c->knn.d2 = nullptr;
     if (total > 0) {
       // entries: [idx | d2] sorted, behind them [idx | d2] in visiting order
       const size_t E = (size_t)total, o_d2 = align256(4 * E), o_ti = o_d2 + align256(8 * E), o_td = o_ti + align256(4 * E);
-      MV_CHECK(ensure_dev(&c->knn_ent, &c->knn_ent_bytes, o_td + align256(8 * E)));
-      c->knn_idx = reinterpret_cast<int*>(c->knn_ent); c->knn_d2 = reinterpret_cast<double*>(c->knn_ent + o_d2);
-      j.off = c->knn_off; j.eidx = reinterpret_cast<int*>(c->knn_ent + o_ti); j.ed2 = reinterpret_cast<double*>(c->knn_ent + o_td);
+      MV_CHECK(c->knn.ent.reserve(o_td + align256(8 * E)));
+      c->knn.idx = reinterpret_cast<int*>(c->knn.ent.p); c->knn.d2 = reinterpret_cast<double*>(c->knn.ent.p + o_d2);
+      j.off = c->knn.off; j.eidx = reinterpret_cast<int*>(c->knn.ent.p + o_ti); j.ed2 = reinterpret_cast<double*>(c->knn.ent.p + o_td);
       {
         ProfScope ps(c, "knn_fill", 36.0 * m + 12.0 * total);
         hipLaunchKernelGGL(knn_all_kernel<true>, dim3(grid_of(m, 128)), dim3(128), 0, st, j);
@@ -395,13 +363,13 @@ long long knn_search(mvicp_ctx* c, const FrameDev& f, const double* queries, int
       MV_HIP(hipGetLastError());
       {
         ProfScope ps(c, "knn_order", 24.0 * total);
-        hipLaunchKernelGGL(knn_order_kernel, dim3(grid_of(m, VT / 64)), dim3(VT), 0, st, c->knn_off, m, j.eidx, j.ed2, c->knn_idx, c->knn_d2);
+        hipLaunchKernelGGL(knn_order_kernel, dim3(grid_of(m, VT / 64)), dim3(VT), 0, st, c->knn.off, m, j.eidx, j.ed2, c->knn.idx, c->knn.d2);
       }
       MV_HIP(hipGetLastError());
       MV_HIP(hipStreamSynchronize(st));
     }
   }
-  c->knn_m = m; c->knn_k = k; c->knn_total = total;
+  c->knn.m = m; c->knn.k = k; c->knn.total = total;
   return total;
 }
 

@@ -31,6 +31,25 @@ struct GridView {
 // (measured: 8 spilled SGPRs in every build of the search kernel)
 struct TreeView { const PointRec* srec; const float* oct; long long first_leaf; int leaf, pad; };
 
+// host: the view of a built cloud's hash; n = the cloud's points
+inline void fill_grid_view(GridView* v, const GridDev& g, int n) {
+  v->crec = (const PointRec*)g.crec; v->n = n;
+  v->table = (const HashEntry*)g.table; v->mask = g.table_mask; v->shift = g.table_shift;
+  v->ox = g.origin[0]; v->oy = g.origin[1]; v->oz = g.origin[2]; v->h = g.cell; v->inv_h = g.inv_cell;
+  v->dx = g.dims[0]; v->dy = g.dims[1]; v->dz = g.dims[2];
+}
+
+// host: the view of the cloud's box tree, staged through the caller's pinned slot h_slot into its device slot d_slot (queued on st; the
+// pinned slot must not be in flight: every call of a stage waits for its work).  *out = d_slot, or stays as it is for a cloud without a tree
+inline int stage_tree_view(const GridDev& g, void* h_slot, void* d_slot, hipStream_t st, const TreeView** out) {
+  if (!g.oct || !g.srec) return MVICP_OK;
+  TreeView* h_tree = reinterpret_cast<TreeView*>(h_slot);
+  h_tree->srec = (const PointRec*)g.srec; h_tree->oct = g.oct; h_tree->first_leaf = g.oct_first_leaf; h_tree->leaf = g.oct_leaf; h_tree->pad = 0;
+  MV_HIP(hipMemcpyAsync(d_slot, h_tree, sizeof(TreeView), hipMemcpyHostToDevice, st));
+  *out = reinterpret_cast<const TreeView*>(d_slot);
+  return MVICP_OK;
+}
+
 // the clamped home cell along one axis; clamped as a double, so that a query far outside the grid cannot overflow the conversion
 __device__ __forceinline__ int home_cell(double q, double o, double inv_h, int d) {
   return (int)fmin(fmax(floor((q - o) * inv_h), 0.0), (double)(d - 1));

@@ -78,17 +78,6 @@ __global__ __launch_bounds__(kThreads) void match_finite_kernel(const double* __
   if (bad) atomicOr(flag, 1);
 }
 
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-int grow(char** buf, size_t* have, size_t need) {
-  if (need <= *have) return MVICP_OK;
-  if (*buf) MV_HIP(hipFree(*buf));
-  *buf = nullptr; *have = 0;
-  MV_HIP(hipMalloc((void**)buf, need));
-  *have = need;
-  return MVICP_OK;
-}
-
 // rows of the right operand per chunk and the number of chunks for `right` rows
 void chunking(const mvicp_ctx* c, long long right, int* chunk, int* chunks) {
   long long ch = c->match_chunk > 0 ? c->match_chunk : 1;
@@ -115,33 +104,25 @@ int launch_direction(mvicp_ctx* c, const char* scope, const double* L, int rows,
 
 }  // namespace
 
-void free_match(mvicp_ctx* c) {
-  if (c->match_dev) (void)hipFree(c->match_dev);
-  if (c->match_tmp) (void)hipFree(c->match_tmp);
-  c->match_dev = nullptr; c->match_tmp = nullptr; c->match_dev_bytes = 0; c->match_tmp_bytes = 0;
-  c->match_fwd_idx = nullptr; c->match_bwd_idx = nullptr; c->match_fwd_d2 = nullptr; c->match_bwd_d2 = nullptr;
-  c->match_m = -1; c->match_n = -1;
-}
-
 long long feature_match(mvicp_ctx* c, const double* A, int a_on_device, long long m, const double* B, int b_on_device, long long n, int dim) {
-  c->match_m = -1; c->match_n = -1;   // (the last result ends here; a failed call leaves none behind)
+  c->match.m = -1; c->match.n = -1;   // (the last result ends here; a failed call leaves none behind)
   hipStream_t st = c->stream;
   const size_t M = (size_t)m, N = (size_t)n, a_bytes = 8 * M * dim, b_bytes = 8 * N * dim;
   int chunk_f = 1, chunks_f = 0, chunk_b = 1, chunks_b = 0;
   if (m > 0 && n > 0) { chunking(c, n, &chunk_f, &chunks_f); chunking(c, m, &chunk_b, &chunks_b); }
   // results: [fwd_idx | fwd_d2 | bwd_idx | bwd_d2 | flag]
   const size_t off_fd = align256(8 * M), off_bi = off_fd + align256(16 * M), off_bd = off_bi + align256(8 * N), off_flag = off_bd + align256(16 * N);
-  MV_CHECK(grow(&c->match_dev, &c->match_dev_bytes, off_flag + 256));
+  MV_CHECK(c->match.dev.reserve(off_flag + 256));
   // scratch: [A staged | B staged | forward partial lists | backward partial lists]
   const size_t off_b = a_on_device ? 0 : align256(a_bytes), off_pf = off_b + (b_on_device ? 0 : align256(b_bytes));
   const size_t off_pb = off_pf + align256(sizeof(Best2) * M * chunks_f), tmp_need = off_pb + align256(sizeof(Best2) * N * chunks_b);
-  MV_CHECK(grow(&c->match_tmp, &c->match_tmp_bytes, tmp_need + 256));
-  c->match_fwd_idx = reinterpret_cast<int*>(c->match_dev); c->match_fwd_d2 = reinterpret_cast<double*>(c->match_dev + off_fd);
-  c->match_bwd_idx = reinterpret_cast<int*>(c->match_dev + off_bi); c->match_bwd_d2 = reinterpret_cast<double*>(c->match_dev + off_bd);
-  int* flag = reinterpret_cast<int*>(c->match_dev + off_flag);
+  MV_CHECK(c->match.tmp.reserve(tmp_need + 256));
+  c->match.fwd_idx = reinterpret_cast<int*>(c->match.dev.p); c->match.fwd_d2 = reinterpret_cast<double*>(c->match.dev.p + off_fd);
+  c->match.bwd_idx = reinterpret_cast<int*>(c->match.dev.p + off_bi); c->match.bwd_d2 = reinterpret_cast<double*>(c->match.dev.p + off_bd);
+  int* flag = reinterpret_cast<int*>(c->match.dev.p + off_flag);
   const double* dA = A; const double* dB = B;
-  if (!a_on_device && a_bytes) { MV_HIP(hipMemcpyAsync(c->match_tmp, A, a_bytes, hipMemcpyHostToDevice, st)); dA = reinterpret_cast<const double*>(c->match_tmp); }
-  if (!b_on_device && b_bytes) { MV_HIP(hipMemcpyAsync(c->match_tmp + off_b, B, b_bytes, hipMemcpyHostToDevice, st)); dB = reinterpret_cast<const double*>(c->match_tmp + off_b); }
+  if (!a_on_device && a_bytes) { MV_HIP(hipMemcpyAsync(c->match.tmp.p, A, a_bytes, hipMemcpyHostToDevice, st)); dA = reinterpret_cast<const double*>(c->match.tmp.p); }
+  if (!b_on_device && b_bytes) { MV_HIP(hipMemcpyAsync(c->match.tmp.p + off_b, B, b_bytes, hipMemcpyHostToDevice, st)); dB = reinterpret_cast<const double*>(c->match.tmp.p + off_b); }
   MV_HIP(hipMemsetAsync(flag, 0, sizeof(int), st));
   const double* checked[2] = {dA, dB};
   const size_t counts[2] = {M * dim, N * dim};
@@ -155,20 +136,20 @@ long long feature_match(mvicp_ctx* c, const double* A, int a_on_device, long lon
   MV_HIP(hipMemcpyAsync(&h_flag, flag, sizeof(int), hipMemcpyDeviceToHost, st));
   MV_HIP(hipStreamSynchronize(st));
   if (h_flag) { set_error("a descriptor value is not finite"); return MVICP_ERR_ARG; }
-  Best2* part_f = reinterpret_cast<Best2*>(c->match_tmp + off_pf);
-  Best2* part_b = reinterpret_cast<Best2*>(c->match_tmp + off_pb);
+  Best2* part_f = reinterpret_cast<Best2*>(c->match.tmp.p + off_pf);
+  Best2* part_b = reinterpret_cast<Best2*>(c->match.tmp.p + off_pb);
   if (chunks_f) {
     MV_CHECK(launch_direction(c, "match_fwd", dA, (int)m, dB, (int)n, dim, chunk_f, chunks_f, part_f));
     MV_CHECK(launch_direction(c, "match_bwd", dB, (int)n, dA, (int)m, dim, chunk_b, chunks_b, part_b));
   }
   {
     ProfScope ps(c, "match_merge", (sizeof(Best2) * (double)chunks_f + 24.0) * m + (sizeof(Best2) * (double)chunks_b + 24.0) * n);
-    if (m) hipLaunchKernelGGL(match_merge_kernel, dim3((unsigned int)((M + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, part_f, (int)m, chunks_f, c->match_fwd_idx, c->match_fwd_d2);
-    if (n) hipLaunchKernelGGL(match_merge_kernel, dim3((unsigned int)((N + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, part_b, (int)n, chunks_b, c->match_bwd_idx, c->match_bwd_d2);
+    if (m) hipLaunchKernelGGL(match_merge_kernel, dim3((unsigned int)((M + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, part_f, (int)m, chunks_f, c->match.fwd_idx, c->match.fwd_d2);
+    if (n) hipLaunchKernelGGL(match_merge_kernel, dim3((unsigned int)((N + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, part_b, (int)n, chunks_b, c->match.bwd_idx, c->match.bwd_d2);
     MV_HIP(hipGetLastError());
   }
   MV_HIP(hipStreamSynchronize(st));
-  c->match_m = m; c->match_n = n;
+  c->match.m = m; c->match.n = n;
   return m;
 }
 

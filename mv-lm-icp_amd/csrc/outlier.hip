@@ -195,36 +195,15 @@ __global__ __launch_bounds__(VT) void outlier_compact_kernel(const double* __res
   if (i == n - 1) ctl->kept = o + f;
 }
 
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-int grid_of(long long n, int t) { return (int)((n + t - 1) / t); }
-
-int ensure_dev(char** p, size_t* have, size_t need) {
-  if (need <= *have) return MVICP_OK;
-  if (*p) MV_HIP(hipFree(*p));
-  *p = nullptr; *have = 0;
-  MV_HIP(hipMalloc((void**)p, need));
-  *have = need;
-  return MVICP_OK;
-}
-
 }  // namespace
 
-void free_outlier(mvicp_ctx* c) {
-  if (c->out_dev) (void)hipFree(c->out_dev);
-  if (c->out_tmp) (void)hipFree(c->out_tmp);
-  if (c->out_pin) (void)hipHostFree(c->out_pin);
-  c->out_dev = nullptr; c->out_tmp = nullptr; c->out_pin = nullptr; c->out_dev_bytes = 0; c->out_tmp_bytes = 0;
-  c->out_xyz = nullptr; c->out_nrm = nullptr; c->out_mdist = nullptr; c->out_kd2 = nullptr; c->out_idx = nullptr;
-  c->out_n = -1; c->out_kept = -1; c->out_has_normals = 0;
-}
-
 long long outlier_filter(mvicp_ctx* c, const FrameDev& f, int k, double std_ratio, double radius, mvicp_outlier_stats* stats) {
-  c->out_n = -1; c->out_kept = -1;   // (the last result ends here; a failed call leaves none behind)
+  c->out.n = -1; c->out.kept = -1;   // (the last result ends here; a failed call leaves none behind)
   mvicp_outlier_stats S;
   std::memset(&S, 0, sizeof(S));
   S.n = f.n; S.has_normals = f.nor ? 1 : 0;
-  c->out_has_normals = f.nor ? 1 : 0;
-  if (f.n == 0) { c->out_n = 0; c->out_kept = 0; if (stats) *stats = S; return 0; }
+  c->out.has_normals = f.nor ? 1 : 0;
+  if (f.n == 0) { c->out.n = 0; c->out.kept = 0; if (stats) *stats = S; return 0; }
   if (!f.has_grid) { set_error("the outlier filter needs the per-cloud hash structure"); return MVICP_ERR_STATE; }
   const int n = f.n;
   const size_t NN = (size_t)n;
@@ -235,18 +214,18 @@ long long outlier_filter(mvicp_ctx* c, const FrameDev& f, int k, double std_rati
   const size_t off_md = 256, off_kd = off_md + align256(8 * NN), off_fl = off_kd + align256(8 * NN), off_ps = off_fl + align256(4 * NN);
   const size_t off_x = off_ps + align256(4 * NN), off_nr = off_x + align256(24 * NN), off_ix = off_nr + (normals ? align256(24 * NN) : 0);
   const size_t bytes = off_ix + align256(4 * NN);
-  MV_CHECK(ensure_dev(&c->out_dev, &c->out_dev_bytes, bytes));
-  if (!c->out_pin) MV_HIP(hipHostMalloc((void**)&c->out_pin, 256, hipHostMallocDefault));
-  char* D = c->out_dev;
+  MV_CHECK(c->out.dev.reserve(bytes));
+  MV_CHECK(c->out.pin.reserve(256));
+  char* D = c->out.dev.p;
   OutCtl* d_ctl = reinterpret_cast<OutCtl*>(D);
-  OutCtl* h_ctl = reinterpret_cast<OutCtl*>(c->out_pin);
-  c->out_mdist = reinterpret_cast<double*>(D + off_md); c->out_kd2 = reinterpret_cast<double*>(D + off_kd);
+  OutCtl* h_ctl = reinterpret_cast<OutCtl*>(c->out.pin.p);
+  c->out.mdist = reinterpret_cast<double*>(D + off_md); c->out.kd2 = reinterpret_cast<double*>(D + off_kd);
   int* flag = reinterpret_cast<int*>(D + off_fl); int* pos = reinterpret_cast<int*>(D + off_ps);
-  c->out_xyz = reinterpret_cast<double*>(D + off_x); c->out_nrm = normals ? reinterpret_cast<double*>(D + off_nr) : nullptr;
-  c->out_idx = reinterpret_cast<int*>(D + off_ix);
+  c->out.xyz = reinterpret_cast<double*>(D + off_x); c->out.nrm = normals ? reinterpret_cast<double*>(D + off_nr) : nullptr;
+  c->out.idx = reinterpret_cast<int*>(D + off_ix);
   size_t scan_bytes = 0;
   MV_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, flag, pos, 0, NN, rocprim::plus<int>(), st));
-  MV_CHECK(ensure_dev(&c->out_tmp, &c->out_tmp_bytes, std::max<size_t>(scan_bytes, 256)));
+  MV_CHECK(c->out.tmp.reserve(std::max<size_t>(scan_bytes, 256)));
 
   MV_HIP(hipMemsetAsync(d_ctl, 0, sizeof(OutCtl), st));
   KnnJob j;
@@ -255,7 +234,7 @@ long long outlier_filter(mvicp_ctx* c, const FrameDev& f, int k, double std_rati
   j.table = (const HashEntry*)g.table; j.mask = g.table_mask; j.shift = g.table_shift;
   j.ox = g.origin[0]; j.oy = g.origin[1]; j.oz = g.origin[2]; j.h = g.cell; j.inv_h = g.inv_cell;
   j.dx = g.dims[0]; j.dy = g.dims[1]; j.dz = g.dims[2];
-  j.k = k; j.mdist = c->out_mdist; j.kd2 = c->out_kd2; j.mmax = &d_ctl->mmax;
+  j.k = k; j.mdist = c->out.mdist; j.kd2 = c->out.kd2; j.mmax = &d_ctl->mmax;
   {
     ProfScope ps(c, "outlier_knn", 0.0);
     if (k <= 8) hipLaunchKernelGGL(outlier_knn_kernel<9>, dim3(grid_of(n, NT)), dim3(NT), 0, st, j);
@@ -278,7 +257,7 @@ long long outlier_filter(mvicp_ctx* c, const FrameDev& f, int k, double std_rati
       q = 31 - ex; stat = 1;
       {
         ProfScope ps(c, "outlier_sum", 8.0 * n);
-        hipLaunchKernelGGL(outlier_sum_kernel, dim3(grid_of(n, VT)), dim3(VT), 0, st, c->out_mdist, n, q, d_ctl);
+        hipLaunchKernelGGL(outlier_sum_kernel, dim3(grid_of(n, VT)), dim3(VT), 0, st, c->out.mdist, n, q, d_ctl);
       }
       MV_HIP(hipGetLastError());
       MV_HIP(hipMemcpyAsync(h_ctl, d_ctl, sizeof(OutCtl), hipMemcpyDeviceToHost, st));
@@ -291,15 +270,15 @@ long long outlier_filter(mvicp_ctx* c, const FrameDev& f, int k, double std_rati
   }
   {
     ProfScope ps(c, "outlier_flag", 20.0 * n);
-    hipLaunchKernelGGL(outlier_flag_kernel, dim3(grid_of(n, VT)), dim3(VT), 0, st, c->out_mdist, c->out_kd2, n, stat, q, T, rad_on ? 1 : 0, radius, flag);
+    hipLaunchKernelGGL(outlier_flag_kernel, dim3(grid_of(n, VT)), dim3(VT), 0, st, c->out.mdist, c->out.kd2, n, stat, q, T, rad_on ? 1 : 0, radius, flag);
   }
   MV_HIP(hipGetLastError());
   {
     ProfScope ps(c, "outlier_compact", (normals ? 108.0 : 60.0) * n);
     size_t tb = scan_bytes;
-    MV_HIP(rocprim::exclusive_scan(c->out_tmp, tb, flag, pos, 0, NN, rocprim::plus<int>(), st));
-    if (normals) hipLaunchKernelGGL(outlier_compact_kernel<true>, dim3(grid_of(n, VT)), dim3(VT), 0, st, f.pts, f.nor, flag, pos, n, c->out_xyz, c->out_nrm, c->out_idx, d_ctl);
-    else hipLaunchKernelGGL(outlier_compact_kernel<false>, dim3(grid_of(n, VT)), dim3(VT), 0, st, f.pts, f.nor, flag, pos, n, c->out_xyz, c->out_nrm, c->out_idx, d_ctl);
+    MV_HIP(rocprim::exclusive_scan(c->out.tmp.p, tb, flag, pos, 0, NN, rocprim::plus<int>(), st));
+    if (normals) hipLaunchKernelGGL(outlier_compact_kernel<true>, dim3(grid_of(n, VT)), dim3(VT), 0, st, f.pts, f.nor, flag, pos, n, c->out.xyz, c->out.nrm, c->out.idx, d_ctl);
+    else hipLaunchKernelGGL(outlier_compact_kernel<false>, dim3(grid_of(n, VT)), dim3(VT), 0, st, f.pts, f.nor, flag, pos, n, c->out.xyz, c->out.nrm, c->out.idx, d_ctl);
   }
   MV_HIP(hipGetLastError());
   MV_HIP(hipMemcpyAsync(h_ctl, d_ctl, sizeof(OutCtl), hipMemcpyDeviceToHost, st));
@@ -308,7 +287,7 @@ long long outlier_filter(mvicp_ctx* c, const FrameDev& f, int k, double std_rati
   if (kept < 0 || kept > n) { set_error("outlier filter: %d kept of %d", kept, n); return MVICP_ERR_INTERNAL; }
   S.kept = kept;
   if (stats) *stats = S;
-  c->out_n = n; c->out_kept = kept;
+  c->out.n = n; c->out.kept = kept;
   return kept;
 }
 

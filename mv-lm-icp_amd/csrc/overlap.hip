@@ -148,7 +148,6 @@ __global__ __launch_bounds__(NT) void overlap_kernel(const OvJob* __restrict__ j
   }
 }
 
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // the cloud's sample list for `s` samples of its n points: positions inv[floor(t n / s)], ascending
 int ensure_samples(GridDev& G, int n, int s) {

@@ -197,38 +197,10 @@ __global__ __launch_bounds__(VT) void vox_reduce_kernel(const VoxSrc* __restrict
   }
 }
 
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-int grid_of(long long n) { return (int)((n + VT - 1) / VT); }
-
-int ensure_dev(char** p, size_t* have, size_t need) {
-  if (need <= *have) return MVICP_OK;
-  if (*p) MV_HIP(hipFree(*p));
-  *p = nullptr; *have = 0;
-  MV_HIP(hipMalloc((void**)p, need));
-  *have = need;
-  return MVICP_OK;
-}
-
-void free_result(mvicp_ctx* c) {
-  if (c->vox_xyz) (void)hipFree(c->vox_xyz);
-  if (c->vox_nrm) (void)hipFree(c->vox_nrm);
-  if (c->vox_cnt) (void)hipFree(c->vox_cnt);
-  c->vox_xyz = nullptr; c->vox_nrm = nullptr; c->vox_cnt = nullptr; c->vox_m = -1; c->vox_has_normals = 0;
-}
-
 }  // namespace
 
-void free_voxel(mvicp_ctx* c) {
-  free_result(c);
-  if (c->vox_scratch) (void)hipFree(c->vox_scratch);
-  if (c->vox_tmp) (void)hipFree(c->vox_tmp);
-  if (c->vox_pin) (void)hipHostFree(c->vox_pin);
-  c->vox_scratch = nullptr; c->vox_tmp = nullptr; c->vox_pin = nullptr;
-  c->vox_scratch_bytes = 0; c->vox_tmp_bytes = 0; c->vox_pin_bytes = 0;
-}
-
 long long voxel_reduce(mvicp_ctx* c, int n_sel, const int* sel, const double* poses, double voxel, int* has_normals) {
-  free_result(c);   // (the last result lives until the next grid call)
+  c->vox.drop_result();   // (the last result lives until the next grid call)
   // the input sequence: the selected frames in order, empty ones left out
   std::vector<VoxSrc> srcs;
   long long total = 0;
@@ -250,8 +222,8 @@ long long voxel_reduce(mvicp_ctx* c, int n_sel, const int* sel, const double* po
     srcs.push_back(s);
   }
   if (has_normals) *has_normals = normals ? 1 : 0;
-  c->vox_has_normals = normals ? 1 : 0;
-  if (total == 0) { c->vox_m = 0; return 0; }
+  c->vox.has_normals = normals ? 1 : 0;
+  if (total == 0) { c->vox.m = 0; return 0; }
   const int N = (int)total, n_src = (int)srcs.size(), with_pose = poses ? 1 : 0;
   const bool permute = c->voxel_permute != 0;
   hipStream_t st = c->stream;
@@ -261,14 +233,9 @@ long long voxel_reduce(mvicp_ctx* c, int n_sel, const int* sel, const double* po
   const size_t off_ctl = align256(sizeof(VoxSrc) * n_src), off_cells = off_ctl + 256, off_ka = off_cells + align256(12 * NN), off_kb = off_ka + align256(8 * NN);
   const size_t off_sa = off_kb + align256(8 * NN), off_sb = off_sa + align256(4 * NN), off_rs = off_sb + align256(4 * NN), off_w = off_rs + align256(4 * (NN + 1));
   const size_t off_m = off_w + (permute ? align256(24 * NN) : 0), bytes = off_m + (permute && normals ? align256(24 * NN) : 0);
-  MV_CHECK(ensure_dev(&c->vox_scratch, &c->vox_scratch_bytes, bytes));
-  if (off_cells > c->vox_pin_bytes) {
-    if (c->vox_pin) MV_HIP(hipHostFree(c->vox_pin));
-    c->vox_pin = nullptr; c->vox_pin_bytes = 0;
-    MV_HIP(hipHostMalloc((void**)&c->vox_pin, off_cells, hipHostMallocDefault));
-    c->vox_pin_bytes = off_cells;
-  }
-  char* D = c->vox_scratch;
+  MV_CHECK(c->vox.scratch.reserve(bytes));
+  MV_CHECK(c->vox.pin.reserve(off_cells));
+  char* D = c->vox.scratch.p;
   const VoxSrc* d_src = reinterpret_cast<const VoxSrc*>(D);
   VoxCtl* d_ctl = reinterpret_cast<VoxCtl*>(D + off_ctl);
   int* cells = reinterpret_cast<int*>(D + off_cells);
@@ -280,12 +247,12 @@ long long voxel_reduce(mvicp_ctx* c, int n_sel, const int* sel, const double* po
   double* W = permute ? reinterpret_cast<double*>(D + off_w) : nullptr;
   double* M = permute && normals ? reinterpret_cast<double*>(D + off_m) : nullptr;
 
-  std::memcpy(c->vox_pin, srcs.data(), sizeof(VoxSrc) * n_src);
-  VoxCtl* h_ctl = reinterpret_cast<VoxCtl*>(c->vox_pin + off_ctl);
+  std::memcpy(c->vox.pin.p, srcs.data(), sizeof(VoxSrc) * n_src);
+  VoxCtl* h_ctl = reinterpret_cast<VoxCtl*>(c->vox.pin.p + off_ctl);
   for (int a = 0; a < 3; ++a) { h_ctl->cmin[a] = INT_MAX; h_ctl->cmax[a] = INT_MIN; }
   h_ctl->bad = 0; h_ctl->m = 0;
-  MV_HIP(hipMemcpyAsync(D, c->vox_pin, off_ctl + sizeof(VoxCtl), hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(vox_cell_kernel, dim3(grid_of(N)), dim3(VT), 0, st, d_src, n_src, N, with_pose, voxel, cells, d_ctl);
+  MV_HIP(hipMemcpyAsync(D, c->vox.pin.p, off_ctl + sizeof(VoxCtl), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(vox_cell_kernel, dim3(grid_of(N, VT)), dim3(VT), 0, st, d_src, n_src, N, with_pose, voxel, cells, d_ctl);
   MV_HIP(hipGetLastError());
   MV_HIP(hipMemcpyAsync(h_ctl, d_ctl, sizeof(VoxCtl), hipMemcpyDeviceToHost, st));
   MV_HIP(hipStreamSynchronize(st));
@@ -304,39 +271,39 @@ long long voxel_reduce(mvicp_ctx* c, int n_sel, const int* sel, const double* po
   MV_HIP(rocprim::radix_sort_pairs(nullptr, sort_bytes, key_a, key_b, seq_a, seq_b, NN, 0, bits, st));
   MV_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, head, rid, 0, NN, rocprim::plus<int>(), st));
   size_t tmp_bytes = std::max<size_t>(std::max(sort_bytes, scan_bytes), 256);
-  MV_CHECK(ensure_dev(&c->vox_tmp, &c->vox_tmp_bytes, tmp_bytes));
+  MV_CHECK(c->vox.tmp.reserve(tmp_bytes));
 
-  hipLaunchKernelGGL(vox_key_kernel, dim3(grid_of(N)), dim3(VT), 0, st, cells, N, h_ctl->cmin[0], h_ctl->cmin[1], h_ctl->cmin[2], d[0], d[1], key_a, seq_a);
+  hipLaunchKernelGGL(vox_key_kernel, dim3(grid_of(N, VT)), dim3(VT), 0, st, cells, N, h_ctl->cmin[0], h_ctl->cmin[1], h_ctl->cmin[2], d[0], d[1], key_a, seq_a);
   MV_HIP(hipGetLastError());
   size_t tb = sort_bytes;
-  MV_HIP(rocprim::radix_sort_pairs(c->vox_tmp, tb, key_a, key_b, seq_a, seq_b, NN, 0, bits, st));
-  hipLaunchKernelGGL(vox_head_kernel, dim3(grid_of(N)), dim3(VT), 0, st, key_b, N, head);
+  MV_HIP(rocprim::radix_sort_pairs(c->vox.tmp.p, tb, key_a, key_b, seq_a, seq_b, NN, 0, bits, st));
+  hipLaunchKernelGGL(vox_head_kernel, dim3(grid_of(N, VT)), dim3(VT), 0, st, key_b, N, head);
   MV_HIP(hipGetLastError());
   tb = scan_bytes;
-  MV_HIP(rocprim::exclusive_scan(c->vox_tmp, tb, head, rid, 0, NN, rocprim::plus<int>(), st));
-  hipLaunchKernelGGL(vox_start_kernel, dim3(grid_of(N)), dim3(VT), 0, st, head, rid, N, rstart, d_ctl);
+  MV_HIP(rocprim::exclusive_scan(c->vox.tmp.p, tb, head, rid, 0, NN, rocprim::plus<int>(), st));
+  hipLaunchKernelGGL(vox_start_kernel, dim3(grid_of(N, VT)), dim3(VT), 0, st, head, rid, N, rstart, d_ctl);
   MV_HIP(hipGetLastError());
   MV_HIP(hipMemcpyAsync(h_ctl, d_ctl, sizeof(VoxCtl), hipMemcpyDeviceToHost, st));
   MV_HIP(hipStreamSynchronize(st));
   const int m = h_ctl->m;
   if (m < 1 || m > N) { set_error("voxel grid: run count %d out of range [1, %d]", m, N); return MVICP_ERR_INTERNAL; }
 
-  MV_HIP(hipMalloc((void**)&c->vox_xyz, sizeof(double) * 3 * (size_t)m));
-  if (normals) MV_HIP(hipMalloc((void**)&c->vox_nrm, sizeof(double) * 3 * (size_t)m));
-  MV_HIP(hipMalloc((void**)&c->vox_cnt, sizeof(int) * (size_t)m));
+  MV_HIP(hipMalloc((void**)&c->vox.xyz, sizeof(double) * 3 * (size_t)m));
+  if (normals) MV_HIP(hipMalloc((void**)&c->vox.nrm, sizeof(double) * 3 * (size_t)m));
+  MV_HIP(hipMalloc((void**)&c->vox.cnt, sizeof(int) * (size_t)m));
   if (permute) {
-    if (normals) hipLaunchKernelGGL(vox_permute_kernel<true>, dim3(grid_of(N)), dim3(VT), 0, st, d_src, n_src, N, with_pose, seq_b, W, M);
-    else hipLaunchKernelGGL(vox_permute_kernel<false>, dim3(grid_of(N)), dim3(VT), 0, st, d_src, n_src, N, with_pose, seq_b, W, M);
+    if (normals) hipLaunchKernelGGL(vox_permute_kernel<true>, dim3(grid_of(N, VT)), dim3(VT), 0, st, d_src, n_src, N, with_pose, seq_b, W, M);
+    else hipLaunchKernelGGL(vox_permute_kernel<false>, dim3(grid_of(N, VT)), dim3(VT), 0, st, d_src, n_src, N, with_pose, seq_b, W, M);
     MV_HIP(hipGetLastError());
   }
 #define MV_VOX_REDUCE(NRM, PERM) \
-  hipLaunchKernelGGL((vox_reduce_kernel<NRM, PERM>), dim3(grid_of(m)), dim3(VT), 0, st, d_src, n_src, with_pose, seq_b, W, M, rstart, m, c->vox_xyz, c->vox_nrm, c->vox_cnt)
+  hipLaunchKernelGGL((vox_reduce_kernel<NRM, PERM>), dim3(grid_of(m, VT)), dim3(VT), 0, st, d_src, n_src, with_pose, seq_b, W, M, rstart, m, c->vox.xyz, c->vox.nrm, c->vox.cnt)
   if (normals) { if (permute) MV_VOX_REDUCE(true, true); else MV_VOX_REDUCE(true, false); }
   else { if (permute) MV_VOX_REDUCE(false, true); else MV_VOX_REDUCE(false, false); }
 #undef MV_VOX_REDUCE
   MV_HIP(hipGetLastError());
   MV_HIP(hipStreamSynchronize(st));
-  c->vox_m = m;
+  c->vox.m = m;
   return m;
 }
 

@@ -661,6 +661,21 @@ class Engine:
         mean_d2 = np.ldexp(sumq / np.maximum(hits, 1).astype(np.float64), -q.value)
         return {"samples": samples, "hits": hits, "sumq": sumq, "q_exp": int(q.value), "fraction": fraction, "mean_d2": mean_d2}
 
+    def _result_arrays(self, device):
+        """What the fetch half of a stage needs -> (mk, ptr, ready, f64, i32, i64, u8): mk(shape, dtype) makes a result array (numpy zeros,
+        or with device=True an uninitialised torch tensor on the engine's GPU), ptr(a) is its pointer or None for an absent or empty
+        array, ready() is called once between the last mk and the fetch (the allocations are the caller's; the library fills them on its
+        own stream and waits), and the rest are the dtypes for mk."""
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            return (lambda shape, dt: torch.empty(shape, dtype=dt, device=dev),
+                    lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None,
+                    lambda: torch.cuda.synchronize(dev), torch.float64, torch.int32, torch.int64, torch.uint8)
+        return (lambda shape, dt: np.zeros(shape, dtype=dt),
+                lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None,
+                lambda: None, np.float64, np.int32, np.int64, np.uint8)
+
     def voxel_grid(self, voxel, frames=None, poses=None, device=False):
         """mvicp_voxel_grid + mvicp_voxel_fetch: the points of `frames` (a list of distinct frame indices; None = all), at `poses` ((K,4,4);
         None = as stored), reduced to one point per voxel of edge `voxel` -> dict(xyz (m,3), nrm (m,3) or None, cnt (m,) int32), rows in
@@ -678,19 +693,9 @@ class Engine:
         st = self.lib.mvicp_voxel_grid(self.h, n_sel, fp, _dp(P) if P is not None else None, float(voxel), C.byref(hn))
         m = int(_check(self.lib, st))
         has_nrm = bool(hn.value)
-        if device:
-            import torch
-            dev = torch.device("cuda", self.device)
-            xyz = torch.empty((m, 3), dtype=torch.float64, device=dev)
-            nrm = torch.empty((m, 3), dtype=torch.float64, device=dev) if has_nrm else None
-            cnt = torch.empty((m,), dtype=torch.int32, device=dev)
-            torch.cuda.synchronize(dev)   # (the allocations are the caller's; the library fills them on its own stream and waits)
-            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and m else None
-        else:
-            xyz = np.zeros((m, 3), dtype=np.float64)
-            nrm = np.zeros((m, 3), dtype=np.float64) if has_nrm else None
-            cnt = np.zeros(m, dtype=np.int32)
-            ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and m else None
+        mk, ptr, ready, f64, i32, i64, u8 = self._result_arrays(device)
+        xyz, nrm, cnt = mk((m, 3), f64), (mk((m, 3), f64) if has_nrm else None), mk((m,), i32)
+        ready()
         _check(self.lib, self.lib.mvicp_voxel_fetch(self.h, m, ptr(xyz), ptr(nrm), ptr(cnt)))
         return {"xyz": xyz, "nrm": nrm, "cnt": cnt}
 
@@ -704,20 +709,10 @@ class Engine:
         kept = int(_check(self.lib, self.lib.mvicp_outlier_filter(self.h, int(frame), int(k), float(std_ratio), float(radius), C.byref(S))))
         n = int(S.n)
         has_nrm = bool(S.has_normals)
-        if device:
-            import torch
-            dev = torch.device("cuda", self.device)
-            mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
-            f64, i32 = torch.float64, torch.int32
-            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
-        else:
-            mk = lambda shape, dt: np.zeros(shape, dtype=dt)
-            f64, i32 = np.float64, np.int32
-            ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+        mk, ptr, ready, f64, i32, i64, u8 = self._result_arrays(device)
         xyz, nrm, idx = mk((kept, 3), f64), (mk((kept, 3), f64) if has_nrm else None), mk((kept,), i32)
         mdist, kd2 = mk((n,), f64), mk((n,), f64)
-        if device:
-            torch.cuda.synchronize(dev)   # (the allocations are the caller's; the library fills them on its own stream and waits)
+        ready()
         _check(self.lib, self.lib.mvicp_outlier_fetch(self.h, kept, ptr(xyz), ptr(nrm), ptr(idx), n, ptr(mdist), ptr(kd2)))
         return {"xyz": xyz, "nrm": nrm, "idx": idx, "mdist": mdist, "kd2": kd2, "stats": S.as_dict()}
 
@@ -748,19 +743,9 @@ class Engine:
             m = self.npts[int(frame)]
         k = int(k)
         entries = m * k if k else total
-        if device:
-            import torch
-            dev = torch.device("cuda", self.device)
-            mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
-            f64, i32, i64 = torch.float64, torch.int32, torch.int64
-            ptr = lambda t: C.c_void_p(t.data_ptr()) if t.numel() else None
-        else:
-            mk = lambda shape, dt: np.zeros(shape, dtype=dt)
-            f64, i32, i64 = np.float64, np.int32, np.int64
-            ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
+        mk, ptr, ready, f64, i32, i64, u8 = self._result_arrays(device)
         cnt, off, idx, d2 = mk((m,), i32), mk((m + 1,), i64), mk((entries,), i32), mk((entries,), f64)
-        if device:
-            torch.cuda.synchronize(dev)   # (the allocations are the caller's; the library fills them on its own stream and waits)
+        ready()
         _check(self.lib, self.lib.mvicp_knn_fetch(self.h, m, entries, ptr(cnt), ptr(off), ptr(idx), ptr(d2)))
         if k:
             idx, d2 = idx.reshape(m, k), d2.reshape(m, k)
@@ -772,15 +757,9 @@ class Engine:
         torch tensors on the engine's GPU instead of numpy arrays.  Afterwards the engine's last neighbour-search result is
         knn_search(frame, None, max_nn, radius).  Needs no graph; history-neutral."""
         n = int(_check(self.lib, self.lib.mvicp_fpfh(self.h, int(frame), float(radius), int(max_nn))))
-        if device:
-            import torch
-            dev = torch.device("cuda", self.device)
-            desc, used = torch.empty((n, 33), dtype=torch.float64, device=dev), torch.empty((n,), dtype=torch.int32, device=dev)
-            ptr = lambda t: C.c_void_p(t.data_ptr()) if t.numel() else None
-            torch.cuda.synchronize(dev)   # (the allocations are the caller's; the library fills them on its own stream and waits)
-        else:
-            desc, used = np.zeros((n, 33), dtype=np.float64), np.zeros((n,), dtype=np.int32)
-            ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
+        mk, ptr, ready, f64, i32, i64, u8 = self._result_arrays(device)
+        desc, used = mk((n, 33), f64), mk((n,), i32)
+        ready()
         _check(self.lib, self.lib.mvicp_fpfh_fetch(self.h, n, ptr(desc), ptr(used)))
         return {"desc": desc, "used": used}
 
@@ -793,20 +772,10 @@ class Engine:
         k = int(_check(self.lib, self.lib.mvicp_iss_keypoints(self.h, int(frame), float(salient_radius), float(non_max_radius), float(gamma21),
                                                               float(gamma32), int(min_neighbors))))
         n = self.npts[int(frame)]
-        if device:
-            import torch
-            dev = torch.device("cuda", self.device)
-            mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
-            f64, i32 = torch.float64, torch.int32
-            ptr = lambda t: C.c_void_p(t.data_ptr()) if t.numel() else None
-        else:
-            mk = lambda shape, dt: np.zeros(shape, dtype=dt)
-            f64, i32 = np.float64, np.int32
-            ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
+        mk, ptr, ready, f64, i32, i64, u8 = self._result_arrays(device)
         idx, xyz = mk((k,), i32), mk((k, 3), f64)
         sal, cs, cn = mk((n,), f64), mk((n,), i32), mk((n,), i32)
-        if device:
-            torch.cuda.synchronize(dev)   # (the allocations are the caller's; the library fills them on its own stream and waits)
+        ready()
         _check(self.lib, self.lib.mvicp_iss_fetch(self.h, k, ptr(idx), ptr(xyz), None, n, ptr(sal), ptr(cs), ptr(cn)))
         return {"idx": idx, "xyz": xyz, "saliency": sal, "cnt_salient": cs, "cnt_nms": cn}
 
@@ -839,19 +808,9 @@ class Engine:
             raise MvicpError(f"a has {ka.shape[1]} columns, b {kb.shape[1]}")
         got = int(_check(self.lib, self.lib.mvicp_feature_match(self.h, pa, m, pb, n, int(ka.shape[1]))))
         assert got == m
-        if device:
-            import torch
-            dev = torch.device("cuda", self.device)
-            mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
-            f64, i32 = torch.float64, torch.int32
-            ptr = lambda t: C.c_void_p(t.data_ptr()) if t.numel() else None
-        else:
-            mk = lambda shape, dt: np.zeros(shape, dtype=dt)
-            f64, i32 = np.float64, np.int32
-            ptr = lambda t: t.ctypes.data_as(C.c_void_p) if t.size else None
+        mk, ptr, ready, f64, i32, i64, u8 = self._result_arrays(device)
         fi, fd, bi, bd = mk((m, 2), i32), mk((m, 2), f64), mk((n, 2), i32), mk((n, 2), f64)
-        if device:
-            torch.cuda.synchronize(dev)   # (the allocations are the caller's; the library fills them on its own stream and waits)
+        ready()
         _check(self.lib, self.lib.mvicp_feature_match_fetch(self.h, m, n, ptr(fi), ptr(fd), ptr(bi), ptr(bd)))
         return {"fwd_idx": fi, "fwd_d2": fd, "bwd_idx": bi, "bwd_d2": bd}
 
@@ -914,15 +873,9 @@ class Engine:
         winner's inliers).  device=True: torch tensors on the engine's GPU."""
         counts = getattr(self, "_coarse_counts", None)
         c = counts[edge] if counts is not None and 0 <= int(edge) < len(counts) else 0
-        if device:
-            import torch
-            dev = torch.device("cuda", self.device)
-            pairs, flags = torch.zeros((c, 2), dtype=torch.int32, device=dev), torch.zeros((c,), dtype=torch.uint8, device=dev)
-            torch.cuda.synchronize(dev)   # (the allocations are the caller's; the library fills them on its own stream and waits)
-            ptr = lambda t: C.c_void_p(t.data_ptr()) if t.numel() else None
-        else:
-            pairs, flags = np.zeros((c, 2), dtype=np.int32), np.zeros(c, dtype=np.uint8)
-            ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
+        mk, ptr, ready, f64, i32, i64, u8 = self._result_arrays(device)
+        pairs, flags = mk((c, 2), i32), mk((c,), u8)
+        ready()
         _check(self.lib, self.lib.mvicp_coarse_pairs_fetch(self.h, int(edge), c, ptr(pairs), ptr(flags)))
         return pairs, flags
 
