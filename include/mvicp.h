@@ -8,6 +8,13 @@
  * library owns all device memory; the caller owns every host buffer it passes.  One context drives
  * one GPU (one process per GPU; see mvicp_set_shard / mvicp_comm_init for the multi-GPU path).
  *
+ * A REFUSED CALL CHANGES NOTHING.  An entry point that returns MVICP_ERR_ARG or MVICP_ERR_STATE for its arguments or the call order has
+ * decided so before it touched the context: clouds, structures, pending builds, the graph, lists, epochs, normals and options are what they
+ * were, and every later call computes what it would have computed without the refused one (tests/test_gpu_rejected_calls.py).  Only the
+ * error string, profile counters and performance-only state (a queued evaluation, the validity of a cache) may differ.  Each set-up entry
+ * below says what a non-OK return leaves; the exceptions are stated where they apply (mvicp_correspond: any non-OK return drops the
+ * cross-round state, see mvicp_correspondence_epochs; errors that are found on the device after work has begun).
+ *
  * Conventions
  *   pose    : 16 doubles, 4x4 COLUMN-major = Eigen::Isometry3d::data()  (include/frame.h:42)
  *   points  : n x 3 doubles AoS = &std::vector<Eigen::Vector3d>[0]      (include/frame.h:38-39)
@@ -66,6 +73,13 @@ int mvicp_destroy(mvicp_ctx* ctx);
  * structures themselves (k-d order, box hierarchy, matrix-pipe operands, hash) are built behind it on a host thread from a private copy
  * of the cloud, so that the clouds of an upload loop are built side by side (option "async_build", default 1); the first entry point that
  * needs a structure (mvicp_set_graph, mvicp_nn_query, mvicp_recompute_normals) waits for the pending builds and reports a failed one. */
+/* Non-OK returns.  mvicp_set_num_frames: n_frames < 0 -> MVICP_ERR_ARG, and the frames, the graph and every stage's last result stay.
+ * mvicp_set_frame: a frame index out of range, n < 0, xyz NULL with n > 0, a non-finite coordinate -> MVICP_ERR_ARG; called while a graph
+ * exists -> MVICP_ERR_STATE.  All of these are decided before the frame is touched (the coordinates are scanned first): the frame keeps
+ * the cloud it held, with its structures, its pending build and its answers, or stays empty if it was empty.  MVICP_ERR_HIP (an
+ * allocation or a copy failed after the old cloud was released) leaves the frame EMPTY (n = 0), never holding undefined bytes.  With
+ * "async_build" 0 a failed build is returned by this call and is sticky like a failed background build: the frame is unusable and says
+ * why until it is uploaded again. */
 int mvicp_set_num_frames(mvicp_ctx* ctx, int n_frames);
 int mvicp_set_frame(mvicp_ctx* ctx, int frame, const double* xyz, const double* nrm, int n);
 
@@ -76,7 +90,10 @@ int mvicp_set_frame(mvicp_ctx* ctx, int frame, const double* xyz, const double* 
  * library-owned buffers before it returns, so the caller may free or overwrite them afterwards.  Everything else is mvicp_set_frame's:
  * before mvicp_set_graph, a non-finite coordinate is MVICP_ERR_ARG reported by this call, option "async_build" moves the rest of the
  * build behind the call (a failed build is reported, sticky, by the next entry point that needs the structures).  The structures are
- * built on the GPU and are byte-identical to the ones mvicp_set_frame builds on the host for the same cloud and options. */
+ * built on the GPU and are byte-identical to the ones mvicp_set_frame builds on the host for the same cloud and options.
+ * Non-OK returns: as mvicp_set_frame's.  The finiteness / bounds reduction runs over the CALLER's array before the frame is touched, so
+ * MVICP_ERR_ARG (index, n, a NULL / host / foreign pointer, a non-finite coordinate) and MVICP_ERR_STATE (a graph exists) leave the frame
+ * exactly as it was; MVICP_ERR_HIP after the old cloud was released leaves it empty. */
 int mvicp_set_frame_device(mvicp_ctx* ctx, int frame, const double* d_xyz, const double* d_nrm, int n);
 
 /* Read-back seam of the per-cloud structures (tests, diagnosis).  Waits for pending builds, then copies the named array of `frame` into
@@ -94,11 +111,19 @@ long long mvicp_get_structure(mvicp_ctx* ctx, int frame, const char* name, void*
  * k nearest points INCLUDING itself (reference k = 10), flipped so n_z <= 0 (include/common.h:331-346).  Overwrites the
  * frame's device normals; nrm_out (n x 3) and knn_out (n x k original indices, nearest first) may be NULL.  May be called
  * at any time: correspondence lists that point into this frame are re-gathered with the new normals (the reference reads
- * dstCloud.nor when it builds the problem, icp-ceres.cpp:270-292). */
+ * dstCloud.nor when it builds the problem, icp-ceres.cpp:270-292).
+ * Non-OK returns: a frame index out of range, k outside [3, 16] -> MVICP_ERR_ARG; fewer than k points, a frame without structures (empty,
+ * or its build failed) -> MVICP_ERR_STATE.  All are decided before anything is allocated: the frame's normals are what they were, and a
+ * frame uploaded WITHOUT normals still has none (point-to-plane evaluation keeps refusing it).  If the launch itself fails, the buffers
+ * this call allocated for such a frame are released again; the normals of a frame that had some are then undefined until the next
+ * successful call. */
 int mvicp_recompute_normals(mvicp_ctx* ctx, int frame, int k, double* nrm_out, int* knn_out);
 
 /* Pose graph = all Frame::neighbours[j].neighbourIdx (frame.cpp:67-89 builds it; main_multiview.cpp:
- * 104-117).  Edge order is the reference's loop order: src ascending, then neighbour order. */
+ * 104-117).  Edge order is the reference's loop order: src ascending, then neighbour order.
+ * Non-OK returns: n_edges < 0, NULL lists with n_edges > 0, a frame index out of range, a self edge -> MVICP_ERR_ARG; a failed structure
+ * build -> MVICP_ERR_STATE.  All are decided before the previous graph is released: it, its lists and its epochs keep working.  A failure
+ * after that point (MVICP_ERR_HIP: an allocation) leaves a context whose graph must be set again. */
 int mvicp_set_graph(mvicp_ctx* ctx, int n_edges, const int* src, const int* dst);
 
 /* ---- overlap census and the pose graph made from it ----------------------------------------------------
@@ -473,7 +498,8 @@ int mvicp_graph_from_overlap(int n_frames, const int* samples, const int* hits, 
                              int skip_frame0, int cap, int* src, int* dst, int* n_components);
 
 /* Multi-GPU: this rank owns a contiguous chunk of the edge list (balanced by N_src).  Call before
- * mvicp_set_graph.  Default rank 0 of 1. */
+ * mvicp_set_graph.  Default rank 0 of 1.  Non-OK returns: world < 1 or rank outside [0, world) -> MVICP_ERR_ARG; called while a
+ * graph exists -> MVICP_ERR_STATE; rank and world stay what they were. */
 int mvicp_set_shard(mvicp_ctx* ctx, int rank, int world);
 /* The partition rule itself (pure host function, no context): owner[e] in [0, world) for edges with n_src[e]
  * source points each.  Contiguous chunks, balanced by source points. */
@@ -507,7 +533,9 @@ int mvicp_correspond(mvicp_ctx* ctx, const double* poses, const unsigned char* f
 int mvicp_reset_history(mvicp_ctx* ctx);
 /* Copy edge e's list back as Frame::neighbours[j].correspondances (frame.h:18-22): ascending `first`.
  * RETURNS THE NUMBER OF TRIPLES WRITTEN (>= 0, = counts[e] of the last mvicp_correspond) or a negative mvicp_status;
- * cap is the capacity of the three output arrays (each may be NULL to skip that field). */
+ * cap is the capacity of the three output arrays (each may be NULL to skip that field).
+ * Non-OK returns (this call and mvicp_map_correspondences): an edge out of range, cap < count, a NULL output -> MVICP_ERR_ARG; no list
+ * yet, an edge of another rank -> MVICP_ERR_STATE.  Nothing changes. */
 int mvicp_get_correspondences(mvicp_ctx* ctx, int edge, int cap, int* first, int* second, double* dist);
 /* ALL lists of the last mvicp_correspond at once, as the reference lays them out: `struct Correspondance {int first; int second; double
  * dist;}` (include/frame.h:18-22), ascending `first` within an edge (frame.cpp:129,156-160).  One device pass un-sorts every edge this
@@ -535,11 +563,16 @@ int mvicp_wait_correspondences(mvicp_ctx* ctx, int edge);
  * mvicp_correspond that does not return MVICP_OK drops the whole cross-round state, as mvicp_reset_history does) gives the edge a new, never repeated epoch.
  * *epochs -> n_edges counters owned by the library, valid until mvicp_set_graph / mvicp_destroy. */
 int mvicp_correspondence_epochs(mvicp_ctx* ctx, const unsigned long long** epochs);
-/* Install an explicit list (pairwise known-correspondence case, main_pairwise.cpp:60-61; tests). */
+/* Install an explicit list (pairwise known-correspondence case, main_pairwise.cpp:60-61; tests).
+ * Non-OK returns: an edge out of range, n < 0 or n > N_src, NULL lists with n > 0, an index out of range anywhere in the lists ->
+ * MVICP_ERR_ARG; an edge of another rank -> MVICP_ERR_STATE.  The whole list is checked before the edge is touched: the edge keeps the
+ * list it had (searched or explicit), its epoch and its weight. */
 int mvicp_set_correspondences(mvicp_ctx* ctx, int edge, int n, const int* first, const int* second, float weight);
 
 /* S1': batch form of Frame::getClosestPoint (frame.h:55, frame.cpp:187-206): queries are already in
- * the frame's local coordinates; returns index and SQUARED distance per query. */
+ * the frame's local coordinates; returns index and SQUARED distance per query.
+ * Non-OK returns: a frame out of range, n < 0, a NULL buffer with n > 0, an nn_method outside mvicp_nn_method -> MVICP_ERR_ARG, decided
+ * before anything is allocated or built; an empty frame, a failed structure build -> MVICP_ERR_STATE.  The call never changes a frame. */
 int mvicp_nn_query(mvicp_ctx* ctx, int frame, const double* queries, int n, int nn_method, int* idx, double* d2);
 
 /* ---- normal equations ---------------------------------------------------------------------------
@@ -548,6 +581,9 @@ int mvicp_nn_query(mvicp_ctx* ctx, int frame, const double* queries, int n, int 
  * Ceres accumulates from the residual blocks of include/icp-ceres.h:49-316 + SoftLOneLoss(edge.weight)
  * (icp-ceres.cpp:284,374,449).  out: n_edges x 91 = [78 upper-triangular row-major H | 12 g | cost]. */
 #define MVICP_EDGE_BLOCK 91
+/* Non-OK returns of both evaluations (and of mvicp_optimize, which evaluates): a NULL pointer -> MVICP_ERR_ARG; no graph, no list yet
+ * (neither mvicp_correspond nor mvicp_set_correspondences), point-to-plane while the target of a non-empty list has no normals ("...
+ * needs normals on frame i") -> MVICP_ERR_STATE.  Lists, epochs and poses are untouched; `out` is not written. */
 int mvicp_linearize(mvicp_ctx* ctx, const double* poses, int point_to_plane, int robust, double* out);
 /* Two evaluations on the SAME correspondences and scales: out_a = what mvicp_linearize gives at poses_a, out_b = what it gives at poses_b,
  * bit for bit.  On a single rank both come from one kernel that reads the operand stream once (the kernel is bandwidth-bound, so the pair
@@ -574,6 +610,9 @@ typedef struct mvicp_summary {
  * converged registration from being a fixed point of the round.  Costs in the summary are those of the round-tripped poses the
  * solver evaluates at (they differ from the returned ones by that last bit at most).  Callers that hand in a NON-orthonormal
  * rotation and rely on the write-back to repair it must orthonormalise it themselves. */
+/* Non-OK returns: a param outside mvicp_param -> MVICP_ERR_ARG; what mvicp_linearize refuses -> MVICP_ERR_STATE; `poses` come back as
+ * they were passed.  A step the trust region REJECTS is not an error: iterations counts it, successful_steps does not, and the solve goes
+ * on from the kept normal equations with a smaller radius (tests/test_gpu_lm_rejected.py). */
 int mvicp_optimize(mvicp_ctx* ctx, double* poses, unsigned char* fixed, int param, int point_to_plane, int robust,
                    int max_iterations /* reference: 50, icp-ceres.cpp:81 */, mvicp_summary* summary);
 
@@ -640,7 +679,10 @@ int mvicp_closedform_point_to_plane(const double* src, const double* dst, const 
  * flat sweep over the block boxes instead of the top-down walk (an experiment: faster only once the poses have settled); "prune_rho", "auto_settle", "auto_switch",
  * see DESIGN.md; "grid_curve" (default 2): device order of the clouds at the next mvicp_set_frame, 2 = balanced k-d order,
  * 1 / 0 = Hilbert / Morton index of the hash cell (nn_cell needs 0 or 1).  Tuning knobs: correspondences are
- * bit-identical for every setting. */
+ * bit-identical for every setting.
+ * Non-OK returns: a NULL or unknown name, a value outside the range its option states ("match_chunk" outside [1, 2^31), "grid_target"
+ * outside [0.5, 64], "tile_mu" outside (0, 1], "mfma_kacc" outside [1, 1024], "tile_miss" outside [0, 64], "nn_search_factor" < 0) ->
+ * MVICP_ERR_ARG; the option keeps its value. */
 int mvicp_set_option(mvicp_ctx* ctx, const char* name, double value);
 /* NN census accumulated while profiling and the "nn_census" option are on: counters in this order — queries, candidate points
  * examined, tree boxes / grid cells looked up, queries that needed the tree fallback, queries answered by the temporal cache,

@@ -595,23 +595,26 @@ int mvicp_set_frame(mvicp_ctx* c, int frame, const double* xyz, const double* nr
   if (frame < 0 || frame >= c->n_frames) { set_error("frame %d out of range [0,%d)", frame, c->n_frames); return MVICP_ERR_ARG; }
   if (n < 0 || (n > 0 && !xyz)) { set_error("bad cloud (n=%d)", n); return MVICP_ERR_ARG; }
   if (c->E) { set_error("set frames before mvicp_set_graph"); return MVICP_ERR_STATE; }
+  // every check comes before the frame is touched: a refused upload leaves the frame's cloud, structures and pending build as they were
+  double max_norm = 0.0;
+  for (int i = 0; i < n; ++i) {
+    const double* p = xyz + 3 * (size_t)i;
+    if (!std::isfinite(p[0]) || !std::isfinite(p[1]) || !std::isfinite(p[2])) { set_error("non-finite coordinate in cloud"); return MVICP_ERR_ARG; }   // (reported by this call, not by a later one)
+    max_norm = std::max(max_norm, std::sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]));
+  }
   FrameDev& f = c->frames[frame];
   if (f.job) { try { (void)f.job->fut.get(); } catch (...) {} f.job.reset(); }   // a build of the cloud this call replaces
   dev_free(f.pts); dev_free(f.nor); free_grid(f.grid); free_tie(f);
   f.has_grid = false; f.build_error.clear();
-  f.n = n;
+  f.n = 0; f.max_norm = 0.0;   // (a failed allocation or copy below leaves an empty frame, not a cloud of undefined bytes)
   MV_CHECK(dev_alloc(&f.pts, 3 * (size_t)n));
   if (n) MV_HIP(hipMemcpy(f.pts, xyz, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice));
   if (nrm) {
     MV_CHECK(dev_alloc(&f.nor, 3 * (size_t)n));
     if (n) MV_HIP(hipMemcpy(f.nor, nrm, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice));
   }
-  f.max_norm = 0.0;
-  for (int i = 0; i < n; ++i) {
-    const double* p = xyz + 3 * (size_t)i;
-    if (!std::isfinite(p[0]) || !std::isfinite(p[1]) || !std::isfinite(p[2])) { set_error("non-finite coordinate in cloud"); return MVICP_ERR_ARG; }   // (reported by this call, not by a later one)
-    f.max_norm = std::max(f.max_norm, std::sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]));
-  }
+  f.n = n;
+  f.max_norm = max_norm;
   if (n == 0) return MVICP_OK;
   if (!c->async_build) {
     const int st = build_frame_structures(c, f, xyz, nrm);
@@ -667,26 +670,32 @@ int mvicp_set_frame_device(mvicp_ctx* c, int frame, const double* d_xyz, const d
     MV_CHECK(check_device_pointer(c, d_xyz, "xyz"));
     if (d_nrm) MV_CHECK(check_device_pointer(c, d_nrm, "nrm"));
   }
+  // The one reduction the call itself needs -- finiteness (reported by this call), max_norm, the bounding box and max |coordinate| of the
+  // build -- runs over the CALLER's array before the frame is touched: a refused upload leaves the frame's cloud, structures and pending
+  // build as they were.  (The library's copy below holds the same bytes, so the build sees the same bounds.)
+  const auto t0 = std::chrono::steady_clock::now();
+  DevBounds b;
+  std::memset(&b, 0, sizeof(b));
+  if (n > 0) {
+    MV_CHECK(device_bounds(c->stream, d_xyz, n, &b));
+    if (b.nonfinite) { set_error("non-finite coordinate in cloud"); return MVICP_ERR_ARG; }
+  }
   FrameDev& f = c->frames[frame];
   if (f.job) { try { (void)f.job->fut.get(); } catch (...) {} f.job.reset(); }   // a build of the cloud this call replaces
   dev_free(f.pts); dev_free(f.nor); free_grid(f.grid); free_tie(f);
   f.has_grid = false; f.build_error.clear();
-  f.n = n;
-  f.max_norm = 0.0;
-  // library-owned copies (the caller may reuse its buffers once this call returns), then the one reduction the call itself needs:
-  // finiteness (reported by this call), max_norm, the bounding box and max |coordinate| of the build
+  f.n = 0; f.max_norm = 0.0;   // (a failed allocation or copy below leaves an empty frame, not a cloud of undefined bytes)
+  // library-owned copies, complete when the call returns: the caller may reuse its buffers, and the build reads them on a stream of its own
   MV_CHECK(dev_alloc(&f.pts, 3 * (size_t)n));
   if (n) MV_HIP(hipMemcpyAsync(f.pts, d_xyz, sizeof(double) * 3 * (size_t)n, hipMemcpyDeviceToDevice, c->stream));
   if (d_nrm) {
     MV_CHECK(dev_alloc(&f.nor, 3 * (size_t)n));
     if (n) MV_HIP(hipMemcpyAsync(f.nor, d_nrm, sizeof(double) * 3 * (size_t)n, hipMemcpyDeviceToDevice, c->stream));
   }
-  if (n == 0) { MV_HIP(hipStreamSynchronize(c->stream)); return MVICP_OK; }
-  const auto t0 = std::chrono::steady_clock::now();
-  DevBounds b;
-  MV_CHECK(device_bounds(c->stream, f.pts, n, &b));
+  MV_HIP(hipStreamSynchronize(c->stream));
+  f.n = n;
+  if (n == 0) return MVICP_OK;
   b.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  if (b.nonfinite) { set_error("non-finite coordinate in cloud"); return MVICP_ERR_ARG; }
   f.max_norm = b.max_norm;
   const int curve = c->grid_curve;
   const double target = c->grid_target;
@@ -773,11 +782,17 @@ int mvicp_recompute_normals(mvicp_ctx* c, int frame, int k, double* nrm_out, int
   MV_CHECK(finish_builds(c));
   FrameDev& f = c->frames[frame];
   if (f.n < k) { set_error("frame %d has %d points < k = %d (common.h:333 asserts >= 3)", frame, f.n, k); return MVICP_ERR_STATE; }
-  if (!f.nor) MV_CHECK(dev_alloc(&f.nor, 3 * (size_t)f.n));
-  if (!f.grid.snor) MV_CHECK(dev_alloc(&f.grid.snor, 3 * (size_t)f.n));
+  // launch_normals' own conditions, decided before anything is allocated: a refused call must not leave a frame without normals holding
+  // normal buffers nobody has written (check_evaluable and the gather take a non-null snor for "this frame has normals")
+  if (k < 3 || k > 16) { set_error("k = %d outside [3, 16]", k); return MVICP_ERR_ARG; }
+  if (!f.has_grid) { set_error("frame %d: normals need the per-cloud hash structure", frame); return MVICP_ERR_STATE; }
+  const bool fresh_nor = !f.nor, fresh_snor = !f.grid.snor;
   int* d_knn = nullptr;
-  if (knn_out) MV_CHECK(dev_alloc(&d_knn, (size_t)f.n * k));
-  int st = launch_normals(c, f, k, d_knn);
+  int st = MVICP_OK;
+  if (fresh_nor) st = dev_alloc(&f.nor, 3 * (size_t)f.n);
+  if (st == MVICP_OK && fresh_snor) st = dev_alloc(&f.grid.snor, 3 * (size_t)f.n);
+  if (st == MVICP_OK && knn_out) st = dev_alloc(&d_knn, (size_t)f.n * k);
+  if (st == MVICP_OK) st = launch_normals(c, f, k, d_knn);
   if (st == MVICP_OK) {
     hipError_t e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess && nrm_out) e = hipMemcpy(nrm_out, f.nor, sizeof(double) * 3 * (size_t)f.n, hipMemcpyDeviceToHost);
@@ -785,6 +800,11 @@ int mvicp_recompute_normals(mvicp_ctx* c, int frame, int k, double* nrm_out, int
     if (e != hipSuccess) { set_error("recompute_normals: %s", hipGetErrorString(e)); st = MVICP_ERR_HIP; }
   }
   dev_free(d_knn);
+  if (st != MVICP_OK) {   // what this call allocated goes with it: the frame has normals only if a call computed them
+    (void)hipStreamSynchronize(c->stream);
+    if (fresh_nor) dev_free(f.nor);
+    if (fresh_snor) dev_free(f.grid.snor);
+  }
   c->spec_ready = false; c->spec2_ready = false;
   if (st == MVICP_OK && c->E > 0) {
     // The packed operand stream bakes the dst normals in (n and c = n . q, gathered at correspond time) while the reference
@@ -2033,6 +2053,7 @@ int mvicp_set_correspondences(mvicp_ctx* c, int edge, int n, const int* first, c
   if (!c->owned[edge]) { set_error("edge %d is owned by another rank", edge); return MVICP_ERR_STATE; }
   const int ns = c->frames[c->esrc[edge]].n, nd = c->frames[c->edst[edge]].n;
   if (n < 0 || n > ns) { set_error("n=%d exceeds the edge capacity N_src=%d", n, ns); return MVICP_ERR_ARG; }
+  if (n > 0 && (!first || !second)) { set_error("null correspondence list (n=%d)", n); return MVICP_ERR_ARG; }
   for (int i = 0; i < n; ++i)
     if (first[i] < 0 || first[i] >= ns || second[i] < 0 || second[i] >= nd) { set_error("correspondence %d out of range", i); return MVICP_ERR_ARG; }
   const size_t off = (size_t)c->cap_off[edge];
@@ -2075,6 +2096,7 @@ int mvicp_nn_query(mvicp_ctx* c, int frame, const double* queries, int n, int nn
   MV_CHECK(bind(c));
   if (frame < 0 || frame >= c->n_frames) { set_error("frame %d out of range", frame); return MVICP_ERR_ARG; }
   if (n < 0 || (n && (!queries || !idx || !d2))) { set_error("bad query buffers"); return MVICP_ERR_ARG; }
+  if (nn_method < MVICP_NN_AUTO || nn_method > MVICP_NN_TILE) { set_error("unknown nn_method %d", nn_method); return MVICP_ERR_ARG; }   // (before anything is allocated or built)
   MV_CHECK(finish_builds(c));
   const FrameDev& f = c->frames[frame];
   if (f.n == 0) { set_error("frame %d is empty (nanoflann throws here: nanoflann.hpp:904)", frame); return MVICP_ERR_STATE; }

@@ -586,7 +586,8 @@ static void lm_solve(const Problem& pb, double* x /* K x ambient, in/out */, int
     double sn = 0.0;
     for (int i = 0; i < K; ++i) if (!pb.fixed[i]) for (int a = 0; a < A; ++a) { const double dd = x[i * A + a] - xc[i * A + a]; sn += dd * dd; }
     const double step_norm = std::sqrt(sn);
-    if (trace) std::fprintf(stderr, "[orc lm] it %d cost %.6e cand %.6e step_norm %.3e x_norm %.3e radius %.3e model_change %.3e\n", iter, cost, cand_cost, step_norm, x_norm, radius, model_cost_change);
+    // (cost, cand and model_change with every digit: tests/lmreject.py recomputes relative_decrease from this line)
+    if (trace) std::fprintf(stderr, "[orc lm] it %d cost %.17g cand %.17g step_norm %.3e x_norm %.3e radius %.3e model_change %.17g\n", iter, cost, cand_cost, step_norm, x_norm, radius, model_cost_change);
     if (step_norm <= parameter_tolerance * (x_norm + parameter_tolerance)) { sm->termination = 2; break; }
     const double cost_change = cost - cand_cost;
     const bool ftol = std::fabs(cost_change) <= function_tolerance * cost;

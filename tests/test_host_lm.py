@@ -143,3 +143,66 @@ def test_product_lm_reproduces_the_readme_vector(orc):
         dt = orc.pose_diff(P, Pout[1])[0]
         assert sm["termination"] == 2 and sm["iterations"] == 6, sm
         assert abs(dt / K["readme_dt"][param] - 1) < 1e-4, (param, dt)   # (1e-10-sized quantity out of 1e-16-relative arithmetic: 4+ digits)
+
+
+# ---------------------------------------------------------------- solves that reject steps (tests/lmreject.py)
+@pytest.fixture(scope="module")
+def rej_world(orc):
+    import lmreject
+    pb, corr, w = lmreject.lists_at_init(orc)
+    return {"pb": pb, "corr": corr, "w": w}
+
+
+def _rej_solve_both(orc, W, case, max_iterations):
+    import lmreject
+    angle, plane, robust, param = case
+    pb, corr, w = W["pb"], W["corr"], W["w"]
+    P0 = lmreject.start_poses(pb, angle)
+    prob = orc.make_problem(pb["pts"], pb["nor"], pb["fixed"], pb["src"], pb["dst"], corr, w, param, plane, robust)
+    ev = lambda poses: orc.edge_blocks(pb["pts"], pb["nor"], pb["src"], pb["dst"], corr, w, poses, plane, robust)
+    P, sm = L.lm_solve_host(len(pb["pts"]), pb["src"], pb["dst"], P0, pb["fixed"], param, ev, max_iterations)
+    return prob, P0, P, sm
+
+
+def _rej_cases():
+    import lmreject
+    return [pytest.param(c, id=lmreject.case_id(c)) for c in lmreject.CASES]
+
+
+@pytest.mark.parametrize("case", _rej_cases())
+def test_lm_rejected_steps_match_oracle(orc, rej_world, case, monkeypatch, capfd):
+    """The trust-region loop's other half: a start 1.5 / 3.0 rad away from the poses the lists were searched at makes the solve REJECT steps
+    (radius /= decrease_factor, the reused diagonal, H / g kept) — no other test does; tests/lmreject.py has the recipe and the measured counts.
+    Iterations, successful steps and termination must equal the oracle's, the poses within the file's 1e-9.  A case of lmreject.REJECTING is
+    admitted only while the ORACLE's own solve rejects (iterations - successful_steps >= 2: the stopping iteration is never successful)."""
+    import lmreject
+    prob, P0, P, sm = _rej_solve_both(orc, rej_world, case, 50)
+    P_ref, sm_ref, rd = lmreject.traced_optimize(orc, prob, P0, 50, monkeypatch, capfd)
+    margin = lmreject.decision_margin(rd)
+    print(lmreject.case_id(case), "oracle", sm_ref["iterations"], "/", sm_ref["successful_steps"], "termination", sm_ref["termination"],
+          "| product", sm["iterations"], "/", sm["successful_steps"], "termination", sm["termination"],
+          "| rejected", int((rd <= lmreject.MIN_RELATIVE_DECREASE).sum()), "| min |relative_decrease - 1e-3| = %.3e" % margin)
+    if case in lmreject.REJECTING:
+        assert sm_ref["iterations"] - sm_ref["successful_steps"] >= 2, sm_ref
+        assert int((rd <= lmreject.MIN_RELATIVE_DECREASE).sum()) >= 1, rd
+    assert (sm_ref["iterations"], sm_ref["successful_steps"]) == lmreject.MEASURED[case], sm_ref   # (the recorded counts are the oracle's)
+    assert sm["iterations"] == sm_ref["iterations"] and sm["successful_steps"] == sm_ref["successful_steps"], (sm, sm_ref)
+    assert sm["termination"] == sm_ref["termination"], (sm, sm_ref)
+    for k in range(len(P)):
+        dt, dr = synth.pose_diff(P[k], P_ref[k])
+        assert dt < 1e-9 and dr < 1e-9, (k, dt, dr)
+    # what tests/test_gpu_lm_rejected.py relies on when it asserts equal COUNTS for blocks that agree to 1e-11: no accept / reject decision
+    # of the case is closer than 1e-6 to the threshold
+    assert margin > 1e-6, (margin, rd)
+
+
+@pytest.mark.parametrize("case", _rej_cases())
+def test_lm_rejected_steps_stop_at_the_iteration_limit(orc, rej_world, case):
+    """The same lists and starts with max_iterations = 3: both solvers stop on the limit (termination 0) with the same poses."""
+    prob, P0, P, sm = _rej_solve_both(orc, rej_world, case, 3)
+    P_ref, sm_ref = orc.optimize(prob, P0, 3)
+    assert sm_ref["termination"] == 0 and sm_ref["iterations"] == 3, sm_ref
+    assert sm["termination"] == 0 and sm["iterations"] == 3 and sm["successful_steps"] == sm_ref["successful_steps"], (sm, sm_ref)
+    for k in range(len(P)):
+        dt, dr = synth.pose_diff(P[k], P_ref[k])
+        assert dt < 1e-9 and dr < 1e-9, (k, dt, dr)
