@@ -591,6 +591,29 @@ int mvicp_linearize(mvicp_ctx* ctx, const double* poses, int point_to_plane, int
  * not touch the evaluations mvicp_correspond queued ahead, nor their buffers.  Profile scope: "linearize_pair". */
 int mvicp_linearize_pair(mvicp_ctx* ctx, const double* poses_a, const double* poses_b, int point_to_plane, int robust, double* out_a, double* out_b);
 
+/* The objective by name.  POINT and PLANE are the reference's two (mvicp_linearize with point_to_plane 0 / 1; any non-zero flag there is
+ * PLANE).  SYMMETRIC is the symmetric point-to-plane objective (Rusinkiewicz, SIGGRAPH 2019): with p~ the source point in the dst frame
+ * and nu the source normal rotated into it,
+ *     r = m . (p~ - q),  m = (n_q + nu) / 2,
+ * the residual along the MEAN of the two normals: zero at the true pose wherever the surface is locally quadratic between the two
+ * samples, where the point-to-plane residual n_q . (p~ - q) keeps a curvature bias.  The factor 1/2 makes r the point-to-plane residual
+ * when the two normals agree, so the loss, the scale a = edge.weight and the cost sum rho / 2 are those of PLANE.  Per row
+ * u = [m ; (p~ x n_q + q x nu) / 2], J = [Ad^T u ; -u] in the coordinates above (csrc/linearize_sym.hip).
+ * THE NORMALS ARE USED AS STORED: no sign flip, no normalisation.  Orienting the normals of the clouds consistently with each other
+ * (the same side of the surface in every frame) is the caller's job; with opposite orientations m is half the DIFFERENCE of the normals.
+ * The source normal is the source frame's current one: after mvicp_recompute_normals the next evaluation sees the new normals.
+ * For this objective the relative transform of an edge is formed with the true inverse of the destination's rotation, in extended
+ * precision (for a rotation that is its transpose): the result does not depend on how far the given poses are from orthonormal to the
+ * last bit.  (A destination matrix that is no rotation at all, determinant outside (0.5, 2), gets the transpose like the other objectives:
+ * finite values, meaningless blocks.)  Accuracy contract: tests/test_gpu_sym_accuracy.py (32 x a plain fp64 evaluation's error against a long-double reference). */
+typedef enum { MVICP_METRIC_POINT = 0, MVICP_METRIC_PLANE = 1, MVICP_METRIC_SYMMETRIC = 2 } mvicp_metric;
+/* mvicp_linearize with the objective named.  Metric 0 / 1 ARE mvicp_linearize(point_to_plane = 0 / 1): same code path, same bytes, the
+ * same use of the evaluations mvicp_correspond queued ahead.  SYMMETRIC always takes the ordinary route (relative transforms and scales
+ * uploaded, one launch, the all-reduce when an exchange is configured, one wait; profile scope "linearize_sym") and is never queued or
+ * paired.  Non-OK returns as mvicp_linearize, and: a metric outside mvicp_metric -> MVICP_ERR_ARG; SYMMETRIC while the destination OR the
+ * source of a non-empty list has no normals ("symmetric needs normals on frame i") -> MVICP_ERR_STATE. */
+int mvicp_linearize_metric(mvicp_ctx* ctx, const double* poses, int metric, int robust, double* out);
+
 /* ---- S2: the LM solve ----------------------------------------------------------------------------
  * Replaces ICP_Ceres::ceresOptimizer / _ceresAngleAxis / _sophusSE3 (frames, pointToPlane, robust)
  * (include/icp-ceres.h:40-42; caller main_multiview.cpp:158-161).  poses in/out (frames[i]->pose).
@@ -615,6 +638,11 @@ typedef struct mvicp_summary {
  * on from the kept normal equations with a smaller radius (tests/test_gpu_lm_rejected.py). */
 int mvicp_optimize(mvicp_ctx* ctx, double* poses, unsigned char* fixed, int param, int point_to_plane, int robust,
                    int max_iterations /* reference: 50, icp-ceres.cpp:81 */, mvicp_summary* summary);
+/* mvicp_optimize with the objective named (mvicp_metric above).  Metric 0 / 1 ARE mvicp_optimize(point_to_plane = 0 / 1), including the
+ * arming of the evaluations the next mvicp_correspond queues ahead.  A SYMMETRIC solve arms nothing and voids what is queued, as a failed
+ * solve does: the search after it queues no evaluation.  A metric outside mvicp_metric -> MVICP_ERR_ARG. */
+int mvicp_optimize_metric(mvicp_ctx* ctx, double* poses, unsigned char* fixed, int param, int metric, int robust,
+                          int max_iterations, mvicp_summary* summary);
 
 /* Host-only form of the same solver over a caller-supplied evaluator (no GPU touched by this call):
  * eval(user, poses[n_frames x 16], blocks[n_edges x 91]) must fill the per-edge canonical blocks exactly

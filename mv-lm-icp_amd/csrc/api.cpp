@@ -158,6 +158,7 @@ void free_graph(mvicp_ctx* c) {
   dev_free(c->d_cd2); dev_free(c->d_qpos); dev_free(c->d_dirty_slots); dev_free(c->d_dslot_off); dev_free(c->d_stream); dev_free(c->d_cblock_off); dev_free(c->d_cblock_cnt);
   dev_free(c->d_sel_hist); dev_free(c->d_median); dev_free(c->d_chunk_edge); dev_free(c->d_chunk_start);
   dev_free(c->d_chunk_first); dev_free(c->d_partials); dev_free(c->d_out);
+  c->sym_lo_pin.release(); c->sym_lo_dev.release();
   if (c->h_pin) (void)hipHostFree(c->h_pin);
   c->h_pin = nullptr; c->h_pin_doubles = 0; c->d_res_host = nullptr; c->d_blocks_host = nullptr; c->lin_out = nullptr;
   c->census_pending = false; c->spec_ready = false; c->spec2_ready = false; c->spec_arm = false; c->d_spec_host = nullptr; c->d_adev_host = nullptr; c->d_res_target = nullptr; c->d_a_check = nullptr;
@@ -285,6 +286,55 @@ static void fill_rel_into(mvicp_ctx* c, const double* poses, double* h) {
 int upload_rel(mvicp_ctx* c, const double* poses) {
   fill_rel(c, poses);
   MV_HIP(hipMemcpyAsync(c->d_rel, c->h_pin + c->ctl_r2_off, sizeof(double) * c->ctl_r2, hipMemcpyHostToDevice, c->stream));
+  return MVICP_OK;
+}
+
+// The symmetric objective's relative transforms.  Its residual m . (A p + t - q) is a small difference of large terms in which an error of the
+// relative transform is COMMON to all correspondences of the edge, so it adds up over N terms where the residuals themselves add up like sqrt(N):
+// the fp64 rounding of (A, t), and the defect of R_d^T against R_d^-1 for a pose that is orthonormal to a few eps only, would cost g a factor
+// sqrt(N) (|t| + |p|) / |r| (measured: 80 - 600 x the error of a plain fp64 evaluation in the world frame, tests/test_gpu_sym_accuracy.py).  So
+// A = R_d^-1 R_s and t = R_d^-1 (t_s - t_d) are formed with the TRUE inverse in extended precision (for a rotation R_d^-1 = R_d^T) and split into
+// hi + lo: hi goes where fill_rel puts the relative transform (the kernel's moments and reduce_expand_kernel read it), lo to a small buffer of
+// its own (sym_lo_pin -> sym_lo_dev, copied in stream order right behind the control block), which the kernel adds to the residual only.
+// A destination matrix whose determinant is not within (0.5, 2) is no rotation: for it the transpose is used, as fill_rel does.
+static void fill_rel_sym(mvicp_ctx* c, const double* poses, double* h, double* lo) {
+  typedef long double ld;
+  for (int e = 0; e < c->E; ++e) {
+    const double* Ps = poses + 16 * (size_t)c->esrc[e];
+    const double* Pd = poses + 16 * (size_t)c->edst[e];
+    ld M[3][3];
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) M[i][j] = Pd[i + 4 * j];
+    ld C[3][3];   // cofactors
+    C[0][0] = M[1][1] * M[2][2] - M[1][2] * M[2][1]; C[0][1] = M[1][2] * M[2][0] - M[1][0] * M[2][2]; C[0][2] = M[1][0] * M[2][1] - M[1][1] * M[2][0];
+    C[1][0] = M[0][2] * M[2][1] - M[0][1] * M[2][2]; C[1][1] = M[0][0] * M[2][2] - M[0][2] * M[2][0]; C[1][2] = M[0][1] * M[2][0] - M[0][0] * M[2][1];
+    C[2][0] = M[0][1] * M[1][2] - M[0][2] * M[1][1]; C[2][1] = M[0][2] * M[1][0] - M[0][0] * M[1][2]; C[2][2] = M[0][0] * M[1][1] - M[0][1] * M[1][0];
+    ld det = M[0][0] * C[0][0] + M[0][1] * C[0][1] + M[0][2] * C[0][2];
+    if (!(det > 0.5L && det < 2.0L)) {
+      // not a rotation (a degenerate or reflected matrix): no inverse worth forming.  Use the transpose, as fill_rel does, so that the values stay finite
+      for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) C[i][j] = M[i][j];
+      det = 1.0L;
+    }
+    ld v[kEdgeRel];
+    const ld dt[3] = {(ld)Ps[12] - (ld)Pd[12], (ld)Ps[13] - (ld)Pd[13], (ld)Ps[14] - (ld)Pd[14]};
+    for (int i = 0; i < 3; ++i) {
+      const ld inv_i[3] = {C[0][i] / det, C[1][i] / det, C[2][i] / det};   // row i of R_d^-1
+      for (int j = 0; j < 3; ++j) v[i + 3 * j] = inv_i[0] * (ld)Ps[0 + 4 * j] + inv_i[1] * (ld)Ps[1 + 4 * j] + inv_i[2] * (ld)Ps[2 + 4 * j];
+      v[9 + i] = inv_i[0] * dt[0] + inv_i[1] * dt[1] + inv_i[2] * dt[2];
+    }
+    for (int k = 0; k < kEdgeRel; ++k) {
+      const double hi = (double)v[k];
+      h[(size_t)e * kEdgeRel + k] = hi;
+      lo[(size_t)e * kEdgeRel + k] = (double)(v[k] - (ld)hi);
+    }
+  }
+}
+int upload_rel_sym(mvicp_ctx* c, const double* poses) {
+  const size_t bytes = sizeof(double) * (size_t)c->E * kEdgeRel;
+  MV_CHECK(c->sym_lo_pin.reserve(bytes));   // (every evaluation ends with a wait for the stream, so the previous copy out of this buffer is done)
+  MV_CHECK(c->sym_lo_dev.reserve(bytes));
+  fill_rel_sym(c, poses, c->h_pin + c->ctl_r2_off, (double*)c->sym_lo_pin.p);
+  MV_HIP(hipMemcpyAsync(c->d_rel, c->h_pin + c->ctl_r2_off, sizeof(double) * c->ctl_r2, hipMemcpyHostToDevice, c->stream));
+  MV_HIP(hipMemcpyAsync(c->sym_lo_dev.p, c->sym_lo_pin.p, bytes, hipMemcpyHostToDevice, c->stream));
   return MVICP_OK;
 }
 
@@ -422,9 +472,17 @@ static void throttle_builds(mvicp_ctx* c) {
 }
 
 // One device evaluation of all per-edge blocks at `poses` -> host `out` (E x 91), all-reduced over ranks.
-static int check_evaluable(mvicp_ctx* c, int plane) {
+// (`metric` is an mvicp_metric: 0 point, 1 plane, 2 symmetric — the older entry points hand in their point_to_plane flag as 0 / 1)
+static int check_evaluable(mvicp_ctx* c, int metric) {
   if (!c->have_corr) { set_error("no correspondences: call mvicp_correspond or mvicp_set_correspondences first"); return MVICP_ERR_STATE; }
-  if (plane) {
+  if (metric == MVICP_METRIC_SYMMETRIC) {
+    // the mean normal needs both: the destination's (baked into the operand stream) and the source's (read from its sorted normals)
+    for (int e = 0; e < c->E; ++e)
+      if (c->owned[e] && c->h_count[e] > 0) {
+        const int missing = c->frames[c->edst[e]].grid.snor == nullptr ? c->edst[e] : c->frames[c->esrc[e]].grid.snor == nullptr ? c->esrc[e] : -1;
+        if (missing >= 0) { set_error("symmetric needs normals on frame %d", missing); return MVICP_ERR_STATE; }
+      }
+  } else if (metric) {
     for (int e = 0; e < c->E; ++e)
       if (c->owned[e] && c->h_count[e] > 0 && c->frames[c->edst[e]].grid.snor == nullptr) {
         set_error("point-to-plane needs normals on frame %d", c->edst[e]);
@@ -451,6 +509,13 @@ int evaluate_pair(mvicp_ctx* c, const double* poses_a, const double* poses_b, in
   return MVICP_OK;
 }
 
+// One launch of the metric's accumulation kernel + the per-edge expansion on the uploaded relative transforms
+static int launch_metric(mvicp_ctx* c, int metric, int robust) {
+  return metric == MVICP_METRIC_SYMMETRIC ? launch_linearize_sym(c, robust) : launch_linearize(c, metric, robust);
+}
+
+// `plane` is the metric (0 point, 1 plane, 2 symmetric).  Only point and plane evaluations are ever queued ahead, so a symmetric one matches no
+// queued result (spec_q_plane / spec2_plane are 0 or 1), drops them like any evaluation they were not made for, and takes the ordinary route below.
 int evaluate_blocks(mvicp_ctx* c, const double* poses, int plane, int robust, double* out) {
   MV_CHECK(check_evaluable(c, plane));
   HostScope hs(c, "host.evaluate");
@@ -485,9 +550,9 @@ int evaluate_blocks(mvicp_ctx* c, const double* poses, int plane, int robust, do
     // by every search) is zeroed, or — if this rank's upload / launch failed — poisoned with a NaN, so that a local failure reaches every
     // rank through the collective instead of leaving the peers blocked in it (see mvicp_correspond).
     c->lin_out = c->d_out;
-    int st_l = upload_rel(c, poses);
+    int st_l = plane == MVICP_METRIC_SYMMETRIC ? upload_rel_sym(c, poses) : upload_rel(c, poses);
     if (st_l == MVICP_OK && c->fault_inject_eval > 0 && --c->fault_inject_eval == 0) { set_error("injected launch failure (option fault_inject_eval)"); st_l = MVICP_ERR_HIP; }
-    if (st_l == MVICP_OK) st_l = launch_linearize(c, plane, robust);
+    if (st_l == MVICP_OK) st_l = launch_metric(c, plane, robust);
     char local_msg[sizeof(g_err)] = "";
     if (st_l != MVICP_OK) std::memcpy(local_msg, g_err, sizeof(local_msg));
     if (hipMemsetAsync(c->d_out + n, st_l == MVICP_OK ? 0 : 0xFF, sizeof(double), c->stream) != hipSuccess) {
@@ -506,9 +571,9 @@ int evaluate_blocks(mvicp_ctx* c, const double* poses, int plane, int robust, do
     std::memcpy(out, hx, sizeof(double) * n);
     return MVICP_OK;
   } else {
-    MV_CHECK(upload_rel(c, poses));
+    MV_CHECK(plane == MVICP_METRIC_SYMMETRIC ? upload_rel_sym(c, poses) : upload_rel(c, poses));
     c->lin_out = c->d_blocks_host;   // 8 * 91 * E bytes: the reduce kernel stores them straight into mapped host memory
-    MV_CHECK(launch_linearize(c, plane, robust));
+    MV_CHECK(launch_metric(c, plane, robust));
   }
   MV_CHECK(stream_wait(c));
   std::memcpy(out, h, sizeof(double) * n);
@@ -2129,7 +2194,18 @@ int mvicp_linearize(mvicp_ctx* c, const double* poses, int point_to_plane, int r
   MV_CHECK(bind(c));
   if (!poses || !out) { set_error("null argument"); return MVICP_ERR_ARG; }
   if (c->E == 0) { set_error("no graph"); return MVICP_ERR_STATE; }
-  MV_CHECK(evaluate_blocks(c, poses, point_to_plane, robust, out));
+  MV_CHECK(evaluate_blocks(c, poses, point_to_plane ? MVICP_METRIC_PLANE : MVICP_METRIC_POINT, robust, out));   // (any non-zero flag is plane)
+  if (c->profile) prof_collect_lazy(c);
+  return MVICP_OK;
+} MVICP_GUARD_ABI
+
+// mvicp_linearize with the objective named: metric 0 / 1 ARE mvicp_linearize(point_to_plane = 0 / 1)
+int mvicp_linearize_metric(mvicp_ctx* c, const double* poses, int metric, int robust, double* out) try {
+  if (metric != MVICP_METRIC_POINT && metric != MVICP_METRIC_PLANE && metric != MVICP_METRIC_SYMMETRIC) { set_error("metric %d is not an mvicp_metric", metric); return MVICP_ERR_ARG; }
+  MV_CHECK(bind(c));
+  if (!poses || !out) { set_error("null argument"); return MVICP_ERR_ARG; }
+  if (c->E == 0) { set_error("no graph"); return MVICP_ERR_STATE; }
+  MV_CHECK(evaluate_blocks(c, poses, metric, robust, out));
   if (c->profile) prof_collect_lazy(c);
   return MVICP_OK;
 } MVICP_GUARD_ABI
@@ -2140,10 +2216,10 @@ int mvicp_linearize_pair(mvicp_ctx* c, const double* poses_a, const double* pose
   if (!poses_a || !poses_b || !out_a || !out_b) { set_error("null argument"); return MVICP_ERR_ARG; }
   if (c->E == 0) { set_error("no graph"); return MVICP_ERR_STATE; }
   if (c->comm || c->ar_fn) {   // an exchange is configured: two ordinary evaluations (one collective each)
-    MV_CHECK(evaluate_blocks(c, poses_a, point_to_plane, robust, out_a));
-    MV_CHECK(evaluate_blocks(c, poses_b, point_to_plane, robust, out_b));
+    MV_CHECK(evaluate_blocks(c, poses_a, point_to_plane ? MVICP_METRIC_PLANE : MVICP_METRIC_POINT, robust, out_a));
+    MV_CHECK(evaluate_blocks(c, poses_b, point_to_plane ? MVICP_METRIC_PLANE : MVICP_METRIC_POINT, robust, out_b));
   } else {
-    MV_CHECK(evaluate_pair(c, poses_a, poses_b, point_to_plane, robust, out_a, out_b));
+    MV_CHECK(evaluate_pair(c, poses_a, poses_b, point_to_plane ? MVICP_METRIC_PLANE : MVICP_METRIC_POINT, robust, out_a, out_b));
   }
   if (c->profile) prof_collect_lazy(c);
   return MVICP_OK;

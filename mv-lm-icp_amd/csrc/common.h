@@ -313,6 +313,8 @@ struct mvicp_ctx {
   int* d_chunk_edge = nullptr; int* d_chunk_start = nullptr; int* d_chunk_first = nullptr;
   double* d_partials = nullptr;     // 2 x n_chunks x kLinPartial (second half: the second pose set of a paired launch)
   bool lin_pair = true;             // option "lin_pair": two queued evaluations of a fixed-point round go as ONE paired launch (0: two launches, a copy between them)
+  mvicp::PinBuf sym_lo_pin; mvicp::DevBuf sym_lo_dev;   // E x kEdgeRel doubles: low parts of the relative transforms of a symmetric evaluation (api.cpp upload_rel_sym,
+                                    // linearize_sym.hip); buffers of their own, allocated by the first symmetric evaluation of a graph, released with the graph
   double* d_out = nullptr;          // E x 91 blocks | E x 2 (count, median d2) | 1 "armed" slot: ONE buffer, so that with N > 1 ranks a round's
                                     // counts / medians / use-the-queued-evaluation decision travel in the same all-reduce as the queued blocks
   double* d_res_target = nullptr;   // where the select kernels put (count, median d2): null = mapped host memory (single rank), else d_out's tail
@@ -513,6 +515,7 @@ int launch_export(mvicp_ctx* c);           // export.hip: every exportable edge'
 int launch_select_bracket(mvicp_ctx* c);   // one-pass select around last round's medians (d_sel_lohi); flags edges it cannot answer
 int launch_linearize(mvicp_ctx* c, int plane, int robust);                            // linearize.hip
 int launch_linearize_pair(mvicp_ctx* c, int plane, int robust, double* out_a, double* out_b);   // linearize.hip: d_rel -> out_a, d_rel2 -> out_b, one pass
+int launch_linearize_sym(mvicp_ctx* c, int robust);                                   // linearize_sym.hip: the symmetric objective, same tables / partials / outputs as launch_linearize
 int launch_normals(mvicp_ctx* c, FrameDev& f, int k, int* d_knn);                      // normals.hip
 int stream_wait(mvicp_ctx* c);      // api.cpp: wait for the context's stream (spin-polls first)
 void census_resolve(mvicp_ctx* c);  // api.cpp: fold the counters of the last NN launch into the profile (after a sync)

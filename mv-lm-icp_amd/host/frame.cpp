@@ -239,12 +239,16 @@ void Session::correspond(std::vector<std::shared_ptr<Frame>>& frames, float thre
 }
 
 void Session::optimize(std::vector<std::shared_ptr<Frame>>& frames, int param, bool pointToPlane, bool robust, mvicp_summary* out) {
+  optimize(frames, param, pointToPlane ? MVICP_METRIC_PLANE : MVICP_METRIC_POINT, robust, out);
+}
+
+void Session::optimize(std::vector<std::shared_ptr<Frame>>& frames, int param, mvicp_metric metric, bool robust, mvicp_summary* out) {
   bind(frames);
   std::vector<double> P(16 * frames.size());
   std::vector<unsigned char> fx(frames.size());
   for (size_t i = 0; i < frames.size(); ++i) { std::memcpy(&P[16 * i], frames[i]->pose.data(), 128); fx[i] = frames[i]->fixed; }
   mvicp_summary sm;
-  check(mvicp_optimize(ctx, P.data(), fx.data(), param, pointToPlane, robust, 50 /* icp-ceres.cpp:81 */, &sm));
+  check(mvicp_optimize_metric(ctx, P.data(), fx.data(), param, metric, robust, 50 /* icp-ceres.cpp:81 */, &sm));
   if (!frames.empty()) frames[0]->fixed = true;  // icp-ceres.cpp:244,341,417
   for (size_t i = 0; i < frames.size(); ++i) std::memcpy(frames[i]->pose.data(), &P[16 * i], 128);
   if (out) *out = sm;

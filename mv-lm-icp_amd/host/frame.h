@@ -154,6 +154,8 @@ struct Session {
                        std::vector<FeatureKeypoints>* keypoints = nullptr);
   void correspond(std::vector<std::shared_ptr<Frame>>& frames, float thresh);
   void optimize(std::vector<std::shared_ptr<Frame>>& frames, int param, bool pointToPlane, bool robust, mvicp_summary* sm = nullptr);
+  // the same with the objective named (MVICP_METRIC_SYMMETRIC needs normals on every frame, oriented consistently)
+  void optimize(std::vector<std::shared_ptr<Frame>>& frames, int param, mvicp_metric metric, bool robust, mvicp_summary* sm = nullptr);
   void reset();
 };
 

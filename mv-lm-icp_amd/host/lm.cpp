@@ -305,18 +305,21 @@ int mvicp_lm_solve(int n_frames, int n_edges, const int* src, const int* dst, do
   return lm_solve(n_frames, n_edges, src, dst, poses, fixed, param, max_iterations, eval, user, summary);
 } MVICP_GUARD_ABI
 
-int mvicp_optimize(mvicp_ctx* c, double* poses, unsigned char* fixed, int param, int point_to_plane, int robust, int max_iterations,
-                   mvicp_summary* summary) try {
+// mvicp_optimize with the objective named (metric: an mvicp_metric, already checked).  Point and plane solves arm the evaluations the next search queues
+// ahead; a symmetric solve arms nothing and voids what is queued, like a failed solve: queued symmetric evaluations do not exist.
+static int optimize_metric(mvicp_ctx* c, double* poses, unsigned char* fixed, int param, int metric, int robust, int max_iterations, mvicp_summary* summary) {
   if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
   hipError_t e = hipSetDevice(c->device);
   if (e != hipSuccess) { set_error("hipSetDevice: %s", hipGetErrorString(e)); return MVICP_ERR_HIP; }
   if (c->E == 0) { set_error("no graph"); return MVICP_ERR_STATE; }
   HostScope hs(c, "host.optimize");
   // what the NEXT search may evaluate ahead of time (api.cpp, speculative first evaluation)
-  c->spec_flags_valid = true; c->spec_param = param; c->spec_plane = point_to_plane ? 1 : 0; c->spec_robust = robust ? 1 : 0;
-  CtxEval u{c, point_to_plane ? 1 : 0, robust ? 1 : 0};
+  const bool sym = metric == MVICP_METRIC_SYMMETRIC;
+  if (sym) c->spec_flags_valid = false;
+  else { c->spec_flags_valid = true; c->spec_param = param; c->spec_plane = metric; c->spec_robust = robust ? 1 : 0; }
+  CtxEval u{c, metric, robust ? 1 : 0};
   const int st = lm_solve(c->n_frames, c->E, c->esrc.data(), c->edst.data(), poses, fixed, param, max_iterations, ctx_eval, &u, summary);
-  if (st != MVICP_OK) { c->spec_flags_valid = false; c->spec_ready = false; c->spec2_ready = false; c->last_cand_poses.clear(); }   // a failed solve must not arm the next search's queued evaluation
+  if (st != MVICP_OK || sym) { c->spec_flags_valid = false; c->spec_ready = false; c->spec2_ready = false; c->last_cand_poses.clear(); }   // a failed solve must not arm the next search's queued evaluation
   if (st == MVICP_OK && summary) {   // feeds the AUTO kernel choice of the next search (api.cpp): RMS residual the solve ended on
     double n = 0.0;
     for (int e = 0; e < c->E; ++e) n += c->h_count[e];
@@ -324,6 +327,17 @@ int mvicp_optimize(mvicp_ctx* c, double* poses, unsigned char* fixed, int param,
   }
   if (c->profile) prof_collect_lazy(c);
   return st;
+}
+
+int mvicp_optimize(mvicp_ctx* c, double* poses, unsigned char* fixed, int param, int point_to_plane, int robust, int max_iterations,
+                   mvicp_summary* summary) try {
+  return optimize_metric(c, poses, fixed, param, point_to_plane ? MVICP_METRIC_PLANE : MVICP_METRIC_POINT, robust, max_iterations, summary);
+} MVICP_GUARD_ABI
+
+int mvicp_optimize_metric(mvicp_ctx* c, double* poses, unsigned char* fixed, int param, int metric, int robust, int max_iterations,
+                          mvicp_summary* summary) try {
+  if (metric != MVICP_METRIC_POINT && metric != MVICP_METRIC_PLANE && metric != MVICP_METRIC_SYMMETRIC) { set_error("metric %d is not an mvicp_metric", metric); return MVICP_ERR_ARG; }
+  return optimize_metric(c, poses, fixed, param, metric, robust, max_iterations, summary);
 } MVICP_GUARD_ABI
 
 }  // extern "C"

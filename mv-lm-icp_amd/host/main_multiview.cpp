@@ -39,6 +39,9 @@
 // (iss: on both sides of every edge; iss_src: the keypoints of the source against every point of the destination).  --feat_salient_radius
 // (default --feat_radius), --feat_nms_radius (default 0.3 x salient), --feat_gamma21, --feat_gamma32 (0.975), --feat_min_neighbors (5).
 // One more line per frame, before the edge lines: `feature init: frame i keypoints k of n`.
+// --symmetric (default off): the solves minimise the symmetric point-to-plane objective (MVICP_METRIC_SYMMETRIC, include/mvicp.h) instead of
+// the one --pointToPlane selects, in the parameterisation the other flags select.  It needs normals on every frame (the clouds' own or
+// --recomputeNormals), oriented consistently between the frames.
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
@@ -85,7 +88,7 @@ static void loadFrames(const Flags& F, std::vector<std::shared_ptr<Frame>>& fram
 int main(int argc, char** argv) {
   Flags F(argc, argv);
   const bool pointToPlane = F.b("pointToPlane", true), sophusSE3 = F.b("sophusSE3", true), angleAxis = F.b("angleAxis", false);
-  const bool robust = F.b("robust", true), quiet = F.b("quiet", false);
+  const bool robust = F.b("robust", true), quiet = F.b("quiet", false), symmetric = F.b("symmetric", false);
   const float cutoff = (float)F.f("cutoff", 0.05);
   const int knn = F.i("knn", 2), rounds = F.i("rounds", 20);
   const std::string dir = F.s("dir", "../samples/Bunny_RealData"), out = F.s("out", "");
@@ -230,6 +233,8 @@ int main(int argc, char** argv) {
         std::cout << "getClosestPoint check: " << checked << " queries, " << bad << " mismatches (" << single << " also asked one by one)" << std::endl;
       }
       if (F.i("freeze_from", 1 << 30) <= r) {}   // (search only: the poses stay bit-identical)
+      else if (symmetric)
+        Session::get().optimize(cur, sophusSE3 ? MVICP_PARAM_SOPHUS_SE3 : angleAxis ? MVICP_PARAM_ANGLE_AXIS : MVICP_PARAM_EIGEN_QUATERNION, MVICP_METRIC_SYMMETRIC, robust);
       else if (sophusSE3) ICP_Ceres::ceresOptimizer_sophusSE3(cur, pointToPlane, robust);
       else if (angleAxis) ICP_Ceres::ceresOptimizer_ceresAngleAxis(cur, pointToPlane, robust);
       else ICP_Ceres::ceresOptimizer(cur, pointToPlane, robust);
