@@ -583,7 +583,18 @@ int mvicp_nn_query(mvicp_ctx* ctx, int frame, const double* queries, int n, int 
 #define MVICP_EDGE_BLOCK 91
 /* Non-OK returns of both evaluations (and of mvicp_optimize, which evaluates): a NULL pointer -> MVICP_ERR_ARG; no graph, no list yet
  * (neither mvicp_correspond nor mvicp_set_correspondences), point-to-plane while the target of a non-empty list has no normals ("...
- * needs normals on frame i") -> MVICP_ERR_STATE.  Lists, epochs and poses are untouched; `out` is not written. */
+ * needs normals on frame i") -> MVICP_ERR_STATE.  Lists, epochs and poses are untouched; `out` is not written.
+ * With several ranks (an exchange configured) a refusal is a verdict on the lists THIS rank owns, and it is the same call on every rank that
+ * returns non-OK: a rank that refuses ("no list yet", "... needs normals on frame i") still enters the evaluation's one collective, with the
+ * exchanged buffer poisoned, and returns its own MVICP_ERR_STATE; every other rank returns MVICP_ERR_COMM ("a peer rank failed ...") from
+ * the same call — the protocol of a failed local launch.  No rank is left waiting in the all-reduce, no rank gets blocks, and the next
+ * evaluation (after mvicp_recompute_normals on that frame on every rank, say) is an ordinary one.  After a search the counts are global,
+ * but the verdict is still taken from the owned edges only: after mvicp_set_correspondences only the owner knows an edge's count (the other
+ * ranks keep the last search's), and a rule that every rank decides from its own copy would let them disagree.  What the caller owes on a
+ * sharded context with explicit lists: every rank makes the same sequence of evaluation calls; every rank holds lists before the first of
+ * them (a search, or mvicp_set_correspondences for each edge it owns that is to be non-empty — a rank that has neither refuses, and with it
+ * every rank); and, because mvicp_set_correspondences drops the evaluation a search queued ahead on the calling rank only, explicit lists are
+ * not mixed with queued evaluations: set "spec_eval" 0 on every rank of a sharded context that installs explicit lists between searches. */
 int mvicp_linearize(mvicp_ctx* ctx, const double* poses, int point_to_plane, int robust, double* out);
 /* Two evaluations on the SAME correspondences and scales: out_a = what mvicp_linearize gives at poses_a, out_b = what it gives at poses_b,
  * bit for bit.  On a single rank both come from one kernel that reads the operand stream once (the kernel is bandwidth-bound, so the pair
@@ -646,7 +657,9 @@ int mvicp_optimize_metric(mvicp_ctx* ctx, double* poses, unsigned char* fixed, i
 
 /* Host-only form of the same solver over a caller-supplied evaluator (no GPU touched by this call):
  * eval(user, poses[n_frames x 16], blocks[n_edges x 91]) must fill the per-edge canonical blocks exactly
- * as mvicp_linearize does.  mvicp_optimize is this with the device evaluator plugged in. */
+ * as mvicp_linearize does.  mvicp_optimize is this with the device evaluator plugged in.
+ * With MVICP_LM_TRACE set in the environment every solve (this one and mvicp_optimize's) writes one line per iteration that evaluated a
+ * candidate to stderr: "[mvicp lm] it I cost C cand C' radius R model_change M" — the accept / reject decision is (C - C') / M against 1e-3. */
 typedef int (*mvicp_eval_fn)(void* user, const double* poses, double* blocks);
 int mvicp_lm_solve(int n_frames, int n_edges, const int* src, const int* dst, double* poses, unsigned char* fixed, int param,
                    int max_iterations, mvicp_eval_fn eval, void* user, mvicp_summary* summary);

@@ -516,10 +516,18 @@ static int launch_metric(mvicp_ctx* c, int metric, int robust) {
 
 // `plane` is the metric (0 point, 1 plane, 2 symmetric).  Only point and plane evaluations are ever queued ahead, so a symmetric one matches no
 // queued result (spec_q_plane / spec2_plane are 0 or 1), drops them like any evaluation they were not made for, and takes the ordinary route below.
+// With an exchange configured a refusal of check_evaluable is a LOCAL verdict (it looks at the edges this rank owns: only the owner knows the count of
+// an explicit list), so it is treated like a failed local launch: the rank enters the evaluation's collective with the slot poisoned, and every
+// rank returns non-OK from the same call (the refusing rank its own MVICP_ERR_STATE, the peers MVICP_ERR_COMM) instead of the peers waiting in it.
+// No rank serves such an evaluation from the queue: a searched non-empty list whose target has no normals disarms the queued evaluation on
+// every rank (mvicp_correspond decides that from the frames, which every rank holds).
 int evaluate_blocks(mvicp_ctx* c, const double* poses, int plane, int robust, double* out) {
-  MV_CHECK(check_evaluable(c, plane));
+  const bool exchange = c->comm || c->ar_fn;
+  const int st_chk = check_evaluable(c, plane);
+  if (st_chk != MVICP_OK && !exchange) return st_chk;
   HostScope hs(c, "host.evaluate");
   const size_t n = (size_t)c->E * MVICP_EDGE_BLOCK;
+  if (st_chk != MVICP_OK) { c->spec_ready = false; c->spec2_ready = false; }
   if (c->spec_ready) {
     // the evaluation mvicp_correspond queued ahead: valid only for exactly these poses and flags
     c->spec_ready = false;
@@ -545,12 +553,13 @@ int evaluate_blocks(mvicp_ctx* c, const double* poses, int plane, int robust, do
   // (an evaluation beyond the solve's first: what the next solve's candidate evaluation will most likely be asked at, if the poses do not move)
   c->last_cand_poses.assign(poses, poses + 16 * (size_t)c->n_frames); c->last_cand_plane = plane; c->last_cand_robust = robust;
   double* h = c->h_pin + c->pin_blocks_off;
-  if (c->comm || c->ar_fn) {
+  if (exchange) {
     // One collective per evaluation: [E x 91 blocks | poison slot].  The slot right behind the blocks (the buffer's tail region, rewritten
-    // by every search) is zeroed, or — if this rank's upload / launch failed — poisoned with a NaN, so that a local failure reaches every
-    // rank through the collective instead of leaving the peers blocked in it (see mvicp_correspond).
+    // by every search) is zeroed, or — if this rank refused the evaluation, or its upload / launch failed — poisoned with a NaN, so that a local
+    // failure reaches every rank through the collective instead of leaving the peers blocked in it (see mvicp_correspond).
     c->lin_out = c->d_out;
-    int st_l = plane == MVICP_METRIC_SYMMETRIC ? upload_rel_sym(c, poses) : upload_rel(c, poses);
+    int st_l = st_chk;
+    if (st_l == MVICP_OK) st_l = plane == MVICP_METRIC_SYMMETRIC ? upload_rel_sym(c, poses) : upload_rel(c, poses);
     if (st_l == MVICP_OK && c->fault_inject_eval > 0 && --c->fault_inject_eval == 0) { set_error("injected launch failure (option fault_inject_eval)"); st_l = MVICP_ERR_HIP; }
     if (st_l == MVICP_OK) st_l = launch_metric(c, plane, robust);
     char local_msg[sizeof(g_err)] = "";

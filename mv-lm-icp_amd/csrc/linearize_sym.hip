@@ -17,7 +17,9 @@
 //   x'_i  = fma(A[i+6], p2, fma(A[i+3], p1, A[i] * p0))          (A column-major; as accumulate<> in linearize.hip)
 //   nu_i  = fma(A[i+6], s2, fma(A[i+3], s1, A[i] * s0))          (s = n_p)
 //   m_i   = 0.5 * (n_i + nu_i)                                   (n = n_q)
-//   f_i   = ((x'_i + t_i) - q_i) + fma(Alo[i+6], p2, fma(Alo[i+3], p1, fma(Alo[i], p0, tlo_i))),   d_i = q_i - t_i
+//   f_i   = residual_component(): h_k = A[i+3k] * p_k with its exact error g_k = fma(A[i+3k], p_k, -h_k); TwoSum chain s1 = h_0 + h_1, s2 = s1 + h_2, s3 = s2 + t_i,
+//           s4 = s3 - q_i with errors e1..e4;  f_i = s4 + ((((e1 + e2) + (e3 + e4)) + ((g_0 + g_1) + g_2)) + fma(Alo[i+6], p2, fma(Alo[i+3], p1, fma(Alo[i], p0, tlo_i))))
+//   d_i   = q_i - t_i
 //   r     = fma(m2, f2, fma(m1, f1, m0 * f0))
 //   u'_3  = 0.5 * fma(x'1, n2, fma(-x'2, n1, fma(d1, nu2, -(d2 * nu1))))     and cyclically (1,2) -> (2,0) -> (0,1) for u'_4, u'_5
 //   s = r * r,  w = 1 (plain) or fast_rsqrt(1 + s * (1 / a^2)),  cost += 0.5 * s or half_rho(s, w)
@@ -39,6 +41,34 @@ namespace mvicp {
 
 namespace {
 
+// s = fl(a + b) and e with a + b = s + e exactly (Knuth's TwoSum: no assumption on the magnitudes)
+__device__ __forceinline__ double two_sum(double a, double b, double& e) {
+#pragma clang fp contract(off)
+  const double s = a + b;
+  const double bb = s - a;
+  e = (a - (s - bb)) + (b - bb);
+  return s;
+}
+
+// One component of f = A p + t - q, a small difference of large terms, to a relative error of a few 2^-53 OF f ITSELF: the three products with their exact
+// errors (fma), the five terms added by TwoSum, the errors and the low parts of (A, t) added at the end.  The plain form ((x' + t) - q) carries the rounding of
+// x' and of x' + t, 2^-53 (|x'| + |t|) per correspondence: against residuals of 5e-4 on clouds of extent 0.4 that is 1e-14 of the cost and of g over 1 500
+// correspondences — the size of a plain fp64 evaluation's own error there, and over 32 x it whenever that evaluation happens to be lucky
+// (tests/test_gpu_sym_regimes.py met that in 6 of 4 140 pieces).  The 37 flops per component are NOT hidden behind the operand traffic at two waves per SIMD:
+// measured at cfg4's shape the launch went from 153 to 166 - 173 us.
+// Contraction is switched off in both functions: a product fused into the sum that follows it would make that sum something other than fl(h_0 + h_1).
+__device__ __forceinline__ double residual_component(double a0, double a1, double a2, double t, double p0, double p1, double p2, double q, double lo) {
+#pragma clang fp contract(off)
+  const double h0 = a0 * p0, h1 = a1 * p1, h2 = a2 * p2;
+  const double g0 = __builtin_fma(a0, p0, -h0), g1 = __builtin_fma(a1, p1, -h1), g2 = __builtin_fma(a2, p2, -h2);
+  double e1, e2, e3, e4;
+  const double s1 = two_sum(h0, h1, e1);
+  const double s2 = two_sum(s1, h2, e2);
+  const double s3 = two_sum(s2, t, e3);
+  const double s4 = two_sum(s3, -q, e4);
+  return s4 + ((((e1 + e2) + (e3 + e4)) + ((g0 + g1) + g2)) + lo);
+}
+
 template <bool ROBUST>
 __device__ __forceinline__ void accumulate_sym(double (&acc)[NACC], const double* __restrict__ A, const double* __restrict__ t, const double* __restrict__ lo, double inv_a2,
                                                double p0, double p1, double p2, double n0, double n1, double n2, double q0, double q1, double q2,
@@ -50,9 +80,9 @@ __device__ __forceinline__ void accumulate_sym(double (&acc)[NACC], const double
   const double v1 = __builtin_fma(A[7], s2, __builtin_fma(A[4], s1, A[1] * s0));
   const double v2 = __builtin_fma(A[8], s2, __builtin_fma(A[5], s1, A[2] * s0));
   // (lo[0..8] = A's low parts, lo[9..11] = t's)
-  const double f0 = ((x0 + t[0]) - q0) + __builtin_fma(lo[6], p2, __builtin_fma(lo[3], p1, __builtin_fma(lo[0], p0, lo[9])));
-  const double f1 = ((x1 + t[1]) - q1) + __builtin_fma(lo[7], p2, __builtin_fma(lo[4], p1, __builtin_fma(lo[1], p0, lo[10])));
-  const double f2 = ((x2 + t[2]) - q2) + __builtin_fma(lo[8], p2, __builtin_fma(lo[5], p1, __builtin_fma(lo[2], p0, lo[11])));
+  const double f0 = residual_component(A[0], A[3], A[6], t[0], p0, p1, p2, q0, __builtin_fma(lo[6], p2, __builtin_fma(lo[3], p1, __builtin_fma(lo[0], p0, lo[9]))));
+  const double f1 = residual_component(A[1], A[4], A[7], t[1], p0, p1, p2, q1, __builtin_fma(lo[7], p2, __builtin_fma(lo[4], p1, __builtin_fma(lo[1], p0, lo[10]))));
+  const double f2 = residual_component(A[2], A[5], A[8], t[2], p0, p1, p2, q2, __builtin_fma(lo[8], p2, __builtin_fma(lo[5], p1, __builtin_fma(lo[2], p0, lo[11]))));
   const double d0 = q0 - t[0], d1 = q1 - t[1], d2 = q2 - t[2];
   double u[6];
   u[0] = 0.5 * (n0 + v0); u[1] = 0.5 * (n1 + v1); u[2] = 0.5 * (n2 + v2);

@@ -20,6 +20,8 @@
 // parameterization is a per-pose 6x6 map M (se3.h): H' = M^T H M, g' = M^T g.
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <vector>
 
@@ -219,6 +221,9 @@ int lm_solve(int K, int E, const int* src, const int* dst, double* poses, unsign
   rescale();
   if (gmax_of(g) <= gradient_tolerance) { sm->termination = 1; return finish(); }
 
+  // MVICP_LM_TRACE (tests): one line per iteration that reached a candidate evaluation, in the format of the oracle's ORC_LM_TRACE — what an
+  // accept / reject decision was taken from (relative_decrease = (cost - cand) / model_change against min_relative_decrease)
+  const bool trace = std::getenv("MVICP_LM_TRACE") != nullptr;
   int iter = 0;
   while (true) {
     if (iter >= max_iterations) { sm->termination = 0; break; }
@@ -260,6 +265,7 @@ int lm_solve(int K, int E, const int* src, const int* dst, double* poses, unsign
     MV_CHECK(eval(user, pc.data(), blocks.data()));
     sm->evaluations++;
     const double cand_cost = as.assemble(xc.data(), blocks.data(), Hn.data(), gn.data(), env.data());
+    if (trace) std::fprintf(stderr, "[mvicp lm] it %d cost %.17g cand %.17g radius %.17g model_change %.17g\n", iter, cost, cand_cost, radius, model_cost_change);
     double sn = 0.0;
     for (int i = 0; i < K; ++i) if (!fixed[i]) for (int a = 0; a < A; ++a) { const double dd = x[i * A + a] - xc[i * A + a]; sn += dd * dd; }
     if (std::sqrt(sn) <= parameter_tolerance * (x_norm + parameter_tolerance)) { sm->termination = 2; break; }

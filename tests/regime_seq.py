@@ -13,9 +13,12 @@ KINDS = ["none", "none", "cutoff", "fixed", "reset", "method", "option", "hold",
 KINDS_EXTENDED = KINDS + ["fail", "fail", "tie_rule", "tie_rule"]
 
 
-def script(seed, K, rounds=14, extended=False):
-    """-> list of per-round event dicts (pure function of its arguments).  extended=False draws exactly the sequences it always drew."""
+def script(seed, K, rounds=14, extended=False, metrics=False):
+    """-> list of per-round event dicts (pure function of its arguments).  extended=False draws exactly the sequences it always drew.
+    metrics=True adds e["metric"] in {0 POINT, 1 PLANE, 2 SYMMETRIC} to every event, drawn from a generator of its own: every other key is
+    what the same call without it gives (tests/test_regime_script_cpu.py holds the scripts of the sharded tests to a recorded digest)."""
     rng = np.random.default_rng(4200 + seed)
+    rng_metric = np.random.default_rng(77000 + seed)
     ev = []
     for rnd in range(rounds):
         kind = str(rng.choice(KINDS_EXTENDED if extended else KINDS)) if rnd > 0 else "none"
@@ -33,18 +36,31 @@ def script(seed, K, rounds=14, extended=False):
             e["inject"] = bool(rng.integers(0, 2)); e["frame"] = int(rng.integers(1, K)); e["shift"] = [float(v) for v in rng.normal(0.0, 2e-3, 3)]
             e["retry_there"] = bool(rng.integers(0, 2))
         e["param"] = int(rng.integers(0, 3)); e["plane"] = int(rng.integers(0, 2)); e["robust"] = bool(rng.integers(0, 2))
+        if metrics:
+            e["metric"] = int(rng_metric.integers(0, 3))
         ev.append(e)
     return ev
 
 
-def run(eng, pb, events):
-    """Replays `events` on an engine that already holds the clouds and the graph.  -> list of (counts, weights-as-bytes, poses) per round."""
+def solves(events):
+    """the events whose round ends with a solve (run() below: every kind but "hold" and "fail"), in order"""
+    return [e for e in events if e["kind"] not in ("hold", "fail")]
+
+
+def run(eng, pb, events, after_search=None, after_round=None):
+    """Replays `events` on an engine that already holds the clouds and the graph.  -> list of (counts, weights-as-bytes, poses) per round.
+    Hooks (tests/test_gpu_sym_regimes.py; the sharded tests use none): after_search(state) runs between the round's search and its solve,
+    after_round(state) after the solve; state = {"round", "event", "poses", "fixed", "cutoff", "method", "options", "counts", "weights"}, the
+    round's own values ("options": what the script has set so far).  A kind the scripts above never draw, for hand-written events: "normals"
+    (mvicp_recompute_normals(frame, 10) before the round's search; the new normals go to state["normals"])."""
     poses = pb["init"].copy()
     fixed = pb["fixed"].copy()
     cutoff, method, rule = 0.05, 0, 1
+    options = {}
     out = []
-    for e in events:
+    for rnd, e in enumerate(events):
         k = e["kind"]
+        state = {"round": rnd, "event": e}
         if k == "cutoff":
             cutoff = e["cutoff"]
         elif k == "fixed":
@@ -55,6 +71,9 @@ def run(eng, pb, events):
             method = e["method"]
         elif k == "option":
             eng.set_option(e["name"], e["value"])
+            options[e["name"]] = e["value"]
+        elif k == "normals":
+            state["normals"] = eng.recompute_normals(e["frame"], 10)
         elif k == "tie_rule":
             rule = 1 - rule
             eng.set_option("tie_rule", rule)
@@ -72,9 +91,18 @@ def run(eng, pb, events):
             if e["retry_there"]:
                 poses = Pf
         counts, weights = eng.correspond(poses, fixed, cutoff, method)
+        state.update(poses=poses, fixed=fixed.copy(), cutoff=cutoff, method=method, options=dict(options), counts=counts.copy(), weights=weights.copy())
+        if after_search is not None:
+            after_search(state)
         if k not in ("hold", "fail") and counts.sum() > 0:
-            poses, _ = eng.optimize(poses, fixed, e["param"], e["plane"], e["robust"], 50)
+            if "metric" in e:
+                poses, _ = eng.optimize_metric(poses, fixed, e["param"], e["metric"], e["robust"], 50)
+            else:
+                poses, _ = eng.optimize(poses, fixed, e["param"], e["plane"], e["robust"], 50)
         out.append((counts.copy(), weights.tobytes(), poses.copy()))
+        if after_round is not None:
+            state["poses"] = poses
+            after_round(state)
     return out
 
 

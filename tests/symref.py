@@ -101,40 +101,54 @@ def blocks_fp64(p, q, nq, npn, Ps, Pd, a, robust):
     return out
 
 
-def centred_blocks(p, q, nq, npn, Ps, Pd, a, robust):
+def centred_blocks(p, q, nq, npn, Ps, Pd, a, robust, inv=None, ftype=LD):
     """The formulation of csrc/linearize_sym.hip in long double: with A = R_d^T R_s, t = R_d^T (t_s - t_d), x' = A p, nu = A n_p,
     m = (n_q + nu) / 2, r = m . (x' + t - q), moments of u' = [m ; (x' x n_q + (q - t) x nu) / 2], expanded as the plane family:
-    H_ss = R6^T U R6, H_sd = -R6^T U L^T, H_dd = L U L^T, g = [R6^T v ; -L v].  -> (H, g, cost)."""
-    p, q, nq, npn = _ld(p).T.copy(), _ld(q).T.copy(), _ld(nq).T.copy(), _ld(npn).T.copy()
-    Ps, Pd = _ld(Ps), _ld(Pd)
-    A = Pd[:3, :3].T @ Ps[:3, :3]
-    t = Pd[:3, :3].T @ (Ps[:3, 3:4] - Pd[:3, 3:4])
+    H_ss = R6^T U R6, H_sd = -R6^T U L^T, H_dd = L U L^T, g = [R6^T v ; -L v].  -> (H, g, cost)
+    inv: the 3x3 matrix to use in the place of R_d^-1 (default R_d^T; for a destination matrix that is no rotation the library substitutes the
+    transpose too, so the default IS what it evaluates there).  ftype=np.float64: the same formulation in plain fp64 with every sum accumulated
+    serially — the yardstick where the direct world-frame rows mean nothing (a destination that is no rotation)."""
+    if ftype is LD:
+        cast, rsum = _ld, _psum
+    else:
+        cast = lambda x: np.asarray(x, dtype=np.float64)   # noqa: E731
+        rsum = lambda x: np.cumsum(x, axis=-1)[..., -1]     # noqa: E731
+    p, q, nq, npn = cast(p).T.copy(), cast(q).T.copy(), cast(nq).T.copy(), cast(npn).T.copy()
+    Ps, Pd = cast(Ps), cast(Pd)
+    Ri = Pd[:3, :3].T if inv is None else cast(inv)
+    A = Ri @ Ps[:3, :3]
+    t = Ri @ (Ps[:3, 3:4] - Pd[:3, 3:4])
     x, nu = A @ p, A @ npn
     m = (nq + nu) / 2
-    r = _psum(np.ascontiguousarray((m * (x + t - q)).T))
+    r = rsum(np.ascontiguousarray((m * (x + t - q)).T))
     s = r * r
     if robust:
-        aa = LD(np.float32(a))
+        aa = ftype(np.float32(a))
         sy = np.sqrt(1 + s / (aa * aa))
         w, half_rho = 1 / sy, s / (sy + 1)
     else:
-        w, half_rho = np.ones(p.shape[1], dtype=LD), s / 2
+        w, half_rho = np.ones(p.shape[1], dtype=ftype), s / 2
     u = np.concatenate([m, (_cross(x, nq) + _cross(q - t, nu)) / 2])
-    U = np.zeros((6, 6), dtype=LD); v = np.zeros(6, dtype=LD)
+    U = np.zeros((6, 6), dtype=ftype); v = np.zeros(6, dtype=ftype)
     for i in range(6):
-        v[i] = _psum(w * r * u[i])
+        v[i] = rsum(w * r * u[i])
         for j in range(6):
-            U[i, j] = _psum(w * u[i] * u[j])
-    R6 = np.zeros((6, 6), dtype=LD); R6[:3, :3] = A; R6[3:, 3:] = A
-    L = np.eye(6, dtype=LD)
+            U[i, j] = rsum(w * u[i] * u[j])
+    R6 = np.zeros((6, 6), dtype=ftype); R6[:3, :3] = A; R6[3:, 3:] = A
+    L = np.eye(6, dtype=ftype)
     tt = t[:, 0]
-    L[3:, :3] = np.array([[0, -tt[2], tt[1]], [tt[2], 0, -tt[0]], [-tt[1], tt[0], 0]], dtype=LD)
-    H = np.zeros((12, 12), dtype=LD)
+    L[3:, :3] = np.array([[0, -tt[2], tt[1]], [tt[2], 0, -tt[0]], [-tt[1], tt[0], 0]], dtype=ftype)
+    H = np.zeros((12, 12), dtype=ftype)
     H[:6, :6] = R6.T @ U @ R6
     H[:6, 6:] = -R6.T @ U @ L.T
     H[6:, :6] = H[:6, 6:].T
     H[6:, 6:] = L @ U @ L.T
-    return H, np.concatenate([R6.T @ v, -L @ v]), _psum(half_rho)
+    return H, np.concatenate([R6.T @ v, -L @ v]), rsum(half_rho)
+
+
+def pack(H, g, cost):
+    """(H, g, cost) -> the 91 values [78 upper H | 12 g | cost] (inverse of unpack)"""
+    return np.concatenate([np.asarray(H)[np.triu_indices(12)], np.asarray(g), [cost]])
 
 
 # ---- the behaviour claim: a small host registration over either objective (tests/test_sym_cpu.py; its GPU twin is in test_gpu_sym_api.py)

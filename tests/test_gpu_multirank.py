@@ -222,3 +222,214 @@ def test_local_failure_reaches_every_rank_through_the_collective(tmp_path):
         poses, _ = eng.optimize(poses, pb["fixed"])
     eng.close()
     assert np.array_equal(P0, poses), np.abs(P0 - poses).max()
+
+
+# ---------------------------------------------------------------- the symmetric objective, sharded
+def _group(rank, world, port, seconds=120):
+    """a process group whose collectives give up after `seconds`: a rank left alone in one ends as an exception, not as a blocked test"""
+    import datetime
+    os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=seconds))
+
+    def allreduce(a):
+        t = torch.from_numpy(a)
+        dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    return allreduce
+
+
+def _regime_problem(seed):
+    from mvicp import synth
+    return synth.make_problem(5, 3500, cone_deg=100.0 if seed % 2 == 0 else 45.0, pose_seed=800 + seed)
+
+
+def _regime_metric_run(rank, world, allreduce, seed, spec):
+    """-> (events, log, spec.hit) of the script with a metric per solve"""
+    import mvicp
+    import regime_seq
+    pb = _regime_problem(seed)
+    eng = mvicp.Engine(0, rank=rank, world=world)
+    eng.set_option("spec_eval", spec)
+    eng.set_frames(pb["pts"], pb["nor"]); eng.set_graph(pb["src"], pb["dst"])
+    if allreduce is not None:
+        eng.comm_set_callback(allreduce)
+    eng.profile(True)
+    events = regime_seq.script(seed, 5, extended=seed >= 100, metrics=True)
+    log = regime_seq.run(eng, pb, events)
+    hits = eng.profile_get("spec.hit")[1]
+    eng.close()
+    return events, log, hits
+
+
+def _regime_metric_worker(rank, world, port, out, seed, spec):
+    allreduce = _group(rank, world, port)
+    sys.path.insert(0, os.path.join(ROOT, "mv-lm-icp_amd")); sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import regime_seq
+    _, log, hits = _regime_metric_run(rank, world, allreduce, seed, spec)
+    regime_seq.save(f"{out}.{rank}.npz", log)
+    np.save(f"{out}.{rank}.hits.npy", np.array([hits]))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+@pytest.mark.timeout(600)
+@pytest.mark.parametrize("seed,spec", [(4, 1), (5, 0), (125, 1)])   # chosen on the CPU (regime_seq.script, metrics=True) for the mix asserted below; 125: extended
+def test_regime_transitions_sharded_symmetric_match_single_process(tmp_path, seed, spec):
+    """The scripted registration of the test above with the objective of every solve drawn from {POINT, PLANE, SYMMETRIC} (mvicp_optimize_metric), on
+    TWO ranks: the symmetric evaluations go through the exchange branch of evaluate_blocks (extended-precision relative transforms uploaded before
+    the collective, no normals gathered for the peer's edges), between solves of the other objectives that arm and consume the queued evaluation.
+    After EVERY round each rank's counts, weight bits and poses equal the single process's bit for bit, and so does the number of evaluations
+    served from the queue."""
+    sys.path.insert(0, os.path.join(ROOT, "mv-lm-icp_amd")); sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import regime_seq
+    out = str(tmp_path / "regime_sym")
+    mp.spawn(_regime_metric_worker, args=(2, _free_port(), out, seed, spec), nprocs=2, join=True)
+    events, log, hits1 = _regime_metric_run(0, 1, None, seed, spec)
+    kinds = [e["kind"] for e in events]
+    m = [e["metric"] for e in regime_seq.solves(events)]
+    assert m.count(2) >= 3, m
+    assert any(a == 1 and b == 2 for a, b in zip(m, m[1:])) and any(a == 2 and b == 1 for a, b in zip(m, m[1:])), m   # symmetric right after plane, and plane right after symmetric
+    assert len(set(kinds)) >= 4, kinds
+    if seed >= 100:
+        assert "fail" in kinds and "tie_rule" in kinds, kinds
+    assert all(l[0].sum() > 0 for l in log)          # every round that the script lets solve did solve
+    if not spec:
+        assert hits1 == 0
+    for r in range(2):
+        regime_seq.assert_equal(f"{out}.{r}.npz", log, (seed, spec, r, kinds, m))
+        assert np.load(f"{out}.{r}.hits.npy")[0] == hits1, (r, hits1)
+
+
+FAULT_METRICS = [1, 2, 2, 1, 2]     # per round; the solve of round 2 (SYMMETRIC) fails on rank 1
+
+
+def _fault_sym_rounds(eng, pb, rank, skip_round2):
+    import mvicp
+    poses = pb["init"].copy()
+    log, errors = [], []
+    for rnd, metric in enumerate(FAULT_METRICS):
+        c, w = eng.correspond(poses, pb["fixed"], 0.05)
+        if rnd == 2 and rank == 1:
+            eng.set_option("fault_inject_eval", 1)   # this rank's next exchanged evaluation fails after the symmetric upload, before the collective
+        if not (rnd == 2 and skip_round2):
+            try:
+                poses, _ = eng.optimize_metric(poses, pb["fixed"], mvicp.lib.PARAM_SOPHUS_SE3, metric, True, 50)
+            except mvicp.MvicpError as ex:
+                errors.append((rnd, str(ex)))
+        log.append((c.copy(), w.tobytes(), poses.copy()))
+    return log, errors
+
+
+def _fault_sym_worker(rank, world, port, out):
+    allreduce = _group(rank, world, port)
+    sys.path.insert(0, os.path.join(ROOT, "mv-lm-icp_amd")); sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import mvicp
+    import regime_seq
+    from mvicp import synth
+    pb = synth.make_problem(5, 2000)
+    eng = mvicp.Engine(0, rank=rank, world=world)
+    eng.set_frames(pb["pts"], pb["nor"]); eng.set_graph(pb["src"], pb["dst"])
+    eng.comm_set_callback(allreduce)
+    log, errors = _fault_sym_rounds(eng, pb, rank, False)
+    eng.close()
+    regime_seq.save(f"{out}.{rank}.npz", log)
+    with open(f"{out}.{rank}.log", "w") as f:
+        for r in errors:
+            f.write("%d|%s\n" % r)
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+@pytest.mark.timeout(300)
+def test_local_failure_in_a_symmetric_evaluation_reaches_every_rank(tmp_path):
+    """The LM leg of the test above for the symmetric objective: rank 1's first evaluation of a symmetric solve fails locally (after upload_rel_sym,
+    before the collective).  Both ranks return an error from that mvicp_optimize_metric — rank 1 its own, rank 0 MVICP_ERR_COMM — and the
+    rounds after it (plane, then symmetric again) agree bit for bit across ranks and with a single process that skipped that solve."""
+    sys.path.insert(0, os.path.join(ROOT, "mv-lm-icp_amd")); sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import mvicp
+    import regime_seq
+    from mvicp import synth
+    out = str(tmp_path / "fault_sym")
+    mp.spawn(_fault_sym_worker, args=(2, _free_port(), out), nprocs=2, join=True)
+    logs = [[l.rstrip("\n").split("|", 1) for l in open(f"{out}.{r}.log")] for r in range(2)]
+    for r in range(2):
+        assert [int(a) for a, _ in logs[r]] == [2], logs[r]
+    assert "injected launch failure" in logs[1][0][1] and "peer rank failed" in logs[0][0][1], logs
+    pb = synth.make_problem(5, 2000)
+    eng = mvicp.Engine(0)
+    eng.set_frames(pb["pts"], pb["nor"]); eng.set_graph(pb["src"], pb["dst"])
+    log, errors = _fault_sym_rounds(eng, pb, 0, True)
+    eng.close()
+    assert not errors
+    assert not np.array_equal(log[-1][2], log[1][2])      # the rounds after the failure moved the poses
+    for r in range(2):
+        regime_seq.assert_equal(f"{out}.{r}.npz", log, ("fault_sym", r))
+
+
+# ---------------------------------------------------------------- a refused evaluation is refused on every rank
+REFUSAL_FRAME = 4    # of make_problem(5, .): edges 3->4, 4->3, 4->2 touch it, all owned by rank 1 of 2 (asserted below)
+
+
+def _refusal_rounds(eng, pb, metric):
+    """frame 4 has no normals: evaluate (must be refused), give it normals, evaluate again -> (message of the refusal, blocks after)"""
+    import mvicp
+    eng.correspond(pb["init"], pb["fixed"], 0.05)
+    msg = ""
+    try:
+        eng.linearize_metric(pb["init"], metric, 1)
+    except mvicp.MvicpError as ex:
+        msg = str(ex)
+    eng.recompute_normals(REFUSAL_FRAME, 10)
+    return msg, eng.linearize_metric(pb["init"], metric, 1)
+
+
+def _refusal_engine(rank, world, allreduce):
+    import mvicp
+    from mvicp import synth
+    pb = synth.make_problem(5, 1500)
+    eng = mvicp.Engine(0, rank=rank, world=world)
+    eng.set_frames(pb["pts"], [None if k == REFUSAL_FRAME else n for k, n in enumerate(pb["nor"])]); eng.set_graph(pb["src"], pb["dst"])
+    if allreduce is not None:
+        eng.comm_set_callback(allreduce)
+    return eng, pb
+
+
+def _refusal_worker(rank, world, port, out, metric):
+    allreduce = _group(rank, world, port, seconds=60)
+    sys.path.insert(0, os.path.join(ROOT, "mv-lm-icp_amd"))
+    eng, pb = _refusal_engine(rank, world, allreduce)
+    msg, blocks = _refusal_rounds(eng, pb, metric)
+    eng.close()
+    np.save(f"{out}.{rank}.npy", blocks)
+    with open(f"{out}.{rank}.log", "w") as f:
+        f.write(msg)
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+@pytest.mark.timeout(300)
+@pytest.mark.parametrize("metric", [1, 2], ids=["PLANE", "SYMMETRIC"])
+def test_an_evaluation_refused_on_one_rank_is_refused_on_every_rank(tmp_path, metric):
+    """check_evaluable looks at the edges a rank owns.  Frame 4 has no normals and only rank 1's edges touch it: rank 1 refuses the evaluation
+    (MVICP_ERR_STATE, naming the frame) and enters the collective with the slot poisoned, so rank 0 — which owns nothing to refuse — returns
+    MVICP_ERR_COMM from the same call instead of waiting in the all-reduce (the process group's timeout turns such a wait into an exception).
+    After mvicp_recompute_normals on that frame on both ranks the next evaluation equals the single process's bytes."""
+    sys.path.insert(0, os.path.join(ROOT, "mv-lm-icp_amd"))
+    from mvicp import lib as L
+    from mvicp import synth
+    pb = synth.make_problem(5, 1500)
+    own = L.edge_owner([1500] * len(pb["src"]), 2)
+    touching = [e for e in range(len(pb["src"])) if REFUSAL_FRAME in (pb["src"][e], pb["dst"][e])]
+    assert touching and all(own[e] == 1 for e in touching), (own, touching)
+    out = str(tmp_path / "refusal")
+    mp.spawn(_refusal_worker, args=(2, _free_port(), out, metric), nprocs=2, join=True)
+    msgs = [open(f"{out}.{r}.log").read() for r in range(2)]
+    assert "needs normals on frame %d" % REFUSAL_FRAME in msgs[1], msgs
+    assert "peer rank failed" in msgs[0], msgs
+    eng, pb = _refusal_engine(0, 1, None)
+    msg, blocks = _refusal_rounds(eng, pb, metric)
+    eng.close()
+    assert "needs normals on frame %d" % REFUSAL_FRAME in msg, msg
+    assert np.any(blocks[touching[0]])
+    for r in range(2):
+        got = np.load(f"{out}.{r}.npy")
+        assert got.tobytes() == blocks.tobytes(), (r, float(np.abs(got - blocks).max()))

@@ -130,7 +130,7 @@ def empty_frame_state(X, frame, q):
     yield ("nn_query of an empty frame", frame), X.status("mvicp_nn_query", frame, L._dp(q), len(q), L.NN_AUTO, L._ip(idx), L._dp(d2))
 
 
-def round_(X, tag, fixed, plane, robust, param):
+def round_(X, tag, fixed, plane, robust, param, sym=False):
     E = X.E
     c, w = E.correspond(X.poses, fixed, CUTOFF)
     yield (tag, "counts"), c
@@ -143,6 +143,11 @@ def round_(X, tag, fixed, plane, robust, param):
     P, sm = E.optimize(X.poses, fixed, param, plane, bool(robust), 50)
     yield (tag, "poses"), P
     yield (tag, "iterations, final cost"), (int(sm["iterations"]), float(sm["final_cost"]))
+    if sym:   # (every frame has normals) the symmetric objective on the same lists, from the same poses; its result is observed, not adopted
+        yield (tag, "symmetric blocks"), E.linearize_metric(X.poses, L.METRIC_SYMMETRIC, robust)
+        Ps, sms = E.optimize_metric(X.poses, fixed, param, L.METRIC_SYMMETRIC, bool(robust), 50)
+        yield (tag, "symmetric poses"), Ps
+        yield (tag, "symmetric iterations, final cost"), (int(sms["iterations"]), float(sms["final_cost"]))
     X.poses = P
 
 
@@ -256,7 +261,15 @@ def refused_evaluations(X, poses, fixed, E_edges, have_lists, plane_refused_fram
     tp, op, ep = C.c_void_p(), C.POINTER(C.c_longlong)(), C.POINTER(C.c_ulonglong)()
     X.reject(ARG, "null argument", "mvicp_linearize", None, 0, 0, L._dp(out))
     X.reject(ARG, "null argument", "mvicp_linearize_pair", L._dp(P), None, 0, 0, L._dp(out), L._dp(out2))
+    # the entry points that name the objective: a metric outside mvicp_metric is refused before anything else is looked at
+    for metric in (3, -1):
+        X.reject(ARG, "metric %d is not an mvicp_metric" % metric, "mvicp_linearize_metric", L._dp(P), metric, 1, L._dp(out))
+        X.reject(ARG, "metric %d is not an mvicp_metric" % metric, "mvicp_optimize_metric", L._dp(P), _u8(fx), 2, metric, 1, 50, C.byref(sm))
+    X.reject(ARG, "null argument", "mvicp_linearize_metric", None, L.METRIC_SYMMETRIC, 1, L._dp(out))
+    X.reject(ARG, "null argument", "mvicp_linearize_metric", L._dp(P), L.METRIC_SYMMETRIC, 1, None)
     if E_edges == 0:
+        X.reject(STATE, "no graph", "mvicp_linearize_metric", L._dp(P), L.METRIC_SYMMETRIC, 1, L._dp(out))
+        X.reject(STATE, "no graph", "mvicp_optimize_metric", L._dp(P), _u8(fx), 2, L.METRIC_SYMMETRIC, 1, 50, C.byref(sm))
         X.reject(STATE, "no graph", "mvicp_linearize", L._dp(P), 0, 0, L._dp(out))
         X.reject(STATE, "no graph", "mvicp_linearize_pair", L._dp(P), L._dp(P), 0, 0, L._dp(out), L._dp(out2))
         X.reject(STATE, "no graph", "mvicp_optimize", L._dp(P), _u8(fx), 2, 0, 0, 50, C.byref(sm))
@@ -267,6 +280,7 @@ def refused_evaluations(X, poses, fixed, E_edges, have_lists, plane_refused_fram
         return
     for param in (3, -1):
         X.reject(ARG, "unknown parameterization", "mvicp_optimize", L._dp(P), _u8(fx), param, 0, 1, 50, C.byref(sm))
+        X.reject(ARG, "unknown parameterization", "mvicp_optimize_metric", L._dp(P), _u8(fx), param, L.METRIC_SYMMETRIC, 1, 50, C.byref(sm))
     X.reject(ARG, "out of range", "mvicp_get_correspondences", E_edges, 4096, L._ip(first), L._ip(second), L._dp(dist))
     X.reject(ARG, "out of range", "mvicp_get_correspondences", -1, 4096, L._ip(first), L._ip(second), L._dp(dist))
     X.reject(ARG, "null output", "mvicp_map_correspondences", None, C.byref(op))
@@ -274,6 +288,8 @@ def refused_evaluations(X, poses, fixed, E_edges, have_lists, plane_refused_fram
         X.reject(STATE, "no correspondences", "mvicp_linearize", L._dp(P), 0, 0, L._dp(out))
         X.reject(STATE, "no correspondences", "mvicp_linearize_pair", L._dp(P), L._dp(P), 0, 0, L._dp(out), L._dp(out2))
         X.reject(STATE, "no correspondences", "mvicp_optimize", L._dp(P), _u8(fx), 2, 0, 0, 50, C.byref(sm))
+        X.reject(STATE, "no correspondences", "mvicp_linearize_metric", L._dp(P), L.METRIC_SYMMETRIC, 1, L._dp(out))
+        X.reject(STATE, "no correspondences", "mvicp_optimize_metric", L._dp(P), _u8(fx), 2, L.METRIC_SYMMETRIC, 1, 50, C.byref(sm))
         X.reject(STATE, "no correspondences yet", "mvicp_get_correspondences", 0, 4096, L._ip(first), L._ip(second), L._dp(dist))
         X.reject(STATE, "no correspondences yet", "mvicp_map_correspondences", C.byref(tp), C.byref(op))
         return
@@ -283,6 +299,8 @@ def refused_evaluations(X, poses, fixed, E_edges, have_lists, plane_refused_fram
         X.reject(STATE, needs, "mvicp_linearize", L._dp(P), 1, 1, L._dp(out))
         X.reject(STATE, needs, "mvicp_linearize_pair", L._dp(P), L._dp(P), 1, 0, L._dp(out), L._dp(out2))
         X.reject(STATE, needs, "mvicp_optimize", L._dp(P), _u8(fx), 2, 1, 1, 50, C.byref(sm))
+        X.reject(STATE, needs, "mvicp_linearize_metric", L._dp(P), L.METRIC_PLANE, 1, L._dp(out))
+        X.reject(STATE, needs, "mvicp_optimize_metric", L._dp(P), _u8(fx), 2, L.METRIC_PLANE, 1, 50, C.byref(sm))
         assert np.array_equal(P, L.poses_to_c(poses))   # (a refused solve returns the caller's poses)
 
 
@@ -321,6 +339,7 @@ def test_refused_calls_change_nothing(pb, variant, path):
     K, E_edges = len(pts), len(src)
     npts = [len(p) for p in pts]
     plane = 1 if variant == "all" else 0
+    sym = variant == "all"     # the symmetric observables need normals on both ends of every non-empty list
     q = np.ascontiguousarray(pts[1][:64] + 0.003)
     other = np.ascontiguousarray(pts[2][:500])   # what the refused uploads carry: another cloud, of another size
 
@@ -350,7 +369,7 @@ def test_refused_calls_change_nothing(pb, variant, path):
         refused_evaluations(X, X.poses, fixed, E_edges, False, None)
         refused_lists(X, 0, npts[src[0]], npts[dst[0]], E_edges)
         refused_evaluations(X, X.poses, fixed, E_edges, False, None)   # (a refused list is no list)
-        yield from round_(X, "round 1", fixed, plane, 1, L.PARAM_SOPHUS_SE3)
+        yield from round_(X, "round 1", fixed, plane, 1, L.PARAM_SOPHUS_SE3, sym)
         # -- a graph with searched lists: the old graph and its lists must keep working
         counts = E.counts
         named = next((int(dst[e]) for e in range(E_edges) if counts[e] > 0 and nor[dst[e]] is None), None)
@@ -370,12 +389,12 @@ def test_refused_calls_change_nothing(pb, variant, path):
         for e in range(E_edges):
             yield ("lists after the refused calls", e), E.get_correspondences(e)
         yield ("blocks after the refused calls",), E.linearize(X.poses, plane, 1)
-        yield from round_(X, "round 2", fixed, plane, 1, L.PARAM_ANGLE_AXIS)
+        yield from round_(X, "round 2", fixed, plane, 1, L.PARAM_ANGLE_AXIS, sym)
         refused_graphs(X, K)
         refused_normals(X, npts)
         refused_lists(X, 2, npts[src[2]], npts[dst[2]], E_edges)
         refused_evaluations(X, X.poses, fixed, E_edges, True, named)
-        yield from round_(X, "round 3", fixed, plane, 0, L.PARAM_EIGEN_QUATERNION)
+        yield from round_(X, "round 3", fixed, plane, 0, L.PARAM_EIGEN_QUATERNION, sym)
         # -- an explicit list survives the refused attempts to replace it
         f0, s0, _ = E.get_correspondences(0)
         E.set_correspondences(0, f0[:50], s0[:50], 0.01)
@@ -387,10 +406,13 @@ def test_refused_calls_change_nothing(pb, variant, path):
         P, sm = E.optimize(X.poses, fixed, L.PARAM_SOPHUS_SE3, plane, True, 50)
         yield ("explicit list", "poses"), P
         yield ("explicit list", "iterations, final cost"), (int(sm["iterations"]), float(sm["final_cost"]))
+        if sym:
+            yield ("explicit list", "symmetric blocks"), E.linearize_metric(X.poses, L.METRIC_SYMMETRIC, 1)
         # a recompute that is NOT refused still works afterwards, on frames with normals and without
         for k in range(K):
             yield ("recompute_normals", k), E.recompute_normals(k, 10, want_knn=True)
         yield ("blocks with recomputed normals",), E.linearize(P, 1, 1)
+        yield ("symmetric blocks with recomputed normals",), E.linearize_metric(P, L.METRIC_SYMMETRIC, 1)    # (every frame has normals now)
 
     assert twin(script) > 200
 
@@ -429,3 +451,48 @@ def test_refused_uploads_onto_an_empty_frame_leave_it_empty(pb, path):
             refused_normals(X, [len(p) for p in pts], frames=(0, 2))
 
     assert twin(script) > 100
+
+
+def test_refused_normals_on_a_source_without_normals_keep_symmetric_refused(pb):
+    """The symmetric objective reads the SOURCE frame's normals too.  Frame 2 is only ever a source (graph 2 -> 0, 1 -> 0) and was uploaded without
+    normals: a refused mvicp_recompute_normals on it (k = 2, 17) must not leave it looking as if it had normals — SYMMETRIC still returns
+    MVICP_ERR_STATE naming frame 2, linearize and solve — while POINT and PLANE (whose targets have normals) give the twin's bytes.  A
+    recompute that is not refused then makes the symmetric evaluation work, with the twin's bytes."""
+    pts, nor = pb["pts"], [pb["nor"][0], pb["nor"][1], None]
+    src, dst, fixed = [2, 1], [0, 0], pb["fixed"]
+    npts = [len(p) for p in pts]
+    needs = "symmetric needs normals on frame 2"
+
+    def refused_symmetric(X):
+        P = L.poses_to_c(X.poses)
+        out = np.zeros((2, L.EDGE_BLOCK)); fx = np.ascontiguousarray(fixed, dtype=np.uint8).copy(); sm = L.Summary()
+        X.reject(STATE, needs, "mvicp_linearize_metric", L._dp(P), L.METRIC_SYMMETRIC, 1, L._dp(out))
+        X.reject(STATE, needs, "mvicp_optimize_metric", L._dp(P), _u8(fx), 2, L.METRIC_SYMMETRIC, 1, 50, C.byref(sm))
+        assert np.array_equal(P, L.poses_to_c(X.poses)) and not np.any(out)
+
+    def script(X):
+        E = X.E
+        X.poses = np.array(pb["init"]).copy()
+        E.set_frames(pts, nor); E.set_graph(src, dst)
+        c, w = E.correspond(X.poses, fixed, CUTOFF)
+        assert c[0] > 0, c
+        yield ("counts",), c
+        refused_symmetric(X)
+        refused_normals(X, npts, first_only=True, frames=(2,))
+        refused_symmetric(X)
+        for metric in (L.METRIC_POINT, L.METRIC_PLANE):
+            yield ("blocks", metric), E.linearize_metric(X.poses, metric, 1)
+        yield ("epochs",), E.correspondence_epochs()
+        for e in range(2):
+            yield ("list", e), E.get_correspondences(e)
+        P, sm = E.optimize_metric(X.poses, fixed, L.PARAM_SOPHUS_SE3, L.METRIC_POINT, True, 50)
+        yield ("point poses",), P
+        yield ("point iterations, final cost",), (int(sm["iterations"]), float(sm["final_cost"]))
+        refused_symmetric(X)
+        yield ("recompute_normals", 2), E.recompute_normals(2, 10)
+        yield ("symmetric blocks",), E.linearize_metric(X.poses, L.METRIC_SYMMETRIC, 1)
+        Ps, sms = E.optimize_metric(X.poses, fixed, L.PARAM_SOPHUS_SE3, L.METRIC_SYMMETRIC, True, 50)
+        yield ("symmetric poses",), Ps
+        yield ("symmetric iterations, final cost",), (int(sms["iterations"]), float(sms["final_cost"]))
+
+    assert twin(script) == 12

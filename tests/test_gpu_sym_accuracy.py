@@ -202,3 +202,33 @@ def test_symmetric_evaluation_sees_recomputed_source_normals():
     finally:
         eng.close()
     assert not failures, failures
+
+
+NO_ROTATIONS = {"reflection": lambda R: R @ np.diag([1.0, 1.0, -1.0]), "3R": lambda R: 3.0 * R, "0.3R": lambda R: 0.3 * R, "zero": lambda R: np.zeros((3, 3))}
+
+
+@pytest.mark.parametrize("kind", list(NO_ROTATIONS))
+def test_symmetric_destination_that_is_no_rotation_gets_the_transpose(kind):
+    """A destination matrix whose determinant is outside (0.5, 2) — a reflection (-1), 3 R (27), 0.3 R (0.027), the zero matrix — takes the other
+    branch of the relative transform (api.cpp fill_rel_sym): R_d^T in the place of the inverse.  The blocks mean nothing there, but they are
+    finite and they ARE the kernel's formulation with that substitution: symref.centred_blocks (which writes R_d^T) in long double.  The direct
+    world-frame rows are no reference for such a matrix, so the yardstick is the same formulation in plain fp64 with serial sums, x MARGIN.
+    N = 513 at chunk 512: two partials, the second a single tail lane."""
+    case = symcases.make_case("no rotation: " + kind, seed=1100, N=513, chunk=512)
+    poses = case["poses"].copy()
+    poses[0][:3, :3] = NO_ROTATIONS[kind](case["poses"][0][:3, :3])
+    det = np.linalg.det(poses[0][:3, :3])
+    assert not 0.5 < det < 2.0, det
+    p, q, nq, npn = symcases.gathered(case)
+    eng = _engine(case)
+    failures = []
+    try:
+        eng.set_correspondences(0, case["first"], case["second"], case["a"])
+        for robust in (1, 0):
+            blk = eng.linearize_metric(poses, METRIC_SYMMETRIC, robust)[0]
+            ref = symref.centred_blocks(p, q, nq, npn, poses[1], poses[0], case["a"], robust)
+            err_ref = symref.piece_errors(symref.centred_blocks(p, q, nq, npn, poses[1], poses[0], case["a"], robust, ftype=np.float64), ref)
+            _judge(blk, ref, err_ref, "no rotation: %s (det %.3g)" % (kind, det), robust, failures)
+    finally:
+        eng.close()
+    assert not failures, failures

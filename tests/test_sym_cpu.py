@@ -193,3 +193,90 @@ def test_symmetric_registration_ends_closer_to_the_truth_than_point_to_plane(par
     print("partial=%s  point-to-plane ends %.4f deg, %.4f spacings  |  symmetric ends %.4f deg, %.4f spacings  (ratios %.1f, %.1f)" % (
         partial, got[False][0], got[False][1], got[True][0], got[True][1], got[False][0] / got[True][0], got[False][1] / got[True][1]))
     assert got[True][0] < got[False][0] and got[True][1] < got[False][1], got
+
+
+def _ld_inverse(M):
+    """3x3 inverse by cofactors in long double (numpy's linalg has no long double)"""
+    M = np.asarray(M, dtype=LD)
+    C = np.array([[M[(i + 1) % 3, (j + 1) % 3] * M[(i + 2) % 3, (j + 2) % 3] - M[(i + 1) % 3, (j + 2) % 3] * M[(i + 2) % 3, (j + 1) % 3] for j in range(3)] for i in range(3)], dtype=LD)
+    return C.T / (M[0] * C[0]).sum()
+
+
+@pytest.mark.parametrize("robust", [1, 0])
+def test_the_transpose_substitution_reduces_to_the_centred_blocks_for_a_rotation(robust):
+    """tests/test_gpu_sym_accuracy.py holds the kernel at a destination that is no rotation to symref.centred_blocks, because that function writes
+    R_d^T where the library (for a rotation) forms the true inverse.  Here: (i) `inv` really is the matrix in the place of R_d^-1 — handing in
+    R_d^T gives the default's values bit for bit, handing in another matrix does not; (ii) for a rotation orthonormal to long-double rounding
+    the true inverse and the transpose give the same blocks to the bound of the tests above, so for rotations the substituted reference is the
+    one every other test uses; (iii) the fp64 variant (the GPU test's yardstick) is the same formulation: it agrees with the long-double one
+    to fp64 rounding, printed, and within the N x 2^-52 x extent / noise that a coherent rounding of the residual can cost."""
+    case = symcases.make_case("substitution", seed=77, N=513)
+    p, q, nq, npn = symcases.gathered(case)
+    Pd, Ps = _ld_orthonormal(case["poses"][0]), _ld_orthonormal(case["poses"][1])
+    base = symref.centred_blocks(p, q, nq, npn, Ps, Pd, case["a"], robust)
+    same = symref.centred_blocks(p, q, nq, npn, Ps, Pd, case["a"], robust, inv=Pd[:3, :3].T)
+    assert all(np.array_equal(np.atleast_1d(a), np.atleast_1d(b)) for a, b in zip(base, same))
+    other = symref.centred_blocks(p, q, nq, npn, Ps, Pd, case["a"], robust, inv=3 * Pd[:3, :3].T)
+    assert not np.array_equal(other[0], base[0])
+    true_inv = symref.centred_blocks(p, q, nq, npn, Ps, Pd, case["a"], robust, inv=_ld_inverse(Pd[:3, :3]))
+    bound = 1024 * LD(2.0) ** -64 * (1 + np.sqrt(len(p)) * 2.0 / lincases.NOISE)     # (clean x coherent rounding of p~ against the residual, as above: extent = |t| + 1 <= 2)
+    worst = 0.0
+    for a, b in zip(true_inv, base):
+        a, b = np.atleast_1d(a), np.atleast_1d(b)
+        worst = max(worst, float(np.abs(a - b).max() / np.abs(b).max()))
+    print("true inverse against transpose, long double, robust=%d: %.1e (bound %.1e)" % (robust, worst, float(bound)))
+    assert worst <= bound
+    err = symref.piece_errors(symref.centred_blocks(p, q, nq, npn, Ps.astype(np.float64), Pd.astype(np.float64), case["a"], robust, ftype=np.float64),
+                              symref.centred_blocks(p, q, nq, npn, Ps.astype(np.float64), Pd.astype(np.float64), case["a"], robust))
+    print("fp64 variant against long double, robust=%d: worst piece %.1e" % (robust, max(err.values())))
+    assert max(err.values()) <= len(p) * 2.0 ** -52 * 2.0 / lincases.NOISE
+    # and for a destination that is no rotation the fp64 variant still is the long-double one to fp64 rounding (nothing cancels there)
+    Pn = case["poses"][0].copy(); Pn[:3, :3] = 3.0 * Pn[:3, :3]
+    err = symref.piece_errors(symref.centred_blocks(p, q, nq, npn, case["poses"][1], Pn, case["a"], robust, ftype=np.float64),
+                              symref.centred_blocks(p, q, nq, npn, case["poses"][1], Pn, case["a"], robust))
+    print("fp64 variant against long double at 3 R, robust=%d: worst piece %.1e" % (robust, max(err.values())))
+    assert max(err.values()) <= len(p) * 2.0 ** -52
+
+
+# ---------------------------------------------------------------- symmetric solves that reject steps (tests/symreject.py)
+@pytest.fixture(scope="module")
+def symrej_world(orc):
+    import lmreject
+    pb, corr, w = lmreject.lists_at_init(orc)
+    return pb, corr, w
+
+
+def _symrej_cases():
+    import symreject
+    return [pytest.param(c, id=symreject.case_id(c)) for c in symreject.CASES]
+
+
+@pytest.mark.parametrize("case", _symrej_cases())
+def test_symmetric_reference_solves_reject_as_recorded(symrej_world, case, monkeypatch, capfd):
+    """The reference of tests/test_gpu_sym_rejected.py — the host solve over symref.blocks_fp64 — from the starts of tests/symreject.py: its
+    iterations and successful steps are the recorded ones, it stops on the function tolerance, a must-reject case rejects at least two steps,
+    and no accept / reject decision of any case is closer than 1e-6 to min_relative_decrease (the recorded margins hold): device blocks that
+    agree with the fp64 rows to 1e-11 cannot flip a decision, so the GPU test may assert equal COUNTS."""
+    import symreject
+    pb, corr, w = symrej_world
+    P0, P, sm, rd = symreject.traced_reference_solve(pb, corr, w, case, 50, monkeypatch, capfd)
+    margin = float(np.abs(rd - symreject.MIN_RELATIVE_DECREASE).min())
+    rejected = int((rd <= symreject.MIN_RELATIVE_DECREASE).sum())
+    print(symreject.case_id(case), sm["iterations"], "/", sm["successful_steps"], "termination", sm["termination"], "| rejected", rejected,
+          "| min |relative_decrease - 1e-3| = %.3e" % margin)
+    assert (sm["iterations"], sm["successful_steps"]) == symreject.MEASURED[case] and sm["termination"] == 3, sm
+    assert rejected == sm["iterations"] - sm["successful_steps"] - 1
+    if case in symreject.REJECTING:
+        assert rejected >= 2, (sm, rd)
+    else:
+        assert rejected == 0, (sm, rd)
+    assert margin > 1e-6 and margin >= symreject.MEASURED_MARGIN[case], (margin, rd)
+    assert not np.array_equal(P, P0)
+
+
+@pytest.mark.parametrize("case", _symrej_cases())
+def test_symmetric_reference_solves_stop_at_the_iteration_limit(symrej_world, case):
+    import symreject
+    pb, corr, w = symrej_world
+    _, _, sm = symreject.reference_solve(pb, corr, w, case, 3)
+    assert sm["termination"] == 0 and sm["iterations"] == 3 and sm["evaluations"] == 4, sm
