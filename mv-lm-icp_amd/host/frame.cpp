@@ -17,19 +17,25 @@ static void check(int st) {
   if (st < 0) throw std::runtime_error(std::string("mvicp: ") + mvicp_last_error());
 }
 
+// a refused call's message, taken before any further library call (a clean-up call may overwrite the thread's message)
+static std::string failure(int st) { return st < 0 ? std::string("mvicp: ") + mvicp_last_error() : std::string(); }
+
 Session& Session::get() {
-  static Session s;
-  return s;
+  static Session* s = new Session();   // never destroyed: ~Frame() of a Frame with static lifetime may still ask for it during exit
+  return *s;
 }
 
 void Session::reset() {
   if (ctx) mvicp_destroy(ctx);
   if (side_ctx) mvicp_destroy(side_ctx);
-  ctx = nullptr; side_ctx = nullptr; side_owner = nullptr;
+  ctx = nullptr; side_ctx = nullptr; side_owner = nullptr; side_key = FrameKey{nullptr, nullptr, 0, nullptr, 0};
   frames_key = nullptr;
   frame_keys.clear();
   last_poses.clear();
   graph_bound = false;
+  esrc.clear(); edst.clear();
+  held.clear(); epochs = nullptr; corr = nullptr; corr_off = nullptr;   // (they pointed into the context that has just ended)
+  ++knn_generation;
 }
 
 void Session::invalidate() {
@@ -38,7 +44,15 @@ void Session::invalidate() {
   frame_keys.clear();
   last_poses.clear();
   side_owner = nullptr;
+  ++knn_generation;
 }
+
+void Session::forget(const Frame* f) {
+  if (side_owner == f) side_owner = nullptr;
+  if (frame_index(f) >= 0) { frames_key = nullptr; frame_keys.clear(); last_poses.clear(); }   // the next bind uploads; the lists' bookkeeping is per edge and stays
+}
+
+Frame::~Frame() { Session::get().forget(this); }
 
 int Session::frame_index(const Frame* f) const {
   for (size_t i = 0; i < frame_keys.size(); ++i) if (frame_keys[i].f == f) return (int)i;
@@ -55,6 +69,10 @@ static std::vector<Session::FrameKey> frame_keys_of(const std::vector<std::share
 }
 
 void Session::upload(std::vector<std::shared_ptr<Frame>>& frames) {
+  // mvicp_set_num_frames drops every cloud and the graph: from here until the caller records the new keys the session holds nothing it
+  // could take for current, whichever call below throws
+  frames_key = nullptr; frame_keys.clear(); graph_bound = false; esrc.clear(); edst.clear();
+  last_poses.clear(); held.clear(); epochs = nullptr; corr = nullptr; corr_off = nullptr;
   if (!ctx) check(mvicp_create(device, &ctx));
   check(mvicp_set_num_frames(ctx, (int)frames.size()));
   for (size_t i = 0; i < frames.size(); ++i) {
@@ -133,6 +151,8 @@ int Session::initFromFeatures(std::vector<std::shared_ptr<Frame>>& frames, const
   if (K < 1) return 0;
   // the clouds that carry the features: the frames themselves or their voxel copies
   std::vector<std::shared_ptr<Frame>> feat;
+  // (with voxel > 0 the session holds the copies, which end with this call -- also when it throws: the next bind uploads the frames)
+  struct Forget { Session* s; bool on; ~Forget() { if (on) s->invalidate(); } } forget_copies{this, o.voxel > 0.0};
   if (o.voxel > 0.0) {
     ensure_uploaded(frames);   // (voxelDownsample then finds every frame in the session)
     for (auto& f : frames) feat.push_back(f->voxelDownsample(o.voxel));
@@ -214,7 +234,6 @@ int Session::initFromFeatures(std::vector<std::shared_ptr<Frame>>& frames, const
                                            nullptr, nullptr);
   check(comps);
   for (int i = 1; i < K; ++i) std::memcpy(frames[i]->pose.data(), &out[16 * (size_t)i], 128);
-  if (o.voxel > 0.0) invalidate();   // (the session holds the copies, which end here: the next bind uploads the frames)
   return comps;
 }
 
@@ -223,14 +242,23 @@ void Session::correspond(std::vector<std::shared_ptr<Frame>>& frames, float thre
   std::vector<double> P(16 * frames.size());
   std::vector<unsigned char> fx(frames.size());
   for (size_t i = 0; i < frames.size(); ++i) { std::memcpy(&P[16 * i], frames[i]->pose.data(), 128); fx[i] = frames[i]->fixed; }
-  if (P == last_poses && thresh == last_thresh && fx == last_fixed) return;  // same round: the batched result is still valid
+  if (P == last_poses && thresh == last_thresh && fx == last_fixed && nn_method == last_nn_method) {
+    // same round: the batched result is still valid.  (copy_back switched on since that search: its lists were never mapped)
+    if (copy_back && !corr) {
+      check(mvicp_map_correspondences_async(ctx, &corr, &corr_off));
+      check(mvicp_correspondence_epochs(ctx, &epochs));
+    }
+    return;
+  }
+  last_poses.clear();   // (a refused search leaves no cached round behind)
+  corr = nullptr; corr_off = nullptr;
   counts.assign(esrc.size(), 0);
   weights.assign(esrc.size(), 0.f);
   check(mvicp_correspond(ctx, P.data(), fx.data(), thresh, nn_method, counts.data(), weights.data()));
   last_poses = P;
   last_thresh = thresh;
   last_fixed = fx;
-  corr = nullptr; corr_off = nullptr;
+  last_nn_method = nn_method;
   // the literal drop-in contract: every list in the reference's layout, un-sorted on the device, ONE copy per round for all edges
   if (copy_back) {
     check(mvicp_map_correspondences_async(ctx, &corr, &corr_off));   // (no device work when the search reproduced every list: mvicp.h); chunks arrive frame by frame
@@ -376,8 +404,9 @@ void Frame::recomputeNormals() {
   int st = mvicp_set_num_frames(c, 1);
   if (st == MVICP_OK) st = mvicp_set_frame(c, 0, pts[0].data(), nullptr, (int)pts.size());
   if (st == MVICP_OK) st = mvicp_recompute_normals(c, 0, 10, nor[0].data(), nullptr);
+  const std::string err = failure(st);
   mvicp_destroy(c);
-  check(st);
+  if (st < 0) throw std::runtime_error(err);
   ++version;   // a bound session re-uploads this cloud (new normals) at its next bind
 }
 
@@ -385,16 +414,20 @@ const std::vector<int>& Frame::getNeighbourIndices(size_t num_results) {
   if (pts.empty()) throw std::runtime_error("mvicp: getNeighbours on an empty cloud (nanoflann throws here: nanoflann.hpp:904)");
   if (num_results < 3 || num_results > 16 || num_results > pts.size())
     throw std::runtime_error("mvicp: getNeighbours supports 3 <= num_results <= 16 (and <= the cloud's size); the reference asks for 10 (frame.cpp:249)");
-  if (knn_k_ == num_results && knn_pts_ == (const void*)pts[0].data() && knn_n_ == pts.size()) return knn_table_;
+  const unsigned long long generation = Session::get().knn_generation;
+  if (knn_k_ == num_results && knn_pts_ == (const void*)pts[0].data() && knn_n_ == pts.size() && knn_version_ == version && knn_generation_ == generation)
+    return knn_table_;
   mvicp_ctx* c = nullptr;
   check(mvicp_create(Session::get().device, &c));
   std::vector<int> table(pts.size() * num_results);
   int st = mvicp_set_num_frames(c, 1);
   if (st == MVICP_OK) st = mvicp_set_frame(c, 0, pts[0].data(), nullptr, (int)pts.size());
   if (st == MVICP_OK) st = mvicp_recompute_normals(c, 0, (int)num_results, nullptr, table.data());
+  const std::string err = failure(st);
   mvicp_destroy(c);
-  check(st);
+  if (st < 0) throw std::runtime_error(err);
   knn_table_.swap(table); knn_k_ = num_results; knn_pts_ = (const void*)pts[0].data(); knn_n_ = pts.size();
+  knn_version_ = version; knn_generation_ = generation;
   return knn_table_;
 }
 
@@ -418,12 +451,16 @@ mvicp_ctx* Session::query_context(Frame* f, int* slot, bool with_normals) {
   if (fi >= 0 && frame_keys[fi].pts == (const void*)f->pts[0].data() && frame_keys[fi].n == f->pts.size() &&
       (!with_normals || (frame_keys[fi].nor == (f->nor.empty() ? nullptr : (const void*)f->nor[0].data()) && frame_keys[fi].version == f->version))) { *slot = fi; return ctx; }
   const bool want_nor = with_normals && has_nor;
-  if (side_owner != f || side_version != f->version || !side_ctx || (want_nor && !side_nor)) {
+  // the same key as the bound path: the frame, its buffers, its size and its version (the normals' buffer only where the side copy holds them)
+  const FrameKey key{f, (const void*)f->pts[0].data(), f->pts.size(), f->nor.empty() ? nullptr : (const void*)f->nor[0].data(), f->version};
+  const bool same = side_ctx && side_owner == f && side_key.f == f && side_key.pts == key.pts && side_key.n == key.n && side_key.version == key.version &&
+                    (!side_nor || side_key.nor == key.nor);
+  if (!same || (want_nor && !side_nor)) {
+    side_owner = nullptr;   // (forgotten first: a refused upload below leaves a side context nobody owns)
     if (!side_ctx) check(mvicp_create(device, &side_ctx));
     check(mvicp_set_num_frames(side_ctx, 1));
-    side_owner = nullptr;
     check(mvicp_set_frame(side_ctx, 0, f->pts[0].data(), want_nor ? f->nor[0].data() : nullptr, (int)f->pts.size()));
-    side_owner = f; side_version = f->version; side_nor = want_nor;
+    side_owner = f; side_version = f->version; side_nor = want_nor; side_key = key;
   }
   *slot = 0;
   return side_ctx;

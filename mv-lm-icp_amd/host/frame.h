@@ -7,6 +7,19 @@
 // Differences forced by the boundary: errors are thrown as std::runtime_error carrying mvicp_last_error() (the
 // reference has nothing to propagate); OutgoingEdge::P_relative (never used, frame.h:28) is dropped; draw()/GL
 // members are out of scope.
+//
+// WHAT THE MIRROR NOTICES (the one rule; INTEGRATION.md "What the mirror notices").  The device copies, the cached search and
+// the k-NN table are keyed on addresses, sizes and counters, never on the clouds' values:
+//   noticed by itself   a `pts` / `nor` vector REPLACED by another one (another buffer address or another size) on a bound and on an
+//                       unbound frame; `version` (recomputeNormals() bumps it); a Frame destroyed, or destroyed and constructed again in
+//                       the same storage (~Frame() tells the session); another frames vector, other frames in it, another order, another
+//                       graph; changed poses / thresh / fixed / Session::nn_method; Session::copy_back switched; any call that threw
+//                       (whatever the session believed about the device copy it was uploading is forgotten before the upload starts).
+//   needs invalidate()  values of `pts` / `nor` edited IN PLACE -- overwritten elements, or an assignment that reuses the vector's capacity
+//                       (same address, same size): call Session::get().invalidate() before the next call.
+//   the k-NN table      of getNeighbours / getNeighbourIndices is dropped by a replaced `pts` vector, by `version` and by
+//                       Session::invalidate() (for in-place edits).
+//   the lists           a caller that overwrites ELEMENTS of a filled correspondence list calls Session::invalidate_lists() (see `held`).
 #pragma once
 #include <memory>
 #include <string>
@@ -35,6 +48,11 @@ class Frame {
   Isometry3d poseGroundTruth;
   std::vector<OutgoingEdge> neighbours;
   unsigned long long version = 0;   // bumped by recomputeNormals(): the session re-uploads the cloud when it changes
+
+  Frame() = default;
+  Frame(const Frame&) = default;
+  Frame& operator=(const Frame&) = default;
+  ~Frame();   // tells the session: a Frame constructed later at this address is never taken for this one
 
   // frame.cpp:67-89 (host; tiny)
   void computePoseNeighboursKnn(std::vector<std::shared_ptr<Frame>>* frames, int i, int k);
@@ -74,7 +92,9 @@ class Frame {
   std::vector<int> issKeypoints(double salient_radius, double non_max_radius, double gamma21 = 0.975, double gamma32 = 0.975, int min_neighbors = 5);
 
  private:
-  std::vector<int> knn_table_; size_t knn_k_ = 0; const void* knn_pts_ = nullptr; size_t knn_n_ = 0;   // cache of getNeighbourIndices
+  // cache of getNeighbourIndices and what it was built from: k, the pts buffer and size, `version`, Session::knn_generation
+  std::vector<int> knn_table_; size_t knn_k_ = 0; const void* knn_pts_ = nullptr; size_t knn_n_ = 0;
+  unsigned long long knn_version_ = 0, knn_generation_ = 0;
 };
 
 // Process-wide device session behind the Frame / ICP_Ceres calls: uploads the (static) clouds once, mirrors the
@@ -96,6 +116,7 @@ struct Session {
   unsigned long long edges_copied = 0, edges_skipped = 0;   // statistics of the copy-back (tests, bench)
   void invalidate_lists() { held.assign(held.size(), Held()); }
   int nn_method = MVICP_NN_AUTO;
+  int last_nn_method = MVICP_NN_AUTO;      // of the cached search
   const void* frames_key = nullptr;
   // what the device copy was built from: per frame {Frame*, pts data, size, nor data, normals version}; any difference
   // (a re-loaded cloud, recomputeNormals(), an edited point vector) triggers a fresh upload at the next bind
@@ -106,13 +127,17 @@ struct Session {
   std::vector<double> last_poses;
   std::vector<unsigned char> last_fixed;
   float last_thresh = -1.f;
-  mvicp_ctx* side_ctx = nullptr; const Frame* side_owner = nullptr; unsigned long long side_version = 0;  // getClosestPoint on an unbound frame
+  // getClosestPoint on an unbound frame: the side context holds the cloud of side_owner as it was at side_key (frame, buffers, size, version)
+  mvicp_ctx* side_ctx = nullptr; const Frame* side_owner = nullptr; unsigned long long side_version = 0;
+  FrameKey side_key{nullptr, nullptr, 0, nullptr, 0};
   bool side_nor = false;                   // the side context holds the frame's normals too (voxelDownsample asks for them)
   int frame_index(const Frame* f) const;   // position of f in the bound vector, or -1
   // context + frame slot that hold `f`'s cloud for raw queries: the bound session if f is part of it, else a one-cloud side context.
   // with_normals: the slot must hold the frame's CURRENT normals as well (the bound session only if it was uploaded from them)
   mvicp_ctx* query_context(Frame* f, int* slot, bool with_normals = false);
-  void invalidate();                       // forget the device copy (forces re-upload + fresh search); for in-place edits of pts/nor data
+  void invalidate();                       // forget the device copy (forces re-upload + fresh search) and every frame's k-NN table; for in-place edits of pts/nor data
+  void forget(const Frame* f);             // ~Frame(): nothing the session holds is attributed to this address any more
+  unsigned long long knn_generation = 1;   // bumped by invalidate(): a Frame's k-NN table of an older generation is rebuilt
   std::vector<int> counts;
   std::vector<float> weights;
   bool graph_bound = false;                                   // the context holds the graph of esrc / edst (false: clouds only)
