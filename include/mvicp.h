@@ -359,6 +359,61 @@ long long mvicp_iss_keypoints(mvicp_ctx* ctx, int frame, double salient_radius, 
 int mvicp_iss_fetch(mvicp_ctx* ctx, long long cap_keys, int* idx, double* xyz, double* nrm, long long cap_n, double* saliency, int* cnt_salient,
                     int* cnt_nms);
 
+/* ---- Normals with curvature, oriented to a viewpoint, exactly specified --------------------------------------------------------------
+ * The stage between "clean cloud" and "describe / register on planes": per point the direction of least variance of its neighbourhood,
+ * turned towards a viewpoint, and the surface variation.  Unlike mvicp_recompute_normals (the reference's recomputeNormals: k <= 16,
+ * nanoflann's tie order, n_z <= 0, agreement to rounding) the result is a pure function of the stored bytes, bit for bit
+ * (tests/normref.py is the same definition in numpy and as a scalar loop), and orienting the normals of several clouds consistently --
+ * which FPFH and the symmetric objective depend on -- is the viewpoint's job: pass the sensor position of each view in that view's own
+ * coordinates.  All arithmetic is fp64, every operation rounded on its own, no fma; only + - x / sqrt, comparisons and negation occur
+ * (DESIGN.md section 3.14):
+ *   Inputs     the stored cloud p_0 .. p_{n-1} of `frame` (the stored bytes, no pose); 3 <= max_nn <= 64; radius <= 0: the max_nn nearest,
+ *              radius finite and > 0: the max_nn nearest within the radius; viewpoint: 3 finite doubles in the frame's local coordinates,
+ *              NULL = (0, 0, 0), the sensor origin of a view in its own frame.
+ *   N(i)       row i of mvicp_knn_search(frame, NULL, max_nn, radius) -- self mode, the order (dist2, original index), the point itself
+ *              and exact duplicates included; c_i = cnt[i], position t of the row holds neighbour j_t.
+ *   Offsets    d_t = p_{j_t} - p_i per component for t < c_i, +0.0 for c_i <= t < 64.  (Offsets from the point itself: a coordinate that
+ *              all neighbours share then cancels exactly.)
+ *   Tree sum   T(y) of 64 values: six times y[u] <- y[2u] + y[2u+1] (u = 0 .. half the length - 1); T(y) = y[0].  The order is part of
+ *              the contract.
+ *   Moments    mean_a = T(d_a) / (double)c_i; x_{t,a} = d_{t,a} - mean_a for t < c_i, else +0.0; C_ab = T(x_a * x_b) for a <= b, mirrored.
+ *   Eigenvectors  A = C, V = the identity.  The Jacobi iteration of mvicp_iss_keypoints: exactly 6 sweeps, no early exit, each over
+ *              (p, q) = (0,1), (0,2), (1,2) in that order.  A rotation is skipped iff A[p][q] == 0; otherwise
+ *              theta = (A[q][q] - A[p][p]) / (2.0 * A[p][q]), t = (theta >= 0 ? 1.0 : -1.0) / (|theta| + sqrt(theta * theta + 1.0)),
+ *              c = 1.0 / sqrt(t * t + 1.0), s = t * c; for r = 0, 1, 2: (A[r][p], A[r][q]) <- (c * A[r][p] - s * A[r][q],
+ *              s * A[r][p] + c * A[r][q]); then for r = 0, 1, 2: (A[p][r], A[q][r]) <- (c * A[p][r] - s * A[q][r], s * A[p][r] + c * A[q][r]);
+ *              then for r = 0, 1, 2: (V[r][p], V[r][q]) <- (c * V[r][p] - s * V[r][q], s * V[r][p] + c * V[r][q]).
+ *   Normal     m = 0; if A[1][1] < A[m][m] then m = 1; if A[2][2] < A[m][m] then m = 2.  v = V[:, m], len = sqrt((v0 v0 + v1 v1) + v2 v2),
+ *              n = v / len.
+ *   Orientation  w = viewpoint - p_i, s = (n0 w0 + n1 w1) + n2 w2.  s < 0: every component of n is negated (a +0.0 becomes -0.0);
+ *              s == 0 keeps n.
+ *   Curvature  the surface variation: S = (A[0][0] + A[1][1]) + A[2][2], l = A[m][m]; curvature = l / S if l > 0 and S > 0, else +0.0.
+ *   Too few    c_i < 3: normal (+0.0, +0.0, +0.0), curvature +0.0.  used[i] = c_i in every case.
+ * nrm is n x 3 doubles, curvature n doubles, used n ints, row i the ORIGINAL index i; n = 0 gives zero rows and is not an error.  Rows of
+ * every neighbour within a radius (k = 0, unbounded length) are not offered: the tree has 64 leaves.
+ * The call performs mvicp_knn_search(frame, NULL, max_nn, radius) internally and AFTERWARDS THAT SEARCH IS THE CONTEXT'S LAST
+ * NEIGHBOUR-SEARCH RESULT, as with mvicp_fpfh.  Otherwise the call is HISTORY-NEUTRAL like mvicp_knn_search -- it does NOT touch the
+ * frame's normals -- needs the frame's hash structure (waits for pending builds and reports a failed one the same way) and NO graph; with
+ * several ranks every rank computes it locally.  It returns when the result is complete; the result lives in library-owned device memory
+ * of its own until the next mvicp_estimate_normals, an upload (mvicp_set_frame / mvicp_set_frame_device) to the same frame,
+ * mvicp_set_num_frames or mvicp_destroy.  Profile scopes: those of the search, "normals_pca".
+ * RETURNS THE NUMBER OF ROWS n (>= 0) or a negative mvicp_status.
+ * Errors: NULL context, max_nn outside [3, 64], a non-finite radius, a non-finite viewpoint entry, a frame index out of range ->
+ * MVICP_ERR_ARG, decided before the context is touched (earlier results stay); a frame never uploaded -> MVICP_ERR_STATE. */
+long long mvicp_estimate_normals(mvicp_ctx* ctx, int frame, int max_nn, double radius, const double* viewpoint);
+/* Copies the last result: nrm (n x 3 doubles), curvature (n doubles), used (n ints: c_i); each may be NULL; each may be a HOST pointer or a
+ * DEVICE pointer of the context's device, decided per pointer as mvicp_voxel_fetch decides.  cap_rows = rows the destinations hold.
+ * Errors: NULL context, cap_rows < n -> MVICP_ERR_ARG; no mvicp_estimate_normals before -> MVICP_ERR_STATE. */
+int mvicp_normals_fetch(mvicp_ctx* ctx, long long cap_rows, double* nrm, double* curvature, int* used);
+/* The frame of the last mvicp_estimate_normals takes that result's nrm as its normals.  In every observable this is what a successful
+ * mvicp_recompute_normals leaves for those values: the frame's original-order and sorted normals are written (allocated if the frame was
+ * uploaded without normals: point-to-plane and symmetric evaluation then accept it), every owned correspondence list that points into the
+ * frame is re-gathered, queued evaluations are voided.  The result stays fetchable afterwards.  With several ranks every rank calls it
+ * (after its own mvicp_estimate_normals); there is no communication.
+ * Errors: NULL context -> MVICP_ERR_ARG; no result, or the frame was uploaded again since the estimate (the upload dropped the result) ->
+ * MVICP_ERR_STATE, with nothing changed. */
+int mvicp_normals_adopt(mvicp_ctx* ctx);
+
 /* ---- Descriptor matching and a consensus coarse pose, exactly specified -------------------------------------------------------
  * The stage that turns two sets of descriptors into a coarse pose: two device stages, one host rule between them.  Each result is a
  * pure function of the input bytes, bit for bit (tests/matchref.py is the same definition in numpy and as a scalar loop).  All
@@ -611,7 +666,8 @@ int mvicp_linearize_pair(mvicp_ctx* ctx, const double* poses_a, const double* po
  * when the two normals agree, so the loss, the scale a = edge.weight and the cost sum rho / 2 are those of PLANE.  Per row
  * u = [m ; (p~ x n_q + q x nu) / 2], J = [Ad^T u ; -u] in the coordinates above (csrc/linearize_sym.hip).
  * THE NORMALS ARE USED AS STORED: no sign flip, no normalisation.  Orienting the normals of the clouds consistently with each other
- * (the same side of the surface in every frame) is the caller's job; with opposite orientations m is half the DIFFERENCE of the normals.
+ * (the same side of the surface in every frame) is the caller's job -- mvicp_estimate_normals with each view's sensor position as
+ * viewpoint is the tool for it; with opposite orientations m is half the DIFFERENCE of the normals.
  * The source normal is the source frame's current one: after mvicp_recompute_normals the next evaluation sees the new normals.
  * For this objective the relative transform of an edge is formed with the true inverse of the destination's rotation, in extended
  * precision (for a rotation that is its transpose): the result does not depend on how far the given poses are from orthonormal to the

@@ -619,7 +619,7 @@ int mvicp_create(int device, mvicp_ctx** out) try {
 // the results and the buffers of every stage that keeps its last result on the context (common.h)
 static void release_stages(mvicp_ctx* c) {
   c->vox.release(); c->out.release(); c->knn.release(); c->fpfh.release();
-  c->match.release(); c->cons.release(); c->coarse.release(); c->iss.release();
+  c->match.release(); c->cons.release(); c->coarse.release(); c->iss.release(); c->nrm.release();
 }
 
 int mvicp_destroy(mvicp_ctx* c) try {
@@ -677,6 +677,7 @@ int mvicp_set_frame(mvicp_ctx* c, int frame, const double* xyz, const double* nr
     max_norm = std::max(max_norm, std::sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]));
   }
   FrameDev& f = c->frames[frame];
+  if (c->nrm.frame == frame) c->nrm.drop_result();   // (estimated normals of the cloud this call replaces: nothing to adopt them into)
   if (f.job) { try { (void)f.job->fut.get(); } catch (...) {} f.job.reset(); }   // a build of the cloud this call replaces
   dev_free(f.pts); dev_free(f.nor); free_grid(f.grid); free_tie(f);
   f.has_grid = false; f.build_error.clear();
@@ -755,6 +756,7 @@ int mvicp_set_frame_device(mvicp_ctx* c, int frame, const double* d_xyz, const d
     if (b.nonfinite) { set_error("non-finite coordinate in cloud"); return MVICP_ERR_ARG; }
   }
   FrameDev& f = c->frames[frame];
+  if (c->nrm.frame == frame) c->nrm.drop_result();   // (estimated normals of the cloud this call replaces: nothing to adopt them into)
   if (f.job) { try { (void)f.job->fut.get(); } catch (...) {} f.job.reset(); }   // a build of the cloud this call replaces
   dev_free(f.pts); dev_free(f.nor); free_grid(f.grid); free_tie(f);
   f.has_grid = false; f.build_error.clear();
@@ -850,6 +852,28 @@ long long mvicp_get_structure(mvicp_ctx* c, int frame, const char* name, void* o
   return (long long)bytes;
 } MVICP_GUARD_ABI
 
+// What follows new normals of `frame` (mvicp_recompute_normals, mvicp_normals_adopt), `st` being the status of the call so far: queued
+// evaluations are void, and after a success every owned list that points into the frame is re-gathered.
+static int normals_changed(mvicp_ctx* c, int frame, int st) {
+  c->spec_ready = false; c->spec2_ready = false;
+  if (st == MVICP_OK && c->E > 0) {
+    // The packed operand stream bakes the dst normals in (n and c = n . q, gathered at correspond time) while the reference
+    // reads dstCloud.nor when it builds the problem (icp-ceres.cpp:270-292): every list that points INTO this frame is stale.
+    // Re-gather those edges now and never reuse their lists unchecked.
+    bool any = false;
+    std::vector<int> dirty(c->E, 0);
+    for (int e = 0; e < c->E; ++e)
+      if (c->owned[e] && c->edst[e] == frame) { c->list_valid[e] = 0; if (c->have_corr && c->h_count[e] > 0) { dirty[e] = 1; any = true; } }
+    if (any) {
+      MV_HIP(hipMemcpy(c->d_dirty, dirty.data(), sizeof(int) * c->E, hipMemcpyHostToDevice));
+      MV_CHECK(launch_gather_stream(c));
+      MV_HIP(hipStreamSynchronize(c->stream));
+    }
+  }
+  if (c->profile) prof_collect_lazy(c);
+  return st;
+}
+
 int mvicp_recompute_normals(mvicp_ctx* c, int frame, int k, double* nrm_out, int* knn_out) try {
   MV_CHECK(bind(c));
   if (frame < 0 || frame >= c->n_frames) { set_error("frame %d out of range", frame); return MVICP_ERR_ARG; }
@@ -879,23 +903,7 @@ int mvicp_recompute_normals(mvicp_ctx* c, int frame, int k, double* nrm_out, int
     if (fresh_nor) dev_free(f.nor);
     if (fresh_snor) dev_free(f.grid.snor);
   }
-  c->spec_ready = false; c->spec2_ready = false;
-  if (st == MVICP_OK && c->E > 0) {
-    // The packed operand stream bakes the dst normals in (n and c = n . q, gathered at correspond time) while the reference
-    // reads dstCloud.nor when it builds the problem (icp-ceres.cpp:270-292): every list that points INTO this frame is stale.
-    // Re-gather those edges now and never reuse their lists unchecked.
-    bool any = false;
-    std::vector<int> dirty(c->E, 0);
-    for (int e = 0; e < c->E; ++e)
-      if (c->owned[e] && c->edst[e] == frame) { c->list_valid[e] = 0; if (c->have_corr && c->h_count[e] > 0) { dirty[e] = 1; any = true; } }
-    if (any) {
-      MV_HIP(hipMemcpy(c->d_dirty, dirty.data(), sizeof(int) * c->E, hipMemcpyHostToDevice));
-      MV_CHECK(launch_gather_stream(c));
-      MV_HIP(hipStreamSynchronize(c->stream));
-    }
-  }
-  if (c->profile) prof_collect_lazy(c);
-  return st;
+  return normals_changed(c, frame, st);
 } MVICP_GUARD_ABI
 
 int mvicp_set_shard(mvicp_ctx* c, int rank, int world) try {
@@ -1100,6 +1108,63 @@ int mvicp_fpfh_fetch(mvicp_ctx* c, long long cap_rows, double* desc, int* used) 
   const size_t n = (size_t)c->fpfh.rows;
   const FetchPart parts[] = {{desc, c->fpfh.desc, 33 * 8 * n, "desc"}, {used, c->fpfh.used, 4 * n, "used"}};
   return fetch_parts(c, parts);
+} MVICP_GUARD_ABI
+
+long long mvicp_estimate_normals(mvicp_ctx* c, int frame, int max_nn, double radius, const double* viewpoint) try {
+  // every argument error that needs no GPU first: nothing of the context has been touched when one of them is reported
+  if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
+  if (max_nn < 3 || max_nn > 64) { set_error("max_nn = %d outside [3, 64]", max_nn); return MVICP_ERR_ARG; }
+  if (!std::isfinite(radius)) { set_error("radius must be finite (<= 0: no radius)"); return MVICP_ERR_ARG; }
+  double vp[3] = {0.0, 0.0, 0.0};
+  for (int a = 0; viewpoint && a < 3; ++a) {
+    if (!std::isfinite(viewpoint[a])) { set_error("viewpoint[%d] is not finite", a); return MVICP_ERR_ARG; }
+    vp[a] = viewpoint[a];
+  }
+  if (frame < 0 || frame >= c->n_frames) { set_error("frame %d out of range [0,%d)", frame, c->n_frames); return MVICP_ERR_ARG; }
+  const FrameDev& f = c->frames[frame];
+  if (!f.pts) { set_error("frame %d was never uploaded", frame); return MVICP_ERR_STATE; }
+  MV_CHECK(bind(c));
+  MV_CHECK(finish_builds(c));
+  const long long rows = normals_estimate(c, f, max_nn, radius, radius > 0.0 ? sqrt_bound(radius) : 0.0, vp);
+  if (rows >= 0) c->nrm.frame = frame;
+  if (c->profile) prof_collect_lazy(c);
+  return rows;
+} MVICP_GUARD_ABI
+
+int mvicp_normals_fetch(mvicp_ctx* c, long long cap_rows, double* nrm, double* curvature, int* used) try {
+  if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
+  if (c->nrm.rows < 0) { set_error("no estimated normals: call mvicp_estimate_normals first"); return MVICP_ERR_STATE; }
+  if (cap_rows < c->nrm.rows) { set_error("cap_rows %lld < %lld rows", cap_rows, c->nrm.rows); return MVICP_ERR_ARG; }
+  if (c->nrm.rows == 0) return MVICP_OK;
+  const size_t n = (size_t)c->nrm.rows;
+  const FetchPart parts[] = {{nrm, c->nrm.nrm, 24 * n, "nrm"}, {curvature, c->nrm.curv, 8 * n, "curvature"}, {used, c->nrm.used, 4 * n, "used"}};
+  return fetch_parts(c, parts);
+} MVICP_GUARD_ABI
+
+int mvicp_normals_adopt(mvicp_ctx* c) try {
+  if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
+  if (c->nrm.rows < 0 || c->nrm.frame < 0 || c->nrm.frame >= c->n_frames) {
+    set_error("no estimated normals to adopt: call mvicp_estimate_normals first (an upload to its frame drops the result)");
+    return MVICP_ERR_STATE;
+  }
+  const int frame = c->nrm.frame;
+  FrameDev& f = c->frames[frame];
+  if (c->nrm.rows != f.n) { set_error("the estimated normals have %lld rows, frame %d has %d points", c->nrm.rows, frame, f.n); return MVICP_ERR_STATE; }
+  MV_CHECK(bind(c));
+  MV_CHECK(finish_builds(c));
+  if (f.n == 0) return MVICP_OK;   // (nothing to write)
+  if (!f.has_grid) { set_error("frame %d: adopting normals needs the per-cloud hash structure", frame); return MVICP_ERR_STATE; }
+  const bool fresh_nor = !f.nor, fresh_snor = !f.grid.snor;
+  int st = MVICP_OK;
+  if (fresh_nor) st = dev_alloc(&f.nor, 3 * (size_t)f.n);
+  if (st == MVICP_OK && fresh_snor) st = dev_alloc(&f.grid.snor, 3 * (size_t)f.n);
+  if (st == MVICP_OK) st = normals_adopt(c, f);
+  if (st != MVICP_OK) {   // what this call allocated goes with it: the frame has normals only if a call wrote them
+    (void)hipStreamSynchronize(c->stream);
+    if (fresh_nor) dev_free(f.nor);
+    if (fresh_snor) dev_free(f.grid.snor);
+  }
+  return normals_changed(c, frame, st);
 } MVICP_GUARD_ABI
 
 long long mvicp_iss_keypoints(mvicp_ctx* c, int frame, double salient_radius, double non_max_radius, double gamma21, double gamma32, int min_neighbors) try {

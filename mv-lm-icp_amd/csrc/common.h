@@ -119,8 +119,8 @@ struct ProfEntry {
 };
 
 // ---- buffers and results a stage of the library owns ---------------------------------------------------------------------------------
-// A stage (voxel grid, outlier filter, neighbour search, FPFH, descriptor matching, consensus, batched coarse poses, ISS keypoints) keeps
-// its LAST result on the context until the caller has fetched it.  Ownership, stated once for all eight: the stage's struct below holds
+// A stage (voxel grid, outlier filter, neighbour search, FPFH, descriptor matching, consensus, batched coarse poses, ISS keypoints, estimated
+// normals) keeps its LAST result on the context until the caller has fetched it.  Ownership, stated once for all nine: the stage's struct below holds
 // buffers of its own (so that a call touches nothing a search, a queued evaluation, the census or another stage uses), kept between
 // calls and grown on demand, the result arrays as views into them, and the sizes / flags, whose defaults mean "no result".  A call marks
 // its result as gone when it starts (a failed call leaves none behind) and sets it after its last wait; the result then lives until the
@@ -223,6 +223,15 @@ struct IssStage {
   double* sal = nullptr; int* cnt_s = nullptr; int* cnt_n = nullptr; int* idx = nullptr; double* xyz = nullptr; double* nrm = nullptr;
   long long n = -1, k = 0; int has_normals = 0;   // points of the frame (< 0: none), keypoints among them
   void release() { dev.release(); tmp.release(); pin.release(); *this = IssStage(); }
+};
+// normals_pca.hip.  dev: [nrm n x 3 doubles | curvature n doubles | used n ints]; the neighbourhoods are the KnnStage result of the search the
+// call runs.  frame: the slot the result was computed for (mvicp_normals_adopt writes there); an upload to that slot drops the result
+struct NormalsStage {
+  DevBuf dev;
+  double* nrm = nullptr; double* curv = nullptr; int* used = nullptr;
+  long long rows = -1; int frame = -1;   // rows < 0: none
+  void drop_result() { rows = -1; frame = -1; }
+  void release() { dev.release(); *this = NormalsStage(); }
 };
 
 struct RcclApi;  // comm.cpp
@@ -368,6 +377,7 @@ struct mvicp_ctx {
   mvicp::ConsensusStage cons;
   mvicp::CoarseStage coarse;
   mvicp::IssStage iss;
+  mvicp::NormalsStage nrm;
 
   // cached small tables
   struct CachedTable { std::vector<char> bytes; void* d = nullptr; size_t cap = 0; };
@@ -508,6 +518,12 @@ long long coarse_pairs(mvicp_ctx* c, const double* desc, int desc_on_device, con
 // radii, q = 20 - the binary exponent of the salient radius.  The result stays on the context (c->iss).  Returns the number of keypoints
 // or a negative status (a salient row of more than 1024 points: MVICP_ERR_ARG, no result).  Waits for the stream once; history-neutral.
 long long iss_keypoints(mvicp_ctx* c, const FrameDev& f, double B2_salient, double B2_nms, int q, double gamma21, double gamma32, int min_neighbors);
+// normals_pca.hip: knn_search(c, f, null, 0, 0, max_nn, radius, B2) and the PCA pass over its rows, for frame f (valid, uploaded, structures
+// built; 3 <= max_nn <= 64, B2 = sqrt_bound(radius) when radius > 0, viewpoint 3 finite doubles); the result stays on the context (c->nrm;
+// the caller sets c->nrm.frame), the search's in c->knn.  Returns the number of rows or a negative status.  Waits for the stream; history-neutral.
+long long normals_estimate(mvicp_ctx* c, const FrameDev& f, int max_nn, double radius, double B2, const double* viewpoint);
+// normals_pca.hip: c->nrm.nrm (f.n rows) into f.nor and f.grid.snor (both allocated, f.n > 0, structures built).  Waits for the stream.
+int normals_adopt(mvicp_ctx* c, FrameDev& f);
 int launch_compact(mvicp_ctx* c, double d2_bound);                                    // corr.hip
 int launch_gather_stream(mvicp_ctx* c);
 int launch_select_median(mvicp_ctx* c, double d2_bound);   // two-pass select anchored at the acceptance bound: any key set, exact

@@ -410,6 +410,21 @@ void Frame::recomputeNormals() {
   ++version;   // a bound session re-uploads this cloud (new normals) at its next bind
 }
 
+std::vector<double> Frame::estimateNormals(int max_nn, double radius, const Vector3d& viewpoint) {
+  std::vector<double> curvature;
+  if (pts.empty()) { nor.clear(); ++version; return curvature; }
+  int slot = 0;
+  mvicp_ctx* c = Session::get().query_context(this, &slot);
+  const long long n = mvicp_estimate_normals(c, slot, max_nn, radius, viewpoint.data());
+  if (n < 0) check((int)n);
+  std::vector<Vector3d> fresh((size_t)n);
+  curvature.assign((size_t)n, 0.0);
+  check(mvicp_normals_fetch(c, n, fresh[0].data(), curvature.data(), nullptr));
+  nor.swap(fresh);
+  ++version;   // a bound session re-uploads this cloud (new normals) at its next bind
+  return curvature;
+}
+
 const std::vector<int>& Frame::getNeighbourIndices(size_t num_results) {
   if (pts.empty()) throw std::runtime_error("mvicp: getNeighbours on an empty cloud (nanoflann throws here: nanoflann.hpp:904)");
   if (num_results < 3 || num_results > 16 || num_results > pts.size())

@@ -11,7 +11,7 @@
 // WHAT THE MIRROR NOTICES (the one rule; INTEGRATION.md "What the mirror notices").  The device copies, the cached search and
 // the k-NN table are keyed on addresses, sizes and counters, never on the clouds' values:
 //   noticed by itself   a `pts` / `nor` vector REPLACED by another one (another buffer address or another size) on a bound and on an
-//                       unbound frame; `version` (recomputeNormals() bumps it); a Frame destroyed, or destroyed and constructed again in
+//                       unbound frame; `version` (recomputeNormals() and estimateNormals() bump it); a Frame destroyed, or destroyed and constructed again in
 //                       the same storage (~Frame() tells the session); another frames vector, other frames in it, another order, another
 //                       graph; changed poses / thresh / fixed / Session::nn_method; Session::copy_back switched; any call that threw
 //                       (whatever the session believed about the device copy it was uploading is forgotten before the upload starts).
@@ -47,7 +47,7 @@ class Frame {
   Isometry3d pose;
   Isometry3d poseGroundTruth;
   std::vector<OutgoingEdge> neighbours;
-  unsigned long long version = 0;   // bumped by recomputeNormals(): the session re-uploads the cloud when it changes
+  unsigned long long version = 0;   // bumped by recomputeNormals() / estimateNormals(): the session re-uploads the cloud when it changes
 
   Frame() = default;
   Frame(const Frame&) = default;
@@ -67,6 +67,13 @@ class Frame {
   std::vector<double> getClosestPoints(const std::vector<Vector3d>& query_pts, std::vector<size_t>& ret_index);
   // frame.cpp:244-255: PCA normals from the 10 nearest points (self included), n_z <= 0; overwrites `nor`
   void recomputeNormals();
+  // Exactly specified normals (no counterpart in the reference): mvicp_estimate_normals on this cloud as it is stored -- the direction of
+  // least variance of the max_nn nearest points (radius > 0: within it), turned towards `viewpoint` (this frame's local coordinates; the
+  // default is the sensor origin of a view in its own frame), so that the frames of one scan agree on the side their normals point to.
+  // Fills `nor` and bumps `version` as recomputeNormals() does (same place in the rule above: the session notices by itself) and returns
+  // the curvatures (surface variation, one per point).  Runs in the context Session::query_context finds for this frame
+  // (bin/multiview --normals_nn / --normals_radius).
+  std::vector<double> estimateNormals(int max_nn, double radius = 0.0, const Vector3d& viewpoint = Vector3d());
   // frame.cpp:208-231: the num_results nearest points of pts[queryIdx] in this cloud — the point itself first — in the order nanoflann's
   // knnSearch returns them (ascending distance, exact ties in the tree's visiting order).  The reference runs one tree query per call; here the
   // first call for a given num_results answers ALL points of the cloud in one device launch (the k-NN kernel behind recomputeNormals, 3 <= k <= 16)

@@ -41,7 +41,11 @@
 // One more line per frame, before the edge lines: `feature init: frame i keypoints k of n`.
 // --symmetric (default off): the solves minimise the symmetric point-to-plane objective (MVICP_METRIC_SYMMETRIC, include/mvicp.h) instead of
 // the one --pointToPlane selects, in the parameterisation the other flags select.  It needs normals on every frame (the clouds' own or
-// --recomputeNormals), oriented consistently between the frames.
+// --recomputeNormals), oriented consistently between the frames (--normals_nn below makes such normals).
+// --normals_nn K [--normals_radius R] (default K = 0 = off): with K > 0 the normals of every frame come from Frame::estimateNormals(K, R) in
+// place of the recomputeNormals step (after the outlier filter, before any coarse level): the exactly specified normals of
+// mvicp_estimate_normals over the K nearest points (3 <= K <= 64; R > 0: within R), turned towards the view's own origin -- the sensor of a
+// range image in its own frame -- so that all frames agree on the side their normals point to, which --symmetric and --init features need.
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
@@ -73,7 +77,8 @@ static void loadFrames(const Flags& F, std::vector<std::shared_ptr<Frame>>& fram
       f->pts.swap(kept->pts); f->nor.swap(kept->nor); ++f->version;   // (a context that holds the old cloud re-uploads)
       std::cout << "outlier filter: frame " << frames.size() << " kept " << f->pts.size() << " of " << before << std::endl;
     }
-    if (F.b("recomputeNormals", true)) f->recomputeNormals();  // main_multiview.cpp:49,68-70 (default on)
+    if (F.i("normals_nn", 0) > 0) f->estimateNormals(F.i("normals_nn", 0), F.f("normals_radius", 0.0));   // (viewpoint: the view's own origin)
+    else if (F.b("recomputeNormals", true)) f->recomputeNormals();  // main_multiview.cpp:49,68-70 (default on)
     if (groundtruth.size() == clouds.size()) {
       f->pose = loadMatrix4d(poses[i]);
       f->poseGroundTruth = loadMatrix4d(groundtruth[i]);

@@ -21,6 +21,7 @@ SYMBOLS = [
     "mvicp_overlap", "mvicp_graph_from_overlap", "mvicp_voxel_grid", "mvicp_voxel_fetch",
     "mvicp_outlier_filter", "mvicp_outlier_fetch", "mvicp_outlier_threshold", "mvicp_cache_allowance",
     "mvicp_knn_search", "mvicp_knn_fetch", "mvicp_fpfh", "mvicp_fpfh_fetch", "mvicp_iss_keypoints", "mvicp_iss_fetch",
+    "mvicp_estimate_normals", "mvicp_normals_fetch", "mvicp_normals_adopt",
     "mvicp_feature_match", "mvicp_feature_match_fetch", "mvicp_match_pairs", "mvicp_consensus", "mvicp_consensus_fetch",
     "mvicp_coarse_pairs", "mvicp_coarse_pairs_fetch", "mvicp_poses_from_pairs",
 ]
@@ -140,6 +141,10 @@ def load_library(path=None):
     lib.mvicp_iss_keypoints.argtypes = [vp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int]
     lib.mvicp_iss_keypoints.restype = C.c_longlong
     lib.mvicp_iss_fetch.argtypes = [vp, C.c_longlong, vp, vp, vp, C.c_longlong, vp, vp, vp]
+    lib.mvicp_estimate_normals.argtypes = [vp, C.c_int, C.c_int, C.c_double, dp]
+    lib.mvicp_estimate_normals.restype = C.c_longlong
+    lib.mvicp_normals_fetch.argtypes = [vp, C.c_longlong, vp, vp, vp]
+    lib.mvicp_normals_adopt.argtypes = [vp]
     lib.mvicp_feature_match.argtypes = [vp, vp, C.c_longlong, vp, C.c_longlong, C.c_int]
     lib.mvicp_feature_match.restype = C.c_longlong
     lib.mvicp_feature_match_fetch.argtypes = [vp, C.c_longlong, C.c_longlong, vp, vp, vp, vp]
@@ -781,6 +786,26 @@ class Engine:
         ready()
         _check(self.lib, self.lib.mvicp_iss_fetch(self.h, k, ptr(idx), ptr(xyz), None, n, ptr(sal), ptr(cs), ptr(cn)))
         return {"idx": idx, "xyz": xyz, "saliency": sal, "cnt_salient": cs, "cnt_nms": cn}
+
+    def estimate_normals(self, frame, max_nn=30, radius=0.0, viewpoint=None, device=False):
+        """mvicp_estimate_normals + mvicp_normals_fetch on the stored cloud of `frame`: per point the direction of least variance of its
+        max_nn nearest neighbours (radius > 0: within `radius`), turned towards `viewpoint` (3 numbers in the frame's local coordinates;
+        None = the origin), and the surface variation -> dict(nrm (n,3) float64, curvature (n,) float64, used (n,) int32 = neighbours
+        that entered; fewer than 3: a zero row).  device=True: torch tensors on the engine's GPU instead of numpy arrays.  The frame's
+        own normals are untouched until adopt_normals().  Afterwards the engine's last neighbour-search result is
+        knn_search(frame, None, max_nn, radius).  Needs no graph; history-neutral."""
+        vp = None if viewpoint is None else np.ascontiguousarray(viewpoint, dtype=np.float64).reshape(3)
+        n = int(_check(self.lib, self.lib.mvicp_estimate_normals(self.h, int(frame), int(max_nn), float(radius), _dp(vp) if vp is not None else None)))
+        mk, ptr, ready, f64, i32, i64, u8 = self._result_arrays(device)
+        nrm, curv, used = mk((n, 3), f64), mk((n,), f64), mk((n,), i32)
+        ready()
+        _check(self.lib, self.lib.mvicp_normals_fetch(self.h, n, ptr(nrm), ptr(curv), ptr(used)))
+        return {"nrm": nrm, "curvature": curv, "used": used}
+
+    def adopt_normals(self):
+        """mvicp_normals_adopt: the frame of the last estimate_normals takes that result as its normals, as recompute_normals would
+        leave them (lists that point into the frame are re-gathered, queued evaluations are voided)."""
+        _check(self.lib, self.lib.mvicp_normals_adopt(self.h))
 
     def _rows_operand(self, x, cols, what):
         """-> (the array kept alive, its pointer or None when empty, rows) for a (rows, cols) float64 numpy array or torch tensor on the engine's GPU"""
