@@ -777,6 +777,10 @@ int mvicp_closedform_point_to_plane(const double* src, const double* dst, const 
  * see DESIGN.md; "grid_curve" (default 2): device order of the clouds at the next mvicp_set_frame, 2 = balanced k-d order,
  * 1 / 0 = Hilbert / Morton index of the hash cell (nn_cell needs 0 or 1).  Tuning knobs: correspondences are
  * bit-identical for every setting.
+ * ONLY ON 3-LEVEL TARGETS: "mfma_entry", "tile_waves" 7 (nn_tile_kernel) / 4 / 6 (nn_mfma_kernel) and "mfma_lbt" (1: the per-lane box test of unseeded
+ * launches, >= 2: also in cache-aware matrix-pipe rounds) select builds that exist only for a launch whose targets all have three box levels (131 073 ..
+ * 8 388 608 points each); at any other depth they are accepted and the launch runs the 2-level or the generic build of the same search ("tile_waves" 8 has a
+ * generic build as well).  mvicp_last_nn_launch says which build ran.
  * Non-OK returns: a NULL or unknown name, a value outside the range its option states ("match_chunk" outside [1, 2^31), "grid_target"
  * outside [0.5, 64], "tile_mu" outside (0, 1], "mfma_kacc" outside [1, 1024], "tile_miss" outside [0, 64], "nn_search_factor" < 0) ->
  * MVICP_ERR_ARG; the option keeps its value. */
@@ -787,6 +791,12 @@ int mvicp_set_option(mvicp_ctx* ctx, const char* name, double value);
 int mvicp_nn_census(mvicp_ctx* ctx, double* out5);              /* the first five counters (the 0.1 contract) */
 /* All counters the build has, at most `cap` of them; returns how many were written (10 since version 0.4) or a negative status. */
 int mvicp_nn_census_ex(mvicp_ctx* ctx, double* out, int cap);
+/* Which NN kernel the last search of this context launched (mvicp_correspond, mvicp_nn_query; "" before the first, or for a NULL context):
+ * "brute", "grid", "tile<WPE,TOP,BND>" (nn_tile_kernel) or "mfma<WPE,TOP,BND,CEN,LBT,ENTRY>" (nn_mfma_kernel) with the template arguments of
+ * the instantiation as integers — WPE waves per SIMD, TOP + 1 box levels (-1: the generic build), then 0/1 flags: BND leaves temporal-cache
+ * bounds, CEN counts the census, LBT per-lane box test per tile, ENTRY enters at the seeds' blocks.  The string lives in the context and is
+ * overwritten by the next search.  Host state only: no device call, never fails. */
+const char* mvicp_last_nn_launch(mvicp_ctx* ctx);
 
 /* ---- profiling (HIP events on the library's own stream) ------------------------------------------ */
 /* on = 0: off; 1: every scope below; 2: only the NN kernels, "linearize", "linearize_pair" and "comm" (fewer event packets between the kernels of

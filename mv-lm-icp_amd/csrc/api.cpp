@@ -2370,6 +2370,7 @@ int mvicp_nn_census_ex(mvicp_ctx* c, double* out, int cap) try {
   for (int i = 0; i < n; ++i) out[i] = v[i];
   return n;
 } MVICP_GUARD_ABI
+const char* mvicp_last_nn_launch(mvicp_ctx* c) { return c ? c->last_nn_launch : ""; }   // (host state only: binds no device, cannot throw)
 int mvicp_nn_census(mvicp_ctx* c, double* out5) try {   // the original 5-counter contract (a caller's 5-element buffer is never overrun)
   const int n = mvicp_nn_census_ex(c, out5, 5);
   return n < 0 ? n : MVICP_OK;

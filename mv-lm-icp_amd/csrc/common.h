@@ -453,6 +453,7 @@ struct mvicp_ctx {
   double grid_target = 5.0;        // points per occupied cell the cell-edge heuristic aims at (4-6 measure the same within 2 %)
   double nn_candidates = 0, nn_nodes = 0, nn_far = 0, nn_queries = 0, nn_hits = 0, nn_fetched = 0;
   double nn_dbg[4] = {0, 0, 0, 0};   // nn_mfma_kernel census: second-screen passes, confirmation rounds, blocks scanned (all per wave), fp64 confirmations (per lane)
+  char last_nn_launch[48] = "";      // which NN kernel instantiation the last search launched (mvicp_last_nn_launch): written by the launchers, "" before the first
 
   // profiling
   bool profile = false; int profile_level = 0;   // 1: every scope, 2: only "nn" and "linearize"

@@ -173,6 +173,7 @@ int run_jobs(mvicp_ctx* c, std::vector<BruteJob>& jobs, double* pairs_out, const
   }
   {
     ProfScope ps(c, "nn_brute", pairs * 24.0);
+    std::snprintf(c->last_nn_launch, sizeof(c->last_nn_launch), "brute");
     hipLaunchKernelGGL(nn_brute_kernel, dim3(qblocks, splits, (unsigned)jobs.size()), dim3(NT), 0, c->stream, d_jobs, splits,
                        c->d_split_idx, c->d_split_d2, d_off);
     if (splits > 1)

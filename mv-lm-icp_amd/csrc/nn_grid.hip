@@ -999,6 +999,7 @@ int run(mvicp_ctx* c, std::vector<GridJob>& jobs, double bound, const FrameDev* 
     // switches, grids too large for a dense brick map) the per-lane hash kernel
     use_cell = c->nn_cell && !c->nn_tree_only && !c->nn_skip_far && edge_path;
     for (const GridJob& j : jobs) if (j.dst.bricks == nullptr || j.xf == nullptr) use_cell = false;
+    std::snprintf(c->last_nn_launch, sizeof(c->last_nn_launch), "grid");
     if (c->nn_tree_only)
       hipLaunchKernelGGL((nn_grid_kernel<true>), grid, dim3(NT), 0, c->stream, d_jobs, bound, search, d_stats, 0, (int2*)c->d_far_list, far_cnt, 0.0);
     else if (use_cell)

@@ -590,7 +590,11 @@ int warm_nn_mfma(mvicp_ctx* c) {
 
 int launch_nn_mfma_edges(mvicp_ctx* c, double d2_bound, bool with_bounds, bool with_cache, bool with_list) {
   return launch_tile_search(c, d2_bound, with_bounds, with_cache, with_list, MT, "nn_mfma", [&](const std::vector<TileJob>& jobs, const TileJob* d_jobs, dim3 grid, int top, unsigned long long* d_stats) {
-#define MVICP_MFMA_L(W, T, B, C, Lb) hipLaunchKernelGGL((nn_mfma_kernel<W, T, B, C, Lb>), grid, dim3(MT), 0, c->stream, d_jobs, d2_bound, search_bound(c, d2_bound), d_stats)
+    // every arm names the instantiation it launches ("mfma<WPE,TOP,BND,CEN,LBT,ENTRY>": mvicp_last_nn_launch; tests/depthcases.py parses the arms below)
+#define MVICP_MFMA_X(W, T, B, C, Lb, En) do { std::snprintf(c->last_nn_launch, sizeof(c->last_nn_launch), "mfma<%d,%d,%d,%d,%d,%d>", W, T, (int)B, (int)C, (int)Lb, (int)En); \
+    hipLaunchKernelGGL((nn_mfma_kernel<W, T, B, C, Lb, En>), grid, dim3(MT), 0, c->stream, d_jobs, d2_bound, search_bound(c, d2_bound), d_stats); } while (0)
+#define MVICP_MFMA_L(W, T, B, C, Lb) MVICP_MFMA_X(W, T, B, C, Lb, false)
+#define MVICP_MFMA_E(W, T, B, C) MVICP_MFMA_X(W, T, B, C, false, true)
 #define MVICP_MFMA_K(W, T, B) do { if (d_stats) MVICP_MFMA_L(W, T, B, true, false); else MVICP_MFMA_L(W, T, B, false, false); } while (0)
     const int waves = c->tile_waves;
     bool unseeded = c->mfma_lbt != 0;
@@ -598,18 +602,21 @@ int launch_nn_mfma_edges(mvicp_ctx* c, double d2_bound, bool with_bounds, bool w
     if (unseeded && !with_bounds && top == 2 && !d_stats) MVICP_MFMA_L(5, 2, false, false, true);   // no seed anywhere: per-lane box test per tile (scan_block)
     else if (unseeded && !with_bounds && top == 2) MVICP_MFMA_L(5, 2, false, true, true);
     else if (with_bounds && with_cache && top == 2 && c->mfma_lbt >= 2 && !d_stats) MVICP_MFMA_L(5, 2, true, false, true);   // cache-aware round (tile_mfma = 2): most lanes sit out, so the per-lane box test prunes nearly every tile
-    else if (with_bounds && c->mfma_entry && !unseeded && !d_stats && top == 2) hipLaunchKernelGGL((nn_mfma_kernel<5, 2, true, false, false, true>), grid, dim3(MT), 0, c->stream, d_jobs, d2_bound, search_bound(c, d2_bound), d_stats);
+    else if (with_bounds && c->mfma_entry && !unseeded && !d_stats && top == 2) MVICP_MFMA_E(5, 2, true, false);
     else if (with_bounds) {
-      if (top == 2) MVICP_MFMA_K(5, 2, true); else MVICP_MFMA_K(5, -1, true);
+      if (top == 2) MVICP_MFMA_K(5, 2, true);
+      else MVICP_MFMA_K(5, -1, true);
     }
-    else if (c->mfma_entry && !unseeded && !d_stats && top == 2 && !with_bounds) hipLaunchKernelGGL((nn_mfma_kernel<5, 2, false, false, false, true>), grid, dim3(MT), 0, c->stream, d_jobs, d2_bound, search_bound(c, d2_bound), d_stats);
-    else if (c->mfma_entry && !unseeded && d_stats && top == 2 && !with_bounds) hipLaunchKernelGGL((nn_mfma_kernel<5, 2, false, true, false, true>), grid, dim3(MT), 0, c->stream, d_jobs, d2_bound, search_bound(c, d2_bound), d_stats);
+    else if (c->mfma_entry && !unseeded && !d_stats && top == 2 && !with_bounds) MVICP_MFMA_E(5, 2, false, false);
+    else if (c->mfma_entry && !unseeded && d_stats && top == 2 && !with_bounds) MVICP_MFMA_E(5, 2, false, true);
     else if (top == 2 && waves == 6) MVICP_MFMA_K(6, 2, false);
     else if (top == 2 && waves == 4) MVICP_MFMA_K(4, 2, false);
     else if (top == 2) MVICP_MFMA_K(5, 2, false);
     else if (top == 1) MVICP_MFMA_K(5, 1, false);
     else MVICP_MFMA_K(5, -1, false);
+#undef MVICP_MFMA_X
 #undef MVICP_MFMA_L
+#undef MVICP_MFMA_E
 #undef MVICP_MFMA_K
   });
 }

@@ -428,11 +428,14 @@ int launch_nn_tile_edges(mvicp_ctx* c, double d2_bound, bool with_bounds, bool w
   // latency of the few that remain (cfg4 rounds 6 / 7: 0.57 / 0.38 ms here against 0.65 / 0.57 ms there)
   if (c->tile_mfma >= 2 || (c->tile_mfma == 1 && (!with_cache || c->cached_on_mfma))) return launch_nn_mfma_edges(c, d2_bound, with_bounds, with_cache, with_list);
   return launch_tile_search(c, d2_bound, with_bounds, with_cache, with_list, TT, "nn_tile", [&](const std::vector<TileJob>&, const TileJob* d_jobs, dim3 grid, int top, unsigned long long* d_stats) {
-#define MVICP_TILE_K(W, T, B) hipLaunchKernelGGL((nn_tile_kernel<W, T, B>), grid, dim3(TT), 0, c->stream, d_jobs, d2_bound, search_bound(c, d2_bound), d_stats)
+    // every arm names the instantiation it launches ("tile<WPE,TOP,BND>": mvicp_last_nn_launch; tests/depthcases.py parses the arms below)
+#define MVICP_TILE_K(W, T, B) do { std::snprintf(c->last_nn_launch, sizeof(c->last_nn_launch), "tile<%d,%d,%d>", W, T, (int)B); \
+    hipLaunchKernelGGL((nn_tile_kernel<W, T, B>), grid, dim3(TT), 0, c->stream, d_jobs, d2_bound, search_bound(c, d2_bound), d_stats); } while (0)
     const int waves = c->tile_waves;   // 0 = pick: 7 waves per SIMD for the depth-3 build, 6 otherwise
     // depth-3 build: 7 waves per SIMD (no spills at 66 VGPRs); 6 and 8 measure 4-10 % slower (profiles/r03_tile_ab.txt)
     if (with_bounds) {   // hand-over round: one more fp64 register pair per lane, so one wave per SIMD fewer
-      if (top == 2) MVICP_TILE_K(6, 2, true); else MVICP_TILE_K(6, -1, true);
+      if (top == 2) MVICP_TILE_K(6, 2, true);
+      else MVICP_TILE_K(6, -1, true);
     }
     else if (top == 2 && (waves == 0 || waves == 7)) MVICP_TILE_K(7, 2, false);
     else if (top == 2 && waves == 8) MVICP_TILE_K(8, 2, false);

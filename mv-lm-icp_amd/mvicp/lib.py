@@ -16,7 +16,7 @@ SYMBOLS = [
     "mvicp_last_error", "mvicp_version", "mvicp_create", "mvicp_destroy", "mvicp_set_num_frames", "mvicp_set_frame",
     "mvicp_recompute_normals", "mvicp_set_graph", "mvicp_set_shard", "mvicp_edge_owner", "mvicp_comm_unique_id", "mvicp_comm_init", "mvicp_comm_nranks", "mvicp_comm_set_callback", "mvicp_correspond",
     "mvicp_get_correspondences", "mvicp_map_correspondences", "mvicp_map_correspondences_async", "mvicp_wait_correspondences", "mvicp_correspondence_epochs", "mvicp_set_correspondences", "mvicp_nn_query", "mvicp_linearize", "mvicp_linearize_pair", "mvicp_linearize_metric", "mvicp_optimize", "mvicp_optimize_metric",
-    "mvicp_lm_solve", "mvicp_set_option", "mvicp_nn_census", "mvicp_nn_census_ex", "mvicp_reset_history", "mvicp_profile_enable", "mvicp_profile_reset", "mvicp_profile_get", "mvicp_profile_get_ex", "mvicp_stream", "mvicp_sync",
+    "mvicp_lm_solve", "mvicp_set_option", "mvicp_nn_census", "mvicp_nn_census_ex", "mvicp_last_nn_launch", "mvicp_reset_history", "mvicp_profile_enable", "mvicp_profile_reset", "mvicp_profile_get", "mvicp_profile_get_ex", "mvicp_stream", "mvicp_sync",
     "mvicp_closedform_point_to_point", "mvicp_closedform_point_to_plane", "mvicp_set_frame_device", "mvicp_get_structure",
     "mvicp_overlap", "mvicp_graph_from_overlap", "mvicp_voxel_grid", "mvicp_voxel_fetch",
     "mvicp_outlier_filter", "mvicp_outlier_fetch", "mvicp_outlier_threshold", "mvicp_cache_allowance",
@@ -108,6 +108,8 @@ def load_library(path=None):
     lib.mvicp_set_option.argtypes = [vp, C.c_char_p, C.c_double]
     lib.mvicp_nn_census.argtypes = [vp, dp]
     lib.mvicp_nn_census_ex.argtypes = [vp, dp, C.c_int]
+    lib.mvicp_last_nn_launch.argtypes = [vp]
+    lib.mvicp_last_nn_launch.restype = C.c_char_p
     lib.mvicp_reset_history.argtypes = [vp]
     lib.mvicp_profile_enable.argtypes = [vp, C.c_int]
     lib.mvicp_profile_reset.argtypes = [vp]
@@ -959,6 +961,10 @@ class Engine:
         _check(self.lib, self.lib.mvicp_nn_census_ex(self.h, _dp(out), 10))
         return {"queries": out[0], "candidates": out[1], "nodes": out[2], "far": out[3], "hits": out[4], "fetched": out[5],
                 "rescreens": out[6], "confirm_rounds": out[7], "blocks": out[8], "confirmations": out[9]}
+
+    def last_nn_launch(self):
+        """Which NN kernel instantiation the last search launched: "brute", "grid", "tile<WPE,TOP,BND>", "mfma<WPE,TOP,BND,CEN,LBT,ENTRY>"."""
+        return self.lib.mvicp_last_nn_launch(self.h).decode()
 
     # ---- profiling
     def profile(self, on=True):

@@ -64,6 +64,9 @@ def small_clouds():
     cl = {}
     for n in (1, 64, 65, 95, 96, 97, 2047, 2048, 2049, 65537):
         cl[f"n{n}"] = r.normal(size=(n, 3))
+    r3 = _rng(8)   # both sides of the boundary between 2 and 3 box levels, and a last node with two boxes (a stream of their own: the clouds below stay what they were)
+    for n in (131072, 131073, 133121):
+        cl[f"n{n}"] = r3.normal(size=(n, 3))
     base = r.uniform(-1, 1, size=(300, 3))
     cl["duplicates"] = np.vstack([base, base, base[:100]])
     g = np.arange(12, dtype=np.float64)

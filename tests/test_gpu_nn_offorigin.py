@@ -6,6 +6,7 @@ operands and -T pieces, the hash cell assignment and its clamp, and the rounding
 import numpy as np
 import pytest
 
+import depthcases as dc
 import mvicp
 import offorigin as oo
 from mvicp import lib as L
@@ -24,7 +25,38 @@ def eng():
     e.close()
 
 
-def _query_all(eng, orc, refnn, dst, q, tag, methods=QUERY_METHODS):
+@pytest.fixture(scope="module")
+def edge_eng():
+    e = mvicp.Engine(0)
+    yield e
+    e.close()
+
+
+# the one-edge route at depths 1 and 2: (launch string of a 2-level target, of a 1-level target), from the table of tests/depthcases.py
+EDGE_BUILDS = [(k, "%s<%d,-1,%s" % (dc.parse_launch(k)["kernel"], dc.parse_launch(k)["WPE"], k.split(",", 2)[2])) for k, _ in dc.variants(2)]
+
+
+def _edge_all(e, orc, dst, q, ri, od, tag):
+    """The same query set as the source cloud of one edge (identity poses, a cutoff above every distance): nn_tile_kernel and
+    nn_mfma_kernel themselves, in the build of the target's depth (asserted through Engine.last_nn_launch)."""
+    thresh = dc.cutoff_above(od)
+    expected = dc.expected_list(orc, ri, od, thresh)
+    frames, src, dsts, poses, fixed = dc.edge_frames([dst], q)
+    e.set_frames(frames, None); e.set_graph(src, dsts)
+    depth = int(e.get_structure(0, "scalars")[13])
+    assert depth == dc.levels(len(dst)) and depth in (1, 2), (tag, depth)
+    for two, one in EDGE_BUILDS:
+        want = two if depth == 2 else one
+        launch = None
+        for r, c, w, launch in dc.search_variant(e, dc.VARIANTS[two], poses, fixed, thresh):
+            gf, gs, gd = e.get_correspondences(0)
+            bad = np.nonzero((gs != expected[1]) | (gd != expected[2]))[0] if len(gs) == len(expected[1]) else np.array([-1])
+            assert c[0] == len(q) and np.array_equal(gf, expected[0]) and len(bad) == 0, (tag, want, r, launch, len(bad), bad[:5].tolist())
+            assert w[0] == expected[3], (tag, want, r)
+        assert launch == want, (tag, want, launch)
+
+
+def _query_all(eng, orc, refnn, dst, q, tag, methods=QUERY_METHODS, edge_eng=None):
     """Distances: the oracle's brute force.  Indices: the real nanoflann's, which is the oracle's lowest index except where the best
     distance is met by several targets (a query 1e6 m from a millimetre cloud ties with half of it): there the reference keeps the
     target its tree visits first, and so must every kernel (test_duplicate_targets_follow_nanoflanns_visit_order)."""
@@ -38,14 +70,19 @@ def _query_all(eng, orc, refnn, dst, q, tag, methods=QUERY_METHODS):
         idx, d2 = eng.nn_query(0, q, m)
         bad = np.nonzero((idx != ri) | (d2 != od))[0]
         assert len(bad) == 0, (tag, name, len(bad), bad[:5].tolist(), idx[bad[:5]].tolist(), ri[bad[:5]].tolist(), oi[bad[:5]].tolist())
+    if edge_eng is not None:
+        _edge_all(edge_eng, orc, dst, q, ri, od, tag)
 
 
 # ---------------------------------------------------------------- a. single queries
 @pytest.mark.parametrize("kind", ["blob", "plane", "lattice", "clusters"])
 @pytest.mark.parametrize("place", ["unit", "local", "mm_local", "local1e6"])
-def test_single_queries_every_kernel(eng, orc, refnn, place, kind):
-    """nn_query through brute force, hash grid, tree only and both tile kernels, clouds of 1 .. 3000 points: queries = another cloud's
-    points, the target's own points +- 1e-9 of the data scale, a blob, and two far ones (1e3 extents and 1e6 m away)."""
+def test_single_queries_every_kernel(eng, edge_eng, orc, refnn, place, kind):
+    """nn_query through brute force, hash grid and tree only, clouds of 1 .. 3000 points: queries = another cloud's points, the target's
+    own points +- 1e-9 of the data scale, a blob, and two far ones (1e3 extents and 1e6 m away).  The rows `tile0` and `tile2` of nn_query
+    are the GRID kernel three times over (mvicp_nn_query maps NN_TILE and NN_AUTO to it: raw queries are not patch-ordered); they stay as
+    rows of that entry point.  The two tile kernels see the same query sets as the source cloud of one edge (_edge_all): 1 .. 777 points
+    are 1-level targets (the generic builds), 3000 points a 2-level one (the <.., 1, ..> builds), unseeded, seeded and counting."""
     assert refnn is not None, "oracle/_ref (real nanoflann) was not built"
     rng = np.random.default_rng(sum(map(ord, place + kind)))
     s = oo.place_scale(place)
@@ -59,7 +96,7 @@ def test_single_queries_every_kernel(eng, orc, refnn, place, kind):
             centre = dst.mean(0)
             extent = max(float(np.ptp(dst, axis=0).max()), s)
             far = np.array([centre + 1e3 * extent * np.array([0.6, -0.64, 0.48]), centre + np.array([0.0, 0.0, 1e6])])
-            _query_all(eng, orc, refnn, dst, np.ascontiguousarray(np.vstack([other, near, blob, far])), (place, kind, n))
+            _query_all(eng, orc, refnn, dst, np.ascontiguousarray(np.vstack([other, near, blob, far])), (place, kind, n), edge_eng=edge_eng)
     finally:
         eng.set_option("tile_mfma", 1)   # the default
 
