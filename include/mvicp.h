@@ -414,6 +414,71 @@ int mvicp_normals_fetch(mvicp_ctx* ctx, long long cap_rows, double* nrm, double*
  * MVICP_ERR_STATE, with nothing changed. */
 int mvicp_normals_adopt(mvicp_ctx* ctx);
 
+/* ---- Consistent normal orientation without a viewpoint: propagation over a neighbour graph ----------------------------------------
+ * mvicp_estimate_normals turns a normal towards a viewpoint, which is right for a range image and for nothing else.  mvicp_orient_normals
+ * makes the normals of ONE cloud agree with each other without one (Hoppe et al. 1992): the sign is carried along the maximum spanning
+ * forest of the neighbour graph weighted by |N_i . N_j|.  The result is a pure function of the stored bytes, bit for bit
+ * (tests/orientref.py is the same definition in numpy and as a scalar Kruskal loop).  All floating-point work is
+ * fp64, every operation rounded on its own, no fma; comparisons are IEEE as written.
+ *   Normals N   source 0: the frame's stored normals (none: MVICP_ERR_STATE); source 1: the nrm of the last mvicp_estimate_normals, which
+ *              must be for this frame and not dropped by an upload (otherwise MVICP_ERR_STATE).
+ *   Graph      the rows of mvicp_knn_search(frame, NULL, k, radius) in self mode, 2 <= k <= 64, radius <= 0: off.  The undirected edge
+ *              {i, j}, i != j, exists iff j is in row i or i is in row j.  Exact duplicates are ordinary points.
+ *   Weight     d_ij = (N_i0 N_j0 + N_i1 N_j1) + N_i2 N_j2 (bitwise symmetric in i and j), w = |d|, f_ij = [d < 0].  A non-finite d ->
+ *              MVICP_ERR_ARG, reported by this call, and no result is left behind.  Zero normals (rows of fewer than 3 points) give
+ *              w = 0, f = 0 and take part like any other.
+ *   Forest     edge e precedes e' iff w_e > w_e', for equal w iff its (min index, max index) is lexicographically smaller: a strict total
+ *              order, so the maximum spanning forest F -- the one Kruskal builds in that order -- is unique, whatever algorithm builds it.
+ *   Labels     comp[i] = the lowest original index in i's tree (its anchor); x_i = the XOR of f along the tree path from i to its anchor.
+ *   Sign g     per component, from exact integer counts.  s_i is the dot below on the STORED N_i, negated iff x_i = 1.
+ *              MVICP_ORIENT_ANCHOR: g = 0.  MVICP_ORIENT_VIEWPOINT: v = ref - p_i (per component), s_i = (N_i0 v0 + N_i1 v1) + N_i2 v2;
+ *              g = 1 iff #(s_i < 0) > #(s_i > 0) over the component (a tie keeps the sign).  MVICP_ORIENT_DIRECTION: the same with v = ref.
+ *              ref3 NULL = (0, 0, 0), legal for ANCHOR and VIEWPOINT only.
+ *   Result     flip[i] = x_i XOR g_comp[i]; nrm[i] = N_i with every component negated iff flip[i] (a +0.0 becomes -0.0).
+ * nrm is n x 3 doubles, flip n bytes, comp n ints, row i the ORIGINAL index i; n = 0 gives zero rows and 0 components.
+ * The call performs mvicp_knn_search(frame, NULL, k, radius) internally and AFTERWARDS THAT SEARCH IS THE CONTEXT'S LAST NEIGHBOUR-SEARCH
+ * RESULT, as with mvicp_fpfh.  Otherwise it is HISTORY-NEUTRAL, touches neither the frame's normals nor the estimate it read, needs the
+ * frame's hash structure and NO graph; with several ranks every rank computes it locally.  The forest is built in Boruvka rounds on the
+ * device; the host waits once per round (a round at least halves the number of trees that can still grow).  The result lives in
+ * library-owned device memory of its own until the next mvicp_orient_normals, an upload to the same frame, mvicp_set_num_frames or
+ * mvicp_destroy.  Profile scopes: those of the search, "orient_round", "orient_finish".
+ * RETURNS THE NUMBER OF COMPONENTS (>= 0) or a negative mvicp_status.
+ * Errors: NULL context, a frame index out of range, a source outside {0, 1}, k outside [2, 64], a mode outside mvicp_orient_mode, a
+ * non-finite radius or ref entry, ref3 NULL with MVICP_ORIENT_DIRECTION -> MVICP_ERR_ARG, decided before the context is touched (earlier
+ * results stay); a frame never uploaded, no normals of the asked source -> MVICP_ERR_STATE (earlier results stay). */
+typedef enum { MVICP_ORIENT_ANCHOR = 0, MVICP_ORIENT_VIEWPOINT = 1, MVICP_ORIENT_DIRECTION = 2 } mvicp_orient_mode;
+long long mvicp_orient_normals(mvicp_ctx* ctx, int frame, int source, int k, double radius, int mode, const double* ref3);
+/* Copies the last result: nrm (n x 3 doubles), flip (n bytes), comp (n ints); each may be NULL; each may be a HOST pointer or a DEVICE
+ * pointer of the context's device, decided per pointer as mvicp_voxel_fetch decides.  cap_rows = rows the destinations hold.
+ * Errors: NULL context, cap_rows < n -> MVICP_ERR_ARG; no mvicp_orient_normals before -> MVICP_ERR_STATE. */
+int mvicp_orient_fetch(mvicp_ctx* ctx, long long cap_rows, double* nrm, unsigned char* flip, int* comp);
+/* The frame of the last mvicp_orient_normals takes that result's nrm as its normals: mvicp_normals_adopt with these values, same side
+ * effects, same refusals (no result, or the frame was uploaded again since -> MVICP_ERR_STATE, with nothing changed). */
+int mvicp_orient_adopt(mvicp_ctx* ctx);
+
+/* Agreement between the normals of DIFFERENT clouds, over the correspondence lists the context holds (searched or explicit) at `poses`
+ * (n_frames x 16).  Per owned edge e = (src, dst) and per pair (first, second) of its list: a = R_src N_first, b = R_dst N_second, each
+ * component (r0 x + r1 y) + r2 z with the rows of the pose's rotation, t = (a0 b0 + a1 b1) + a2 b2, no fma; pos[e] counts t > 0, neg[e]
+ * counts t < 0 (n_edges ints each; either may be NULL).  Edges of other ranks and edges whose source frame was fixed in the last
+ * mvicp_correspond give 0 / 0.  HISTORY-NEUTRAL, one launch and one wait, integer sums (the counts are exact).  Profile scope
+ * "normal_agreement".
+ * Errors: NULL context or poses -> MVICP_ERR_ARG; what mvicp_linearize_metric(MVICP_METRIC_SYMMETRIC) refuses -- no graph, no list yet,
+ * no normals on either frame of a non-empty list -> MVICP_ERR_STATE. */
+int mvicp_normal_agreement(mvicp_ctx* ctx, const double* poses, int* pos, int* neg);
+/* The sign rule on top of the counts (pure host function, no context; host pointers), in the style of mvicp_poses_from_pairs.  Edge e is
+ * usable iff pos[e] + neg[e] >= min_count and pos[e] != neg[e].  The maximum spanning forest over the frames is the one Kruskal builds
+ * from the usable edges in the order (|pos - neg| descending, e ascending).  component[f] = the lowest frame index of f's tree, which keeps
+ * its sign; flip[f] = the XOR of [pos < neg] along the tree path from f to it.  component may be NULL.
+ * RETURNS THE NUMBER OF COMPONENTS (>= 1).
+ * Errors (MVICP_ERR_ARG): flip NULL, src / dst / pos / neg NULL with n_edges > 0, n_frames < 1, n_edges < 0, an edge index out of range or
+ * src[e] == dst[e], a negative count, min_count < 0. */
+int mvicp_signs_from_agreement(int n_frames, int n_edges, const int* src, const int* dst, const int* pos, const int* neg, int min_count,
+                               unsigned char* flip, int* component);
+/* Every stored normal of `frame` is negated, in original and in sorted order (a +0.0 becomes -0.0).  The side effects are exactly those of
+ * mvicp_normals_adopt: owned lists that point into the frame are re-gathered, queued evaluations are voided.
+ * Errors: NULL context, a frame index out of range -> MVICP_ERR_ARG; a frame never uploaded or without normals -> MVICP_ERR_STATE. */
+int mvicp_negate_normals(mvicp_ctx* ctx, int frame);
+
 /* ---- Descriptor matching and a consensus coarse pose, exactly specified -------------------------------------------------------
  * The stage that turns two sets of descriptors into a coarse pose: two device stages, one host rule between them.  Each result is a
  * pure function of the input bytes, bit for bit (tests/matchref.py is the same definition in numpy and as a scalar loop).  All
@@ -667,7 +732,8 @@ int mvicp_linearize_pair(mvicp_ctx* ctx, const double* poses_a, const double* po
  * u = [m ; (p~ x n_q + q x nu) / 2], J = [Ad^T u ; -u] in the coordinates above (csrc/linearize_sym.hip).
  * THE NORMALS ARE USED AS STORED: no sign flip, no normalisation.  Orienting the normals of the clouds consistently with each other
  * (the same side of the surface in every frame) is the caller's job -- mvicp_estimate_normals with each view's sensor position as
- * viewpoint is the tool for it; with opposite orientations m is half the DIFFERENCE of the normals.
+ * viewpoint is the tool for it, mvicp_orient_normals + mvicp_normal_agreement + mvicp_signs_from_agreement + mvicp_negate_normals where
+ * there is no sensor position; with opposite orientations m is half the DIFFERENCE of the normals.
  * The source normal is the source frame's current one: after mvicp_recompute_normals the next evaluation sees the new normals.
  * For this objective the relative transform of an edge is formed with the true inverse of the destination's rotation, in extended
  * precision (for a rotation that is its transpose): the result does not depend on how far the given poses are from orthonormal to the

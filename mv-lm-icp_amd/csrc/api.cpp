@@ -3,6 +3,7 @@
 // The LM solve (S2) lives in host/lm.cpp; the RCCL glue in comm.cpp.
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <ctime>
 #include <chrono>
@@ -620,6 +621,7 @@ int mvicp_create(int device, mvicp_ctx** out) try {
 static void release_stages(mvicp_ctx* c) {
   c->vox.release(); c->out.release(); c->knn.release(); c->fpfh.release();
   c->match.release(); c->cons.release(); c->coarse.release(); c->iss.release(); c->nrm.release();
+  c->ori.release(); c->agree.release();
 }
 
 int mvicp_destroy(mvicp_ctx* c) try {
@@ -678,6 +680,7 @@ int mvicp_set_frame(mvicp_ctx* c, int frame, const double* xyz, const double* nr
   }
   FrameDev& f = c->frames[frame];
   if (c->nrm.frame == frame) c->nrm.drop_result();   // (estimated normals of the cloud this call replaces: nothing to adopt them into)
+  if (c->ori.frame == frame) c->ori.drop_result();   // (and its oriented normals)
   if (f.job) { try { (void)f.job->fut.get(); } catch (...) {} f.job.reset(); }   // a build of the cloud this call replaces
   dev_free(f.pts); dev_free(f.nor); free_grid(f.grid); free_tie(f);
   f.has_grid = false; f.build_error.clear();
@@ -757,6 +760,7 @@ int mvicp_set_frame_device(mvicp_ctx* c, int frame, const double* d_xyz, const d
   }
   FrameDev& f = c->frames[frame];
   if (c->nrm.frame == frame) c->nrm.drop_result();   // (estimated normals of the cloud this call replaces: nothing to adopt them into)
+  if (c->ori.frame == frame) c->ori.drop_result();   // (and its oriented normals)
   if (f.job) { try { (void)f.job->fut.get(); } catch (...) {} f.job.reset(); }   // a build of the cloud this call replaces
   dev_free(f.pts); dev_free(f.nor); free_grid(f.grid); free_tie(f);
   f.has_grid = false; f.build_error.clear();
@@ -1141,15 +1145,11 @@ int mvicp_normals_fetch(mvicp_ctx* c, long long cap_rows, double* nrm, double* c
   return fetch_parts(c, parts);
 } MVICP_GUARD_ABI
 
-int mvicp_normals_adopt(mvicp_ctx* c) try {
-  if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
-  if (c->nrm.rows < 0 || c->nrm.frame < 0 || c->nrm.frame >= c->n_frames) {
-    set_error("no estimated normals to adopt: call mvicp_estimate_normals first (an upload to its frame drops the result)");
-    return MVICP_ERR_STATE;
-  }
-  const int frame = c->nrm.frame;
+// The shared part of mvicp_normals_adopt and mvicp_orient_adopt: `nrm` (rows x 3 doubles in library-owned device memory, computed for
+// `frame`) becomes the frame's normals, as a successful mvicp_recompute_normals would leave them.
+static int adopt_normals_into(mvicp_ctx* c, int frame, long long rows, const double* nrm, const char* what) {
   FrameDev& f = c->frames[frame];
-  if (c->nrm.rows != f.n) { set_error("the estimated normals have %lld rows, frame %d has %d points", c->nrm.rows, frame, f.n); return MVICP_ERR_STATE; }
+  if (rows != f.n) { set_error("the %s normals have %lld rows, frame %d has %d points", what, rows, frame, f.n); return MVICP_ERR_STATE; }
   MV_CHECK(bind(c));
   MV_CHECK(finish_builds(c));
   if (f.n == 0) return MVICP_OK;   // (nothing to write)
@@ -1158,13 +1158,136 @@ int mvicp_normals_adopt(mvicp_ctx* c) try {
   int st = MVICP_OK;
   if (fresh_nor) st = dev_alloc(&f.nor, 3 * (size_t)f.n);
   if (st == MVICP_OK && fresh_snor) st = dev_alloc(&f.grid.snor, 3 * (size_t)f.n);
-  if (st == MVICP_OK) st = normals_adopt(c, f);
+  if (st == MVICP_OK) st = normals_adopt(c, f, nrm);
   if (st != MVICP_OK) {   // what this call allocated goes with it: the frame has normals only if a call wrote them
     (void)hipStreamSynchronize(c->stream);
     if (fresh_nor) dev_free(f.nor);
     if (fresh_snor) dev_free(f.grid.snor);
   }
   return normals_changed(c, frame, st);
+}
+
+int mvicp_normals_adopt(mvicp_ctx* c) try {
+  if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
+  if (c->nrm.rows < 0 || c->nrm.frame < 0 || c->nrm.frame >= c->n_frames) {
+    set_error("no estimated normals to adopt: call mvicp_estimate_normals first (an upload to its frame drops the result)");
+    return MVICP_ERR_STATE;
+  }
+  return adopt_normals_into(c, c->nrm.frame, c->nrm.rows, c->nrm.nrm, "estimated");
+} MVICP_GUARD_ABI
+
+long long mvicp_orient_normals(mvicp_ctx* c, int frame, int source, int k, double radius, int mode, const double* ref3) try {
+  // every argument error that needs no GPU first: nothing of the context has been touched when one of them is reported
+  if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
+  if (source != 0 && source != 1) { set_error("source = %d: 0 (the frame's stored normals) or 1 (the last mvicp_estimate_normals)", source); return MVICP_ERR_ARG; }
+  if (k < 2 || k > 64) { set_error("k = %d outside [2, 64]", k); return MVICP_ERR_ARG; }
+  if (mode < MVICP_ORIENT_ANCHOR || mode > MVICP_ORIENT_DIRECTION) { set_error("mode = %d outside mvicp_orient_mode", mode); return MVICP_ERR_ARG; }
+  if (!std::isfinite(radius)) { set_error("radius must be finite (<= 0: no radius)"); return MVICP_ERR_ARG; }
+  if (!ref3 && mode == MVICP_ORIENT_DIRECTION) { set_error("MVICP_ORIENT_DIRECTION needs a direction"); return MVICP_ERR_ARG; }
+  double ref[3] = {0.0, 0.0, 0.0};
+  for (int a = 0; ref3 && a < 3; ++a) {
+    if (!std::isfinite(ref3[a])) { set_error("ref[%d] is not finite", a); return MVICP_ERR_ARG; }
+    ref[a] = ref3[a];
+  }
+  if (frame < 0 || frame >= c->n_frames) { set_error("frame %d out of range [0,%d)", frame, c->n_frames); return MVICP_ERR_ARG; }
+  const FrameDev& f = c->frames[frame];
+  if (!f.pts) { set_error("frame %d was never uploaded", frame); return MVICP_ERR_STATE; }
+  const double* N = nullptr;
+  if (source == 0) {
+    if (f.n > 0 && !f.nor) { set_error("frame %d has no normals to orient", frame); return MVICP_ERR_STATE; }
+    N = f.nor;
+  } else {
+    if (c->nrm.rows < 0 || c->nrm.frame != frame || c->nrm.rows != f.n) {
+      set_error("no estimated normals of frame %d: call mvicp_estimate_normals on it first (an upload to the frame drops the result)", frame);
+      return MVICP_ERR_STATE;
+    }
+    N = c->nrm.nrm;
+  }
+  MV_CHECK(bind(c));
+  MV_CHECK(finish_builds(c));
+  const long long comps = orient_normals(c, f, N, k, radius, radius > 0.0 ? sqrt_bound(radius) : 0.0, mode, ref);
+  if (comps >= 0) c->ori.frame = frame;
+  if (c->profile) prof_collect_lazy(c);
+  return comps;
+} MVICP_GUARD_ABI
+
+int mvicp_orient_fetch(mvicp_ctx* c, long long cap_rows, double* nrm, unsigned char* flip, int* comp) try {
+  if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
+  if (c->ori.rows < 0) { set_error("no oriented normals: call mvicp_orient_normals first"); return MVICP_ERR_STATE; }
+  if (cap_rows < c->ori.rows) { set_error("cap_rows %lld < %lld rows", cap_rows, c->ori.rows); return MVICP_ERR_ARG; }
+  if (c->ori.rows == 0) return MVICP_OK;
+  const size_t n = (size_t)c->ori.rows;
+  const FetchPart parts[] = {{nrm, c->ori.nrm, 24 * n, "nrm"}, {flip, c->ori.flip, n, "flip"}, {comp, c->ori.comp, 4 * n, "comp"}};
+  return fetch_parts(c, parts);
+} MVICP_GUARD_ABI
+
+int mvicp_orient_adopt(mvicp_ctx* c) try {
+  if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
+  if (c->ori.rows < 0 || c->ori.frame < 0 || c->ori.frame >= c->n_frames) {
+    set_error("no oriented normals to adopt: call mvicp_orient_normals first (an upload to its frame drops the result)");
+    return MVICP_ERR_STATE;
+  }
+  return adopt_normals_into(c, c->ori.frame, c->ori.rows, c->ori.nrm, "oriented");
+} MVICP_GUARD_ABI
+
+int mvicp_negate_normals(mvicp_ctx* c, int frame) try {
+  if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
+  if (frame < 0 || frame >= c->n_frames) { set_error("frame %d out of range [0,%d)", frame, c->n_frames); return MVICP_ERR_ARG; }
+  FrameDev& f = c->frames[frame];
+  if (!f.pts) { set_error("frame %d was never uploaded", frame); return MVICP_ERR_STATE; }
+  if (f.n > 0 && !f.nor) { set_error("frame %d has no normals to negate", frame); return MVICP_ERR_STATE; }
+  MV_CHECK(bind(c));
+  MV_CHECK(finish_builds(c));
+  if (f.n == 0) return MVICP_OK;   // (nothing to write)
+  if (!f.grid.snor) { set_error("frame %d: negating normals needs the per-cloud hash structure", frame); return MVICP_ERR_STATE; }
+  return normals_changed(c, frame, negate_normals(c, f));
+} MVICP_GUARD_ABI
+
+int mvicp_normal_agreement(mvicp_ctx* c, const double* poses, int* pos, int* neg) try {
+  if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
+  if (!poses) { set_error("poses is null"); return MVICP_ERR_ARG; }
+  MV_CHECK(bind(c));
+  MV_CHECK(check_evaluable(c, MVICP_METRIC_SYMMETRIC));
+  std::vector<char> use((size_t)c->E, 0);
+  for (int e = 0; e < c->E; ++e) use[e] = c->owned[e] && c->h_count[e] > 0 && !((int)c->src_fixed.size() == c->E && c->src_fixed[e]);
+  const int st = normal_agreement(c, poses, use.data(), pos, neg);
+  if (c->profile) prof_collect_lazy(c);
+  return st;
+} MVICP_GUARD_ABI
+
+int mvicp_signs_from_agreement(int n_frames, int n_edges, const int* src, const int* dst, const int* pos, const int* neg, int min_count,
+                               unsigned char* flip, int* component) try {
+  if (!flip || n_frames < 1 || n_edges < 0 || min_count < 0 || (n_edges > 0 && (!src || !dst || !pos || !neg))) { set_error("bad arguments"); return MVICP_ERR_ARG; }
+  for (int e = 0; e < n_edges; ++e) {
+    if (src[e] < 0 || src[e] >= n_frames || dst[e] < 0 || dst[e] >= n_frames || src[e] == dst[e]) { set_error("edge %d: bad frame indices", e); return MVICP_ERR_ARG; }
+    if (pos[e] < 0 || neg[e] < 0) { set_error("edge %d: a negative count", e); return MVICP_ERR_ARG; }
+  }
+  std::vector<int> order;
+  for (int e = 0; e < n_edges; ++e)
+    if ((long long)pos[e] + neg[e] >= min_count && pos[e] != neg[e]) order.push_back(e);
+  auto margin = [&](int e) { return std::llabs((long long)pos[e] - neg[e]); };
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return margin(a) > margin(b); });   // (stable: e ascending among equals)
+  // Kruskal with a weighted union-find: par[f] = (parent, parity to it); the lower index is always the root, so a root is its tree's anchor
+  std::vector<int> par((size_t)n_frames), px((size_t)n_frames, 0);
+  for (int i = 0; i < n_frames; ++i) par[i] = i;
+  auto find = [&](int i, int* parity) { int x = 0; while (par[i] != i) { x ^= px[i]; i = par[i]; } *parity = x; return i; };
+  for (int e : order) {
+    int xa = 0, xb = 0;
+    const int ra = find(src[e], &xa), rb = find(dst[e], &xb);
+    if (ra == rb) continue;
+    const int f = pos[e] < neg[e] ? 1 : 0;
+    const int lo = std::min(ra, rb), hi = std::max(ra, rb);
+    par[hi] = lo; px[hi] = xa ^ xb ^ f;
+  }
+  int comps = 0;
+  for (int i = 0; i < n_frames; ++i) {
+    int x = 0;
+    const int r = find(i, &x);
+    flip[i] = (unsigned char)x;
+    if (component) component[i] = r;
+    if (r == i) ++comps;
+  }
+  return comps;
 } MVICP_GUARD_ABI
 
 long long mvicp_iss_keypoints(mvicp_ctx* c, int frame, double salient_radius, double non_max_radius, double gamma21, double gamma32, int min_neighbors) try {
@@ -1462,6 +1585,7 @@ int mvicp_set_graph(mvicp_ctx* c, int n_edges, const int* src, const int* dst) t
   c->edst.assign(dst, dst + E);
   c->owned.assign(E, 0);
   c->active.assign(E, 0);
+  c->src_fixed.assign(E, 0);
   c->h_count.assign(E, 0);
   c->h_weight.assign(E, 0.f);
   // contiguous edge chunks balanced by N_src
@@ -1717,6 +1841,7 @@ static int correspond_body(mvicp_ctx* c, const double* poses, const unsigned cha
   double* hx = c->h_pin;
   for (int e = 0; e < E; ++e) {
     c->active[e] = c->owned[e] && !(fixed && fixed[c->esrc[e]]);
+    c->src_fixed[e] = fixed && fixed[c->esrc[e]];
     if (same_active_set && (c->active[e] != 0) != (c->nn_cache_edge[e] != 0)) same_active_set = false;
     nsrc[e] = c->active[e] ? c->frames[c->esrc[e]].n : 0;
     const double* Ps = poses + 16 * (size_t)c->esrc[e];

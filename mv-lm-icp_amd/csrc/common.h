@@ -120,7 +120,7 @@ struct ProfEntry {
 
 // ---- buffers and results a stage of the library owns ---------------------------------------------------------------------------------
 // A stage (voxel grid, outlier filter, neighbour search, FPFH, descriptor matching, consensus, batched coarse poses, ISS keypoints, estimated
-// normals) keeps its LAST result on the context until the caller has fetched it.  Ownership, stated once for all nine: the stage's struct below holds
+// normals, oriented normals) keeps its LAST result on the context until the caller has fetched it.  Ownership, stated once for all ten: the stage's struct below holds
 // buffers of its own (so that a call touches nothing a search, a queued evaluation, the census or another stage uses), kept between
 // calls and grown on demand, the result arrays as views into them, and the sizes / flags, whose defaults mean "no result".  A call marks
 // its result as gone when it starts (a failed call leaves none behind) and sets it after its last wait; the result then lives until the
@@ -232,6 +232,22 @@ struct NormalsStage {
   long long rows = -1; int frame = -1;   // rows < 0: none
   void drop_result() { rows = -1; frame = -1; }
   void release() { dev.release(); *this = NormalsStage(); }
+};
+
+// orient.hip.  dev: [nrm n x 3 doubles | comp n ints | flip n bytes | the work arrays of the Boruvka rounds], pin: the counters the host
+// reads per round; the neighbourhoods are the KnnStage result of the search the call runs.  frame: the slot the result was computed for
+// (mvicp_orient_adopt writes there); an upload to that slot drops the result
+struct OrientStage {
+  DevBuf dev; PinBuf pin;
+  double* nrm = nullptr; unsigned char* flip = nullptr; int* comp = nullptr;
+  long long rows = -1, comps = 0; int frame = -1;   // rows < 0: none
+  void drop_result() { rows = -1; comps = 0; frame = -1; }
+  void release() { dev.release(); pin.release(); *this = OrientStage(); }
+};
+// orient.hip (mvicp_normal_agreement).  dev: [poses | per-edge pointer tables | per-edge counts | pos | neg], pin: the host copy of pos | neg
+struct AgreementStage {
+  DevBuf dev; PinBuf pin;
+  void release() { dev.release(); pin.release(); *this = AgreementStage(); }
 };
 
 struct RcclApi;  // comm.cpp
@@ -378,6 +394,9 @@ struct mvicp_ctx {
   mvicp::CoarseStage coarse;
   mvicp::IssStage iss;
   mvicp::NormalsStage nrm;
+  mvicp::OrientStage ori;
+  mvicp::AgreementStage agree;
+  std::vector<char> src_fixed;     // E: the edge's source frame was fixed in the last mvicp_correspond (0 before the first): mvicp_normal_agreement skips it
 
   // cached small tables
   struct CachedTable { std::vector<char> bytes; void* d = nullptr; size_t cap = 0; };
@@ -523,8 +542,18 @@ long long iss_keypoints(mvicp_ctx* c, const FrameDev& f, double B2_salient, doub
 // built; 3 <= max_nn <= 64, B2 = sqrt_bound(radius) when radius > 0, viewpoint 3 finite doubles); the result stays on the context (c->nrm;
 // the caller sets c->nrm.frame), the search's in c->knn.  Returns the number of rows or a negative status.  Waits for the stream; history-neutral.
 long long normals_estimate(mvicp_ctx* c, const FrameDev& f, int max_nn, double radius, double B2, const double* viewpoint);
-// normals_pca.hip: c->nrm.nrm (f.n rows) into f.nor and f.grid.snor (both allocated, f.n > 0, structures built).  Waits for the stream.
-int normals_adopt(mvicp_ctx* c, FrameDev& f);
+// normals_pca.hip: nrm (f.n rows, device memory) into f.nor and f.grid.snor (both allocated, f.n > 0, structures built).  Waits for the stream.
+int normals_adopt(mvicp_ctx* c, FrameDev& f, const double* nrm);
+// orient.hip: knn_search(c, f, null, 0, 0, k, radius, B2) and the propagation over its rows for the normals N (f.n x 3, device memory) of
+// frame f (valid, uploaded, structures built; 2 <= k <= 64, mode an mvicp_orient_mode, ref 3 finite doubles); the result stays on the
+// context (c->ori; the caller sets c->ori.frame), the search's in c->knn.  Returns the number of components or a negative status (a
+// non-finite weight: MVICP_ERR_ARG, no result).  Waits for the stream once per round; history-neutral.
+long long orient_normals(mvicp_ctx* c, const FrameDev& f, const double* N, int k, double radius, double B2, int mode, const double* ref);
+// orient.hip: every stored normal of f negated in place, in original and in sorted order (f.nor and f.grid.snor non-null).  Waits for the stream.
+int negate_normals(mvicp_ctx* c, FrameDev& f);
+// orient.hip: per owned edge with use[e] != 0 the counts of positive / negative dots between the rotated normals of its list's pairs, at
+// poses (n_frames x 16); every used edge's frames have sorted normals.  One launch, one wait; history-neutral.
+int normal_agreement(mvicp_ctx* c, const double* poses, const char* use, int* pos, int* neg);
 int launch_compact(mvicp_ctx* c, double d2_bound);                                    // corr.hip
 int launch_gather_stream(mvicp_ctx* c);
 int launch_select_median(mvicp_ctx* c, double d2_bound);   // two-pass select anchored at the acceptance bound: any key set, exact

@@ -141,8 +141,8 @@ long long normals_estimate(mvicp_ctx* c, const FrameDev& f, int max_nn, double r
   return n;
 }
 
-int normals_adopt(mvicp_ctx* c, FrameDev& f) {
-  hipLaunchKernelGGL(normals_adopt_kernel, dim3(grid_of(f.n, VT)), dim3(VT), 0, c->stream, c->nrm.nrm, f.n, f.grid.inv, f.nor, f.grid.snor);
+int normals_adopt(mvicp_ctx* c, FrameDev& f, const double* nrm) {
+  hipLaunchKernelGGL(normals_adopt_kernel, dim3(grid_of(f.n, VT)), dim3(VT), 0, c->stream, nrm, f.n, f.grid.inv, f.nor, f.grid.snor);
   MV_HIP(hipGetLastError());
   MV_HIP(hipStreamSynchronize(c->stream));
   return MVICP_OK;

@@ -425,6 +425,43 @@ std::vector<double> Frame::estimateNormals(int max_nn, double radius, const Vect
   return curvature;
 }
 
+int Frame::orientNormals(int k, double radius) {
+  if (pts.empty()) return 0;
+  if (nor.size() != pts.size()) throw std::runtime_error("mvicp: orientNormals needs a normal per point");
+  int slot = 0;
+  mvicp_ctx* c = Session::get().query_context(this, &slot, true);
+  const long long comps = mvicp_orient_normals(c, slot, 0, k, radius, MVICP_ORIENT_ANCHOR, nullptr);
+  if (comps < 0) check((int)comps);
+  std::vector<Vector3d> fresh(pts.size());
+  check(mvicp_orient_fetch(c, (long long)fresh.size(), fresh[0].data(), nullptr, nullptr));
+  nor.swap(fresh);
+  ++version;   // a bound session re-uploads this cloud (new normals) at its next bind
+  return (int)comps;
+}
+
+int Session::orientFrames(std::vector<std::shared_ptr<Frame>>& frames, float thresh, int min_count, std::vector<unsigned char>* flipped) {
+  const int K = (int)frames.size();
+  correspond(frames, thresh);
+  std::vector<double> P(16 * (size_t)K);
+  for (int i = 0; i < K; ++i) std::memcpy(&P[16 * (size_t)i], frames[i]->pose.data(), 128);
+  const int E = (int)esrc.size();
+  std::vector<int> pos((size_t)E + 1, 0), neg((size_t)E + 1, 0);
+  check(mvicp_normal_agreement(ctx, P.data(), pos.data(), neg.data()));
+  std::vector<unsigned char> flip((size_t)K, 0);
+  const int comps = mvicp_signs_from_agreement(K, E, esrc.data(), edst.data(), pos.data(), neg.data(), min_count, flip.data(), nullptr);
+  check(comps);
+  for (int i = 0; i < K; ++i) {
+    if (!flip[i]) continue;
+    Frame& f = *frames[i];
+    std::vector<Vector3d> turned(f.nor.size());
+    for (size_t j = 0; j < turned.size(); ++j) turned[j] = Vector3d(-f.nor[j][0], -f.nor[j][1], -f.nor[j][2]);
+    f.nor.swap(turned);
+    ++f.version;
+  }
+  if (flipped) *flipped = flip;
+  return comps;
+}
+
 const std::vector<int>& Frame::getNeighbourIndices(size_t num_results) {
   if (pts.empty()) throw std::runtime_error("mvicp: getNeighbours on an empty cloud (nanoflann throws here: nanoflann.hpp:904)");
   if (num_results < 3 || num_results > 16 || num_results > pts.size())

@@ -11,7 +11,7 @@
 // WHAT THE MIRROR NOTICES (the one rule; INTEGRATION.md "What the mirror notices").  The device copies, the cached search and
 // the k-NN table are keyed on addresses, sizes and counters, never on the clouds' values:
 //   noticed by itself   a `pts` / `nor` vector REPLACED by another one (another buffer address or another size) on a bound and on an
-//                       unbound frame; `version` (recomputeNormals() and estimateNormals() bump it); a Frame destroyed, or destroyed and constructed again in
+//                       unbound frame; `version` (recomputeNormals(), estimateNormals(), orientNormals() and Session::orientFrames bump it); a Frame destroyed, or destroyed and constructed again in
 //                       the same storage (~Frame() tells the session); another frames vector, other frames in it, another order, another
 //                       graph; changed poses / thresh / fixed / Session::nn_method; Session::copy_back switched; any call that threw
 //                       (whatever the session believed about the device copy it was uploading is forgotten before the upload starts).
@@ -74,6 +74,12 @@ class Frame {
   // the curvatures (surface variation, one per point).  Runs in the context Session::query_context finds for this frame
   // (bin/multiview --normals_nn / --normals_radius).
   std::vector<double> estimateNormals(int max_nn, double radius = 0.0, const Vector3d& viewpoint = Vector3d());
+  // Consistent orientation without a viewpoint (no counterpart in the reference): mvicp_orient_normals on this cloud and its `nor` as they
+  // are stored (source 0, MVICP_ORIENT_ANCHOR) -- the sign of point 0's normal (of every tree's lowest point) is carried along the maximum
+  // spanning forest of the graph of the k nearest neighbours (radius > 0: within it) weighted by |n_i . n_j|.  Replaces `nor` and bumps
+  // `version` as estimateNormals() does and returns the number of trees (1: the whole cloud agrees with itself).  Which side the cloud
+  // ends on is arbitrary: Session::orientFrames makes the frames agree with each other (bin/multiview --normals_orient mst).
+  int orientNormals(int k, double radius = 0.0);
   // frame.cpp:208-231: the num_results nearest points of pts[queryIdx] in this cloud — the point itself first — in the order nanoflann's
   // knnSearch returns them (ascending distance, exact ties in the tree's visiting order).  The reference runs one tree query per call; here the
   // first call for a given num_results answers ALL points of the cloud in one device launch (the k-NN kernel behind recomputeNormals, 3 <= k <= 16)
@@ -185,6 +191,12 @@ struct Session {
   int initFromFeatures(std::vector<std::shared_ptr<Frame>>& frames, const FeatureInit& opts, std::vector<FeatureEdge>* edges = nullptr,
                        std::vector<FeatureKeypoints>* keypoints = nullptr);
   void correspond(std::vector<std::shared_ptr<Frame>>& frames, float thresh);
+  // The step between the clouds of a consistent orientation (every frame consistent in itself, e.g. by Frame::orientNormals, and the graph
+  // built): one search at the current poses, mvicp_normal_agreement over its lists, mvicp_signs_from_agreement over the graph's edges (an
+  // edge is usable with at least min_count pairs); the normals of every frame the rule flips are negated (a replaced `nor` vector and a
+  // bumped `version`: the next bind uploads them).  `flipped` receives one flag per frame.  Returns the number of components of the sign
+  // graph (more than one is reported, not repaired).
+  int orientFrames(std::vector<std::shared_ptr<Frame>>& frames, float thresh, int min_count = 0, std::vector<unsigned char>* flipped = nullptr);
   void optimize(std::vector<std::shared_ptr<Frame>>& frames, int param, bool pointToPlane, bool robust, mvicp_summary* sm = nullptr);
   // the same with the objective named (MVICP_METRIC_SYMMETRIC needs normals on every frame, oriented consistently)
   void optimize(std::vector<std::shared_ptr<Frame>>& frames, int param, mvicp_metric metric, bool robust, mvicp_summary* sm = nullptr);

@@ -46,6 +46,12 @@
 // place of the recomputeNormals step (after the outlier filter, before any coarse level): the exactly specified normals of
 // mvicp_estimate_normals over the K nearest points (3 <= K <= 64; R > 0: within R), turned towards the view's own origin -- the sensor of a
 // range image in its own frame -- so that all frames agree on the side their normals point to, which --symmetric and --init features need.
+// --normals_orient mst [--orient_nn K] (default off; K = 10): consistent orientation WITHOUT a viewpoint, for clouds whose frame origin is no
+// sensor.  Per frame, after the normals step: Frame::orientNormals(K) (mvicp_orient_normals: the signs are carried along the maximum spanning
+// forest of the K-nearest-neighbour graph weighted by |n_i . n_j|); then once across the frames, at the start poses, after the graph is built
+// and before round 0: Session::orientFrames (one search, the agreement of the normals over its lists, a spanning forest over the frames;
+// the frames it flips are negated).  One line per frame, `normal orientation: frame i trees t`, and one line
+// `normal orientation: C component(s), flipped f0 f1 ..` (printed with --quiet too).
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
@@ -79,6 +85,8 @@ static void loadFrames(const Flags& F, std::vector<std::shared_ptr<Frame>>& fram
     }
     if (F.i("normals_nn", 0) > 0) f->estimateNormals(F.i("normals_nn", 0), F.f("normals_radius", 0.0));   // (viewpoint: the view's own origin)
     else if (F.b("recomputeNormals", true)) f->recomputeNormals();  // main_multiview.cpp:49,68-70 (default on)
+    if (F.s("normals_orient", "") == "mst")
+      std::cout << "normal orientation: frame " << frames.size() << " trees " << f->orientNormals(F.i("orient_nn", 10)) << std::endl;
     if (groundtruth.size() == clouds.size()) {
       f->pose = loadMatrix4d(poses[i]);
       f->poseGroundTruth = loadMatrix4d(groundtruth[i]);
@@ -102,6 +110,7 @@ int main(int argc, char** argv) {
   Session::get().copy_threads = F.i("copy_threads", 8);
   noiseStream() = F.s("noise_stream", "libstdc++") == "libc++" ? 1 : F.s("noise_stream", "libstdc++") == "g++" ? 2 : 0;
 
+  if (!F.s("normals_orient", "").empty() && F.s("normals_orient", "") != "mst") { std::cerr << "--normals_orient must be mst" << std::endl; return 1; }
   std::vector<std::shared_ptr<Frame>> frames;
   try {
     loadFrames(F, frames, dir);
@@ -161,6 +170,15 @@ int main(int argc, char** argv) {
       std::cout << std::endl;
     }
     if (overlap_graph) std::cout << "overlap graph: " << components << " component(s)" << std::endl;
+  }
+  if (F.s("normals_orient", "") == "mst" && frames.size() > 1) {
+    try {
+      std::vector<unsigned char> flipped;
+      const int comps = Session::get().orientFrames(frames, cutoff, 0, &flipped);
+      std::cout << "normal orientation: " << comps << " component(s), flipped";
+      for (unsigned char f : flipped) std::cout << " " << (int)f;
+      std::cout << std::endl;
+    } catch (const std::exception& ex) { std::cerr << ex.what() << std::endl; return 2; }
   }
   const int coarse_rounds = F.i("coarse_rounds", 0);
   std::vector<std::shared_ptr<Frame>> coarse;   // the frames' voxelDownsample copies (coarse_rounds > 0)

@@ -10,6 +10,7 @@ LIB_PATH = os.environ.get("MVICP_LIB") or os.path.join(os.path.dirname(_HERE), "
 PARAM_EIGEN_QUATERNION, PARAM_ANGLE_AXIS, PARAM_SOPHUS_SE3 = 0, 1, 2
 METRIC_POINT, METRIC_PLANE, METRIC_SYMMETRIC = 0, 1, 2   # mvicp_metric
 NN_AUTO, NN_BRUTE, NN_GRID, NN_TILE = 0, 1, 2, 3
+ORIENT_ANCHOR, ORIENT_VIEWPOINT, ORIENT_DIRECTION = 0, 1, 2   # mvicp_orient_mode
 EDGE_BLOCK = 91
 
 SYMBOLS = [
@@ -22,6 +23,7 @@ SYMBOLS = [
     "mvicp_outlier_filter", "mvicp_outlier_fetch", "mvicp_outlier_threshold", "mvicp_cache_allowance",
     "mvicp_knn_search", "mvicp_knn_fetch", "mvicp_fpfh", "mvicp_fpfh_fetch", "mvicp_iss_keypoints", "mvicp_iss_fetch",
     "mvicp_estimate_normals", "mvicp_normals_fetch", "mvicp_normals_adopt",
+    "mvicp_orient_normals", "mvicp_orient_fetch", "mvicp_orient_adopt", "mvicp_normal_agreement", "mvicp_signs_from_agreement", "mvicp_negate_normals",
     "mvicp_feature_match", "mvicp_feature_match_fetch", "mvicp_match_pairs", "mvicp_consensus", "mvicp_consensus_fetch",
     "mvicp_coarse_pairs", "mvicp_coarse_pairs_fetch", "mvicp_poses_from_pairs",
 ]
@@ -147,6 +149,13 @@ def load_library(path=None):
     lib.mvicp_estimate_normals.restype = C.c_longlong
     lib.mvicp_normals_fetch.argtypes = [vp, C.c_longlong, vp, vp, vp]
     lib.mvicp_normals_adopt.argtypes = [vp]
+    lib.mvicp_orient_normals.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, dp]
+    lib.mvicp_orient_normals.restype = C.c_longlong
+    lib.mvicp_orient_fetch.argtypes = [vp, C.c_longlong, vp, vp, vp]
+    lib.mvicp_orient_adopt.argtypes = [vp]
+    lib.mvicp_normal_agreement.argtypes = [vp, dp, ip, ip]
+    lib.mvicp_signs_from_agreement.argtypes = [C.c_int, C.c_int, ip, ip, ip, ip, C.c_int, C.POINTER(C.c_ubyte), ip]
+    lib.mvicp_negate_normals.argtypes = [vp, C.c_int]
     lib.mvicp_feature_match.argtypes = [vp, vp, C.c_longlong, vp, C.c_longlong, C.c_int]
     lib.mvicp_feature_match.restype = C.c_longlong
     lib.mvicp_feature_match_fetch.argtypes = [vp, C.c_longlong, C.c_longlong, vp, vp, vp, vp]
@@ -354,6 +363,41 @@ def poses_from_pairs(n_frames, src, dst, count, pose, min_count=0, root=0, root_
                                                 _dp(out), _ip(parent), _ip(pedge), _ip(comp)))
     return {"poses": poses_from_c(out[:K]), "parent": parent[:K].copy(), "parent_edge": pedge[:K].copy(), "component": comp[:K].copy(),
             "components": int(nc)}
+
+
+def signs_from_agreement(n_frames, src, dst, pos, neg, min_count=0):
+    """mvicp_signs_from_agreement: which frames to negate so that the normals of all frames agree.  Edge e = (src[e], dst[e]) with pos[e]
+    pairs whose normals agree and neg[e] that disagree is usable iff pos + neg >= min_count and pos != neg; the maximum spanning forest by
+    (|pos - neg| descending, e ascending); every tree's lowest frame keeps its sign.
+    -> dict(flip (K,) uint8, component (K,) int32 = the lowest frame of the tree, components).  Host only."""
+    lib = load_library()
+    src = np.ascontiguousarray(src, dtype=np.int32).reshape(-1); dst = np.ascontiguousarray(dst, dtype=np.int32).reshape(-1)
+    pos = np.ascontiguousarray(pos, dtype=np.int32).reshape(-1); neg = np.ascontiguousarray(neg, dtype=np.int32).reshape(-1)
+    E = len(src)
+    if len(dst) != E or len(pos) != E or len(neg) != E:
+        raise ValueError("src, dst, pos and neg differ in length")
+    K = int(n_frames)
+    flip = np.zeros(max(K, 1), dtype=np.uint8); comp = np.zeros(max(K, 1), dtype=np.int32)
+    spare = np.zeros(1, dtype=np.int32)   # (an empty array still gets a pointer that is not NULL)
+    ip = lambda a: _ip(a if a.size else spare)
+    nc = _check(lib, lib.mvicp_signs_from_agreement(K, E, ip(src), ip(dst), ip(pos), ip(neg), int(min_count), flip.ctypes.data_as(C.POINTER(C.c_ubyte)),
+                                                    _ip(comp)))
+    return {"flip": flip[:K].copy(), "component": comp[:K].copy(), "components": int(nc)}
+
+
+def orient_frames(eng, poses, fixed, cutoff, min_count=0):
+    """The cross-frame step of a consistent orientation, on an engine with a graph whose frames all have normals (each consistent in
+    itself: Engine.orient_normals + adopt_orientation): correspond(poses, fixed, cutoff) -> normal_agreement(poses) ->
+    signs_from_agreement over the engine's edges -> negate_normals on every frame the rule flips -> reset_history, so that the
+    registration that follows is an ordinary one.  -> dict(flip, component, components, pos, neg, counts)."""
+    counts, _ = eng.correspond(poses, fixed, cutoff)
+    pos, neg = eng.normal_agreement(poses)
+    out = signs_from_agreement(len(eng.npts), eng.src, eng.dst, pos, neg, min_count)
+    for i in np.flatnonzero(out["flip"]):
+        eng.negate_normals(int(i))
+    eng.reset_history()
+    out.update(pos=pos, neg=neg, counts=np.asarray(counts).copy())
+    return out
 
 
 def init_from_clouds(eng, frames, xyz_list, radius, tau, max_nn=64, edges=None, hypotheses=10000, seed=0, edge_sim=0.9, mutual=True, ratio=1.0,
@@ -808,6 +852,41 @@ class Engine:
         """mvicp_normals_adopt: the frame of the last estimate_normals takes that result as its normals, as recompute_normals would
         leave them (lists that point into the frame are re-gathered, queued evaluations are voided)."""
         _check(self.lib, self.lib.mvicp_normals_adopt(self.h))
+
+    def orient_normals(self, frame, k=10, radius=0.0, source=0, mode=ORIENT_ANCHOR, ref=None, device=False):
+        """mvicp_orient_normals + mvicp_orient_fetch: the normals of `frame` (source 0: its stored ones, 1: those of the last
+        estimate_normals of this frame) made consistent with each other along the maximum spanning forest of the graph of the k nearest
+        neighbours (radius > 0: within `radius`) weighted by |N_i . N_j|; every tree's sign is its lowest point's (ORIENT_ANCHOR), or a
+        majority vote towards the point `ref` (ORIENT_VIEWPOINT; None = the origin) or along the direction `ref` (ORIENT_DIRECTION)
+        -> dict(nrm (n,3) float64, flip (n,) uint8, comp (n,) int32 = the lowest point of the tree, components).  device=True: torch
+        tensors on the engine's GPU instead of numpy arrays.  The frame's own normals are untouched until adopt_orientation().
+        Afterwards the engine's last neighbour-search result is knn_search(frame, None, k, radius).  Needs no graph; history-neutral."""
+        rf = None if ref is None else np.ascontiguousarray(ref, dtype=np.float64).reshape(3)
+        comps = int(_check(self.lib, self.lib.mvicp_orient_normals(self.h, int(frame), int(source), int(k), float(radius), int(mode),
+                                                                   _dp(rf) if rf is not None else None)))
+        n = self.npts[int(frame)]
+        mk, ptr, ready, f64, i32, i64, u8 = self._result_arrays(device)
+        nrm, flip, comp = mk((n, 3), f64), mk((n,), u8), mk((n,), i32)
+        ready()
+        _check(self.lib, self.lib.mvicp_orient_fetch(self.h, n, ptr(nrm), ptr(flip), ptr(comp)))
+        return {"nrm": nrm, "flip": flip, "comp": comp, "components": comps}
+
+    def adopt_orientation(self):
+        """mvicp_orient_adopt: the frame of the last orient_normals takes that result as its normals, with the side effects of adopt_normals."""
+        _check(self.lib, self.lib.mvicp_orient_adopt(self.h))
+
+    def normal_agreement(self, poses):
+        """mvicp_normal_agreement at `poses` ((K,4,4)) over the lists the engine holds -> (pos (E,) int32, neg (E,) int32): per edge the pairs
+        whose normals, rotated into the world, have a positive / a negative dot.  History-neutral."""
+        P = poses_to_c(poses)
+        E = self.E
+        pos, neg = np.zeros(max(E, 1), dtype=np.int32), np.zeros(max(E, 1), dtype=np.int32)
+        _check(self.lib, self.lib.mvicp_normal_agreement(self.h, _dp(P), _ip(pos), _ip(neg)))
+        return pos[:E].copy(), neg[:E].copy()
+
+    def negate_normals(self, frame):
+        """mvicp_negate_normals: every stored normal of `frame` is negated, with the side effects of adopt_normals."""
+        _check(self.lib, self.lib.mvicp_negate_normals(self.h, int(frame)))
 
     def _rows_operand(self, x, cols, what):
         """-> (the array kept alive, its pointer or None when empty, rows) for a (rows, cols) float64 numpy array or torch tensor on the engine's GPU"""
