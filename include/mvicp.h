@@ -414,6 +414,49 @@ int mvicp_normals_fetch(mvicp_ctx* ctx, long long cap_rows, double* nrm, double*
  * MVICP_ERR_STATE, with nothing changed. */
 int mvicp_normals_adopt(mvicp_ctx* ctx);
 
+/* ---- Jet-fitted normals (osculating polynomial), exactly specified -----------------------------------------------------------------------
+ * A PCA normal is the normal of the best plane through a curved, unevenly sampled patch.  mvicp_fit_normals fits a height polynomial of
+ * degree 2 or 3 over the PCA tangent plane (an osculating jet, Cazals & Pouget 2005) and takes the gradient of that polynomial at the
+ * point.  The result is a pure function of the stored bytes, bit for bit (tests/jetref.py is the same definition in numpy and as a scalar
+ * loop).  All arithmetic is fp64, every operation rounded on its own, no fma; only + - x / sqrt, comparisons and
+ * negation occur.  Arguments other than `degree` are those of mvicp_estimate_normals; the coordinates are finite and no product below
+ * overflows.
+ *   1 PCA      n (unit, oriented to the viewpoint), curvature and used = c_i exactly as mvicp_estimate_normals defines them, with that
+ *              contract's row, offsets d_t = p_{j_t} - p_i (+0.0 for t >= c_i) and tree sum T.
+ *   2 Basis    the monomials b_0 .. b_{M-1} = 1, X, Y, X2, XY, Y2 (degree 2, M = 6), continued by X3, X2Y, XY2, Y3 (degree 3, M = 10).
+ *   3 Fallback the point keeps step 1's bytes unchanged, fitted = 0, if c_i < M, if h == 0 (step 5), if a pivot fails (step 8), or if a
+ *              component of g or its length is not finite or the length is 0 (step 10).  Otherwise fitted = 1.
+ *   4 Frame    from n alone: a = the index of the smallest |n_a|, the lowest index among equals; w = e_a x n written out:
+ *              a = 0: w = (+0.0, -n2, n1); a = 1: w = (n2, +0.0, -n0); a = 2: w = (-n1, n0, +0.0).
+ *              u = w / sqrt((w0 w0 + w1 w1) + w2 w2); v = n x u: v0 = n1 u2 - n2 u1, v1 = n2 u0 - n0 u2, v2 = n0 u1 - n1 u0.
+ *   5 Scale    h2 = the largest (d_t0 d_t0 + d_t1 d_t1) + d_t2 d_t2 over t < c_i; h = sqrt(h2).
+ *   6 Coordinates  for t < c_i: X_t = ((d_t0 u0 + d_t1 u1) + d_t2 u2) / h, Y_t the same with v, Z_t the same with n; X2 = X * X, XY = X * Y,
+ *              Y2 = Y * Y, X3 = X2 * X, X2Y = X2 * Y, XY2 = X * Y2, Y3 = Y2 * Y; b_0 = 1.0.  For t >= c_i every b_m and Z are +0.0.
+ *   7 Normal equations  G_ml = T(b_m * b_l) for m <= l (mirrored), r_m = T(b_m * Z).
+ *   8 Cholesky  for j = 0 .. M-1: s = G_jj, then for q = 0 .. j-1 ascending s <- s - L_jq * L_jq; the pivot fails unless
+ *              s > 2^-20 * G_jj (a NaN fails); L_jj = sqrt(s); for r = j+1 .. M-1: s = G_rj, then for q = 0 .. j-1 ascending
+ *              s <- s - L_rq * L_jq; L_rj = s / L_jj.  The threshold 2^-20 is part of the contract.
+ *   9 Solves   forward, j = 0 .. M-1: s = r_j, for q = 0 .. j-1 ascending s <- s - L_jq * y_q; y_j = s / L_jj.  Back, m = M-1 .. 1:
+ *              s = y_m, for q = M-1 .. m+1 descending s <- s - L_qm * a_q; a_m = s / L_mm.  a_0 (the height at the point) is NOT computed.
+ *  10 Normal   g_b = (n_b - a_1 * u_b) - a_2 * v_b; len = sqrt((g0 g0 + g1 g1) + g2 g2); nrm = g / len.  No re-orientation: g . n is 1 up
+ *              to rounding.
+ * The curvature stays the PCA surface variation of step 1.  THE RESULT REPLACES THE CONTEXT'S LAST mvicp_estimate_normals RESULT: the same
+ * slot, so mvicp_normals_fetch, mvicp_normals_adopt and mvicp_orient_normals(source = 1) act on it unchanged, and its lifetime and drop
+ * rules are the estimate's (the next mvicp_estimate_normals or mvicp_fit_normals, an upload to the frame, mvicp_set_num_frames,
+ * mvicp_destroy).  In addition it holds one byte per point, fitted, for mvicp_normals_fit_fetch.  Like the estimate the call leaves its
+ * internal search as the context's last neighbour search, is otherwise HISTORY-NEUTRAL and needs NO graph.  Profile scopes: those of the
+ * search, "normals_jet".
+ * RETURNS THE NUMBER OF ROWS n (>= 0) or a negative mvicp_status.
+ * Errors: those of mvicp_estimate_normals, and a degree outside {2, 3} -> MVICP_ERR_ARG; argument errors are decided before the context
+ * is touched (earlier results stay). */
+long long mvicp_fit_normals(mvicp_ctx* ctx, int frame, int max_nn, double radius, const double* viewpoint, int degree);
+/* Copies the fitted bytes (n unsigned chars, 1 = the row is the fit, 0 = the row is the PCA estimate) of the last mvicp_fit_normals; a
+ * HOST pointer or a DEVICE pointer of the context's device, decided as mvicp_voxel_fetch decides; may be NULL.  cap_rows = rows the
+ * destination holds.
+ * Errors: NULL context, cap_rows < n -> MVICP_ERR_ARG; the context's last estimate is not a mvicp_fit_normals result, or there is none ->
+ * MVICP_ERR_STATE. */
+int mvicp_normals_fit_fetch(mvicp_ctx* ctx, long long cap_rows, unsigned char* fitted);
+
 /* ---- Consistent normal orientation without a viewpoint: propagation over a neighbour graph ----------------------------------------
  * mvicp_estimate_normals turns a normal towards a viewpoint, which is right for a range image and for nothing else.  mvicp_orient_normals
  * makes the normals of ONE cloud agree with each other without one (Hoppe et al. 1992): the sign is carried along the maximum spanning

@@ -224,13 +224,14 @@ struct IssStage {
   long long n = -1, k = 0; int has_normals = 0;   // points of the frame (< 0: none), keypoints among them
   void release() { dev.release(); tmp.release(); pin.release(); *this = IssStage(); }
 };
-// normals_pca.hip.  dev: [nrm n x 3 doubles | curvature n doubles | used n ints]; the neighbourhoods are the KnnStage result of the search the
-// call runs.  frame: the slot the result was computed for (mvicp_normals_adopt writes there); an upload to that slot drops the result
+// normals_pca.hip, normals_jet.hip.  dev: [nrm n x 3 doubles | curvature n doubles | used n ints | fitted n bytes, after mvicp_fit_normals only];
+// the neighbourhoods are the KnnStage result of the search the call runs.  frame: the slot the result was computed for (mvicp_normals_adopt
+// writes there); an upload to that slot drops the result.  has_fit: the result is mvicp_fit_normals' (mvicp_normals_fit_fetch serves it)
 struct NormalsStage {
   DevBuf dev;
-  double* nrm = nullptr; double* curv = nullptr; int* used = nullptr;
-  long long rows = -1; int frame = -1;   // rows < 0: none
-  void drop_result() { rows = -1; frame = -1; }
+  double* nrm = nullptr; double* curv = nullptr; int* used = nullptr; unsigned char* fitted = nullptr;
+  long long rows = -1; int frame = -1, has_fit = 0;   // rows < 0: none
+  void drop_result() { rows = -1; frame = -1; has_fit = 0; }
   void release() { dev.release(); *this = NormalsStage(); }
 };
 
@@ -542,6 +543,8 @@ long long iss_keypoints(mvicp_ctx* c, const FrameDev& f, double B2_salient, doub
 // built; 3 <= max_nn <= 64, B2 = sqrt_bound(radius) when radius > 0, viewpoint 3 finite doubles); the result stays on the context (c->nrm;
 // the caller sets c->nrm.frame), the search's in c->knn.  Returns the number of rows or a negative status.  Waits for the stream; history-neutral.
 long long normals_estimate(mvicp_ctx* c, const FrameDev& f, int max_nn, double radius, double B2, const double* viewpoint);
+// normals_jet.hip: the same with the jet fit of `degree` (2 or 3) behind the PCA part; the result replaces c->nrm's and carries the fitted bytes.
+long long normals_fit(mvicp_ctx* c, const FrameDev& f, int max_nn, double radius, double B2, const double* viewpoint, int degree);
 // normals_pca.hip: nrm (f.n rows, device memory) into f.nor and f.grid.snor (both allocated, f.n > 0, structures built).  Waits for the stream.
 int normals_adopt(mvicp_ctx* c, FrameDev& f, const double* nrm);
 // orient.hip: knn_search(c, f, null, 0, 0, k, radius, B2) and the propagation over its rows for the normals N (f.n x 3, device memory) of

@@ -10,51 +10,17 @@
 //                butterfly forms the pairwise tree y[u] <- y[2u] + y[2u+1] of the contract in every lane at once, because IEEE addition
 //                is commutative -- then the 3 x 3 Jacobi iteration of the ISS contract with the vectors, on values every lane holds alike;
 //                lanes 0 .. 2 store the normal, lane 3 the curvature, lane 4 the count.
-// Every fp64 operation is an __d*_rn intrinsic: rounded on its own, never contracted into an fma.
+// Every fp64 operation is an __d*_rn intrinsic: rounded on its own, never contracted into an fma.  The per-point part lives in normals_pca.h,
+// which normals_jet.hip (mvicp_fit_normals) shares.
 #include "common.h"
+#include "normals_pca.h"
 
 namespace mvicp {
 
 namespace {
 
 constexpr int kWavesPerBlock = 4;
-constexpr int kSweeps = 6;
 constexpr int VT = 256;
-
-// T(y): the sum of the 64 lanes' values in the order of the contract's tree, in every lane
-__device__ __forceinline__ double tree_sum(double v) {
-#pragma unroll
-  for (int x = 1; x < 64; x <<= 1) v = __dadd_rn(v, __shfl_xor(v, x, 64));
-  return v;
-}
-
-// a 3 x 3 matrix in nine named registers: every index below is a template argument, so nothing is addressed at run time
-struct M33 { double m00, m01, m02, m10, m11, m12, m20, m21, m22; };
-template <int R, int C> __device__ __forceinline__ double& at(M33& m) {
-  if constexpr (R == 0) { if constexpr (C == 0) return m.m00; else if constexpr (C == 1) return m.m01; else return m.m02; }
-  else if constexpr (R == 1) { if constexpr (C == 0) return m.m10; else if constexpr (C == 1) return m.m11; else return m.m12; }
-  else { if constexpr (C == 0) return m.m20; else if constexpr (C == 1) return m.m21; else return m.m22; }
-}
-// columns P, Q: (x[r][P], x[r][Q]) <- (c x[r][P] - s x[r][Q], s x[r][P] + c x[r][Q])
-template <int R, int P, int Q> __device__ __forceinline__ void rot_cols(M33& x, double c, double s) {
-  const double xp = at<R, P>(x), xq = at<R, Q>(x);
-  at<R, P>(x) = __dsub_rn(__dmul_rn(c, xp), __dmul_rn(s, xq)); at<R, Q>(x) = __dadd_rn(__dmul_rn(s, xp), __dmul_rn(c, xq));
-}
-template <int R, int P, int Q> __device__ __forceinline__ void rot_rows(M33& x, double c, double s) {
-  const double xp = at<P, R>(x), xq = at<Q, R>(x);
-  at<P, R>(x) = __dsub_rn(__dmul_rn(c, xp), __dmul_rn(s, xq)); at<Q, R>(x) = __dadd_rn(__dmul_rn(s, xp), __dmul_rn(c, xq));
-}
-// one rotation of the ISS contract's Jacobi iteration (iss.hip jacobi_eigenvalues) on the pair (P, Q), with the vectors
-template <int P, int Q> __device__ __forceinline__ void rotate(M33& A, M33& V) {
-  const double apq = at<P, Q>(A);
-  if (apq == 0.0) return;
-  const double theta = __ddiv_rn(__dsub_rn(at<Q, Q>(A), at<P, P>(A)), __dmul_rn(2.0, apq));
-  const double t = __ddiv_rn(theta >= 0 ? 1.0 : -1.0, __dadd_rn(fabs(theta), __dsqrt_rn(__dadd_rn(__dmul_rn(theta, theta), 1.0))));
-  const double c = __ddiv_rn(1.0, __dsqrt_rn(__dadd_rn(__dmul_rn(t, t), 1.0))), s = __dmul_rn(t, c);
-  rot_cols<0, P, Q>(A, c, s); rot_cols<1, P, Q>(A, c, s); rot_cols<2, P, Q>(A, c, s);   // A <- A J
-  rot_rows<0, P, Q>(A, c, s); rot_rows<1, P, Q>(A, c, s); rot_rows<2, P, Q>(A, c, s);   // A <- J^T A
-  rot_cols<0, P, Q>(V, c, s); rot_cols<1, P, Q>(V, c, s); rot_cols<2, P, Q>(V, c, s);   // V <- V J
-}
 
 __global__ __launch_bounds__(64 * kWavesPerBlock) void normals_pca_kernel(const double* __restrict__ pts, int n, int k, const int* __restrict__ cnt,
                                                                           const int* __restrict__ idx, double vx, double vy, double vz,
@@ -65,36 +31,9 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void normals_pca_kernel(const 
   const int len = cnt[i];   // <= k <= 64
   const double* pi = pts + 3 * (size_t)i;
   const double px = pi[0], py = pi[1], pz = pi[2];
-  double d0 = 0.0, d1 = 0.0, d2 = 0.0;
-  if (lane < len) {
-    const double* pj = pts + 3 * (size_t)idx[(size_t)i * (size_t)k + lane];
-    d0 = __dsub_rn(pj[0], px); d1 = __dsub_rn(pj[1], py); d2 = __dsub_rn(pj[2], pz);
-  }
-  double nx = 0.0, ny = 0.0, nz = 0.0, cv = 0.0;
-  if (len >= 3) {   // (wave-uniform)
-    const double c = (double)len;
-    const double m0 = __ddiv_rn(tree_sum(d0), c), m1 = __ddiv_rn(tree_sum(d1), c), m2 = __ddiv_rn(tree_sum(d2), c);
-    const bool in = lane < len;
-    const double x0 = in ? __dsub_rn(d0, m0) : 0.0, x1 = in ? __dsub_rn(d1, m1) : 0.0, x2 = in ? __dsub_rn(d2, m2) : 0.0;
-    const double c00 = tree_sum(__dmul_rn(x0, x0)), c01 = tree_sum(__dmul_rn(x0, x1)), c02 = tree_sum(__dmul_rn(x0, x2));
-    const double c11 = tree_sum(__dmul_rn(x1, x1)), c12 = tree_sum(__dmul_rn(x1, x2)), c22 = tree_sum(__dmul_rn(x2, x2));
-    M33 A = {c00, c01, c02, c01, c11, c12, c02, c12, c22}, V = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
-#pragma unroll 1
-    for (int sweep = 0; sweep < kSweeps; ++sweep) { rotate<0, 1>(A, V); rotate<0, 2>(A, V); rotate<1, 2>(A, V); }
-    const double a0 = A.m00, a1 = A.m11, a2 = A.m22;
-    const bool b1 = a1 < a0;
-    const double l1 = b1 ? a1 : a0;
-    const bool b2 = a2 < l1;
-    const double l = b2 ? a2 : l1;
-    const double e0 = b2 ? V.m02 : b1 ? V.m01 : V.m00, e1 = b2 ? V.m12 : b1 ? V.m11 : V.m10, e2 = b2 ? V.m22 : b1 ? V.m21 : V.m20;
-    const double nn = __dsqrt_rn(__dadd_rn(__dadd_rn(__dmul_rn(e0, e0), __dmul_rn(e1, e1)), __dmul_rn(e2, e2)));
-    nx = __ddiv_rn(e0, nn); ny = __ddiv_rn(e1, nn); nz = __ddiv_rn(e2, nn);
-    const double w0 = __dsub_rn(vx, px), w1 = __dsub_rn(vy, py), w2 = __dsub_rn(vz, pz);
-    const double s = __dadd_rn(__dadd_rn(__dmul_rn(nx, w0), __dmul_rn(ny, w1)), __dmul_rn(nz, w2));
-    if (s < 0.0) { nx = -nx; ny = -ny; nz = -nz; }
-    const double S = __dadd_rn(__dadd_rn(a0, a1), a2);
-    if (l > 0.0 && S > 0.0) cv = __ddiv_rn(l, S);
-  }
+  double d0, d1, d2, nx, ny, nz, cv;
+  pca::row_offset(pts, idx, i, k, len, lane, px, py, pz, d0, d1, d2);
+  pca::point_normal(d0, d1, d2, len, lane, px, py, pz, vx, vy, vz, nx, ny, nz, cv);
   if (lane < 3) nrm[3 * (size_t)i + lane] = lane == 0 ? nx : lane == 1 ? ny : nz;
   if (lane == 3) curv[i] = cv;
   if (lane == 4) used[i] = len;
@@ -117,7 +56,7 @@ __global__ __launch_bounds__(VT) void normals_adopt_kernel(const double* __restr
 }  // namespace
 
 long long normals_estimate(mvicp_ctx* c, const FrameDev& f, int max_nn, double radius, double B2, const double* viewpoint) {
-  c->nrm.rows = -1; c->nrm.frame = -1;   // (the last result ends here; a failed call leaves none behind)
+  c->nrm.drop_result();   // (the last result ends here; a failed call leaves none behind)
   const long long total = knn_search(c, f, nullptr, 0, 0, max_nn, radius, B2);
   if (total < 0) return total;
   const int n = f.n;

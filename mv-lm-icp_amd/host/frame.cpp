@@ -410,19 +410,28 @@ void Frame::recomputeNormals() {
   ++version;   // a bound session re-uploads this cloud (new normals) at its next bind
 }
 
-std::vector<double> Frame::estimateNormals(int max_nn, double radius, const Vector3d& viewpoint) {
+// estimateNormals (degree 0) and fitNormals (degree 2 or 3): the call, the fetch into `nor`, the version bump
+static std::vector<double> normals_into(Frame* f, int max_nn, double radius, const Vector3d& viewpoint, int degree) {
   std::vector<double> curvature;
-  if (pts.empty()) { nor.clear(); ++version; return curvature; }
+  if (f->pts.empty()) { f->nor.clear(); ++f->version; return curvature; }
   int slot = 0;
-  mvicp_ctx* c = Session::get().query_context(this, &slot);
-  const long long n = mvicp_estimate_normals(c, slot, max_nn, radius, viewpoint.data());
+  mvicp_ctx* c = Session::get().query_context(f, &slot);
+  const long long n = degree ? mvicp_fit_normals(c, slot, max_nn, radius, viewpoint.data(), degree)
+                             : mvicp_estimate_normals(c, slot, max_nn, radius, viewpoint.data());
   if (n < 0) check((int)n);
   std::vector<Vector3d> fresh((size_t)n);
   curvature.assign((size_t)n, 0.0);
   check(mvicp_normals_fetch(c, n, fresh[0].data(), curvature.data(), nullptr));
-  nor.swap(fresh);
-  ++version;   // a bound session re-uploads this cloud (new normals) at its next bind
+  f->nor.swap(fresh);
+  ++f->version;   // a bound session re-uploads this cloud (new normals) at its next bind
   return curvature;
+}
+
+std::vector<double> Frame::estimateNormals(int max_nn, double radius, const Vector3d& viewpoint) { return normals_into(this, max_nn, radius, viewpoint, 0); }
+
+std::vector<double> Frame::fitNormals(int max_nn, double radius, int degree, const Vector3d& viewpoint) {
+  if (degree != 2 && degree != 3) throw std::runtime_error("mvicp: fitNormals needs degree 2 or 3");
+  return normals_into(this, max_nn, radius, viewpoint, degree);
 }
 
 int Frame::orientNormals(int k, double radius) {

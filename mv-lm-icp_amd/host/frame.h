@@ -11,7 +11,7 @@
 // WHAT THE MIRROR NOTICES (the one rule; INTEGRATION.md "What the mirror notices").  The device copies, the cached search and
 // the k-NN table are keyed on addresses, sizes and counters, never on the clouds' values:
 //   noticed by itself   a `pts` / `nor` vector REPLACED by another one (another buffer address or another size) on a bound and on an
-//                       unbound frame; `version` (recomputeNormals(), estimateNormals(), orientNormals() and Session::orientFrames bump it); a Frame destroyed, or destroyed and constructed again in
+//                       unbound frame; `version` (recomputeNormals(), estimateNormals(), fitNormals(), orientNormals() and Session::orientFrames bump it); a Frame destroyed, or destroyed and constructed again in
 //                       the same storage (~Frame() tells the session); another frames vector, other frames in it, another order, another
 //                       graph; changed poses / thresh / fixed / Session::nn_method; Session::copy_back switched; any call that threw
 //                       (whatever the session believed about the device copy it was uploading is forgotten before the upload starts).
@@ -74,6 +74,10 @@ class Frame {
   // the curvatures (surface variation, one per point).  Runs in the context Session::query_context finds for this frame
   // (bin/multiview --normals_nn / --normals_radius).
   std::vector<double> estimateNormals(int max_nn, double radius = 0.0, const Vector3d& viewpoint = Vector3d());
+  // Jet-fitted normals (no counterpart in the reference): mvicp_fit_normals in place of mvicp_estimate_normals -- the same normal corrected
+  // by the slope of a height polynomial of `degree` 2 or 3 fitted over its tangent plane; a point whose fit is refused keeps the estimate.
+  // Everything else is estimateNormals(): fills `nor`, bumps `version`, returns the curvatures (bin/multiview --normals_fit).
+  std::vector<double> fitNormals(int max_nn, double radius, int degree, const Vector3d& viewpoint = Vector3d());
   // Consistent orientation without a viewpoint (no counterpart in the reference): mvicp_orient_normals on this cloud and its `nor` as they
   // are stored (source 0, MVICP_ORIENT_ANCHOR) -- the sign of point 0's normal (of every tree's lowest point) is carried along the maximum
   // spanning forest of the graph of the k nearest neighbours (radius > 0: within it) weighted by |n_i . n_j|.  Replaces `nor` and bumps

@@ -46,6 +46,9 @@
 // place of the recomputeNormals step (after the outlier filter, before any coarse level): the exactly specified normals of
 // mvicp_estimate_normals over the K nearest points (3 <= K <= 64; R > 0: within R), turned towards the view's own origin -- the sensor of a
 // range image in its own frame -- so that all frames agree on the side their normals point to, which --symmetric and --init features need.
+// --normals_fit D (default 0 = off; D = 2 or 3, needs --normals_nn K): Frame::fitNormals(K, R, D) in place of Frame::estimateNormals(K, R) -- the
+// same normals corrected by the slope of a height polynomial of degree D fitted over the tangent plane (mvicp_fit_normals).  Composes with
+// --normals_orient and --symmetric.
 // --normals_orient mst [--orient_nn K] (default off; K = 10): consistent orientation WITHOUT a viewpoint, for clouds whose frame origin is no
 // sensor.  Per frame, after the normals step: Frame::orientNormals(K) (mvicp_orient_normals: the signs are carried along the maximum spanning
 // forest of the K-nearest-neighbour graph weighted by |n_i . n_j|); then once across the frames, at the start poses, after the graph is built
@@ -83,7 +86,8 @@ static void loadFrames(const Flags& F, std::vector<std::shared_ptr<Frame>>& fram
       f->pts.swap(kept->pts); f->nor.swap(kept->nor); ++f->version;   // (a context that holds the old cloud re-uploads)
       std::cout << "outlier filter: frame " << frames.size() << " kept " << f->pts.size() << " of " << before << std::endl;
     }
-    if (F.i("normals_nn", 0) > 0) f->estimateNormals(F.i("normals_nn", 0), F.f("normals_radius", 0.0));   // (viewpoint: the view's own origin)
+    if (F.i("normals_nn", 0) > 0 && F.i("normals_fit", 0)) f->fitNormals(F.i("normals_nn", 0), F.f("normals_radius", 0.0), F.i("normals_fit", 0));
+    else if (F.i("normals_nn", 0) > 0) f->estimateNormals(F.i("normals_nn", 0), F.f("normals_radius", 0.0));   // (viewpoint: the view's own origin)
     else if (F.b("recomputeNormals", true)) f->recomputeNormals();  // main_multiview.cpp:49,68-70 (default on)
     if (F.s("normals_orient", "") == "mst")
       std::cout << "normal orientation: frame " << frames.size() << " trees " << f->orientNormals(F.i("orient_nn", 10)) << std::endl;
@@ -111,6 +115,8 @@ int main(int argc, char** argv) {
   noiseStream() = F.s("noise_stream", "libstdc++") == "libc++" ? 1 : F.s("noise_stream", "libstdc++") == "g++" ? 2 : 0;
 
   if (!F.s("normals_orient", "").empty() && F.s("normals_orient", "") != "mst") { std::cerr << "--normals_orient must be mst" << std::endl; return 1; }
+  if (F.i("normals_fit", 0) != 0 && F.i("normals_fit", 0) != 2 && F.i("normals_fit", 0) != 3) { std::cerr << "--normals_fit must be 2 or 3" << std::endl; return 1; }
+  if (F.i("normals_fit", 0) != 0 && F.i("normals_nn", 0) <= 0) { std::cerr << "--normals_fit needs --normals_nn K" << std::endl; return 1; }
   std::vector<std::shared_ptr<Frame>> frames;
   try {
     loadFrames(F, frames, dir);

@@ -22,7 +22,7 @@ SYMBOLS = [
     "mvicp_overlap", "mvicp_graph_from_overlap", "mvicp_voxel_grid", "mvicp_voxel_fetch",
     "mvicp_outlier_filter", "mvicp_outlier_fetch", "mvicp_outlier_threshold", "mvicp_cache_allowance",
     "mvicp_knn_search", "mvicp_knn_fetch", "mvicp_fpfh", "mvicp_fpfh_fetch", "mvicp_iss_keypoints", "mvicp_iss_fetch",
-    "mvicp_estimate_normals", "mvicp_normals_fetch", "mvicp_normals_adopt",
+    "mvicp_estimate_normals", "mvicp_normals_fetch", "mvicp_normals_adopt", "mvicp_fit_normals", "mvicp_normals_fit_fetch",
     "mvicp_orient_normals", "mvicp_orient_fetch", "mvicp_orient_adopt", "mvicp_normal_agreement", "mvicp_signs_from_agreement", "mvicp_negate_normals",
     "mvicp_feature_match", "mvicp_feature_match_fetch", "mvicp_match_pairs", "mvicp_consensus", "mvicp_consensus_fetch",
     "mvicp_coarse_pairs", "mvicp_coarse_pairs_fetch", "mvicp_poses_from_pairs",
@@ -149,6 +149,9 @@ def load_library(path=None):
     lib.mvicp_estimate_normals.restype = C.c_longlong
     lib.mvicp_normals_fetch.argtypes = [vp, C.c_longlong, vp, vp, vp]
     lib.mvicp_normals_adopt.argtypes = [vp]
+    lib.mvicp_fit_normals.argtypes = [vp, C.c_int, C.c_int, C.c_double, dp, C.c_int]
+    lib.mvicp_fit_normals.restype = C.c_longlong
+    lib.mvicp_normals_fit_fetch.argtypes = [vp, C.c_longlong, vp]
     lib.mvicp_orient_normals.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, dp]
     lib.mvicp_orient_normals.restype = C.c_longlong
     lib.mvicp_orient_fetch.argtypes = [vp, C.c_longlong, vp, vp, vp]
@@ -848,8 +851,26 @@ class Engine:
         _check(self.lib, self.lib.mvicp_normals_fetch(self.h, n, ptr(nrm), ptr(curv), ptr(used)))
         return {"nrm": nrm, "curvature": curv, "used": used}
 
+    def fit_normals(self, frame, max_nn=16, radius=0.0, viewpoint=None, degree=3, device=False):
+        """mvicp_fit_normals + mvicp_normals_fetch + mvicp_normals_fit_fetch on the stored cloud of `frame`: the normal of estimate_normals
+        corrected by the slope of a height polynomial of `degree` 2 or 3 fitted over its tangent plane (an osculating jet) -> dict(nrm
+        (n,3) float64, curvature (n,) float64 = the PCA surface variation, used (n,) int32, fitted (n,) uint8 = 1 where the row is the fit,
+        0 where it kept the PCA estimate: fewer than 6 / 10 neighbours, or a refused factorisation).  device=True: torch tensors on the
+        engine's GPU instead of numpy arrays.  The result takes the place of the last estimate_normals: adopt_normals() and
+        orient_normals(source=1) act on it.  Afterwards the engine's last neighbour-search result is knn_search(frame, None, max_nn,
+        radius).  Needs no graph; history-neutral."""
+        vp = None if viewpoint is None else np.ascontiguousarray(viewpoint, dtype=np.float64).reshape(3)
+        n = int(_check(self.lib, self.lib.mvicp_fit_normals(self.h, int(frame), int(max_nn), float(radius), _dp(vp) if vp is not None else None,
+                                                            int(degree))))
+        mk, ptr, ready, f64, i32, i64, u8 = self._result_arrays(device)
+        nrm, curv, used, fitted = mk((n, 3), f64), mk((n,), f64), mk((n,), i32), mk((n,), u8)
+        ready()
+        _check(self.lib, self.lib.mvicp_normals_fetch(self.h, n, ptr(nrm), ptr(curv), ptr(used)))
+        _check(self.lib, self.lib.mvicp_normals_fit_fetch(self.h, n, ptr(fitted)))
+        return {"nrm": nrm, "curvature": curv, "used": used, "fitted": fitted}
+
     def adopt_normals(self):
-        """mvicp_normals_adopt: the frame of the last estimate_normals takes that result as its normals, as recompute_normals would
+        """mvicp_normals_adopt: the frame of the last estimate_normals or fit_normals takes that result as its normals, as recompute_normals would
         leave them (lists that point into the frame are re-gathered, queued evaluations are voided)."""
         _check(self.lib, self.lib.mvicp_normals_adopt(self.h))
 
