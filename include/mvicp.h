@@ -645,7 +645,7 @@ int mvicp_poses_from_pairs(int n_frames, int n_edges, const int* src, const int*
  * mvicp_correspond computes it) and B(x) = ||Rd^-1||_F (|ts| + 16 ||Rs||_F max_norm + 13 |ts - td|):
  *   *out = 2^-52 (B(x_old) + B(x_new)), and 0 iff the two transforms are bit-identical (then every query is, too).
  * It bounds the rounding of both evaluations of the fp64 query map (which rounds R p + ts at the size of ts, not of ts - td) and of
- * dM, dv themselves; the derivation is at cache_allowance_xf in csrc/api.cpp and in DESIGN.md section 3.4.
+ * dM, dv themselves; the derivation is at cache_allowance_xf in csrc/search_plan.h and in DESIGN.md section 3.4.
  * Errors: a NULL pointer, max_norm < 0 or NaN -> MVICP_ERR_ARG. */
 int mvicp_cache_allowance(const double* pose_src_old, const double* pose_dst_old, const double* pose_src, const double* pose_dst,
                           double max_norm, double* out);

@@ -169,91 +169,13 @@ void free_graph(mvicp_ctx* c) {
   if (c->d_export) (void)hipFree(c->d_export);
   if (c->h_export) (void)hipHostFree(c->h_export);
   c->d_export = nullptr; c->h_export = nullptr; c->export_cap = 0;
-  c->E = 0; c->total_cap = 0; c->n_cblocks = 0; c->n_chunks = 0; c->have_corr = false;
+  c->E = 0; c->total_cap = 0; c->n_cblocks = 0; c->n_chunks = 0; c->hist.have_corr = false;
 }
 
 int bind(mvicp_ctx* c) {
   if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
   MV_HIP(hipSetDevice(c->device));
   return MVICP_OK;
-}
-
-// smallest double x such that the correctly rounded sqrt(x) >= t  ==>  (sqrt(d2) < t)  <=>  (d2 < x)
-double sqrt_bound(double t) {
-  double x = t * t;
-  while (std::sqrt(x) >= t && x > 0.0) x = std::nextafter(x, 0.0);
-  while (std::sqrt(x) < t) x = std::nextafter(x, INFINITY);
-  return x;
-}
-
-// Eigen 3x3 inverse (cofactor form), column-major — frame.cpp:118 `dstCloud.pose.linear().inverse()`.
-void inverse3(const double* m, double* r) {
-#define M(i, j) m[(i) + 3 * (j)]
-#define COF(i, j) (M(((i) + 1) % 3, ((j) + 1) % 3) * M(((i) + 2) % 3, ((j) + 2) % 3) - M(((i) + 1) % 3, ((j) + 2) % 3) * M(((i) + 2) % 3, ((j) + 1) % 3))
-  const double c00 = COF(0, 0), c10 = COF(1, 0), c20 = COF(2, 0);
-  const double det = (c00 * M(0, 0) + c10 * M(1, 0)) + c20 * M(2, 0);
-  const double invdet = 1.0 / det;
-  r[0] = c00 * invdet; r[3] = c10 * invdet; r[6] = c20 * invdet;
-  r[1] = COF(0, 1) * invdet; r[4] = COF(1, 1) * invdet; r[7] = COF(2, 1) * invdet;
-  r[2] = COF(0, 2) * invdet; r[5] = COF(1, 2) * invdet; r[8] = COF(2, 2) * invdet;
-#undef COF
-#undef M
-}
-
-// The query transform of a directed pair src -> dst (frame.cpp:117-118,131,136), the first 24 doubles of an edge's kEdgeXf:
-// Rs(9) ts(3) Rd^-1(9) td(3), column-major.  mvicp_correspond and mvicp_overlap both build theirs here.
-void fill_query_xf(const double* Ps, const double* Pd, double* x) {
-  double Rd[9];
-  for (int j = 0; j < 3; ++j)
-    for (int i = 0; i < 3; ++i) { x[i + 3 * j] = Ps[i + 4 * j]; Rd[i + 3 * j] = Pd[i + 4 * j]; }
-  for (int i = 0; i < 3; ++i) { x[9 + i] = Ps[12 + i]; x[21 + i] = Pd[12 + i]; }
-  inverse3(Rd, x + 12);
-}
-
-// The affine form of a query transform block x (fill_query_xf): q = M p + v with M = Rd^-1 Rs (9, column-major), v = Rd^-1 (ts - td) (3).
-// The kernels never evaluate it (they run xf_point); its change between two searches is the displacement cache_eps reads.
-void query_affine(const double* x, double* Mq) {
-  for (int j = 0; j < 3; ++j)
-    for (int i = 0; i < 3; ++i) Mq[i + 3 * j] = x[12 + i] * x[0 + 3 * j] + x[12 + i + 3] * x[1 + 3 * j] + x[12 + i + 6] * x[2 + 3 * j];
-  const double dt[3] = {x[9] - x[21], x[10] - x[22], x[11] - x[23]};
-  for (int i = 0; i < 3; ++i) Mq[9 + i] = x[12 + i] * dt[0] + x[12 + i + 3] * dt[1] + x[12 + i + 6] * dt[2];
-}
-
-// The rounding allowance of the temporal cache (nn_cache.h: cache_eps adds it to |dM p + dv|): a bound on everything that separates the
-// displacement the kernel computes from the distance between the two queries the kernels really searched with.
-//
-// u = 2^-53; bounds to first order in u (the result is doubled at the end).  A block x = (R, ts, Ri, td) and a point |p| <= r define the
-// exact query q(x) = Ri (R p + ts - td) and the affine pair M(x) = Ri R, v(x) = Ri (ts - td) over the reals.  Norms of vectors are
-// Euclidean, of matrices Frobenius (|| |A| y || <= ||A||_F |y|), s_i = sum_j |R_ij||p_j|, so |s| <= ||R||_F r.
-//  (a) xf_point (nn_metric.h), per component.  The three products and two sums of R p: error <= 3 u s_i.  The sum with ts_i rounds
-//      at the size of its RESULT: u |g_i| <= u (|ts_i| + s_i).  u^_i = fl(g^_i - td_i) rounds at the size of ITS result (exact when g^_i
-//      and td_i are close, Sterbenz): u |u_i| <= u (s_i + |ts_i - td_i|).  Together |u^ - u| <= u (|ts| + 5 ||R||_F r + |ts - td|).
-//      q^ = fl(Ri u^), three products and two sums: 3 u |Ri||u^|, |u^| <= ||R||_F r + |ts - td|.  So
-//          |q^ - q| <= u ||Ri||_F (|ts| + 8 ||R||_F r + 4 |ts - td|).
-//      The leading term lives at the size of ts, NOT of v: two poses that share a large world translation (georeferenced scans) have
-//      a small v and still round g = R p + ts at |ts| — 4e-10 m at a UTM northing of 4e6 m.
-//  (b) query_affine: |M^ - M| <= 3 u |Ri||R| and |v^ - v| <= 4 u |Ri||ts - td| entrywise (the difference ts - td is rounded once, at
-//      its own size), so |(M^ - M) p + (v^ - v)| <= u ||Ri||_F (3 ||R||_F r + 4 |ts - td|).
-//  (c) the kernel's e^ = fl(dM p + dv) with dM = fl(M^_new - M^_old), dv likewise: one rounding for the difference, four through the
-//      sum, each relative to the terms and not to the (possibly cancelling) result: |e^ - e| <= 5 u (|dM||p| + |dv|) <=
-//      5 u sum over both blocks of ||Ri||_F (||R||_F r + |ts - td|).  (The norm's own roundings are relative to |e^|: cache_eps'
-//      factor 1 + 1e-9.)
-// Both searches count, each with its own block:
-//     |q^_new - q^_old| <= |e^| (1 + 1e-9) + u sum over both blocks of ||Ri||_F (|ts| + 16 ||R||_F r + 13 |ts - td|).
-// The allowance is that sum with 2 u = 2^-52: the spare factor covers the second-order terms and the roundings of the norms, of r
-// (max_norm, a rounded norm) and of this sum.  Contracted multiply-adds only remove roundings.  Blocks that are bit-identical give the
-// same queries bit for bit: 0, which the kernels read as "nothing moved"; any other pair gives a positive value.
-double cache_allowance_xf(const double* x_old, const double* x_new, double r) {
-  if (std::memcmp(x_old, x_new, sizeof(double) * kXfRigid) == 0) return 0.0;
-  double b = 0.0;
-  for (const double* x : {x_old, x_new}) {
-    double fr = 0.0, fi = 0.0;
-    for (int k = 0; k < 9; ++k) { fr += x[k] * x[k]; fi += x[12 + k] * x[12 + k]; }
-    const double dt[3] = {x[9] - x[21], x[10] - x[22], x[11] - x[23]};
-    const double ts = std::sqrt(x[9] * x[9] + x[10] * x[10] + x[11] * x[11]), dtn = std::sqrt(dt[0] * dt[0] + dt[1] * dt[1] + dt[2] * dt[2]);
-    b += std::sqrt(fi) * (ts + 16.0 * std::sqrt(fr) * r + 13.0 * dtn);
-  }
-  return std::max(0x1p-52 * b, std::numeric_limits<double>::min());
 }
 
 int ensure_pin(mvicp_ctx* c, size_t doubles) {
@@ -475,17 +397,17 @@ static void throttle_builds(mvicp_ctx* c) {
 // One device evaluation of all per-edge blocks at `poses` -> host `out` (E x 91), all-reduced over ranks.
 // (`metric` is an mvicp_metric: 0 point, 1 plane, 2 symmetric — the older entry points hand in their point_to_plane flag as 0 / 1)
 static int check_evaluable(mvicp_ctx* c, int metric) {
-  if (!c->have_corr) { set_error("no correspondences: call mvicp_correspond or mvicp_set_correspondences first"); return MVICP_ERR_STATE; }
+  if (!c->hist.have_corr) { set_error("no correspondences: call mvicp_correspond or mvicp_set_correspondences first"); return MVICP_ERR_STATE; }
   if (metric == MVICP_METRIC_SYMMETRIC) {
     // the mean normal needs both: the destination's (baked into the operand stream) and the source's (read from its sorted normals)
     for (int e = 0; e < c->E; ++e)
-      if (c->owned[e] && c->h_count[e] > 0) {
+      if (c->owned[e] && c->hist.h_count[e] > 0) {
         const int missing = c->frames[c->edst[e]].grid.snor == nullptr ? c->edst[e] : c->frames[c->esrc[e]].grid.snor == nullptr ? c->esrc[e] : -1;
         if (missing >= 0) { set_error("symmetric needs normals on frame %d", missing); return MVICP_ERR_STATE; }
       }
   } else if (metric) {
     for (int e = 0; e < c->E; ++e)
-      if (c->owned[e] && c->h_count[e] > 0 && c->frames[c->edst[e]].grid.snor == nullptr) {
+      if (c->owned[e] && c->hist.h_count[e] > 0 && c->frames[c->edst[e]].grid.snor == nullptr) {
         set_error("point-to-plane needs normals on frame %d", c->edst[e]);
         return MVICP_ERR_STATE;
       }
@@ -547,12 +469,12 @@ int evaluate_blocks(mvicp_ctx* c, const double* poses, int plane, int robust, do
         std::memcmp(poses, c->spec2_poses.data(), sizeof(double) * c->spec2_poses.size()) == 0) {
       std::memcpy(out, c->h_pin + c->pin_spec2_off, sizeof(double) * n);
       if (c->profile) c->prof["spec2.hit"].launches += 1;
-      c->last_cand_poses.assign(poses, poses + 16 * (size_t)c->n_frames); c->last_cand_plane = plane; c->last_cand_robust = robust;
+      c->hist.last_cand_poses.assign(poses, poses + 16 * (size_t)c->n_frames); c->hist.last_cand_plane = plane; c->hist.last_cand_robust = robust;
       return MVICP_OK;
     }
   }
   // (an evaluation beyond the solve's first: what the next solve's candidate evaluation will most likely be asked at, if the poses do not move)
-  c->last_cand_poses.assign(poses, poses + 16 * (size_t)c->n_frames); c->last_cand_plane = plane; c->last_cand_robust = robust;
+  c->hist.last_cand_poses.assign(poses, poses + 16 * (size_t)c->n_frames); c->hist.last_cand_plane = plane; c->hist.last_cand_robust = robust;
   double* h = c->h_pin + c->pin_blocks_off;
   if (exchange) {
     // One collective per evaluation: [E x 91 blocks | poison slot].  The slot right behind the blocks (the buffer's tail region, rewritten
@@ -867,7 +789,7 @@ static int normals_changed(mvicp_ctx* c, int frame, int st) {
     bool any = false;
     std::vector<int> dirty(c->E, 0);
     for (int e = 0; e < c->E; ++e)
-      if (c->owned[e] && c->edst[e] == frame) { c->list_valid[e] = 0; if (c->have_corr && c->h_count[e] > 0) { dirty[e] = 1; any = true; } }
+      if (c->owned[e] && c->edst[e] == frame) { c->hist.list_valid[e] = 0; if (c->hist.have_corr && c->hist.h_count[e] > 0) { dirty[e] = 1; any = true; } }
     if (any) {
       MV_HIP(hipMemcpy(c->d_dirty, dirty.data(), sizeof(int) * c->E, hipMemcpyHostToDevice));
       MV_CHECK(launch_gather_stream(c));
@@ -1280,7 +1202,7 @@ int mvicp_normal_agreement(mvicp_ctx* c, const double* poses, int* pos, int* neg
   MV_CHECK(bind(c));
   MV_CHECK(check_evaluable(c, MVICP_METRIC_SYMMETRIC));
   std::vector<char> use((size_t)c->E, 0);
-  for (int e = 0; e < c->E; ++e) use[e] = c->owned[e] && c->h_count[e] > 0 && !((int)c->src_fixed.size() == c->E && c->src_fixed[e]);
+  for (int e = 0; e < c->E; ++e) use[e] = c->owned[e] && c->hist.h_count[e] > 0 && !((int)c->src_fixed.size() == c->E && c->src_fixed[e]);
   const int st = normal_agreement(c, poses, use.data(), pos, neg);
   if (c->profile) prof_collect_lazy(c);
   return st;
@@ -1617,8 +1539,7 @@ int mvicp_set_graph(mvicp_ctx* c, int n_edges, const int* src, const int* dst) t
   c->owned.assign(E, 0);
   c->active.assign(E, 0);
   c->src_fixed.assign(E, 0);
-  c->h_count.assign(E, 0);
-  c->h_weight.assign(E, 0.f);
+  c->hist.new_graph(E);   // every per-edge row of the search history: the new graph's size, describing no search
   // contiguous edge chunks balanced by N_src
   {
     std::vector<int> ns(E), owner(E);
@@ -1681,17 +1602,14 @@ int mvicp_set_graph(mvicp_ctx* c, int n_edges, const int* src, const int* dst) t
   MV_HIP(hipMemset(c->d_ctl, 0, sizeof(double) * std::max<size_t>(c->ctl_r2_off + c->ctl_r2, 1)));
   c->d_xf = c->d_ctl; c->d_nsrc = reinterpret_cast<int*>(c->d_ctl + (size_t)E * kEdgeXf); c->d_dirty = c->d_nsrc + E;
   c->d_sel_lohi = c->d_ctl + (size_t)E * (kEdgeXf + 1);
-  c->sel_med1.assign(E, -1.0); c->sel_med2.assign(E, -1.0);
   c->d_rel = c->d_ctl + c->ctl_r2_off; c->d_a = c->d_rel + (size_t)E * kEdgeRel; c->d_rel2 = c->d_ctl + c->ctl_rel2_off;
   MV_CHECK(dev_alloc(&c->d_nn_idx, cap)); MV_CHECK(dev_alloc(&c->d_nn_d2, cap)); MV_CHECK(dev_alloc(&c->d_nn_lb, cap));
-  c->nn_cache_valid = false; c->prev_q.assign((size_t)E * 12, 0.0); c->nn_cache_edge.assign(E, 0);
-  c->auto_prev_dist = 0.0; c->auto_last_method = -1; c->corr_tie_seen = c->corr_far_seen = 1u;
   MV_CHECK(dev_alloc(&c->d_first, cap)); MV_CHECK(dev_alloc(&c->d_second, cap)); MV_CHECK(dev_alloc(&c->d_cd2, cap));
   MV_CHECK(dev_alloc(&c->d_stream, 10 * cap));
   MV_CHECK(dev_alloc(&c->d_qpos, cap));
   MV_HIP(hipMemset(c->d_qpos, 0xff, sizeof(int) * std::max<size_t>(cap, 1)));
-  c->list_valid.assign(E, 0); c->explicit_list.assign(E, 0); c->export_valid = false; c->export_off.assign((size_t)E + 1, 0);
-  c->qpos_valid.assign(E, 0); c->corr_epoch.assign(E, 0);
+  c->export_valid = false; c->export_off.assign((size_t)E + 1, 0);
+  c->corr_epoch.assign(E, 0);
   for (int e = 0; e < E; ++e) c->corr_epoch[e] = ++c->epoch_counter;
   c->dslot_off.assign(E + 1, 0);
   for (int e = 0; e < E; ++e) c->dslot_off[e + 1] = c->dslot_off[e] + (int)(((c->owned[e] ? c->frames[src[e]].n : 0) + 255) / 256);
@@ -1702,7 +1620,7 @@ int mvicp_set_graph(mvicp_ctx* c, int n_edges, const int* src, const int* dst) t
   MV_CHECK(dev_alloc(&c->d_cblock_off, E + 1)); MV_CHECK(dev_alloc(&c->d_cblock_cnt, (size_t)c->n_cblocks));
   MV_CHECK(dev_alloc(&c->d_sel_hist, (size_t)E * (2048 + 2)));   // cnt_lt [E] | cnt_mid [E] | hist [E][2048] (corr.hip); zeroed here, kept zero by the select kernels
   MV_HIP(hipMemset(c->d_sel_hist, 0, sizeof(unsigned int) * std::max<size_t>((size_t)E * (2048 + 2), 1)));
-  c->sel_scratch_clean = true; c->sel_result_valid = false; c->sel_result_armed = false;
+  c->sel_scratch_clean = true;
   c->sblock_off.assign(E + 1, 0);
   for (int e = 0; e < E; ++e) c->sblock_off[e + 1] = c->sblock_off[e] + (int)(((c->owned[e] ? c->frames[src[e]].n : 0) + kSelBlock - 1) / kSelBlock);
   c->n_sblocks = c->sblock_off[E];
@@ -1718,7 +1636,7 @@ int mvicp_set_graph(mvicp_ctx* c, int n_edges, const int* src, const int* dst) t
     c->far_cap = cap;
   }
   MV_CHECK(warm_nn_grid(c)); MV_CHECK(warm_nn_tile(c)); MV_CHECK(warm_nn_mfma(c));
-  if (c->tie_rule && !(c->tie_lazy && c->world == 1)) {   // the reference's own trees over the targets of the edges THIS RANK owns: they decide exact distance ties (the others are never searched here)
+  if (c->opt.tie_rule && !(c->opt.tie_lazy && c->world == 1)) {   // the reference's own trees over the targets of the edges THIS RANK owns: they decide exact distance ties (the others are never searched here)
     std::vector<int> need;
     for (int e = 0; e < E; ++e) if (c->owned[e]) need.push_back(dst[e]);
     MV_CHECK(ensure_tie_trees(c, need));
@@ -1763,30 +1681,18 @@ int mvicp_set_graph(mvicp_ctx* c, int n_edges, const int* src, const int* dst) t
     c->d_blocks2_host = (double*)dp + c->pin_blocks2_off;
   }
   c->spec_ready = false; c->spec_arm = false;
-  c->spec2_ready = false; c->spec2_armed = false; c->last_cand_poses.clear();
-  c->prev_xf.assign((size_t)E * kXfRigid, 0.0);
+  c->spec2_ready = false; c->spec2_armed = false;
   if (!c->h_census) MV_HIP(hipHostMalloc((void**)&c->h_census, 8 * sizeof(unsigned long long), hipHostMallocDefault));
   return MVICP_OK;
 } MVICP_GUARD_ABI
 
-// everything earlier searches left behind (host-side bookkeeping only)
+// everything earlier searches left behind (host-side bookkeeping only): the history, and what of it the context mirrors
 static void forget_history(mvicp_ctx* c) {
-  const int E = c->E;
-  c->nn_cache_valid = false; c->nn_cache_thresh = -1.f;
-  c->prev_q.assign((size_t)E * 12, 0.0); c->prev_xf.assign((size_t)E * kXfRigid, 0.0);
-  c->nn_cache_edge.assign(E, 0);                      // no seeds, no temporal cache: d_nn_idx / d_nn_lb are dead until the next search rewrites them
-  c->auto_prev_dist = 0.0; c->auto_last_method = -1; c->last_rms = -1.0; c->prev_grid_kernel = false;
-  c->corr_tie_seen = c->corr_far_seen = 1u;
-  c->list_valid.assign(E, 0);                          // every list is re-compacted and re-gathered
+  c->hist.forget(c->E);
   c->export_valid = false;
-  c->qpos_valid.assign(E, 0);
-  for (int e = 0; e < E; ++e) c->corr_epoch[e] = ++c->epoch_counter;
-  c->sel_med1.assign(E, -1.0); c->sel_med2.assign(E, -1.0);
-  c->sel_result_valid = false;
-  c->spec_ready = false; c->spec_arm = false; c->spec_flags_valid = false;
-  c->spec2_ready = false; c->spec2_armed = false; c->last_cand_poses.clear();
-  c->have_corr = false;
-  std::fill(c->h_count.begin(), c->h_count.end(), 0); std::fill(c->h_weight.begin(), c->h_weight.end(), 0.f);
+  for (int e = 0; e < c->E; ++e) c->corr_epoch[e] = ++c->epoch_counter;
+  c->spec_ready = false; c->spec_arm = false;
+  c->spec2_ready = false; c->spec2_armed = false;
 }
 
 int mvicp_reset_history(mvicp_ctx* c) try {
@@ -1796,27 +1702,7 @@ int mvicp_reset_history(mvicp_ctx* c) try {
   return MVICP_OK;
 } MVICP_GUARD_ABI
 
-// mvicp_correspond — cross-round state at a glance.  A search is a PURE FUNCTION of (clouds, graph, poses, fixed mask, cutoff): every field below
-// only decides HOW FAST the same answer is found, and tests/test_gpu_parity.py::test_correspond_regime_transitions_match_a_fresh_context checks
-// after every round of randomly perturbed registrations that the answer equals a fresh context's.  mvicp_reset_history, a search that does not
-// return OK (mvicp_correspond's Forget guard: every error return below, an exception, a poisoned exchange) and a change of the "tie_rule" option
-// (forget_history) drop all of it — "reset" in the last column stands for all three (tests/test_gpu_search_state.py).
-//   field (common.h)              written by                               read by / meaning                                    invalidated by
-//   nn_cache_valid, _thresh       this call's end (grid / BND tile round)  temporal cache may be consulted next search          cutoff change, set_correspondences, options, reset
-//   nn_cache_edge[e]              this call's end (= active mask)          edge e was searched last time: seeds + bounds usable   fixed-mask change (per edge), reset
-//   prev_q / prev_xf[e]           the per-edge loop below                  dM, dv of the temporal cache; bit-identical transform  every search rewrites them; a search that does not return OK, reset
-//   list_valid[e], explicit_list  end of the NN stage / set_correspondences  the edge's compacted list may be maintained in place  set_correspondences, recompute_normals (dst), reset
-//   sel_med1/2[e]                 after the wait below                     one-pass bracket select once the median has settled   inactive edge, set_correspondences, reset
-//   sel_result_valid, _armed      this call's end (single rank)            no select launch in a search in which no list can change   any search that does not return OK, set_graph, set_correspondences, reset
-//   auto_prev_dist, auto_last_method   the AUTO policy block               hand-over tile -> grid, "already handed over"          set_graph, reset
-//   corr_tie_seen, corr_far_seen  after the wait below (own launches only) tie fix-up / far launch may be skipped at a fixed point  any search that is not bit-identical; reset
-//   prev_grid_kernel              end of the NN stage                      corr_far_seen describes the last search                every search rewrites it
-//   spec_flags_valid, spec_param/plane/robust   mvicp_optimize             arm the queued first evaluation of the NEXT solve      failed solve / search, spec_eval option, reset
-//   spec_ready, spec_poses        end of this call                         evaluate_blocks may serve the first evaluation from it  consumed by the next evaluation, any list change
-//   last_rms                      mvicp_optimize                           nn_cell policy only                                    consumed here
-//   export_valid                  ensure_export                            h_export holds the lists as they are on the device     every search that can change a list, set_correspondences, reset
-//   qpos_valid[e]                 end of the NN stage                      d_qpos / second / cd2 = the last search's result (export)  set_correspondences, failed search, reset
-//   corr_epoch[e]                 end of this call                         callers skip copying a list whose epoch they hold      bumped unless the edge's inputs are bit-identical to last search's
+// mvicp_correspond: the policy, its options and the table of the cross-round state are csrc/search_plan.h; what follows executes a plan.
 static int correspond_once(mvicp_ctx* c, const double* poses, const unsigned char* fixed, float thresh, int nn_method, int* counts, float* weights, bool* tie_unresolved);
 
 int mvicp_correspond(mvicp_ctx* c, const double* poses, const unsigned char* fixed, float thresh, int nn_method, int* counts, float* weights) try {
@@ -1844,315 +1730,202 @@ int mvicp_correspond(mvicp_ctx* c, const double* poses, const unsigned char* fix
   return MVICP_OK;
 } MVICP_GUARD_ABI
 
-static int correspond_body(mvicp_ctx* c, const double* poses, const unsigned char* fixed, float thresh, int nn_method, int* counts, float* weights, bool* tie_unresolved);
+// ---- the executor: builds the inputs, asks search_plan.h for the plan, then uploads, launches, exchanges and waits as the plan says ----
+
+namespace {
+struct CorrMarks {   // the host.corr.* profile scopes: each mark closes the interval since the one before
+  mvicp_ctx* c; double t;
+  void operator()(const char* nm) { if (c->profile) { const double now = now_ms(); ProfEntry& pe = c->prof[nm]; pe.ms += now - t; pe.launches += 1; t = now; } }
+};
+// the exchanged / pinned result buffer: E x 91 blocks | (count, median d2) x E | armed | a x E
+size_t out_blocks(const mvicp_ctx* c) { return (size_t)c->E * MVICP_EDGE_BLOCK; }
+size_t out_tail(const mvicp_ctx* c) { return 3 * (size_t)c->E + 1; }
+size_t out_armed(const mvicp_ctx* c) { return out_blocks(c) + 2 * (size_t)c->E; }
+void spec_failed(mvicp_ctx* c) { c->hist.spec_flags_valid = false; c->spec_arm = false; }
+}  // namespace
+
+// what a search is a function of (search_plan.h), read off the context
+static SearchInputs search_inputs(mvicp_ctx* c, const double* poses, const unsigned char* fixed, float thresh, int nn_method) {
+  c->plan_frames.resize(c->frames.size());
+  for (size_t k = 0; k < c->frames.size(); ++k) {
+    const FrameDev& f = c->frames[k];
+    PlanFrame& pf = c->plan_frames[k];
+    pf.n = f.n; pf.max_norm = f.max_norm; pf.cell = f.grid.cell; pf.has_grid = f.has_grid; pf.has_tie = f.has_tie; pf.has_snor = f.grid.snor != nullptr;
+  }
+  SearchInputs in;
+  in.E = c->E; in.n_frames = c->n_frames;
+  in.esrc = c->esrc.data(); in.edst = c->edst.data(); in.owned = c->owned.data(); in.frames = c->plan_frames.data();
+  in.poses = poses; in.fixed = fixed; in.thresh = thresh; in.nn_method = nn_method;
+  in.exchange = c->comm != nullptr || c->ar_fn != nullptr; in.world = c->world;
+  return in;
+}
+
+// The poses of the queued evaluations, staged behind region 1 of the control-block mirror.  -> how many doubles of it go up with the search
+static size_t stage_queued_evaluations(mvicp_ctx* c, const SearchPlan& plan, const double* poses) {
+  if (!plan.spec_arm) return c->ctl_r1;
+  // the solve evaluates at x_to_pose(pose_to_x(P)) (host/lm.cpp): the same round trip here, so the poses match bit for bit.  The
+  // relative transforms of that evaluation ride on the control-block upload (region 2 follows region 1; the SoftLOne scales
+  // behind them are written on the device by the select kernels later in the stream)
+  c->spec_poses.resize(16 * (size_t)c->n_frames);
+  double xp[7];
+  for (int k = 0; k < c->n_frames; ++k) { se3::pose_to_x(c->hist.spec_param, poses + 16 * (size_t)k, xp); se3::x_to_pose(c->hist.spec_param, xp, &c->spec_poses[16 * (size_t)k]); }
+  fill_rel(c, c->spec_poses.data());
+  c->spec_q_plane = c->hist.spec_plane; c->spec_q_robust = c->hist.spec_robust;
+  // paired launch (option lin_pair): its relative transforms lie between region 1 and rel, so they ride on the same upload
+  if (plan.spec2_plan && c->opt.lin_pair) fill_rel_into(c, c->hist.last_cand_poses.data(), c->h_pin + c->ctl_rel2_off);
+  return c->ctl_r2_off + (size_t)c->E * kEdgeRel;
+}
+
+// The local launches of a search: control-block upload, the NN kernel of the plan, list maintenance, the select
+static int launch_local_search(mvicp_ctx* c, const SearchInputs& in, const SearchPlan& plan, double bound, size_t upload_doubles, CorrMarks& mark) {
+  MV_HIP(hipMemcpyAsync(c->d_ctl, c->h_pin, sizeof(double) * upload_doubles, hipMemcpyHostToDevice, c->stream));
+  if (c->fault_inject > 0 && --c->fault_inject == 0) { set_error("injected launch failure (option fault_inject)"); return MVICP_ERR_HIP; }   // tests: a local failure before the exchange
+  if (plan.method == MVICP_NN_BRUTE) MV_CHECK(launch_nn_brute_edges(c));
+  else if (plan.method == MVICP_NN_GRID) MV_CHECK(launch_nn_grid_edges(c, bound, plan));
+  else {
+    if (c->profile && plan.eps_over_mu >= 0.0) { ProfEntry& pe = c->prof["auto.eps_over_mu"]; pe.ms = plan.eps_over_mu; pe.launches += 1; }   // (observable: the last cache-aware round's ratio)
+    MV_CHECK(launch_nn_tile_edges(c, bound, plan));
+  }
+  record_queued(in, c->opt, plan, c->hist);
+  if (!plan.all_unchanged) c->export_valid = false;   // (a search that reproduces every list leaves the exported copy what it is)
+  mark("host.corr.nn_launch");
+  if (!plan.nothing_can_change) {
+    MV_CHECK(launch_compact(c, bound));
+    MV_CHECK(launch_gather_stream(c));
+  }
+  if (plan.sel_skip) { c->h_pin[c->pin_res_off + 2 * (size_t)c->E] = plan.spec_arm ? 1.0 : 0.0; return MVICP_OK; }   // (nothing on the device writes the mapped results in this search)
+  return plan.use_bracket ? launch_select_bracket(c) : launch_select_median(c, bound);
+}
+
+// This rank's share of the exchanged buffer (N > 1 ranks): the queued first evaluation, or zeros
+static int queue_exchanged_evaluation(mvicp_ctx* c, const SearchPlan& plan) {
+  c->lin_out = c->d_out;
+  if (plan.spec_arm) return launch_linearize(c, c->spec_q_plane, c->spec_q_robust);
+  // this rank queued no evaluation: its share of the block region and of the scale slots is ZERO, not whatever the last exchange left
+  // there (already-summed values would be summed again round after round).  Every rank sends the same buffer size whatever it decided.
+  if (hipMemsetAsync(c->d_out, 0, sizeof(double) * out_blocks(c), c->stream) != hipSuccess ||
+      hipMemsetAsync(c->d_out + out_armed(c) + 1, 0, sizeof(double) * (size_t)c->E, c->stream) != hipSuccess) { set_error("hipMemsetAsync of the exchange buffer failed"); return MVICP_ERR_HIP; }
+  return MVICP_OK;
+}
+
+// The queued evaluations of a single rank (the plan armed): one, or at a fixed point two — paired in one launch or as two launches
+static int queue_evaluations(mvicp_ctx* c, const SearchPlan& plan) {
+  auto second_armed = [c]() { c->spec2_armed = true; c->spec2_poses = c->hist.last_cand_poses; c->spec2_plane = c->spec_q_plane; c->spec2_robust = c->spec_q_robust; };
+  c->spec2_armed = false;
+  if (plan.spec2_plan && c->opt.lin_pair) {
+    // both queued evaluations in one pass over the operand stream: first blocks -> d_spec_host, second -> d_spec2_host
+    const int st = launch_linearize_pair(c, c->spec_q_plane, c->spec_q_robust, c->d_spec_host, c->d_spec2_host);
+    if (st == MVICP_OK) second_armed();
+    return st;
+  }
+  c->lin_out = c->d_spec_host;
+  int st = launch_linearize(c, c->spec_q_plane, c->spec_q_robust);
+  if (st == MVICP_OK && plan.spec2_plan) {
+    fill_rel_into(c, c->hist.last_cand_poses.data(), c->h_pin + c->pin_rel2_off);
+    if (hipMemcpyAsync(c->d_rel, c->h_pin + c->pin_rel2_off, sizeof(double) * (size_t)c->E * kEdgeRel, hipMemcpyHostToDevice, c->stream) == hipSuccess) {
+      c->lin_out = c->d_spec2_host;
+      st = launch_linearize(c, c->spec_q_plane, c->spec_q_robust);
+      if (st == MVICP_OK) second_armed();
+    }
+  }
+  return st;
+}
+
+// One collective of a search: d_out[off, off + len) summed over the ranks, then copied to its pinned mirror (`what` names it in the error).
+// Failure semantics with N > 1 ranks.  A rank that failed locally before the collective (an allocation, an upload, a
+// launch) used to return at once — and its peers blocked in the collective forever.  Now every local step up to the exchange only records
+// its status (st_local); a rank whose share cannot be delivered still ENTERS the collective, with the "armed" slot of the exchanged buffer
+// poisoned (eight 0xFF bytes = a NaN): the sum is NaN on every rank, every rank sees it after its own wait, drops its cross-round state and
+// returns an error from this same call — the failing rank its own status (its message kept in local_msg), the others MVICP_ERR_COMM.  (A
+// device that no longer executes anything cannot poison or exchange: that stays fatal for the job, as any collective library has it; then
+// *entered is false and the caller returns st_local.)
+static int exchange_out(mvicp_ctx* c, size_t off, size_t len, const char* what, int st_local, char* local_msg, bool* entered) {
+  *entered = true;
+  if (st_local != MVICP_OK) {
+    std::memcpy(local_msg, g_err, sizeof(g_err));
+    if (hipMemsetAsync(c->d_out + out_armed(c), 0xFF, sizeof(double), c->stream) != hipSuccess) {
+      if (off == 0) set_error("%s — and the exchange buffer could not be poisoned: the peers of this rank will block in the collective", local_msg);
+      *entered = false;
+      return st_local;
+    }
+  }
+  int st;
+  { ProfScope pc(c, "comm", 8.0 * (double)len); st = comm_allreduce_sum(c, c->d_out + off, len); }
+  if (st == MVICP_OK && hipMemcpyAsync(c->h_pin + c->pin_spec_off + off, c->d_out + off, sizeof(double) * len, hipMemcpyDeviceToHost, c->stream) != hipSuccess) {
+    set_error("hipMemcpyAsync of the exchanged %s failed", what); st = MVICP_ERR_HIP;
+  }
+  return st;
+}
+
+// A median left its bracket (flagged -1 in its slot): with N > 1 ranks every rank sees the summed slots, so every rank takes the same
+// decision: full select for everything (rare once the registration has settled) and a second, tail-only exchange
+static int redo_select(mvicp_ctx* c, double bound, bool exchange, char* local_msg) {
+  int st = launch_select_median(c, bound);
+  if (exchange) {
+    const int st_r = st;
+    bool entered;
+    st = exchange_out(c, out_blocks(c), out_tail(c), "tail", st_r, local_msg, &entered);
+    if (!entered) { spec_failed(c); return st_r; }
+    if (st == MVICP_OK) st = stream_wait(c);
+    if (st != MVICP_OK) { spec_failed(c); return st; }
+    if (std::isnan(c->h_pin[c->pin_spec_off + out_armed(c)])) {
+      forget_history(c);
+      if (st_r != MVICP_OK) { set_error("%s", local_msg); return st_r; }
+      set_error("a peer rank failed before the second exchange of this search (poisoned exchange buffer); cross-round state dropped on every rank");
+      return MVICP_ERR_COMM;
+    }
+    return MVICP_OK;
+  }
+  if (st == MVICP_OK) st = stream_wait(c);
+  if (st != MVICP_OK) spec_failed(c);
+  return st;
+}
 
 static int correspond_once(mvicp_ctx* c, const double* poses, const unsigned char* fixed, float thresh, int nn_method, int* counts, float* weights, bool* tie_unresolved) {
   // whatever way a search ends other than OK (an error status, an exception): the next one neither reuses its select result nor trusts the
   // self-cleaning select scratch (a kernel that never ran has not re-zeroed what its predecessor filled)
-  struct Guard { mvicp_ctx* c; bool ok = false; ~Guard() { if (!ok) { c->sel_result_valid = false; c->sel_scratch_clean = false; } } } guard{c};
-  const int st = correspond_body(c, poses, fixed, thresh, nn_method, counts, weights, tie_unresolved);
-  guard.ok = st == MVICP_OK;
-  return st;
-}
-
-static int correspond_body(mvicp_ctx* c, const double* poses, const unsigned char* fixed, float thresh, int nn_method, int* counts, float* weights, bool* tie_unresolved) {
+  struct Guard { mvicp_ctx* c; bool ok = false; ~Guard() { if (!ok) { c->hist.sel_result_valid = false; c->sel_scratch_clean = false; } } } guard{c};
   if (!poses) { set_error("poses is null"); return MVICP_ERR_ARG; }
   if (c->E == 0) { set_error("no graph: call mvicp_set_graph first"); return MVICP_ERR_STATE; }
   const int E = c->E;
   HostScope hs_all(c, "host.correspond");
-  // per-edge query transforms (frame.cpp:117-118,131,136) + active mask (frame.cpp:93)
-  std::vector<int> nsrc(E, 0);
-  std::vector<char> same_edge(E, 0);   // the edge's query transform is bit-identical to last search's (and the temporal cache is on for it)
-  // the edge's list after this search IS last search's, bit for bit: a search is a pure function of (clouds, transform, cutoff), and all three are
-  // last search's — whichever kernel runs.  Such an edge keeps its epoch (mvicp_correspondence_epochs), and if every edge does, the export too.
-  std::vector<char> unchanged(E, 0);
-  const bool hist_ok = c->have_corr && (int)c->nn_cache_edge.size() == E && c->nn_cache_thresh == thresh && (int)c->qpos_valid.size() == E;
-  std::vector<double> eps_ratio;       // per active edge: displacement bound of its queries since the last search / guard band mu
-  bool same_active_set = (int)c->nn_cache_edge.size() == E;   // the set of searched edges is last search's (a changed `fixed` mask changes it)
-  double* hx = c->h_pin;
-  for (int e = 0; e < E; ++e) {
-    c->active[e] = c->owned[e] && !(fixed && fixed[c->esrc[e]]);
-    c->src_fixed[e] = fixed && fixed[c->esrc[e]];
-    if (same_active_set && (c->active[e] != 0) != (c->nn_cache_edge[e] != 0)) same_active_set = false;
-    nsrc[e] = c->active[e] ? c->frames[c->esrc[e]].n : 0;
-    const double* Ps = poses + 16 * (size_t)c->esrc[e];
-    const double* Pd = poses + 16 * (size_t)c->edst[e];
-    double* x = hx + (size_t)e * kEdgeXf;
-    fill_query_xf(Ps, Pd, x);
-    // temporal cache: q = M p + v with M = Rd^-1 Rs, v = Rd^-1 (ts - td).  Between two searches every query of the edge
-    // moves by at most ||dM||_F max|p| + |dv|  (+ the rounding allowance of cache_allowance_xf).
-    double Mq[12];
-    query_affine(x, Mq);
-    double* pq = &c->prev_q[(size_t)e * 12];
-    for (int k = 0; k < 12; ++k) x[kXfDM + k] = Mq[k] - pq[k];
-    const double rmax = c->frames[c->esrc[e]].max_norm;
-    if (c->active[e]) {
-      // how far this edge's queries can have moved since the last search, in units of the bounds-leaving builds' guard band: what decides the
-      // temporal-cache hit rate of a cache-aware round before it runs (a hit needs d_new < d_old + mu - eps)
-      double fro = 0.0;
-      for (int k = 0; k < 9; ++k) fro += x[kXfDM + k] * x[kXfDM + k];
-      const double eps_e = std::sqrt(fro) * rmax + std::sqrt(x[kXfDv] * x[kXfDv] + x[kXfDv + 1] * x[kXfDv + 1] + x[kXfDv + 2] * x[kXfDv + 2]);
-      const double mu_e = c->tile_mu * c->frames[c->edst[e]].grid.cell;
-      eps_ratio.push_back(mu_e > 0.0 ? eps_e / mu_e : 1e300);
-    }
-    const bool cache_on = c->nn_cache_valid && c->nn_cache_enable && c->active[e] && (int)c->nn_cache_edge.size() == E && c->nn_cache_edge[e] &&
-                          c->nn_cache_thresh == thresh;
-    // allowance for the rounding of the fp64 query map itself (both evaluations) and of dM, dv: cache_allowance_xf.
-    // A transform that is BIT-IDENTICAL to last search's (a converged registration: the LM ends without stepping) reproduces every
-    // query bit for bit: no allowance, and dM = dv = 0 below, so the kernel sees eps == 0 and re-verifies without rewriting anything.
-    double* pxf = &c->prev_xf[(size_t)e * kXfRigid];
-    if (!c->owned[e]) unchanged[e] = 1;   // (another rank's edge: nothing of it lives here)
-    else if (c->active[e]) unchanged[e] = hist_ok && c->nn_cache_edge[e] && c->qpos_valid[e] && !c->explicit_list[e] && std::memcmp(pxf, x, sizeof(double) * kXfRigid) == 0;
-    else unchanged[e] = hist_ok && !c->nn_cache_edge[e] && !c->explicit_list[e] && c->h_count[e] == 0;   // not searched now, not searched then: stays empty
-    const bool same_xf = cache_on && std::memcmp(pxf, x, sizeof(double) * kXfRigid) == 0;
-    x[kXfCache] = cache_on ? cache_allowance_xf(pxf, x, rmax) : -1.0;
-    same_edge[e] = same_xf;
-    std::memcpy(pxf, x, sizeof(double) * kXfRigid);
-    for (int k = kXfPad; k < kEdgeXf; ++k) x[k] = 0.0;
-    std::memcpy(pq, Mq, sizeof(Mq));
-  }
-  // region 1 of the control block (xf | nsrc | dirty) goes up in ONE copy once the dirty flags are known (below)
-  int* hn = reinterpret_cast<int*>(hx + (size_t)E * kEdgeXf);
-  int* hd = hn + E;
-  std::memcpy(hn, nsrc.data(), sizeof(int) * E);
-
-  // Failure semantics with N > 1 ranks.  A search has ONE collective; a rank that failed locally before it (an allocation,
-  // an upload, a launch) used to return at once — and its peers blocked in the collective forever.  Now every local step up to the exchange
-  // only records its status (st_local); a rank whose share cannot be delivered still ENTERS the collective, with the "armed" slot of the
-  // exchanged buffer poisoned (NaN): the sum is NaN on every rank, every rank sees it after its own wait, drops its cross-round state and
-  // returns an error from this same call — the failing rank its own status, the others MVICP_ERR_COMM.  (A device that no longer executes
-  // anything cannot poison or exchange: that stays fatal for the job, as any collective library has it.)
+  CorrMarks mark{c, now_ms()};
+  // the plan.  Region 1 of the control block (xf | nsrc | dirty | select brackets) is planned straight into its pinned mirror and goes up in ONE copy
+  const SearchInputs in = search_inputs(c, poses, fixed, thresh, nn_method);
+  SearchPlan& plan = c->plan;
+  plan.active = c->active.data(); plan.src_fixed = c->src_fixed.data();
+  plan.xf = c->h_pin; plan.nsrc = reinterpret_cast<int*>(c->h_pin + (size_t)E * kEdgeXf); plan.dirty = plan.nsrc + E; plan.lohi = c->h_pin + (size_t)E * (kEdgeXf + 1);
+  plan_search(in, c->opt, c->hist, plan);
+  // every local step up to the exchange only records its status: see exchange_out
   int st_local = MVICP_OK;
-  if (c->tie_rule && !(c->tie_lazy && c->world == 1)) {   // a cloud uploaded after mvicp_set_graph has no tree yet (the reference builds its index lazily as well, frame.cpp:188-193)
-    std::vector<int> need;
-    for (int e = 0; e < E; ++e) if (c->active[e] && !c->frames[c->edst[e]].has_tie) need.push_back(c->edst[e]);
-    if (!need.empty()) st_local = ensure_tie_trees(c, need);
-  }
+  if (!plan.tie_need.empty()) st_local = ensure_tie_trees(c, plan.tie_need);
   const double bound = sqrt_bound((double)thresh);
-  double t_mark = now_ms();
-  auto mark = [&](const char* nm) { if (c->profile) { const double t = now_ms(); ProfEntry& pe = c->prof[nm]; pe.ms += t - t_mark; pe.launches += 1; t_mark = t; } };
   mark("host.corr.setup");
-  int method = nn_method;
-  if (method == MVICP_NN_AUTO) {
-    // Two exact kernels, two regimes.  While the poses still move by more than the spacing of the points, nearly every
-    // query needs a fresh search and the wave-cooperative tile kernel (seeded with last round's neighbours) is fastest.
-    // Once the registration settles, the hash-grid kernel wins: its temporal cache answers a query whose neighbour provably
-    // did not change with one distance evaluation.  The switch costs one uncached grid round, so it is made when the
-    // median correspondence distance has stopped contracting (last > half of the one before) — or, with a single round
-    // of history, when it is already well inside a hash cell.
-    method = MVICP_NN_TILE;
-    if (c->have_corr) {
-      double dist = 0.0, cell = 0.0;
-      int m = 0;
-      for (int e = 0; e < E; ++e)
-        if (c->h_count[e] > 0) { dist += c->h_weight[e] / 1.5; cell += c->frames[c->edst[e]].grid.cell; ++m; }
-      if (m > 0) {
-        dist /= m; cell /= m;
-        const bool settled = c->auto_prev_dist > 0.0 ? dist > c->auto_settle * c->auto_prev_dist : dist < 0.5 * cell;
-        if (c->nn_cell) {
-          // cell-staging grid kernel: it resolves a query whose neighbour is within about a cell of it (home block + ball) at a cost
-          // that follows that distance, not the cache hit rate — so it takes over as soon as the queries are EXPECTED to land that
-          // close: the smaller of last round's median distance and the residual the LM solve has just left (RMS over all
-          // correspondences, with a floor of a fraction of a cell for the sampling of the surface)
-          double pred = dist;
-          if (c->last_rms >= 0.0) pred = std::min(pred, std::sqrt(c->last_rms * c->last_rms + 0.09 * cell * cell));
-          if (pred < c->auto_switch * cell || c->auto_last_method == MVICP_NN_GRID) method = MVICP_NN_GRID;
-        } else if (dist < 1.5 * cell && (settled || c->auto_last_method == MVICP_NN_GRID)) method = MVICP_NN_GRID;
-        c->auto_prev_dist = dist;
-      }
-    }
-  }
-  if (method == MVICP_NN_GRID || method == MVICP_NN_TILE) {
-    for (int e = 0; e < E; ++e)
-      if (c->active[e] && (!c->frames[c->edst[e]].has_grid || !c->frames[c->esrc[e]].has_grid)) method = MVICP_NN_BRUTE;
-  }
-  // The round in which AUTO hands over to the grid kernel would be an UNCACHED grid round (every query searched through the hash:
-  // 2.4-2.6 ms on cfg4, the slowest round after the first).  Instead the tile kernel runs once more in its BND build (~1.2 ms), which
-  // also leaves the per-query lower bounds the temporal cache needs; the grid kernel takes over one round later, with cache hits.
-  bool tile_lb = false, handed_over = false;
-  if (nn_method == MVICP_NN_AUTO && method == MVICP_NN_GRID && c->auto_last_method == MVICP_NN_TILE && c->tile_bounds >= 1 &&
-      c->nn_cache_enable && !c->nn_cell) { method = MVICP_NN_TILE; tile_lb = true; handed_over = true; }
-  if (method == MVICP_NN_TILE && c->tile_bounds >= 2 && c->nn_cache_enable) tile_lb = true;
-  // Cache-aware tile rounds (round 3).  After the hand-over the grid kernel answers cache hits at streaming speed but pays 1.5-2 ns for
-  // every isolated miss (per-lane hash probing), which dominates the rounds in which the poses still move a little (hit rates 74-99 %).
-  // Those rounds run the tile kernel's bounds-leaving build with the cache check as its prologue instead: a missed lane is searched by
-  // its wave, cooperatively.  Once every transform is bit-identical to last search's (the fixed point) the grid kernel's verify pass is
-  // the cheaper one and takes over.
-  bool tile_cached = false;
-  bool all_same = true;   // every active edge's query transform is bit-identical to last search's
-  {
-    for (int e = 0; e < E; ++e) if (c->active[e] && !same_edge[e]) all_same = false;
-    if (nn_method == MVICP_NN_AUTO && method == MVICP_NN_GRID && !handed_over && c->tile_cache && c->tile_bounds >= 1 && c->nn_cache_valid &&
-        c->nn_cache_enable && !c->nn_cell && !all_same) { method = MVICP_NN_TILE; tile_lb = true; tile_cached = true; handed_over = true; }
-    // experiment (round 6, "tile_cache" = 2): the cache prologue in EVERY tile round that follows a bounds-leaving one (with "tile_bounds" = 2: from
-    // round 3 on), not only after the hand-over — measures how early the temporal cache starts to hit (profiles/r06_tile_ab.txt)
-    if (method == MVICP_NN_TILE && !tile_cached && c->tile_cache >= 2 && tile_lb && c->nn_cache_valid && c->nn_cache_enable && !all_same) tile_cached = true;
-  }
-  {
-    // an edge may keep last round's compacted list only if a kernel that checks every query's acceptance and patches changed
-    // neighbours in place runs (the grid kernel, the tile kernel: nn_list.h) and the list on the device really is last round's result
-    // for this edge
-    std::vector<int> dirty(E, 1);
-    if ((method == MVICP_NN_TILE || (method == MVICP_NN_GRID && !c->nn_tree_only && !c->nn_skip_far)) && c->list_reuse)
-      for (int e = 0; e < E; ++e) if (c->active[e] && c->list_valid[e]) dirty[e] = 0;
-    std::memcpy(hd, dirty.data(), sizeof(int) * E);
-  }
-  // One-pass bracket select (corr.hip) instead of the two-pass anchored select: only when EVERY active edge of this rank has a
-  // median that has settled (last two rounds within 0.1 %); the bracket is +-0.6 % in d2 around the last one.
-  bool use_bracket = c->sel_bracket && c->have_corr;
-  {
-    double* lohi = hx + (size_t)E * (kEdgeXf + 1);
-    for (int e = 0; e < E; ++e) {
-      lohi[2 * e] = lohi[2 * e + 1] = 0.0;
-      if (!c->active[e]) continue;
-      const double m1 = c->sel_med1[e], m2 = c->sel_med2[e];
-      if (!(m1 > 0.0 && m2 > 0.0 && std::fabs(m1 - m2) <= 0.001 * m1)) { use_bracket = false; continue; }
-      lohi[2 * e] = m1 * 0.994; lohi[2 * e + 1] = m1 * 1.006;
-    }
-  }
-  // A search whose every edge has last round's exact transform and a valid list reproduces every query bit for bit: no list can
-  // change, so the (data-dependent, early-exiting) list-maintenance kernels — dirty-flag reduction, compaction, gather — are not
-  // even launched.
-  // (not with the cell-staging variant: nn_cell_kernel has no bit-identical-query shortcut, so a fixed-point round is not a pure no-op there)
-  bool nothing_can_change = method == MVICP_NN_GRID && c->list_reuse && !c->nn_tree_only && !c->nn_skip_far && same_active_set && !c->nn_cell;
-  for (int e = 0; e < E && nothing_can_change; ++e)
-    if (c->active[e] && !(same_edge[e] && hd[e] == 0)) nothing_can_change = false;
-  c->skip_dirty_reduce = nothing_can_change;
-  // ... and the tie fix-up (nn_tie.hip) neither, if last round's search reported no tie: the same queries meet the same targets
-  c->tie_skip = nothing_can_change && c->corr_tie_seen == 0u;
-  c->far_skip = nothing_can_change && c->corr_far_seen == 0u && c->prev_grid_kernel && method == MVICP_NN_GRID;
-  const bool tie_launched = c->tie_rule && !c->tie_skip, far_launched = method == MVICP_NN_GRID && !c->far_skip;
-  // Speculative first evaluation of the solve that follows (see common.h).  Every rank decides for itself (its own last solve set
-  // the flags); with N > 1 ranks the decisions are SUMMED in the "armed" slot of the one exchanged buffer and the queued blocks are
-  // used only if every rank armed — a rank that did not arm still takes part in the same collective with the same size.  (A rank that fails
-  // LOCALLY before the exchange — a launch error — returns without it and its peers block in the collective: a failed launch is fatal for the job.)
-  const bool exchange = c->comm != nullptr || c->ar_fn != nullptr;
+  if (plan.status != MVICP_OK) { set_error("unknown nn_method %d", nn_method); return plan.status; }
   c->spec_ready = false; c->spec2_ready = false;
-  c->spec_arm = c->spec_enable && c->spec_flags_valid;
-  if (c->spec_arm && c->spec_plane)
-    for (int e = 0; e < E; ++e) if (!(fixed && fixed[c->esrc[e]]) && c->frames[c->edst[e]].n > 0 && c->frames[c->edst[e]].grid.snor == nullptr) c->spec_arm = false;
-  const size_t nb = (size_t)E * MVICP_EDGE_BLOCK, ntail = 3 * (size_t)E + 1;   // tail = (count, median d2) x E | armed | a x E
-  c->d_res_target = exchange ? c->d_out + nb : nullptr;
-  c->d_a_check = exchange ? c->d_out + nb + 2 * (size_t)E + 1 : c->d_adev_host;   // where the select kernels copy the scales they derive
-  size_t upload_doubles = c->ctl_r1;
-  bool spec2_plan = false;
-  if (c->spec_arm) {
-    // the solve evaluates at x_to_pose(pose_to_x(P)) (host/lm.cpp): the same round trip here, so the poses match bit for bit.  The
-    // relative transforms of that evaluation ride on the control-block upload (region 2 follows region 1; the SoftLOne scales
-    // behind them are written on the device by the select kernels later in the stream)
-    c->spec_poses.resize(16 * (size_t)c->n_frames);
-    double xp[7];
-    for (int k = 0; k < c->n_frames; ++k) { se3::pose_to_x(c->spec_param, poses + 16 * (size_t)k, xp); se3::x_to_pose(c->spec_param, xp, &c->spec_poses[16 * (size_t)k]); }
-    fill_rel(c, c->spec_poses.data());
-    c->spec_q_plane = c->spec_plane; c->spec_q_robust = c->spec_robust;
-    upload_doubles = c->ctl_r2_off + (size_t)E * kEdgeRel;
-    // second queued evaluation: this search's poses are last search's bit for bit, so the solve that follows will ask for last solve's candidate again
-    spec2_plan = !exchange && c->spec2_enable && all_same && same_active_set && c->have_corr && c->last_cand_poses.size() == 16 * (size_t)c->n_frames &&
-                 c->last_cand_plane == c->spec_q_plane && c->last_cand_robust == c->spec_q_robust;
-    // paired launch (option lin_pair): its relative transforms lie between region 1 and rel, so they ride on the same upload
-    if (spec2_plan && c->lin_pair) fill_rel_into(c, c->last_cand_poses.data(), hx + c->ctl_rel2_off);
-  }
-  // ... and the median select neither (single rank): the median of an edge is a function of its d2 list and its count, nothing rewrites either in such
-  // a search, and the last search's select finished — d_median, d_a (the select's own values, or the host's bit-identical mirror uploaded by an
-  // evaluation since) and the mapped (count, median d2) pairs ARE this search's result.  Only the "armed" slot is this search's own: the host writes
-  // it.  With N > 1 ranks that tail lives in the exchanged buffer and is summed in place, so it is rewritten every search.
-  const bool sel_skip = !exchange && c->sel_reuse && nothing_can_change && c->sel_result_valid && (!c->spec_arm || c->sel_result_armed);
-  if (method != MVICP_NN_BRUTE && method != MVICP_NN_GRID && method != MVICP_NN_TILE) { set_error("unknown nn_method %d", nn_method); return MVICP_ERR_ARG; }   // (an argument error: the same on every rank)
-  bool all_unchanged = true;
-  for (int e = 0; e < E; ++e) { if (!unchanged[e]) all_unchanged = false; if (c->active[e]) c->qpos_valid[e] = 0; }   // (set again once the NN stage is queued)
-  auto local_search = [&]() -> int {
-  MV_HIP(hipMemcpyAsync(c->d_ctl, hx, sizeof(double) * upload_doubles, hipMemcpyHostToDevice, c->stream));
-  c->far_narrow = nn_method == MVICP_NN_AUTO && method == MVICP_NN_GRID && c->nn_cache_valid && c->nn_cache_enable && all_same;   // the fixed point: (almost) every query is a cache hit
-  if (c->fault_inject > 0 && --c->fault_inject == 0) { set_error("injected launch failure (option fault_inject)"); return MVICP_ERR_HIP; }   // tests: a local failure before the exchange
-  if (method == MVICP_NN_BRUTE) MV_CHECK(launch_nn_brute_edges(c));
-  else if (method == MVICP_NN_GRID) MV_CHECK(launch_nn_grid_edges(c, bound));
-  else {
-    // Cache-aware rounds: which build?  With most lanes finished by the cache, nn_tile_kernel (per-lane box tests, miss_block) wins; with hit rates
-    // below ~80 % the matrix-pipe build does (cfg4_partial rounds 5-13: -4 ... -10 %, profiles/r06_tile_ab.txt).  The hit rate is not known before
-    // the launch, but what decides it is: the median displacement bound of the queries in units of the guard band (eps / mu).
-    c->cached_on_mfma = false;
-    if (tile_cached && c->tile_mfma == 1 && c->cache_mfma_ratio > 0.0 && !eps_ratio.empty()) {
-      std::nth_element(eps_ratio.begin(), eps_ratio.begin() + eps_ratio.size() / 2, eps_ratio.end());
-      const double med = eps_ratio[eps_ratio.size() / 2];
-      if (c->profile) { ProfEntry& pe = c->prof["auto.eps_over_mu"]; pe.ms = med; pe.launches += 1; }   // (observable: the last cache-aware round's ratio)
-      c->cached_on_mfma = med > c->cache_mfma_ratio;
-    }
-    MV_CHECK(launch_nn_tile_edges(c, bound, tile_lb, tile_cached, c->list_reuse));
-  }
-  c->tie_skip = false; c->far_skip = false;
-  c->prev_grid_kernel = method == MVICP_NN_GRID;
-  // only the grid kernel and the tile kernel's BND build leave the per-query lower bounds the temporal cache needs; the cutoff must
-  // not change either
-  c->last_rms = -1.0;   // consumed: only a solve that follows THIS search may predict the next one
-  c->nn_cache_valid = ((method == MVICP_NN_GRID) && !c->nn_tree_only && !c->nn_skip_far) || tile_lb;
-  c->nn_cache_thresh = thresh;
-  c->auto_last_method = handed_over ? MVICP_NN_GRID : method;   // (the policy's "already handed over" state)
-  c->nn_cache_edge.assign(c->active.begin(), c->active.end());
-  for (int e = 0; e < E; ++e) { c->list_valid[e] = c->active[e]; if (c->owned[e]) c->qpos_valid[e] = c->active[e]; if (c->active[e]) c->explicit_list[e] = 0; }
-  if (!all_unchanged) c->export_valid = false;   // (a search that reproduces every list leaves the exported copy what it is)
-
-  mark("host.corr.nn_launch");
-  if (!nothing_can_change) {
-    MV_CHECK(launch_compact(c, bound));
-    MV_CHECK(launch_gather_stream(c));
-  }
-  if (sel_skip) { c->h_pin[c->pin_res_off + 2 * (size_t)E] = c->spec_arm ? 1.0 : 0.0; return MVICP_OK; }   // (nothing on the device writes the mapped results in this search)
-  return use_bracket ? launch_select_bracket(c) : launch_select_median(c, bound);
-  };   // local_search
-  if (st_local == MVICP_OK) st_local = local_search();
-  if (st_local != MVICP_OK && !exchange) { c->spec_flags_valid = false; return st_local; }
+  c->spec_arm = plan.spec_arm;
+  const size_t nb = out_blocks(c), armed = out_armed(c);
+  c->d_res_target = in.exchange ? c->d_out + nb : nullptr;
+  c->d_a_check = in.exchange ? c->d_out + armed + 1 : c->d_adev_host;   // where the select kernels copy the scales they derive
+  const size_t upload_doubles = stage_queued_evaluations(c, plan, poses);
+  if (st_local == MVICP_OK) st_local = launch_local_search(c, in, plan, bound, upload_doubles, mark);
+  if (st_local != MVICP_OK && !in.exchange) { c->hist.spec_flags_valid = false; return st_local; }
   // the queued first evaluation (its relative transforms went up with the control block).  With N > 1 ranks: ONE collective per
   // search — [E x 91 blocks | (count, median d2) x E | armed | a x E], always the full buffer — and ONE wait.
   int st_q = MVICP_OK;
   char local_msg[sizeof(g_err)] = "";
-  if (exchange) {
-    c->lin_out = c->d_out;
-    if (st_local == MVICP_OK) {
-      if (c->spec_arm) st_local = launch_linearize(c, c->spec_q_plane, c->spec_q_robust);
-      else {
-        // this rank queued no evaluation: its share of the block region and of the scale slots is ZERO, not whatever the last exchange left
-        // there (already-summed values would be summed again round after round).  Every rank sends the same buffer size whatever it decided.
-        if (hipMemsetAsync(c->d_out, 0, sizeof(double) * nb, c->stream) != hipSuccess ||
-            hipMemsetAsync(c->d_out + nb + 2 * (size_t)E + 1, 0, sizeof(double) * (size_t)E, c->stream) != hipSuccess) { set_error("hipMemsetAsync of the exchange buffer failed"); st_local = MVICP_ERR_HIP; }
-      }
-    }
-    if (st_local != MVICP_OK) {
-      // this rank's share cannot be delivered: enter the collective all the same, with the armed slot poisoned (eight 0xFF bytes = a NaN)
-      std::memcpy(local_msg, g_err, sizeof(local_msg));
-      if (hipMemsetAsync(c->d_out + nb + 2 * (size_t)E, 0xFF, sizeof(double), c->stream) != hipSuccess) {
-        set_error("%s — and the exchange buffer could not be poisoned: the peers of this rank will block in the collective", local_msg);
-        c->spec_flags_valid = false; c->spec_arm = false;
-        return st_local;
-      }
-    }
-    { ProfScope pc(c, "comm", 8.0 * (double)(nb + ntail)); st_q = comm_allreduce_sum(c, c->d_out, nb + ntail); }
-    if (st_q == MVICP_OK && hipMemcpyAsync(c->h_pin + c->pin_spec_off, c->d_out, sizeof(double) * (nb + ntail), hipMemcpyDeviceToHost, c->stream) != hipSuccess) {
-      set_error("hipMemcpyAsync of the exchanged buffer failed"); st_q = MVICP_ERR_HIP;
-    }
-  } else if (c->spec_arm && spec2_plan && c->lin_pair) {
-    // both queued evaluations in one pass over the operand stream: first blocks -> d_spec_host, second -> d_spec2_host
-    c->spec2_armed = false;
-    st_q = launch_linearize_pair(c, c->spec_q_plane, c->spec_q_robust, c->d_spec_host, c->d_spec2_host);
-    if (st_q == MVICP_OK) { c->spec2_armed = true; c->spec2_poses = c->last_cand_poses; c->spec2_plane = c->spec_q_plane; c->spec2_robust = c->spec_q_robust; }
-  } else if (c->spec_arm) {
-    c->lin_out = c->d_spec_host;
-    st_q = launch_linearize(c, c->spec_q_plane, c->spec_q_robust);
-    c->spec2_armed = false;
-    if (st_q == MVICP_OK && spec2_plan) {
-      fill_rel_into(c, c->last_cand_poses.data(), c->h_pin + c->pin_rel2_off);
-      if (hipMemcpyAsync(c->d_rel, c->h_pin + c->pin_rel2_off, sizeof(double) * (size_t)E * kEdgeRel, hipMemcpyHostToDevice, c->stream) == hipSuccess) {
-        c->lin_out = c->d_spec2_host;
-        st_q = launch_linearize(c, c->spec_q_plane, c->spec_q_robust);
-        if (st_q == MVICP_OK) { c->spec2_armed = true; c->spec2_poses = c->last_cand_poses; c->spec2_plane = c->spec_q_plane; c->spec2_robust = c->spec_q_robust; }
-      }
-    }
-  }
+  if (in.exchange) {
+    if (st_local == MVICP_OK) st_local = queue_exchanged_evaluation(c, plan);
+    bool entered;
+    st_q = exchange_out(c, 0, nb + out_tail(c), "buffer", st_local, local_msg, &entered);
+    if (!entered) { spec_failed(c); return st_local; }
+  } else if (plan.spec_arm) st_q = queue_evaluations(c, plan);
   mark("host.corr.post_launch");
   // (count, median d2) per edge arrive in mapped host memory, written by bracket_final_kernel (single rank), or summed over ranks
-  // behind the blocks; weight = (float)(1.5 * sqrt(median d2))  (frame.cpp:168-176)
+  // behind the blocks
   if (st_q == MVICP_OK) st_q = stream_wait(c);
-  if (st_q != MVICP_OK) { c->spec_flags_valid = false; c->spec_arm = false; return st_q; }
-  if (exchange && std::isnan(c->h_pin[c->pin_spec_off + nb + 2 * (size_t)E])) {
+  if (st_q != MVICP_OK) { spec_failed(c); return st_q; }
+  if (in.exchange && std::isnan(c->h_pin[c->pin_spec_off + armed])) {
     // some rank (this one if st_local says so) entered the collective without its share: nothing of this search is usable anywhere.  Every
     // rank forgets what earlier searches left behind — the next search is a first search on all of them, so their states agree again.
     forget_history(c);
@@ -2162,85 +1935,28 @@ static int correspond_body(mvicp_ctx* c, const double* poses, const unsigned cha
     return MVICP_ERR_COMM;
   }
   census_resolve(c);
-  // what THIS search's tie fix-up / far launch reported (a skipped launch keeps last search's zero): the next search's skip decisions
-  if (tie_launched) c->corr_tie_seen = c->h_tie_seen ? *c->h_tie_seen : 1u;
-  if (tie_launched && c->h_tie_seen && c->h_tie_seen[1] != 0u) *tie_unresolved = true;
-  if (tie_launched && c->h_tie_seen && c->h_tie_seen[2] != 0u) { set_error("tie fix-up: a walk ran out of stack (a tree deeper than its recorded levels)"); return MVICP_ERR_INTERNAL; }
-  if (far_launched) c->corr_far_seen = c->h_far_seen ? *c->h_far_seen : 1u;
-  else if (method != MVICP_NN_GRID) c->corr_far_seen = 1u;
+  if (plan.tie_launched && c->h_tie_seen && c->h_tie_seen[1] != 0u) *tie_unresolved = true;
+  if (plan.tie_launched && c->h_tie_seen && c->h_tie_seen[2] != 0u) { set_error("tie fix-up: a walk ran out of stack (a tree deeper than its recorded levels)"); return MVICP_ERR_INTERNAL; }
   mark("host.corr.wait");
-  const double* hr = exchange ? c->h_pin + c->pin_spec_off + nb : c->h_pin + c->pin_res_off;
-  bool spec_bad = false;
-  {
-    // a median that left its bracket is flagged -1 in its slot; with N > 1 ranks every rank sees the summed slots, so every rank takes
-    // the same decision: full select for everything (rare once the registration has settled) and a second, tail-only exchange
-    bool redo = false;
-    for (int e = 0; e < E; ++e) if (hr[2 * e + 1] < 0.0) redo = true;
-    if (redo) {
-      spec_bad = true;   // the queued evaluation used the scales of the failed select
-      int st_r = launch_select_median(c, bound);
-      if (exchange) {
-        int st_x = MVICP_OK;
-        if (st_r != MVICP_OK) {   // same protocol as above: the second (tail-only) collective is entered with a poisoned armed slot
-          std::memcpy(local_msg, g_err, sizeof(local_msg));
-          if (hipMemsetAsync(c->d_out + nb + 2 * (size_t)E, 0xFF, sizeof(double), c->stream) != hipSuccess) { c->spec_flags_valid = false; c->spec_arm = false; return st_r; }
-        }
-        { ProfScope pc(c, "comm", 8.0 * (double)ntail); st_x = comm_allreduce_sum(c, c->d_out + nb, ntail); }
-        if (st_x == MVICP_OK && hipMemcpyAsync(c->h_pin + c->pin_spec_off + nb, c->d_out + nb, sizeof(double) * ntail, hipMemcpyDeviceToHost, c->stream) != hipSuccess) {
-          set_error("hipMemcpyAsync of the exchanged tail failed"); st_x = MVICP_ERR_HIP;
-        }
-        if (st_x == MVICP_OK) st_x = stream_wait(c);
-        if (st_x != MVICP_OK) { c->spec_flags_valid = false; c->spec_arm = false; return st_x; }
-        if (std::isnan(hr[2 * (size_t)E])) {
-          forget_history(c);
-          if (st_r != MVICP_OK) { set_error("%s", local_msg); return st_r; }
-          set_error("a peer rank failed before the second exchange of this search (poisoned exchange buffer); cross-round state dropped on every rank");
-          return MVICP_ERR_COMM;
-        }
-      } else {
-        if (st_r == MVICP_OK) st_r = stream_wait(c);
-        if (st_r != MVICP_OK) { c->spec_flags_valid = false; c->spec_arm = false; return st_r; }
-      }
-    }
-  }
-  for (int e = 0; e < E; ++e) {
-    if (!(c->owned[e] && c->active[e])) { c->sel_med1[e] = c->sel_med2[e] = -1.0; continue; }
-    c->sel_med2[e] = c->sel_med1[e];
-    c->sel_med1[e] = hr[2 * e] > 0 ? hr[2 * e + 1] : -1.0;
-  }
-  std::vector<double> pack(2 * (size_t)E, 0.0);
-  for (int e = 0; e < E; ++e)
-    if (exchange || (c->owned[e] && c->active[e])) { pack[2 * e] = hr[2 * e]; pack[2 * e + 1] = hr[2 * e] > 0 ? hr[2 * e + 1] : 0.0; }
-  if (c->spec_arm) {
-    // trust the queued evaluation only if (i) every rank queued one, and (ii) the scales the device derived from the medians are the
-    // host's (IEEE sqrt) bit for bit — checked on ALL edges from exchanged data, so every rank reaches the same verdict
-    const double* ad = exchange ? hr + 2 * (size_t)E + 1 : c->h_pin + c->pin_adev_off;
-    if (hr[2 * (size_t)E] != (double)(exchange ? c->world : 1)) spec_bad = true;
-    for (int e = 0; e < E && !spec_bad; ++e)
-      if (exchange || (c->owned[e] && c->active[e])) {
-        const double a_host = pack[2 * e] > 0 ? (double)(float)(std::sqrt(pack[2 * e + 1]) * 1.5) : 0.0;
-        if (ad[e] != a_host) spec_bad = true;
-      }
-  }
-  c->spec_ready = c->spec_arm && !spec_bad;
+  const double* hr = in.exchange ? c->h_pin + c->pin_spec_off + nb : c->h_pin + c->pin_res_off;
+  bool redone = false;
+  for (int e = 0; e < E; ++e) if (hr[2 * e + 1] < 0.0) redone = true;
+  if (redone) MV_CHECK(redo_select(c, bound, in.exchange, local_msg));
+  c->spec_ready = record_arrived(in, plan, c->hist, c->h_tie_seen ? *c->h_tie_seen : 1u, c->h_far_seen ? *c->h_far_seen : 1u, hr,
+                                 in.exchange ? hr + 2 * (size_t)E + 1 : c->h_pin + c->pin_adev_off, redone);
   c->spec2_ready = c->spec_ready && c->spec2_armed;   // (same scales, same lists: valid whenever the first one is)
   c->spec2_armed = false;
-  if (!sel_skip) c->sel_result_armed = c->spec_arm;   // (a skipped select leaves d_a and its mapped copy as they were)
-  c->sel_result_valid = !exchange;
   c->spec_arm = false;
   double* ha = c->h_pin + c->ctl_r2_off + (size_t)E * kEdgeRel;   // `a` slice of region 2: uploaded with rel by the next evaluation
   for (int e = 0; e < E; ++e) {
-    c->h_count[e] = (int)pack[2 * e];
-    const double nth = std::sqrt(pack[2 * e + 1]);
-    c->h_weight[e] = c->h_count[e] > 0 ? (float)(nth * 1.5) : 0.f;
-    ha[e] = (double)c->h_weight[e];
-    if (counts) counts[e] = c->h_count[e];
-    if (weights) weights[e] = c->h_weight[e];
+    ha[e] = (double)c->hist.h_weight[e];
+    if (counts) counts[e] = c->hist.h_count[e];
+    if (weights) weights[e] = c->hist.h_weight[e];
+    if (!plan.unchanged[e]) c->corr_epoch[e] = ++c->epoch_counter;
   }
-  for (int e = 0; e < E; ++e) if (!unchanged[e]) c->corr_epoch[e] = ++c->epoch_counter;
-  c->have_corr = true;
   mark("host.corr.finish");
   if (c->profile) prof_collect_lazy(c);
+  guard.ok = true;
   return MVICP_OK;
 }
 
@@ -2262,7 +1978,7 @@ static int ensure_export(mvicp_ctx* c, bool wait = true) {
 int mvicp_map_correspondences(mvicp_ctx* c, const mvicp_corr** triples, const long long** offsets) try {
   MV_CHECK(bind(c));
   if (!triples || !offsets) { set_error("null output"); return MVICP_ERR_ARG; }
-  if (!c->have_corr) { set_error("no correspondences yet"); return MVICP_ERR_STATE; }
+  if (!c->hist.have_corr) { set_error("no correspondences yet"); return MVICP_ERR_STATE; }
   MV_CHECK(ensure_export(c));
   *triples = (const mvicp_corr*)c->h_export;
   *offsets = c->export_off.data();
@@ -2272,7 +1988,7 @@ int mvicp_map_correspondences(mvicp_ctx* c, const mvicp_corr** triples, const lo
 int mvicp_map_correspondences_async(mvicp_ctx* c, const mvicp_corr** triples, const long long** offsets) try {
   MV_CHECK(bind(c));
   if (!triples || !offsets) { set_error("null output"); return MVICP_ERR_ARG; }
-  if (!c->have_corr) { set_error("no correspondences yet"); return MVICP_ERR_STATE; }
+  if (!c->hist.have_corr) { set_error("no correspondences yet"); return MVICP_ERR_STATE; }
   MV_CHECK(ensure_export(c, false));
   *triples = (const mvicp_corr*)c->h_export;
   *offsets = c->export_off.data();
@@ -2301,11 +2017,11 @@ int mvicp_correspondence_epochs(mvicp_ctx* c, const unsigned long long** epochs)
 int mvicp_get_correspondences(mvicp_ctx* c, int edge, int cap, int* first, int* second, double* dist) try {
   MV_CHECK(bind(c));
   if (edge < 0 || edge >= c->E) { set_error("edge %d out of range", edge); return MVICP_ERR_ARG; }
-  if (!c->have_corr) { set_error("no correspondences yet"); return MVICP_ERR_STATE; }
+  if (!c->hist.have_corr) { set_error("no correspondences yet"); return MVICP_ERR_STATE; }
   if (!c->owned[edge]) { set_error("edge %d is owned by another rank", edge); return MVICP_ERR_STATE; }
-  const int n = c->h_count[edge];
+  const int n = c->hist.h_count[edge];
   if (cap < n) { set_error("capacity %d < count %d", cap, n); return MVICP_ERR_ARG; }
-  if (!c->explicit_list[edge]) {
+  if (!c->hist.explicit_list[edge]) {
     // a list built by mvicp_correspond: slice of the one export of this search (first call after a search runs it for ALL edges)
     if (n == 0) return 0;
     MV_CHECK(ensure_export(c));
@@ -2363,12 +2079,10 @@ int mvicp_set_correspondences(mvicp_ctx* c, int edge, int n, const int* first, c
     MV_HIP(hipMemcpy(c->d_second + off, b.data(), sizeof(int) * n, hipMemcpyHostToDevice));
     MV_HIP(hipMemset(c->d_cd2 + off, 0, sizeof(double) * n));
   }
-  c->nn_cache_valid = false;
+  c->hist.explicit_edge(edge, n, weight);
   c->spec_ready = false; c->spec2_ready = false;
-  c->list_valid[edge] = 0; c->explicit_list[edge] = 1; c->export_valid = false;
-  c->qpos_valid[edge] = 0; c->corr_epoch[edge] = ++c->epoch_counter;
-  c->sel_med1[edge] = c->sel_med2[edge] = -1.0;
-  c->sel_result_valid = false;   // d_count, d_cd2 and d_a of this edge are no longer the last select's
+  c->export_valid = false;
+  c->corr_epoch[edge] = ++c->epoch_counter;
   const double a = (double)weight;
   MV_HIP(hipMemcpy(c->d_count + edge, &n, sizeof(int), hipMemcpyHostToDevice));
   {   // an explicit list is arbitrary (repeats, any order): never the identity list the linearize kernel may shortcut
@@ -2377,9 +2091,6 @@ int mvicp_set_correspondences(mvicp_ctx* c, int edge, int n, const int* first, c
   }
   MV_HIP(hipMemcpy(c->d_a + edge, &a, sizeof(double), hipMemcpyHostToDevice));
   c->h_pin[c->ctl_r2_off + (size_t)c->E * kEdgeRel + edge] = a;   // host mirror: region 2 is re-uploaded by every evaluation
-  c->h_count[edge] = n;
-  c->h_weight[edge] = weight;
-  c->have_corr = true;
   const int one = 1;
   MV_HIP(hipMemcpy(c->d_dirty + edge, &one, sizeof(int), hipMemcpyHostToDevice));  // this edge's operands must be (re)gathered
   MV_CHECK(launch_gather_stream(c));
@@ -2400,8 +2111,7 @@ int mvicp_nn_query(mvicp_ctx* c, int frame, const double* queries, int n, int nn
   MV_CHECK(dev_alloc(&dq, 3 * (size_t)n)); MV_CHECK(dev_alloc(&di, (size_t)n)); MV_CHECK(dev_alloc(&dd, (size_t)n));
   MV_HIP(hipMemcpy(dq, queries, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice));
   int method = (nn_method == MVICP_NN_AUTO || nn_method == MVICP_NN_TILE) ? MVICP_NN_GRID : nn_method;  // raw queries are not patch-ordered
-  if (c->tie_rule) MV_CHECK(ensure_tie_trees(c, std::vector<int>(1, frame)));
-  c->tie_skip = false;
+  if (c->opt.tie_rule) MV_CHECK(ensure_tie_trees(c, std::vector<int>(1, frame)));
   if (method == MVICP_NN_GRID && !f.has_grid) method = MVICP_NN_BRUTE;
   int st;
   if (method == MVICP_NN_BRUTE) st = launch_nn_brute_queries(c, f, dq, n, di, dd);
@@ -2410,7 +2120,7 @@ int mvicp_nn_query(mvicp_ctx* c, int frame, const double* queries, int n, int nn
   if (st == MVICP_OK) {
     hipError_t e1 = hipStreamSynchronize(c->stream);
     if (e1 == hipSuccess) census_resolve(c);
-    if (e1 == hipSuccess && c->tie_rule && c->h_tie_seen && c->h_tie_seen[2] != 0u) { set_error("tie fix-up: a walk ran out of stack (a tree deeper than its recorded levels)"); st = MVICP_ERR_INTERNAL; }
+    if (e1 == hipSuccess && c->opt.tie_rule && c->h_tie_seen && c->h_tie_seen[2] != 0u) { set_error("tie fix-up: a walk ran out of stack (a tree deeper than its recorded levels)"); st = MVICP_ERR_INTERNAL; }
     hipError_t e2 = hipMemcpy(idx, di, sizeof(int) * n, hipMemcpyDeviceToHost);
     hipError_t e3 = hipMemcpy(d2, dd, sizeof(double) * n, hipMemcpyDeviceToHost);
     if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) { set_error("nn_query copy-back failed"); st = MVICP_ERR_HIP; }
@@ -2460,44 +2170,44 @@ int mvicp_set_option(mvicp_ctx* c, const char* name, double value) try {
   if (!name) { set_error("null option name"); return MVICP_ERR_ARG; }
   if (std::strcmp(name, "async_build") == 0) { c->async_build = value != 0.0; return MVICP_OK; }
   if (std::strcmp(name, "grid_target") == 0 || std::strcmp(name, "grid_curve") == 0) MV_CHECK(finish_builds(c));   // (pending builds read them)
-  if (std::strcmp(name, "nn_tree_only") == 0) { c->nn_tree_only = value != 0.0; return MVICP_OK; }
-  if (std::strcmp(name, "nn_cache") == 0) { c->nn_cache_enable = value != 0.0; c->nn_cache_valid = false; return MVICP_OK; }
+  if (std::strcmp(name, "nn_tree_only") == 0) { c->opt.nn_tree_only = value != 0.0; return MVICP_OK; }
+  if (std::strcmp(name, "nn_cache") == 0) { c->opt.nn_cache_enable = value != 0.0; c->hist.nn_cache_valid = false; return MVICP_OK; }
   if (std::strcmp(name, "lin_chunk") == 0) { c->lin_chunk_override = (int)value; return MVICP_OK; }  // takes effect at the next mvicp_set_graph
-  if (std::strcmp(name, "list_reuse") == 0) { c->list_reuse = value != 0.0; return MVICP_OK; }
+  if (std::strcmp(name, "list_reuse") == 0) { c->opt.list_reuse = value != 0.0; return MVICP_OK; }
   if (std::strcmp(name, "lin_interleave") == 0) { c->lin_interleave = value != 0.0; return MVICP_OK; }   // takes effect at the next mvicp_set_graph
   if (std::strcmp(name, "lin_share_p") == 0) { c->lin_share_p = value != 0.0; return MVICP_OK; }
-  if (std::strcmp(name, "lin_pair") == 0) { c->lin_pair = value != 0.0; return MVICP_OK; }   // 0: the two queued evaluations of a fixed-point round as two launches
+  if (std::strcmp(name, "lin_pair") == 0) { c->opt.lin_pair = value != 0.0; return MVICP_OK; }   // 0: the two queued evaluations of a fixed-point round as two launches
   if (std::strcmp(name, "nn_census") == 0) { c->nn_census = value != 0.0; return MVICP_OK; }
-  if (std::strcmp(name, "nn_skip_far") == 0) { c->nn_skip_far = value != 0.0; return MVICP_OK; }
-  if (std::strcmp(name, "sel_bracket") == 0) { c->sel_bracket = value != 0.0; return MVICP_OK; }
-  if (std::strcmp(name, "sel_reuse") == 0) { c->sel_reuse = value != 0.0; return MVICP_OK; }   // 0: launch the median select in every search
+  if (std::strcmp(name, "nn_skip_far") == 0) { c->opt.nn_skip_far = value != 0.0; return MVICP_OK; }
+  if (std::strcmp(name, "sel_bracket") == 0) { c->opt.sel_bracket = value != 0.0; return MVICP_OK; }
+  if (std::strcmp(name, "sel_reuse") == 0) { c->opt.sel_reuse = value != 0.0; return MVICP_OK; }   // 0: launch the median select in every search
   if (std::strcmp(name, "prune_rho") == 0) { c->prune_rho = value; return MVICP_OK; }
   if (std::strcmp(name, "grid_curve") == 0) { c->grid_curve = (int)value; return MVICP_OK; }   // takes effect at the next mvicp_set_frame
-  if (std::strcmp(name, "auto_settle") == 0) { c->auto_settle = value; return MVICP_OK; }
-  if (std::strcmp(name, "auto_switch") == 0) { c->auto_switch = value; return MVICP_OK; }
-  if (std::strcmp(name, "nn_cell") == 0) { c->nn_cell = value != 0.0; return MVICP_OK; }
-  if (std::strcmp(name, "nn_search_factor") == 0) { if (!(value >= 0.0)) { set_error("nn_search_factor < 0"); return MVICP_ERR_ARG; } c->nn_search_factor = value; c->nn_cache_valid = false; return MVICP_OK; }
+  if (std::strcmp(name, "auto_settle") == 0) { c->opt.auto_settle = value; return MVICP_OK; }
+  if (std::strcmp(name, "auto_switch") == 0) { c->opt.auto_switch = value; return MVICP_OK; }
+  if (std::strcmp(name, "nn_cell") == 0) { c->opt.nn_cell = value != 0.0; return MVICP_OK; }
+  if (std::strcmp(name, "nn_search_factor") == 0) { if (!(value >= 0.0)) { set_error("nn_search_factor < 0"); return MVICP_ERR_ARG; } c->nn_search_factor = value; c->hist.nn_cache_valid = false; return MVICP_OK; }
   if (std::strcmp(name, "tie_rule") == 0) {
     // the rule is an INPUT of every search (which target a tied query gets), not a tuning knob: a change drops what earlier searches left behind —
     // lists, seeds, the "no tie was reported" memory, the exported copy — and gives every edge a new epoch, like mvicp_reset_history
     const bool on = value != 0.0;
-    if (on != c->tie_rule) { MV_HIP(hipStreamSynchronize(c->stream)); c->tie_rule = on; forget_history(c); }
+    if (on != c->opt.tie_rule) { MV_HIP(hipStreamSynchronize(c->stream)); c->opt.tie_rule = on; forget_history(c); }
     return MVICP_OK;
   }
-  if (std::strcmp(name, "tie_lazy") == 0) { c->tie_lazy = value != 0.0; return MVICP_OK; }   // takes effect at the next mvicp_set_graph
+  if (std::strcmp(name, "tie_lazy") == 0) { c->opt.tie_lazy = value != 0.0; return MVICP_OK; }   // takes effect at the next mvicp_set_graph
   if (std::strcmp(name, "tile_seed") == 0) { c->tile_seed = value != 0.0; return MVICP_OK; }
-  if (std::strcmp(name, "tile_bounds") == 0) { c->tile_bounds = (int)value; return MVICP_OK; }
-  if (std::strcmp(name, "tile_mu") == 0) { if (!(value > 0.0 && value <= 1.0)) { set_error("tile_mu outside (0, 1]"); return MVICP_ERR_ARG; } c->tile_mu = value; return MVICP_OK; }
+  if (std::strcmp(name, "tile_bounds") == 0) { c->opt.tile_bounds = (int)value; return MVICP_OK; }
+  if (std::strcmp(name, "tile_mu") == 0) { if (!(value > 0.0 && value <= 1.0)) { set_error("tile_mu outside (0, 1]"); return MVICP_ERR_ARG; } c->opt.tile_mu = value; return MVICP_OK; }
   if (std::strcmp(name, "mfma_kacc") == 0) { if (!(value >= 1.0 && value <= 1024.0)) { set_error("mfma_kacc outside [1, 1024]"); return MVICP_ERR_ARG; } c->mfma_kacc = value; return MVICP_OK; }
   if (std::strcmp(name, "mfma_lbt") == 0) { c->mfma_lbt = (int)value; return MVICP_OK; }
   if (std::strcmp(name, "mfma_entry") == 0) { c->mfma_entry = (int)value; return MVICP_OK; }
   if (std::strcmp(name, "mfma_trig") == 0) { c->mfma_trig = (int)value; return MVICP_OK; }
-  if (std::strcmp(name, "tile_mfma") == 0) { c->tile_mfma = (int)value; return MVICP_OK; }
+  if (std::strcmp(name, "tile_mfma") == 0) { c->opt.tile_mfma = (int)value; return MVICP_OK; }
   if (std::strcmp(name, "tile_waves") == 0) { c->tile_waves = (int)value; return MVICP_OK; }
-  if (std::strcmp(name, "cache_mfma_ratio") == 0) { c->cache_mfma_ratio = value; return MVICP_OK; }
+  if (std::strcmp(name, "cache_mfma_ratio") == 0) { c->opt.cache_mfma_ratio = value; return MVICP_OK; }
   if (std::strcmp(name, "reject_cache") == 0) { c->reject_cache = value != 0.0; return MVICP_OK; }
   if (std::strcmp(name, "tile_miss") == 0) { if (!(value >= 0.0 && value <= 64.0)) { set_error("tile_miss outside [0, 64]"); return MVICP_ERR_ARG; } c->tile_miss = (int)value; return MVICP_OK; }
-  if (std::strcmp(name, "tile_cache") == 0) { c->tile_cache = (int)value; return MVICP_OK; }
+  if (std::strcmp(name, "tile_cache") == 0) { c->opt.tile_cache = (int)value; return MVICP_OK; }
   if (std::strcmp(name, "voxel_permute") == 0) { c->voxel_permute = value != 0.0; return MVICP_OK; }
   if (std::strcmp(name, "knn_order") == 0) { c->knn_order = value != 0.0; return MVICP_OK; }
   if (std::strcmp(name, "match_chunk") == 0) {
@@ -2508,8 +2218,8 @@ int mvicp_set_option(mvicp_ctx* c, const char* name, double value) try {
   if (std::strcmp(name, "fault_inject") == 0) { c->fault_inject = (int)value; return MVICP_OK; }            // tests: the value-th mvicp_correspond from now fails locally before its exchange
   if (std::strcmp(name, "fault_inject_build") == 0) { c->fault_inject_build.store((int)value); return MVICP_OK; }      // tests: the value-th structure build from now fails
   if (std::strcmp(name, "fault_inject_eval") == 0) { c->fault_inject_eval = (int)value; return MVICP_OK; }  // tests: the value-th exchanged LM evaluation from now fails locally
-  if (std::strcmp(name, "spec_eval") == 0) { c->spec_enable = value != 0.0; c->spec_ready = false; c->spec2_ready = false; return MVICP_OK; }
-  if (std::strcmp(name, "spec2_eval") == 0) { c->spec2_enable = value != 0.0; c->spec2_ready = false; return MVICP_OK; }
+  if (std::strcmp(name, "spec_eval") == 0) { c->opt.spec_enable = value != 0.0; c->spec_ready = false; c->spec2_ready = false; return MVICP_OK; }
+  if (std::strcmp(name, "spec2_eval") == 0) { c->opt.spec2_enable = value != 0.0; c->spec2_ready = false; return MVICP_OK; }
   if (std::strcmp(name, "grid_target") == 0) {
     if (!(value >= 0.5 && value <= 64.0)) { set_error("grid_target out of range"); return MVICP_ERR_ARG; }
     c->grid_target = value;

@@ -13,6 +13,7 @@
 
 #include "../../include/mvicp.h"
 #include "abi_guard.h"
+#include "search_plan.h"   // host-only: the search policy, its options and history, the layout of the per-edge transform block
 
 namespace mvicp {
 
@@ -37,12 +38,6 @@ constexpr int kLinPartial = 32;      // doubles per linearize workgroup partial 
 constexpr int kLinThreads = 256;
 constexpr int kCompactBlock = 1024;  // queries per compaction workgroup
 constexpr int kSelBlock = 8192;      // keys per radix-select workgroup
-constexpr int kEdgeXf = 40;          // doubles per edge of the query-transform block, laid out as:
-constexpr int kXfRigid = 24;         //   [0, 24): Rs(9) ts(3) Rdinv(9) td(3), column-major (what xf_point reads, nn_metric.h)
-constexpr int kXfCache = 24;         //   temporal-cache switch (>= 0: on, value = rounding allowance in metres; < 0: off)
-constexpr int kXfDM = 25;            //   dM (9, column-major) and
-constexpr int kXfDv = 34;            //   dv (3): change of the query map q = M p + v since the last search, so a query moved by exactly |dM p + dv|
-constexpr int kXfPad = 37;           //   [37, kEdgeXf): zero padding
 constexpr int kEdgeRel = 12;         // R_ds(9, column-major) t_ds(3)
 
 // Uniform grid (spatial hash) over one cloud; see nn_grid.hip.
@@ -261,6 +256,12 @@ struct mvicp_ctx {
   int n_frames = 0;
   std::vector<mvicp::FrameDev> frames;
 
+  // the search policy's options, cross-round state and per-call plan (search_plan.h; api.cpp correspond_once executes the plan)
+  mvicp::SearchOptions opt;
+  mvicp::SearchHistory hist;
+  mvicp::SearchPlan plan;
+  std::vector<mvicp::PlanFrame> plan_frames;   // n_frames: what the policy reads of the clouds, refreshed by every search
+
   // graph + sharding
   int rank = 0, world = 1;
   int E = 0;
@@ -268,9 +269,6 @@ struct mvicp_ctx {
   std::vector<char> owned;         // E
   std::vector<long long> cap_off;  // E+1: prefix of N_src over OWNED edges (0-width for others)
   long long total_cap = 0;
-  std::vector<int> h_count;        // E, valid after correspond / set_correspondences (owned edges)
-  std::vector<float> h_weight;     // E
-  bool have_corr = false;
 
   // device per-edge tables.  d_xf / d_nsrc / d_dirty and d_rel / d_a are views into ONE control block (d_ctl) mirrored in
   // pinned host memory, so a round costs one upload before the NN stage and one per LM evaluation:
@@ -289,17 +287,11 @@ struct mvicp_ctx {
   // per-query (total_cap)
   int* d_nn_idx = nullptr; double* d_nn_d2 = nullptr;
   float* d_nn_lb = nullptr;         // fp32, rounded down: lower bound on the DISTANCE from the query to every target other than nn_idx (temporal cache)
-  bool nn_cache_valid = false; bool nn_cache_enable = true; float nn_cache_thresh = -1.f;
-  std::vector<char> nn_cache_edge;  // edges searched (active) in the last grid search
-  std::vector<double> prev_q;       // E x 12: query map M = Rd^-1 Rs (9, col-major) and v = Rd^-1 (ts - td) of the last search
-  std::vector<double> prev_xf;      // E x 24: the raw query transform (Rs ts Rd^-1 td) of the last search: bit-identical -> queries bit-identical
   // per-correspondence (total_cap)
   int* d_first = nullptr; int* d_second = nullptr; double* d_cd2 = nullptr;
   int* d_qpos = nullptr;            // per query: its position in the edge's compacted list, or -1 (rejected by the cutoff)
   int* d_dirty = nullptr;           // E: != 0 -> the edge's list (membership or a neighbour) changed this round: re-compact + re-gather
   int* d_dirty_slots = nullptr; int* d_dslot_off = nullptr; std::vector<int> dslot_off; int n_dslots = 0;  // one slot per 256 queries
-  std::vector<char> list_valid;     // E: d_qpos / lists describe last round's result of this edge
-  std::vector<char> explicit_list;  // E: the edge's list was installed by mvicp_set_correspondences (arbitrary order / repeats: no d_qpos for it)
   // the lists in the reference's layout (export.hip): {first, second, dist} triples, ascending first, all exportable edges of the last search
   void* d_export = nullptr; void* h_export = nullptr; size_t export_cap = 0;   // device staging / pinned host copy (capacity in triples)
   int* d_xblock_cnt = nullptr;
@@ -308,8 +300,6 @@ struct mvicp_ctx {
   // the copy of the export into pinned memory goes in CHUNKS (one per run of edges with the same source frame), each followed by an event, so that a
   // caller that fills its lists frame by frame (host/frame.cpp) slices frame i while frames i+1.. are still on the bus (mvicp_map_correspondences_async)
   std::vector<hipEvent_t> export_events; std::vector<int> export_edge_chunk; int export_chunks = 0; bool export_in_flight = false;
-  std::vector<char> qpos_valid;      // E: d_qpos / d_second / d_cd2 describe the LAST SEARCH's result of this edge (what the export reads).  Unlike list_valid
-                                     // (= the list may be maintained in place next round) it survives mvicp_recompute_normals, which only re-gathers operands
   std::vector<unsigned long long> corr_epoch;   // E: changes whenever the edge's list (count, triples, weight) may differ from what it was (mvicp_correspondence_epochs)
   unsigned long long epoch_counter = 0;
   double* d_stream = nullptr;       // 10 x total_cap SoA: p (3) | n (3) | c = n . q | q (3)   (linearize.hip)
@@ -322,12 +312,7 @@ struct mvicp_ctx {
   double* d_median = nullptr;
   int n_sblocks = 0; std::vector<int> sblock_off; int* d_sblock_off = nullptr;   // kSelBlock keys per workgroup
   double* d_sel_lohi = nullptr;      // view into the control block: per edge the bracket [lo, hi] (d2) of the one-pass select
-  std::vector<double> sel_med1, sel_med2;   // per owned edge: median d2 of the last / the one-before-last round (< 0: unknown)
-  bool sel_bracket = true;           // option: use the one-pass bracket select once the medians have settled
   bool sel_scratch_clean = false;    // d_sel_hist is all zero on the device: after mvicp_set_graph's memset and after every search that returned OK
-  bool sel_reuse = true;             // option "sel_reuse": no select launch in a single-rank search in which no list can change (0: launch it every search)
-  bool sel_result_valid = false;     // the last search on this context finished its select: d_median, d_a and the mapped (count, median d2) pairs are that select's
-  bool sel_result_armed = false;     // ... and that select also wrote the SoftLOne scales (d_a and their mapped copy)
   double* d_sel_keys1 = nullptr;     // compact key buffer of the bracket pass (total_cap)
   // linearize chunks
   bool lin_interleave = true;       // launch order of the linearize workgroups: chunks of the edges that share a source cloud interleaved in groups of 8 (api.cpp mvicp_set_graph)
@@ -338,7 +323,6 @@ struct mvicp_ctx {
   std::vector<int> chunk_first;     // E+1
   int* d_chunk_edge = nullptr; int* d_chunk_start = nullptr; int* d_chunk_first = nullptr;
   double* d_partials = nullptr;     // 2 x n_chunks x kLinPartial (second half: the second pose set of a paired launch)
-  bool lin_pair = true;             // option "lin_pair": two queued evaluations of a fixed-point round go as ONE paired launch (0: two launches, a copy between them)
   mvicp::PinBuf sym_lo_pin; mvicp::DevBuf sym_lo_dev;   // E x kEdgeRel doubles: low parts of the relative transforms of a symmetric evaluation (api.cpp upload_rel_sym,
                                     // linearize_sym.hip); buffers of their own, allocated by the first symmetric evaluation of a graph, released with the graph
   double* d_out = nullptr;          // E x 91 blocks | E x 2 (count, median d2) | 1 "armed" slot: ONE buffer, so that with N > 1 ranks a round's
@@ -353,7 +337,6 @@ struct mvicp_ctx {
   // Speculative first evaluation: mvicp_correspond queues the linearization the NEXT mvicp_optimize will ask for first (same poses,
   // the parameterization / cost flags of the previous solve) right behind the select kernels, so the round waits once for
   // (counts, medians, first blocks) instead of twice.  Used only if the solve really asks for exactly that evaluation.
-  bool spec_enable = true; bool spec_flags_valid = false; int spec_param = 0, spec_plane = 0, spec_robust = 0;
   int spec_q_plane = 0, spec_q_robust = 0;   // flags the QUEUED evaluation was launched with (spec_plane / spec_robust may have moved on since)
   bool spec_arm = false;            // this correspond call queues one (select kernels write the SoftLOne scales on the device)
   bool spec_ready = false;          // blocks of spec_poses are in the pinned spec region
@@ -365,10 +348,8 @@ struct mvicp_ctx {
   // pinned slice, copied into d_rel in stream order between the two — or, option lin_pair, both in ONE paired launch that reads the operand stream once, with
   // the second set of relative transforms riding on the control-block upload), so the round waits ONCE for both.  Used only if the solve really asks for exactly those
   // poses; nothing is skipped — the work is queued earlier.
-  bool spec2_enable = true, spec2_armed = false, spec2_ready = false; int spec2_plane = 0, spec2_robust = 0;
+  bool spec2_armed = false, spec2_ready = false; int spec2_plane = 0, spec2_robust = 0;
   std::vector<double> spec2_poses;       // poses the second queued evaluation was made at
-  std::vector<double> last_cand_poses;   // poses of the last evaluation a solve asked for beyond its first (the prediction for the next solve's candidate)
-  int last_cand_plane = -1, last_cand_robust = -1;
   size_t pin_spec2_off = 0, pin_rel2_off = 0; double* d_spec2_host = nullptr;
   size_t pin_blocks2_off = 0; double* d_blocks2_host = nullptr;   // second block set of mvicp_linearize_pair (device view of its pinned region)
   double* d_a_check = nullptr;      // where this search's select kernels copy the SoftLOne scales they derive: mapped host memory (single rank) or d_out's tail
@@ -416,58 +397,25 @@ struct mvicp_ctx {
   std::atomic<int> fault_inject_build{0};   // tests only: the n-th structure build from now fails (builds run on background threads)
   int fault_inject = 0, fault_inject_eval = 0;   // tests only: make the n-th search / exchanged evaluation from now fail locally before its collective
   // options / NN census (profiling only)
-  bool list_reuse = true;          // skip compaction + gather for edges whose list did not change
-  bool nn_tree_only = false;
   bool nn_census = false;          // count candidates / tree nodes per launch while profiling (small extra cost)
   void* d_census = nullptr; size_t census_bytes = 0;
   void* d_far_list = nullptr; size_t far_cap = 0; unsigned int* d_far_count = nullptr;  // nn_grid far-query list
   int far_parity = 0;              // d_far_count holds TWO counters used alternately; a launch zeroes the one the next launch will use
   unsigned int* h_far_seen = nullptr; unsigned int* d_far_seen = nullptr;   // mapped host word: far-list length of the last nn_far_kernel launch
-  bool prev_grid_kernel = false;   // the previous search ran nn_grid_kernel + nn_far_kernel (so h_far_seen describes it)
-  bool far_skip = false;           // set by mvicp_correspond: bit-identical queries after a grid round without far queries -> no far query, no phase-2 launch
-  bool far_narrow = false;         // this grid launch expects (almost) no far queries: narrow far-kernel launch (set by mvicp_correspond)
-  bool skip_dirty_reduce = false;  // set by mvicp_correspond for a search in which no list can change (see api.cpp)
-  bool nn_skip_far = false;        // PROFILING ONLY: leave unresolved queries unresolved (wrong results)
   double nn_search_factor = 4.0;   // the kernels look for a neighbour within this many cutoffs (0 = unbounded, like the reference's findNeighbors): a query the
                                    // cutoff rejects then still has a neighbour to seed next round's search with and a temporal-cache bound, instead of being
                                    // searched from scratch every round (partial overlap: a third of the queries); the filter of frame.cpp:156 is applied after
-  bool tie_lazy = true;            // single rank: the reference-equivalent trees (kdvisit.h) are built when a search first REPORTS a tie on a target without one (the
-                                   // search is then repeated once), like the reference's own lazily built index (frame.cpp:188-193) — synthetic clouds never tie, and
-                                   // the eager build was most of cfg5's set-up time.  N > 1 ranks build them at mvicp_set_graph (a repeated search is a collective)
-  bool tie_rule = true;            // exact distance ties are decided as nanoflann decides them (first visited; nn_tie.hip); false: lowest original index
   unsigned long long* d_tie_list = nullptr; size_t tie_cap = 0; unsigned int* d_tie_count = nullptr; int tie_parity = 0;   // queries reported by the NN kernels
   void* d_tie_deep = nullptr; size_t tie_deep_bytes = 0;   // per-lane walk stacks of nn_tie_deep_kernel (targets whose tree has more levels than the per-lane array)
   unsigned int* h_tie_seen = nullptr; unsigned int* d_tie_seen = nullptr;   // mapped host word: reports of the last fix-up launch (read after the round's wait)
-  unsigned int corr_tie_seen = 1u, corr_far_seen = 1u;   // what the LAST mvicp_correspond's own fix-up / far launch reported (read after its wait; 1 = unknown).
-                                   // mvicp_nn_query runs the same launches and overwrites the mapped words, so the skip decisions below use these copies
-  bool tie_skip = false;           // set by mvicp_correspond: a search that reproduces last round's queries bit for bit after a round without any report cannot report
   bool tile_seed = true;           // tile kernel starts from last round's neighbours when there are any
-  int tile_bounds = 1;             // 1: the AUTO round that would hand over to the grid kernel runs the tile kernel's BND build instead (it leaves the
-                                   // temporal-cache bounds, so the grid kernel starts with cache hits one round later and the uncached grid round — the
-                                   // slowest of a registration — never runs); 2: every tile round leaves bounds (tests); 0: off
-  int tile_cache = 1;              // AUTO, after the hand-over: rounds whose transforms still move run the tile kernel's bounds-leaving build WITH the
-                                   // temporal-cache check as its prologue (missed lanes are searched wave-cooperatively) instead of the grid kernel
-  double cache_mfma_ratio = 3.0;   // cache-aware rounds run on the matrix-pipe build when the median displacement bound of the queries exceeds this many guard bands
-                                   // (eps / mu; 0 = never: always nn_tile_kernel).  Measured (profiles/r06_tile_ab.txt): eps / mu <= 2.2 <-> hit rates >= 0.86 (nn_tile_kernel +
-                                   // miss_block faster), eps / mu >= 3.4 <-> hit rates <= 0.77 (nn_mfma_kernel 6-12 % faster)
-  bool cached_on_mfma = false;     // this launch's decision (api.cpp -> launch_nn_tile_edges)
   bool reject_cache = true;        // cache-aware rounds: "provably still rejected by the cutoff" counts as a temporal-cache hit (nn_tile.hip / nn_mfma.hip prologue)
   int tile_miss = 8;               // cache-aware rounds: waves with at most this many missed lanes use nn_tile.hip's miss_block (0 = off)
-  double tile_mu = 0.02;           // BND guard band as a fraction of the target's hash-cell edge (same role as prune_rho in the grid kernel); round 3 sweep on cfg4
-                                   // (hand-over round + the two cache-aware rounds after it): 0.02 -> 2.06 ms, 0.05 -> 2.11, 0.1 -> 2.23, 0.2 -> 2.45
-  int tile_mfma = 1;               // tile method: 1 = the screen of an opened tile runs on the matrix pipe (nn_mfma.hip) except in cache-aware rounds, 2 = always,
-                                   // 0 = never (the fp32 VALU screen of nn_tile.hip)
   double mfma_kacc = 34.0;         // nn_mfma.hip: allowance for the fp32 accumulation inside one matrix instruction, in units of 2^-24 x sum |terms| (see tau_pieces)
   int mfma_lbt = 1;                // nn_mfma.hip: unseeded launches test every tile's box per lane before screening it (scan_block LBT)
   int mfma_entry = 0;              // nn_mfma.hip experiment (round 6): seeded launches enter at the seeds' blocks + one flat sweep over the block boxes instead of the top-down walk
   int mfma_trig = 2;               // nn_mfma.hip: a lane with more than this many screen hits in a tile triggers the nearest-first second screen
   int tile_waves = 0;              // nn_tile_kernel variant: waves per SIMD it is compiled for (0 = the measured best for the depth)
-  double auto_prev_dist = 0.0; int auto_last_method = -1; double auto_settle = 0.5;   // MVICP_NN_AUTO policy state (api.cpp)
-  double last_rms = -1.0;          // RMS residual at the end of the last mvicp_optimize since the last search (< 0: none): predicts the next NN distances
-  bool nn_cell = false;            // grid method: wave-cooperative cell-staging kernel (nn_cell_kernel) instead of the per-lane hash kernel.  Exact and
-                                   // tested at full size, but measured SLOWER on MI355X (cfg4 rounds 3-7: 5.4 / 3.2 / 2.3 / 1.7 / 1.0 ms vs 2.3 / 1.8 / 2.6 / 0.9 / 0.6 ms,
-                                   // profiles/r02_nn_cell_experiment.txt): off by default
-  double auto_switch = 1.0;        // AUTO: hand over from the tile kernel to the grid method once the median distance is below this many hash cells
   double prune_rho = 0.05;         // grid kernel: with a seed, skip block cells farther than seed distance + prune_rho * cell edge; 0 = off
   int grid_curve = 2;              // order of the sorted clouds: 0 Morton (Z-order) of the cells, 1 Hilbert of the cells, 2 balanced k-d order
   double grid_target = 5.0;        // points per occupied cell the cell-edge heuristic aims at (4-6 measure the same within 2 %)
@@ -485,9 +433,9 @@ namespace mvicp {
 // kernels (each defined in its own TU)
 int launch_nn_brute_edges(mvicp_ctx* c);                                             // nn_brute.hip
 int launch_nn_brute_queries(mvicp_ctx* c, const FrameDev& f, const double* d_q, int n, int* d_idx, double* d_d2);
-int launch_nn_grid_edges(mvicp_ctx* c, double d2_bound);                              // nn_grid.hip (d2_bound = the cutoff's; the search radius is search_bound())
+int launch_nn_grid_edges(mvicp_ctx* c, double d2_bound, const SearchPlan& plan);                          // nn_grid.hip (d2_bound = the cutoff's; the search radius is search_bound())
 double search_bound(const mvicp_ctx* c, double d2_bound);                               // api.cpp                              // nn_grid.hip
-int launch_nn_tile_edges(mvicp_ctx* c, double d2_bound, bool with_bounds, bool with_cache, bool with_list);
+int launch_nn_tile_edges(mvicp_ctx* c, double d2_bound, const SearchPlan& plan);   // nn_tile.hip: the build the plan chose (tile_lb, tile_cached, cached_on_mfma)
 int launch_nn_mfma_edges(mvicp_ctx* c, double d2_bound, bool with_bounds, bool with_cache, bool with_list);   // nn_mfma.hip
 int build_mfma(FrameDev& f, const double* sorted_pts);                                 // nn_mfma.hip (host, called by build_grid)
 int warm_nn_mfma(mvicp_ctx* c);

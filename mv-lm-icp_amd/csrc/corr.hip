@@ -488,7 +488,7 @@ static void launch_bracket_final(mvicp_ctx* c, unsigned int* cnt_lt, unsigned in
 int launch_select_bracket(mvicp_ctx* c) {
   if (c->E == 0) return MVICP_OK;
   double bytes = 0;
-  for (int e = 0; e < c->E; ++e) if (c->owned[e]) bytes += 8.0 * c->h_count[e];   // one full read of the key list
+  for (int e = 0; e < c->E; ++e) if (c->owned[e]) bytes += 8.0 * c->hist.h_count[e];   // one full read of the key list
   ProfScope ps(c, "select", bytes);
   unsigned int *cnt_lt, *cnt_mid, *hist;
   MV_CHECK(select_scratch(c, &cnt_lt, &cnt_mid, &hist));
@@ -503,7 +503,7 @@ int launch_select_bracket(mvicp_ctx* c) {
 int launch_select_median(mvicp_ctx* c, double d2_bound) {
   if (c->E == 0) return MVICP_OK;
   double bytes = 0;
-  for (int e = 0; e < c->E; ++e) if (c->owned[e]) bytes += 16.0 * c->h_count[e];   // two full reads of the key list (last round's length)
+  for (int e = 0; e < c->E; ++e) if (c->owned[e]) bytes += 16.0 * c->hist.h_count[e];   // two full reads of the key list (last round's length)
   ProfScope ps(c, "select", bytes);
   unsigned int *cnt_lt, *cnt_mid, *hist;
   MV_CHECK(select_scratch(c, &cnt_lt, &cnt_mid, &hist));

@@ -246,10 +246,10 @@ static double stream_pass_bytes(mvicp_ctx* c, int plane) {
   std::vector<char> src_counted((size_t)c->n_frames, 0);
   for (int e = 0; e < c->E; ++e) {
     if (!c->owned[e]) continue;
-    const double cnt = c->h_count[e];
+    const double cnt = c->hist.h_count[e];
     const int s = c->esrc[e];
     bytes += (plane ? 32.0 : 24.0) * cnt;
-    if (c->lin_share_p && c->lin_interleave && c->h_count[e] == c->frames[s].n) { if (!src_counted[s]) { bytes += 24.0 * cnt; src_counted[s] = 1; } }
+    if (c->lin_share_p && c->lin_interleave && c->hist.h_count[e] == c->frames[s].n) { if (!src_counted[s]) { bytes += 24.0 * cnt; src_counted[s] = 1; } }
     else bytes += 24.0 * cnt;
   }
   return bytes;

@@ -244,10 +244,10 @@ static double sym_pass_bytes(mvicp_ctx* c) {
   std::vector<char> src_counted((size_t)c->n_frames, 0);
   for (int e = 0; e < c->E; ++e) {
     if (!c->owned[e]) continue;
-    const double cnt = c->h_count[e];
+    const double cnt = c->hist.h_count[e];
     const int s = c->esrc[e];
     bytes += 48.0 * cnt;
-    if (c->lin_share_p && !c->explicit_list[e] && c->h_count[e] == c->frames[s].n) {
+    if (c->lin_share_p && !c->hist.explicit_list[e] && c->hist.h_count[e] == c->frames[s].n) {
       if (!c->lin_interleave) bytes += 48.0 * cnt;
       else if (!src_counted[s]) { bytes += 48.0 * cnt; src_counted[s] = 1; }
     } else {

@@ -2,7 +2,7 @@
 //
 // Last search left, per query, its neighbour and a lower bound L on the distance to every OTHER target (out_lb, fp32 rounded down).  Since
 // then the query moved by at most eps = |dM p + dv| (1 + 1e-9) + allowance (pose update; the edge's kEdgeXf block carries dM, dv and the rounding
-// allowance of api.cpp:cache_allowance_xf, which bounds what separates that figure from the distance between the two ROUNDED queries), so every
+// allowance of search_plan.h:cache_allowance_xf, which bounds what separates that figure from the distance between the two ROUNDED queries), so every
 // other target is still >= L - eps away: if the re-evaluated distance to the old neighbour is strictly below that, it is still the unique
 // nearest neighbour and its exact squared distance (reference arithmetic) is the answer — no search.
 #pragma once

@@ -948,11 +948,12 @@ GridView view_of(const FrameDev& f) {
   return v;
 }
 
-int run(mvicp_ctx* c, std::vector<GridJob>& jobs, double bound, const FrameDev* const* dst_of) {
+// plan: the search these jobs belong to (its skip decisions: search_plan.h); null for raw queries — no list to maintain, nothing skipped, nothing narrowed
+int run(mvicp_ctx* c, std::vector<GridJob>& jobs, double bound, const FrameDev* const* dst_of, const SearchPlan* plan) {
   if (jobs.empty()) return MVICP_OK;
   const double search = search_bound(c, bound);
   std::vector<TieJob> ties;
-  if (!(c->tie_skip && jobs[0].list.dirty_slots != nullptr)) {
+  if (!(plan && plan->tie_skip)) {
     double launch_q = 0;
     for (const GridJob& j : jobs) launch_q += j.n;
     const TieRef tref = tie_ref(c, (size_t)launch_q, 0u);
@@ -982,7 +983,7 @@ int run(mvicp_ctx* c, std::vector<GridJob>& jobs, double bound, const FrameDev* 
     MV_HIP(hipMalloc((void**)&c->d_far_list, sizeof(int2) * total_q));
     c->far_cap = total_q;
   }
-  const bool edge_path = jobs[0].list.dirty_slots != nullptr;   // dirty_reduce_kernel re-zeroes the counter after phase 2
+  const bool edge_path = plan != nullptr;   // dirty_reduce_kernel re-zeroes the counter after phase 2
   if (!c->d_far_count) {
     MV_HIP(hipMalloc((void**)&c->d_far_count, 2 * sizeof(unsigned int)));
     MV_HIP(hipMemsetAsync(c->d_far_count, 0, 2 * sizeof(unsigned int), c->stream));
@@ -997,26 +998,26 @@ int run(mvicp_ctx* c, std::vector<GridJob>& jobs, double bound, const FrameDev* 
     ProfScope ps(c, "nn_grid", 36.0 * nq);  // the phase-1 kernel alone: query 24 B + result 12 B; the rest comes from the census below (0 if the census is off)
     // edge searches on clouds with a brick map: the wave-cooperative cell-staging kernel; otherwise (raw queries, profiling
     // switches, grids too large for a dense brick map) the per-lane hash kernel
-    use_cell = c->nn_cell && !c->nn_tree_only && !c->nn_skip_far && edge_path;
+    use_cell = c->opt.nn_cell && !c->opt.nn_tree_only && !c->opt.nn_skip_far && edge_path;
     for (const GridJob& j : jobs) if (j.dst.bricks == nullptr || j.xf == nullptr) use_cell = false;
     std::snprintf(c->last_nn_launch, sizeof(c->last_nn_launch), "grid");
-    if (c->nn_tree_only)
+    if (c->opt.nn_tree_only)
       hipLaunchKernelGGL((nn_grid_kernel<true>), grid, dim3(NT), 0, c->stream, d_jobs, bound, search, d_stats, 0, (int2*)c->d_far_list, far_cnt, 0.0);
     else if (use_cell)
       hipLaunchKernelGGL(nn_cell_kernel, grid, dim3(NT), 0, c->stream, d_jobs, bound, search, d_stats, (int2*)c->d_far_list, far_cnt, c->prune_rho);
     else
-      hipLaunchKernelGGL((nn_grid_kernel<false>), grid, dim3(NT), 0, c->stream, d_jobs, bound, search, d_stats, c->nn_skip_far ? 1 : 0, (int2*)c->d_far_list, far_cnt,
+      hipLaunchKernelGGL((nn_grid_kernel<false>), grid, dim3(NT), 0, c->stream, d_jobs, bound, search, d_stats, c->opt.nn_skip_far ? 1 : 0, (int2*)c->d_far_list, far_cnt,
                          c->prune_rho);
   }
-  const bool launch_far = !(edge_path && c->far_skip), launch_dirty = edge_path && !c->skip_dirty_reduce;
+  const bool launch_far = !(plan && plan->far_skip), launch_dirty = plan && !plan->nothing_can_change;
   if (launch_far || launch_dirty) {
     ProfScope ps(c, "nn_far", 0.0);   // phase 2 + the list flags: their own scope, so that "nn_grid" times one kernel ("nn" = every nn_* scope together)
     // phase 2: persistent grid-stride launch (the far count is only known on the device)
     // With the temporal cache on, at most a fraction of a per cent of the queries ever reach the far list (0.1-0.2 % in the hand-over rounds,
     // none at the fixed point): a 2048-workgroup launch then costs 19-22 us to find an empty list — 128 workgroups walk the same list
-    // (grid-stride) and cost ~4 us.  Only at the fixed point (api.cpp sets far_narrow: every transform bit-identical to last search's): with
+    // (grid-stride) and cost ~4 us.  Only at the fixed point (the plan's far_narrow: every transform bit-identical to last search's): with
     // 0.2 % far queries (the 96 %-hit round of a hand-over) the narrow launch measured 0.1 ms SLOWER than the wide one.
-    const size_t far_wide = (edge_path && c->far_narrow) ? 128 : 256 * 8;
+    const size_t far_wide = (plan && plan->far_narrow) ? 128 : 256 * 8;
     const unsigned int far_blocks = (unsigned int)std::min<size_t>(far_wide, (total_q * 8 + NT - 1) / NT);
     if (!c->h_far_seen) {
       MV_HIP(hipHostMalloc((void**)&c->h_far_seen, sizeof(unsigned int), hipHostMallocMapped));
@@ -1024,17 +1025,17 @@ int run(mvicp_ctx* c, std::vector<GridJob>& jobs, double bound, const FrameDev* 
       MV_HIP(hipHostGetDevicePointer((void**)&c->d_far_seen, c->h_far_seen, 0));
     }
     // (at the fixed point — every query bit-identical to last round's — a round that follows one without far queries has none either:
-    // its counter stays zero and phase 2 is not launched at all, api.cpp far_skip)
+    // its counter stays zero and phase 2 is not launched at all, the plan's far_skip)
     if (launch_far)
       hipLaunchKernelGGL(nn_far_kernel, dim3(far_blocks), dim3(NT), 0, c->stream, d_jobs, (const int2*)c->d_far_list, bound, (const unsigned int*)far_cnt, far_next, d_stats, slots,
                          edge_path ? c->d_far_seen : nullptr);
-    // per-edge OR of the "list changed" slots — not needed when the host already knows that nothing can change (api.cpp: every
+    // per-edge OR of the "list changed" slots — not needed when the host already knows that nothing can change (search_plan.h: every
     // transform bit-identical, every list valid): no query marks a slot then
     if (launch_dirty)
       hipLaunchKernelGGL(dirty_reduce_kernel, dim3(c->E), dim3(256), 0, c->stream, c->E, c->d_dslot_off, c->d_dirty_slots, c->d_dirty);
   }
   MV_HIP(hipGetLastError());
-  if (d_stats) MV_CHECK(census_collect(c, d_stats, slots, nq, c->nn_tree_only ? 1 : (use_cell ? 3 : 0), "nn_grid"));
+  if (d_stats) MV_CHECK(census_collect(c, d_stats, slots, nq, c->opt.nn_tree_only ? 1 : (use_cell ? 3 : 0), "nn_grid"));
   MV_CHECK(launch_tie_fixup(c, ties, bound));   // exact distance ties: the reference's own descent decides (nn_tie.hip)
   return MVICP_OK;
 }
@@ -1062,7 +1063,7 @@ int warm_nn_grid(mvicp_ctx* c) {
   return MVICP_OK;
 }
 
-int launch_nn_grid_edges(mvicp_ctx* c, double d2_bound) {
+int launch_nn_grid_edges(mvicp_ctx* c, double d2_bound, const SearchPlan& plan) {
   std::vector<GridJob> jobs;
   std::vector<const FrameDev*> dsts;
   for (int e = 0; e < c->E; ++e) {
@@ -1078,10 +1079,10 @@ int launch_nn_grid_edges(mvicp_ctx* c, double d2_bound) {
     j.inv = d.grid.inv; j.out_lb = c->d_nn_lb + c->cap_off[e];
     j.list = ListRef{c->d_qpos + c->cap_off[e], c->d_second + c->cap_off[e], c->d_cd2 + c->cap_off[e], c->d_dirty + e, c->d_dirty_slots + c->dslot_off[e],
                      c->d_stream + c->cap_off[e], c->total_cap, d.grid.snor, (const PointRec*)d.grid.srec};
-    j.seed = ((int)c->nn_cache_edge.size() == c->E && c->nn_cache_edge[e]) ? 1 : 0;
+    j.seed = ((int)c->hist.nn_cache_edge.size() == c->E && c->hist.nn_cache_edge[e]) ? 1 : 0;
     jobs.push_back(j); dsts.push_back(&d);
   }
-  return run(c, jobs, d2_bound, dsts.data());
+  return run(c, jobs, d2_bound, dsts.data(), &plan);
 }
 
 int launch_nn_grid_queries(mvicp_ctx* c, const FrameDev& f, const double* d_q, int n, int* d_idx, double* d_d2) {
@@ -1093,7 +1094,7 @@ int launch_nn_grid_queries(mvicp_ctx* c, const FrameDev& f, const double* d_q, i
   jobs[0].out_idx = d_idx; jobs[0].out_d2 = d_d2;
   jobs[0].inv = nullptr; jobs[0].out_lb = nullptr;   // (list stays zeroed: list.dirty null = no list to maintain)
   const FrameDev* dst = &f;
-  return run(c, jobs, 1.7976931348623157e308, &dst);
+  return run(c, jobs, 1.7976931348623157e308, &dst, nullptr);
 }
 
 }  // namespace mvicp

@@ -158,7 +158,7 @@ int ensure_tie_trees(mvicp_ctx* c, const std::vector<int>& frames) {
 
 TieRef tie_ref(mvicp_ctx* c, size_t launch_queries, unsigned int job) {
   TieRef T{nullptr, nullptr, 0u, job};
-  if (!c->tie_rule) return T;
+  if (!c->opt.tie_rule) return T;
   // capacity: every query of the launch up to 4 M entries (32 MB); beyond that an overflow makes the fix-up re-answer the whole launch
   const size_t want = std::min<size_t>(std::max<size_t>(launch_queries, 1024), (size_t)4 << 20);
   if (want > c->tie_cap) {
@@ -182,8 +182,7 @@ void tie_job_fill(const FrameDev& F, TieJob& j) {
 }
 
 int launch_tie_fixup(mvicp_ctx* c, const std::vector<TieJob>& jobs, double d2_bound) {
-  if (!c->tie_rule || jobs.empty() || !c->d_tie_count) return MVICP_OK;
-  if (c->tie_skip) return MVICP_OK;   // (the launch's counter stays zero and keeps its turn)
+  if (!c->opt.tie_rule || jobs.empty() || !c->d_tie_count) return MVICP_OK;
   if (!c->h_tie_seen) {
     MV_HIP(hipHostMalloc((void**)&c->h_tie_seen, 4 * sizeof(unsigned int), hipHostMallocMapped));   // [0] reports of the launch, [1] "a reported query's target has no tree", [2] "a walk ran out of stack"
     c->h_tie_seen[0] = 1u;   // unknown until a launch has written it

@@ -422,11 +422,12 @@ int warm_nn_tile(mvicp_ctx* c) {   // see warm_nn_grid (nn_grid.hip): loads this
   return MVICP_OK;
 }
 
-int launch_nn_tile_edges(mvicp_ctx* c, double d2_bound, bool with_bounds, bool with_cache, bool with_list) {
+int launch_nn_tile_edges(mvicp_ctx* c, double d2_bound, const SearchPlan& plan) {
+  const bool with_bounds = plan.tile_lb, with_cache = plan.tile_cached, with_list = c->opt.list_reuse;
   // the matrix-pipe build of the same search (nn_mfma.hip).  Cache-aware rounds (a few missed lanes per wave) stay here by default: with
   // most lanes finished by the cache the per-lane box tests prune nearly every tile, and the 7-wave occupancy of this build hides the
   // latency of the few that remain (cfg4 rounds 6 / 7: 0.57 / 0.38 ms here against 0.65 / 0.57 ms there)
-  if (c->tile_mfma >= 2 || (c->tile_mfma == 1 && (!with_cache || c->cached_on_mfma))) return launch_nn_mfma_edges(c, d2_bound, with_bounds, with_cache, with_list);
+  if (c->opt.tile_mfma >= 2 || (c->opt.tile_mfma == 1 && (!with_cache || plan.cached_on_mfma))) return launch_nn_mfma_edges(c, d2_bound, with_bounds, with_cache, with_list);
   return launch_tile_search(c, d2_bound, with_bounds, with_cache, with_list, TT, "nn_tile", [&](const std::vector<TileJob>&, const TileJob* d_jobs, dim3 grid, int top, unsigned long long* d_stats) {
     // every arm names the instantiation it launches ("tile<WPE,TOP,BND>": mvicp_last_nn_launch; tests/depthcases.py parses the arms below)
 #define MVICP_TILE_K(W, T, B) do { std::snprintf(c->last_nn_launch, sizeof(c->last_nn_launch), "tile<%d,%d,%d>", W, T, (int)B); \

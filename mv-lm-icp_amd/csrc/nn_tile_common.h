@@ -286,8 +286,8 @@ inline int build_tile_jobs(mvicp_ctx* c, bool with_bounds, bool with_cache, bool
     j.q = s.grid.spts; j.qidx = nullptr; j.xf = c->d_xf + (size_t)e * kEdgeXf; j.n = s.n;
     j.out_idx = c->d_nn_idx + c->cap_off[e]; j.out_d2 = c->d_nn_d2 + c->cap_off[e];
     j.inv = d.grid.inv;
-    j.seed = (c->tile_seed && (int)c->nn_cache_edge.size() == c->E && c->nn_cache_edge[e]) ? 1 : 0;
-    if (with_bounds) { j.out_lb = c->d_nn_lb + c->cap_off[e]; j.mu = (float)(c->tile_mu * d.grid.cell); }
+    j.seed = (c->tile_seed && (int)c->hist.nn_cache_edge.size() == c->E && c->hist.nn_cache_edge[e]) ? 1 : 0;
+    if (with_bounds) { j.out_lb = c->d_nn_lb + c->cap_off[e]; j.mu = (float)(c->opt.tile_mu * d.grid.cell); }
     if (with_bounds && with_cache) { j.cache = 1; j.miss_max = c->tile_miss; j.reject_cache = c->reject_cache ? 1 : 0; }
     if (with_list) {
       j.list = ListRef{c->d_qpos + c->cap_off[e], c->d_second + c->cap_off[e], c->d_cd2 + c->cap_off[e], c->d_dirty + e, c->d_dirty_slots + c->dslot_off[e],

@@ -369,7 +369,7 @@ int normal_agreement(mvicp_ctx* c, const double* poses, const char* use, int* po
   int* cnt = reinterpret_cast<int*>(h + o_cnt);
   bool any = false;
   for (int e = 0; e < E; ++e) {
-    cnt[e] = use[e] ? c->h_count[e] : 0;
+    cnt[e] = use[e] ? c->hist.h_count[e] : 0;
     ns[e] = c->frames[c->esrc[e]].grid.snor; nd[e] = c->frames[c->edst[e]].grid.snor;
     any = any || cnt[e] > 0;
   }

@@ -321,15 +321,15 @@ static int optimize_metric(mvicp_ctx* c, double* poses, unsigned char* fixed, in
   HostScope hs(c, "host.optimize");
   // what the NEXT search may evaluate ahead of time (api.cpp, speculative first evaluation)
   const bool sym = metric == MVICP_METRIC_SYMMETRIC;
-  if (sym) c->spec_flags_valid = false;
-  else { c->spec_flags_valid = true; c->spec_param = param; c->spec_plane = metric; c->spec_robust = robust ? 1 : 0; }
+  if (sym) c->hist.spec_flags_valid = false;
+  else { c->hist.spec_flags_valid = true; c->hist.spec_param = param; c->hist.spec_plane = metric; c->hist.spec_robust = robust ? 1 : 0; }
   CtxEval u{c, metric, robust ? 1 : 0};
   const int st = lm_solve(c->n_frames, c->E, c->esrc.data(), c->edst.data(), poses, fixed, param, max_iterations, ctx_eval, &u, summary);
-  if (st != MVICP_OK || sym) { c->spec_flags_valid = false; c->spec_ready = false; c->spec2_ready = false; c->last_cand_poses.clear(); }   // a failed solve must not arm the next search's queued evaluation
+  if (st != MVICP_OK || sym) { c->hist.spec_flags_valid = false; c->spec_ready = false; c->spec2_ready = false; c->hist.last_cand_poses.clear(); }   // a failed solve must not arm the next search's queued evaluation
   if (st == MVICP_OK && summary) {   // feeds the AUTO kernel choice of the next search (api.cpp): RMS residual the solve ended on
     double n = 0.0;
-    for (int e = 0; e < c->E; ++e) n += c->h_count[e];
-    c->last_rms = n > 0.0 && summary->final_cost >= 0.0 ? std::sqrt(2.0 * summary->final_cost / n) : -1.0;
+    for (int e = 0; e < c->E; ++e) n += c->hist.h_count[e];
+    c->hist.last_rms = n > 0.0 && summary->final_cost >= 0.0 ? std::sqrt(2.0 * summary->final_cost / n) : -1.0;
   }
   if (c->profile) prof_collect_lazy(c);
   return st;

@@ -5,7 +5,7 @@ on the PLACED inputs, never with the unplaced run.  A scripted pose sequence is 
 moves applied as pose @ T_small like the cache tests of test_gpu_parity.py) and every pose set of it is placed, so that the physical
 motion of a round is the same under every placement.
 
-`query_block`, `xf_point` and `inverse3` restate csrc/api.cpp:fill_query_xf / inverse3 and csrc/nn_metric.h:xf_point operation by
+`query_block`, `xf_point` and `inverse3` restate csrc/search_plan.h:fill_query_xf / inverse3 and csrc/nn_metric.h:xf_point operation by
 operation; run on np.longdouble inputs the same code is the extended-precision map."""
 import numpy as np
 
