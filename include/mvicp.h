@@ -790,6 +790,33 @@ typedef enum { MVICP_METRIC_POINT = 0, MVICP_METRIC_PLANE = 1, MVICP_METRIC_SYMM
  * source of a non-empty list has no normals ("symmetric needs normals on frame i") -> MVICP_ERR_STATE. */
 int mvicp_linearize_metric(mvicp_ctx* ctx, const double* poses, int metric, int robust, double* out);
 
+/* The plane-to-plane objective: Generalized-ICP (Segal, Haehnel, Thrun, RSS 2009) in its standard form, where the covariance of a point is a
+ * function of its normal alone, C(n) = I - (1 - epsilon) n^ n^T: epsilon along the normal, 1 in the tangent plane.  Per correspondence, with
+ * the relative transform (A, t) of the edge formed as for SYMMETRIC (the true inverse of R_d in extended precision, hi + lo parts):
+ *     p~ = A p + t,   f = p~ - q,   nu = A n_p
+ *     P(n) = n n^T / (n . n)  if n . n (as computed in fp64) is finite and > 0,  else the zero matrix      (such a normal means C = I)
+ *     S = 2 I - (1 - epsilon) (P(n_q) + P(nu)),      W = 2 epsilon S^-1                  (symmetric, eigenvalues in [epsilon, 1])
+ *     s = f^T W f
+ *     J_f = [ A , -A [p]x , -I , [p~]x ]                                  (3 x 12, coordinates [ups_s om_s ups_d om_d], T <- T exp(delta))
+ *     H = sum w J_f^T W J_f,   g = sum w J_f^T W f,   cost = sum rho(s) / 2
+ * The loss, the corrector weight w, the scale a = edge.weight and the cost are those of POINT: soft-L1 on the squared length of a three-vector.
+ * W IS FROZEN: it is held at its value at the evaluation poses, fixed in the destination frame, while f is differentiated — the Gauss-Newton
+ * form of Segal's section III, of PCL and of Open3D; the term with dW / d(pose) is dropped.  The cost returned at candidate poses uses W at those
+ * poses.  The factor 2 epsilon makes the largest weight 1, so s <= |f|^2 and the robust scale keeps its meaning.  epsilon = 1 is POINT's
+ * objective (W = I: the same cost and the same g; H differs from POINT's in the om_d blocks by terms of first order in f, because f is the
+ * residual in the destination frame, whose om_d rows are [p~]x where POINT's are [q]x).  With agreeing unit normals
+ * W = epsilon I + (1 - epsilon) n n^T: PLANE in the limit epsilon -> 0.
+ * THE NORMALS ARE USED AS STORED, and P(n) depends on neither the sign nor the length of n: their orientation does not matter for this
+ * objective.  The source normal is the source frame's current one (after mvicp_recompute_normals the next evaluation sees the new normals).
+ * epsilon must be finite and within [1e-6, 1]; anything else -> MVICP_ERR_ARG.
+ * The evaluation takes the ordinary route (relative transforms and scales uploaded, one launch, the all-reduce when an exchange is configured,
+ * one wait; profile scope "linearize_gicp") and is never queued or paired.  Non-OK returns as mvicp_linearize, and: while the destination OR
+ * the source of a non-empty list has no normals ("gicp needs normals on frame i") -> MVICP_ERR_STATE.  A refused call changes nothing.
+ * Accuracy contract: the symmetric objective's — per piece at most 32 x the error of a plain fp64 evaluation of the direct rows against a
+ * long-double reference (tests/test_gpu_gicp_accuracy.py, tests/gicpref.py).  Kernel: csrc/linearize_gicp.hip.
+ * This objective has NO mvicp_metric value: the metric calls refuse 3 as before. */
+int mvicp_linearize_gicp(mvicp_ctx* ctx, const double* poses, double epsilon, int robust, double* out);
+
 /* ---- S2: the LM solve ----------------------------------------------------------------------------
  * Replaces ICP_Ceres::ceresOptimizer / _ceresAngleAxis / _sophusSE3 (frames, pointToPlane, robust)
  * (include/icp-ceres.h:40-42; caller main_multiview.cpp:158-161).  poses in/out (frames[i]->pose).
@@ -819,6 +846,10 @@ int mvicp_optimize(mvicp_ctx* ctx, double* poses, unsigned char* fixed, int para
  * solve does: the search after it queues no evaluation.  A metric outside mvicp_metric -> MVICP_ERR_ARG. */
 int mvicp_optimize_metric(mvicp_ctx* ctx, double* poses, unsigned char* fixed, int param, int metric, int robust,
                           int max_iterations, mvicp_summary* summary);
+/* mvicp_optimize over the plane-to-plane objective (mvicp_linearize_gicp above; epsilon within [1e-6, 1], else MVICP_ERR_ARG).  Like a
+ * SYMMETRIC solve it arms nothing and voids what is queued: the search after it queues no evaluation. */
+int mvicp_optimize_gicp(mvicp_ctx* ctx, double* poses, unsigned char* fixed, int param, double epsilon, int robust,
+                        int max_iterations, mvicp_summary* summary);
 
 /* Host-only form of the same solver over a caller-supplied evaluator (no GPU touched by this call):
  * eval(user, poses[n_frames x 16], blocks[n_edges x 91]) must fill the per-edge canonical blocks exactly

@@ -398,12 +398,12 @@ static void throttle_builds(mvicp_ctx* c) {
 // (`metric` is an mvicp_metric: 0 point, 1 plane, 2 symmetric — the older entry points hand in their point_to_plane flag as 0 / 1)
 static int check_evaluable(mvicp_ctx* c, int metric) {
   if (!c->hist.have_corr) { set_error("no correspondences: call mvicp_correspond or mvicp_set_correspondences first"); return MVICP_ERR_STATE; }
-  if (metric == MVICP_METRIC_SYMMETRIC) {
-    // the mean normal needs both: the destination's (baked into the operand stream) and the source's (read from its sorted normals)
+  if (metric == MVICP_METRIC_SYMMETRIC || metric == kMetricGicp) {
+    // the mean normal, and the sum of the two covariances, need both normals: the destination's (baked into the operand stream) and the source's (read from its sorted normals)
     for (int e = 0; e < c->E; ++e)
       if (c->owned[e] && c->hist.h_count[e] > 0) {
         const int missing = c->frames[c->edst[e]].grid.snor == nullptr ? c->edst[e] : c->frames[c->esrc[e]].grid.snor == nullptr ? c->esrc[e] : -1;
-        if (missing >= 0) { set_error("symmetric needs normals on frame %d", missing); return MVICP_ERR_STATE; }
+        if (missing >= 0) { set_error("%s needs normals on frame %d", metric == kMetricGicp ? "gicp" : "symmetric", missing); return MVICP_ERR_STATE; }
       }
   } else if (metric) {
     for (int e = 0; e < c->E; ++e)
@@ -434,10 +434,12 @@ int evaluate_pair(mvicp_ctx* c, const double* poses_a, const double* poses_b, in
 
 // One launch of the metric's accumulation kernel + the per-edge expansion on the uploaded relative transforms
 static int launch_metric(mvicp_ctx* c, int metric, int robust) {
+  if (metric == kMetricGicp) return launch_linearize_gicp(c, c->gicp_eps, robust);
   return metric == MVICP_METRIC_SYMMETRIC ? launch_linearize_sym(c, robust) : launch_linearize(c, metric, robust);
 }
 
-// `plane` is the metric (0 point, 1 plane, 2 symmetric).  Only point and plane evaluations are ever queued ahead, so a symmetric one matches no
+// `plane` is the metric (0 point, 1 plane, 2 symmetric, kMetricGicp plane-to-plane at c->gicp_eps).  Only point and plane evaluations are ever queued ahead, so a symmetric
+// or plane-to-plane one matches no
 // queued result (spec_q_plane / spec2_plane are 0 or 1), drops them like any evaluation they were not made for, and takes the ordinary route below.
 // With an exchange configured a refusal of check_evaluable is a LOCAL verdict (it looks at the edges this rank owns: only the owner knows the count of
 // an explicit list), so it is treated like a failed local launch: the rank enters the evaluation's collective with the slot poisoned, and every
@@ -482,7 +484,7 @@ int evaluate_blocks(mvicp_ctx* c, const double* poses, int plane, int robust, do
     // failure reaches every rank through the collective instead of leaving the peers blocked in it (see mvicp_correspond).
     c->lin_out = c->d_out;
     int st_l = st_chk;
-    if (st_l == MVICP_OK) st_l = plane == MVICP_METRIC_SYMMETRIC ? upload_rel_sym(c, poses) : upload_rel(c, poses);
+    if (st_l == MVICP_OK) st_l = (plane == MVICP_METRIC_SYMMETRIC || plane == kMetricGicp) ? upload_rel_sym(c, poses) : upload_rel(c, poses);
     if (st_l == MVICP_OK && c->fault_inject_eval > 0 && --c->fault_inject_eval == 0) { set_error("injected launch failure (option fault_inject_eval)"); st_l = MVICP_ERR_HIP; }
     if (st_l == MVICP_OK) st_l = launch_metric(c, plane, robust);
     char local_msg[sizeof(g_err)] = "";
@@ -503,7 +505,7 @@ int evaluate_blocks(mvicp_ctx* c, const double* poses, int plane, int robust, do
     std::memcpy(out, hx, sizeof(double) * n);
     return MVICP_OK;
   } else {
-    MV_CHECK(plane == MVICP_METRIC_SYMMETRIC ? upload_rel_sym(c, poses) : upload_rel(c, poses));
+    MV_CHECK((plane == MVICP_METRIC_SYMMETRIC || plane == kMetricGicp) ? upload_rel_sym(c, poses) : upload_rel(c, poses));
     c->lin_out = c->d_blocks_host;   // 8 * 91 * E bytes: the reduce kernel stores them straight into mapped host memory
     MV_CHECK(launch_metric(c, plane, robust));
   }
@@ -2146,6 +2148,18 @@ int mvicp_linearize_metric(mvicp_ctx* c, const double* poses, int metric, int ro
   if (!poses || !out) { set_error("null argument"); return MVICP_ERR_ARG; }
   if (c->E == 0) { set_error("no graph"); return MVICP_ERR_STATE; }
   MV_CHECK(evaluate_blocks(c, poses, metric, robust, out));
+  if (c->profile) prof_collect_lazy(c);
+  return MVICP_OK;
+} MVICP_GUARD_ABI
+
+// The plane-to-plane objective: an entry point of its own because epsilon does not fit mvicp_linearize_metric (mvicp_metric stays as it is)
+int mvicp_linearize_gicp(mvicp_ctx* c, const double* poses, double epsilon, int robust, double* out) try {
+  if (!gicp_epsilon_ok(epsilon)) { set_error("gicp epsilon %g is not within [1e-6, 1]", epsilon); return MVICP_ERR_ARG; }
+  MV_CHECK(bind(c));
+  if (!poses || !out) { set_error("null argument"); return MVICP_ERR_ARG; }
+  if (c->E == 0) { set_error("no graph"); return MVICP_ERR_STATE; }
+  c->gicp_eps = epsilon;
+  MV_CHECK(evaluate_blocks(c, poses, kMetricGicp, robust, out));
   if (c->profile) prof_collect_lazy(c);
   return MVICP_OK;
 } MVICP_GUARD_ABI

@@ -323,6 +323,7 @@ struct mvicp_ctx {
   std::vector<int> chunk_first;     // E+1
   int* d_chunk_edge = nullptr; int* d_chunk_start = nullptr; int* d_chunk_first = nullptr;
   double* d_partials = nullptr;     // 2 x n_chunks x kLinPartial (second half: the second pose set of a paired launch)
+  double gicp_eps = 1e-3;           // the epsilon of the plane-to-plane evaluation under way (mvicp_linearize_gicp / mvicp_optimize_gicp set it before evaluate_blocks(kMetricGicp))
   mvicp::PinBuf sym_lo_pin; mvicp::DevBuf sym_lo_dev;   // E x kEdgeRel doubles: low parts of the relative transforms of a symmetric evaluation (api.cpp upload_rel_sym,
                                     // linearize_sym.hip); buffers of their own, allocated by the first symmetric evaluation of a graph, released with the graph
   double* d_out = nullptr;          // E x 91 blocks | E x 2 (count, median d2) | 1 "armed" slot: ONE buffer, so that with N > 1 ranks a round's
@@ -512,6 +513,9 @@ int launch_export(mvicp_ctx* c);           // export.hip: every exportable edge'
 int launch_select_bracket(mvicp_ctx* c);   // one-pass select around last round's medians (d_sel_lohi); flags edges it cannot answer
 int launch_linearize(mvicp_ctx* c, int plane, int robust);                            // linearize.hip
 int launch_linearize_pair(mvicp_ctx* c, int plane, int robust, double* out_a, double* out_b);   // linearize.hip: d_rel -> out_a, d_rel2 -> out_b, one pass
+constexpr int kMetricGicp = 3;   // the plane-to-plane objective inside the library (evaluate_blocks, check_evaluable); NOT an mvicp_metric: the metric calls refuse 3
+inline bool gicp_epsilon_ok(double eps) { return eps >= 1e-6 && eps <= 1.0; }   // (false for a NaN)
+int launch_linearize_gicp(mvicp_ctx* c, double eps, int robust);                      // linearize_gicp.hip: the plane-to-plane objective, the symmetric launch's tables / partials / outputs
 int launch_linearize_sym(mvicp_ctx* c, int robust);                                   // linearize_sym.hip: the symmetric objective, same tables / partials / outputs as launch_linearize
 int launch_normals(mvicp_ctx* c, FrameDev& f, int k, int* d_knn);                      // normals.hip
 int stream_wait(mvicp_ctx* c);      // api.cpp: wait for the context's stream (spin-polls first)

@@ -187,6 +187,29 @@ static int source_table(mvicp_ctx* c, const double* const** d_src) {
   return MVICP_OK;
 }
 
+// algorithmic bytes of one symmetric or plane-to-plane pass (linearize_sym.hip, linearize_gicp.hip: the same operands by the same routes):
+// 48 B (n_q, q) per correspondence + 24 B p + 24 B n_p — per correspondence, plus the 4-B index, when the edge
+// reads its private p from the stream and gathers n_p, ONCE PER SOURCE POINT for the edges of one source cloud that read the sorted cloud side by side.
+// The condition is the kernel's own: a searched list that holds every source point with lin_share_p on (an explicit list never is the identity,
+// mvicp_set_correspondences), and the second reader's hit needs lin_interleave; stream_pass_bytes in linearize.hip is coarser on both points.
+static double sym_pass_bytes(mvicp_ctx* c) {
+  double bytes = 0;
+  std::vector<char> src_counted((size_t)c->n_frames, 0);
+  for (int e = 0; e < c->E; ++e) {
+    if (!c->owned[e]) continue;
+    const double cnt = c->hist.h_count[e];
+    const int s = c->esrc[e];
+    bytes += 48.0 * cnt;
+    if (c->lin_share_p && !c->hist.explicit_list[e] && c->hist.h_count[e] == c->frames[s].n) {
+      if (!c->lin_interleave) bytes += 48.0 * cnt;
+      else if (!src_counted[s]) { bytes += 48.0 * cnt; src_counted[s] = 1; }
+    } else {
+      bytes += 52.0 * cnt;
+    }
+  }
+  return bytes;
+}
+
 }  // namespace
 
 }  // namespace mvicp

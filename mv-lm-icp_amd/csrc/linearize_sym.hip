@@ -17,7 +17,7 @@
 //   x'_i  = fma(A[i+6], p2, fma(A[i+3], p1, A[i] * p0))          (A column-major; as accumulate<> in linearize.hip)
 //   nu_i  = fma(A[i+6], s2, fma(A[i+3], s1, A[i] * s0))          (s = n_p)
 //   m_i   = 0.5 * (n_i + nu_i)                                   (n = n_q)
-//   f_i   = residual_component(): h_k = A[i+3k] * p_k with its exact error g_k = fma(A[i+3k], p_k, -h_k); TwoSum chain s1 = h_0 + h_1, s2 = s1 + h_2, s3 = s2 + t_i,
+//   f_i   = residual_component() (lin_residual.h): h_k = A[i+3k] * p_k with its exact error g_k = fma(A[i+3k], p_k, -h_k); TwoSum chain s1 = h_0 + h_1, s2 = s1 + h_2, s3 = s2 + t_i,
 //           s4 = s3 - q_i with errors e1..e4;  f_i = s4 + ((((e1 + e2) + (e3 + e4)) + ((g_0 + g_1) + g_2)) + fma(Alo[i+6], p2, fma(Alo[i+3], p1, fma(Alo[i], p0, tlo_i))))
 //   d_i   = q_i - t_i
 //   r     = fma(m2, f2, fma(m1, f1, m0 * f0))
@@ -36,38 +36,11 @@
 // The gather index of the step AFTER the next is loaded one step early, so its latency is not on the path of the prefetch that depends on it.
 // Mapping, chunk tables, partial slots: those of linearize_kernel (launch_linearize's tables; the XCD interleave comes with them).
 #include "lin_common.h"
+#include "lin_residual.h"
 
 namespace mvicp {
 
 namespace {
-
-// s = fl(a + b) and e with a + b = s + e exactly (Knuth's TwoSum: no assumption on the magnitudes)
-__device__ __forceinline__ double two_sum(double a, double b, double& e) {
-#pragma clang fp contract(off)
-  const double s = a + b;
-  const double bb = s - a;
-  e = (a - (s - bb)) + (b - bb);
-  return s;
-}
-
-// One component of f = A p + t - q, a small difference of large terms, to a relative error of a few 2^-53 OF f ITSELF: the three products with their exact
-// errors (fma), the five terms added by TwoSum, the errors and the low parts of (A, t) added at the end.  The plain form ((x' + t) - q) carries the rounding of
-// x' and of x' + t, 2^-53 (|x'| + |t|) per correspondence: against residuals of 5e-4 on clouds of extent 0.4 that is 1e-14 of the cost and of g over 1 500
-// correspondences — the size of a plain fp64 evaluation's own error there, and over 32 x it whenever that evaluation happens to be lucky
-// (tests/test_gpu_sym_regimes.py met that in 6 of 4 140 pieces).  The 37 flops per component are NOT hidden behind the operand traffic at two waves per SIMD:
-// measured at cfg4's shape the launch went from 153 to 166 - 173 us.
-// Contraction is switched off in both functions: a product fused into the sum that follows it would make that sum something other than fl(h_0 + h_1).
-__device__ __forceinline__ double residual_component(double a0, double a1, double a2, double t, double p0, double p1, double p2, double q, double lo) {
-#pragma clang fp contract(off)
-  const double h0 = a0 * p0, h1 = a1 * p1, h2 = a2 * p2;
-  const double g0 = __builtin_fma(a0, p0, -h0), g1 = __builtin_fma(a1, p1, -h1), g2 = __builtin_fma(a2, p2, -h2);
-  double e1, e2, e3, e4;
-  const double s1 = two_sum(h0, h1, e1);
-  const double s2 = two_sum(s1, h2, e2);
-  const double s3 = two_sum(s2, t, e3);
-  const double s4 = two_sum(s3, -q, e4);
-  return s4 + ((((e1 + e2) + (e3 + e4)) + ((g0 + g1) + g2)) + lo);
-}
 
 template <bool ROBUST>
 __device__ __forceinline__ void accumulate_sym(double (&acc)[NACC], const double* __restrict__ A, const double* __restrict__ t, const double* __restrict__ lo, double inv_a2,
@@ -234,28 +207,6 @@ __global__ __launch_bounds__(NT) void linearize_sym_kernel(const int* __restrict
 }
 
 }  // namespace
-
-// algorithmic bytes of one symmetric pass: 48 B (n_q, q) per correspondence + 24 B p + 24 B n_p — per correspondence, plus the 4-B index, when the edge
-// reads its private p from the stream and gathers n_p, ONCE PER SOURCE POINT for the edges of one source cloud that read the sorted cloud side by side.
-// The condition is the kernel's own: a searched list that holds every source point with lin_share_p on (an explicit list never is the identity,
-// mvicp_set_correspondences), and the second reader's hit needs lin_interleave; stream_pass_bytes in linearize.hip is coarser on both points.
-static double sym_pass_bytes(mvicp_ctx* c) {
-  double bytes = 0;
-  std::vector<char> src_counted((size_t)c->n_frames, 0);
-  for (int e = 0; e < c->E; ++e) {
-    if (!c->owned[e]) continue;
-    const double cnt = c->hist.h_count[e];
-    const int s = c->esrc[e];
-    bytes += 48.0 * cnt;
-    if (c->lin_share_p && !c->hist.explicit_list[e] && c->hist.h_count[e] == c->frames[s].n) {
-      if (!c->lin_interleave) bytes += 48.0 * cnt;
-      else if (!src_counted[s]) { bytes += 48.0 * cnt; src_counted[s] = 1; }
-    } else {
-      bytes += 52.0 * cnt;
-    }
-  }
-  return bytes;
-}
 
 int launch_linearize_sym(mvicp_ctx* c, int robust) {
   if (c->E == 0) return MVICP_OK;

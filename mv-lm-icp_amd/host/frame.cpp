@@ -282,6 +282,18 @@ void Session::optimize(std::vector<std::shared_ptr<Frame>>& frames, int param, m
   if (out) *out = sm;
 }
 
+void Session::optimizeGicp(std::vector<std::shared_ptr<Frame>>& frames, int param, double epsilon, bool robust, mvicp_summary* out) {
+  bind(frames);
+  std::vector<double> P(16 * frames.size());
+  std::vector<unsigned char> fx(frames.size());
+  for (size_t i = 0; i < frames.size(); ++i) { std::memcpy(&P[16 * i], frames[i]->pose.data(), 128); fx[i] = frames[i]->fixed; }
+  mvicp_summary sm;
+  check(mvicp_optimize_gicp(ctx, P.data(), fx.data(), param, epsilon, robust, 50 /* icp-ceres.cpp:81 */, &sm));
+  if (!frames.empty()) frames[0]->fixed = true;  // icp-ceres.cpp:244,341,417
+  for (size_t i = 0; i < frames.size(); ++i) std::memcpy(frames[i]->pose.data(), &P[16 * i], 128);
+  if (out) *out = sm;
+}
+
 void Frame::computePoseNeighboursKnn(std::vector<std::shared_ptr<Frame>>* frames, int i, int k) {
   neighbours.clear();
   const Vector3d t1 = pose.translation();

@@ -204,6 +204,8 @@ struct Session {
   void optimize(std::vector<std::shared_ptr<Frame>>& frames, int param, bool pointToPlane, bool robust, mvicp_summary* sm = nullptr);
   // the same with the objective named (MVICP_METRIC_SYMMETRIC needs normals on every frame, oriented consistently)
   void optimize(std::vector<std::shared_ptr<Frame>>& frames, int param, mvicp_metric metric, bool robust, mvicp_summary* sm = nullptr);
+  // the plane-to-plane (Generalized-ICP) objective at the given epsilon (mvicp_optimize_gicp): needs normals on every frame, in any orientation
+  void optimizeGicp(std::vector<std::shared_ptr<Frame>>& frames, int param, double epsilon, bool robust, mvicp_summary* sm = nullptr);
   void reset();
 };
 

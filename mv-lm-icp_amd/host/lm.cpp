@@ -311,7 +311,7 @@ int mvicp_lm_solve(int n_frames, int n_edges, const int* src, const int* dst, do
   return lm_solve(n_frames, n_edges, src, dst, poses, fixed, param, max_iterations, eval, user, summary);
 } MVICP_GUARD_ABI
 
-// mvicp_optimize with the objective named (metric: an mvicp_metric, already checked).  Point and plane solves arm the evaluations the next search queues
+// mvicp_optimize with the objective named (metric: an mvicp_metric, already checked, or kMetricGicp at c->gicp_eps).  Point and plane solves arm the evaluations the next search queues
 // ahead; a symmetric solve arms nothing and voids what is queued, like a failed solve: queued symmetric evaluations do not exist.
 static int optimize_metric(mvicp_ctx* c, double* poses, unsigned char* fixed, int param, int metric, int robust, int max_iterations, mvicp_summary* summary) {
   if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
@@ -320,7 +320,7 @@ static int optimize_metric(mvicp_ctx* c, double* poses, unsigned char* fixed, in
   if (c->E == 0) { set_error("no graph"); return MVICP_ERR_STATE; }
   HostScope hs(c, "host.optimize");
   // what the NEXT search may evaluate ahead of time (api.cpp, speculative first evaluation)
-  const bool sym = metric == MVICP_METRIC_SYMMETRIC;
+  const bool sym = metric == MVICP_METRIC_SYMMETRIC || metric == kMetricGicp;   // (neither is ever queued ahead)
   if (sym) c->hist.spec_flags_valid = false;
   else { c->hist.spec_flags_valid = true; c->hist.spec_param = param; c->hist.spec_plane = metric; c->hist.spec_robust = robust ? 1 : 0; }
   CtxEval u{c, metric, robust ? 1 : 0};
@@ -344,6 +344,14 @@ int mvicp_optimize_metric(mvicp_ctx* c, double* poses, unsigned char* fixed, int
                           mvicp_summary* summary) try {
   if (metric != MVICP_METRIC_POINT && metric != MVICP_METRIC_PLANE && metric != MVICP_METRIC_SYMMETRIC) { set_error("metric %d is not an mvicp_metric", metric); return MVICP_ERR_ARG; }
   return optimize_metric(c, poses, fixed, param, metric, robust, max_iterations, summary);
+} MVICP_GUARD_ABI
+
+// mvicp_optimize over the plane-to-plane objective; like a symmetric solve it arms nothing and voids what is queued
+int mvicp_optimize_gicp(mvicp_ctx* c, double* poses, unsigned char* fixed, int param, double epsilon, int robust, int max_iterations,
+                        mvicp_summary* summary) try {
+  if (!gicp_epsilon_ok(epsilon)) { set_error("gicp epsilon %g is not within [1e-6, 1]", epsilon); return MVICP_ERR_ARG; }
+  if (c) c->gicp_eps = epsilon;
+  return optimize_metric(c, poses, fixed, param, kMetricGicp, robust, max_iterations, summary);
 } MVICP_GUARD_ABI
 
 }  // extern "C"

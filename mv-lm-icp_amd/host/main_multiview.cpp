@@ -42,6 +42,9 @@
 // --symmetric (default off): the solves minimise the symmetric point-to-plane objective (MVICP_METRIC_SYMMETRIC, include/mvicp.h) instead of
 // the one --pointToPlane selects, in the parameterisation the other flags select.  It needs normals on every frame (the clouds' own or
 // --recomputeNormals), oriented consistently between the frames (--normals_nn below makes such normals).
+// --gicp [--gicp_epsilon E] (default off; E = 1e-3, within [1e-6, 1]): the solves minimise the plane-to-plane objective of Generalized-ICP
+// (mvicp_optimize_gicp, include/mvicp.h) with the covariances I - (1 - E) n n^T.  It needs normals on every frame, in any orientation.
+// Together with --symmetric it is refused.
 // --normals_nn K [--normals_radius R] (default K = 0 = off): with K > 0 the normals of every frame come from Frame::estimateNormals(K, R) in
 // place of the recomputeNormals step (after the outlier filter, before any coarse level): the exactly specified normals of
 // mvicp_estimate_normals over the K nearest points (3 <= K <= 64; R > 0: within R), turned towards the view's own origin -- the sensor of a
@@ -106,6 +109,9 @@ int main(int argc, char** argv) {
   Flags F(argc, argv);
   const bool pointToPlane = F.b("pointToPlane", true), sophusSE3 = F.b("sophusSE3", true), angleAxis = F.b("angleAxis", false);
   const bool robust = F.b("robust", true), quiet = F.b("quiet", false), symmetric = F.b("symmetric", false);
+  const bool gicp = F.b("gicp", false);
+  const double gicpEpsilon = F.f("gicp_epsilon", 1e-3);
+  if (gicp && symmetric) { std::cerr << "--gicp and --symmetric name two objectives: give one" << std::endl; return 1; }
   const float cutoff = (float)F.f("cutoff", 0.05);
   const int knn = F.i("knn", 2), rounds = F.i("rounds", 20);
   const std::string dir = F.s("dir", "../samples/Bunny_RealData"), out = F.s("out", "");
@@ -262,6 +268,8 @@ int main(int argc, char** argv) {
         std::cout << "getClosestPoint check: " << checked << " queries, " << bad << " mismatches (" << single << " also asked one by one)" << std::endl;
       }
       if (F.i("freeze_from", 1 << 30) <= r) {}   // (search only: the poses stay bit-identical)
+      else if (gicp)
+        Session::get().optimizeGicp(cur, sophusSE3 ? MVICP_PARAM_SOPHUS_SE3 : angleAxis ? MVICP_PARAM_ANGLE_AXIS : MVICP_PARAM_EIGEN_QUATERNION, gicpEpsilon, robust);
       else if (symmetric)
         Session::get().optimize(cur, sophusSE3 ? MVICP_PARAM_SOPHUS_SE3 : angleAxis ? MVICP_PARAM_ANGLE_AXIS : MVICP_PARAM_EIGEN_QUATERNION, MVICP_METRIC_SYMMETRIC, robust);
       else if (sophusSE3) ICP_Ceres::ceresOptimizer_sophusSE3(cur, pointToPlane, robust);

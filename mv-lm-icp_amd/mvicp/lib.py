@@ -16,7 +16,7 @@ EDGE_BLOCK = 91
 SYMBOLS = [
     "mvicp_last_error", "mvicp_version", "mvicp_create", "mvicp_destroy", "mvicp_set_num_frames", "mvicp_set_frame",
     "mvicp_recompute_normals", "mvicp_set_graph", "mvicp_set_shard", "mvicp_edge_owner", "mvicp_comm_unique_id", "mvicp_comm_init", "mvicp_comm_nranks", "mvicp_comm_set_callback", "mvicp_correspond",
-    "mvicp_get_correspondences", "mvicp_map_correspondences", "mvicp_map_correspondences_async", "mvicp_wait_correspondences", "mvicp_correspondence_epochs", "mvicp_set_correspondences", "mvicp_nn_query", "mvicp_linearize", "mvicp_linearize_pair", "mvicp_linearize_metric", "mvicp_optimize", "mvicp_optimize_metric",
+    "mvicp_get_correspondences", "mvicp_map_correspondences", "mvicp_map_correspondences_async", "mvicp_wait_correspondences", "mvicp_correspondence_epochs", "mvicp_set_correspondences", "mvicp_nn_query", "mvicp_linearize", "mvicp_linearize_pair", "mvicp_linearize_metric", "mvicp_linearize_gicp", "mvicp_optimize", "mvicp_optimize_metric", "mvicp_optimize_gicp",
     "mvicp_lm_solve", "mvicp_set_option", "mvicp_nn_census", "mvicp_nn_census_ex", "mvicp_last_nn_launch", "mvicp_reset_history", "mvicp_profile_enable", "mvicp_profile_reset", "mvicp_profile_get", "mvicp_profile_get_ex", "mvicp_stream", "mvicp_sync",
     "mvicp_closedform_point_to_point", "mvicp_closedform_point_to_plane", "mvicp_set_frame_device", "mvicp_get_structure",
     "mvicp_overlap", "mvicp_graph_from_overlap", "mvicp_voxel_grid", "mvicp_voxel_fetch",
@@ -106,6 +106,8 @@ def load_library(path=None):
     lib.mvicp_optimize.argtypes = [vp, dp, u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Summary)]
     lib.mvicp_linearize_metric.argtypes = [vp, dp, C.c_int, C.c_int, dp]
     lib.mvicp_optimize_metric.argtypes = [vp, dp, u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Summary)]
+    lib.mvicp_linearize_gicp.argtypes = [vp, dp, C.c_double, C.c_int, dp]
+    lib.mvicp_optimize_gicp.argtypes = [vp, dp, u8p, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(Summary)]
     lib.mvicp_lm_solve.argtypes = [C.c_int, C.c_int, ip, ip, dp, u8p, C.c_int, C.c_int, EVAL_FN, vp, C.POINTER(Summary)]
     lib.mvicp_set_option.argtypes = [vp, C.c_char_p, C.c_double]
     lib.mvicp_nn_census.argtypes = [vp, dp]
@@ -1044,6 +1046,21 @@ class Engine:
         np.copyto(b["P44"], np.transpose(np.asarray(poses, dtype=np.float64), (0, 2, 1)))
         b["fx"][:] = fixed
         _check(self.lib, self.lib.mvicp_optimize_metric(self.h, b["pP"], b["pfx"], param, int(metric), int(robust), max_iterations, b["psm"]))
+        return np.ascontiguousarray(np.transpose(b["P44"], (0, 2, 1))), b["sm"].as_dict()
+
+    def linearize_gicp(self, poses, epsilon=1e-3, robust=True):
+        """linearize over the plane-to-plane (Generalized-ICP) objective, C(n) = I - (1 - epsilon) n n^T; epsilon within [1e-6, 1]."""
+        P = poses_to_c(poses)
+        out = np.zeros((self.E, EDGE_BLOCK), dtype=np.float64)
+        _check(self.lib, self.lib.mvicp_linearize_gicp(self.h, _dp(P), float(epsilon), int(robust), _dp(out)))
+        return out
+
+    def optimize_gicp(self, poses, fixed, param=PARAM_SOPHUS_SE3, epsilon=1e-3, robust=True, max_iterations=50):
+        """optimize over the plane-to-plane objective; like a symmetric solve it queues nothing for the next search."""
+        b = self._round_buffers(len(poses))
+        np.copyto(b["P44"], np.transpose(np.asarray(poses, dtype=np.float64), (0, 2, 1)))
+        b["fx"][:] = fixed
+        _check(self.lib, self.lib.mvicp_optimize_gicp(self.h, b["pP"], b["pfx"], param, float(epsilon), int(robust), max_iterations, b["psm"]))
         return np.ascontiguousarray(np.transpose(b["P44"], (0, 2, 1))), b["sm"].as_dict()
 
     def optimize(self, poses, fixed, param=PARAM_SOPHUS_SE3, point_to_plane=True, robust=True, max_iterations=50):
