@@ -1,6 +1,8 @@
 // What the translation units of the linearization share (linearize.hip: point-to-point and point-to-plane; linearize_sym.hip: the symmetric
-// objective): the launch constants, the robust-loss helpers, the extra arguments of a paired launch, and the per-edge reduce + expansion
-// kernel, which every family runs behind its own accumulation kernel, and the host table of the per-edge sorted source clouds.  Everything sits in an anonymous namespace, as it did inside
+// objective; linearize_gicp.hip: plane-to-plane): the launch constants, the robust-loss helpers, the extra arguments of a paired launch, the block
+// reduction that ends every accumulation kernel (block_reduce_store), and the per-edge reduce + expansion
+// kernel, which every family runs behind its own accumulation kernel, and the host table of the per-edge sorted source clouds.  The rest of what the two
+// normal-carrying families share — the body of their kernels and their host launch — is in lin_normal.h.  Everything sits in an anonymous namespace, as it did inside
 // linearize.hip: each unit gets its own internal copy, under the same names.
 #pragma once
 #include "common.h"
@@ -35,6 +37,29 @@ __device__ __forceinline__ double fast_rsqrt(double y) {
 // Extra kernel arguments of the two-pose builds (empty for one pose set, so the one-pose kernels keep their argument layout).
 template <int NP> struct PairArgs {};
 template <> struct PairArgs<2> { const double* rel2; size_t partials2_off; double* out2; };
+
+// Block reduction of one workgroup's NACC sums through LDS, transposed, into partial slot c of pk: every thread stores value j into row j (stride-1
+// across lanes: conflict-free ds_write_b64), then 16 threads per row add 16 columns each and finish with a 4-step xor-shuffle inside their lane group
+// (two passes of 16 rows keep the LDS footprint at 33 KB).  Fixed association order -> deterministic, and the same for every family.
+// lead_sync: red is still being read (a second reduction through the same rows), so a barrier comes first.
+__device__ __forceinline__ void block_reduce_store(const double (&acc)[NACC], double (&red)[NACC / 2][NT + 1], double* __restrict__ pk, int c, bool lead_sync) {
+#pragma unroll
+  for (int pass = 0; pass < 2; ++pass) {
+    if (pass || lead_sync) __syncthreads();
+#pragma unroll
+    for (int j = 0; j < NACC / 2; ++j) red[j][threadIdx.x] = acc[pass * (NACC / 2) + j];
+    __syncthreads();
+    const int row = threadIdx.x >> 4, part = threadIdx.x & 15;  // 16 rows x 16 parts
+    double sum = 0.0;
+#pragma unroll 8
+    for (int i = 0; i < NT / 16; ++i) sum += red[row][part + 16 * i];
+    sum += __shfl_xor(sum, 1, 64);
+    sum += __shfl_xor(sum, 2, 64);
+    sum += __shfl_xor(sum, 4, 64);
+    sum += __shfl_xor(sum, 8, 64);
+    if (part == 0) pk[(size_t)c * NACC + pass * (NACC / 2) + row] = sum;
+  }
+}
 
 // ---- per edge: fixed-order sum of the workgroup partials, then expansion to the canonical 12x12 block
 __device__ __forceinline__ void cross_mat(const double* a, double* M) {  // row-major [a]x

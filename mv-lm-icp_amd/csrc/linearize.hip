@@ -39,7 +39,7 @@
 //
 // Mapping: one 256-thread workgroup per chunk of `chunk` correspondences of ONE edge; ~60 accumulator
 // VGPRs per lane leave room to keep the next correspondences' loads in flight; transposed LDS block
-// reduction; one partial per workgroup; a second kernel sums each edge's partials in fixed order and does
+// reduction (block_reduce_store, lin_common.h: one text for every family); one partial per workgroup; a second kernel sums each edge's partials in fixed order and does
 // the expansion -> deterministic, and independent of how edges are sharded across GPUs.
 #include "lin_common.h"
 
@@ -210,29 +210,12 @@ __global__ __launch_bounds__(NT) void linearize_kernel(const int* __restrict__ c
     pos = npos;
   }
 
-  // Block reduction through LDS, transposed: every thread stores value j into row j (stride-1 across lanes:
-  // conflict-free ds_write_b64), then 16 threads per row add 16 columns each and finish with a 4-step xor-shuffle
-  // inside their lane group (two passes of 16 rows keep the LDS footprint at 33 KB).  Fixed association order -> deterministic.
+  // each pose set through the one block reduction (lin_common.h), the second after a barrier on the rows the first still reads
 #pragma unroll
   for (int k = 0; k < NP; ++k) {
     double* __restrict__ pk = partials;
     if constexpr (NP > 1) { if (k) pk = partials + x.partials2_off; }
-#pragma unroll
-    for (int pass = 0; pass < 2; ++pass) {
-      if (pass || k) __syncthreads();
-#pragma unroll
-      for (int j = 0; j < NACC / 2; ++j) red[j][threadIdx.x] = acc[k][pass * (NACC / 2) + j];
-      __syncthreads();
-      const int row = threadIdx.x >> 4, part = threadIdx.x & 15;  // 16 rows x 16 parts
-      double sum = 0.0;
-#pragma unroll 8
-      for (int i = 0; i < NT / 16; ++i) sum += red[row][part + 16 * i];
-      sum += __shfl_xor(sum, 1, 64);
-      sum += __shfl_xor(sum, 2, 64);
-      sum += __shfl_xor(sum, 4, 64);
-      sum += __shfl_xor(sum, 8, 64);
-      if (part == 0) pk[(size_t)c * NACC + pass * (NACC / 2) + row] = sum;
-    }
+    block_reduce_store(acc[k], red, pk, c, k != 0);
   }
 }
 

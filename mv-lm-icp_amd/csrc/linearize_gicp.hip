@@ -28,12 +28,11 @@
 //   w = 1 (plain) or fast_rsqrt(1 + s * (1 / a^2)),  cost += 0.5 * s or half_rho(s, w)
 //   V = w W,  T_i = x' x V_i (row i: T_i0 = fma(x'1, V_i2, -(x'2 * V_i1)) and cyclically),  R_ij = (x' x (T_0j, T_1j, T_2j))_i  for i <= j
 //   acc: V (6), T (9), R (6) into the 21 slots of the upper triangle of U, row-major;  v_i += w y_i (3),  v_3.. += x' x (w y) (3)
-// then the transposed LDS reduction of linearize_kernel in the same fixed order.
+// then the block reduction of every family (block_reduce_store, lin_common.h).
 //
-// Operands, mapping, look-ahead, chunk tables, XCD interleave, partial slots: those of linearize_sym_kernel, with one difference: the 12 low parts of the
-// relative transform are read straight from global memory at a block-uniform address, before the barrier, and so by scalar loads into SGPRs.  Through LDS
-// like the high parts they cost 24 VGPRs, and the robust build then needs 256 + 2 AGPRs: one wave per SIMD where this one runs at two (234 / 232 VGPRs).
-#include "lin_common.h"
+// Operands, mapping, look-ahead, chunk tables, XCD interleave, partial slots and the host launch: lin_normal.h, shared with the symmetric objective
+// (linearize_sym.hip), with its switch set to the scalar route for the 12 low parts of the relative transform (see the kernel below).
+#include "lin_normal.h"
 #include "lin_residual.h"
 
 namespace mvicp {
@@ -129,8 +128,8 @@ __device__ __forceinline__ void accumulate_gicp(double (&acc)[NACC], const doubl
   acc[26] += __builtin_fma(x0, wy1, -(x1 * wy0));
 }
 
-// One 256-thread workgroup per chunk of one edge, two adjacent correspondences per lane per step, the next step's operands in flight during the
-// arithmetic: linearize_sym_kernel's mapping and loads.  Register slots: 0-2 p, 3-5 n_q, 6-8 q, 9-11 n_p.
+// The shared pipeline (lin_normal.h) around accumulate_gicp, the 12 low parts by scalar loads: through LDS like the high parts they cost 24 VGPRs, and
+// the robust build then needs 256 + 2 AGPRs: one wave per SIMD where this one runs at two (234 / 232 VGPRs).
 template <bool ROBUST>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void linearize_gicp_kernel(const int* __restrict__ chunk_edge, const int* __restrict__ chunk_start, int chunk,
                                                             const int* __restrict__ count, const long long* __restrict__ cap_off, long long total_cap,
@@ -139,156 +138,26 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void li
                                                             const double* const* __restrict__ src_pts, const double* const* __restrict__ src_nor,
                                                             const int* __restrict__ first, const int* __restrict__ nsrc,
                                                             const int* __restrict__ chunk_first, double eps) {
-  const int e = chunk_edge[blockIdx.x];
-  const int start = chunk_start[blockIdx.x];
-  const int c = chunk_first[e] + start / chunk;   // the partial's slot: the chunk's place in its edge's run, whatever the launch order
-  const int cnt = count[e];
-  if (start >= cnt) return;
-  const int end = min(cnt, start + chunk);
-  // the low parts at a block-uniform address, before the barrier: scalar loads, so they occupy SGPRs, which is what keeps this kernel within 256 VGPRs
-  // at two waves per SIMD
-  double lo[kEdgeRel];
-#pragma unroll
-  for (int i = 0; i < kEdgeRel; ++i) lo[i] = rel_lo[(size_t)e * kEdgeRel + i];
-  __shared__ double srel[kEdgeRel];
-  __shared__ double red[NACC / 2][NT + 1];
-  if (threadIdx.x < kEdgeRel) srel[threadIdx.x] = rel[(size_t)e * kEdgeRel + threadIdx.x];
-  __syncthreads();
-  double A[9], t[3];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) A[i] = srel[i];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) t[i] = srel[9 + i];
-  double inv_a2 = 1.0;
-  if (ROBUST) { const double a = a_scale[e]; inv_a2 = 1.0 / (a * a); }
   GicpEps E;
   E.eps = eps; E.c = 1.0 - eps; E.c2 = E.c * E.c; E.four_eps = 4.0 * eps; E.eps_c = eps * E.c; E.one_p_eps = 1.0 + eps;
-
-  double acc[NACC];
-#pragma unroll
-  for (int i = 0; i < NACC; ++i) acc[i] = 0.0;
-
-  const size_t base = (size_t)cap_off[e];  // multiple of 64 -> 16-B aligned double2 loads, 8-B aligned index pairs
-  const double* __restrict__ s0 = stream + base;
-  const int* __restrict__ fi = first + base;
-  const double* __restrict__ sn = src_nor[e];   // the source frame's normals in its sorted order (non-null: check_evaluable)
-  // identity list (count == N_src): p AND n_p are the source cloud's own arrays at position pos
-  const double* __restrict__ sp = (src_pts != nullptr && cnt == nsrc[e]) ? src_pts[e] : nullptr;
-  constexpr int NS = 12;
-  // register slot j < 9 -> stream array: p = arrays 0-2, n_q = arrays 3-5, q = arrays 7-9
-  auto arr = [](int j) { return j < 6 ? j : j + 1; };
-  typedef double d2v __attribute__((ext_vector_type(2)));
-  typedef int i2v __attribute__((ext_vector_type(2)));
-  auto aos_pair = [](const double* __restrict__ b, int at, double2& v0, double2& v1, double2& v2) {   // rows at, at + 1 of an n x 3 array (at even)
-    const double2 a = *reinterpret_cast<const double2*>(b + 3 * (size_t)at);
-    const double2 m = *reinterpret_cast<const double2*>(b + 3 * (size_t)at + 2);
-    const double2 z = *reinterpret_cast<const double2*>(b + 3 * (size_t)at + 4);
-    v0 = make_double2(a.x, m.y); v1 = make_double2(a.y, z.x); v2 = make_double2(m.x, z.y);
-  };
-  // sorted positions of the source points of the pair at `at` (unused for an identity list)
-  auto load_idx = [&](int2& ix, int at) {
-    if (sp != nullptr) return;
-    if (at + 1 < end) { const i2v k = __builtin_nontemporal_load(reinterpret_cast<const i2v*>(fi + at)); ix = make_int2(k.x, k.y); }
-    else if (at < end) { ix = make_int2(fi[at], 0); }
-  };
-  auto load = [&](double2 (&v)[NS], int at, const int2& ix) {
-    if (at + 1 < end) {
-      if (sp != nullptr) {
-        aos_pair(sp, at, v[0], v[1], v[2]);
-        aos_pair(sn, at, v[9], v[10], v[11]);
-      } else {
-        const double* __restrict__ na = sn + 3 * (size_t)ix.x;
-        const double* __restrict__ nb = sn + 3 * (size_t)ix.y;
-#pragma unroll
-        for (int j = 0; j < 3; ++j) v[9 + j] = make_double2(na[j], nb[j]);
-      }
-#pragma unroll
-      for (int j = 0; j < 9; ++j) {
-        if (j < 3 && sp != nullptr) continue;
-        const d2v x = __builtin_nontemporal_load(reinterpret_cast<const d2v*>(s0 + (size_t)arr(j) * total_cap + at));   // read once per evaluation
-        v[j] = make_double2(x.x, x.y);
-      }
-    } else if (at < end) {
-      const double* __restrict__ na = sn + 3 * (size_t)(sp != nullptr ? at : ix.x);
-#pragma unroll
-      for (int j = 0; j < 3; ++j) { v[9 + j].x = na[j]; v[9 + j].y = 0.0; }
-#pragma unroll
-      for (int j = 0; j < 9; ++j) { v[j].x = (j < 3 && sp != nullptr) ? sp[3 * (size_t)at + j] : s0[(size_t)arr(j) * total_cap + at]; v[j].y = 0.0; }
-    }
-  };
-  int pos = start + 2 * threadIdx.x;
-  double2 cur[NS], nxt[NS];
-#pragma unroll
-  for (int j = 0; j < NS; ++j) { cur[j] = make_double2(0.0, 0.0); nxt[j] = make_double2(0.0, 0.0); }
-  int2 ix = make_int2(0, 0), ix_next = make_int2(0, 0);
-  load_idx(ix, pos);
-  load_idx(ix_next, pos + 2 * NT);
-  load(cur, pos, ix);
-  while (pos < end) {
-    const int npos = pos + 2 * NT;
-    ix = ix_next;
-    load_idx(ix_next, npos + 2 * NT);
-    load(nxt, npos, ix);
-    accumulate_gicp<ROBUST>(acc, A, t, lo, inv_a2, E, cur[0].x, cur[1].x, cur[2].x, cur[3].x, cur[4].x, cur[5].x, cur[6].x, cur[7].x, cur[8].x, cur[9].x, cur[10].x, cur[11].x);
-    if (pos + 1 < end)
-      accumulate_gicp<ROBUST>(acc, A, t, lo, inv_a2, E, cur[0].y, cur[1].y, cur[2].y, cur[3].y, cur[4].y, cur[5].y, cur[6].y, cur[7].y, cur[8].y, cur[9].y, cur[10].y, cur[11].y);
-#pragma unroll
-    for (int j = 0; j < NS; ++j) cur[j] = nxt[j];
-    pos = npos;
-  }
-
-  // Block reduction through LDS, transposed, in the fixed order of linearize_kernel: row j holds value j of every lane, 16 threads per row add 16 columns
-  // each and finish with a 4-step xor-shuffle; two passes of 16 rows.
-#pragma unroll
-  for (int pass = 0; pass < 2; ++pass) {
-    if (pass) __syncthreads();
-#pragma unroll
-    for (int j = 0; j < NACC / 2; ++j) red[j][threadIdx.x] = acc[pass * (NACC / 2) + j];
-    __syncthreads();
-    const int row = threadIdx.x >> 4, part = threadIdx.x & 15;
-    double sum = 0.0;
-#pragma unroll 8
-    for (int i = 0; i < NT / 16; ++i) sum += red[row][part + 16 * i];
-    sum += __shfl_xor(sum, 1, 64);
-    sum += __shfl_xor(sum, 2, 64);
-    sum += __shfl_xor(sum, 4, 64);
-    sum += __shfl_xor(sum, 8, 64);
-    if (part == 0) partials[(size_t)c * NACC + pass * (NACC / 2) + row] = sum;
-  }
+  linearize_normal_body<ROBUST, true>(chunk_edge, chunk_start, chunk, count, cap_off, total_cap, rel, rel_lo, a_scale, stream, partials, src_pts, src_nor, first, nsrc, chunk_first,
+                                      [&E](double (&acc)[NACC], const double* A, const double* t, const double* lo, double inv_a2, auto... operands) {
+                                        accumulate_gicp<ROBUST>(acc, A, t, lo, inv_a2, E, operands...);
+                                      });
 }
 
 }  // namespace
 
+// (the symmetric launch's tables, cached by content under the same keys, and the symmetric pass's bytes: the same operands by the same routes)
 int launch_linearize_gicp(mvicp_ctx* c, double eps, int robust) {
-  if (c->E == 0) return MVICP_OK;
-  const int chunk = c->lin_chunk;
-  if (c->n_chunks > 0) {
-    const double bytes = sym_pass_bytes(c);   // the symmetric pass's bytes: the same operands by the same routes
-    // per-edge sorted source clouds and their normals: the symmetric launch's tables (cached by content under the same keys)
-    const double* const* d_src = nullptr;
-    MV_CHECK(source_table(c, &d_src));
-    std::vector<const double*> nor((size_t)c->E, nullptr);
-    for (int e = 0; e < c->E; ++e) if (c->owned[e]) nor[e] = c->frames[c->esrc[e]].grid.snor;
-    const double* const* d_nor = nullptr;
-    MV_CHECK(cached_upload(c, "lin_src_nor", nor.data(), sizeof(void*) * nor.size(), (void**)&d_nor));
-    // the low parts of the relative transforms this evaluation uploaded behind the control block (api.cpp upload_rel_sym)
-    if (c->sym_lo_dev.cap < sizeof(double) * (size_t)c->E * kEdgeRel) { set_error("gicp launch without its relative transforms"); return MVICP_ERR_STATE; }
-    const double* d_lo = (const double*)c->sym_lo_dev.p;
-    ProfScope ps(c, "linearize_gicp", bytes);
-#define LAUNCH(R)                                                                                                                               \
-  hipLaunchKernelGGL((linearize_gicp_kernel<R>), dim3(c->n_chunks), dim3(NT), 0, c->stream, c->d_chunk_edge, c->d_chunk_start, chunk, c->d_count, \
-                     c->d_cap_off, c->total_cap, c->d_rel, d_lo, c->d_a, c->d_stream, c->d_partials, d_src, d_nor, (const int*)c->d_first,       \
-                     (const int*)c->d_nsrc, (const int*)c->d_chunk_first, eps)
-    if (robust) LAUNCH(true);
-    else LAUNCH(false);
-#undef LAUNCH
-  }
-  {
-    ProfScope ps(c, "reduce", 0.0);
-    hipLaunchKernelGGL((reduce_expand_kernel<true, 1>), dim3(c->E), dim3(256), 0, c->stream, c->d_chunk_first, chunk, c->d_count, c->d_rel, c->d_partials, c->lin_out ? c->lin_out : c->d_out, PairArgs<1>{});
-  }
-  MV_HIP(hipGetLastError());
-  return MVICP_OK;
+  return launch_linearize_normal(c, robust, "linearize_gicp", "gicp", [&](bool rob, int chunk, const double* d_lo, const double* const* d_src, const double* const* d_nor) {
+    auto go = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3(c->n_chunks), dim3(NT), 0, c->stream, c->d_chunk_edge, c->d_chunk_start, chunk, c->d_count, c->d_cap_off, c->total_cap, c->d_rel, d_lo,
+                         c->d_a, c->d_stream, c->d_partials, d_src, d_nor, (const int*)c->d_first, (const int*)c->d_nsrc, (const int*)c->d_chunk_first, eps);
+    };
+    if (rob) go(linearize_gicp_kernel<true>);
+    else go(linearize_gicp_kernel<false>);
+  });
 }
 
 }  // namespace mvicp

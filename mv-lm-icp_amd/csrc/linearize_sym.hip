@@ -24,18 +24,15 @@
 //   u'_3  = 0.5 * fma(x'1, n2, fma(-x'2, n1, fma(d1, nu2, -(d2 * nu1))))     and cyclically (1,2) -> (2,0) -> (0,1) for u'_4, u'_5
 //   s = r * r,  w = 1 (plain) or fast_rsqrt(1 + s * (1 / a^2)),  cost += 0.5 * s or half_rho(s, w)
 //   for i = 0..5: wu = w * u'_i;  U_ij = fma(wu, u'_j, U_ij) for j = i..5;  v_i = fma(wu, r, v_i)
-// then the transposed LDS reduction of linearize_kernel in the same fixed order.
+// then the block reduction of every family (block_reduce_store, lin_common.h).
 //
 // The relative transform comes as hi + lo (api.cpp upload_rel_sym: R_d^-1 by the true inverse, in extended precision): an error of (A, t) is common to
 // every correspondence of the edge and would add up coherently in g against residuals that add up like sqrt(N).  The low parts enter the residual's f
 // only; the moments, nu and the expansion use the hi parts, where that error is an ordinary relative one.
 //
-// Operands: n_q (arrays 3-5) and q (arrays 7-9) from the operand stream, non-temporal; p from arrays 0-2 or, for an identity list, from the shared
-// sorted source cloud (as linearize_kernel); n_p from the source frame's sorted normals at first[pos] — the stream is NOT widened — which for an identity
-// list is position pos itself, three 16-B loads per pair like p.  Both cloud-side loads are ordinary cacheable loads: the edges of a source frame share them.
-// The gather index of the step AFTER the next is loaded one step early, so its latency is not on the path of the prefetch that depends on it.
-// Mapping, chunk tables, partial slots: those of linearize_kernel (launch_linearize's tables; the XCD interleave comes with them).
-#include "lin_common.h"
+// Operands, mapping, look-ahead, chunk tables, XCD interleave, partial slots and the host launch: lin_normal.h, shared with the plane-to-plane objective
+// (linearize_gicp.hip).  This file holds the arithmetic of one correspondence; the 12 low parts reach it through LDS, next to the high parts.
+#include "lin_normal.h"
 #include "lin_residual.h"
 
 namespace mvicp {
@@ -82,8 +79,7 @@ __device__ __forceinline__ void accumulate_sym(double (&acc)[NACC], const double
   }
 }
 
-// One 256-thread workgroup per chunk of one edge, two adjacent correspondences per lane per step, the next step's operands in flight during the
-// arithmetic: linearize_kernel's mapping.  Register slots: 0-2 p, 3-5 n_q, 6-8 q, 9-11 n_p.
+// The shared pipeline (lin_normal.h) around accumulate_sym, the 12 low parts through LDS.
 template <bool ROBUST>
 __global__ __launch_bounds__(NT) void linearize_sym_kernel(const int* __restrict__ chunk_edge, const int* __restrict__ chunk_start, int chunk,
                                                            const int* __restrict__ count, const long long* __restrict__ cap_off, long long total_cap,
@@ -92,152 +88,21 @@ __global__ __launch_bounds__(NT) void linearize_sym_kernel(const int* __restrict
                                                            const double* const* __restrict__ src_pts, const double* const* __restrict__ src_nor,
                                                            const int* __restrict__ first, const int* __restrict__ nsrc,
                                                            const int* __restrict__ chunk_first) {
-  const int e = chunk_edge[blockIdx.x];
-  const int start = chunk_start[blockIdx.x];
-  const int c = chunk_first[e] + start / chunk;   // the partial's slot: the chunk's place in its edge's run, whatever the launch order
-  const int cnt = count[e];
-  if (start >= cnt) return;
-  const int end = min(cnt, start + chunk);
-  __shared__ double srel[2][kEdgeRel];
-  __shared__ double red[NACC / 2][NT + 1];
-  if (threadIdx.x < kEdgeRel) srel[0][threadIdx.x] = rel[(size_t)e * kEdgeRel + threadIdx.x];
-  if (threadIdx.x >= 32 && threadIdx.x < 32 + kEdgeRel) srel[1][threadIdx.x - 32] = rel_lo[(size_t)e * kEdgeRel + threadIdx.x - 32];
-  __syncthreads();
-  double A[9], t[3], lo[kEdgeRel];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) A[i] = srel[0][i];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) t[i] = srel[0][9 + i];
-#pragma unroll
-  for (int i = 0; i < kEdgeRel; ++i) lo[i] = srel[1][i];
-  double inv_a2 = 1.0;
-  if (ROBUST) { const double a = a_scale[e]; inv_a2 = 1.0 / (a * a); }
-
-  double acc[NACC];
-#pragma unroll
-  for (int i = 0; i < NACC; ++i) acc[i] = 0.0;
-
-  const size_t base = (size_t)cap_off[e];  // multiple of 64 -> 16-B aligned double2 loads, 8-B aligned index pairs
-  const double* __restrict__ s0 = stream + base;
-  const int* __restrict__ fi = first + base;
-  const double* __restrict__ sn = src_nor[e];   // the source frame's normals in its sorted order (non-null: check_evaluable)
-  // identity list (count == N_src): p AND n_p are the source cloud's own arrays at position pos
-  const double* __restrict__ sp = (src_pts != nullptr && cnt == nsrc[e]) ? src_pts[e] : nullptr;
-  constexpr int NS = 12;
-  // register slot j < 9 -> stream array: p = arrays 0-2, n_q = arrays 3-5, q = arrays 7-9
-  auto arr = [](int j) { return j < 6 ? j : j + 1; };
-  typedef double d2v __attribute__((ext_vector_type(2)));
-  typedef int i2v __attribute__((ext_vector_type(2)));
-  auto aos_pair = [](const double* __restrict__ b, int at, double2& v0, double2& v1, double2& v2) {   // rows at, at + 1 of an n x 3 array (at even)
-    const double2 a = *reinterpret_cast<const double2*>(b + 3 * (size_t)at);
-    const double2 m = *reinterpret_cast<const double2*>(b + 3 * (size_t)at + 2);
-    const double2 z = *reinterpret_cast<const double2*>(b + 3 * (size_t)at + 4);
-    v0 = make_double2(a.x, m.y); v1 = make_double2(a.y, z.x); v2 = make_double2(m.x, z.y);
-  };
-  // sorted positions of the source points of the pair at `at` (unused for an identity list)
-  auto load_idx = [&](int2& ix, int at) {
-    if (sp != nullptr) return;
-    if (at + 1 < end) { const i2v k = __builtin_nontemporal_load(reinterpret_cast<const i2v*>(fi + at)); ix = make_int2(k.x, k.y); }
-    else if (at < end) { ix = make_int2(fi[at], 0); }
-  };
-  auto load = [&](double2 (&v)[NS], int at, const int2& ix) {
-    if (at + 1 < end) {
-      if (sp != nullptr) {
-        aos_pair(sp, at, v[0], v[1], v[2]);
-        aos_pair(sn, at, v[9], v[10], v[11]);
-      } else {
-        const double* __restrict__ na = sn + 3 * (size_t)ix.x;
-        const double* __restrict__ nb = sn + 3 * (size_t)ix.y;
-#pragma unroll
-        for (int j = 0; j < 3; ++j) v[9 + j] = make_double2(na[j], nb[j]);
-      }
-#pragma unroll
-      for (int j = 0; j < 9; ++j) {
-        if (j < 3 && sp != nullptr) continue;
-        const d2v x = __builtin_nontemporal_load(reinterpret_cast<const d2v*>(s0 + (size_t)arr(j) * total_cap + at));   // read once per evaluation
-        v[j] = make_double2(x.x, x.y);
-      }
-    } else if (at < end) {
-      const double* __restrict__ na = sn + 3 * (size_t)(sp != nullptr ? at : ix.x);
-#pragma unroll
-      for (int j = 0; j < 3; ++j) { v[9 + j].x = na[j]; v[9 + j].y = 0.0; }
-#pragma unroll
-      for (int j = 0; j < 9; ++j) { v[j].x = (j < 3 && sp != nullptr) ? sp[3 * (size_t)at + j] : s0[(size_t)arr(j) * total_cap + at]; v[j].y = 0.0; }
-    }
-  };
-  int pos = start + 2 * threadIdx.x;
-  double2 cur[NS], nxt[NS];
-#pragma unroll
-  for (int j = 0; j < NS; ++j) { cur[j] = make_double2(0.0, 0.0); nxt[j] = make_double2(0.0, 0.0); }
-  int2 ix = make_int2(0, 0), ix_next = make_int2(0, 0);
-  load_idx(ix, pos);
-  load_idx(ix_next, pos + 2 * NT);
-  load(cur, pos, ix);
-  while (pos < end) {
-    const int npos = pos + 2 * NT;
-    ix = ix_next;
-    load_idx(ix_next, npos + 2 * NT);
-    load(nxt, npos, ix);
-    accumulate_sym<ROBUST>(acc, A, t, lo, inv_a2, cur[0].x, cur[1].x, cur[2].x, cur[3].x, cur[4].x, cur[5].x, cur[6].x, cur[7].x, cur[8].x, cur[9].x, cur[10].x, cur[11].x);
-    if (pos + 1 < end)
-      accumulate_sym<ROBUST>(acc, A, t, lo, inv_a2, cur[0].y, cur[1].y, cur[2].y, cur[3].y, cur[4].y, cur[5].y, cur[6].y, cur[7].y, cur[8].y, cur[9].y, cur[10].y, cur[11].y);
-#pragma unroll
-    for (int j = 0; j < NS; ++j) cur[j] = nxt[j];
-    pos = npos;
-  }
-
-  // Block reduction through LDS, transposed, in the fixed order of linearize_kernel: row j holds value j of every lane, 16 threads per row add 16 columns
-  // each and finish with a 4-step xor-shuffle; two passes of 16 rows.
-#pragma unroll
-  for (int pass = 0; pass < 2; ++pass) {
-    if (pass) __syncthreads();
-#pragma unroll
-    for (int j = 0; j < NACC / 2; ++j) red[j][threadIdx.x] = acc[pass * (NACC / 2) + j];
-    __syncthreads();
-    const int row = threadIdx.x >> 4, part = threadIdx.x & 15;
-    double sum = 0.0;
-#pragma unroll 8
-    for (int i = 0; i < NT / 16; ++i) sum += red[row][part + 16 * i];
-    sum += __shfl_xor(sum, 1, 64);
-    sum += __shfl_xor(sum, 2, 64);
-    sum += __shfl_xor(sum, 4, 64);
-    sum += __shfl_xor(sum, 8, 64);
-    if (part == 0) partials[(size_t)c * NACC + pass * (NACC / 2) + row] = sum;
-  }
+  linearize_normal_body<ROBUST, false>(chunk_edge, chunk_start, chunk, count, cap_off, total_cap, rel, rel_lo, a_scale, stream, partials, src_pts, src_nor, first, nsrc, chunk_first,
+                                       [](double (&acc)[NACC], auto... operands) { accumulate_sym<ROBUST>(acc, operands...); });
 }
 
 }  // namespace
 
 int launch_linearize_sym(mvicp_ctx* c, int robust) {
-  if (c->E == 0) return MVICP_OK;
-  const int chunk = c->lin_chunk;
-  if (c->n_chunks > 0) {
-    const double bytes = sym_pass_bytes(c);
-    // per-edge sorted source clouds (launch_linearize's table) and their normals, cached by content
-    const double* const* d_src = nullptr;
-    MV_CHECK(source_table(c, &d_src));
-    std::vector<const double*> nor((size_t)c->E, nullptr);
-    for (int e = 0; e < c->E; ++e) if (c->owned[e]) nor[e] = c->frames[c->esrc[e]].grid.snor;
-    const double* const* d_nor = nullptr;
-    MV_CHECK(cached_upload(c, "lin_src_nor", nor.data(), sizeof(void*) * nor.size(), (void**)&d_nor));
-    // the low parts of the relative transforms this evaluation uploaded behind the control block (api.cpp upload_rel_sym)
-    if (c->sym_lo_dev.cap < sizeof(double) * (size_t)c->E * kEdgeRel) { set_error("symmetric launch without its relative transforms"); return MVICP_ERR_STATE; }
-    const double* d_lo = (const double*)c->sym_lo_dev.p;
-    ProfScope ps(c, "linearize_sym", bytes);
-#define LAUNCH(R)                                                                                                                              \
-  hipLaunchKernelGGL((linearize_sym_kernel<R>), dim3(c->n_chunks), dim3(NT), 0, c->stream, c->d_chunk_edge, c->d_chunk_start, chunk, c->d_count, \
-                     c->d_cap_off, c->total_cap, c->d_rel, d_lo, c->d_a, c->d_stream, c->d_partials, d_src, d_nor, (const int*)c->d_first,      \
-                     (const int*)c->d_nsrc, (const int*)c->d_chunk_first)
-    if (robust) LAUNCH(true);
-    else LAUNCH(false);
-#undef LAUNCH
-  }
-  {
-    ProfScope ps(c, "reduce", 0.0);
-    hipLaunchKernelGGL((reduce_expand_kernel<true, 1>), dim3(c->E), dim3(256), 0, c->stream, c->d_chunk_first, chunk, c->d_count, c->d_rel, c->d_partials, c->lin_out ? c->lin_out : c->d_out, PairArgs<1>{});
-  }
-  MV_HIP(hipGetLastError());
-  return MVICP_OK;
+  return launch_linearize_normal(c, robust, "linearize_sym", "symmetric", [&](bool rob, int chunk, const double* d_lo, const double* const* d_src, const double* const* d_nor) {
+    auto go = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3(c->n_chunks), dim3(NT), 0, c->stream, c->d_chunk_edge, c->d_chunk_start, chunk, c->d_count, c->d_cap_off, c->total_cap, c->d_rel, d_lo,
+                         c->d_a, c->d_stream, c->d_partials, d_src, d_nor, (const int*)c->d_first, (const int*)c->d_nsrc, (const int*)c->d_chunk_first);
+    };
+    if (rob) go(linearize_sym_kernel<true>);
+    else go(linearize_sym_kernel<false>);
+  });
 }
 
 }  // namespace mvicp
