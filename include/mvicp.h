@@ -794,7 +794,9 @@ int mvicp_linearize_metric(mvicp_ctx* ctx, const double* poses, int metric, int 
  * function of its normal alone, C(n) = I - (1 - epsilon) n^ n^T: epsilon along the normal, 1 in the tangent plane.  Per correspondence, with
  * the relative transform (A, t) of the edge formed as for SYMMETRIC (the true inverse of R_d in extended precision, hi + lo parts):
  *     p~ = A p + t,   f = p~ - q,   nu = A n_p
- *     P(n) = n n^T / (n . n)  if n . n (as computed in fp64) is finite and > 0,  else the zero matrix      (such a normal means C = I)
+ *     P(n) = n n^T / (n . n)  if 2^-1022 <= n . n < inf (as computed in fp64),  else the zero matrix       (such a normal means C = I)
+ *            (n . n zero, subnormal, overflowed or NaN: a zero normal, one with a NaN or Inf component, one whose components are below
+ *             about 1e-154 or above about 1e154 in size.  A subnormal n . n has lost the bits that say how long n is.)
  *     S = 2 I - (1 - epsilon) (P(n_q) + P(nu)),      W = 2 epsilon S^-1                  (symmetric, eigenvalues in [epsilon, 1])
  *     s = f^T W f
  *     J_f = [ A , -A [p]x , -I , [p~]x ]                                  (3 x 12, coordinates [ups_s om_s ups_d om_d], T <- T exp(delta))

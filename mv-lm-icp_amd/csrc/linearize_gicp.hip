@@ -3,7 +3,7 @@
 //
 // With the relative transform of linearize_sym.hip (hi + lo, api.cpp upload_rel_sym), a correspondence (p, n_p) of the source frame and (q, n_q) of the dst frame:
 //   x' = A p,  p~ = x' + t,  f = p~ - q,  a = n_q,  b = nu = A n_p
-//   P(n) = n n^T / (n . n) if n . n is finite and > 0 (as computed in fp64), else 0
+//   P(n) = n n^T / (n . n) if 2^-1022 <= n . n < inf (as computed in fp64: a normal number), else 0
 //   S = 2 I - (1 - eps) (P(a) + P(b)),  W = 2 eps S^-1                        (symmetric, eigenvalues in [eps, 1]; eps = 1: W = I)
 //   s = f^T W f,  J_f = [A, -A [p]x, -I, [p~]x]                                (W frozen at the evaluation poses, fixed in the dst frame)
 // For any W = sum_k g_k g_k^T the three rows r_k = g_k . f have the plane family's form u'_k = [g_k ; x' x g_k], u_k = L u'_k, J_k = [Ad^T u_k ; -u_k], and
@@ -12,7 +12,7 @@
 // in the plane partial layout, so the per-edge expansion is reduce_expand_kernel<true, 1> (lin_common.h), unchanged.  Loss, corrector, half_rho, the
 // scale a = edge.weight and the cost sum rho / 2 are the point family's: soft-L1 on the squared length s of a three-vector; s <= |f|^2.
 //
-// W without an inverse that cancels.  With a^, b^ the normalised normals (0 for a zero or non-finite one), d = a^ . b^, c = 1 - eps, Woodbury gives
+// W without an inverse that cancels.  With a^, b^ the normalised normals (0 where P(n) = 0), d = a^ . b^, c = 1 - eps, Woodbury gives
 //   W = eps I + kappa [ (1 + eps) (a^ a^T + b^ b^T) + c d (a^ b^T + b^ a^T) ],   kappa = eps c / Delta,
 //   Delta = (1 + eps)^2 - c^2 d^2 = 4 eps + c^2 |a^ x b^|^2                     (Lagrange's identity: both terms >= 0, nothing cancels as |d| -> 1)
 // and with one of the two normals missing |a^ x b^|^2 is replaced by 1 (Delta = (1 + eps)^2: W = eps I + eps c / (1 + eps) b^ b^T); with both, W = eps I.
@@ -20,7 +20,7 @@
 //
 // Operation order per correspondence (explicit fma):
 //   x'_i, nu_i, f_i, : as linearize_sym.hip (f by residual_component, lin_residual.h)
-//   alpha = fma(a2, a2, fma(a1, a1, a0 * a0)),  ok_a = alpha > 0 && alpha < inf,  a^_i = ok_a ? a_i * fast_rsqrt(alpha) : 0;  the same for b
+//   alpha = fma(a2, a2, fma(a1, a1, a0 * a0)),  ok_a = alpha >= 2^-1022 && alpha < inf,  a^_i = ok_a ? a_i * fast_rsqrt(alpha) : 0;  the same for b
 //   d = fma(a^2, b^2, fma(a^1, b^1, a^0 * b^0));  z = a^ x b^ with z_0 = fma(a^1, b^2, -(a^2 * b^1)) and cyclically;  z2 = ok_a && ok_b ? |z|^2 : 1
 //   Delta = fma(c * c, z2, 4 eps);  kappa = (eps c) / Delta  (v_rcp_f64 seed + two Newton steps);  k1 = kappa (1 + eps),  k2 = kappa (c d)
 //   a'_i = fma(k2, b^_i, k1 * a^_i),  b'_i = fma(k2, a^_i, k1 * b^_i);  W_ij = fma(b^_i, b'_j, fma(a^_i, a'_j, i == j ? eps : 0))  for i <= j
@@ -42,10 +42,11 @@ namespace {
 // the constants of one launch that depend on eps alone
 struct GicpEps { double eps, c, c2, four_eps, eps_c, one_p_eps; };
 
-// n / |n|, or 0 where n . n is zero or not finite; ok says which
+// n / |n|, or 0 where n . n is below 2^-1022 (zero or subnormal: it no longer carries the length of n) or not finite; ok says which.
+// fast_rsqrt (documented for y >= 1) is used on [2^-1022, inf): y r r stays of order 1 there, and r r <= 2^1022 does not overflow.
 __device__ __forceinline__ bool unit_or_zero(double n0, double n1, double n2, double& u0, double& u1, double& u2) {
   const double nn = __builtin_fma(n2, n2, __builtin_fma(n1, n1, n0 * n0));
-  const bool ok = nn > 0.0 && nn < __builtin_inf();
+  const bool ok = nn >= 0x1p-1022 && nn < __builtin_inf();
   const double r = fast_rsqrt(ok ? nn : 1.0);
   u0 = ok ? n0 * r : 0.0; u1 = ok ? n1 * r : 0.0; u2 = ok ? n2 * r : 0.0;
   return ok;

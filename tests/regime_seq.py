@@ -52,7 +52,8 @@ def run(eng, pb, events, after_search=None, after_round=None):
     Hooks (tests/test_gpu_sym_regimes.py; the sharded tests use none): after_search(state) runs between the round's search and its solve,
     after_round(state) after the solve; state = {"round", "event", "poses", "fixed", "cutoff", "method", "options", "counts", "weights"}, the
     round's own values ("options": what the script has set so far).  A kind the scripts above never draw, for hand-written events: "normals"
-    (mvicp_recompute_normals(frame, 10) before the round's search; the new normals go to state["normals"])."""
+    (mvicp_recompute_normals(frame, 10) before the round's search; the new normals go to state["normals"]).  And a metric they never draw: 3, the
+    plane-to-plane objective — the round's solve is mvicp_optimize_gicp at e["epsilon"] (default 1e-3; tests/test_gpu_gicp_regimes.py)."""
     poses = pb["init"].copy()
     fixed = pb["fixed"].copy()
     cutoff, method, rule = 0.05, 0, 1
@@ -95,7 +96,9 @@ def run(eng, pb, events, after_search=None, after_round=None):
         if after_search is not None:
             after_search(state)
         if k not in ("hold", "fail") and counts.sum() > 0:
-            if "metric" in e:
+            if e.get("metric") == 3:       # hand-written events only (script() draws 0, 1, 2): the plane-to-plane objective, which has no mvicp_metric value
+                poses, _ = eng.optimize_gicp(poses, fixed, e["param"], e.get("epsilon", 1e-3), e["robust"], 50)
+            elif "metric" in e:
                 poses, _ = eng.optimize_metric(poses, fixed, e["param"], e["metric"], e["robust"], 50)
             else:
                 poses, _ = eng.optimize(poses, fixed, e["param"], e["plane"], e["robust"], 50)

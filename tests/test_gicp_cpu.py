@@ -279,3 +279,93 @@ def test_gicp_registration_ends_closer_to_the_truth_than_point_to_plane(partial)
     print("partial=%s  " % partial + "  |  ".join("%s ends %.4f deg, %.4f spacings" % (k, v[0], v[1]) for k, v in got.items())
           + "  (plane / gicp: %.1f, %.1f)" % (got["plane"][0] / got["gicp"][0], got["plane"][1] / got["gicp"][1]))
     assert got["gicp"][0] < got["plane"][0] and got["gicp"][1] < got["plane"][1], got
+
+
+# ---------------------------------------------------------------- the predicate of P(n): 2^-1022 <= n . n < inf on the fp64 value
+def test_a_subnormal_n_dot_n_is_a_missing_normal_and_why():
+    """tests/gicpcases.py's subnormal band: rows scaled to lengths 2^-536 ... 2^-512, so n . n computed in fp64 is a subnormal number with 2 to 50 bits.
+    (i) What the predicate `n . n > 0` gave there, with the kernel's operation order emulated in numpy fp64 (gicpcases.kernel_unit_fp64): a^ is
+    off unit length by the relative rounding of n . n, up to 2^-2 — and W = eps I + kappa [...] is off by as much, against a bar that is 32 x an
+    fp64 evaluation's 1e-13.  A reference that normalises in long double does not see it: that was a band the specification did not cover.
+    (ii) The rule now: P(n) = 0 unless 2^-1022 <= n . n < inf as computed in fp64 (include/mvicp.h).  gicpref takes the predicate on the fp64
+    value whatever type it computes in, so these rows, rows whose n . n overflows fp64 (1e200: finite in long double) or underflows to 0
+    (1e-200: positive in long double), and NaN / Inf rows give exactly the sums of the same case with those normals set to 0."""
+    import gicpcases
+    eps = 1e-3
+    case = symcases.make_case("subnormal", seed=1600, N=2001, M=3000, chunk=512)
+    unit_nor = case["nor"].copy()
+    rows = gicpcases.subnormal(case)
+    scaled = case["nor"][rows[0]]
+    with np.errstate(under="ignore"):
+        nn = (scaled * scaled).sum(axis=1)
+    assert np.all(nn > 0) and np.all(nn < gicpref.TINY)
+    u = gicpcases.kernel_unit_fp64(scaled)
+    off = np.abs((u * u).sum(axis=1) - 1)
+    away = np.abs(u - unit_nor[rows[0]]).max(axis=1)          # (the rows were unit vectors before the scaling)
+    print("subnormal n . n, predicate `> 0`: |a^|^2 - 1 up to %.1e (over 1e-6 on %d of %d rows); a^ away from n / |n| by up to %.1e" % (
+        off.max(), int((off > 1e-6).sum()), len(off), away.max()))
+    assert off.max() > 1e-2 and (off > 1e-6).sum() > 50           # the hole: far beyond any bar
+    assert not gicpref.has_normal(scaled.T).any() and gicpref.has_normal(unit_nor.T).all()
+    for edit in (None, gicpcases.nonfinite):
+        c = case if edit is None else symcases.make_case("nonfinite", seed=1700, N=2001, M=3000, chunk=512)
+        r = rows if edit is None else edit(c)
+        z = gicpcases.zeroed(c, r)
+        Pd, Ps = c["poses"]
+        for robust in (1, 0):
+            got, want = gicpref.edge_block(*symcases.gathered(c), Ps, Pd, c["a"], eps, robust), gicpref.edge_block(*symcases.gathered(z), Ps, Pd, c["a"], eps, robust)
+            assert np.array_equal(gicpref.pack(*got), gicpref.pack(*want)) and np.all(np.isfinite(gicpref.pack(*got).astype(np.float64)))
+            assert np.array_equal(gicpref.blocks_fp64(*symcases.gathered(c), Ps, Pd, c["a"], eps, robust), gicpref.blocks_fp64(*symcases.gathered(z), Ps, Pd, c["a"], eps, robust))
+            got_c = gicpref.centred_blocks(*symcases.gathered(c), Ps, Pd, c["a"], eps, robust)
+            assert np.array_equal(gicpref.pack(*got_c), gicpref.pack(*gicpref.centred_blocks(*symcases.gathered(z), Ps, Pd, c["a"], eps, robust)))
+
+
+# ---------------------------------------------------------------- plane-to-plane solves that reject steps (tests/gicpreject.py)
+@pytest.fixture(scope="module")
+def gicprej_world(orc):
+    import lmreject
+    pb, corr, w = lmreject.lists_at_init(orc)
+    return pb, corr, w
+
+
+def _gicprej_cases():
+    import gicpreject
+    return [pytest.param(c, id=gicpreject.case_id(c)) for c in gicpreject.CASES]
+
+
+@pytest.mark.parametrize("case", _gicprej_cases())
+def test_gicp_reference_solves_reject_as_recorded(gicprej_world, case, monkeypatch, capfd):
+    """The reference of tests/test_gpu_gicp_rejected.py — the host solve over gicpref.blocks_fp64 at epsilon = 1e-3 — from the starts of
+    tests/gicpreject.py: its iterations and successful steps are the recorded ones, it stops on the function tolerance (the one AT_LIMIT case:
+    at the iteration limit), a must-reject case rejects at least two steps, and no accept / reject decision of any case is closer than 1e-6
+    to min_relative_decrease (the recorded margins hold): device blocks that agree with the fp64 rows to 1e-11 cannot flip a decision, so the
+    GPU test may assert equal COUNTS."""
+    import gicpreject
+    pb, corr, w = gicprej_world
+    P0, P, sm, rd = gicpreject.traced_reference_solve(pb, corr, w, case, 50, monkeypatch, capfd)
+    margin = float(np.abs(rd - gicpreject.MIN_RELATIVE_DECREASE).min())
+    rejected = int((rd <= gicpreject.MIN_RELATIVE_DECREASE).sum())
+    print(gicpreject.case_id(case), sm["iterations"], "/", sm["successful_steps"], "termination", sm["termination"], "| rejected", rejected,
+          "| min |relative_decrease - 1e-3| = %.3e" % margin)
+    assert (sm["iterations"], sm["successful_steps"]) == gicpreject.MEASURED[case], sm
+    assert sm["termination"] == (0 if case in gicpreject.AT_LIMIT else 3), sm
+    assert rejected == sm["iterations"] - sm["successful_steps"] - (0 if case in gicpreject.AT_LIMIT else 1)
+    if case in gicpreject.REJECTING:
+        assert rejected >= 2, (sm, rd)
+    else:
+        assert rejected == 0, (sm, rd)
+    assert margin > 1e-6 and margin >= gicpreject.MEASURED_MARGIN[case], (margin, rd)
+    assert not np.array_equal(P, P0)
+
+
+def test_gicp_rejecting_cases_cover_both_losses_and_both_rotation_parameterizations():
+    import gicpreject
+    R = gicpreject.REJECTING
+    assert len(R) >= 4 and {c[1] for c in R} == {0, 1} and {mlib.PARAM_EIGEN_QUATERNION, mlib.PARAM_ANGLE_AXIS} <= {c[2] for c in R}, R
+
+
+@pytest.mark.parametrize("case", _gicprej_cases())
+def test_gicp_reference_solves_stop_at_the_iteration_limit(gicprej_world, case):
+    import gicpreject
+    pb, corr, w = gicprej_world
+    _, _, sm = gicpreject.reference_solve(pb, corr, w, case, 3)
+    assert sm["termination"] == 0 and sm["iterations"] == 3 and sm["evaluations"] == 4, sm

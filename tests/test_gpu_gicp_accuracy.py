@@ -8,10 +8,14 @@ the angle family.  tests/test_gicp_cpu.py checks on the CPU that the reference's
 
 Routes, at the sizes of the symmetric sweep (tests/symcases.py): explicit lists, a strict-subset list (a `first` that is not the identity), a
 searched identity list with lin_share_p 1 and 0, a three-frame graph (interleaved launch order, an empty edge, a subset), and zero normals on
-either side.  Every case prints its worst ratio; the table is in DESIGN.md section 3.17."""
+either side.  Normal families (tests/gicpcases.py), each on an explicit list of 2 001 of 3 000 at chunk 512 and on a searched identity list of
+513: nearly parallel and antiparallel normals at epsilon 1e-6 ... 1, flipped normals (same bytes), normals of any length, and normals whose
+n . n is subnormal, overflows, underflows or is not finite (the bytes of the case with those normals set to 0).  Every case prints its worst
+ratio; the tables are in DESIGN.md section 3.17."""
 import numpy as np
 import pytest
 
+import gicpcases
 import gicpref
 import lincases
 import mvicp
@@ -203,3 +207,134 @@ def test_gicp_zero_normals_on_either_side():
         assert (zq & ~zp).sum() > 100 and (zp & ~zq).sum() > 100 and (zp & zq).sum() > 10
     failures = _run_explicit("zero normals", dict(N=2001, M=3000, chunk=512), seed=1200, edit=edit)
     assert not failures, failures
+
+
+# ---------------------------------------------------------------- normal families (tests/gicpcases.py)
+# symcases draws n_q and n_p independently, so d = a^ . b^ is spread over [-1, 1] and Delta = 4 eps + c^2 |a^ x b^|^2 is seldom near its lower end.
+# Each family below runs on two routes: an explicit list of 2 001 pairs on clouds of 3 000 at chunk 512 (four partials, an odd tail, n_p gathered
+# through `first`), and a searched identity list of 513 at chunk 512 (the route of test_gicp_sweep_searched_identity_list).
+FAMILY_ROUTES = {"explicit": dict(N=2001, M=3000, chunk=512), "searched": symcases.SEARCHED[0]}
+
+
+def _family_blocks(route, seed, edit, epsilons, label, robusts=(1, 0)):
+    """the case of `route` after edit(case) -> (case, first, second, a, {(eps, robust): block})"""
+    case = symcases.make_case(label, seed=seed, **FAMILY_ROUTES[route])
+    edit(case)
+    eng = _engine(case)
+    try:
+        if route == "explicit":
+            first, second, a = case["first"], case["second"], case["a"]
+            eng.set_correspondences(0, first, second, a)
+        else:
+            counts, weights = eng.correspond(case["search_poses"], [1, 0], 100 * lincases.NOISE)
+            assert counts[0] == len(case["src"]), (counts, len(case["src"]))
+            first, second, _ = eng.get_correspondences(0)
+            assert np.array_equal(first, np.arange(len(case["src"])))
+            a = weights[0]
+        blocks = {(eps, r): eng.linearize_gicp(case["poses"], eps, r)[0] for eps in epsilons for r in robusts}
+    finally:
+        eng.close()
+    return case, first, second, a, blocks
+
+
+def _judge_blocks(blocks, ref_case, first, second, a, label, failures):
+    """every block against gicpref on the normals of ref_case, by the bar"""
+    p, q, nq, npn = symcases.gathered(ref_case, first, second)
+    for eps in sorted({k[0] for k in blocks}):
+        refs = _references(p, q, nq, npn, ref_case["poses"][1], ref_case["poses"][0], a, eps)
+        for (e, r), blk in blocks.items():
+            if e == eps:
+                _judge(blk, refs[r][0], refs[r][1], label, eps, r, failures)
+
+
+@pytest.mark.parametrize("route", list(FAMILY_ROUTES))
+@pytest.mark.parametrize("theta", gicpcases.THETAS, ids=gicpcases.theta_name)
+def test_gicp_parallel_normals(theta, route):
+    """n_p = A^T R(theta) n_q (gicpcases.parallel): theta = 0, 1e-8, 1e-4, 1e-2, pi - 1e-4, pi; epsilon = 1e-6, 1e-4, 1e-3, 1; robust on and off.  The
+    normals of a registration: Delta = 4 eps + c^2 |a^ x b^|^2 at its lower end, kappa = eps c / Delta at its largest — the regime of the claim
+    that nothing cancels as the normals become parallel (csrc/linearize_gicp.hip), which tests/test_gicp_cpu.py checks for the reference only.
+    The reference at epsilon = 1e-6: gicpref's long-double W resolves 2^-64 / eps = 5e-14 there (5e-16 at 1e-4, gicpref's docstring), and the
+    fp64 yardstick's worst piece is about 2e-10 (2e-12 at 1e-4, 2e-13 at 1e-3, 4e-14 at 1; CPU, N = 513), so the reference is far inside the bar.
+    The bar at 1e-6 is LOOSE for the same reason: it catches a wrong limit, not a cancellation no worse than the cofactor inverse's — so every
+    case prints the kernel's own error next to the yardstick's (the GICP lines; table in DESIGN.md section 3.17)."""
+    label = "parallel theta=%s %s" % (gicpcases.theta_name(theta), route)
+    case, first, second, a, blocks = _family_blocks(route, 1300, lambda c: gicpcases.parallel(c, theta), gicpcases.PARALLEL_EPSILONS, label)
+    p, q, nq, npn = symcases.gathered(case, first, second)
+    A = case["poses"][0][:3, :3].T @ case["poses"][1][:3, :3]
+    cosang = np.einsum("ij,ij->i", nq, npn @ A.T)
+    assert np.median(np.abs(cosang - np.cos(theta))) <= 1e-12       # the list's pairs carry the tilt asked for
+    failures = []
+    _judge_blocks(blocks, case, first, second, a, label, failures)
+    assert not failures, failures
+
+
+@pytest.mark.parametrize("route", list(FAMILY_ROUTES))
+def test_gicp_flipped_normals_give_the_same_bytes(route):
+    """A random half of the destination normals and, independently, of the source normals negated: the blocks equal the unflipped case's byte for
+    byte (epsilon 1e-3 and 1, robust on and off), and are gicpref's for the flipped normals by the bar.  By the operation order of
+    csrc/linearize_gicp.hip: nu -> -nu and a^ -> -a^ exactly (every product changes sign, no sum is reordered); d and k2 change sign; a' changes
+    sign with a^ (or b' with b^); z -> -z leaves |z|^2; so every W_ij = fma(b^_i, b'_j, fma(a^_i, a'_j, .)) is unchanged bit for bit."""
+    label = "sign " + route
+    _, _, _, _, plain = _family_blocks(route, 1400, lambda c: None, EPSILONS, label + " (unflipped)")
+    case, first, second, a, blocks = _family_blocks(route, 1400, gicpcases.sign, EPSILONS, label)
+    p, q, nq, npn = symcases.gathered(case, first, second)
+    assert np.all(np.abs(np.linalg.norm(nq, axis=1) - 1) < 1e-12)
+    failures = []
+    _judge_blocks(blocks, case, first, second, a, label, failures)
+    for k in blocks:
+        assert blocks[k].tobytes() == plain[k].tobytes(), (route, k, float(np.abs(blocks[k] - plain[k]).max()))
+    assert not failures, failures
+
+
+@pytest.mark.parametrize("route", list(FAMILY_ROUTES))
+def test_gicp_normals_of_any_length(route):
+    """Every normal of both sides times 2^k, k uniform in [-500, 500] per normal: gicpref's by the bar (P(n) does not depend on |n|; n . n stays a
+    normal number, where fast_rsqrt is used outside the range lin_common.h documents it for).  Printed, not asserted: whether the bytes are the
+    unscaled case's (v_rsq_f64 and the Newton steps need not commute with a power of 4)."""
+    label = "length " + route
+    _, _, _, _, plain = _family_blocks(route, 1500, lambda c: None, EPSILONS, label + " (unscaled)")
+    case, first, second, a, blocks = _family_blocks(route, 1500, gicpcases.length, EPSILONS, label)
+    failures = []
+    _judge_blocks(blocks, case, first, second, a, label, failures)
+    print("GICP  %s: bytes equal to the unscaled case's: %s" % (label, {k: blocks[k].tobytes() == plain[k].tobytes() for k in blocks}))
+    assert not failures, failures
+
+
+def _as_missing(route, seed, family, label):
+    """the rows family(case) spoils must count as missing normals: finite blocks, byte for byte those of the same case with these rows set to 0, and
+    gicpref's for the zeroed normals by the bar"""
+    rows = {}
+    case, first, second, a, blocks = _family_blocks(route, seed, lambda c: rows.update(r=family(c)), EPSILONS, label)
+    zcase = gicpcases.zeroed(case, rows["r"])
+
+    def put_zeroed(c):
+        c["nor"][:] = zcase["nor"]; c["snor"][:] = zcase["snor"]
+
+    _, zfirst, zsecond, za, zblocks = _family_blocks(route, seed, put_zeroed, EPSILONS, label + " (zeroed)")
+    assert np.array_equal(first, zfirst) and np.array_equal(second, zsecond) and a == za
+    p, q, nq, npn = symcases.gathered(zcase, first, second)
+    zq, zp = ~np.any(nq != 0, axis=1), ~np.any(npn != 0, axis=1)
+    assert (zq & ~zp).sum() >= 100 and (zp & ~zq).sum() >= 100 and (zp & zq).sum() >= 4, ((zq & ~zp).sum(), (zp & ~zq).sum(), (zp & zq).sum())
+    failures = []
+    for k in blocks:
+        assert np.all(np.isfinite(blocks[k])), (label, k)
+    _judge_blocks(blocks, zcase, first, second, a, label, failures)
+    for k in blocks:
+        assert blocks[k].tobytes() == zblocks[k].tobytes(), (label, k, float(np.abs(blocks[k] - zblocks[k]).max()))
+    assert not failures, failures
+
+
+@pytest.mark.parametrize("route", list(FAMILY_ROUTES))
+def test_gicp_subnormal_n_dot_n_is_a_missing_normal(route):
+    """Rows scaled to lengths 2^-536 ... 2^-512: n . n is a subnormal fp64 number with 2 to 50 bits left.  With the predicate `n . n > 0` the kernel's a^
+    was off unit length by up to 2^-2 there and the block missed gicpref by far more than any bar (tests/test_gicp_cpu.py shows it on the CPU).
+    On an MI355X that build's pieces were off by up to 1.6 (H), 1.1 (g), 0.6 (cost) relative at epsilon = 1e-3 on these cases.
+    The contract now asks 2^-1022 <= n . n < inf, taken on the fp64 value, and these rows count as missing normals."""
+    _as_missing(route, 1600, gicpcases.subnormal, "subnormal " + route)
+
+
+@pytest.mark.parametrize("route", list(FAMILY_ROUTES))
+def test_gicp_nonfinite_and_out_of_range_normals_are_missing_normals(route):
+    """A NaN component, a +-Inf component, components of 1e200 (n . n overflows), components of 1e-200 (n . n underflows to 0), on about 300 rows of
+    each side and on both sides of a few pairs.  mvicp_set_frame does not look at normals, so all of them reach the kernel."""
+    _as_missing(route, 1700, gicpcases.nonfinite, "nonfinite " + route)

@@ -279,3 +279,30 @@ def test_gicp_registration_on_the_gpu_ends_closer_to_the_truth_than_point_to_pla
     print("GPU partial=%s  point-to-plane ends %.4f deg, %.4f spacings  |  gicp ends %.4f deg, %.4f spacings  (ratios %.1f, %.1f)" % (
         partial, a[0], a[1], b[0], b[1], a[0] / b[0], a[1] / b[1]))
     assert b[0] < a[0] and b[1] < a[1], got
+
+
+def test_epsilon_belongs_to_the_call_and_is_not_kept(pb):
+    """epsilon is an argument of every plane-to-plane call; the context keeps the last one (c->gicp_eps) only for the evaluations of a running
+    solve.  On the 3-frame problem: mvicp_linearize_gicp(Q, 1e-3), then mvicp_optimize_gicp at 1e-2, then mvicp_linearize_gicp(Q, 1e-3) again give
+    the same bytes; and mvicp_linearize_gicp(Q, 1e-2) after a solve at 1e-3 equals the same call on a fresh engine that holds the same lists."""
+    eng, fresh = _engine(pb), _engine(pb)
+    try:
+        Q = pb["init"]
+        c, w = eng.correspond(Q, pb["fixed"], CUTOFF)
+        first = eng.linearize_gicp(Q, 1e-3, True)
+        P, sm = eng.optimize_gicp(Q, pb["fixed"], L.PARAM_SOPHUS_SE3, 1e-2, True, 50)
+        assert sm["successful_steps"] >= 1 and not np.array_equal(P, Q)
+        again = eng.linearize_gicp(Q, 1e-3, True)
+        assert again.tobytes() == first.tobytes(), float(np.abs(again - first).max())
+        eng.optimize_gicp(Q, pb["fixed"], L.PARAM_SOPHUS_SE3, 1e-3, True, 50)
+        got = eng.linearize_gicp(Q, 1e-2, True)
+        cf, wf = fresh.correspond(Q, pb["fixed"], CUTOFF)        # the same search: the same lists and scales
+        assert np.array_equal(c, cf) and w.tobytes() == wf.tobytes()
+        for e in range(len(pb["src"])):
+            for x, y in zip(eng.get_correspondences(e), fresh.get_correspondences(e)):
+                assert x.tobytes() == y.tobytes(), e
+        want = fresh.linearize_gicp(Q, 1e-2, True)
+        assert got.tobytes() == want.tobytes(), float(np.abs(got - want).max())
+        assert got.tobytes() != first.tobytes() and np.all(np.isfinite(got))
+    finally:
+        eng.close(); fresh.close()

@@ -366,20 +366,22 @@ def test_local_failure_in_a_symmetric_evaluation_reaches_every_rank(tmp_path):
 
 
 # ---------------------------------------------------------------- a refused evaluation is refused on every rank
+GICP = 3             # not an mvicp_metric value: the plane-to-plane objective has calls of its own (mvicp_linearize_gicp / mvicp_optimize_gicp, epsilon 1e-3 here)
 REFUSAL_FRAME = 4    # of make_problem(5, .): edges 3->4, 4->3, 4->2 touch it, all owned by rank 1 of 2 (asserted below)
 
 
 def _refusal_rounds(eng, pb, metric):
     """frame 4 has no normals: evaluate (must be refused), give it normals, evaluate again -> (message of the refusal, blocks after)"""
     import mvicp
+    evaluate = (lambda: eng.linearize_gicp(pb["init"], 1e-3, 1)) if metric == GICP else (lambda: eng.linearize_metric(pb["init"], metric, 1))
     eng.correspond(pb["init"], pb["fixed"], 0.05)
     msg = ""
     try:
-        eng.linearize_metric(pb["init"], metric, 1)
+        evaluate()
     except mvicp.MvicpError as ex:
         msg = str(ex)
     eng.recompute_normals(REFUSAL_FRAME, 10)
-    return msg, eng.linearize_metric(pb["init"], metric, 1)
+    return msg, evaluate()
 
 
 def _refusal_engine(rank, world, allreduce):
@@ -407,7 +409,7 @@ def _refusal_worker(rank, world, port, out, metric):
 
 
 @pytest.mark.timeout(300)
-@pytest.mark.parametrize("metric", [1, 2], ids=["PLANE", "SYMMETRIC"])
+@pytest.mark.parametrize("metric", [1, 2, GICP], ids=["PLANE", "SYMMETRIC", "GICP"])
 def test_an_evaluation_refused_on_one_rank_is_refused_on_every_rank(tmp_path, metric):
     """check_evaluable looks at the edges a rank owns.  Frame 4 has no normals and only rank 1's edges touch it: rank 1 refuses the evaluation
     (MVICP_ERR_STATE, naming the frame) and enters the collective with the slot poisoned, so rank 0 — which owns nothing to refuse — returns
@@ -424,6 +426,8 @@ def test_an_evaluation_refused_on_one_rank_is_refused_on_every_rank(tmp_path, me
     mp.spawn(_refusal_worker, args=(2, _free_port(), out, metric), nprocs=2, join=True)
     msgs = [open(f"{out}.{r}.log").read() for r in range(2)]
     assert "needs normals on frame %d" % REFUSAL_FRAME in msgs[1], msgs
+    if metric == GICP:
+        assert "gicp needs normals on frame %d" % REFUSAL_FRAME in msgs[1], msgs     # (its own arm of check_evaluable)
     assert "peer rank failed" in msgs[0], msgs
     eng, pb = _refusal_engine(0, 1, None)
     msg, blocks = _refusal_rounds(eng, pb, metric)
@@ -433,3 +437,60 @@ def test_an_evaluation_refused_on_one_rank_is_refused_on_every_rank(tmp_path, me
     for r in range(2):
         got = np.load(f"{out}.{r}.npy")
         assert got.tobytes() == blocks.tobytes(), (r, float(np.abs(got - blocks).max()))
+
+
+# ---------------------------------------------------------------- the plane-to-plane objective, sharded
+GICP_ROUNDS = [1, GICP, GICP, 1, GICP]     # per round: PLANE or plane-to-plane.  GICP follows an arming solve, and a plane solve follows GICP
+
+
+def _gicp_rounds_run(rank, world, allreduce):
+    """-> (log, spec.hit): five rounds of search + solve on make_problem(5, 1500)"""
+    import mvicp
+    from mvicp import synth
+    pb = synth.make_problem(5, 1500)
+    eng = mvicp.Engine(0, rank=rank, world=world)
+    eng.set_frames(pb["pts"], pb["nor"]); eng.set_graph(pb["src"], pb["dst"])
+    if allreduce is not None:
+        eng.comm_set_callback(allreduce)
+    eng.profile(True)
+    poses = pb["init"].copy()
+    log = []
+    for metric in GICP_ROUNDS:
+        c, w = eng.correspond(poses, pb["fixed"], 0.05)
+        if metric == GICP:
+            poses, _ = eng.optimize_gicp(poses, pb["fixed"], mvicp.lib.PARAM_SOPHUS_SE3, 1e-3, True, 50)
+        else:
+            poses, _ = eng.optimize_metric(poses, pb["fixed"], mvicp.lib.PARAM_SOPHUS_SE3, metric, True, 50)
+        log.append((c.copy(), w.tobytes(), poses.copy()))
+    hits = eng.profile_get("spec.hit")[1]
+    eng.close()
+    return log, hits
+
+
+def _gicp_rounds_worker(rank, world, port, out):
+    allreduce = _group(rank, world, port)
+    sys.path.insert(0, os.path.join(ROOT, "mv-lm-icp_amd")); sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import regime_seq
+    log, hits = _gicp_rounds_run(rank, world, allreduce)
+    regime_seq.save(f"{out}.{rank}.npz", log)
+    np.save(f"{out}.{rank}.hits.npy", np.array([hits]))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+@pytest.mark.timeout(300)
+def test_gicp_rounds_sharded_match_single_process(tmp_path):
+    """mvicp_optimize_gicp on TWO ranks: its evaluations take the exchange branch of evaluate_blocks (upload_rel_sym before the collective, the
+    per-rank c->gicp_eps, its own arm of check_evaluable), between plane solves that arm the queued evaluation and consume it.  Five rounds of
+    search + solve, objectives PLANE, GICP, GICP, PLANE, GICP at epsilon 1e-3: after EVERY round each rank's counts, weight bits and poses equal
+    the single process's bit for bit, and so does the number of evaluations served from the queue."""
+    sys.path.insert(0, os.path.join(ROOT, "mv-lm-icp_amd")); sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import regime_seq
+    out = str(tmp_path / "gicp_rounds")
+    mp.spawn(_gicp_rounds_worker, args=(2, _free_port(), out), nprocs=2, join=True)
+    log, hits1 = _gicp_rounds_run(0, 1, None)
+    assert all(l[0].sum() > 0 for l in log)
+    assert not np.array_equal(log[-1][2], log[0][2])      # the later rounds moved the poses
+    for r in range(2):
+        regime_seq.assert_equal(f"{out}.{r}.npz", log, ("gicp_rounds", r))
+        assert np.load(f"{out}.{r}.hits.npy")[0] == hits1, (r, hits1)

@@ -42,8 +42,9 @@ def _ev(kind, metric, param=2, robust=True, **kw):
     return dict(kind=kind, metric=metric, param=param, plane=1, robust=robust, **kw)
 
 
-def events():
-    tail = [
+def tail():
+    """the hand-written rounds, from the state `frame 2 fixed after a searched round` (tests/test_gpu_gicp_regimes.py replays them with its own solves)"""
+    return [
         _ev("fixed", 2, frame=2),                                  # frame 2 free again: its edges are searched afresh
         _ev("option", 2, name="list_reuse", value=1.0),
         _ev("cutoff", 1, cutoff=FULL),                             # every list full: the identity shortcut (lin_share_p is on by default)
@@ -61,7 +62,10 @@ def events():
         _ev("fixed", 1, frame=3),
         _ev("cutoff", 2, cutoff=0.05),
     ]
-    return regime_seq.script(PREFIX_SEED, K, rounds=PREFIX_ROUNDS, metrics=True) + tail
+
+
+def events():
+    return regime_seq.script(PREFIX_SEED, K, rounds=PREFIX_ROUNDS, metrics=True) + tail()
 
 
 _REFS = {}
@@ -139,7 +143,16 @@ def test_symmetric_blocks_belong_to_the_lists_after_every_round_of_a_scripted_re
     finally:
         eng.close()
 
-    # ---- the script reached the states it was written for (on the recorded rounds)
+    assert reached_states(rec, src, dst) == set(STATES), sorted(set(STATES) - reached_states(rec, src, dst))
+    metrics = [e["metric"] for e in regime_seq.solves(events())]
+    assert set(metrics) == {0, 1, 2}
+    assert len(rec) == len(events())
+    assert not failures, failures
+
+
+def reached_states(rec, src, dst):
+    """the STATES that the recorded rounds went through (rec: one dict per round, as after_round above appends them)"""
+    E = len(src)
     reached = set()
     active = lambda r: [e for e in range(E) if not r["fixed"][src[e]]]   # noqa: E731
     for i, r in enumerate(rec):
@@ -163,8 +176,4 @@ def test_symmetric_blocks_belong_to_the_lists_after_every_round_of_a_scripted_re
                 reached.add(STATES[7])
         if prev and prev["explicit"] and prev["lens"][EXPLICIT_EDGE] == N and r["fixed"][src[EXPLICIT_EDGE]] and r["lens"][EXPLICIT_EDGE] == 0:
             reached.add(STATES[8])
-    assert reached == set(STATES), sorted(set(STATES) - reached)
-    metrics = [e["metric"] for e in regime_seq.solves(events())]
-    assert set(metrics) == {0, 1, 2}
-    assert len(rec) == len(events())
-    assert not failures, failures
+    return reached
