@@ -4,7 +4,7 @@
 // form).  DESIGN.md §3.13.
 //
 // Passes, all on the context's stream, no host wait before the last one:
-//   1  moments  one lane per point in hash-CELL order (GridDev::crec): the traversal of knn_all_kernel (knn_traverse.h, stop rule B2 <= m m)
+//   1  moments  one lane per point in hash-CELL order (GridDev::crec): traverse() of knn_traverse.h (stop rule B2 <= m m)
 //               whose offer adds the neighbour's count and nine integer sums in registers -- g = floor((p_j - p_i) 2^q) fits an int, so a
 //               product is one 32 x 32 -> 64 multiply-add, and integer sums do not depend on the visiting order: no row is stored and
 //               nothing is sorted.  Then, in the same lane, D = c S - m m^T, C = D / c^2, six Jacobi sweeps and the tests; saliency and
@@ -18,6 +18,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "common.h"
+#include "jacobi3.h"
 #include "knn_traverse.h"
 #include "nn_metric.h"
 
@@ -49,32 +50,6 @@ struct IssJob {
 
 __device__ __forceinline__ int scaled_floor(double pj, double pi, double scale) { return (int)floor(__dmul_rn(__dsub_rn(pj, pi), scale)); }
 
-// the diagonal of A after kSweeps sweeps over (0,1), (0,2), (1,2): the rotation of jacobi_min_eigvec (normals.hip) without its exit test
-// and without the vectors
-__device__ __forceinline__ void jacobi_eigenvalues(double (&A)[3][3]) {
-#pragma unroll 1
-  for (int sweep = 0; sweep < kSweeps; ++sweep) {
-#pragma unroll
-    for (int pq = 0; pq < 3; ++pq) {
-      const int p = pq == 2 ? 1 : 0, q = pq == 0 ? 1 : 2;
-      if (A[p][q] == 0.0) continue;
-      const double theta = __ddiv_rn(__dsub_rn(A[q][q], A[p][p]), __dmul_rn(2.0, A[p][q]));
-      const double t = __ddiv_rn(theta >= 0 ? 1.0 : -1.0, __dadd_rn(fabs(theta), __dsqrt_rn(__dadd_rn(__dmul_rn(theta, theta), 1.0))));
-      const double c = __ddiv_rn(1.0, __dsqrt_rn(__dadd_rn(__dmul_rn(t, t), 1.0))), s = __dmul_rn(t, c);
-#pragma unroll
-      for (int r = 0; r < 3; ++r) {  // A <- A J
-        const double arp = A[r][p], arq = A[r][q];
-        A[r][p] = __dsub_rn(__dmul_rn(c, arp), __dmul_rn(s, arq)); A[r][q] = __dadd_rn(__dmul_rn(s, arp), __dmul_rn(c, arq));
-      }
-#pragma unroll
-      for (int r = 0; r < 3; ++r) {  // A <- J^T A
-        const double apr = A[p][r], aqr = A[q][r];
-        A[p][r] = __dsub_rn(__dmul_rn(c, apr), __dmul_rn(s, aqr)); A[q][r] = __dadd_rn(__dmul_rn(s, apr), __dmul_rn(c, aqr));
-      }
-    }
-  }
-}
-
 __global__ __launch_bounds__(NT) void iss_moments_kernel(IssJob job) {
   const int i = blockIdx.x * NT + threadIdx.x;   // position in cell order
   if (i >= job.g.n) return;
@@ -104,9 +79,11 @@ __global__ __launch_bounds__(NT) void iss_moments_kernel(IssJob job) {
     const double c00 = __ddiv_rn(__ll2double_rn(cc * s00 - m0 * m0), den), c01 = __ddiv_rn(__ll2double_rn(cc * s01 - m0 * m1), den);
     const double c02 = __ddiv_rn(__ll2double_rn(cc * s02 - m0 * m2), den), c11 = __ddiv_rn(__ll2double_rn(cc * s11 - m1 * m1), den);
     const double c12 = __ddiv_rn(__ll2double_rn(cc * s12 - m1 * m2), den), c22 = __ddiv_rn(__ll2double_rn(cc * s22 - m2 * m2), den);
-    double A[3][3] = {{c00, c01, c02}, {c01, c11, c12}, {c02, c12, c22}};
-    jacobi_eigenvalues(A);
-    const double a = A[0][0], b = A[1][1], e = A[2][2];
+    // the diagonal after kSweeps sweeps of jacobi3.h: no exit test, no vectors
+    jacobi3::M33 A = {c00, c01, c02, c01, c11, c12, c02, c12, c22};
+#pragma unroll 1
+    for (int sweep = 0; sweep < kSweeps; ++sweep) jacobi3::sweep(A);
+    const double a = A.m00, b = A.m11, e = A.m22;
     const double l1 = fmax(fmax(a, b), e), l3 = fmin(fmin(a, b), e);
     const double l2 = fmax(fmin(a, b), fmin(fmax(a, b), e));   // the median of three
     if (l2 < __dmul_rn(job.g21, l1) && l3 < __dmul_rn(job.g32, l2) && l3 > 0.0) sal = __dmul_rn(l3, job.unscale);

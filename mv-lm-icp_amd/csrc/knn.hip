@@ -6,18 +6,18 @@
 // Passes, all on the context's stream:
 //   k mode    1  key     (query mode, option "knn_order") clamped home cell of every query -> linear cell key; rocprim radix sort of (key, query id)
 //             2  search  one lane per query in that order (self mode: one lane per point in hash-CELL order, GridDev::crec, nothing to sort):
-//                        the growing cell block of outlier_knn_kernel with a list of (d2, index) entries; rows go to the query's own position
+//                        traverse() of knn_traverse.h with a list of (d2, index) entries; rows go to the query's own position
 //   all mode  1  key     as above
 //             2  count   the same traversal, counting the points with dist2 < B2; exits on B2 <= m m only
 //                -- rocprim exclusive scan of the counts = off; host wait: the total --
 //             3  fill    the same traversal again, the candidates of row i stored from off[i] on in visiting order
 //             4  order   one wave per row: every entry's rank under (d2, index) by counting, stored at its rank (the pairs are distinct, so the
 //                        ranks are a permutation; no sort stability is asked of anything).  O(len^2 / 64) per row: rows of thousands are correct, not fast.
-// What the search kernel takes from outlier_knn_kernel: the worst entry in registers (a candidate that cannot enter costs one comparison and
-// no LDS access), the SHELL scan when the block grows (an entry is a real point and stays valid), the scan of the cloud itself once the
-// block exceeds 2 n cells (the last resort; a query in empty space goes to the box tree first, see traverse).  What is new: entries carry
-// the original index and the comparator is the contract's order, so a candidate with d == worst and a lower index DOES enter; the radius
-// exit; the face test for queries outside the grid (face_bound below); the box-tree walk for queries in empty space.
+// What the search kernel shares with outlier_knn_kernel: the worst entry in registers (a candidate that cannot enter costs one comparison
+// and no LDS access).  The SHELL scan when the block grows (an entry is a real point and stays valid), the scan of the cloud itself once
+// the block exceeds 2 n cells (the last resort; a query in empty space goes to the box tree first), the face test for queries outside the
+// grid and the box-tree walk are traverse()'s.  This kernel's own: entries carry the original index and the comparator is the contract's
+// order, so a candidate with d == worst and a lower index DOES enter; the radius exit.
 #include <algorithm>
 #include <cmath>
 #include <cstring>

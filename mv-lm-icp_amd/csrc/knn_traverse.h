@@ -1,22 +1,17 @@
-// The growing-block traversal of the per-cloud hash that the exact neighbourhood kernels share (knn.hip: the k-nearest and radius searches;
-// iss.hip: the keypoint moments and the non-maximum suppression): the views of the structures it reads and traverse() itself.  offer gets
-// the candidate's record, so a caller that needs the neighbour's coordinates reads them from the registers the distance was computed from.
+// The growing-block traversal of the per-cloud hash, written once for every kernel that asks "which points of this cloud lie around this
+// point" (knn.hip: the k-nearest and radius searches; iss.hip: the keypoint moments and the non-maximum suppression; outlier.hip: the
+// k+1 smallest distances; normals.hip: the reference-parity k-NN lists): the views of the structures it reads and traverse() itself, with
+// every exactness argument (the face bound, the 0.999 margin, the 2 n rule).  The hash's small parts are build_common.h's.  offer gets the
+// candidate's record, so a caller that needs the neighbour's coordinates reads them from the registers the distance was computed from,
+// and one that needs its cell-order position takes record - g.crec (valid without a tree: a tree leaf's records are in sorted order).
 #pragma once
+#include "build_common.h"
 #include "common.h"
 #include "nn_metric.h"
 
 namespace mvicp {
 
 namespace {
-constexpr unsigned long long EMPTY = ~0ull;
-
-struct HashEntry { unsigned long long key; unsigned int start, count; };
-
-__device__ __forceinline__ unsigned long long cell_key(int ix, int iy, int iz) {
-  return (unsigned long long)ix | ((unsigned long long)iy << 21) | ((unsigned long long)iz << 42);
-}
-__device__ __forceinline__ unsigned int hash_slot(unsigned long long k, int shift) { return (unsigned int)((k * 0x9E3779B97F4A7C15ull) >> shift); }
-
 constexpr int kTreeAfter = 4;   // a block of this radius (9^3 cells) that has not finished hands the query to the box tree
 
 struct GridView {
@@ -70,9 +65,9 @@ __device__ __forceinline__ int home_cell(double q, double o, double inv_h, int d
 // in a cell outside that range along at least one axis, on one side of it; it is then beyond the block's face on that side, and its
 // distance to the query is at least the query's distance to that face's plane, PROVIDED the query is on the inner side of the plane.
 //   * A face that coincides with the grid boundary (c - r <= 0 on the low side, c + r >= d - 1 on the high side) has no cell beyond it,
-//     so no point is "outside the block on that side" and the face does not enter the minimum.  (The kernels that only ever query the
-//     cloud's own points take all six faces; for a query outside the grid the clamped home cell makes the boundary face's term <= 0 and
-//     the search would never stop early.)
+//     so no point is "outside the block on that side" and the face does not enter the minimum.  (With all six faces a query outside
+//     the grid would never stop early: the clamped home cell makes the boundary face's term <= 0.  One of the cloud's own points merely
+//     stops a block sooner without it.)
 //   * For every other face the query is on the inner side: on the low side c - r > 0 implies c > 0, so the home cell was not clamped from
 //     below and q >= o + c h >= o + (c - r) h + h (up to the rounding of the cell assignment); a query beyond the HIGH grid boundary has
 //     c = d - 1 and is even farther from every low face.  The high side mirrors this.  So the existing expressions q - f and f + w - q are
@@ -115,8 +110,8 @@ __device__ __forceinline__ void traverse(const GridView& g, const TreeView* tree
           const unsigned long long key = cell_key(ix, iy, iz);
           unsigned int slot = hash_slot(key, g.shift) & g.mask;
           HashEntry e = g.table[slot];
-          while (e.key != key && e.key != EMPTY) { slot = (slot + 1) & g.mask; e = g.table[slot]; }
-          if (e.key != EMPTY) scan_run(e.start, e.start + e.count);
+          while (e.key != key && e.key != kEmptyKey) { slot = (slot + 1) & g.mask; e = g.table[slot]; }
+          if (e.key != kEmptyKey) scan_run(e.start, e.start + e.count);
         }
       }
     rprev = r;

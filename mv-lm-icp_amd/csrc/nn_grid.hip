@@ -52,7 +52,6 @@ namespace {
 #define MVICP_GRID_THREADS 256
 #endif
 constexpr int NT = MVICP_GRID_THREADS;
-constexpr unsigned long long EMPTY = ~0ull;
 
 struct GridView {  // device view of one cloud's structure
   const double* spts; const int* sidx; const PointRec* srec; int n;   // canonical (sorted-position) order
@@ -200,21 +199,21 @@ __global__ __launch_bounds__(NT) void nn_grid_kernel(const GridJob* __restrict__
         const double lbc = ((df & 1) ? ax2 : 0.0) + ((df & 2) ? ay2 : 0.0) + ((df & 4) ? az2 : 0.0);
         if (lbc > rp2) { in = false; skipped = fmin(skipped, lbc); }
       }
-      key[c] = in ? cell_key(ix, iy, iz) : EMPTY;
+      key[c] = in ? cell_key(ix, iy, iz) : kEmptyKey;
       slot[c] = hash_slot(key[c], g.shift) & g.mask;
     }
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
-      ent[c].key = EMPTY; ent[c].start = 0; ent[c].count = 0;
-      if (key[c] != EMPTY) ent[c] = g.table[slot[c]];
+      ent[c].key = kEmptyKey; ent[c].start = 0; ent[c].count = 0;
+      if (key[c] != kEmptyKey) ent[c] = g.table[slot[c]];
     }
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
-      while (ent[c].key != key[c] && ent[c].key != EMPTY) {
+      while (ent[c].key != key[c] && ent[c].key != kEmptyKey) {
         slot[c] = (slot[c] + 1) & g.mask;
         ent[c] = g.table[slot[c]];
       }
-      if (ent[c].key == EMPTY) ent[c].count = 0;
+      if (ent[c].key == kEmptyKey) ent[c].count = 0;
     }
     // One flattened candidate loop per lane.  Scanning cell after cell would cost, per wave, the SUM over the 8 cells of the
     // longest run any lane has in that cell; walking each lane's own runs back to back costs the longest TOTAL of any lane
@@ -331,8 +330,8 @@ __device__ __forceinline__ double cell_lb2(const GridView& g, int ix, int iy, in
 __device__ __forceinline__ bool cell_insert(unsigned long long* __restrict__ hk, unsigned long long key) {
   unsigned int s = hash_slot(key, 64 - 7) & (CELL_HS - 1);
   for (int probe = 0; probe < 24; ++probe) {
-    const unsigned long long old = atomicCAS(&hk[s], EMPTY, key);
-    if (old == EMPTY || old == key) return true;
+    const unsigned long long old = atomicCAS(&hk[s], kEmptyKey, key);
+    if (old == kEmptyKey || old == key) return true;
     s = (s + 1) & (CELL_HS - 1);
   }
   return false;   // set (nearly) full
@@ -342,7 +341,7 @@ __device__ __forceinline__ int cell_find(const unsigned long long* __restrict__ 
   for (int probe = 0; probe < 24; ++probe) {
     const unsigned long long k = hk[s];
     if (k == key) return (int)s;
-    if (k == EMPTY) return -1;
+    if (k == kEmptyKey) return -1;
     s = (s + 1) & (CELL_HS - 1);
   }
   return -1;
@@ -369,7 +368,7 @@ __device__ __forceinline__ unsigned int cell_stage(const GridView& g, const unsi
   unsigned int staged = 0;
   for (int s = lane; s < CELL_HS; s += 64) {
     const unsigned long long key = hk[s];
-    if (key == EMPTY || hv[s] != CELL_UNSET) continue;
+    if (key == kEmptyKey || hv[s] != CELL_UNSET) continue;
     const int ix = (int)(key & 0x1fffffull), iy = (int)((key >> 21) & 0x1fffffull), iz = (int)((key >> 42) & 0x1fffffull);
     const long long b = ((long long)(iz >> 2) * g.by + (iy >> 2)) * g.bx + (ix >> 2);
     const unsigned int tab = g.bricks[b].tab;
@@ -426,7 +425,7 @@ __global__ __launch_bounds__(NT, 5) void nn_cell_kernel(const GridJob* __restric
   unsigned long long* hk = s_hkey[wave];
   unsigned int* hv = s_hval[wave];
   unsigned int* hs = s_hstart[wave];
-  hk[lane] = EMPTY; hk[lane + 64] = EMPTY;
+  hk[lane] = kEmptyKey; hk[lane + 64] = kEmptyKey;
   hv[lane] = CELL_UNSET; hv[lane + 64] = CELL_UNSET;
   if (threadIdx.x == 0) s_pool = 0u;
   if (lane < 3) s_stat[wave][lane] = 0u;

@@ -1,47 +1,21 @@
 // The per-point part of mvicp_estimate_normals that normals_pca.hip and normals_jet.hip share: the gather of a row's offsets, the tree sum,
-// the 3 x 3 Jacobi iteration and the oriented PCA normal with its surface variation.  One wave per point, lane t = entry t of the row.
+// the 3 x 3 Jacobi iteration (jacobi3.h) and the oriented PCA normal with its surface variation.  One wave per point, lane t = entry t of the row.
 // Every fp64 operation is an __d*_rn intrinsic: rounded on its own, never contracted into an fma.
 #pragma once
 #include "common.h"
+#include "jacobi3.h"
 
 namespace mvicp {
 namespace pca {
 
 constexpr int kSweeps = 6;
+using jacobi3::M33;
 
 // T(y): the sum of the 64 lanes' values in the order of the contract's tree, in every lane
 __device__ __forceinline__ double tree_sum(double v) {
 #pragma unroll
   for (int x = 1; x < 64; x <<= 1) v = __dadd_rn(v, __shfl_xor(v, x, 64));
   return v;
-}
-
-// a 3 x 3 matrix in nine named registers: every index below is a template argument, so nothing is addressed at run time
-struct M33 { double m00, m01, m02, m10, m11, m12, m20, m21, m22; };
-template <int R, int C> __device__ __forceinline__ double& at(M33& m) {
-  if constexpr (R == 0) { if constexpr (C == 0) return m.m00; else if constexpr (C == 1) return m.m01; else return m.m02; }
-  else if constexpr (R == 1) { if constexpr (C == 0) return m.m10; else if constexpr (C == 1) return m.m11; else return m.m12; }
-  else { if constexpr (C == 0) return m.m20; else if constexpr (C == 1) return m.m21; else return m.m22; }
-}
-// columns P, Q: (x[r][P], x[r][Q]) <- (c x[r][P] - s x[r][Q], s x[r][P] + c x[r][Q])
-template <int R, int P, int Q> __device__ __forceinline__ void rot_cols(M33& x, double c, double s) {
-  const double xp = at<R, P>(x), xq = at<R, Q>(x);
-  at<R, P>(x) = __dsub_rn(__dmul_rn(c, xp), __dmul_rn(s, xq)); at<R, Q>(x) = __dadd_rn(__dmul_rn(s, xp), __dmul_rn(c, xq));
-}
-template <int R, int P, int Q> __device__ __forceinline__ void rot_rows(M33& x, double c, double s) {
-  const double xp = at<P, R>(x), xq = at<Q, R>(x);
-  at<P, R>(x) = __dsub_rn(__dmul_rn(c, xp), __dmul_rn(s, xq)); at<Q, R>(x) = __dadd_rn(__dmul_rn(s, xp), __dmul_rn(c, xq));
-}
-// one rotation of the ISS contract's Jacobi iteration (iss.hip jacobi_eigenvalues) on the pair (P, Q), with the vectors
-template <int P, int Q> __device__ __forceinline__ void rotate(M33& A, M33& V) {
-  const double apq = at<P, Q>(A);
-  if (apq == 0.0) return;
-  const double theta = __ddiv_rn(__dsub_rn(at<Q, Q>(A), at<P, P>(A)), __dmul_rn(2.0, apq));
-  const double t = __ddiv_rn(theta >= 0 ? 1.0 : -1.0, __dadd_rn(fabs(theta), __dsqrt_rn(__dadd_rn(__dmul_rn(theta, theta), 1.0))));
-  const double c = __ddiv_rn(1.0, __dsqrt_rn(__dadd_rn(__dmul_rn(t, t), 1.0))), s = __dmul_rn(t, c);
-  rot_cols<0, P, Q>(A, c, s); rot_cols<1, P, Q>(A, c, s); rot_cols<2, P, Q>(A, c, s);   // A <- A J
-  rot_rows<0, P, Q>(A, c, s); rot_rows<1, P, Q>(A, c, s); rot_rows<2, P, Q>(A, c, s);   // A <- J^T A
-  rot_cols<0, P, Q>(V, c, s); rot_cols<1, P, Q>(V, c, s); rot_cols<2, P, Q>(V, c, s);   // V <- V J
 }
 
 // lane t's offset d = p_j - p_i for entry t of row i (k entries wide, len of them filled); lanes past the row carry +0.0
@@ -67,7 +41,7 @@ __device__ __forceinline__ void point_normal(double d0, double d1, double d2, in
     const double c11 = tree_sum(__dmul_rn(x1, x1)), c12 = tree_sum(__dmul_rn(x1, x2)), c22 = tree_sum(__dmul_rn(x2, x2));
     M33 A = {c00, c01, c02, c01, c11, c12, c02, c12, c22}, V = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
 #pragma unroll 1
-    for (int sweep = 0; sweep < kSweeps; ++sweep) { rotate<0, 1>(A, V); rotate<0, 2>(A, V); rotate<1, 2>(A, V); }
+    for (int sweep = 0; sweep < kSweeps; ++sweep) jacobi3::sweep(A, V);
     const double a0 = A.m00, a1 = A.m11, a2 = A.m22;
     const bool b1 = a1 < a0;
     const double l1 = b1 ? a1 : a0;

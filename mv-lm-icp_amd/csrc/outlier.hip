@@ -4,9 +4,9 @@
 // numpy form).  DESIGN.md §3.8.
 //
 // Passes, all on the context's stream:
-//   1  knn      one lane per point in hash-CELL order (GridDev::crec): the growing cell block of normals_kernel with its exactness test
-//               (the k+1-th value lies inside the scanned block's faces, or the block covers the grid), VALUES ONLY: no index, no tie
-//               order, no PCA.  Writes kd2 and mdist in original order; one atomic max per wave on the bit pattern of mdist (>= 0).
+//   1  knn      one lane per point in hash-CELL order (GridDev::crec): traverse() of knn_traverse.h without a box tree, stopping once
+//               the k+1-th value lies inside the scanned block's faces, VALUES ONLY: no index, no tie order, no PCA.  Writes kd2 and
+//               mdist in original order; one atomic max per wave on the bit pattern of mdist (>= 0).
 //      -- host wait (statistical rule only): mmax; the host chooses q_exp --
 //   2  sum      M = floor(mdist 2^q_exp) < 2^31; S1 = sum M and the two 32-bit halves of M^2 summed apart (each sum < 2^63 for
 //               n < 2^31): wave reduction, then three 64-bit integer atomics per workgroup.  Integer sums: order-independent.
@@ -14,14 +14,12 @@
 //   3  flag     keep = ((double)M <= T) and (sqrt(kd2) < radius), each rule only when it is on
 //   4  compact  exclusive scan of the flags (rocprim), then one lane per point stores its row at its rank: ascending original index
 //      -- host wait: the number kept --
-// What the knn kernel does differently from normals_kernel, and why (this kernel is the whole feature, that one runs once per cloud):
+// What the knn kernel keeps to itself next to the other users of traverse() (this kernel is the whole feature):
 //   * the list capacity is a template parameter (9 / 17 / 33 doubles per lane, one LDS column per lane): 9 / 17 / 33 KiB per 128-lane
 //     workgroup, so k <= 8 still runs at the 32-waves-per-CU cap, k <= 16 at 18 waves and only k > 16 at 8 (160 KiB of LDS per CU);
 //   * the current k+1-th value stays in a register: a candidate that cannot enter the list costs one comparison and no LDS access
 //     (after the first cell nearly every candidate);
-//   * a grown block scans only the SHELL of new cells — the list holds values only, so what the smaller block found stays valid;
-//   * a lane whose block would exceed 2 n cells (a point far from everything in a sparse grid) scans the cloud itself instead: O(n),
-//     exact by construction, where the growing block would look up O(r^3) empty cells.
+//   * the list holds values only, so offer ignores the record.
 // Consecutive cell-order lanes read the same few cells, so the candidate loads of a wave are mostly one address (a broadcast from L1).
 #include <algorithm>
 #include <cmath>
@@ -30,6 +28,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "common.h"
+#include "knn_traverse.h"
 #include "nn_metric.h"
 
 namespace mvicp {
@@ -38,20 +37,9 @@ namespace {
 
 constexpr int NT = 128;   // lanes per workgroup of the knn kernel
 constexpr int VT = 256;   // of the streaming passes
-constexpr unsigned long long EMPTY = ~0ull;
-
-struct HashEntry { unsigned long long key; unsigned int start, count; };
-
-__device__ __forceinline__ unsigned long long cell_key(int ix, int iy, int iz) {
-  return (unsigned long long)ix | ((unsigned long long)iy << 21) | ((unsigned long long)iz << 42);
-}
-__device__ __forceinline__ unsigned int hash_slot(unsigned long long k, int shift) { return (unsigned int)((k * 0x9E3779B97F4A7C15ull) >> shift); }
 
 struct KnnJob {
-  const PointRec* crec; int n;   // records in hash-CELL order
-  const HashEntry* table; unsigned int mask; int shift;
-  double ox, oy, oz, h, inv_h;
-  int dx, dy, dz;
+  GridView g;
   int k;
   double* mdist; double* kd2;    // n each, original order
   unsigned long long* mmax;      // bit pattern of the largest mdist
@@ -66,14 +54,17 @@ __global__ __launch_bounds__(NT) void outlier_knn_kernel(KnnJob job) {
   __shared__ double s_d[KCAP][NT];
 #define LD(t) s_d[t][threadIdx.x]
   const int i = blockIdx.x * NT + threadIdx.x;   // position in cell order
-  const bool active = i < job.n;
+  const bool active = i < job.g.n;
   double md = 0.0;
   if (active) {
-    const PointRec me = job.crec[i];
+    const PointRec me = job.g.crec[i];
     const int L = job.k + 1;
-    for (int t = 0; t < L; ++t) LD(t) = INFINITY;
     double worst = INFINITY;   // = LD(L - 1)
-    auto offer = [&](double d) {
+    auto reset = [&]() {
+      for (int t = 0; t < L; ++t) LD(t) = INFINITY;
+      worst = INFINITY;
+    };
+    auto offer = [&](double d, const PointRec*) {
       if (!(d < worst)) return;   // (an equal value changes nothing: only the values enter)
       int pos = L - 1;
       while (pos > 0) {
@@ -85,52 +76,11 @@ __global__ __launch_bounds__(NT) void outlier_knn_kernel(KnnJob job) {
       LD(pos) = d;
       worst = LD(L - 1);
     };
-    auto scan_run = [&](unsigned int a, unsigned int b) {
-      for (unsigned int j = a; j < b; ++j) {
-        const PointRec* p = job.crec + j;
-        offer(dist2(me.x, me.y, me.z, p->x, p->y, p->z));
-      }
-    };
-    auto scan_cells = [&](int x0, int x1, int iy, int iz) {
-      for (int ix = x0; ix <= x1; ++ix) {
-        const unsigned long long key = cell_key(ix, iy, iz);
-        unsigned int slot = hash_slot(key, job.shift) & job.mask;
-        HashEntry e = job.table[slot];
-        while (e.key != key && e.key != EMPTY) { slot = (slot + 1) & job.mask; e = job.table[slot]; }
-        if (e.key != EMPTY) scan_run(e.start, e.start + e.count);
-      }
-    };
-    const int cx = min(max((int)floor((me.x - job.ox) * job.inv_h), 0), job.dx - 1);
-    const int cy = min(max((int)floor((me.y - job.oy) * job.inv_h), 0), job.dy - 1);
-    const int cz = min(max((int)floor((me.z - job.oz) * job.inv_h), 0), job.dz - 1);
-    const int rmax = max(job.dx, max(job.dy, job.dz));
-    int rprev = -1;   // the cells within this Chebyshev distance of (cx, cy, cz) are scanned
-    for (int r = 1;; ++r) {
-      const int x0 = max(cx - r, 0), x1 = min(cx + r, job.dx - 1), y0 = max(cy - r, 0), y1 = min(cy + r, job.dy - 1);
-      const int z0 = max(cz - r, 0), z1 = min(cz + r, job.dz - 1);
-      if (r > 1 && (long long)(x1 - x0 + 1) * (y1 - y0 + 1) * (z1 - z0 + 1) > 2ll * job.n) {
-        // far from everything in a sparse grid: the cloud itself is the smaller scan
-        for (int t = 0; t < L; ++t) LD(t) = INFINITY;
-        worst = INFINITY;
-        scan_run(0u, (unsigned int)job.n);
-        break;
-      }
-      for (int iz = z0; iz <= z1; ++iz)
-        for (int iy = y0; iy <= y1; ++iy) {
-          if (max(abs(iz - cz), abs(iy - cy)) > rprev) scan_cells(x0, x1, iy, iz);
-          else {   // only the cells of this row that the smaller block did not hold
-            scan_cells(x0, min(cx - rprev - 1, x1), iy, iz);
-            scan_cells(max(cx + rprev + 1, x0), x1, iy, iz);
-          }
-        }
-      rprev = r;
-      // exact iff the k+1-th value is inside the scanned block: every unscanned point is >= m away along some axis (normals.hip)
-      const double fx = job.ox + (cx - r) * job.h, fy = job.oy + (cy - r) * job.h, fz = job.oz + (cz - r) * job.h;
-      const double w = (2 * r + 1) * job.h;
-      double m = fmin(fmin(me.x - fx, fx + w - me.x), fmin(fmin(me.y - fy, fy + w - me.y), fmin(me.z - fz, fz + w - me.z)));
-      m *= 0.999;
-      if ((m > 0.0 && worst < m * m) || r >= rmax) break;   // (worst < m m implies a full list: +inf is not below it)
-    }
+    auto stop = [&](double m2) { return worst < m2; };   // (implies a full list: +inf is not below it)
+    auto open = [](double) { return true; };
+    auto seed = [](double) {};
+    reset();
+    traverse(job.g, nullptr, me.x, me.y, me.z, 0, offer, reset, stop, open, seed);
     double s = 0.0;
     for (int t = 1; t < L; ++t) s = __dadd_rn(s, __dsqrt_rn(LD(t)));
     md = __ddiv_rn(s, (double)job.k);
@@ -229,11 +179,7 @@ long long outlier_filter(mvicp_ctx* c, const FrameDev& f, int k, double std_rati
 
   MV_HIP(hipMemsetAsync(d_ctl, 0, sizeof(OutCtl), st));
   KnnJob j;
-  const GridDev& g = f.grid;
-  j.crec = (const PointRec*)g.crec; j.n = n;
-  j.table = (const HashEntry*)g.table; j.mask = g.table_mask; j.shift = g.table_shift;
-  j.ox = g.origin[0]; j.oy = g.origin[1]; j.oz = g.origin[2]; j.h = g.cell; j.inv_h = g.inv_cell;
-  j.dx = g.dims[0]; j.dy = g.dims[1]; j.dz = g.dims[2];
+  fill_grid_view(&j.g, f.grid, n);
   j.k = k; j.mdist = c->out.mdist; j.kd2 = c->out.kd2; j.mmax = &d_ctl->mmax;
   {
     ProfScope ps(c, "outlier_knn", 0.0);

@@ -10,6 +10,7 @@ import issref
 import matchref as mr
 import mvicp
 import offorigin as oo
+import traverseref
 from mvicp import synth
 
 pytestmark = pytest.mark.gpu
@@ -75,32 +76,7 @@ def test_few_points(eng, n):
     assert_same(eng.iss_keypoints(0, 0.1, 0.1, 0.975, 0.975, 1, device=True), want, (n, "device"))
 
 
-# ---- the ways out of the traversal
-def exits(p, sc, n, radius):
-    """Which way every point's traversal (csrc/knn_traverse.h) ends at this radius, from the grid's scalars: "stop" (the block holds the
-    radius), "grid" (the block covers the grid), "cloud" (the block exceeds 2 n cells: the cloud is scanned) or "tree" (the block of
-    radius 4 has not finished: the box tree).  The face distances are taken with a margin of a hundredth of a cell, so a point this
-    function calls "cloud" or "tree" takes that way whatever the rounding of the kernel's own face arithmetic."""
-    dims, o, h = sc[:3].astype(np.int64), sc[3:6], float(sc[6])
-    out = []
-    for q in p:
-        c = np.clip(np.floor((q - o) / h), 0, dims - 1).astype(np.int64)
-        for r in range(1, 6):
-            lo, hi = np.maximum(c - r, 0), np.minimum(c + r, dims - 1)
-            if r > 1 and int(np.prod(hi - lo + 1)) > 2 * n:
-                out.append("cloud"); break
-            m = [q[a] - (o[a] + (c[a] - r) * h) for a in range(3) if c[a] - r > 0] + [o[a] + (c[a] + r + 1) * h - q[a] for a in range(3) if c[a] + r < dims[a] - 1]
-            if not m:
-                out.append("grid"); break
-            if radius <= min(m) - 0.01 * h:
-                out.append("stop"); break
-            if radius <= min(m) + 0.01 * h:
-                out.append("edge"); break
-            if r == 4:
-                out.append("tree"); break
-    return out
-
-
+# ---- the ways out of the traversal (tests/traverseref.py)
 SEP = 1000.0
 
 
@@ -132,7 +108,7 @@ def test_far_clusters_take_the_other_ways_out(eng, kind):
     sc = eng.get_structure(0, "scalars")
     radius = (5.2 if kind == "tree" else 2.6) * float(sc[6])
     assert SEP > (1e3 if kind == "tree" else 20.0) * radius and eng.get_structure(0, "oct").size > 0
-    ways = exits(p, sc, n, radius)
+    ways = traverseref.exits(p, sc, n, radius)[0]
     print(kind, "cell", sc[6], "dims", sc[:3], {w: ways.count(w) for w in set(ways)})
     assert ways.count(kind) > 0.5 * n
     want = issref.iss(p, radius, 0.5 * radius, 0.975, 0.975, 3)

@@ -10,6 +10,7 @@ import pytest
 import mvicp
 import outlierref
 import pathcases
+import traverseref
 from mvicp import synth
 
 pytestmark = pytest.mark.gpu
@@ -96,8 +97,13 @@ def test_lattice_ties_and_a_far_cluster(eng):
     assert len(p) == 293 and outlierref.tie_count(p, k) == 108        # exact ties at the k-th place
     assert (p[:, 0] > 2.9).sum() == 5 < k + 1                           # the far cluster cannot fill a list: its block grows across the grid
     eng.set_frames([p], [nr])
-    dims = eng.get_structure(0, "scalars")[:3]
+    sc = eng.get_structure(0, "scalars")
+    dims = sc[:3]
     assert dims.max() >= 8, dims
+    # the knn kernel stops at the k+1-th reference distance and walks no box tree: the far cluster cannot stop (tests/traverseref.py)
+    ways = traverseref.exits(p, sc, len(p), np.sqrt(outlierref.k_distances(p, k)[1]), tree=False)[0]
+    print("lattice", "cell", sc[6], "dims", dims, {w: ways.count(w) for w in set(ways)}, "the far five:", ways[288:])
+    assert all(w in ("cloud", "grid") for w in ways[288:]) and ways[:288].count("stop") > 200
     for std_ratio, radius in ((2.0, 0.0), (-1.0, 0.0076), (1.0, 0.0076)):
         want = outlierref.outlier_filter(p, nr, k, std_ratio, radius)
         assert 0 < want["stats"]["kept"] < len(p) and not (want["idx"] >= 288).any()
@@ -127,11 +133,19 @@ def test_points_on_a_line(eng):
     p = np.outer(t, [1.0, 0.0, 0.0]) + [0.5, -0.25, 3.0]
     p = p[rng.permutation(len(p))]
     eng.set_frames([p], None)
-    dims = eng.get_structure(0, "scalars")[:3]
+    sc = eng.get_structure(0, "scalars")
+    dims = sc[:3]
     assert sorted(dims.tolist())[:2] == [2.0, 2.0] and dims.max() > 8, dims
     for k in (4, 16):
         want = outlierref.outlier_filter(p, None, k, 1.0, 0.0)
         assert 0 < want["stats"]["kept"] < len(p)
+        # a face of the block at or beyond the grid's boundary does not enter the stop rule: points stop whose k+1-th distance exceeds
+        # the distance to such a face's plane, which the rule over all six faces would have sent on to a larger block
+        d = np.sqrt(want["kd2"])
+        ways, radii, left_out = traverseref.exits(p, sc, len(p), d, tree=False)
+        sooner = int(((np.array(ways) == "stop") & (d > left_out + 0.01 * sc[6])).sum())
+        print("line", "k", k, "cell", sc[6], "dims", dims, {w: ways.count(w) for w in set(ways)}, "stop with a boundary face nearer than the k+1-th distance:", sooner)
+        assert ways.count("stop") > 0.9 * len(p) and (sooner >= 1 or k == 4)
         assert_same(eng.outlier_filter(0, k, 1.0, 0.0), want, ("line", k))
 
 
