@@ -902,7 +902,8 @@ int mvicp_closedform_point_to_plane(const double* src, const double* dst, const 
  * two queued evaluations go as ONE paired launch that reads the operand stream once (see mvicp_linearize_pair; 0: two launches with a copy between them); "lin_share_p"
  * (0/1, default 1): the linearization reads the source points of an all-accepted edge from the shared sorted cloud; "lin_interleave" (0/1, default 1; read at
  * mvicp_set_graph): the linearization's workgroups of the edges that share a source cloud are launched interleaved in groups of 8, so that the second reader of a
- * piece of the cloud runs on the XCD whose L2 still holds it; "nn_cell"
+ * piece of the cloud runs on the XCD whose L2 still holds it; "lin_tail_last" (0/1, default 1; read at mvicp_set_graph): every edge's full chunks are launched before
+ * all partial last chunks, so that the workgroups that start last, and run almost alone, are the short ones; "nn_cell"
  * (0/1, default 0): wave-cooperative cell-staging variant of the grid kernel; "tile_bounds" (default 1): the MVICP_NN_AUTO round
  * that hands over from the tile kernel to the grid kernel runs a build of the tile kernel that also leaves the temporal-cache
  * bounds (2: every tile round does, 0: off), "tile_mu" (default 0.02): its guard band in hash-cell edges; "tile_cache" (0/1, default 1):

@@ -17,6 +17,7 @@
 #include "common.h"
 #include "comm.h"
 #include "nn_tie.h"
+#include "lin_table.h"
 #include "../host/se3.h"
 
 namespace mvicp {
@@ -169,7 +170,7 @@ void free_graph(mvicp_ctx* c) {
   if (c->d_export) (void)hipFree(c->d_export);
   if (c->h_export) (void)hipHostFree(c->h_export);
   c->d_export = nullptr; c->h_export = nullptr; c->export_cap = 0;
-  c->E = 0; c->total_cap = 0; c->n_cblocks = 0; c->n_chunks = 0; c->hist.have_corr = false;
+  c->E = 0; c->total_cap = 0; c->n_cblocks = 0; c->n_chunks = 0; c->n_lin_wg = 0; c->hist.have_corr = false;
 }
 
 int bind(mvicp_ctx* c) {
@@ -1568,30 +1569,17 @@ int mvicp_set_graph(mvicp_ctx* c, int n_edges, const int* src, const int* dst) t
     c->cblock_off[e + 1] = c->cblock_off[e] + (int)((n + kCompactBlock - 1) / kCompactBlock);
     const int nch = (int)((n + kLinChunk - 1) / kLinChunk);
     c->chunk_first[e + 1] = c->chunk_first[e] + nch;
-    for (int k = 0; k < nch; ++k) { chunk_edge.push_back(e); chunk_start.push_back(k * kLinChunk); }
   }
   c->total_cap = c->cap_off[E];
   c->n_cblocks = c->cblock_off[E];
   c->n_chunks = c->chunk_first[E];
-  if (c->lin_interleave) {
-    // Launch order of the linearize workgroups (option "lin_interleave"): the edges of one source cloud read the same p (identity lists, lin_share_p).  Their
-    // chunks are interleaved in groups of 8 — A0..A7, B0..B7, A8..A15, ... — so that chunk k of the second edge runs on the XCD (workgroup b runs on XCD b % 8)
-    // that chunk k of the first edge ran on a moment ago: its piece of p is still in that XCD's L2.  Slots of the partials are per edge (linearize.hip).
-    std::vector<int> ce, cs;
-    for (int e0 = 0; e0 < E;) {
-      int e1 = e0 + 1;
-      while (e1 < E && src[e1] == src[e0]) ++e1;
-      int maxc = 0;
-      for (int e = e0; e < e1; ++e) maxc = std::max(maxc, c->chunk_first[e + 1] - c->chunk_first[e]);
-      for (int g = 0; g < maxc; g += 8)
-        for (int e = e0; e < e1; ++e) {
-          const int nch = c->chunk_first[e + 1] - c->chunk_first[e];
-          for (int k = g; k < std::min(g + 8, nch); ++k) { ce.push_back(e); cs.push_back(k * kLinChunk); }
-        }
-      e0 = e1;
-    }
-    chunk_edge.swap(ce); chunk_start.swap(cs);
+  {
+    // the launch order of the linearize workgroups (lin_table.h: options "lin_interleave", "lin_tail_last"); slots of the partials are per edge (linearize.hip)
+    std::vector<long long> ns(E);
+    for (int e = 0; e < E; ++e) ns[e] = c->owned[e] ? c->frames[src[e]].n : 0;
+    lin_launch_table(E, src, ns.data(), kLinChunk, c->lin_interleave, c->lin_tail_last, chunk_edge, chunk_start);
   }
+  c->n_lin_wg = (int)chunk_edge.size();   // workgroups of a launch: the n_chunks chunks + the table's pads
   const size_t cap = (size_t)c->total_cap;
   MV_CHECK(dev_alloc(&c->d_esrc, E)); MV_CHECK(dev_alloc(&c->d_edst, E)); MV_CHECK(dev_alloc(&c->d_cap_off, E + 1));
   MV_CHECK(dev_alloc(&c->d_count, E));
@@ -1644,7 +1632,7 @@ int mvicp_set_graph(mvicp_ctx* c, int n_edges, const int* src, const int* dst) t
     MV_CHECK(ensure_tie_trees(c, need));
   }
   MV_CHECK(dev_alloc(&c->d_median, E));
-  MV_CHECK(dev_alloc(&c->d_chunk_edge, (size_t)c->n_chunks)); MV_CHECK(dev_alloc(&c->d_chunk_start, (size_t)c->n_chunks));
+  MV_CHECK(dev_alloc(&c->d_chunk_edge, (size_t)c->n_lin_wg)); MV_CHECK(dev_alloc(&c->d_chunk_start, (size_t)c->n_lin_wg));
   MV_CHECK(dev_alloc(&c->d_chunk_first, E + 1));
   MV_CHECK(dev_alloc(&c->d_partials, 2 * (size_t)c->n_chunks * kLinPartial));   // (second half: the second pose set of a paired launch)
   MV_CHECK(dev_alloc(&c->d_out, (size_t)E * (MVICP_EDGE_BLOCK + 3) + 2));   // blocks | (count, median d2) x E | armed | a x E  (see common.h)
@@ -1657,9 +1645,9 @@ int mvicp_set_graph(mvicp_ctx* c, int n_edges, const int* src, const int* dst) t
   MV_HIP(hipMemcpy(c->d_cap_off, c->cap_off.data(), sizeof(long long) * (E + 1), hipMemcpyHostToDevice));
   MV_HIP(hipMemcpy(c->d_cblock_off, c->cblock_off.data(), sizeof(int) * (E + 1), hipMemcpyHostToDevice));
   MV_HIP(hipMemcpy(c->d_chunk_first, c->chunk_first.data(), sizeof(int) * (E + 1), hipMemcpyHostToDevice));
-  if (c->n_chunks) {
-    MV_HIP(hipMemcpy(c->d_chunk_edge, chunk_edge.data(), sizeof(int) * c->n_chunks, hipMemcpyHostToDevice));
-    MV_HIP(hipMemcpy(c->d_chunk_start, chunk_start.data(), sizeof(int) * c->n_chunks, hipMemcpyHostToDevice));
+  if (c->n_lin_wg) {
+    MV_HIP(hipMemcpy(c->d_chunk_edge, chunk_edge.data(), sizeof(int) * c->n_lin_wg, hipMemcpyHostToDevice));
+    MV_HIP(hipMemcpy(c->d_chunk_start, chunk_start.data(), sizeof(int) * c->n_lin_wg, hipMemcpyHostToDevice));
   }
   // pinned, device-mapped staging: control-block mirror | blocks | results | misc
   c->pin_blocks_off = c->ctl_r2_off + c->ctl_r2;
@@ -2188,6 +2176,7 @@ int mvicp_set_option(mvicp_ctx* c, const char* name, double value) try {
   if (std::strcmp(name, "nn_cache") == 0) { c->opt.nn_cache_enable = value != 0.0; c->hist.nn_cache_valid = false; return MVICP_OK; }
   if (std::strcmp(name, "lin_chunk") == 0) { c->lin_chunk_override = (int)value; return MVICP_OK; }  // takes effect at the next mvicp_set_graph
   if (std::strcmp(name, "list_reuse") == 0) { c->opt.list_reuse = value != 0.0; return MVICP_OK; }
+  if (std::strcmp(name, "lin_tail_last") == 0) { c->lin_tail_last = value != 0.0; return MVICP_OK; }   // takes effect at the next mvicp_set_graph
   if (std::strcmp(name, "lin_interleave") == 0) { c->lin_interleave = value != 0.0; return MVICP_OK; }   // takes effect at the next mvicp_set_graph
   if (std::strcmp(name, "lin_share_p") == 0) { c->lin_share_p = value != 0.0; return MVICP_OK; }
   if (std::strcmp(name, "lin_pair") == 0) { c->opt.lin_pair = value != 0.0; return MVICP_OK; }   // 0: the two queued evaluations of a fixed-point round as two launches

@@ -316,10 +316,12 @@ struct mvicp_ctx {
   double* d_sel_keys1 = nullptr;     // compact key buffer of the bracket pass (total_cap)
   // linearize chunks
   bool lin_interleave = true;       // launch order of the linearize workgroups: chunks of the edges that share a source cloud interleaved in groups of 8 (api.cpp mvicp_set_graph)
+  bool lin_tail_last = true;        // ... and every edge's partial last chunk behind all full chunks: the workgroups that start last are the short ones (api.cpp mvicp_set_graph)
   bool lin_share_p = true;          // linearize reads p from the sorted source cloud when an edge's list is the identity (option "lin_share_p")
   int lin_chunk_override = 0;
   int lin_chunk = 4096;             // correspondences per linearize workgroup (chosen from the GLOBAL problem size)
-  int n_chunks = 0;
+  int n_chunks = 0;                 // chunks = slots of the partials
+  int n_lin_wg = 0;                 // entries of the launch table = workgroups of a launch (>= n_chunks: the table may hold pads)
   std::vector<int> chunk_first;     // E+1
   int* d_chunk_edge = nullptr; int* d_chunk_start = nullptr; int* d_chunk_first = nullptr;
   double* d_partials = nullptr;     // 2 x n_chunks x kLinPartial (second half: the second pose set of a paired launch)

@@ -247,7 +247,7 @@ int launch_linearize(mvicp_ctx* c, int plane, int robust) {
     MV_CHECK(source_table(c, &d_src));
     ProfScope ps(c, "linearize", bytes);
 #define LAUNCH(P, R)                                                                                                                           \
-  hipLaunchKernelGGL((linearize_kernel<P, R, 1>), dim3(c->n_chunks), dim3(NT), 0, c->stream, c->d_chunk_edge, c->d_chunk_start, chunk, c->d_count, \
+  hipLaunchKernelGGL((linearize_kernel<P, R, 1>), dim3(c->n_lin_wg), dim3(NT), 0, c->stream, c->d_chunk_edge, c->d_chunk_start, chunk, c->d_count, \
                      c->d_cap_off, c->total_cap, c->d_rel, c->d_a, c->d_stream, c->d_partials, d_src, (const int*)c->d_nsrc, (const int*)c->d_chunk_first, PairArgs<1>{})
     if (plane && robust) LAUNCH(true, true);
     else if (plane) LAUNCH(true, false);
@@ -279,7 +279,7 @@ int launch_linearize_pair(mvicp_ctx* c, int plane, int robust, double* out_a, do
     MV_CHECK(source_table(c, &d_src));
     ProfScope ps(c, "linearize_pair", bytes);
 #define LAUNCH(P, R)                                                                                                                              \
-  hipLaunchKernelGGL((linearize_kernel<P, R, 2>), dim3(c->n_chunks), dim3(NT), 0, c->stream, c->d_chunk_edge, c->d_chunk_start, chunk, c->d_count, \
+  hipLaunchKernelGGL((linearize_kernel<P, R, 2>), dim3(c->n_lin_wg), dim3(NT), 0, c->stream, c->d_chunk_edge, c->d_chunk_start, chunk, c->d_count, \
                      c->d_cap_off, c->total_cap, c->d_rel, c->d_a, c->d_stream, c->d_partials, d_src, (const int*)c->d_nsrc, (const int*)c->d_chunk_first, x)
     if (plane && robust) LAUNCH(true, true);
     else if (plane) LAUNCH(true, false);

@@ -153,7 +153,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2))) void li
 int launch_linearize_gicp(mvicp_ctx* c, double eps, int robust) {
   return launch_linearize_normal(c, robust, "linearize_gicp", "gicp", [&](bool rob, int chunk, const double* d_lo, const double* const* d_src, const double* const* d_nor) {
     auto go = [&](auto kernel) {
-      hipLaunchKernelGGL(kernel, dim3(c->n_chunks), dim3(NT), 0, c->stream, c->d_chunk_edge, c->d_chunk_start, chunk, c->d_count, c->d_cap_off, c->total_cap, c->d_rel, d_lo,
+      hipLaunchKernelGGL(kernel, dim3(c->n_lin_wg), dim3(NT), 0, c->stream, c->d_chunk_edge, c->d_chunk_start, chunk, c->d_count, c->d_cap_off, c->total_cap, c->d_rel, d_lo,
                          c->d_a, c->d_stream, c->d_partials, d_src, d_nor, (const int*)c->d_first, (const int*)c->d_nsrc, (const int*)c->d_chunk_first, eps);
     };
     if (rob) go(linearize_gicp_kernel<true>);

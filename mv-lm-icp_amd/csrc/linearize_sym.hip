@@ -97,7 +97,7 @@ __global__ __launch_bounds__(NT) void linearize_sym_kernel(const int* __restrict
 int launch_linearize_sym(mvicp_ctx* c, int robust) {
   return launch_linearize_normal(c, robust, "linearize_sym", "symmetric", [&](bool rob, int chunk, const double* d_lo, const double* const* d_src, const double* const* d_nor) {
     auto go = [&](auto kernel) {
-      hipLaunchKernelGGL(kernel, dim3(c->n_chunks), dim3(NT), 0, c->stream, c->d_chunk_edge, c->d_chunk_start, chunk, c->d_count, c->d_cap_off, c->total_cap, c->d_rel, d_lo,
+      hipLaunchKernelGGL(kernel, dim3(c->n_lin_wg), dim3(NT), 0, c->stream, c->d_chunk_edge, c->d_chunk_start, chunk, c->d_count, c->d_cap_off, c->total_cap, c->d_rel, d_lo,
                          c->d_a, c->d_stream, c->d_partials, d_src, d_nor, (const int*)c->d_first, (const int*)c->d_nsrc, (const int*)c->d_chunk_first);
     };
     if (rob) go(linearize_sym_kernel<true>);
