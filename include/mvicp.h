@@ -230,6 +230,66 @@ int mvicp_outlier_fetch(mvicp_ctx* ctx, long long cap_kept, double* xyz, double*
  * Errors: n < 2, NULL T, a non-finite std_ratio, n S2 >= 2^128 or S1^2 > n S2 -> MVICP_ERR_ARG. */
 int mvicp_outlier_threshold(long long n, unsigned long long s1, unsigned long long s2_hi, unsigned long long s2_lo, double std_ratio, double* T);
 
+/* ---- clusters: DBSCAN / Euclidean cluster extraction over one stored cloud; drop small clusters -------------------------
+ * Answers "which points belong together", which the two outlier rules cannot: they judge the density of a k-neighbourhood and keep a compact
+ * clump of stray points (a clamp, a hand, a piece of the turntable).  The result is a pure function of the stored cloud p_0 .. p_{n-1} of
+ * `frame` (the stored bytes, no pose), bit for bit, whatever order the GPU's threads run in (tests/clusterref.py is the same definition in
+ * numpy and as a scalar loop); only comparisons and integers enter:
+ *   Adjacency  j in N(i) iff sqrt(dist2(p_i, p_j)) < radius (IEEE sqrt, strict) -- the predicate of mvicp_knn_search and
+ *              mvicp_outlier_filter; equivalently dist2 < B2, B2 as defined at mvicp_overlap; dist2 = (d0 d0 + d1 d1) + d2 d2, every
+ *              operation rounded on its own, no fma (csrc/nn_metric.h).  i in N(i) (d2 = +0).  dist2 is BITWISE SYMMETRIC in its arguments
+ *              (the two differences are exact negatives of each other and the squares drop the sign), so the graph is undirected.
+ *   Core       i is a core point iff |N(i)| >= min_pts; the point itself counts (as in sklearn and Open3D).  Only the comparison enters; no
+ *              per-point count is output.
+ *   Cluster    a connected component of the graph on the CORE points whose edges are {i, j}, both core, j in N(i).
+ *   Border     a non-core i with at least one core point in N(i) joins the cluster of THE core point of N(i) that comes first in the order
+ *              (dist2 ascending, original index ascending) -- the order of mvicp_knn_search; a minimum over a strict total order, so it
+ *              does not depend on any visiting order.  A border point never links two clusters.
+ *   Noise      every other point: label -1.
+ *   Labels     the clusters are numbered 0 .. C-1 in ascending order of their smallest CORE original index (on core points this is sklearn's
+ *              numbering).
+ *   Output     label (n int32), core (n bytes, 1 = core), size (C int32, border members included), and the stats below; largest_label is the
+ *              lowest label among the clusters of the largest size (-1 when C = 0).
+ *   Limits     n = 0 gives zero clusters and is no error.  min_pts = 1 is plain Euclidean cluster extraction: every point is core, no noise.
+ * Needs a finite radius > 0 and 1 <= min_pts <= 2^30; needs the frame's hash structure (waits for pending builds and reports a failed one,
+ * like mvicp_overlap), NO graph, and is HISTORY-NEUTRAL: it does not modify the frame and leaves caches, seeds, lists, epochs, medians, the AUTO
+ * state and queued evaluations alone, so a registration with cluster calls in between is bit-identical to one without.  With several ranks
+ * every rank computes it locally.  The call returns when the result is complete; the result lives in library-owned device memory until the
+ * next mvicp_cluster, an upload to `frame`, mvicp_set_num_frames or mvicp_destroy.  Profile scopes: "cluster_core", "cluster_union",
+ * "cluster_border", "cluster_label", "cluster_compact".
+ * RETURNS THE NUMBER OF CLUSTERS C (>= 0) or a negative mvicp_status; stats may be NULL.
+ * Errors: NULL context, min_pts outside [1, 2^30], a radius that is not finite or <= 0, a frame index out of range -> MVICP_ERR_ARG, decided
+ * before the context is touched: the previous result stays; a frame never uploaded -> MVICP_ERR_STATE; a neighbour distance that can
+ * overflow -- with a = the largest |coordinate| of the cloud and t = a + a, (t t + t t) + t t = +inf, a bound on every dist2 of the cloud
+ * -- -> MVICP_ERR_ARG, reported by this call, and no result is left behind. */
+typedef struct mvicp_cluster_stats {
+  long long n, clusters, core, border, noise;   /* core + border + noise = n */
+  long long largest;                            /* size of the largest cluster (0 when there is none) */
+  int largest_label;
+  int has_normals;                              /* the frame has normals: mvicp_cluster_fetch_kept gives nrm */
+} mvicp_cluster_stats;
+long long mvicp_cluster(mvicp_ctx* ctx, int frame, double radius, int min_pts, mvicp_cluster_stats* stats);
+/* Copies the last result: label (n ints), core (n bytes), size (C ints); each may be NULL; each may be a HOST pointer or a DEVICE pointer of
+ * the context's device, decided per pointer as mvicp_voxel_fetch decides.  cap_n = entries label / core hold, cap_clusters = entries size holds
+ * (each looked at only when one of its arrays is given).
+ * Errors: NULL context, cap_n < n, cap_clusters < C -> MVICP_ERR_ARG; no mvicp_cluster before -> MVICP_ERR_STATE. */
+int mvicp_cluster_fetch(mvicp_ctx* ctx, long long cap_n, int* label, unsigned char* core, long long cap_clusters, int* size);
+/* Which clusters stay (pure host function, no context): the clusters are ranked by (size descending, label ascending), rank 0 first, and
+ *   keep[c] = size[c] >= min_size && (max_clusters == 0 || rank(c) < max_clusters)     (1 / 0; n_clusters bytes)
+ * Errors: a negative n_clusters, min_size or max_clusters, NULL size or keep -> MVICP_ERR_ARG. */
+int mvicp_cluster_keep_rule(long long n_clusters, const int* size, long long min_size, long long max_clusters, unsigned char* keep);
+/* Applies mvicp_cluster_keep_rule to the last mvicp_cluster result: the points with label >= 0 whose cluster is kept, in ascending original
+ * index (noise always goes), compacted on the device.  The rows are the frame's stored bytes at the time of this call.  May be called again
+ * with another rule; the selection lives as long as the mvicp_cluster result.  RETURNS THE NUMBER OF ROWS KEPT or a negative mvicp_status.
+ * Errors: NULL context, min_size < 0, max_clusters < 0 -> MVICP_ERR_ARG; no mvicp_cluster result -> MVICP_ERR_STATE. */
+long long mvicp_cluster_select(mvicp_ctx* ctx, long long min_size, long long max_clusters);
+/* Copies the last selection: xyz / nrm (kept x 3 doubles: the stored bytes; nrm iff the frame has normals), idx (kept ints: original
+ * indices, ascending), label (kept ints); each may be NULL; each may be a HOST pointer or a DEVICE pointer of the context's device, decided
+ * per pointer as mvicp_voxel_fetch decides, so a device result goes straight into mvicp_set_frame_device.  cap = rows each destination holds.
+ * Errors: NULL context, cap < kept -> MVICP_ERR_ARG; no mvicp_cluster result, no mvicp_cluster_select of it, or nrm != NULL for a frame
+ * without normals -> MVICP_ERR_STATE. */
+int mvicp_cluster_fetch_kept(mvicp_ctx* ctx, long long cap, double* xyz, double* nrm, int* idx, int* label);
+
 /* ---- neighbour search: the k nearest and / or all points within a radius, for arbitrary queries, with indices ------------
  * The search primitive of every point-cloud toolkit (search_knn, search_radius, the hybrid of the two) over one stored cloud.  The result
  * is a pure function of the inputs, bit for bit (tests/knnref.py is the same definition in numpy):

@@ -546,7 +546,7 @@ int mvicp_create(int device, mvicp_ctx** out) try {
 static void release_stages(mvicp_ctx* c) {
   c->vox.release(); c->out.release(); c->knn.release(); c->fpfh.release();
   c->match.release(); c->cons.release(); c->coarse.release(); c->iss.release(); c->nrm.release();
-  c->ori.release(); c->agree.release();
+  c->ori.release(); c->agree.release(); c->clu.release();
 }
 
 int mvicp_destroy(mvicp_ctx* c) try {
@@ -606,6 +606,7 @@ int mvicp_set_frame(mvicp_ctx* c, int frame, const double* xyz, const double* nr
   FrameDev& f = c->frames[frame];
   if (c->nrm.frame == frame) c->nrm.drop_result();   // (estimated normals of the cloud this call replaces: nothing to adopt them into)
   if (c->ori.frame == frame) c->ori.drop_result();   // (and its oriented normals)
+  if (c->clu.frame == frame) c->clu.drop_result();   // (and its clusters: a selection would read the new rows)
   if (f.job) { try { (void)f.job->fut.get(); } catch (...) {} f.job.reset(); }   // a build of the cloud this call replaces
   dev_free(f.pts); dev_free(f.nor); free_grid(f.grid); free_tie(f);
   f.has_grid = false; f.build_error.clear();
@@ -686,6 +687,7 @@ int mvicp_set_frame_device(mvicp_ctx* c, int frame, const double* d_xyz, const d
   FrameDev& f = c->frames[frame];
   if (c->nrm.frame == frame) c->nrm.drop_result();   // (estimated normals of the cloud this call replaces: nothing to adopt them into)
   if (c->ori.frame == frame) c->ori.drop_result();   // (and its oriented normals)
+  if (c->clu.frame == frame) c->clu.drop_result();   // (and its clusters: a selection would read the new rows)
   if (f.job) { try { (void)f.job->fut.get(); } catch (...) {} f.job.reset(); }   // a build of the cloud this call replaces
   dev_free(f.pts); dev_free(f.nor); free_grid(f.grid); free_tie(f);
   f.has_grid = false; f.build_error.clear();
@@ -981,6 +983,58 @@ int mvicp_outlier_fetch(mvicp_ctx* c, long long cap_kept, double* xyz, double* n
   const size_t m = (size_t)c->out.kept, n = (size_t)c->out.n;
   const FetchPart parts[] = {{xyz, c->out.xyz, 24 * m, "xyz"}, {nrm, c->out.nrm, 24 * m, "nrm"}, {idx, c->out.idx, 4 * m, "idx"},
                              {mdist, c->out.mdist, 8 * n, "mdist"}, {kd2, c->out.kd2, 8 * n, "kd2"}};
+  return fetch_parts(c, parts);
+} MVICP_GUARD_ABI
+
+long long mvicp_cluster(mvicp_ctx* c, int frame, double radius, int min_pts, mvicp_cluster_stats* stats) try {
+  // every argument error that needs no GPU first: nothing of the context has been touched when one of them is reported
+  if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
+  if (min_pts < 1 || min_pts > (1 << 30)) { set_error("min_pts = %d outside [1, 2^30]", min_pts); return MVICP_ERR_ARG; }
+  if (!std::isfinite(radius) || !(radius > 0.0)) { set_error("radius must be finite and > 0"); return MVICP_ERR_ARG; }
+  if (frame < 0 || frame >= c->n_frames) { set_error("frame %d out of range [0,%d)", frame, c->n_frames); return MVICP_ERR_ARG; }
+  if (!c->frames[frame].pts) { set_error("frame %d was never uploaded", frame); return MVICP_ERR_STATE; }
+  MV_CHECK(bind(c));
+  MV_CHECK(finish_builds(c));
+  const long long clusters = cluster_points(c, c->frames[frame], frame, sqrt_bound(radius), min_pts, stats);
+  if (c->profile) prof_collect_lazy(c);
+  return clusters;
+} MVICP_GUARD_ABI
+
+int mvicp_cluster_fetch(mvicp_ctx* c, long long cap_n, int* label, unsigned char* core, long long cap_clusters, int* size) try {
+  if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
+  if (c->clu.n < 0) { set_error("no cluster result: call mvicp_cluster first"); return MVICP_ERR_STATE; }
+  if ((label || core) && cap_n < c->clu.n) { set_error("cap_n %lld < %lld points", cap_n, c->clu.n); return MVICP_ERR_ARG; }
+  if (size && cap_clusters < c->clu.clusters) { set_error("cap_clusters %lld < %lld clusters", cap_clusters, c->clu.clusters); return MVICP_ERR_ARG; }
+  if (c->clu.n == 0) return MVICP_OK;
+  const size_t n = (size_t)c->clu.n, k = (size_t)c->clu.clusters;
+  const FetchPart parts[] = {{label, c->clu.label, 4 * n, "label"}, {core, c->clu.core, n, "core"}, {size, c->clu.size, 4 * k, "size"}};
+  return fetch_parts(c, parts);
+} MVICP_GUARD_ABI
+
+long long mvicp_cluster_select(mvicp_ctx* c, long long min_size, long long max_clusters) try {
+  if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
+  if (min_size < 0 || max_clusters < 0) { set_error("min_size and max_clusters must be >= 0"); return MVICP_ERR_ARG; }
+  if (c->clu.n < 0) { set_error("no cluster result: call mvicp_cluster first"); return MVICP_ERR_STATE; }
+  const int frame = c->clu.frame;
+  if (frame < 0 || frame >= c->n_frames || c->frames[frame].n != c->clu.n || (c->clu.n > 0 && !c->frames[frame].pts)) {
+    set_error("the clustered frame is gone: call mvicp_cluster again");
+    return MVICP_ERR_STATE;
+  }
+  MV_CHECK(bind(c));
+  const long long kept = cluster_select(c, c->frames[frame], min_size, max_clusters);
+  if (c->profile) prof_collect_lazy(c);
+  return kept;
+} MVICP_GUARD_ABI
+
+int mvicp_cluster_fetch_kept(mvicp_ctx* c, long long cap, double* xyz, double* nrm, int* idx, int* label) try {
+  if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
+  if (c->clu.n < 0) { set_error("no cluster result: call mvicp_cluster first"); return MVICP_ERR_STATE; }
+  if (c->clu.kept < 0) { set_error("no selection: call mvicp_cluster_select first"); return MVICP_ERR_STATE; }
+  if (cap < c->clu.kept) { set_error("cap %lld < %lld kept rows", cap, c->clu.kept); return MVICP_ERR_ARG; }
+  if (nrm && !c->clu.has_normals) { set_error("the clustered frame has no normals"); return MVICP_ERR_STATE; }
+  if (c->clu.kept == 0) return MVICP_OK;
+  const size_t m = (size_t)c->clu.kept;
+  const FetchPart parts[] = {{xyz, c->clu.xyz, 24 * m, "xyz"}, {nrm, c->clu.nrm, 24 * m, "nrm"}, {idx, c->clu.idx, 4 * m, "idx"}, {label, c->clu.klabel, 4 * m, "label"}};
   return fetch_parts(c, parts);
 } MVICP_GUARD_ABI
 
@@ -1460,6 +1514,20 @@ int mvicp_poses_from_pairs(int n_frames, int n_edges, const int* src, const int*
     if (component) component[i] = comp[i];
   }
   return components;
+} MVICP_GUARD_ABI
+
+int mvicp_cluster_keep_rule(long long n_clusters, const int* size, long long min_size, long long max_clusters, unsigned char* keep) try {
+  if (n_clusters < 0 || min_size < 0 || max_clusters < 0) { set_error("cluster keep rule: negative argument"); return MVICP_ERR_ARG; }
+  if (!size || !keep) { set_error("cluster keep rule: needs size and keep"); return MVICP_ERR_ARG; }
+  std::vector<long long> order((size_t)n_clusters);
+  for (long long k = 0; k < n_clusters; ++k) order[(size_t)k] = k;
+  // rank by (size descending, label ascending): a stable sort of the labels by size
+  std::stable_sort(order.begin(), order.end(), [&](long long a, long long b) { return size[a] > size[b]; });
+  for (long long r = 0; r < n_clusters; ++r) {
+    const long long k = order[(size_t)r];
+    keep[k] = (size[k] >= min_size && (max_clusters == 0 || r < max_clusters)) ? 1 : 0;
+  }
+  return MVICP_OK;
 } MVICP_GUARD_ABI
 
 int mvicp_outlier_threshold(long long n, unsigned long long s1, unsigned long long s2_hi, unsigned long long s2_lo, double std_ratio, double* T) try {

@@ -115,7 +115,7 @@ struct ProfEntry {
 
 // ---- buffers and results a stage of the library owns ---------------------------------------------------------------------------------
 // A stage (voxel grid, outlier filter, neighbour search, FPFH, descriptor matching, consensus, batched coarse poses, ISS keypoints, estimated
-// normals, oriented normals) keeps its LAST result on the context until the caller has fetched it.  Ownership, stated once for all ten: the stage's struct below holds
+// normals, oriented normals, clusters) keeps its LAST result on the context until the caller has fetched it.  Ownership, stated once for all eleven: the stage's struct below holds
 // buffers of its own (so that a call touches nothing a search, a queued evaluation, the census or another stage uses), kept between
 // calls and grown on demand, the result arrays as views into them, and the sizes / flags, whose defaults mean "no result".  A call marks
 // its result as gone when it starts (a failed call leaves none behind) and sets it after its last wait; the result then lives until the
@@ -239,6 +239,19 @@ struct OrientStage {
   long long rows = -1, comps = 0; int frame = -1;   // rows < 0: none
   void drop_result() { rows = -1; comps = 0; frame = -1; }
   void release() { dev.release(); pin.release(); *this = OrientStage(); }
+};
+// cluster.hip.  dev: one arena [control | core | parent | root | flag | rank | label | size | keep | xyz | nrm | idx | klabel], tmp: rocprim storage,
+// pin: the host copy of [control | size, later the keep bytes]; h_size: the cluster sizes for the select rule.  frame: the slot the result was
+// computed for (mvicp_cluster_select reads its stored rows); an upload to that slot drops the result.  kept: the rows of the last
+// mvicp_cluster_select of this result (< 0: none)
+struct ClusterStage {
+  DevBuf dev, tmp; PinBuf pin;
+  int* label = nullptr; unsigned char* core = nullptr; int* size = nullptr;
+  double* xyz = nullptr; double* nrm = nullptr; int* idx = nullptr; int* klabel = nullptr;
+  std::vector<int> h_size;
+  long long n = -1, clusters = -1, kept = -1; int frame = -1, has_normals = 0;   // n < 0: none
+  void drop_result() { n = -1; clusters = -1; kept = -1; frame = -1; has_normals = 0; h_size.clear(); }
+  void release() { dev.release(); tmp.release(); pin.release(); *this = ClusterStage(); }
 };
 // orient.hip (mvicp_normal_agreement).  dev: [poses | per-edge pointer tables | per-edge counts | pos | neg], pin: the host copy of pos | neg
 struct AgreementStage {
@@ -381,6 +394,7 @@ struct mvicp_ctx {
   mvicp::NormalsStage nrm;
   mvicp::OrientStage ori;
   mvicp::AgreementStage agree;
+  mvicp::ClusterStage clu;
   std::vector<char> src_fixed;     // E: the edge's source frame was fixed in the last mvicp_correspond (0 before the first): mvicp_normal_agreement skips it
 
   // cached small tables
@@ -462,6 +476,14 @@ long long voxel_reduce(mvicp_ctx* c, int n_sel, const int* sel, const double* po
 // (std_ratio >= 0) and the radius (radius > 0) rule; the result stays on the context (c->out).  Returns the number kept or a negative
 // status.  Waits for the stream; history-neutral.
 long long outlier_filter(mvicp_ctx* c, const FrameDev& f, int k, double std_ratio, double radius, mvicp_outlier_stats* stats);
+// cluster.hip: the clusters of frame f = c->frames[frame] (valid, uploaded, structures built) for B2 = sqrt_bound(radius) and 1 <= min_pts <= 2^30;
+// the result stays on the context (c->clu).  Returns the number of clusters or a negative status (coordinates whose distances can
+// overflow: MVICP_ERR_ARG, no result).  Waits for the stream once; history-neutral.
+long long cluster_points(mvicp_ctx* c, const FrameDev& f, int frame, double B2, int min_pts, mvicp_cluster_stats* stats);
+// cluster.hip: the rows of f (the frame of the last cluster_points, unchanged since: c->clu.n == f.n >= 0) whose cluster the rule
+// mvicp_cluster_keep_rule(min_size, max_clusters) keeps, compacted in ascending original index into c->clu.  Returns the rows kept or a
+// negative status.  Waits for the stream once; history-neutral.
+long long cluster_select(mvicp_ctx* c, const FrameDev& f, long long min_size, long long max_clusters);
 // knn.hip: the neighbourhoods of m queries (host or device memory, as `queries_on_device` says) or, queries == null, of the cloud's own
 // points, in frame f (valid, uploaded, structures built); 0 <= k <= 64, k == 0 needs radius > 0; B2 = sqrt_bound(radius) when radius > 0.
 // The result stays on the context (c->knn).  Returns the number of entries or a negative status.  Waits for the stream; history-neutral.

@@ -570,6 +570,35 @@ std::shared_ptr<Frame> Frame::removeOutliers(int k, double std_ratio, double rad
   return out;
 }
 
+std::shared_ptr<Frame> Frame::removeSmallClusters(double radius, int min_pts, long long min_size, long long max_clusters, long long* clusters,
+                                                  long long* kept_clusters) {
+  std::shared_ptr<Frame> out(new Frame());
+  out->fixed = fixed; out->pose = pose; out->poseGroundTruth = poseGroundTruth;
+  for (const OutgoingEdge& e : neighbours) out->neighbours.push_back(OutgoingEdge{e.neighbourIdx, e.weight, {}});
+  if (clusters) *clusters = 0;
+  if (kept_clusters) *kept_clusters = 0;
+  if (pts.empty()) return out;
+  int slot = 0;
+  mvicp_ctx* c = Session::get().query_context(this, &slot, true);
+  mvicp_cluster_stats st;
+  const long long nc = mvicp_cluster(c, slot, radius, min_pts, &st);
+  if (nc < 0) check((int)nc);
+  const long long m = mvicp_cluster_select(c, min_size, max_clusters);
+  if (m < 0) check((int)m);
+  out->pts.assign((size_t)m, Vector3d());
+  out->nor.assign(st.has_normals && nor.size() == pts.size() ? (size_t)m : 0, Vector3d());
+  if (m) check(mvicp_cluster_fetch_kept(c, m, out->pts[0].data(), out->nor.empty() ? nullptr : out->nor[0].data(), nullptr, nullptr));
+  if (clusters) *clusters = nc;
+  if (kept_clusters && nc) {
+    std::vector<int> size((size_t)nc);
+    std::vector<unsigned char> keep((size_t)nc);
+    check(mvicp_cluster_fetch(c, 0, nullptr, nullptr, nc, size.data()));
+    check(mvicp_cluster_keep_rule(nc, size.data(), min_size, max_clusters, keep.data()));
+    for (unsigned char k : keep) *kept_clusters += k;
+  }
+  return out;
+}
+
 std::vector<int> Frame::issKeypoints(double salient_radius, double non_max_radius, double gamma21, double gamma32, int min_neighbors) {
   std::vector<int> idx;
   if (pts.empty()) return idx;

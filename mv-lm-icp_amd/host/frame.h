@@ -104,6 +104,14 @@ class Frame {
   // pose, poseGroundTruth, fixed and neighbours (index and weight; the correspondence lists start empty).  Runs in the context
   // Session::query_context finds for this frame (bin/multiview --sor_k / --sor_ratio / --ror_radius).
   std::shared_ptr<Frame> removeOutliers(int k, double std_ratio, double radius);
+  // A copy of this frame without its small clusters (no counterpart in the reference): mvicp_cluster on this cloud as it is stored -- DBSCAN
+  // with the strict radius predicate, the point itself counting towards min_pts -- and mvicp_cluster_select: the points of the clusters with
+  // at least min_size members, of those only the max_clusters largest (0: all of them); noise always goes.  The new Frame has the kept
+  // pts / nor in their original order and the same pose, poseGroundTruth, fixed and neighbours (index and weight; the correspondence
+  // lists start empty).  clusters / kept_clusters, if given, receive the number of clusters found and kept.  Runs in the context
+  // Session::query_context finds for this frame (bin/multiview --cluster_radius / --cluster_min_pts / --cluster_min_size / --cluster_keep).
+  std::shared_ptr<Frame> removeSmallClusters(double radius, int min_pts, long long min_size, long long max_clusters, long long* clusters = nullptr,
+                                             long long* kept_clusters = nullptr);
   // The ISS keypoints of this frame (no counterpart in the reference): mvicp_iss_keypoints on this cloud as it is stored -> the indices
   // of the keypoints, ascending.  Runs in the context Session::query_context finds for this frame (bin/multiview --feat_keypoints).
   std::vector<int> issKeypoints(double salient_radius, double non_max_radius, double gamma21 = 0.975, double gamma32 = 0.975, int min_neighbors = 5);

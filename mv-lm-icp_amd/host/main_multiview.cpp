@@ -28,6 +28,11 @@
 // coarse level, by Frame::removeOutliers(K, A, R): the statistical rule over the K nearest neighbours (A < 0, the default without --sor_ratio
 // when only a radius is given: off; --sor_ratio alone defaults to 2) and / or the radius rule (at least K neighbours within R; R <= 0: off).
 // One line per frame, `outlier filter: frame i kept a of b` (printed with --quiet too).
+// --cluster_radius R [--cluster_min_pts M] [--cluster_min_size S] [--cluster_keep N] (default R = 0 = off; M = 4, S = 0, N = 0 = all): with R > 0
+// every frame loses its small clusters after the outlier filter and before the normals step and any coarse level, by
+// Frame::removeSmallClusters(R, M, S, N): the clusters of mvicp_cluster (DBSCAN: a core point has M points, itself included, within R) with at
+// least S members, of those the N largest; noise always goes.  What the outlier rules keep -- a compact clump of stray points -- goes here.
+// One line per frame, `cluster filter: frame i kept a of b, c of d clusters` (printed with --quiet too).
 // --init features: the initial poses of frames 1 .. K-1 come from the clouds alone (Session::initFromFeatures, after loadFrames and before the
 // graph is built; frame 0 keeps its loaded pose): FPFH descriptors, one batched matching + consensus over all frame pairs, a spanning tree
 // over the inlier counts.  --feat_voxel H (0 = the full clouds; otherwise Frame::voxelDownsample(H) copies carry the features),
@@ -88,6 +93,14 @@ static void loadFrames(const Flags& F, std::vector<std::shared_ptr<Frame>>& fram
       std::shared_ptr<Frame> kept = f->removeOutliers(F.i("sor_k", 0), F.f("sor_ratio", radius > 0.0 ? -1.0 : 2.0), radius);
       f->pts.swap(kept->pts); f->nor.swap(kept->nor); ++f->version;   // (a context that holds the old cloud re-uploads)
       std::cout << "outlier filter: frame " << frames.size() << " kept " << f->pts.size() << " of " << before << std::endl;
+    }
+    if (F.f("cluster_radius", 0.0) > 0.0) {
+      const size_t before = f->pts.size();
+      long long found = 0, stay = 0;
+      std::shared_ptr<Frame> kept = f->removeSmallClusters(F.f("cluster_radius", 0.0), F.i("cluster_min_pts", 4), std::atoll(F.s("cluster_min_size", "0").c_str()),
+                                                           std::atoll(F.s("cluster_keep", "0").c_str()), &found, &stay);
+      f->pts.swap(kept->pts); f->nor.swap(kept->nor); ++f->version;   // (a context that holds the old cloud re-uploads)
+      std::cout << "cluster filter: frame " << frames.size() << " kept " << f->pts.size() << " of " << before << ", " << stay << " of " << found << " clusters" << std::endl;
     }
     if (F.i("normals_nn", 0) > 0 && F.i("normals_fit", 0)) f->fitNormals(F.i("normals_nn", 0), F.f("normals_radius", 0.0), F.i("normals_fit", 0));
     else if (F.i("normals_nn", 0) > 0) f->estimateNormals(F.i("normals_nn", 0), F.f("normals_radius", 0.0));   // (viewpoint: the view's own origin)

@@ -21,6 +21,7 @@ SYMBOLS = [
     "mvicp_closedform_point_to_point", "mvicp_closedform_point_to_plane", "mvicp_set_frame_device", "mvicp_get_structure",
     "mvicp_overlap", "mvicp_graph_from_overlap", "mvicp_voxel_grid", "mvicp_voxel_fetch",
     "mvicp_outlier_filter", "mvicp_outlier_fetch", "mvicp_outlier_threshold", "mvicp_cache_allowance",
+    "mvicp_cluster", "mvicp_cluster_fetch", "mvicp_cluster_keep_rule", "mvicp_cluster_select", "mvicp_cluster_fetch_kept",
     "mvicp_knn_search", "mvicp_knn_fetch", "mvicp_fpfh", "mvicp_fpfh_fetch", "mvicp_iss_keypoints", "mvicp_iss_fetch",
     "mvicp_estimate_normals", "mvicp_normals_fetch", "mvicp_normals_adopt", "mvicp_fit_normals", "mvicp_normals_fit_fetch",
     "mvicp_orient_normals", "mvicp_orient_fetch", "mvicp_orient_adopt", "mvicp_normal_agreement", "mvicp_signs_from_agreement", "mvicp_negate_normals",
@@ -53,6 +54,14 @@ class OutlierStats(C.Structure):
         d = {k: getattr(self, k) for k, _ in self._fields_}
         d["s2"] = (d["s2_hi"] << 64) | d["s2_lo"]
         return d
+
+
+class ClusterStats(C.Structure):
+    _fields_ = [("n", C.c_longlong), ("clusters", C.c_longlong), ("core", C.c_longlong), ("border", C.c_longlong), ("noise", C.c_longlong),
+                ("largest", C.c_longlong), ("largest_label", C.c_int), ("has_normals", C.c_int)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class ConsensusResult(C.Structure):
@@ -137,6 +146,13 @@ def load_library(path=None):
     lib.mvicp_outlier_filter.restype = C.c_longlong
     lib.mvicp_outlier_fetch.argtypes = [vp, C.c_longlong, vp, vp, vp, C.c_longlong, vp, vp]
     lib.mvicp_outlier_threshold.argtypes = [C.c_longlong, C.c_ulonglong, C.c_ulonglong, C.c_ulonglong, C.c_double, dp]
+    lib.mvicp_cluster.argtypes = [vp, C.c_int, C.c_double, C.c_int, C.POINTER(ClusterStats)]
+    lib.mvicp_cluster.restype = C.c_longlong
+    lib.mvicp_cluster_fetch.argtypes = [vp, C.c_longlong, vp, vp, C.c_longlong, vp]
+    lib.mvicp_cluster_keep_rule.argtypes = [C.c_longlong, vp, C.c_longlong, C.c_longlong, vp]
+    lib.mvicp_cluster_select.argtypes = [vp, C.c_longlong, C.c_longlong]
+    lib.mvicp_cluster_select.restype = C.c_longlong
+    lib.mvicp_cluster_fetch_kept.argtypes = [vp, C.c_longlong, vp, vp, vp, vp]
     lib.mvicp_cache_allowance.argtypes = [dp, dp, dp, dp, C.c_double, dp]
     lib.mvicp_knn_search.argtypes = [vp, C.c_int, vp, C.c_longlong, C.c_int, C.c_double]
     lib.mvicp_knn_search.restype = C.c_longlong
@@ -269,6 +285,18 @@ def outlier_threshold(n, s1, s2, std_ratio):
     T = C.c_double(0.0)
     _check(lib, lib.mvicp_outlier_threshold(int(n), s1, s2 >> 64, s2 & ((1 << 64) - 1), float(std_ratio), C.byref(T)))
     return T.value
+
+
+def cluster_keep_rule(size, min_size=0, max_clusters=0):
+    """mvicp_cluster_keep_rule: which clusters stay, from their sizes (index = label).  The clusters are ranked by (size descending, label
+    ascending); keep[c] = size[c] >= min_size and (max_clusters == 0 or rank(c) < max_clusters) -> (C,) uint8.  Host only."""
+    lib = load_library()
+    size = np.ascontiguousarray(size, dtype=np.int32).reshape(-1)
+    n = len(size)
+    src = np.concatenate([size, np.zeros(1, dtype=np.int32)])   # (never a NULL pointer for C = 0)
+    keep = np.zeros(n + 1, dtype=np.uint8)
+    _check(lib, lib.mvicp_cluster_keep_rule(n, src.ctypes.data_as(C.c_void_p), int(min_size), int(max_clusters), keep.ctypes.data_as(C.c_void_p)))
+    return keep[:n].copy()
 
 
 def cache_allowance(pose_src_old, pose_dst_old, pose_src, pose_dst, max_norm):
@@ -510,6 +538,7 @@ class Engine:
         self.n_frames = 0
         self.E = 0
         self.rank, self.world = rank, world
+        self._cluster_has_nrm = False   # the frame of the last cluster() had normals
         if world > 1:
             _check(self.lib, self.lib.mvicp_set_shard(self.h, rank, world))
 
@@ -774,6 +803,34 @@ class Engine:
         ready()
         _check(self.lib, self.lib.mvicp_outlier_fetch(self.h, kept, ptr(xyz), ptr(nrm), ptr(idx), n, ptr(mdist), ptr(kd2)))
         return {"xyz": xyz, "nrm": nrm, "idx": idx, "mdist": mdist, "kd2": kd2, "stats": S.as_dict()}
+
+    def cluster(self, frame, radius, min_pts=4, device=False):
+        """mvicp_cluster + mvicp_cluster_fetch on the stored cloud of `frame`: DBSCAN with the strict radius predicate of knn_search, the
+        point itself counting towards min_pts, border points joining the cluster of their first core neighbour in the order (d2, index),
+        clusters numbered by their smallest core index -> dict(label (n,) int32 with -1 = noise, core (n,) uint8, size (C,) int32,
+        stats).  min_pts = 1: plain Euclidean cluster extraction.  device=True: torch tensors on the engine's GPU instead of numpy arrays.
+        Needs no graph; history-neutral."""
+        S = ClusterStats()
+        nc = int(_check(self.lib, self.lib.mvicp_cluster(self.h, int(frame), float(radius), int(min_pts), C.byref(S))))
+        n = int(S.n)
+        self._cluster_has_nrm = bool(S.has_normals)
+        mk, ptr, ready, f64, i32, i64, u8 = self._result_arrays(device)
+        label, core, size = mk((n,), i32), mk((n,), u8), mk((nc,), i32)
+        ready()
+        _check(self.lib, self.lib.mvicp_cluster_fetch(self.h, n, ptr(label), ptr(core), nc, ptr(size)))
+        return {"label": label, "core": core, "size": size, "stats": S.as_dict()}
+
+    def cluster_select(self, min_size=0, max_clusters=0, device=False):
+        """mvicp_cluster_select + mvicp_cluster_fetch_kept on the last cluster() result: the points of the clusters that cluster_keep_rule
+        keeps (noise always goes), in ascending original index -> dict(xyz (kept,3), nrm (kept,3) or None, idx (kept,) int32, label (kept,)
+        int32, kept).  device=True: torch tensors on the engine's GPU (xyz / nrm ready for set_frame_device)."""
+        kept = int(_check(self.lib, self.lib.mvicp_cluster_select(self.h, int(min_size), int(max_clusters))))
+        mk, ptr, ready, f64, i32, i64, u8 = self._result_arrays(device)
+        xyz, idx, label = mk((kept, 3), f64), mk((kept,), i32), mk((kept,), i32)
+        nrm = mk((kept, 3), f64) if self._cluster_has_nrm else None   # (normals cannot leave a frame without an upload, which ends the result)
+        ready()
+        _check(self.lib, self.lib.mvicp_cluster_fetch_kept(self.h, kept, ptr(xyz), ptr(nrm), ptr(idx), ptr(label)))
+        return {"xyz": xyz, "nrm": nrm, "idx": idx, "label": label, "kept": kept}
 
     def knn_search(self, frame, queries=None, k=8, radius=0.0, device=False):
         """mvicp_knn_search + mvicp_knn_fetch on the stored cloud of `frame`: per query the candidates (every point, or with radius > 0 the
