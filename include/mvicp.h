@@ -290,6 +290,87 @@ long long mvicp_cluster_select(mvicp_ctx* ctx, long long min_size, long long max
  * without normals -> MVICP_ERR_STATE. */
 int mvicp_cluster_fetch_kept(mvicp_ctx* ctx, long long cap, double* xyz, double* nrm, int* idx, int* label);
 
+/* ---- plane segmentation: the dominant plane of one stored cloud by RANSAC, refitted over its inliers; plane out, then cluster --------
+ * Objects stand on a table, a floor or a turntable, and that plane joins them into one cluster of mvicp_cluster; it is also the one thing
+ * of a turntable scan that is the same in every view.  This stage names it.  The result is a pure function of the stored cloud
+ * p_0 .. p_{n-1} of `frame` (the stored bytes in original order, finite by mvicp_set_frame's own check; no pose, no hash structure, no
+ * graph) and of the arguments, bit for bit, whatever order the GPU's threads run in (tests/planeref.py is the same definition in numpy and
+ * as a scalar loop): only comparisons, integer sums and a maximum cross lanes.  fp64, every operation rounded on its own, no fma;
+ * dot(x, y) = (x0 y0 + x1 y1) + x2 y2 and cross(x, y) = (x1 y2 - x2 y1, x2 y0 - x0 y2, x0 y1 - x1 y0), the forms of mvicp_consensus.
+ *   Sample     hypothesis h (0 <= h < hypotheses), slot t in {0, 1, 2}: the generator of mvicp_consensus with c = n gives the index i_t.
+ *              Two equal indices: the hypothesis is rejected.  The check precedes every load, so n < 3 rejects everything and is no error.
+ *   Plane      a = p_{i0}, u = p_{i1} - a, v = p_{i2} - a, w = cross(u, v), nw = sqrt(dot(w, w)); rejected unless 0 < nw < +inf;
+ *              m = w / nw, componentwise.
+ *   Direction  only when `axis` is given (3 finite doubles, not all zero; cos_min in [0, 1]): da = dot(m, axis); rejected unless
+ *              da * da >= (cos_min * cos_min) * dot(axis, axis).  The cosine, not an angle: no cos() enters the contract.
+ *   Score      o_i = p_i - a, r_i = dot(m, o_i); point i is an inlier iff fabs(r_i) <= tau (inclusive).  count[h] = the number of
+ *              inliers, -1 for a rejected hypothesis.  The offset from a is taken BEFORE the dot product, so the test keeps its meaning
+ *              at UTM coordinates.
+ *   Winner     the largest count, the lowest h among equals.  Nothing accepted: best = -1, count = 0, the plane all zeros, no flag set;
+ *              that is no error.
+ *   Refit      (refine != 0 and a winner exists) over the winner's inlier set I, c = |I|:
+ *              omax = the maximum over I and the three axes of |o_i|; omax == 0: the refit is refused and the refined plane is the
+ *                hypothesis, refit = 0.
+ *              L = the bit length of c, b = min(21, (62 - L) / 2) in integer division, q = the integer with 2^(b-1) <= omax 2^q < 2^b.
+ *              M_i = floor(ldexp(o_i, q)) componentwise, as int64; s_k = sum M_ik and S_kl = sum M_ik M_il (k <= l) are exact int64 sums
+ *                (|s| < 2^(L+b), |S| < 2^(L+2b) <= 2^62).
+ *              The rest is mvicp_plane_from_moments(c, s, S, q, a, m): C_kl = the 128-bit integer c S_kl - s_k s_l converted to double
+ *                with round-to-nearest-even (as mvicp_outlier_threshold converts its 128-bit value); the Jacobi iteration of
+ *                mvicp_estimate_normals on C with V = I (6 sweeps over (0,1), (0,2), (1,2); a rotation is skipped iff C[p][q] == 0); the
+ *                index of the smallest diagonal entry by that contract's two strict comparisons; that column divided by its length;
+ *                negated iff its dot product with m is < 0: the normal m'.  The point g_k = a_k + ldexp((double)s_k / (double)c + 0.5, -q)
+ *                (the 0.5 undoes the floor's bias).
+ *              Refined flags: fabs(dot(m', p_i - g)) <= tau; count_refined is their number.
+ *   Output     the record below, count (hypotheses ints) and flags (n bytes): by the refined plane when refit == 1, otherwise by the
+ *              hypothesis.  Without a refit normal / point repeat hyp_normal / hyp_point, count_refined = count and b = q = 0.
+ *   Selection  mvicp_plane_select: the points with flag = 1 (the plane) or flag = 0 (the rest) in ascending original index, each with
+ *              xyz, nrm (iff the frame has normals) and idx, as the stored bytes.
+ * Repeated extraction is the caller's loop: select the rest, mvicp_set_frame_device, call again.  Left out: adaptive early termination
+ * (count[h] is an output for every h), a point-normal agreement test per inlier, models other than a plane, sampling from a mask.
+ * Needs 1 <= hypotheses <= 2^24 and a finite tau > 0.  HISTORY-NEUTRAL like mvicp_cluster: it does not modify the frame and leaves caches,
+ * seeds, lists, epochs, medians, the AUTO state and queued evaluations alone.  With several ranks every rank computes it locally.  The call
+ * returns when the result is complete; the result lives in library-owned device memory until the next mvicp_segment_plane, an upload to
+ * `frame`, mvicp_set_num_frames or mvicp_destroy.  Profile scopes: "plane_hyp", "plane_score", "plane_pick", "plane_moments",
+ * "plane_flags", "plane_compact".
+ * Errors: NULL context or result, a frame index out of range, hypotheses outside [1, 2^24], a tau that is not finite or <= 0, an axis
+ * that is not finite or all zero, cos_min outside [0, 1] (looked at only with an axis) -> MVICP_ERR_ARG, decided before the context is
+ * touched: the previous result stays; a frame never uploaded -> MVICP_ERR_STATE. */
+typedef struct mvicp_plane_result {
+  int best, count, accepted;         /* the winning hypothesis (-1: none), its inliers, the hypotheses not rejected */
+  int refit;                         /* 1: normal / point / flags are the refitted plane's */
+  int count_refined;                 /* the flags set */
+  int b, q;                          /* the refit's bit budget and scale exponent (0 without a refit) */
+  int has_normals;                   /* the frame has normals: mvicp_plane_fetch_kept gives nrm */
+  long long n;                       /* points of the frame */
+  double normal[3], point[3], d;     /* the plane dot(normal, x) + d = 0 through point; d = -dot(normal, point) */
+  double hyp_normal[3], hyp_point[3];/* the winning hypothesis's own m and a */
+} mvicp_plane_result;
+int mvicp_segment_plane(mvicp_ctx* ctx, int frame, long long hypotheses, unsigned long long seed, double tau, const double* axis /* may be NULL */,
+                        double cos_min, int refine, mvicp_plane_result* result);
+/* Copies the last result: count (hypotheses ints), flags (n bytes); each may be NULL; each may be a HOST pointer or a DEVICE pointer of the
+ * context's device, decided per pointer as mvicp_voxel_fetch decides.  cap_h / cap_n = entries count / flags hold (each looked at only
+ * when its array is given).
+ * Errors: NULL context, cap_h < hypotheses, cap_n < n -> MVICP_ERR_ARG; no mvicp_segment_plane before -> MVICP_ERR_STATE. */
+int mvicp_plane_fetch(mvicp_ctx* ctx, long long cap_h, int* count, long long cap_n, unsigned char* flags);
+/* The points of the last mvicp_segment_plane result with flag = 1 (inliers != 0: the plane) or flag = 0 (inliers == 0: the rest), in
+ * ascending original index, compacted on the device (the compaction of mvicp_outlier_filter and mvicp_cluster_select).  The rows are the
+ * frame's stored bytes.  May be called again with the other choice; the selection lives as long as the result.
+ * RETURNS THE NUMBER OF ROWS or a negative mvicp_status.
+ * Errors: NULL context -> MVICP_ERR_ARG; no mvicp_segment_plane result -> MVICP_ERR_STATE. */
+long long mvicp_plane_select(mvicp_ctx* ctx, int inliers);
+/* Copies the last selection: xyz / nrm (kept x 3 doubles: the stored bytes; nrm iff the frame has normals), idx (kept ints: original
+ * indices, ascending); each may be NULL; each may be a HOST pointer or a DEVICE pointer of the context's device, decided per pointer as
+ * mvicp_voxel_fetch decides, so a device result goes straight into mvicp_set_frame_device.  cap = rows each destination holds.
+ * Errors: NULL context, cap < kept -> MVICP_ERR_ARG; no mvicp_segment_plane result, no mvicp_plane_select of it, or nrm != NULL for a
+ * frame without normals -> MVICP_ERR_STATE. */
+int mvicp_plane_fetch_kept(mvicp_ctx* ctx, long long cap, double* xyz, double* nrm, int* idx);
+/* The refit rule from the integer sums on (pure host function, no context): c = the number of inliers, s[3] = sum M_k, S[6] = sum M_k M_l
+ * in the order 00 01 02 11 12 22, q = the scale exponent, a / m = the hypothesis's point and unit normal -> normal[3], point[3] as the
+ * Refit paragraph above defines them.  The device part of a refit ends at the ten integers; this function finishes it.
+ * Errors: c outside [1, 2^31), a NULL pointer, q outside [-1100, 1100], a non-finite a or m, a negative S_kk or
+ * c S_kk - s_k s_k < 0 (not the sums of one set) -> MVICP_ERR_ARG. */
+int mvicp_plane_from_moments(long long c, const long long s[3], const long long S[6], int q, const double a[3], const double m[3], double normal[3], double point[3]);
+
 /* ---- neighbour search: the k nearest and / or all points within a radius, for arbitrary queries, with indices ------------
  * The search primitive of every point-cloud toolkit (search_knn, search_radius, the hybrid of the two) over one stored cloud.  The result
  * is a pure function of the inputs, bit for bit (tests/knnref.py is the same definition in numpy):

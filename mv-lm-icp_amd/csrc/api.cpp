@@ -546,7 +546,7 @@ int mvicp_create(int device, mvicp_ctx** out) try {
 static void release_stages(mvicp_ctx* c) {
   c->vox.release(); c->out.release(); c->knn.release(); c->fpfh.release();
   c->match.release(); c->cons.release(); c->coarse.release(); c->iss.release(); c->nrm.release();
-  c->ori.release(); c->agree.release(); c->clu.release();
+  c->ori.release(); c->agree.release(); c->clu.release(); c->plane.release();
 }
 
 int mvicp_destroy(mvicp_ctx* c) try {
@@ -607,6 +607,7 @@ int mvicp_set_frame(mvicp_ctx* c, int frame, const double* xyz, const double* nr
   if (c->nrm.frame == frame) c->nrm.drop_result();   // (estimated normals of the cloud this call replaces: nothing to adopt them into)
   if (c->ori.frame == frame) c->ori.drop_result();   // (and its oriented normals)
   if (c->clu.frame == frame) c->clu.drop_result();   // (and its clusters: a selection would read the new rows)
+  if (c->plane.frame == frame) c->plane.drop_result();   // (and its plane, for the same reason)
   if (f.job) { try { (void)f.job->fut.get(); } catch (...) {} f.job.reset(); }   // a build of the cloud this call replaces
   dev_free(f.pts); dev_free(f.nor); free_grid(f.grid); free_tie(f);
   f.has_grid = false; f.build_error.clear();
@@ -688,6 +689,7 @@ int mvicp_set_frame_device(mvicp_ctx* c, int frame, const double* d_xyz, const d
   if (c->nrm.frame == frame) c->nrm.drop_result();   // (estimated normals of the cloud this call replaces: nothing to adopt them into)
   if (c->ori.frame == frame) c->ori.drop_result();   // (and its oriented normals)
   if (c->clu.frame == frame) c->clu.drop_result();   // (and its clusters: a selection would read the new rows)
+  if (c->plane.frame == frame) c->plane.drop_result();   // (and its plane, for the same reason)
   if (f.job) { try { (void)f.job->fut.get(); } catch (...) {} f.job.reset(); }   // a build of the cloud this call replaces
   dev_free(f.pts); dev_free(f.nor); free_grid(f.grid); free_tie(f);
   f.has_grid = false; f.build_error.clear();
@@ -1035,6 +1037,63 @@ int mvicp_cluster_fetch_kept(mvicp_ctx* c, long long cap, double* xyz, double* n
   if (c->clu.kept == 0) return MVICP_OK;
   const size_t m = (size_t)c->clu.kept;
   const FetchPart parts[] = {{xyz, c->clu.xyz, 24 * m, "xyz"}, {nrm, c->clu.nrm, 24 * m, "nrm"}, {idx, c->clu.idx, 4 * m, "idx"}, {label, c->clu.klabel, 4 * m, "label"}};
+  return fetch_parts(c, parts);
+} MVICP_GUARD_ABI
+
+int mvicp_segment_plane(mvicp_ctx* c, int frame, long long hypotheses, unsigned long long seed, double tau, const double* axis, double cos_min, int refine,
+                        mvicp_plane_result* result) try {
+  // every argument error that needs no GPU first: nothing of the context has been touched when one of them is reported
+  if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
+  if (!result) { set_error("null result"); return MVICP_ERR_ARG; }
+  if (hypotheses < 1 || hypotheses > (1ll << 24)) { set_error("hypotheses = %lld outside [1, 2^24]", hypotheses); return MVICP_ERR_ARG; }
+  if (!std::isfinite(tau) || !(tau > 0.0)) { set_error("tau must be finite and > 0"); return MVICP_ERR_ARG; }
+  if (axis) {
+    if (!std::isfinite(axis[0]) || !std::isfinite(axis[1]) || !std::isfinite(axis[2]) || (axis[0] == 0.0 && axis[1] == 0.0 && axis[2] == 0.0)) {
+      set_error("axis must be finite and not all zero");
+      return MVICP_ERR_ARG;
+    }
+    if (!(cos_min >= 0.0 && cos_min <= 1.0)) { set_error("cos_min must lie in [0, 1]"); return MVICP_ERR_ARG; }
+  }
+  if (frame < 0 || frame >= c->n_frames) { set_error("frame %d out of range [0,%d)", frame, c->n_frames); return MVICP_ERR_ARG; }
+  if (!c->frames[frame].pts) { set_error("frame %d was never uploaded", frame); return MVICP_ERR_STATE; }
+  MV_CHECK(bind(c));
+  const int st = plane_segment(c, c->frames[frame], frame, hypotheses, seed, tau, axis, cos_min, refine, result);
+  if (c->profile) prof_collect_lazy(c);
+  return st;
+} MVICP_GUARD_ABI
+
+int mvicp_plane_fetch(mvicp_ctx* c, long long cap_h, int* count, long long cap_n, unsigned char* flags) try {
+  if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
+  if (c->plane.n < 0) { set_error("no plane result: call mvicp_segment_plane first"); return MVICP_ERR_STATE; }
+  if (count && cap_h < c->plane.H) { set_error("cap_h %lld < %lld hypotheses", cap_h, c->plane.H); return MVICP_ERR_ARG; }
+  if (flags && cap_n < c->plane.n) { set_error("cap_n %lld < %lld points", cap_n, c->plane.n); return MVICP_ERR_ARG; }
+  const FetchPart parts[] = {{count, c->plane.count, 4 * (size_t)c->plane.H, "count"}, {flags, c->plane.n ? c->plane.flags : nullptr, (size_t)c->plane.n, "flags"}};
+  return fetch_parts(c, parts);
+} MVICP_GUARD_ABI
+
+long long mvicp_plane_select(mvicp_ctx* c, int inliers) try {
+  if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
+  if (c->plane.n < 0) { set_error("no plane result: call mvicp_segment_plane first"); return MVICP_ERR_STATE; }
+  const int frame = c->plane.frame;
+  if (frame < 0 || frame >= c->n_frames || c->frames[frame].n != c->plane.n || (c->plane.n > 0 && !c->frames[frame].pts)) {
+    set_error("the segmented frame is gone: call mvicp_segment_plane again");
+    return MVICP_ERR_STATE;
+  }
+  MV_CHECK(bind(c));
+  const long long kept = plane_select(c, c->frames[frame], inliers);
+  if (c->profile) prof_collect_lazy(c);
+  return kept;
+} MVICP_GUARD_ABI
+
+int mvicp_plane_fetch_kept(mvicp_ctx* c, long long cap, double* xyz, double* nrm, int* idx) try {
+  if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
+  if (c->plane.n < 0) { set_error("no plane result: call mvicp_segment_plane first"); return MVICP_ERR_STATE; }
+  if (c->plane.kept < 0) { set_error("no selection: call mvicp_plane_select first"); return MVICP_ERR_STATE; }
+  if (cap < c->plane.kept) { set_error("cap %lld < %lld kept rows", cap, c->plane.kept); return MVICP_ERR_ARG; }
+  if (nrm && !c->plane.has_normals) { set_error("the segmented frame has no normals"); return MVICP_ERR_STATE; }
+  if (c->plane.kept == 0) return MVICP_OK;
+  const size_t m = (size_t)c->plane.kept;
+  const FetchPart parts[] = {{xyz, c->plane.xyz, 24 * m, "xyz"}, {nrm, c->plane.nrm, 24 * m, "nrm"}, {idx, c->plane.idx, 4 * m, "idx"}};
   return fetch_parts(c, parts);
 } MVICP_GUARD_ABI
 
@@ -1526,6 +1585,50 @@ int mvicp_cluster_keep_rule(long long n_clusters, const int* size, long long min
   for (long long r = 0; r < n_clusters; ++r) {
     const long long k = order[(size_t)r];
     keep[k] = (size[k] >= min_size && (max_clusters == 0 || r < max_clusters)) ? 1 : 0;
+  }
+  return MVICP_OK;
+} MVICP_GUARD_ABI
+
+// one Jacobi rotation on the pair (p, q), p < q, of the symmetric 3 x 3 A with the vectors V: the rotation of csrc/jacobi3.h (whose __d*_rn
+// intrinsics exist on the device only) in plain operators -- this TU is built without fma contraction, so every one is rounded on its own
+static void plane_jacobi_rotate(double (&A)[3][3], double (&V)[3][3], int p, int q) {
+  const double apq = A[p][q];
+  if (apq == 0.0) return;
+  const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
+  const double t = (theta >= 0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+  const double cs = 1.0 / std::sqrt(t * t + 1.0), sn = t * cs;
+  for (int r = 0; r < 3; ++r) { const double xp = A[r][p], xq = A[r][q]; A[r][p] = cs * xp - sn * xq; A[r][q] = sn * xp + cs * xq; }   // A <- A J
+  for (int r = 0; r < 3; ++r) { const double xp = A[p][r], xq = A[q][r]; A[p][r] = cs * xp - sn * xq; A[q][r] = sn * xp + cs * xq; }   // A <- J^T A
+  for (int r = 0; r < 3; ++r) { const double xp = V[r][p], xq = V[r][q]; V[r][p] = cs * xp - sn * xq; V[r][q] = sn * xp + cs * xq; }   // V <- V J
+}
+
+int mvicp_plane_from_moments(long long c, const long long* s, const long long* S, int q, const double* a, const double* m, double* normal, double* point) try {
+  if (c < 1 || c >= (1ll << 31)) { set_error("plane from moments: needs 1 <= c < 2^31"); return MVICP_ERR_ARG; }
+  if (!s || !S || !a || !m || !normal || !point) { set_error("plane from moments: needs s, S, a, m, normal and point"); return MVICP_ERR_ARG; }
+  if (q < -1100 || q > 1100) { set_error("plane from moments: q = %d outside [-1100, 1100]", q); return MVICP_ERR_ARG; }
+  for (int k = 0; k < 3; ++k)
+    if (!std::isfinite(a[k]) || !std::isfinite(m[k])) { set_error("plane from moments: a and m must be finite"); return MVICP_ERR_ARG; }
+  // the 128-bit integers c S_kl - s_k s_l (|c S| < 2^94, |s s| <= 2^126: no overflow), each converted with round-to-nearest-even
+  static const int at[3][3] = {{0, 1, 2}, {1, 3, 4}, {2, 4, 5}};
+  double A[3][3], V[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
+  for (int k = 0; k < 3; ++k)
+    for (int l = 0; l < 3; ++l) {
+      const __int128 v = (__int128)c * S[at[k][l]] - (__int128)s[k] * s[l];
+      if (k == l && (S[at[k][k]] < 0 || v < 0)) { set_error("plane from moments: S_%d%d or c S - s s is negative (not the sums of one set)", k, k); return MVICP_ERR_ARG; }
+      A[k][l] = (double)v;
+    }
+  for (int sweep = 0; sweep < 6; ++sweep) { plane_jacobi_rotate(A, V, 0, 1); plane_jacobi_rotate(A, V, 0, 2); plane_jacobi_rotate(A, V, 1, 2); }
+  int j = 0;
+  if (A[1][1] < A[j][j]) j = 1;
+  if (A[2][2] < A[j][j]) j = 2;
+  const double v0 = V[0][j], v1 = V[1][j], v2 = V[2][j];
+  const double ln = std::sqrt((v0 * v0 + v1 * v1) + v2 * v2);
+  double nv[3] = {v0 / ln, v1 / ln, v2 / ln};
+  if ((nv[0] * m[0] + nv[1] * m[1]) + nv[2] * m[2] < 0) { nv[0] = -nv[0]; nv[1] = -nv[1]; nv[2] = -nv[2]; }
+  const double dc = (double)c;
+  for (int k = 0; k < 3; ++k) {
+    normal[k] = nv[k];
+    point[k] = a[k] + std::ldexp((double)s[k] / dc + 0.5, -q);
   }
   return MVICP_OK;
 } MVICP_GUARD_ABI

@@ -18,7 +18,7 @@
 //   4  label    exclusive scan of the root flags over the original index (rocprim) = the rank of a root among the roots = the contract's
 //               numbering; label[i] = rank[root[i]]; sizes and the three counts by integer atomics, one per distinct label of a wave.
 // mvicp_cluster_select: keep byte per cluster from the host rule (mvicp_cluster_keep_rule), flag = label >= 0 and kept, scan, compact --
-// the compaction of outlier.hip with the label as a fourth row.
+// the compaction of compact_rows.h with the label as a fourth row.
 // The radius graph is undirected because dist2 is bitwise symmetric (the differences are exact negatives, the squares drop the sign), so
 // "j < i" in the union pass loses no edge.  Every store is a plain vector store or a vector atomic; no kernel waits for another workgroup.
 #include <algorithm>
@@ -28,6 +28,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "common.h"
+#include "compact_rows.h"
 #include "knn_traverse.h"
 #include "nn_metric.h"
 
@@ -180,27 +181,6 @@ __global__ __launch_bounds__(VT) void cluster_keep_kernel(const int* __restrict_
   flag[i] = lab >= 0 && keep[lab] ? 1 : 0;
 }
 
-// outlier.hip's compaction with the label as a fourth row
-template <bool NRM>
-__global__ __launch_bounds__(VT) void cluster_compact_kernel(const double* __restrict__ pts, const double* __restrict__ nor, const int* __restrict__ label,
-                                                             const int* __restrict__ flag, const int* __restrict__ pos, int n, double* __restrict__ xyz,
-                                                             double* __restrict__ nrm, int* __restrict__ idx, int* __restrict__ klabel, ClCtl* __restrict__ ctl) {
-  const int i = blockIdx.x * VT + threadIdx.x;
-  if (i >= n) return;
-  const int f = flag[i], o = pos[i];   // o <= i < n: inside the n-row destinations
-  if (f) {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) xyz[3 * (size_t)o + a] = pts[3 * (size_t)i + a];
-    if (NRM) {
-#pragma unroll
-      for (int a = 0; a < 3; ++a) nrm[3 * (size_t)o + a] = nor[3 * (size_t)i + a];
-    }
-    idx[o] = i;
-    klabel[o] = label[i];
-  }
-  if (i == n - 1) ctl->kept = o + f;
-}
-
 // the arena of a frame of n points: [control | core | parent | root | flag | rank | label | size | keep | xyz | nrm | idx | klabel]
 struct Arena {
   size_t core, parent, root, flag, pos, label, size, keep, xyz, nrm, idx, klabel, bytes;
@@ -319,8 +299,7 @@ long long cluster_select(mvicp_ctx* c, const FrameDev& f, long long min_size, lo
     hipLaunchKernelGGL(cluster_keep_kernel, dim3(grid_of(n, VT)), dim3(VT), 0, st, S.label, d_keep, n, flag);
     size_t tb = S.tmp.cap;
     MV_HIP(rocprim::exclusive_scan(S.tmp.p, tb, flag, pos, 0, NN, rocprim::plus<int>(), st));
-    if (normals) hipLaunchKernelGGL(cluster_compact_kernel<true>, dim3(grid_of(n, VT)), dim3(VT), 0, st, f.pts, f.nor, S.label, flag, pos, n, S.xyz, S.nrm, S.idx, S.klabel, d_ctl);
-    else hipLaunchKernelGGL(cluster_compact_kernel<false>, dim3(grid_of(n, VT)), dim3(VT), 0, st, f.pts, f.nor, S.label, flag, pos, n, S.xyz, S.nrm, S.idx, S.klabel, d_ctl);
+    compact_rows<true>(st, f.pts, f.nor, S.label, flag, pos, n, S.xyz, S.nrm, S.idx, S.klabel, &d_ctl->kept);
   }
   MV_HIP(hipGetLastError());
   MV_HIP(hipMemcpyAsync(h_ctl, d_ctl, sizeof(ClCtl), hipMemcpyDeviceToHost, st));

@@ -115,7 +115,7 @@ struct ProfEntry {
 
 // ---- buffers and results a stage of the library owns ---------------------------------------------------------------------------------
 // A stage (voxel grid, outlier filter, neighbour search, FPFH, descriptor matching, consensus, batched coarse poses, ISS keypoints, estimated
-// normals, oriented normals, clusters) keeps its LAST result on the context until the caller has fetched it.  Ownership, stated once for all eleven: the stage's struct below holds
+// normals, oriented normals, clusters, the dominant plane) keeps its LAST result on the context until the caller has fetched it.  Ownership, stated once for all twelve: the stage's struct below holds
 // buffers of its own (so that a call touches nothing a search, a queued evaluation, the census or another stage uses), kept between
 // calls and grown on demand, the result arrays as views into them, and the sizes / flags, whose defaults mean "no result".  A call marks
 // its result as gone when it starts (a failed call leaves none behind) and sets it after its last wait; the result then lives until the
@@ -252,6 +252,17 @@ struct ClusterStage {
   long long n = -1, clusters = -1, kept = -1; int frame = -1, has_normals = 0;   // n < 0: none
   void drop_result() { n = -1; clusters = -1; kept = -1; frame = -1; has_normals = 0; h_size.clear(); }
   void release() { dev.release(); tmp.release(); pin.release(); *this = ClusterStage(); }
+};
+// plane.hip.  dev: one arena [control | count | accepted h | flags | flag | rank | xyz | nrm | idx], tmp: rocprim storage, pin: the host copy of
+// the control block.  frame: the slot the result was computed for (mvicp_plane_select reads its stored rows); an upload to that slot drops
+// the result.  kept: the rows of the last mvicp_plane_select of this result (< 0: none)
+struct PlaneStage {
+  DevBuf dev, tmp; PinBuf pin;
+  int* count = nullptr; unsigned char* flags = nullptr;
+  double* xyz = nullptr; double* nrm = nullptr; int* idx = nullptr;
+  long long n = -1, H = -1, kept = -1; int frame = -1, has_normals = 0;   // n < 0: none
+  void drop_result() { n = -1; H = -1; kept = -1; frame = -1; has_normals = 0; }
+  void release() { dev.release(); tmp.release(); pin.release(); *this = PlaneStage(); }
 };
 // orient.hip (mvicp_normal_agreement).  dev: [poses | per-edge pointer tables | per-edge counts | pos | neg], pin: the host copy of pos | neg
 struct AgreementStage {
@@ -395,6 +406,7 @@ struct mvicp_ctx {
   mvicp::OrientStage ori;
   mvicp::AgreementStage agree;
   mvicp::ClusterStage clu;
+  mvicp::PlaneStage plane;
   std::vector<char> src_fixed;     // E: the edge's source frame was fixed in the last mvicp_correspond (0 before the first): mvicp_normal_agreement skips it
 
   // cached small tables
@@ -484,6 +496,14 @@ long long cluster_points(mvicp_ctx* c, const FrameDev& f, int frame, double B2, 
 // mvicp_cluster_keep_rule(min_size, max_clusters) keeps, compacted in ascending original index into c->clu.  Returns the rows kept or a
 // negative status.  Waits for the stream once; history-neutral.
 long long cluster_select(mvicp_ctx* c, const FrameDev& f, long long min_size, long long max_clusters);
+// plane.hip: the dominant plane of frame f = c->frames[frame] (valid, uploaded) over H hypotheses (1 <= H <= 2^24, finite tau > 0; axis null or
+// 3 finite doubles, not all zero, with cos_min in [0, 1]); the result stays on the context (c->plane).  One wait without a refit, two
+// with one (the host rule mvicp_plane_from_moments stands between them); history-neutral.
+int plane_segment(mvicp_ctx* c, const FrameDev& f, int frame, long long H, unsigned long long seed, double tau, const double* axis, double cos_min, int refine,
+                  mvicp_plane_result* out);
+// plane.hip: the rows of f (the frame of the last plane_segment, unchanged since: c->plane.n == f.n >= 0) with flag == (inliers ? 1 : 0),
+// compacted in ascending original index into c->plane.  Returns the rows kept or a negative status.  Waits for the stream once.
+long long plane_select(mvicp_ctx* c, const FrameDev& f, int inliers);
 // knn.hip: the neighbourhoods of m queries (host or device memory, as `queries_on_device` says) or, queries == null, of the cloud's own
 // points, in frame f (valid, uploaded, structures built); 0 <= k <= 64, k == 0 needs radius > 0; B2 = sqrt_bound(radius) when radius > 0.
 // The result stays on the context (c->knn).  Returns the number of entries or a negative status.  Waits for the stream; history-neutral.

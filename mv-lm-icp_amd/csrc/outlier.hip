@@ -12,7 +12,7 @@
 //               n < 2^31): wave reduction, then three 64-bit integer atomics per workgroup.  Integer sums: order-independent.
 //      -- host wait: the sums; T = mvicp_outlier_threshold --
 //   3  flag     keep = ((double)M <= T) and (sqrt(kd2) < radius), each rule only when it is on
-//   4  compact  exclusive scan of the flags (rocprim), then one lane per point stores its row at its rank: ascending original index
+//   4  compact  exclusive scan of the flags (rocprim), then compact_rows.h: one lane per point stores its row at its rank
 //      -- host wait: the number kept --
 // What the knn kernel keeps to itself next to the other users of traverse() (this kernel is the whole feature):
 //   * the list capacity is a template parameter (9 / 17 / 33 doubles per lane, one LDS column per lane): 9 / 17 / 33 KiB per 128-lane
@@ -28,6 +28,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "common.h"
+#include "compact_rows.h"
 #include "knn_traverse.h"
 #include "nn_metric.h"
 
@@ -126,25 +127,6 @@ __global__ __launch_bounds__(VT) void outlier_flag_kernel(const double* __restri
   flag[i] = keep ? 1 : 0;
 }
 
-template <bool NRM>
-__global__ __launch_bounds__(VT) void outlier_compact_kernel(const double* __restrict__ pts, const double* __restrict__ nor, const int* __restrict__ flag,
-                                                             const int* __restrict__ pos, int n, double* __restrict__ xyz, double* __restrict__ nrm,
-                                                             int* __restrict__ idx, OutCtl* __restrict__ ctl) {
-  const int i = blockIdx.x * VT + threadIdx.x;
-  if (i >= n) return;
-  const int f = flag[i], o = pos[i];   // o <= i < n: inside the n-row destinations
-  if (f) {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) xyz[3 * (size_t)o + a] = pts[3 * (size_t)i + a];
-    if (NRM) {
-#pragma unroll
-      for (int a = 0; a < 3; ++a) nrm[3 * (size_t)o + a] = nor[3 * (size_t)i + a];
-    }
-    idx[o] = i;
-  }
-  if (i == n - 1) ctl->kept = o + f;
-}
-
 }  // namespace
 
 long long outlier_filter(mvicp_ctx* c, const FrameDev& f, int k, double std_ratio, double radius, mvicp_outlier_stats* stats) {
@@ -223,8 +205,7 @@ long long outlier_filter(mvicp_ctx* c, const FrameDev& f, int k, double std_rati
     ProfScope ps(c, "outlier_compact", (normals ? 108.0 : 60.0) * n);
     size_t tb = scan_bytes;
     MV_HIP(rocprim::exclusive_scan(c->out.tmp.p, tb, flag, pos, 0, NN, rocprim::plus<int>(), st));
-    if (normals) hipLaunchKernelGGL(outlier_compact_kernel<true>, dim3(grid_of(n, VT)), dim3(VT), 0, st, f.pts, f.nor, flag, pos, n, c->out.xyz, c->out.nrm, c->out.idx, d_ctl);
-    else hipLaunchKernelGGL(outlier_compact_kernel<false>, dim3(grid_of(n, VT)), dim3(VT), 0, st, f.pts, f.nor, flag, pos, n, c->out.xyz, c->out.nrm, c->out.idx, d_ctl);
+    compact_rows<false>(st, f.pts, f.nor, nullptr, flag, pos, n, c->out.xyz, c->out.nrm, c->out.idx, nullptr, &d_ctl->kept);
   }
   MV_HIP(hipGetLastError());
   MV_HIP(hipMemcpyAsync(h_ctl, d_ctl, sizeof(OutCtl), hipMemcpyDeviceToHost, st));

@@ -599,6 +599,28 @@ std::shared_ptr<Frame> Frame::removeSmallClusters(double radius, int min_pts, lo
   return out;
 }
 
+std::shared_ptr<Frame> Frame::removePlane(double tau, long long hypotheses, unsigned long long seed, const double* axis, double cos_min, bool keep_plane,
+                                          mvicp_plane_result* result) {
+  std::shared_ptr<Frame> out(new Frame());
+  out->fixed = fixed; out->pose = pose; out->poseGroundTruth = poseGroundTruth;
+  for (const OutgoingEdge& e : neighbours) out->neighbours.push_back(OutgoingEdge{e.neighbourIdx, e.weight, {}});
+  mvicp_plane_result R;
+  std::memset(&R, 0, sizeof(R));
+  R.best = -1;
+  if (result) *result = R;
+  if (pts.empty()) return out;
+  int slot = 0;
+  mvicp_ctx* c = Session::get().query_context(this, &slot, true);
+  check(mvicp_segment_plane(c, slot, hypotheses, seed, tau, axis, cos_min, 1, &R));
+  const long long m = mvicp_plane_select(c, keep_plane ? 1 : 0);
+  if (m < 0) check((int)m);
+  out->pts.assign((size_t)m, Vector3d());
+  out->nor.assign(R.has_normals && nor.size() == pts.size() ? (size_t)m : 0, Vector3d());
+  if (m) check(mvicp_plane_fetch_kept(c, m, out->pts[0].data(), out->nor.empty() ? nullptr : out->nor[0].data(), nullptr));
+  if (result) *result = R;
+  return out;
+}
+
 std::vector<int> Frame::issKeypoints(double salient_radius, double non_max_radius, double gamma21, double gamma32, int min_neighbors) {
   std::vector<int> idx;
   if (pts.empty()) return idx;

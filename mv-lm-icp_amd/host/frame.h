@@ -112,6 +112,16 @@ class Frame {
   // Session::query_context finds for this frame (bin/multiview --cluster_radius / --cluster_min_pts / --cluster_min_size / --cluster_keep).
   std::shared_ptr<Frame> removeSmallClusters(double radius, int min_pts, long long min_size, long long max_clusters, long long* clusters = nullptr,
                                              long long* kept_clusters = nullptr);
+  // A copy of this frame without its dominant plane, or of that plane alone (no counterpart in the reference): mvicp_segment_plane on this
+  // cloud as it is stored -- RANSAC over `hypotheses` three-point samples of the generator seeded with `seed`, a point within tau of the plane
+  // an inlier, with `axis` (3 doubles; null: any plane) only planes whose normal has |cos| >= cos_min to it, the winner refitted over its
+  // inliers -- and mvicp_plane_select: the points off the refitted plane (keep_plane = false) or on it (true).  The new Frame has the kept
+  // pts / nor in their original order and the same pose, poseGroundTruth, fixed and neighbours (index and weight; the correspondence
+  // lists start empty).  result, if given, receives the call's record (best = -1: no plane was found and nothing is an inlier).  Runs in
+  // the context Session::query_context finds for this frame (bin/multiview --plane_tau / --plane_hyp / --plane_seed / --plane_keep /
+  // --plane_axis / --plane_cos).
+  std::shared_ptr<Frame> removePlane(double tau, long long hypotheses = 1024, unsigned long long seed = 0, const double* axis = nullptr, double cos_min = 0.0,
+                                     bool keep_plane = false, mvicp_plane_result* result = nullptr);
   // The ISS keypoints of this frame (no counterpart in the reference): mvicp_iss_keypoints on this cloud as it is stored -> the indices
   // of the keypoints, ascending.  Runs in the context Session::query_context finds for this frame (bin/multiview --feat_keypoints).
   std::vector<int> issKeypoints(double salient_radius, double non_max_radius, double gamma21 = 0.975, double gamma32 = 0.975, int min_neighbors = 5);

@@ -33,6 +33,11 @@
 // Frame::removeSmallClusters(R, M, S, N): the clusters of mvicp_cluster (DBSCAN: a core point has M points, itself included, within R) with at
 // least S members, of those the N largest; noise always goes.  What the outlier rules keep -- a compact clump of stray points -- goes here.
 // One line per frame, `cluster filter: frame i kept a of b, c of d clusters` (printed with --quiet too).
+// --plane_tau T [--plane_hyp H] [--plane_seed S] [--plane_keep rest|plane] [--plane_axis=x,y,z --plane_cos C] (default T = 0 = off; H = 1024,
+// S = 0, rest, no axis, C = 0): with T > 0 every frame loses its dominant plane (or, with --plane_keep plane, everything else) after the outlier
+// filter and before the cluster filter, by Frame::removePlane(T, H, S, axis, C, keep): mvicp_segment_plane's RANSAC plane, refitted over its
+// inliers; with an axis only planes whose normal has |cos| >= C to it.  The table, floor or turntable that joins the objects standing on it into
+// one cluster goes here.  One line per frame, `plane filter: frame i kept a of b, c inliers, plane nx ny nz d` (%.17g; printed with --quiet too).
 // --init features: the initial poses of frames 1 .. K-1 come from the clouds alone (Session::initFromFeatures, after loadFrames and before the
 // graph is built; frame 0 keeps its loaded pose): FPFH descriptors, one batched matching + consensus over all frame pairs, a spanning tree
 // over the inlier counts.  --feat_voxel H (0 = the full clouds; otherwise Frame::voxelDownsample(H) copies carry the features),
@@ -64,6 +69,7 @@
 // the frames it flips are negated).  One line per frame, `normal orientation: frame i trees t`, and one line
 // `normal orientation: C component(s), flipped f0 f1 ..` (printed with --quiet too).
 #include <chrono>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
@@ -93,6 +99,23 @@ static void loadFrames(const Flags& F, std::vector<std::shared_ptr<Frame>>& fram
       std::shared_ptr<Frame> kept = f->removeOutliers(F.i("sor_k", 0), F.f("sor_ratio", radius > 0.0 ? -1.0 : 2.0), radius);
       f->pts.swap(kept->pts); f->nor.swap(kept->nor); ++f->version;   // (a context that holds the old cloud re-uploads)
       std::cout << "outlier filter: frame " << frames.size() << " kept " << f->pts.size() << " of " << before << std::endl;
+    }
+    if (F.f("plane_tau", 0.0) > 0.0) {
+      const size_t before = f->pts.size();
+      double axis[3] = {0.0, 0.0, 0.0};
+      const std::string ax = F.s("plane_axis", "");
+      const bool has_axis = !ax.empty();
+      if (has_axis && std::sscanf(ax.c_str(), "%lf,%lf,%lf", &axis[0], &axis[1], &axis[2]) != 3) { std::cerr << "--plane_axis needs x,y,z" << std::endl; std::exit(2); }
+      const std::string keep = F.s("plane_keep", "rest");
+      if (keep != "rest" && keep != "plane") { std::cerr << "--plane_keep needs rest or plane" << std::endl; std::exit(2); }
+      mvicp_plane_result pr;
+      std::shared_ptr<Frame> kept = f->removePlane(F.f("plane_tau", 0.0), std::atoll(F.s("plane_hyp", "1024").c_str()), std::strtoull(F.s("plane_seed", "0").c_str(), nullptr, 10),
+                                                   has_axis ? axis : nullptr, F.f("plane_cos", 0.0), keep == "plane", &pr);
+      f->pts.swap(kept->pts); f->nor.swap(kept->nor); ++f->version;   // (a context that holds the old cloud re-uploads)
+      char line[256];
+      std::snprintf(line, sizeof(line), "plane filter: frame %zu kept %zu of %zu, %d inliers, plane %.17g %.17g %.17g %.17g", frames.size(), f->pts.size(), before,
+                    pr.count_refined, pr.normal[0], pr.normal[1], pr.normal[2], pr.d);
+      std::cout << line << std::endl;
     }
     if (F.f("cluster_radius", 0.0) > 0.0) {
       const size_t before = f->pts.size();

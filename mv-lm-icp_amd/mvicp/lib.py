@@ -22,6 +22,7 @@ SYMBOLS = [
     "mvicp_overlap", "mvicp_graph_from_overlap", "mvicp_voxel_grid", "mvicp_voxel_fetch",
     "mvicp_outlier_filter", "mvicp_outlier_fetch", "mvicp_outlier_threshold", "mvicp_cache_allowance",
     "mvicp_cluster", "mvicp_cluster_fetch", "mvicp_cluster_keep_rule", "mvicp_cluster_select", "mvicp_cluster_fetch_kept",
+    "mvicp_segment_plane", "mvicp_plane_fetch", "mvicp_plane_select", "mvicp_plane_fetch_kept", "mvicp_plane_from_moments",
     "mvicp_knn_search", "mvicp_knn_fetch", "mvicp_fpfh", "mvicp_fpfh_fetch", "mvicp_iss_keypoints", "mvicp_iss_fetch",
     "mvicp_estimate_normals", "mvicp_normals_fetch", "mvicp_normals_adopt", "mvicp_fit_normals", "mvicp_normals_fit_fetch",
     "mvicp_orient_normals", "mvicp_orient_fetch", "mvicp_orient_adopt", "mvicp_normal_agreement", "mvicp_signs_from_agreement", "mvicp_negate_normals",
@@ -62,6 +63,16 @@ class ClusterStats(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class PlaneResult(C.Structure):
+    _fields_ = [("best", C.c_int), ("count", C.c_int), ("accepted", C.c_int), ("refit", C.c_int), ("count_refined", C.c_int), ("b", C.c_int),
+                ("q", C.c_int), ("has_normals", C.c_int), ("n", C.c_longlong), ("normal", C.c_double * 3), ("point", C.c_double * 3),
+                ("d", C.c_double), ("hyp_normal", C.c_double * 3), ("hyp_point", C.c_double * 3)]
+
+    def as_dict(self):
+        vec = ("normal", "point", "hyp_normal", "hyp_point")
+        return {k: np.array(getattr(self, k)) if k in vec else getattr(self, k) for k, _ in self._fields_}
 
 
 class ConsensusResult(C.Structure):
@@ -153,6 +164,12 @@ def load_library(path=None):
     lib.mvicp_cluster_select.argtypes = [vp, C.c_longlong, C.c_longlong]
     lib.mvicp_cluster_select.restype = C.c_longlong
     lib.mvicp_cluster_fetch_kept.argtypes = [vp, C.c_longlong, vp, vp, vp, vp]
+    lib.mvicp_segment_plane.argtypes = [vp, C.c_int, C.c_longlong, C.c_ulonglong, C.c_double, dp, C.c_double, C.c_int, C.POINTER(PlaneResult)]
+    lib.mvicp_plane_fetch.argtypes = [vp, C.c_longlong, vp, C.c_longlong, vp]
+    lib.mvicp_plane_select.argtypes = [vp, C.c_int]
+    lib.mvicp_plane_select.restype = C.c_longlong
+    lib.mvicp_plane_fetch_kept.argtypes = [vp, C.c_longlong, vp, vp, vp]
+    lib.mvicp_plane_from_moments.argtypes = [C.c_longlong, vp, vp, C.c_int, dp, dp, dp, dp]
     lib.mvicp_cache_allowance.argtypes = [dp, dp, dp, dp, C.c_double, dp]
     lib.mvicp_knn_search.argtypes = [vp, C.c_int, vp, C.c_longlong, C.c_int, C.c_double]
     lib.mvicp_knn_search.restype = C.c_longlong
@@ -297,6 +314,20 @@ def cluster_keep_rule(size, min_size=0, max_clusters=0):
     keep = np.zeros(n + 1, dtype=np.uint8)
     _check(lib, lib.mvicp_cluster_keep_rule(n, src.ctypes.data_as(C.c_void_p), int(min_size), int(max_clusters), keep.ctypes.data_as(C.c_void_p)))
     return keep[:n].copy()
+
+
+def plane_from_moments(c, s, S, q, a, m):
+    """mvicp_plane_from_moments: the refit rule of mvicp_segment_plane from the exact integer sums on -- c inliers, s (3) = sum M_k,
+    S (6) = sum M_k M_l in the order 00 01 02 11 12 22, q the scale exponent, a / m the hypothesis's point and unit normal
+    -> (normal (3,), point (3,)).  Host only."""
+    lib = load_library()
+    s = np.ascontiguousarray(s, dtype=np.int64).reshape(3)
+    S = np.ascontiguousarray(S, dtype=np.int64).reshape(6)
+    a = np.ascontiguousarray(a, dtype=np.float64).reshape(3)
+    m = np.ascontiguousarray(m, dtype=np.float64).reshape(3)
+    normal, point = np.zeros(3), np.zeros(3)
+    _check(lib, lib.mvicp_plane_from_moments(int(c), s.ctypes.data_as(C.c_void_p), S.ctypes.data_as(C.c_void_p), int(q), _dp(a), _dp(m), _dp(normal), _dp(point)))
+    return normal, point
 
 
 def cache_allowance(pose_src_old, pose_dst_old, pose_src, pose_dst, max_norm):
@@ -539,6 +570,7 @@ class Engine:
         self.E = 0
         self.rank, self.world = rank, world
         self._cluster_has_nrm = False   # the frame of the last cluster() had normals
+        self._plane_has_nrm = False     # the frame of the last segment_plane() had normals
         if world > 1:
             _check(self.lib, self.lib.mvicp_set_shard(self.h, rank, world))
 
@@ -831,6 +863,38 @@ class Engine:
         ready()
         _check(self.lib, self.lib.mvicp_cluster_fetch_kept(self.h, kept, ptr(xyz), ptr(nrm), ptr(idx), ptr(label)))
         return {"xyz": xyz, "nrm": nrm, "idx": idx, "label": label, "kept": kept}
+
+    def segment_plane(self, frame, tau, hypotheses=1024, seed=0, axis=None, cos_min=0.0, refine=True, device=False):
+        """mvicp_segment_plane + mvicp_plane_fetch on the stored cloud of `frame`: the plane with the most points within tau among
+        `hypotheses` three-point samples (the generator of consensus; the lowest h among equals), with axis (3,) only planes whose normal
+        has |cos| >= cos_min to it, refitted over its inliers through exact integer moments (refine) -> dict(the record's fields: best,
+        count, accepted, refit, count_refined, b, q, n, has_normals, normal, point, d, hyp_normal, hyp_point; counts (hypotheses,) int32
+        with -1 = rejected; flags (n,) uint8).  device=True: counts / flags as torch tensors on the engine's GPU.  Needs no graph and no
+        structure; history-neutral."""
+        R = PlaneResult()
+        ax = None if axis is None else np.ascontiguousarray(axis, dtype=np.float64).reshape(3)
+        _check(self.lib, self.lib.mvicp_segment_plane(self.h, int(frame), int(hypotheses), int(seed) & (2 ** 64 - 1), float(tau), _dp(ax) if ax is not None else None,
+                                                      float(cos_min), 1 if refine else 0, C.byref(R)))
+        self._plane_has_nrm = bool(R.has_normals)
+        mk, ptr, ready, f64, i32, i64, u8 = self._result_arrays(device)
+        counts, flags = mk((int(hypotheses),), i32), mk((int(R.n),), u8)
+        ready()
+        _check(self.lib, self.lib.mvicp_plane_fetch(self.h, int(hypotheses), ptr(counts), int(R.n), ptr(flags)))
+        out = R.as_dict()
+        out.update(counts=counts, flags=flags)
+        return out
+
+    def plane_select(self, inliers=True, device=False):
+        """mvicp_plane_select + mvicp_plane_fetch_kept on the last segment_plane() result: the points of the plane (inliers) or the rest,
+        in ascending original index -> dict(xyz (kept,3), nrm (kept,3) or None, idx (kept,) int32, kept).  device=True: torch tensors on
+        the engine's GPU (xyz / nrm ready for set_frame_device)."""
+        kept = int(_check(self.lib, self.lib.mvicp_plane_select(self.h, 1 if inliers else 0)))
+        mk, ptr, ready, f64, i32, i64, u8 = self._result_arrays(device)
+        xyz, idx = mk((kept, 3), f64), mk((kept,), i32)
+        nrm = mk((kept, 3), f64) if self._plane_has_nrm else None   # (normals cannot leave a frame without an upload, which ends the result)
+        ready()
+        _check(self.lib, self.lib.mvicp_plane_fetch_kept(self.h, kept, ptr(xyz), ptr(nrm), ptr(idx)))
+        return {"xyz": xyz, "nrm": nrm, "idx": idx, "kept": kept}
 
     def knn_search(self, frame, queries=None, k=8, radius=0.0, device=False):
         """mvicp_knn_search + mvicp_knn_fetch on the stored cloud of `frame`: per query the candidates (every point, or with radius > 0 the
