@@ -371,6 +371,69 @@ int mvicp_plane_fetch_kept(mvicp_ctx* ctx, long long cap, double* xyz, double* n
  * c S_kk - s_k s_k < 0 (not the sums of one set) -> MVICP_ERR_ARG. */
 int mvicp_plane_from_moments(long long c, const long long s[3], const long long S[6], int q, const double a[3], const double m[3], double normal[3], double point[3]);
 
+/* ---- boundary points: where one stored cloud ends, exactly specified; reject pairs on them ---------------------------------------------
+ * For views that overlap only in part, source points outside the overlap find their nearest neighbour on the rim of the target and those
+ * pairs pull the pose; Rusinkiewicz & Levoy ("Efficient Variants of the ICP Algorithm", section 3.4) reject pairs that contain boundary
+ * points.  This stage names them: a point is on the boundary when, seen in its tangent plane, the directions to its neighbours leave an
+ * angular gap of at least theta (the criterion of PCL's BoundaryEstimation and Open3D's compute_boundary_points).  The result is a pure
+ * function of the stored bytes and the arguments, bit for bit, whatever order the GPU's threads run in (tests/boundref.py is the same
+ * definition in numpy and as a scalar loop): only comparisons, a per-lane OR and a count cross lanes.  All arithmetic
+ * is fp64, every operation rounded on its own, no fma; only + - x / sqrt, comparisons and negation occur.
+ *   Normals N  source 0: the frame's stored normals; source 1: the nrm of the last mvicp_estimate_normals / mvicp_fit_normals, which must
+ *              be for this frame and not dropped by an upload -- exactly as mvicp_orient_normals defines them.  A missing source ->
+ *              MVICP_ERR_STATE.
+ *   Row        row i of mvicp_knn_search(frame, NULL, max_nn, radius) in self mode, 3 <= max_nn <= 64; radius <= 0: the max_nn nearest,
+ *              radius finite and > 0: the max_nn nearest within the radius.  c_i = cnt[i], position t holds neighbour j_t,
+ *              d_t = p_{j_t} - p_i per component for t < c_i.  The point itself and exact duplicates are in the row.
+ *   Unit normal  l = sqrt((N0 N0 + N1 N1) + N2 N2).  Point i is UNDECIDED (flag 0, open 0, valid 0) unless 0 < l < +inf and c_i >= 3 (a NaN
+ *              fails the comparison).  Otherwise n = N / l, componentwise.
+ *   Tangent frame  step 4 of the mvicp_fit_normals contract, word for word: from n alone, a = the index of the smallest |n_a|, the lowest
+ *              index among equals; w = e_a x n written out: a = 0: w = (+0.0, -n2, n1); a = 1: w = (n2, +0.0, -n0); a = 2: w = (-n1, n0, +0.0).
+ *              u = w / sqrt((w0 w0 + w1 w1) + w2 w2); v = n x u: v0 = n1 u2 - n2 u1, v1 = n2 u0 - n0 u2, v2 = n0 u1 - n1 u0.
+ *   Directions  x_t = (d_t0 u0 + d_t1 u1) + d_t2 u2, y_t the same with v, r_t = sqrt(x_t x_t + y_t y_t).  Entry t is VALID iff t < c_i and
+ *              0 < r_t < +inf (the point itself, its duplicates and neighbours straight along the normal are not).  Then
+ *              ex_t = x_t / r_t, ey_t = y_t / r_t.
+ *   Sector     a valid entry s lies in t's sector iff ex_t ey_s - ey_t ex_s > 0 and ex_t ex_s + ey_t ey_s > cos_gap: s is counter-clockwise
+ *              of t by an angle in (0, theta), theta = acos(cos_gap).  The caller passes the cosine, so no acos or atan2 enters the
+ *              contract; cos_gap is finite and lies in (-1, 1); both comparisons are strict, so a gap of exactly theta is a gap.
+ *   Result     open[i] = the number of valid t whose sector holds no valid s; flag[i] = (open[i] > 0); valid[i] = the number of valid
+ *              entries; used[i] = c_i.  flag is n bytes, open / valid / used n ints each, row i the ORIGINAL index i; n = 0 gives zero rows
+ *              and is not an error.
+ *   Selection  mvicp_boundary_select: the points with flag = 1 (the boundary) or flag = 0 (the rest, UNDECIDED points among them) in
+ *              ascending original index, each with xyz, nrm (iff the frame has STORED normals, whatever the source was) and idx, as the
+ *              stored bytes.
+ * Negating N mirrors the plane (x -> -x exactly, y unchanged), which turns counter-clockwise into clockwise: a gap of at least theta
+ * stays one, so flag is unchanged up to rounding exactly at the threshold; open may differ where a row has several gaps of which a
+ * rounding decides one.  Nothing more is promised.  Left out: rows of every neighbour within a radius (a row is a wave), boundaries from
+ * range-image structure, hole filling.
+ * The call performs mvicp_knn_search(frame, NULL, max_nn, radius) internally and AFTERWARDS THAT SEARCH IS THE CONTEXT'S LAST
+ * NEIGHBOUR-SEARCH RESULT, as with mvicp_estimate_normals.  Otherwise it is HISTORY-NEUTRAL: the result lives in a stage of its own, the
+ * frame, its normals and the estimate it read are never touched; it needs the frame's hash structure (waits for pending builds and reports
+ * a failed one the same way) and NO graph; with several ranks every rank computes it locally.  It returns when the result is complete; the
+ * result lives in library-owned device memory until the next mvicp_boundary, an upload to the same frame, mvicp_set_num_frames or
+ * mvicp_destroy.  Profile scopes: those of the search, "boundary"; of the selection "boundary_compact".
+ * RETURNS THE NUMBER OF FLAGGED POINTS (>= 0) or a negative mvicp_status.
+ * Errors: NULL context, a frame index out of range, a source outside {0, 1}, max_nn outside [3, 64], a non-finite radius, a cos_gap not
+ * in (-1, 1) (a NaN is not) -> MVICP_ERR_ARG, decided before the context is touched (earlier results stay); a frame never uploaded, no
+ * normals of the asked source -> MVICP_ERR_STATE (earlier results stay). */
+long long mvicp_boundary(mvicp_ctx* ctx, int frame, int source, int max_nn, double radius, double cos_gap);
+/* Copies the last result: flag (n bytes), open / valid / used (n ints each); each may be NULL; each may be a HOST pointer or a DEVICE
+ * pointer of the context's device, decided per pointer as mvicp_voxel_fetch decides.  cap_rows = rows the destinations hold.
+ * Errors: NULL context, cap_rows < n -> MVICP_ERR_ARG; no mvicp_boundary before -> MVICP_ERR_STATE. */
+int mvicp_boundary_fetch(mvicp_ctx* ctx, long long cap_rows, unsigned char* flag, int* open, int* valid, int* used);
+/* The points of the last mvicp_boundary result with flag = 1 (boundary != 0: the boundary points) or flag = 0 (boundary == 0: the rest), in
+ * ascending original index, compacted on the device (the compaction of mvicp_outlier_filter, mvicp_cluster_select and mvicp_plane_select).
+ * The rows are the frame's stored bytes.  May be called again with the other choice; the selection lives as long as the result.
+ * RETURNS THE NUMBER OF ROWS or a negative mvicp_status.
+ * Errors: NULL context -> MVICP_ERR_ARG; no mvicp_boundary result -> MVICP_ERR_STATE. */
+long long mvicp_boundary_select(mvicp_ctx* ctx, int boundary);
+/* Copies the last selection: xyz / nrm (kept x 3 doubles: the stored bytes; nrm iff the frame has normals), idx (kept ints: original
+ * indices, ascending); each may be NULL; each may be a HOST pointer or a DEVICE pointer of the context's device, decided per pointer as
+ * mvicp_voxel_fetch decides, so a device result goes straight into mvicp_set_frame_device.  cap = rows each destination holds.
+ * Errors: NULL context, cap < kept -> MVICP_ERR_ARG; no mvicp_boundary result, no mvicp_boundary_select of it, or nrm != NULL for a
+ * frame without normals -> MVICP_ERR_STATE. */
+int mvicp_boundary_fetch_kept(mvicp_ctx* ctx, long long cap, double* xyz, double* nrm, int* idx);
+
 /* ---- neighbour search: the k nearest and / or all points within a radius, for arbitrary queries, with indices ------------
  * The search primitive of every point-cloud toolkit (search_knn, search_radius, the hybrid of the two) over one stored cloud.  The result
  * is a pure function of the inputs, bit for bit (tests/knnref.py is the same definition in numpy):

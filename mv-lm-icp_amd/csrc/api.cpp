@@ -546,7 +546,7 @@ int mvicp_create(int device, mvicp_ctx** out) try {
 static void release_stages(mvicp_ctx* c) {
   c->vox.release(); c->out.release(); c->knn.release(); c->fpfh.release();
   c->match.release(); c->cons.release(); c->coarse.release(); c->iss.release(); c->nrm.release();
-  c->ori.release(); c->agree.release(); c->clu.release(); c->plane.release();
+  c->ori.release(); c->agree.release(); c->clu.release(); c->plane.release(); c->bnd.release();
 }
 
 int mvicp_destroy(mvicp_ctx* c) try {
@@ -608,6 +608,7 @@ int mvicp_set_frame(mvicp_ctx* c, int frame, const double* xyz, const double* nr
   if (c->ori.frame == frame) c->ori.drop_result();   // (and its oriented normals)
   if (c->clu.frame == frame) c->clu.drop_result();   // (and its clusters: a selection would read the new rows)
   if (c->plane.frame == frame) c->plane.drop_result();   // (and its plane, for the same reason)
+  if (c->bnd.frame == frame) c->bnd.drop_result();   // (and its boundary points, for the same reason)
   if (f.job) { try { (void)f.job->fut.get(); } catch (...) {} f.job.reset(); }   // a build of the cloud this call replaces
   dev_free(f.pts); dev_free(f.nor); free_grid(f.grid); free_tie(f);
   f.has_grid = false; f.build_error.clear();
@@ -690,6 +691,7 @@ int mvicp_set_frame_device(mvicp_ctx* c, int frame, const double* d_xyz, const d
   if (c->ori.frame == frame) c->ori.drop_result();   // (and its oriented normals)
   if (c->clu.frame == frame) c->clu.drop_result();   // (and its clusters: a selection would read the new rows)
   if (c->plane.frame == frame) c->plane.drop_result();   // (and its plane, for the same reason)
+  if (c->bnd.frame == frame) c->bnd.drop_result();   // (and its boundary points, for the same reason)
   if (f.job) { try { (void)f.job->fut.get(); } catch (...) {} f.job.reset(); }   // a build of the cloud this call replaces
   dev_free(f.pts); dev_free(f.nor); free_grid(f.grid); free_tie(f);
   f.has_grid = false; f.build_error.clear();
@@ -1094,6 +1096,70 @@ int mvicp_plane_fetch_kept(mvicp_ctx* c, long long cap, double* xyz, double* nrm
   if (c->plane.kept == 0) return MVICP_OK;
   const size_t m = (size_t)c->plane.kept;
   const FetchPart parts[] = {{xyz, c->plane.xyz, 24 * m, "xyz"}, {nrm, c->plane.nrm, 24 * m, "nrm"}, {idx, c->plane.idx, 4 * m, "idx"}};
+  return fetch_parts(c, parts);
+} MVICP_GUARD_ABI
+
+long long mvicp_boundary(mvicp_ctx* c, int frame, int source, int max_nn, double radius, double cos_gap) try {
+  // every argument error that needs no GPU first: nothing of the context has been touched when one of them is reported
+  if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
+  if (source != 0 && source != 1) { set_error("source = %d: 0 (the frame's stored normals) or 1 (the last mvicp_estimate_normals / mvicp_fit_normals)", source); return MVICP_ERR_ARG; }
+  if (max_nn < 3 || max_nn > 64) { set_error("max_nn = %d outside [3, 64]", max_nn); return MVICP_ERR_ARG; }
+  if (!std::isfinite(radius)) { set_error("radius must be finite (<= 0: no radius)"); return MVICP_ERR_ARG; }
+  if (!(cos_gap > -1.0 && cos_gap < 1.0)) { set_error("cos_gap must lie in (-1, 1)"); return MVICP_ERR_ARG; }
+  if (frame < 0 || frame >= c->n_frames) { set_error("frame %d out of range [0,%d)", frame, c->n_frames); return MVICP_ERR_ARG; }
+  const FrameDev& f = c->frames[frame];
+  if (!f.pts) { set_error("frame %d was never uploaded", frame); return MVICP_ERR_STATE; }
+  const double* N = nullptr;
+  if (source == 0) {
+    if (f.n > 0 && !f.nor) { set_error("frame %d has no normals", frame); return MVICP_ERR_STATE; }
+    N = f.nor;
+  } else {
+    if (c->nrm.rows < 0 || c->nrm.frame != frame || c->nrm.rows != f.n) {
+      set_error("no estimated normals of frame %d: call mvicp_estimate_normals on it first (an upload to the frame drops the result)", frame);
+      return MVICP_ERR_STATE;
+    }
+    N = c->nrm.nrm;
+  }
+  MV_CHECK(bind(c));
+  MV_CHECK(finish_builds(c));
+  const long long flagged = boundary_points(c, f, frame, N, max_nn, radius, radius > 0.0 ? sqrt_bound(radius) : 0.0, cos_gap);
+  if (c->profile) prof_collect_lazy(c);
+  return flagged;
+} MVICP_GUARD_ABI
+
+int mvicp_boundary_fetch(mvicp_ctx* c, long long cap_rows, unsigned char* flag, int* open, int* valid, int* used) try {
+  if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
+  if (c->bnd.n < 0) { set_error("no boundary result: call mvicp_boundary first"); return MVICP_ERR_STATE; }
+  if (cap_rows < c->bnd.n) { set_error("cap_rows %lld < %lld rows", cap_rows, c->bnd.n); return MVICP_ERR_ARG; }
+  if (c->bnd.n == 0) return MVICP_OK;
+  const size_t n = (size_t)c->bnd.n;
+  const FetchPart parts[] = {{flag, c->bnd.flag, n, "flag"}, {open, c->bnd.open, 4 * n, "open"}, {valid, c->bnd.valid, 4 * n, "valid"}, {used, c->bnd.used, 4 * n, "used"}};
+  return fetch_parts(c, parts);
+} MVICP_GUARD_ABI
+
+long long mvicp_boundary_select(mvicp_ctx* c, int boundary) try {
+  if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
+  if (c->bnd.n < 0) { set_error("no boundary result: call mvicp_boundary first"); return MVICP_ERR_STATE; }
+  const int frame = c->bnd.frame;
+  if (frame < 0 || frame >= c->n_frames || c->frames[frame].n != c->bnd.n || (c->bnd.n > 0 && !c->frames[frame].pts)) {
+    set_error("the frame of the boundary result is gone: call mvicp_boundary again");
+    return MVICP_ERR_STATE;
+  }
+  MV_CHECK(bind(c));
+  const long long kept = boundary_select(c, c->frames[frame], boundary);
+  if (c->profile) prof_collect_lazy(c);
+  return kept;
+} MVICP_GUARD_ABI
+
+int mvicp_boundary_fetch_kept(mvicp_ctx* c, long long cap, double* xyz, double* nrm, int* idx) try {
+  if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
+  if (c->bnd.n < 0) { set_error("no boundary result: call mvicp_boundary first"); return MVICP_ERR_STATE; }
+  if (c->bnd.kept < 0) { set_error("no selection: call mvicp_boundary_select first"); return MVICP_ERR_STATE; }
+  if (cap < c->bnd.kept) { set_error("cap %lld < %lld kept rows", cap, c->bnd.kept); return MVICP_ERR_ARG; }
+  if (nrm && !c->bnd.has_normals) { set_error("the frame of the boundary result has no normals"); return MVICP_ERR_STATE; }
+  if (c->bnd.kept == 0) return MVICP_OK;
+  const size_t m = (size_t)c->bnd.kept;
+  const FetchPart parts[] = {{xyz, c->bnd.xyz, 24 * m, "xyz"}, {nrm, c->bnd.nrm, 24 * m, "nrm"}, {idx, c->bnd.idx, 4 * m, "idx"}};
   return fetch_parts(c, parts);
 } MVICP_GUARD_ABI
 

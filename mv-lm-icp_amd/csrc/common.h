@@ -115,7 +115,7 @@ struct ProfEntry {
 
 // ---- buffers and results a stage of the library owns ---------------------------------------------------------------------------------
 // A stage (voxel grid, outlier filter, neighbour search, FPFH, descriptor matching, consensus, batched coarse poses, ISS keypoints, estimated
-// normals, oriented normals, clusters, the dominant plane) keeps its LAST result on the context until the caller has fetched it.  Ownership, stated once for all twelve: the stage's struct below holds
+// normals, oriented normals, clusters, the dominant plane, boundary points) keeps its LAST result on the context until the caller has fetched it.  Ownership, stated once for all thirteen: the stage's struct below holds
 // buffers of its own (so that a call touches nothing a search, a queued evaluation, the census or another stage uses), kept between
 // calls and grown on demand, the result arrays as views into them, and the sizes / flags, whose defaults mean "no result".  A call marks
 // its result as gone when it starts (a failed call leaves none behind) and sets it after its last wait; the result then lives until the
@@ -264,6 +264,17 @@ struct PlaneStage {
   void drop_result() { n = -1; H = -1; kept = -1; frame = -1; has_normals = 0; }
   void release() { dev.release(); tmp.release(); pin.release(); *this = PlaneStage(); }
 };
+// boundary.hip.  dev: one arena [control | flag bytes | open | valid | used | flag | rank | xyz | nrm | idx], tmp: rocprim storage, pin: the host
+// copy of the control block.  frame: the slot the result was computed for (mvicp_boundary_select reads its stored rows); an upload to that
+// slot drops the result.  kept: the rows of the last mvicp_boundary_select of this result (< 0: none)
+struct BoundaryStage {
+  DevBuf dev, tmp; PinBuf pin;
+  unsigned char* flag = nullptr; int* open = nullptr; int* valid = nullptr; int* used = nullptr;
+  double* xyz = nullptr; double* nrm = nullptr; int* idx = nullptr;
+  long long n = -1, kept = -1; int frame = -1, has_normals = 0;   // n < 0: none
+  void drop_result() { n = -1; kept = -1; frame = -1; has_normals = 0; }
+  void release() { dev.release(); tmp.release(); pin.release(); *this = BoundaryStage(); }
+};
 // orient.hip (mvicp_normal_agreement).  dev: [poses | per-edge pointer tables | per-edge counts | pos | neg], pin: the host copy of pos | neg
 struct AgreementStage {
   DevBuf dev; PinBuf pin;
@@ -407,6 +418,7 @@ struct mvicp_ctx {
   mvicp::AgreementStage agree;
   mvicp::ClusterStage clu;
   mvicp::PlaneStage plane;
+  mvicp::BoundaryStage bnd;
   std::vector<char> src_fixed;     // E: the edge's source frame was fixed in the last mvicp_correspond (0 before the first): mvicp_normal_agreement skips it
 
   // cached small tables
@@ -504,6 +516,14 @@ int plane_segment(mvicp_ctx* c, const FrameDev& f, int frame, long long H, unsig
 // plane.hip: the rows of f (the frame of the last plane_segment, unchanged since: c->plane.n == f.n >= 0) with flag == (inliers ? 1 : 0),
 // compacted in ascending original index into c->plane.  Returns the rows kept or a negative status.  Waits for the stream once.
 long long plane_select(mvicp_ctx* c, const FrameDev& f, int inliers);
+// boundary.hip: the boundary points of frame f = c->frames[frame] (valid, uploaded, structures built) by the normals N (n x 3 doubles on the
+// device: the frame's own or the last estimate's; unread when n == 0); 3 <= max_nn <= 64, B2 = sqrt_bound(radius) when radius > 0, cos_gap in
+// (-1, 1).  Runs knn_search in self mode (that search stays the context's last) and leaves the result on the context (c->bnd).  Returns the
+// number of flagged points or a negative status.  Waits for the stream; otherwise history-neutral.
+long long boundary_points(mvicp_ctx* c, const FrameDev& f, int frame, const double* N, int max_nn, double radius, double B2, double cos_gap);
+// boundary.hip: the rows of f (the frame of the last boundary_points, unchanged since: c->bnd.n == f.n >= 0) with flag == (boundary ? 1 : 0),
+// compacted in ascending original index into c->bnd.  Returns the rows kept or a negative status.  Waits for the stream once.
+long long boundary_select(mvicp_ctx* c, const FrameDev& f, int boundary);
 // knn.hip: the neighbourhoods of m queries (host or device memory, as `queries_on_device` says) or, queries == null, of the cloud's own
 // points, in frame f (valid, uploaded, structures built); 0 <= k <= 64, k == 0 needs radius > 0; B2 = sqrt_bound(radius) when radius > 0.
 // The result stays on the context (c->knn).  Returns the number of entries or a negative status.  Waits for the stream; history-neutral.

@@ -1,4 +1,4 @@
-// The order-preserving compaction of the stages that select rows of a stored cloud (outlier.hip, cluster.hip, plane.hip): after an
+// The order-preserving compaction of the stages that select rows of a stored cloud (outlier.hip, cluster.hip, plane.hip, boundary.hip): after an
 // exclusive scan of the 0 / 1 flags over the original index, one lane per point stores its row at its rank, so the kept rows come out
 // in ascending original index.  Plain vector stores only; the last lane leaves the number kept.
 #pragma once
@@ -27,6 +27,14 @@ __global__ __launch_bounds__(kCompactRowsThreads) void compact_rows_kernel(const
     if (LAB) klabel[o] = label[i];
   }
   if (i == n - 1) *kept = o + f;
+}
+
+// flag[i] = (flags[i] == want) as an int: what the scan and the compaction read, from a stage's flag bytes (plane.hip, boundary.hip).  A
+// template only so that the header may define it
+template <int THREADS = kCompactRowsThreads>
+__global__ __launch_bounds__(THREADS) void rows_wanted_kernel(const unsigned char* __restrict__ flags, int n, int want, int* __restrict__ flag) {
+  const int i = blockIdx.x * THREADS + threadIdx.x;
+  if (i < n) flag[i] = flags[i] == want ? 1 : 0;
 }
 
 // the launch: flag and pos are n ints each, pos = the exclusive scan of flag

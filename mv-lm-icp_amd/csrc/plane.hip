@@ -234,11 +234,6 @@ __global__ __launch_bounds__(kThreads) void plane_final_kernel(const double* __r
   }
 }
 
-__global__ __launch_bounds__(kThreads) void plane_want_kernel(const unsigned char* __restrict__ flags, int n, int want, int* __restrict__ flag) {
-  const int i = blockIdx.x * kThreads + threadIdx.x;
-  if (i < n) flag[i] = flags[i] == want ? 1 : 0;
-}
-
 // the arena of H hypotheses over n points: [control | count | accepted h | flags | flag | rank | xyz | nrm | idx]
 struct Arena {
   size_t count, hidx, flags, flag, pos, xyz, nrm, idx, bytes;
@@ -384,7 +379,7 @@ long long plane_select(mvicp_ctx* c, const FrameDev& f, int inliers) {
   S.idx = reinterpret_cast<int*>(D + A.idx);
   {
     ProfScope ps(c, "plane_compact", (f.nor ? 109.0 : 61.0) * n);
-    hipLaunchKernelGGL(plane_want_kernel, dim3(grid_of(n, kThreads)), dim3(kThreads), 0, st, S.flags, n, inliers ? 1 : 0, flag);
+    hipLaunchKernelGGL(rows_wanted_kernel<>, dim3(grid_of(n, kCompactRowsThreads)), dim3(kCompactRowsThreads), 0, st, S.flags, n, inliers ? 1 : 0, flag);
     size_t tb = S.tmp.cap;
     MV_HIP(rocprim::exclusive_scan(S.tmp.p, tb, flag, pos, 0, NN, rocprim::plus<int>(), st));
     compact_rows<false>(st, f.pts, f.nor, nullptr, flag, pos, n, S.xyz, S.nrm, S.idx, nullptr, &d_ctl->kept);

@@ -266,6 +266,46 @@ void Session::correspond(std::vector<std::shared_ptr<Frame>>& frames, float thre
   }
 }
 
+std::vector<long long> Session::rejectBoundary(std::vector<std::shared_ptr<Frame>>& frames, const std::vector<std::vector<unsigned char>>& masks) {
+  if (!ctx || !graph_bound || last_poses.empty()) throw std::runtime_error("mvicp: rejectBoundary needs the round's search before it");
+  if (!copy_back) throw std::runtime_error("mvicp: rejectBoundary filters the Frame's lists: it needs copy_back");
+  if (masks.size() != frames.size()) throw std::runtime_error("mvicp: rejectBoundary needs one mask per frame");
+  for (size_t j = 0; j < frames.size(); ++j)
+    if (!masks[j].empty() && masks[j].size() != frames[j]->pts.size()) throw std::runtime_error("mvicp: rejectBoundary: a mask has one byte per point of its frame");
+  std::vector<long long> dropped;
+  std::vector<int> first, second;
+  bool any = false;
+  size_t e = 0;
+  for (size_t i = 0; i < frames.size(); ++i) {
+    Frame& f = *frames[i];
+    for (OutgoingEdge& edge : f.neighbours) {
+      const std::vector<unsigned char>& m = masks[(size_t)edge.neighbourIdx];
+      std::vector<Correspondance>& L = edge.correspondances;
+      size_t w = 0;
+      if (!f.fixed && !m.empty()) {   // (a fixed frame is not searched: computeClosestPointsToNeighbours left its lists alone)
+        for (size_t r = 0; r < L.size(); ++r)
+          if (!m[(size_t)L[r].second]) L[w++] = L[r];
+      } else {
+        w = L.size();
+      }
+      const long long d = (long long)(L.size() - w);
+      if (d) {
+        L.resize(w);
+        first.resize(w); second.resize(w);
+        for (size_t r = 0; r < w; ++r) { first[r] = L[r].first; second[r] = L[r].second; }
+        check(mvicp_set_correspondences(ctx, (int)e, (int)w, first.data(), second.data(), weights[e]));
+        if (e < held.size()) held[e] = Held();   // (the library's list has a new epoch and the Frame's vector is not a copy of the mapped triples)
+        any = true;
+      }
+      dropped.push_back(d);
+      ++e;
+    }
+  }
+  // an installed list ends the mapped triples and the cached round: the next correspond() searches again and maps anew
+  if (any) { last_poses.clear(); corr = nullptr; corr_off = nullptr; }
+  return dropped;
+}
+
 void Session::optimize(std::vector<std::shared_ptr<Frame>>& frames, int param, bool pointToPlane, bool robust, mvicp_summary* out) {
   optimize(frames, param, pointToPlane ? MVICP_METRIC_PLANE : MVICP_METRIC_POINT, robust, out);
 }
@@ -619,6 +659,19 @@ std::shared_ptr<Frame> Frame::removePlane(double tau, long long hypotheses, unsi
   if (m) check(mvicp_plane_fetch_kept(c, m, out->pts[0].data(), out->nor.empty() ? nullptr : out->nor[0].data(), nullptr));
   if (result) *result = R;
   return out;
+}
+
+std::vector<unsigned char> Frame::boundaryPoints(int max_nn, double radius, double cos_gap) {
+  std::vector<unsigned char> flag;
+  if (pts.empty()) return flag;
+  if (nor.size() != pts.size()) throw std::runtime_error("mvicp: boundaryPoints needs normals");
+  int slot = 0;
+  mvicp_ctx* c = Session::get().query_context(this, &slot, true);
+  const long long flagged = mvicp_boundary(c, slot, 0, max_nn, radius, cos_gap);
+  if (flagged < 0) check((int)flagged);
+  flag.assign(pts.size(), 0);
+  check(mvicp_boundary_fetch(c, (long long)flag.size(), flag.data(), nullptr, nullptr, nullptr));
+  return flag;
 }
 
 std::vector<int> Frame::issKeypoints(double salient_radius, double non_max_radius, double gamma21, double gamma32, int min_neighbors) {

@@ -122,6 +122,11 @@ class Frame {
   // --plane_axis / --plane_cos).
   std::shared_ptr<Frame> removePlane(double tau, long long hypotheses = 1024, unsigned long long seed = 0, const double* axis = nullptr, double cos_min = 0.0,
                                      bool keep_plane = false, mvicp_plane_result* result = nullptr);
+  // The boundary points of this frame (no counterpart in the reference): mvicp_boundary on this cloud and its `nor` as they are stored
+  // (source 0) -- a point is flagged when, in its tangent plane, the directions to its max_nn nearest neighbours (radius > 0: within it)
+  // leave a gap of at least acos(cos_gap) -> one byte per point, 1 = boundary.  The frame needs normals.  Runs in the context
+  // Session::query_context finds for this frame (bin/multiview --reject_boundary / --boundary_nn / --boundary_radius / --boundary_cos).
+  std::vector<unsigned char> boundaryPoints(int max_nn = 30, double radius = 0.0, double cos_gap = -0.5);
   // The ISS keypoints of this frame (no counterpart in the reference): mvicp_iss_keypoints on this cloud as it is stored -> the indices
   // of the keypoints, ascending.  Runs in the context Session::query_context finds for this frame (bin/multiview --feat_keypoints).
   std::vector<int> issKeypoints(double salient_radius, double non_max_radius, double gamma21 = 0.975, double gamma32 = 0.975, int min_neighbors = 5);
@@ -219,6 +224,15 @@ struct Session {
   // bumped `version`: the next bind uploads them).  `flipped` receives one flag per frame.  Returns the number of components of the sign
   // graph (more than one is reported, not repaired).
   int orientFrames(std::vector<std::shared_ptr<Frame>>& frames, float thresh, int min_count = 0, std::vector<unsigned char>* flipped = nullptr);
+  // Rejects the pairs that end on a flagged point of their target (Rusinkiewicz & Levoy 2001, section 3.4: for views that overlap only in
+  // part), AFTER every frame's computeClosestPointsToNeighbours of a round and BEFORE its solve, with copy_back on: masks[j] is one byte per
+  // point of frames[j] (Frame::boundaryPoints; an empty mask flags nothing).  Entries whose `second` is flagged are erased from
+  // frames[i]->neighbours[k].correspondances, in their order, and every list that lost an entry is installed with
+  // mvicp_set_correspondences at the searched weight, so that the solve sees what the Frame holds.  The installed lists are explicit (their
+  // distances read 0 in the library) and have a new epoch; the session forgets the round's search and what it held of the changed lists,
+  // so the next computeClosestPointsToNeighbours searches again -- like a first search, the temporal cache is gone -- and refills.
+  // Returns the pairs dropped per edge, in edge order.
+  std::vector<long long> rejectBoundary(std::vector<std::shared_ptr<Frame>>& frames, const std::vector<std::vector<unsigned char>>& masks);
   void optimize(std::vector<std::shared_ptr<Frame>>& frames, int param, bool pointToPlane, bool robust, mvicp_summary* sm = nullptr);
   // the same with the objective named (MVICP_METRIC_SYMMETRIC needs normals on every frame, oriented consistently)
   void optimize(std::vector<std::shared_ptr<Frame>>& frames, int param, mvicp_metric metric, bool robust, mvicp_summary* sm = nullptr);

@@ -68,6 +68,14 @@
 // and before round 0: Session::orientFrames (one search, the agreement of the normals over its lists, a spanning forest over the frames;
 // the frames it flips are negated).  One line per frame, `normal orientation: frame i trees t`, and one line
 // `normal orientation: C component(s), flipped f0 f1 ..` (printed with --quiet too).
+// --reject_boundary [--boundary_nn K] [--boundary_radius R] [--boundary_cos=C] (default off; K = 30, R = 0 = no radius, C = -0.5; a negative C needs the = form): pairs whose
+// target is a boundary point of its cloud are dropped every round between the search and the solve (Rusinkiewicz & Levoy 2001, section 3.4:
+// for views that overlap only in part, where source points outside the overlap find their nearest neighbour on the rim of the target).  The
+// masks are Frame::boundaryPoints(K, R, C) -- mvicp_boundary on the frame's stored normals: a gap of at least acos(C) between the directions
+// to the K nearest neighbours -- computed once per frame after the pre-processing flags (and once per coarse copy); Session::rejectBoundary
+// applies them.  One line per frame, `boundary: frame i flagged a of b`, and one per round, `boundary: round r dropped n pairs` (printed with
+// --quiet too).  Refused when a frame has no normals after pre-processing, when C is outside (-1, 1) and with --copyback 0 (the Frame's lists
+// are what is filtered).  The installed lists are explicit, so every round searches like a first round: the temporal cache is lost.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -159,6 +167,11 @@ int main(int argc, char** argv) {
   if (!F.s("normals_orient", "").empty() && F.s("normals_orient", "") != "mst") { std::cerr << "--normals_orient must be mst" << std::endl; return 1; }
   if (F.i("normals_fit", 0) != 0 && F.i("normals_fit", 0) != 2 && F.i("normals_fit", 0) != 3) { std::cerr << "--normals_fit must be 2 or 3" << std::endl; return 1; }
   if (F.i("normals_fit", 0) != 0 && F.i("normals_nn", 0) <= 0) { std::cerr << "--normals_fit needs --normals_nn K" << std::endl; return 1; }
+  const bool reject_boundary = F.b("reject_boundary", false);
+  const int boundary_nn = F.i("boundary_nn", 30);
+  const double boundary_radius = F.f("boundary_radius", 0.0), boundary_cos = F.f("boundary_cos", -0.5);
+  if (reject_boundary && !(boundary_cos > -1.0 && boundary_cos < 1.0)) { std::cerr << "--boundary_cos must lie in (-1, 1)" << std::endl; return 1; }
+  if (reject_boundary && !Session::get().copy_back) { std::cerr << "--reject_boundary filters the frames' lists: it needs --copyback 1" << std::endl; return 1; }
   std::vector<std::shared_ptr<Frame>> frames;
   try {
     loadFrames(F, frames, dir);
@@ -240,6 +253,21 @@ int main(int argc, char** argv) {
     if (!quiet)
       for (size_t i = 0; i < frames.size(); ++i) std::cout << "coarse frame " << i << ": " << coarse[i]->pts.size() << " of " << frames[i]->pts.size() << " points" << std::endl;
   }
+  std::vector<std::vector<unsigned char>> masks, coarse_masks;   // --reject_boundary: one byte per point of every frame (and of every coarse copy)
+  if (reject_boundary) {
+    for (size_t i = 0; i < frames.size(); ++i)
+      if (frames[i]->nor.size() != frames[i]->pts.size()) { std::cerr << "--reject_boundary: frame " << i << " has no normals" << std::endl; return 1; }
+    try {
+      Session::get().ensure_uploaded(frames);   // (every frame is found in the session: no context of its own per frame)
+      for (size_t i = 0; i < frames.size(); ++i) {
+        masks.push_back(frames[i]->boundaryPoints(boundary_nn, boundary_radius, boundary_cos));
+        size_t flagged = 0;
+        for (unsigned char b : masks[i]) flagged += b;
+        std::cout << "boundary: frame " << i << " flagged " << flagged << " of " << masks[i].size() << std::endl;
+      }
+      for (auto& f : coarse) coarse_masks.push_back(f->boundaryPoints(boundary_nn, boundary_radius, boundary_cos));
+    } catch (const std::exception& ex) { std::cerr << ex.what() << std::endl; return 2; }
+  }
   auto poses_to_full = [&]() { for (size_t i = 0; i < coarse.size(); ++i) frames[i]->pose = coarse[i]->pose; };
   double wall_search = 0.0, wall_solve = 0.0;
   std::ofstream trace;
@@ -253,6 +281,11 @@ int main(int argc, char** argv) {
       const unsigned long long c0 = Session::get().edges_copied, s0 = Session::get().edges_skipped;
       const auto t0 = std::chrono::steady_clock::now();
       for (auto& f : cur) f->computeClosestPointsToNeighbours(&cur, cutoff);
+      if (reject_boundary) {
+        long long total = 0;
+        for (long long d : Session::get().rejectBoundary(cur, r < coarse_rounds ? coarse_masks : masks)) total += d;
+        std::cout << "boundary: round " << r << " dropped " << total << " pairs" << std::endl;
+      }
       const auto t1 = std::chrono::steady_clock::now();
       if (trace.is_open())
         for (size_t i = 0; i < cur.size(); ++i)

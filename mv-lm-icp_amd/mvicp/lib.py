@@ -23,6 +23,7 @@ SYMBOLS = [
     "mvicp_outlier_filter", "mvicp_outlier_fetch", "mvicp_outlier_threshold", "mvicp_cache_allowance",
     "mvicp_cluster", "mvicp_cluster_fetch", "mvicp_cluster_keep_rule", "mvicp_cluster_select", "mvicp_cluster_fetch_kept",
     "mvicp_segment_plane", "mvicp_plane_fetch", "mvicp_plane_select", "mvicp_plane_fetch_kept", "mvicp_plane_from_moments",
+    "mvicp_boundary", "mvicp_boundary_fetch", "mvicp_boundary_select", "mvicp_boundary_fetch_kept",
     "mvicp_knn_search", "mvicp_knn_fetch", "mvicp_fpfh", "mvicp_fpfh_fetch", "mvicp_iss_keypoints", "mvicp_iss_fetch",
     "mvicp_estimate_normals", "mvicp_normals_fetch", "mvicp_normals_adopt", "mvicp_fit_normals", "mvicp_normals_fit_fetch",
     "mvicp_orient_normals", "mvicp_orient_fetch", "mvicp_orient_adopt", "mvicp_normal_agreement", "mvicp_signs_from_agreement", "mvicp_negate_normals",
@@ -170,6 +171,12 @@ def load_library(path=None):
     lib.mvicp_plane_select.restype = C.c_longlong
     lib.mvicp_plane_fetch_kept.argtypes = [vp, C.c_longlong, vp, vp, vp]
     lib.mvicp_plane_from_moments.argtypes = [C.c_longlong, vp, vp, C.c_int, dp, dp, dp, dp]
+    lib.mvicp_boundary.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double]
+    lib.mvicp_boundary.restype = C.c_longlong
+    lib.mvicp_boundary_fetch.argtypes = [vp, C.c_longlong, vp, vp, vp, vp]
+    lib.mvicp_boundary_select.argtypes = [vp, C.c_int]
+    lib.mvicp_boundary_select.restype = C.c_longlong
+    lib.mvicp_boundary_fetch_kept.argtypes = [vp, C.c_longlong, vp, vp, vp]
     lib.mvicp_cache_allowance.argtypes = [dp, dp, dp, dp, C.c_double, dp]
     lib.mvicp_knn_search.argtypes = [vp, C.c_int, vp, C.c_longlong, C.c_int, C.c_double]
     lib.mvicp_knn_search.restype = C.c_longlong
@@ -328,6 +335,22 @@ def plane_from_moments(c, s, S, q, a, m):
     normal, point = np.zeros(3), np.zeros(3)
     _check(lib, lib.mvicp_plane_from_moments(int(c), s.ctypes.data_as(C.c_void_p), S.ctypes.data_as(C.c_void_p), int(q), _dp(a), _dp(m), _dp(normal), _dp(point)))
     return normal, point
+
+
+def reject_by_mask(first, second, src_mask, dst_mask):
+    """The pairs (first[i], second[i]) neither of whose ends is flagged, in their order: src_mask / dst_mask are per-point flags of the
+    source / target cloud (nonzero = reject every pair on that point; the flag of Engine.boundary, say), either may be None.
+    -> (first, second) int32.  Pure numpy; the filter of Engine.reject_correspondences."""
+    first = np.ascontiguousarray(first, dtype=np.int32).reshape(-1)
+    second = np.ascontiguousarray(second, dtype=np.int32).reshape(-1)
+    if len(first) != len(second):
+        raise ValueError("first and second differ in length")
+    keep = np.ones(len(first), dtype=bool)
+    if src_mask is not None:
+        keep &= np.asarray(src_mask).reshape(-1)[first] == 0
+    if dst_mask is not None:
+        keep &= np.asarray(dst_mask).reshape(-1)[second] == 0
+    return np.ascontiguousarray(first[keep]), np.ascontiguousarray(second[keep])
 
 
 def cache_allowance(pose_src_old, pose_dst_old, pose_src, pose_dst, max_norm):
@@ -895,6 +918,65 @@ class Engine:
         ready()
         _check(self.lib, self.lib.mvicp_plane_fetch_kept(self.h, kept, ptr(xyz), ptr(nrm), ptr(idx)))
         return {"xyz": xyz, "nrm": nrm, "idx": idx, "kept": kept}
+
+    def boundary(self, frame, max_nn=30, radius=0.0, cos_gap=-0.5, source=0, device=False):
+        """mvicp_boundary + mvicp_boundary_fetch on the stored cloud of `frame`: a point is flagged when, in its tangent plane (normals of
+        `source`: 0 the frame's stored ones, 1 the last estimate_normals / fit_normals of this frame), the directions to the neighbours of
+        its row (the max_nn nearest, within `radius` if > 0) leave a gap of at least acos(cos_gap) -> dict(flag (n,) uint8, open (n,) int32
+        = the directions that look into such a gap, valid (n,) int32 = the directions of the row, used (n,) int32 = the row's length,
+        boundary = the number flagged).  device=True: torch tensors on the engine's GPU.  Leaves its search as the last neighbour search;
+        needs no graph; otherwise history-neutral."""
+        flagged = int(_check(self.lib, self.lib.mvicp_boundary(self.h, int(frame), int(source), int(max_nn), float(radius), float(cos_gap))))
+        n = int(self.npts[frame])
+        mk, ptr, ready, f64, i32, i64, u8 = self._result_arrays(device)
+        flag, opn, valid, used = mk((n,), u8), mk((n,), i32), mk((n,), i32), mk((n,), i32)
+        ready()
+        _check(self.lib, self.lib.mvicp_boundary_fetch(self.h, n, ptr(flag), ptr(opn), ptr(valid), ptr(used)))
+        return {"flag": flag, "open": opn, "valid": valid, "used": used, "boundary": flagged}
+
+    def boundary_select(self, boundary=True, device=False):
+        """mvicp_boundary_select + mvicp_boundary_fetch_kept on the last boundary() result: the flagged points (boundary) or the rest, in
+        ascending original index -> dict(xyz (kept,3), nrm (kept,3) or None, idx (kept,) int32, kept).  device=True: torch tensors on
+        the engine's GPU (xyz / nrm ready for set_frame_device)."""
+        kept = int(_check(self.lib, self.lib.mvicp_boundary_select(self.h, 1 if boundary else 0)))
+        mk, ptr, ready, f64, i32, i64, u8 = self._result_arrays(device)
+        xyz, nrm, idx = mk((kept, 3), f64), mk((kept, 3), f64), mk((kept,), i32)
+        ready()
+        # (the C call has no record that says whether the frame has stored normals: asking for them answers it -- a refusal is MVICP_ERR_STATE
+        # and writes nothing; with no rows nothing is written either way, so any non-NULL pointer asks)
+        st = self.lib.mvicp_boundary_fetch_kept(self.h, kept, None, ptr(nrm) if kept else C.c_void_p(8), None)
+        if st == -3:
+            nrm = None
+        else:
+            _check(self.lib, st)
+        _check(self.lib, self.lib.mvicp_boundary_fetch_kept(self.h, kept, ptr(xyz), None, ptr(idx)))
+        return {"xyz": xyz, "nrm": nrm, "idx": idx, "kept": kept}
+
+    def reject_correspondences(self, dst_masks, src_masks=None):
+        """Drops from every list this engine owns the pairs that end on a flagged point: per owned edge e = (s, d) get_correspondences(e),
+        reject_by_mask with src_masks[s] / dst_masks[d] (sequences indexed by frame; an entry, or src_masks itself, may be None), then
+        set_correspondences(e, kept, weight = the weight the last correspond() returned for e).  -> (E,) int32, the pairs dropped per edge
+        (0 for edges of other ranks).  The default rejects on the target side only (Rusinkiewicz & Levoy 2001, section 3.4, for partial
+        overlap; rejecting on the source side as well did not help on the project's test pair).
+        A host composition of existing calls, with their consequences: the lists are EXPLICIT until the next correspond(); their stored
+        distances read 0; installing them gives every owned edge a new epoch, drops the evaluation the search queued ahead and invalidates
+        the temporal NN cache, so the next search runs like a first search.  On a sharded context the header's rule for explicit lists
+        applies: set the option "spec_eval" to 0 on every rank."""
+        rb = getattr(self, "_rb", None)
+        if rb is None:
+            raise MvicpError("reject_correspondences needs a correspond() before it")
+        weights = rb["weights"]
+        owner = edge_owner([self.npts[s] for s in self.src], self.world) if self.world > 1 else np.zeros(self.E, dtype=np.int32)
+        dropped = np.zeros(self.E, dtype=np.int32)
+        for e in range(self.E):
+            if owner[e] != self.rank:
+                continue
+            s, d = int(self.src[e]), int(self.dst[e])
+            first, second, _ = self.get_correspondences(e)
+            kf, ks = reject_by_mask(first, second, None if src_masks is None else src_masks[s], None if dst_masks is None else dst_masks[d])
+            self.set_correspondences(e, kf, ks, weights[e])
+            dropped[e] = len(first) - len(kf)
+        return dropped
 
     def knn_search(self, frame, queries=None, k=8, radius=0.0, device=False):
         """mvicp_knn_search + mvicp_knn_fetch on the stored cloud of `frame`: per query the candidates (every point, or with radius > 0 the
