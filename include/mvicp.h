@@ -434,6 +434,45 @@ long long mvicp_boundary_select(mvicp_ctx* ctx, int boundary);
  * frame without normals -> MVICP_ERR_STATE. */
 int mvicp_boundary_fetch_kept(mvicp_ctx* ctx, long long cap, double* xyz, double* nrm, int* idx);
 
+/* ---- reject masks: pairs that touch flagged points are dropped INSIDE the search ------------------------------------------------
+ * A frame may carry a per-point reject mask (n bytes, ORIGINAL point order, nonzero = reject) that applies when the frame is the target
+ * of an edge (MVICP_REJECT_AS_TARGET), its source (MVICP_REJECT_AS_SOURCE) or both.  A MASKED SEARCH is mvicp_correspond with this
+ * acceptance test for query k of edge (s, d) whose nearest neighbour is j (original indices):
+ *     accepted  <=>  j >= 0  &&  sqrt(d2) < thresh  &&  !(src_mask_s && src_mask_s[k])  &&  !(dst_mask_d && dst_mask_d[j])
+ * The nearest neighbour itself is unchanged: a query whose neighbour is flagged is DROPPED, not re-matched to the next unflagged point
+ * (Rusinkiewicz & Levoy 2001, section 3.4).  Counts, lists, stored distances, the upper median and the weight (float)(1.5 * median)
+ * follow from the accepted set: they are what the unmasked search gives over the kept pairs alone (tests/rejectref.py is this
+ * statement in numpy, and the search equals it byte for byte).  THE SCALE THEREFORE DIFFERS FROM THE HOST COMPOSITION (fetch the list,
+ * filter it, mvicp_set_correspondences with the weight the search returned), which keeps the weight of the UNFILTERED list: here the
+ * median is taken over what is kept -- the reference's rule applied to the list that exists.
+ * The lists stay SEARCHED lists: the temporal NN cache, the in-place list upkeep, the fixed-point shortcuts and the queued evaluations
+ * all keep working, and no list crosses the bus.  Everything downstream (the operand stream, the select, the export,
+ * mvicp_normal_agreement, every objective) reads the filtered list.  Explicit lists (mvicp_set_correspondences) are never filtered.
+ * With no mask on any frame every call behaves exactly as without this interface.
+ * Setting, changing or clearing the mask of frame f voids the queued evaluations and makes every owned edge whose target (role TARGET)
+ * or source (role SOURCE) is f re-compact and re-gather its list in the NEXT search, which gives it a new epoch; until that search the
+ * lists on the device are the last search's.  The temporal NN cache stays valid: it is a fact about nearest neighbours, not about
+ * lists.  Installing the same bytes again counts as a change.  mvicp_set_frame, mvicp_set_frame_device and mvicp_set_num_frames drop
+ * the frame's mask with its cloud.
+ * Sharded contexts: lists belong to their owner and counts are exchanged as before; THE CALLER OWES THE SAME MASKS ON EVERY RANK
+ * BEFORE THE SAME SEARCH.  Unlike explicit lists, masks do not turn the queued evaluation ("spec_eval") off. */
+enum { MVICP_REJECT_AS_TARGET = 1, MVICP_REJECT_AS_SOURCE = 2 };
+/* mask: n bytes (n = the frame's points) in original point order, a HOST pointer or a DEVICE pointer of the context's device (decided
+ * as mvicp_voxel_fetch decides); copied before the call returns.  mask NULL or roles == 0 clears the frame's mask.  Needs the frame's
+ * structures (waits for pending builds) and NO graph.
+ * Errors: NULL context, a frame out of range, roles outside [0, 3], a mask on another device -> MVICP_ERR_ARG; a frame never uploaded
+ * or without structures -> MVICP_ERR_STATE.  All are decided before anything changes. */
+int mvicp_set_reject_mask(mvicp_ctx* ctx, int frame, const unsigned char* mask, int roles);
+/* The flags of the last mvicp_boundary become its frame's reject mask without leaving the device (the analogue of
+ * mvicp_normals_adopt); roles == 0 clears that frame's mask.
+ * Errors: NULL context, roles outside [0, 3] -> MVICP_ERR_ARG; no boundary result, or the frame was uploaded again since (the upload
+ * dropped the result) -> MVICP_ERR_STATE, with nothing changed. */
+int mvicp_boundary_adopt(mvicp_ctx* ctx, int roles);
+/* Reads the frame's mask back: the caller's bytes in original order into out (HOST or DEVICE pointer; NULL: only the size), *roles
+ * (may be NULL) = its roles.  RETURNS n, or 0 with *roles = 0 when the frame has no mask.
+ * Errors: NULL context, a frame out of range, cap < n with out != NULL -> MVICP_ERR_ARG. */
+long long mvicp_get_reject_mask(mvicp_ctx* ctx, int frame, unsigned char* out, long long cap, int* roles);
+
 /* ---- neighbour search: the k nearest and / or all points within a radius, for arbitrary queries, with indices ------------
  * The search primitive of every point-cloud toolkit (search_knn, search_radius, the hybrid of the two) over one stored cloud.  The result
  * is a pure function of the inputs, bit for bit (tests/knnref.py is the same definition in numpy):

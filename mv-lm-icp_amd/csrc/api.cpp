@@ -1163,6 +1163,96 @@ int mvicp_boundary_fetch_kept(mvicp_ctx* c, long long cap, double* xyz, double* 
   return fetch_parts(c, parts);
 } MVICP_GUARD_ABI
 
+// What follows a new, changed or cleared reject mask of `frame`; roles = the old and the new roles together.  Modelled on normals_changed:
+// queued evaluations are void, and every owned edge the mask bears on loses its list (list_valid: the next search re-compacts and re-gathers
+// it, so nothing_can_change / sel_skip cannot hold) and its "this is last search's result" mark (qpos_valid: the edge gets a new epoch
+// then).  The temporal NN cache -- seeds, bounds, nn_cache_valid, nn_cache_edge -- is a fact about nearest neighbours and stays.
+static void reject_mask_changed(mvicp_ctx* c, int frame, int roles) {
+  c->spec_ready = false; c->spec2_ready = false;
+  for (int e = 0; e < c->E; ++e) {
+    if (!c->owned[e]) continue;
+    if (((roles & MVICP_REJECT_AS_TARGET) && c->edst[e] == frame) || ((roles & MVICP_REJECT_AS_SOURCE) && c->esrc[e] == frame)) {
+      c->hist.list_valid[e] = 0; c->hist.qpos_valid[e] = 0;
+    }
+  }
+}
+
+// `src` (f.n bytes in device memory of this context, or host memory when !on_device) becomes the mask of `frame` in `roles` (1..3).  The
+// checks are the callers'; a failure after the first write leaves the frame without a mask.
+static int install_reject_mask(mvicp_ctx* c, int frame, const unsigned char* src, bool on_device, int roles) {
+  FrameDev& f = c->frames[frame];
+  const int old_roles = f.grid.mask_roles;
+  MV_HIP(hipStreamSynchronize(c->stream));   // (a search in flight may still read the old bytes)
+  int st = MVICP_OK;
+  if (!f.grid.omask) st = dev_alloc(&f.grid.omask, (size_t)f.n);
+  if (st == MVICP_OK && !f.grid.smask) st = dev_alloc(&f.grid.smask, (size_t)f.n);
+  if (st == MVICP_OK && f.n > 0) {
+    f.grid.mask_roles = 0;
+    hipError_t e = hipMemcpyAsync(f.grid.omask, src, (size_t)f.n, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) { st = launch_mask_permute(c, f); if (st == MVICP_OK) e = hipStreamSynchronize(c->stream); }
+    if (e != hipSuccess) { set_error("reject mask of frame %d: %s", frame, hipGetErrorString(e)); st = MVICP_ERR_HIP; }
+  }
+  if (st == MVICP_OK) f.grid.mask_roles = roles;
+  reject_mask_changed(c, frame, old_roles | f.grid.mask_roles);
+  if (c->profile) prof_collect_lazy(c);
+  return st;
+}
+
+static int clear_reject_mask(mvicp_ctx* c, int frame) {
+  FrameDev& f = c->frames[frame];
+  const int old_roles = f.grid.mask_roles;
+  if (old_roles == 0) return MVICP_OK;   // (nothing set: nothing changes)
+  MV_CHECK(bind(c));
+  MV_HIP(hipStreamSynchronize(c->stream));
+  f.grid.mask_roles = 0;   // (the buffers stay for the next mask of this cloud)
+  reject_mask_changed(c, frame, old_roles);
+  return MVICP_OK;
+}
+
+int mvicp_set_reject_mask(mvicp_ctx* c, int frame, const unsigned char* mask, int roles) try {
+  if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
+  if (roles < 0 || roles > 3) { set_error("roles = %d outside [0, 3] (MVICP_REJECT_AS_TARGET | MVICP_REJECT_AS_SOURCE)", roles); return MVICP_ERR_ARG; }
+  if (frame < 0 || frame >= c->n_frames) { set_error("frame %d out of range [0,%d)", frame, c->n_frames); return MVICP_ERR_ARG; }
+  if (!mask || roles == 0) return clear_reject_mask(c, frame);
+  FrameDev& f = c->frames[frame];
+  if (!f.pts) { set_error("frame %d was never uploaded", frame); return MVICP_ERR_STATE; }
+  MV_CHECK(bind(c));
+  MV_CHECK(finish_builds(c));
+  if (f.n > 0 && !f.has_grid) { set_error("frame %d: a reject mask needs the per-cloud structure", frame); return MVICP_ERR_STATE; }
+  const int kind = f.n > 0 ? destination_kind(c, mask, "mask") : 0;
+  if (kind < 0) return kind;
+  return install_reject_mask(c, frame, mask, kind == 1, roles);
+} MVICP_GUARD_ABI
+
+int mvicp_boundary_adopt(mvicp_ctx* c, int roles) try {
+  if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
+  if (roles < 0 || roles > 3) { set_error("roles = %d outside [0, 3] (MVICP_REJECT_AS_TARGET | MVICP_REJECT_AS_SOURCE)", roles); return MVICP_ERR_ARG; }
+  const int frame = c->bnd.frame;
+  if (c->bnd.n < 0 || frame < 0 || frame >= c->n_frames || c->frames[frame].n != c->bnd.n || (c->bnd.n > 0 && !c->frames[frame].pts)) {
+    set_error("no boundary result to adopt: call mvicp_boundary first (an upload to its frame drops the result)");
+    return MVICP_ERR_STATE;
+  }
+  if (roles == 0) return clear_reject_mask(c, frame);
+  MV_CHECK(bind(c));
+  MV_CHECK(finish_builds(c));
+  if (c->bnd.n > 0 && !c->frames[frame].has_grid) { set_error("frame %d: a reject mask needs the per-cloud structure", frame); return MVICP_ERR_STATE; }
+  return install_reject_mask(c, frame, c->bnd.flag, true, roles);
+} MVICP_GUARD_ABI
+
+long long mvicp_get_reject_mask(mvicp_ctx* c, int frame, unsigned char* out, long long cap, int* roles) try {
+  if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
+  if (frame < 0 || frame >= c->n_frames) { set_error("frame %d out of range [0,%d)", frame, c->n_frames); return MVICP_ERR_ARG; }
+  const FrameDev& f = c->frames[frame];
+  if (f.grid.mask_roles == 0) { if (roles) *roles = 0; return 0; }
+  if (out && cap < f.n) { set_error("cap %lld < %d bytes", cap, f.n); return MVICP_ERR_ARG; }
+  if (out && f.n > 0) {
+    const FetchPart parts[] = {{out, f.grid.omask, (size_t)f.n, "mask"}};
+    MV_CHECK(fetch_parts(c, parts));
+  }
+  if (roles) *roles = f.grid.mask_roles;
+  return f.n;
+} MVICP_GUARD_ABI
+
 long long mvicp_knn_search(mvicp_ctx* c, int frame, const double* queries, long long m, int k, double radius) try {
   // every argument error that needs no GPU first: nothing of the context has been touched when one of them is reported
   if (!c) { set_error("null context"); return MVICP_ERR_ARG; }

@@ -51,6 +51,10 @@ struct GridDev {
   void* srec = nullptr;        // n x 32 B {x, y, z, idx}: the same, packed for the per-lane candidate scans
   void* crec = nullptr;        // the records in hash-CELL order ({start, count} runs of `table`); aliases srec unless grid_curve = 2
   double* snor = nullptr;      // n x 3 normals in sorted order (null without normals)
+  // reject mask (mvicp_set_reject_mask): n bytes, nonzero = pairs with this point are dropped by the search's acceptance test.  smask in
+  // sorted order (what the kernels index), omask the caller's bytes in original order (the read-back); mask_roles = MVICP_REJECT_AS_* bits,
+  // 0 = no mask (the buffers may stay allocated).  Lives and dies with the cloud, like snor
+  unsigned char* smask = nullptr; unsigned char* omask = nullptr; int mask_roles = 0;
   int* inv = nullptr;          // n: original index -> sorted position
   std::vector<int> h_order, h_inv;  // host copies: sorted -> original, original -> sorted
   void* table = nullptr;       // open-addressing hash: cell -> (start, count), 16-B entries
@@ -102,6 +106,9 @@ struct FrameDev {
   // ties the way the reference does (nn_tie.hip) and orders the k-NN lists of the normals (normals.hip); built on first use
   void* tie_nodes = nullptr; int* tie_ord = nullptr; int* tie_slot = nullptr; double tie_box[6] = {0, 0, 0, 0, 0, 0}; bool has_tie = false; int tie_levels = 0;   // tie_levels: levels of the tree (build_visit_tree)
 };
+
+// the frame's reject mask in sorted order when it applies in `role` (one MVICP_REJECT_AS_* bit), else null
+inline const unsigned char* reject_mask_of(const FrameDev& f, int role) { return (f.grid.mask_roles & role) ? f.grid.smask : nullptr; }
 
 struct ProfEntry {
   double ms = 0.0;
@@ -324,7 +331,7 @@ struct mvicp_ctx {
   float* d_nn_lb = nullptr;         // fp32, rounded down: lower bound on the DISTANCE from the query to every target other than nn_idx (temporal cache)
   // per-correspondence (total_cap)
   int* d_first = nullptr; int* d_second = nullptr; double* d_cd2 = nullptr;
-  int* d_qpos = nullptr;            // per query: its position in the edge's compacted list, or -1 (rejected by the cutoff)
+  int* d_qpos = nullptr;            // per query: its position in the edge's compacted list, or -1 (rejected by the cutoff or by a reject mask)
   int* d_dirty = nullptr;           // E: != 0 -> the edge's list (membership or a neighbour) changed this round: re-compact + re-gather
   int* d_dirty_slots = nullptr; int* d_dslot_off = nullptr; std::vector<int> dslot_off; int n_dslots = 0;  // one slot per 256 queries
   // the lists in the reference's layout (export.hip): {first, second, dist} triples, ascending first, all exportable edges of the last search
@@ -572,6 +579,7 @@ int negate_normals(mvicp_ctx* c, FrameDev& f);
 int normal_agreement(mvicp_ctx* c, const double* poses, const char* use, int* pos, int* neg);
 int launch_compact(mvicp_ctx* c, double d2_bound);                                    // corr.hip
 int launch_gather_stream(mvicp_ctx* c);
+int launch_mask_permute(mvicp_ctx* c, const FrameDev& f);                            // f.grid.omask (original order) -> f.grid.smask (sorted order)
 int launch_select_median(mvicp_ctx* c, double d2_bound);   // two-pass select anchored at the acceptance bound: any key set, exact
 int launch_export(mvicp_ctx* c);           // export.hip: every exportable edge's list -> reference-order triples in pinned memory (async; caller waits)
 int launch_select_bracket(mvicp_ctx* c);   // one-pass select around last round's medians (d_sel_lohi); flags edges it cannot answer

@@ -7,11 +7,14 @@
 // double whose correctly rounded sqrt is >= (double)thresh, so the decision is bit-identical to the
 // reference's `sqrt(d2) < thresh` without a device sqrt.  sqrt is monotone, so the median of the
 // distances is the sqrt of the median of d2; the host takes that one sqrt (IEEE, exact).
+// With reject masks (mvicp_set_reject_mask) the test is list_accepts (nn_list.h): the cutoff AND neither end flagged; everything below --
+// scan, scatter, gather, select, scale -- then runs over the kept pairs alone.
 //
 // The gather kernel also materialises, once per ICP round, the per-correspondence operand stream the
 // LM evaluations re-read up to ~100 times: SoA p (3) | n (3) | c = n . q | q (3), 10 arrays, of which point-to-plane
 // streams 7 (56 B per correspondence) and point-to-point 6 — instead of 2-3 random 24-B gathers per evaluation.
 #include "common.h"
+#include "nn_list.h"
 
 #include <cstring>
 
@@ -53,10 +56,19 @@ __device__ __forceinline__ int block_exclusive_scan(int v, int* __restrict__ wav
   return base + inc - v;
 }
 
+// The reject masks of edge e (mvicp_set_reject_mask): mask_tab = E source-side pointers, then E target-side ones, each the frame's mask in
+// sorted order or null; mask_tab itself is null while no frame has a mask, so a maskless search pays one wave-uniform branch per workgroup.
+struct EdgeMasks { const unsigned char* src; const unsigned char* dst; };
+__device__ __forceinline__ EdgeMasks edge_masks(const unsigned char* const* __restrict__ mask_tab, int E, int e) {
+  EdgeMasks m = {nullptr, nullptr};
+  if (mask_tab != nullptr) { m.src = mask_tab[e]; m.dst = mask_tab[E + e]; }
+  return m;
+}
+
 __global__ __launch_bounds__(NT) void count_kernel(const int* __restrict__ cblock_off, int E, const int* __restrict__ nsrc,
                                                    const long long* __restrict__ cap_off, const int* __restrict__ nn_idx,
                                                    const double* __restrict__ nn_d2, double bound, int* __restrict__ cblock_cnt,
-                                                   const int* __restrict__ dirty) {
+                                                   const int* __restrict__ dirty, const unsigned char* const* __restrict__ mask_tab) {
   __shared__ int wave_tot[NT / 64];
   const int b = blockIdx.x;
   const int e = find_edge(cblock_off, E, b);
@@ -64,11 +76,12 @@ __global__ __launch_bounds__(NT) void count_kernel(const int* __restrict__ cbloc
   const int lb = b - cblock_off[e];
   const int n = nsrc[e];
   const long long base = cap_off[e];
+  const EdgeMasks m = edge_masks(mask_tab, E, e);
   int cnt = 0;
 #pragma unroll
   for (int i = 0; i < IPT; ++i) {
     const int k = lb * kCompactBlock + threadIdx.x * IPT + i;
-    if (k < n) cnt += (nn_idx[base + k] >= 0 && nn_d2[base + k] < bound) ? 1 : 0;
+    if (k < n) cnt += list_accepts(k, nn_idx[base + k], nn_d2[base + k], bound, m.src, m.dst) ? 1 : 0;
   }
   int total;
   block_exclusive_scan(cnt, wave_tot, &total);
@@ -103,7 +116,8 @@ __global__ __launch_bounds__(NT) void scatter_kernel(const int* __restrict__ cbl
                                                      const long long* __restrict__ cap_off, const int* __restrict__ nn_idx,
                                                      const double* __restrict__ nn_d2, double bound, const int* __restrict__ cblock_cnt,
                                                      int* __restrict__ first, int* __restrict__ second, double* __restrict__ cd2,
-                                                     int* __restrict__ qpos, const int* __restrict__ dirty) {
+                                                     int* __restrict__ qpos, const int* __restrict__ dirty,
+                                                     const unsigned char* const* __restrict__ mask_tab) {
   __shared__ int wave_tot[NT / 64];
   const int b = blockIdx.x;
   const int e = find_edge(cblock_off, E, b);
@@ -111,6 +125,7 @@ __global__ __launch_bounds__(NT) void scatter_kernel(const int* __restrict__ cbl
   const int lb = b - cblock_off[e];
   const int n = nsrc[e];
   const long long base = cap_off[e];
+  const EdgeMasks m = edge_masks(mask_tab, E, e);
   int idx[IPT];
   double d2[IPT];
   bool ok[IPT];
@@ -122,7 +137,7 @@ __global__ __launch_bounds__(NT) void scatter_kernel(const int* __restrict__ cbl
     if (k < n) {
       idx[i] = nn_idx[base + k];
       d2[i] = nn_d2[base + k];
-      ok[i] = idx[i] >= 0 && d2[i] < bound;
+      ok[i] = list_accepts(k, idx[i], d2[i], bound, m.src, m.dst);
     }
     cnt += ok[i] ? 1 : 0;
   }
@@ -137,6 +152,21 @@ __global__ __launch_bounds__(NT) void scatter_kernel(const int* __restrict__ cbl
     second[base + pos] = idx[i];
     cd2[base + pos] = d2[i];
     ++pos;
+  }
+}
+
+// A frame's reject mask from original into sorted order, so that the acceptance test reads one byte at the index it already holds:
+// smask[i] = omask[sidx[i]], four sorted positions per thread (one 16-B index load, four byte gathers, one 4-B store; smask comes from
+// hipMalloc, so its words are aligned).  Every access is bounded by n.
+__global__ __launch_bounds__(NT) void mask_permute_kernel(const unsigned char* __restrict__ omask, const int* __restrict__ sidx, int n,
+                                                          unsigned char* __restrict__ smask) {
+  const long long i = 4ll * ((long long)blockIdx.x * NT + threadIdx.x);
+  if (i + 3 < n) {
+    const int4 s = *reinterpret_cast<const int4*>(sidx + i);
+    const unsigned int w = (unsigned int)omask[s.x] | ((unsigned int)omask[s.y] << 8) | ((unsigned int)omask[s.z] << 16) | ((unsigned int)omask[s.w] << 24);
+    *reinterpret_cast<unsigned int*>(smask + i) = w;
+  } else {
+    for (long long k = i; k < n; ++k) smask[k] = omask[sidx[k]];
   }
 }
 
@@ -438,12 +468,33 @@ int launch_compact(mvicp_ctx* c, double d2_bound) {
   if (c->n_cblocks == 0) return MVICP_OK;
   double bytes = 0;
   for (int e = 0; e < c->E; ++e) if (c->owned[e]) bytes += 2.0 * 12.0 * c->frames[c->esrc[e]].n;
+  // the per-edge reject masks (null table: no frame has one, and nothing is uploaded)
+  const unsigned char* const* d_masks = nullptr;
+  bool any_mask = false;
+  for (const FrameDev& f : c->frames) if (f.grid.mask_roles) any_mask = true;
+  if (any_mask) {
+    std::vector<const unsigned char*> tab(2 * (size_t)c->E, nullptr);
+    for (int e = 0; e < c->E; ++e) {
+      tab[e] = reject_mask_of(c->frames[c->esrc[e]], MVICP_REJECT_AS_SOURCE);
+      tab[c->E + e] = reject_mask_of(c->frames[c->edst[e]], MVICP_REJECT_AS_TARGET);
+    }
+    MV_CHECK(cached_upload(c, "mask_tab", tab.data(), sizeof(void*) * tab.size(), (void**)&d_masks));
+  }
   ProfScope ps(c, "compact", bytes);
   hipLaunchKernelGGL(count_kernel, dim3(c->n_cblocks), dim3(NT), 0, c->stream, c->d_cblock_off, c->E, c->d_nsrc, c->d_cap_off, c->d_nn_idx,
-                     c->d_nn_d2, d2_bound, c->d_cblock_cnt, c->d_dirty);
+                     c->d_nn_d2, d2_bound, c->d_cblock_cnt, c->d_dirty, d_masks);
   hipLaunchKernelGGL(scan_kernel, dim3(c->E), dim3(NT), 0, c->stream, c->d_cblock_off, c->d_cblock_cnt, c->d_count, c->d_dirty);
   hipLaunchKernelGGL(scatter_kernel, dim3(c->n_cblocks), dim3(NT), 0, c->stream, c->d_cblock_off, c->E, c->d_nsrc, c->d_cap_off, c->d_nn_idx,
-                     c->d_nn_d2, d2_bound, c->d_cblock_cnt, c->d_first, c->d_second, c->d_cd2, c->d_qpos, c->d_dirty);
+                     c->d_nn_d2, d2_bound, c->d_cblock_cnt, c->d_first, c->d_second, c->d_cd2, c->d_qpos, c->d_dirty, d_masks);
+  MV_HIP(hipGetLastError());
+  return MVICP_OK;
+}
+
+// smask = omask in the frame's sorted order (f.grid.omask holds the caller's n bytes): what the acceptance test indexes
+int launch_mask_permute(mvicp_ctx* c, const FrameDev& f) {
+  if (f.n == 0) return MVICP_OK;
+  ProfScope ps(c, "mask_permute", 5.0 * f.n);
+  hipLaunchKernelGGL(mask_permute_kernel, dim3((f.n + 4 * NT - 1) / (4 * NT)), dim3(NT), 0, c->stream, f.grid.omask, f.grid.sidx, f.n, f.grid.smask);
   MV_HIP(hipGetLastError());
   return MVICP_OK;
 }

@@ -70,9 +70,12 @@ struct GridJob {
   int n;
   int* out_idx; double* out_d2;
   const int* inv;      // target original index -> sorted position (null: emit original indices, raw-query API)
-  ListRef list;        // "did anything change?" bookkeeping of the edge's compacted list (nn_list.h; list.dirty null: none, the raw-query API)
   float* out_lb;       // per query: lower bound on the distance to every target other than out_idx, fp32 ROUNDED DOWN (null: no cache)
   int seed;            // out_idx still holds last round's neighbours (from any kernel): a starting candidate for far queries
+  // (out_lb and seed stand BEFORE the list: every workgroup of a fixed-point round reads them and nothing of the list, and behind a ListRef
+  // that had grown by the two mask pointers they fell into a further cache line of the job -- nn_grid_kernel 117 -> 128 us on the 32 x 200 k
+  // benchmark, back to 115 us with them here)
+  ListRef list;        // "did anything change?" bookkeeping of the edge's compacted list (nn_list.h; list.dirty null: none, the raw-query API)
   TieRef tie;          // where queries whose best distance was met by more than one target are reported (nn_tie.h)
 };
 
@@ -922,6 +925,8 @@ void free_grid(GridDev& g) {
   if (g.crec && g.crec != g.srec) (void)hipFree(g.crec);
   if (g.srec) (void)hipFree(g.srec);
   if (g.snor) (void)hipFree(g.snor);
+  if (g.smask) (void)hipFree(g.smask);
+  if (g.omask) (void)hipFree(g.omask);
   if (g.inv) (void)hipFree(g.inv);
   if (g.table) (void)hipFree(g.table);
   if (g.wide) (void)hipFree(g.wide);
@@ -1077,7 +1082,8 @@ int launch_nn_grid_edges(mvicp_ctx* c, double d2_bound, const SearchPlan& plan) 
     j.out_idx = c->d_nn_idx + c->cap_off[e]; j.out_d2 = c->d_nn_d2 + c->cap_off[e];
     j.inv = d.grid.inv; j.out_lb = c->d_nn_lb + c->cap_off[e];
     j.list = ListRef{c->d_qpos + c->cap_off[e], c->d_second + c->cap_off[e], c->d_cd2 + c->cap_off[e], c->d_dirty + e, c->d_dirty_slots + c->dslot_off[e],
-                     c->d_stream + c->cap_off[e], c->total_cap, d.grid.snor, (const PointRec*)d.grid.srec};
+                     c->d_stream + c->cap_off[e], c->total_cap, d.grid.snor, (const PointRec*)d.grid.srec,
+                     reject_mask_of(s, MVICP_REJECT_AS_SOURCE), reject_mask_of(d, MVICP_REJECT_AS_TARGET)};
     j.seed = ((int)c->hist.nn_cache_edge.size() == c->E && c->hist.nn_cache_edge[e]) ? 1 : 0;
     jobs.push_back(j); dsts.push_back(&d);
   }

@@ -14,14 +14,29 @@ struct ListRef {
   const int* qpos; int* second; double* cd2; const int* dirty; int* dirty_slots;   // dirty: host-forced flag of the edge
   double* stream; long long total_cap; const double* dst_nor;                      // the edge's slice of the operand stream (linearize.hip) + sorted dst normals
   const PointRec* dst_srec;                                                         // the target's sorted records
+  const unsigned char* src_mask; const unsigned char* dst_mask;                     // reject masks of the source / the target in sorted order, or null
 };
 
+// THE acceptance test of a searched list (count_kernel, scatter_kernel, update_list_entry: nowhere else).  k = the query's sorted position in
+// its source, idx = its neighbour's sorted position in the target (< 0: none), d2 < bound <=> sqrt(d2) < thresh (corr.hip); src_mask / dst_mask:
+// the frames' reject masks in sorted order (mvicp_set_reject_mask), null = none.  The pointers are the same in every lane of an edge's
+// workgroup, so a null mask costs a wave-uniform branch; the target's byte is loaded only for a pair that is still accepted.
+__device__ __forceinline__ bool list_accepts(int k, int idx, double d2, double bound, const unsigned char* __restrict__ src_mask,
+                                             const unsigned char* __restrict__ dst_mask) {
+  bool acc = idx >= 0 && d2 < bound;
+  if (src_mask != nullptr) acc = acc && src_mask[k] == 0;
+  if (dst_mask != nullptr) { if (acc) acc = dst_mask[idx] == 0; }
+  return acc;
+}
+
+// A query that a mask keeps out of the list has pos < 0 and stays "not accepted" whatever its distance does: pos < 0 does NOT mean
+// d2 >= bound, and nothing here reads it that way (clean = the acceptance recomputed from scratch equals the membership).
 // same_neighbour: the caller KNOWS idx_new is last round's neighbour (temporal-cache hit): a valid list then holds exactly that index at
 // the query's position (the list was built from out_idx and every round since kept every neighbour), so the load is skipped.
 __device__ __forceinline__ void update_list_entry(const ListRef& R, int i, int idx_new, double d2_new, double bound, bool same_neighbour) {
   if (*R.dirty != 0) return;   // forced dirty by the host (no valid list yet): nothing to check, qpos may be uninitialised
   const int pos = R.qpos[i];
-  const bool acc = idx_new >= 0 && d2_new < bound;
+  const bool acc = list_accepts(i, idx_new, d2_new, bound, R.src_mask, R.dst_mask);
   bool clean;
   if (pos < 0) clean = !acc;
   else {

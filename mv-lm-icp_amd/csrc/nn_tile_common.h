@@ -291,7 +291,8 @@ inline int build_tile_jobs(mvicp_ctx* c, bool with_bounds, bool with_cache, bool
     if (with_bounds && with_cache) { j.cache = 1; j.miss_max = c->tile_miss; j.reject_cache = c->reject_cache ? 1 : 0; }
     if (with_list) {
       j.list = ListRef{c->d_qpos + c->cap_off[e], c->d_second + c->cap_off[e], c->d_cd2 + c->cap_off[e], c->d_dirty + e, c->d_dirty_slots + c->dslot_off[e],
-                       c->d_stream + c->cap_off[e], c->total_cap, d.grid.snor, (const PointRec*)d.grid.srec};
+                       c->d_stream + c->cap_off[e], c->total_cap, d.grid.snor, (const PointRec*)d.grid.srec,
+                       reject_mask_of(s, MVICP_REJECT_AS_SOURCE), reject_mask_of(d, MVICP_REJECT_AS_TARGET)};
     }
     j.kacc = (float)c->mfma_kacc; j.trig = c->mfma_trig;
     j.tie = tref; j.tie.job = (unsigned int)jobs.size();

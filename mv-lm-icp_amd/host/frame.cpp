@@ -35,6 +35,7 @@ void Session::reset() {
   graph_bound = false;
   esrc.clear(); edst.clear();
   held.clear(); epochs = nullptr; corr = nullptr; corr_off = nullptr;   // (they pointed into the context that has just ended)
+  reject_masks.clear(); reject_roles = 0; reject_key = nullptr;
   ++knn_generation;
 }
 
@@ -80,6 +81,7 @@ void Session::upload(std::vector<std::shared_ptr<Frame>>& frames) {
     const double* nrm = f.nor.size() == f.pts.size() && !f.nor.empty() ? f.nor[0].data() : nullptr;
     check(mvicp_set_frame(ctx, (int)i, f.pts.empty() ? nullptr : f.pts[0].data(), nrm, (int)f.pts.size()));
   }
+  install_reject_masks(frames);   // (mvicp_set_num_frames dropped them with the clouds; no-op unless setRejectMasks was given this vector)
 }
 
 void Session::bind(std::vector<std::shared_ptr<Frame>>& frames) {
@@ -304,6 +306,26 @@ std::vector<long long> Session::rejectBoundary(std::vector<std::shared_ptr<Frame
   // an installed list ends the mapped triples and the cached round: the next correspond() searches again and maps anew
   if (any) { last_poses.clear(); corr = nullptr; corr_off = nullptr; }
   return dropped;
+}
+
+void Session::install_reject_masks(const std::vector<std::shared_ptr<Frame>>& frames) {
+  if (reject_key != (const void*)&frames || reject_masks.size() != frames.size()) return;   // (masks of another frames vector: not these clouds')
+  for (size_t j = 0; j < frames.size(); ++j) {
+    const std::vector<unsigned char>& m = reject_masks[j];
+    if (!m.empty() && m.size() != frames[j]->pts.size()) throw std::runtime_error("mvicp: setRejectMasks: a mask has one byte per point of its frame");
+    check(mvicp_set_reject_mask(ctx, (int)j, m.empty() ? nullptr : m.data(), reject_roles));
+  }
+}
+
+void Session::setRejectMasks(std::vector<std::shared_ptr<Frame>>& frames, const std::vector<std::vector<unsigned char>>& masks, int roles) {
+  if (masks.size() != frames.size()) throw std::runtime_error("mvicp: setRejectMasks needs one mask per frame");
+  if (roles < 0 || roles > 3) throw std::runtime_error("mvicp: setRejectMasks: roles outside [0, 3]");
+  for (size_t j = 0; j < frames.size(); ++j)
+    if (!masks[j].empty() && masks[j].size() != frames[j]->pts.size()) throw std::runtime_error("mvicp: setRejectMasks: a mask has one byte per point of its frame");
+  reject_masks = masks; reject_roles = roles; reject_key = (const void*)&frames;
+  // into the context now if it holds exactly these clouds; otherwise the upload that brings them installs the masks
+  if (ctx && frames_key == (const void*)&frames && frame_keys_of(frames) == frame_keys) install_reject_masks(frames);
+  last_poses.clear(); corr = nullptr; corr_off = nullptr;   // (a cached round was searched under the old masks)
 }
 
 void Session::optimize(std::vector<std::shared_ptr<Frame>>& frames, int param, bool pointToPlane, bool robust, mvicp_summary* out) {

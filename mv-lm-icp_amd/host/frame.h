@@ -233,6 +233,16 @@ struct Session {
   // so the next computeClosestPointsToNeighbours searches again -- like a first search, the temporal cache is gone -- and refills.
   // Returns the pairs dropped per edge, in edge order.
   std::vector<long long> rejectBoundary(std::vector<std::shared_ptr<Frame>>& frames, const std::vector<std::vector<unsigned char>>& masks);
+  // The same rejection INSIDE the search (mvicp_set_reject_mask), set ONCE for a frames vector and called in no round: masks[j] is one byte
+  // per point of frames[j] (an empty mask, or roles 0, clears that frame's), applied in `roles` (MVICP_REJECT_AS_TARGET / _AS_SOURCE, or-ed).
+  // Every later computeClosestPointsToNeighbours over these frames drops the pairs on flagged points on the device: the lists stay searched
+  // lists (temporal cache, in-place upkeep, queued evaluations), copy_back is not needed, and with it on the Frame's vectors receive the
+  // filtered lists through the ordinary copy-back.  The edge's weight is the median over the KEPT pairs (rejectBoundary keeps the
+  // unfiltered list's).  The session keeps the masks and installs them again whenever it uploads this frames vector; masks set for
+  // another vector (a coarse level) are replaced.  The cached round, if any, is forgotten: the next search runs.
+  void setRejectMasks(std::vector<std::shared_ptr<Frame>>& frames, const std::vector<std::vector<unsigned char>>& masks, int roles = MVICP_REJECT_AS_TARGET);
+  std::vector<std::vector<unsigned char>> reject_masks; int reject_roles = 0; const void* reject_key = nullptr;   // what setRejectMasks was given last
+  void install_reject_masks(const std::vector<std::shared_ptr<Frame>>& frames);   // the kept masks into the context that holds `frames`
   void optimize(std::vector<std::shared_ptr<Frame>>& frames, int param, bool pointToPlane, bool robust, mvicp_summary* sm = nullptr);
   // the same with the objective named (MVICP_METRIC_SYMMETRIC needs normals on every frame, oriented consistently)
   void optimize(std::vector<std::shared_ptr<Frame>>& frames, int param, mvicp_metric metric, bool robust, mvicp_summary* sm = nullptr);

@@ -76,6 +76,11 @@
 // applies them.  One line per frame, `boundary: frame i flagged a of b`, and one per round, `boundary: round r dropped n pairs` (printed with
 // --quiet too).  Refused when a frame has no normals after pre-processing, when C is outside (-1, 1) and with --copyback 0 (the Frame's lists
 // are what is filtered).  The installed lists are explicit, so every round searches like a first round: the temporal cache is lost.
+// --reject_mode host|device (default host: the route above, unchanged): device hands the same masks to the search itself
+// (Session::setRejectMasks -> mvicp_set_reject_mask, target side), once when a level's first round starts, and calls nothing per round: the
+// lists stay searched lists, so the temporal cache, the list upkeep and the queued evaluations keep working, --copyback 1 is not needed, and
+// with it on the frames receive the filtered lists through the ordinary copy-back.  No `boundary: round r dropped n pairs` lines.  The edge
+// weight is the median over the kept pairs (host: over the unfiltered list), so the two modes' poses agree closely, not bit for bit.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -171,7 +176,10 @@ int main(int argc, char** argv) {
   const int boundary_nn = F.i("boundary_nn", 30);
   const double boundary_radius = F.f("boundary_radius", 0.0), boundary_cos = F.f("boundary_cos", -0.5);
   if (reject_boundary && !(boundary_cos > -1.0 && boundary_cos < 1.0)) { std::cerr << "--boundary_cos must lie in (-1, 1)" << std::endl; return 1; }
-  if (reject_boundary && !Session::get().copy_back) { std::cerr << "--reject_boundary filters the frames' lists: it needs --copyback 1" << std::endl; return 1; }
+  const std::string reject_mode = F.s("reject_mode", "host");
+  if (reject_mode != "host" && reject_mode != "device") { std::cerr << "--reject_mode must be host or device" << std::endl; return 1; }
+  const bool reject_device = reject_boundary && reject_mode == "device";
+  if (reject_boundary && !reject_device && !Session::get().copy_back) { std::cerr << "--reject_boundary filters the frames' lists: it needs --copyback 1" << std::endl; return 1; }
   std::vector<std::shared_ptr<Frame>> frames;
   try {
     loadFrames(F, frames, dir);
@@ -276,12 +284,14 @@ int main(int argc, char** argv) {
     for (int r = 0; r < rounds; ++r) {
       if (r == coarse_rounds && !coarse.empty()) poses_to_full();
       std::vector<std::shared_ptr<Frame>>& cur = r < coarse_rounds ? coarse : frames;   // this round's level
+      // --reject_mode device: the level's masks go to the device once, when its first round starts; nothing is called per round
+      if (reject_device && (r == 0 || r == coarse_rounds)) Session::get().setRejectMasks(cur, r < coarse_rounds ? coarse_masks : masks, MVICP_REJECT_AS_TARGET);
       if (r == F.i("perturb_round", -1) && F.i("perturb_frame", -1) >= 0 && F.i("perturb_frame", -1) < (int)cur.size())
         cur[F.i("perturb_frame", -1)]->pose.m[12] += 1e-4;
       const unsigned long long c0 = Session::get().edges_copied, s0 = Session::get().edges_skipped;
       const auto t0 = std::chrono::steady_clock::now();
       for (auto& f : cur) f->computeClosestPointsToNeighbours(&cur, cutoff);
-      if (reject_boundary) {
+      if (reject_boundary && !reject_device) {
         long long total = 0;
         for (long long d : Session::get().rejectBoundary(cur, r < coarse_rounds ? coarse_masks : masks)) total += d;
         std::cout << "boundary: round " << r << " dropped " << total << " pairs" << std::endl;

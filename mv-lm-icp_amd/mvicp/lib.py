@@ -11,6 +11,7 @@ PARAM_EIGEN_QUATERNION, PARAM_ANGLE_AXIS, PARAM_SOPHUS_SE3 = 0, 1, 2
 METRIC_POINT, METRIC_PLANE, METRIC_SYMMETRIC = 0, 1, 2   # mvicp_metric
 NN_AUTO, NN_BRUTE, NN_GRID, NN_TILE = 0, 1, 2, 3
 ORIENT_ANCHOR, ORIENT_VIEWPOINT, ORIENT_DIRECTION = 0, 1, 2   # mvicp_orient_mode
+REJECT_AS_TARGET, REJECT_AS_SOURCE = 1, 2   # roles of a reject mask (mvicp_set_reject_mask), may be or-ed
 EDGE_BLOCK = 91
 
 SYMBOLS = [
@@ -24,6 +25,7 @@ SYMBOLS = [
     "mvicp_cluster", "mvicp_cluster_fetch", "mvicp_cluster_keep_rule", "mvicp_cluster_select", "mvicp_cluster_fetch_kept",
     "mvicp_segment_plane", "mvicp_plane_fetch", "mvicp_plane_select", "mvicp_plane_fetch_kept", "mvicp_plane_from_moments",
     "mvicp_boundary", "mvicp_boundary_fetch", "mvicp_boundary_select", "mvicp_boundary_fetch_kept",
+    "mvicp_set_reject_mask", "mvicp_boundary_adopt", "mvicp_get_reject_mask",
     "mvicp_knn_search", "mvicp_knn_fetch", "mvicp_fpfh", "mvicp_fpfh_fetch", "mvicp_iss_keypoints", "mvicp_iss_fetch",
     "mvicp_estimate_normals", "mvicp_normals_fetch", "mvicp_normals_adopt", "mvicp_fit_normals", "mvicp_normals_fit_fetch",
     "mvicp_orient_normals", "mvicp_orient_fetch", "mvicp_orient_adopt", "mvicp_normal_agreement", "mvicp_signs_from_agreement", "mvicp_negate_normals",
@@ -177,7 +179,11 @@ def load_library(path=None):
     lib.mvicp_boundary_select.argtypes = [vp, C.c_int]
     lib.mvicp_boundary_select.restype = C.c_longlong
     lib.mvicp_boundary_fetch_kept.argtypes = [vp, C.c_longlong, vp, vp, vp]
-    lib.mvicp_cache_allowance.argtypes = [dp, dp, dp, dp, C.c_double, dp]
+    lib.mvicp_set_reject_mask.argtypes = [vp, C.c_int, vp, C.c_int]
+    lib.mvicp_boundary_adopt.argtypes = [vp, C.c_int]
+    lib.mvicp_get_reject_mask.argtypes = [vp, C.c_int, vp, C.c_longlong, ip]
+    lib.mvicp_get_reject_mask.restype = C.c_longlong
+    lib.mvicp_cache_allowance.argtypes =[dp, dp, dp, dp, C.c_double, dp]
     lib.mvicp_knn_search.argtypes = [vp, C.c_int, vp, C.c_longlong, C.c_int, C.c_double]
     lib.mvicp_knn_search.restype = C.c_longlong
     lib.mvicp_knn_fetch.argtypes = [vp, C.c_longlong, C.c_longlong, vp, vp, vp, vp]
@@ -977,6 +983,49 @@ class Engine:
             self.set_correspondences(e, kf, ks, weights[e])
             dropped[e] = len(first) - len(kf)
         return dropped
+
+    def set_reject_mask(self, frame, mask, roles=REJECT_AS_TARGET):
+        """mvicp_set_reject_mask: `mask` (one byte per point of `frame` in original order, nonzero = reject: a numpy array, a uint8 torch
+        tensor on the engine's GPU, or None = clear) is applied INSIDE every later correspond() -- a pair whose target (REJECT_AS_TARGET),
+        source (REJECT_AS_SOURCE) or either end (both, or-ed) is flagged is dropped, and counts, lists, distances and the weight are those
+        of the kept pairs.  Unlike reject_correspondences the lists stay searched lists: nothing crosses the bus and the temporal cache,
+        the in-place upkeep and the queued evaluations keep working.  Note the weight: the median over the KEPT pairs, where
+        reject_correspondences keeps the unfiltered list's."""
+        if mask is None or not 0 <= int(frame) < len(self.npts):   # (a frame out of range: the library refuses it)
+            mask = None if mask is None else C.cast(C.create_string_buffer(8), C.c_void_p)
+            _check(self.lib, self.lib.mvicp_set_reject_mask(self.h, int(frame), mask, int(roles)))
+            return
+        n = int(self.npts[int(frame)])
+        if isinstance(mask, np.ndarray) or not hasattr(mask, "data_ptr"):
+            a = np.asarray(mask).reshape(-1)
+            keep = np.ascontiguousarray(a) if a.dtype == np.uint8 else np.ascontiguousarray(a != 0, dtype=np.uint8)   # (uint8 bytes go in as they are)
+            if len(keep) != n:
+                raise MvicpError(f"set_reject_mask: {len(keep)} flags for the {n} points of frame {frame}")
+            p = keep.ctypes.data_as(C.c_void_p) if n else C.cast(C.create_string_buffer(8), C.c_void_p)   # (never NULL: NULL clears)
+        else:
+            import torch
+            if not mask.is_cuda or mask.dtype != torch.uint8 or (mask.device.index or 0) != self.device:
+                raise MvicpError("set_reject_mask: a torch `mask` must be a uint8 tensor on the engine's GPU")
+            keep = mask.contiguous().reshape(-1)
+            if keep.shape[0] != n:
+                raise MvicpError(f"set_reject_mask: {keep.shape[0]} flags for the {n} points of frame {frame}")
+            torch.cuda.synchronize(keep.device)   # (a device array must be fully written when the call is made)
+            p = C.c_void_p(keep.data_ptr()) if n else C.cast(C.create_string_buffer(8), C.c_void_p)
+        _check(self.lib, self.lib.mvicp_set_reject_mask(self.h, int(frame), p, int(roles)))
+
+    def adopt_boundary_mask(self, roles=REJECT_AS_TARGET):
+        """mvicp_boundary_adopt: the flags of the last boundary() become that frame's reject mask without leaving the device."""
+        _check(self.lib, self.lib.mvicp_boundary_adopt(self.h, int(roles)))
+
+    def reject_mask(self, frame):
+        """mvicp_get_reject_mask -> (mask (n,) uint8 in original order or None when the frame has none, roles)."""
+        roles = C.c_int(0)
+        n = int(_check(self.lib, self.lib.mvicp_get_reject_mask(self.h, int(frame), None, 0, C.byref(roles))))
+        if roles.value == 0:
+            return None, 0
+        out = np.zeros(n, dtype=np.uint8)
+        _check(self.lib, self.lib.mvicp_get_reject_mask(self.h, int(frame), out.ctypes.data_as(C.c_void_p) if n else None, n, C.byref(roles)))
+        return out, int(roles.value)
 
     def knn_search(self, frame, queries=None, k=8, radius=0.0, device=False):
         """mvicp_knn_search + mvicp_knn_fetch on the stored cloud of `frame`: per query the candidates (every point, or with radius > 0 the

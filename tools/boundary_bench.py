@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Times the boundary stage (Engine.boundary, csrc/boundary.hip) next to mvicp_estimate_normals on the same clouds, and one registration
-round with and without Engine.reject_correspondences.
+round without rejection, with Engine.reject_correspondences (the host route) and with Engine.set_reject_mask (the mask inside the search).
 
   one200k : one synthetic view of 200 000 points
   one1m   : one synthetic view of 1 000 000 points
@@ -13,15 +13,17 @@ after WARM untimed ones of
 and the library's own profile scopes (HIP events on its stream): the search's, "boundary" and "normals_pca".  Reported: boundary / estimate
 at equal max_nn for whole calls and for the kernels alone, the points flagged, and mvicp_boundary_select.
 
-The round: bench-like problems of 4 views; per round mvicp_correspond + mvicp_optimize (point-to-plane, robust), with and without
-reject_correspondences(target masks) between them, alternating, on an engine each; medians of REPS rounds.  Twice: a FIRST round (from the
-start poses after reset_history: a first search in both legs, so the difference is the lists' two trips through the host and the lost
-queued evaluation) and LATER rounds (the loop continued: the plain leg settles into cached and fixed-point rounds, the rejecting leg
-searches like a first round every time).
+The round: bench-like problems of 4 views; per round mvicp_correspond + mvicp_optimize (point-to-plane, robust) in three legs, alternating,
+on an engine each; medians of REPS rounds: "plain" (no rejection), "reject" (the host route: reject_correspondences(target masks) between
+the search and the solve) and "device" (the same masks handed to the search once, set_reject_mask(i, mask, REJECT_AS_TARGET), nothing per
+round).  Twice: a FIRST round (from the start poses after reset_history: a first search in every leg, so the host leg's difference is the
+lists' two trips through the host and the lost queued evaluation) and LATER rounds (the loop continued: the plain and the device leg settle
+into cached and fixed-point rounds, the host leg searches like a first round every time).  The yardstick of the device leg is the plain
+leg of the same run.
 
 One JSON line per measurement, on stdout and in --out.
 
-    python tools/boundary_bench.py [--cases one200k,one1m] [--reps 7] [--warm 2] [--out profiles/boundary_bench.txt]
+    python tools/boundary_bench.py [--cases one200k,one1m | --cases none] [--reps 7] [--warm 2] [--out profiles/boundary_bench.txt]
 """
 import argparse
 import json
@@ -125,15 +127,18 @@ def run_case(name, args):
 
 
 def run_round(N, args):
-    """one registration round, with and without reject_correspondences, alternating, each from the same start on an engine of its own"""
+    """one registration round in three legs -- plain, rejecting on the host, mask inside the search --, alternating, each from the same start on an
+    engine of its own"""
     pb = synth.make_problem(4, N)
     engines = {}
     try:
-        for key in ("plain", "reject"):
+        for key in ("plain", "reject", "device"):
             e = mvicp.Engine(0)
             e.set_frames(pb["pts"], pb["nor"])
             engines[key] = e
         masks = [engines["reject"].boundary(i, 30)["flag"] for i in range(4)]
+        for i in range(4):   # once, before the graph: nothing of this leg is called per round
+            engines["device"].set_reject_mask(i, masks[i], L.REJECT_AS_TARGET)
         for e in engines.values():
             e.set_graph(pb["src"], pb["dst"])
         poses = {key: pb["init"].copy() for key in engines}
@@ -170,7 +175,12 @@ def run_round(N, args):
                first_reject_over_plain=med1["reject"] / med1["plain"],
                later_plain_median_ms=med["plain"], later_plain_min_ms=float(np.min(times["plain"])), later_plain_max_ms=float(np.max(times["plain"])),
                later_reject_median_ms=med["reject"], later_reject_min_ms=float(np.min(times["reject"])), later_reject_max_ms=float(np.max(times["reject"])),
-               later_reject_over_plain=med["reject"] / med["plain"])
+               later_reject_over_plain=med["reject"] / med["plain"],
+               first_device_median_ms=med1["device"], first_device_min_ms=float(np.min(first["device"])), first_device_max_ms=float(np.max(first["device"])),
+               first_device_over_plain=med1["device"] / med1["plain"],
+               later_device_median_ms=med["device"], later_device_min_ms=float(np.min(times["device"])), later_device_max_ms=float(np.max(times["device"])),
+               later_device_over_plain=med["device"] / med["plain"], later_device_over_reject=med["device"] / med["reject"],
+               pairs_last_round_device=int(engines["device"].counts.sum()))
     finally:
         for e in engines.values():
             e.close()
@@ -186,7 +196,8 @@ def main():
     args = ap.parse_args()
     OUT = open(args.out, "w")
     for name in args.cases.split(","):
-        run_case(name, args)
+        if name and name != "none":   # (--cases none: the rounds alone)
+            run_case(name, args)
     for N in ROUND_SIZES:
         run_round(N, args)
     OUT.close()
