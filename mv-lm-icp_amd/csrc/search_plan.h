@@ -151,7 +151,7 @@ struct SearchHistory {
   std::vector<char> explicit_list;  // E: the edge's list was installed by mvicp_set_correspondences (arbitrary order / repeats: no d_qpos for it)
   std::vector<char> qpos_valid;     // E: d_qpos / d_second / d_cd2 describe the LAST SEARCH's result of this edge (what the export reads).  Unlike list_valid
                                     // (= the list may be maintained in place next round) it survives mvicp_recompute_normals, which only re-gathers operands
-  std::vector<double> sel_med1, sel_med2;   // per owned edge: median d2 of the last / the one-before-last round (< 0: unknown)
+  std::vector<double> sel_med1, sel_med2;   // per searched edge (single rank: owned; with an exchange: every rank's): median d2 of the last / the one-before-last round (< 0: unknown)
   bool sel_result_valid = false;    // the last search on this context finished its select: d_median, d_a and the mapped (count, median d2) pairs are that select's
   bool sel_result_armed = false;    // ... and that select also wrote the SoftLOne scales (d_a and their mapped copy)
   double auto_prev_dist = 0.0; int auto_last_method = -1;   // MVICP_NN_AUTO policy state
@@ -389,15 +389,19 @@ inline void plan_search(const SearchInputs& in, const SearchOptions& opt, Search
   const bool grid_lists = method == MVICP_NN_GRID && !opt.nn_tree_only && !opt.nn_skip_far;
   const bool keep_lists = (method == MVICP_NN_TILE || grid_lists) && opt.list_reuse;
   for (int e = 0; e < E; ++e) p.dirty[e] = (keep_lists && p.active[e] && h.list_valid[e]) ? 0 : 1;
-  // One-pass bracket select (corr.hip) instead of the two-pass anchored select: only when EVERY active edge of this rank has a
-  // median that has settled (last two rounds within 0.1 %); the bracket is +-0.6 % in d2 around the last one.
+  // One-pass bracket select (corr.hip) instead of the two-pass anchored select: only when EVERY searched edge has a median that has
+  // settled (last two rounds within 0.1 %); the bracket is +-0.6 % in d2 around the last one.  With N > 1 ranks the medians of ALL edges
+  // arrive in the exchanged buffer (record_arrived keeps them), and every searched edge of the graph is asked, not only this rank's: the
+  // ranks then take the decision a single process takes.  A rank that asked its own edges alone armed a bracket whenever the unsettled
+  // edges happened to be a peer's; the next medians left it, every rank ran the select again (redo_select: a second launch and a second
+  // exchange) and the queued evaluation was dropped on all of them, where a single process does neither.
   p.use_bracket = opt.sel_bracket && h.have_corr;
   for (int e = 0; e < E; ++e) {
     p.lohi[2 * e] = p.lohi[2 * e + 1] = 0.0;
-    if (!p.active[e]) continue;
+    if (!(in.exchange ? !p.src_fixed[e] : (bool)p.active[e])) continue;
     const double m1 = h.sel_med1[e], m2 = h.sel_med2[e];
     if (!(m1 > 0.0 && m2 > 0.0 && std::fabs(m1 - m2) <= 0.001 * m1)) { p.use_bracket = false; continue; }
-    p.lohi[2 * e] = m1 * 0.994; p.lohi[2 * e + 1] = m1 * 1.006;
+    if (p.active[e]) { p.lohi[2 * e] = m1 * 0.994; p.lohi[2 * e + 1] = m1 * 1.006; }
   }
   // A search whose every edge has last round's exact transform and a valid list reproduces every query bit for bit: no list can
   // change, so the (data-dependent, early-exiting) list-maintenance kernels — dirty-flag reduction, compaction, gather — are not
@@ -463,7 +467,7 @@ inline bool record_arrived(const SearchInputs& in, const SearchPlan& p, SearchHi
     const bool mine = in.owned[e] && p.active[e];
     // (count, median d2): weight = (float)(1.5 * sqrt(median d2))  (frame.cpp:168-176)
     const double cnt = (in.exchange || mine) ? res[2 * e] : 0.0, med = cnt > 0 ? res[2 * e + 1] : 0.0;
-    if (!mine) h.sel_med1[e] = h.sel_med2[e] = -1.0;
+    if (!(in.exchange ? !p.src_fixed[e] : mine)) h.sel_med1[e] = h.sel_med2[e] = -1.0;   // (exchanged: every searched edge's median is known here)
     else { h.sel_med2[e] = h.sel_med1[e]; h.sel_med1[e] = cnt > 0 ? med : -1.0; }
     if (p.spec_arm && !spec_bad && (in.exchange || mine)) {
       const double a_host = cnt > 0 ? (double)(float)(std::sqrt(med) * 1.5) : 0.0;

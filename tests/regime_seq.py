@@ -47,17 +47,22 @@ def solves(events):
     return [e for e in events if e["kind"] not in ("hold", "fail")]
 
 
-def run(eng, pb, events, after_search=None, after_round=None):
+def run(eng, pb, events, after_search=None, after_round=None, masks=None):
     """Replays `events` on an engine that already holds the clouds and the graph.  -> list of (counts, weights-as-bytes, poses) per round.
     Hooks (tests/test_gpu_sym_regimes.py; the sharded tests use none): after_search(state) runs between the round's search and its solve,
     after_round(state) after the solve; state = {"round", "event", "poses", "fixed", "cutoff", "method", "options", "counts", "weights"}, the
     round's own values ("options": what the script has set so far).  A kind the scripts above never draw, for hand-written events: "normals"
     (mvicp_recompute_normals(frame, 10) before the round's search; the new normals go to state["normals"]).  And a metric they never draw: 3, the
-    plane-to-plane objective — the round's solve is mvicp_optimize_gicp at e["epsilon"] (default 1e-3; tests/test_gpu_gicp_regimes.py)."""
+    plane-to-plane objective — the round's solve is mvicp_optimize_gicp at e["epsilon"] (default 1e-3; tests/test_gpu_gicp_regimes.py).
+    Another hand-written kind: "mask" (tests/maskcases.py) — eng.set_reject_mask(e["frame"], e["mask"], e["roles"]) before the round's search; the
+    round is otherwise a "none" round.  state["masks"]: per frame the (mask, roles) currently set, (None, 0) for none; `masks` = {frame: (mask,
+    roles)}: what the caller has set on the engine before the call."""
     poses = pb["init"].copy()
     fixed = pb["fixed"].copy()
     cutoff, method, rule = 0.05, 0, 1
     options = {}
+    cur_masks = {f: (None, 0) for f in range(len(pb["pts"]))}
+    cur_masks.update(masks or {})
     out = []
     for rnd, e in enumerate(events):
         k = e["kind"]
@@ -75,6 +80,9 @@ def run(eng, pb, events, after_search=None, after_round=None):
             options[e["name"]] = e["value"]
         elif k == "normals":
             state["normals"] = eng.recompute_normals(e["frame"], 10)
+        elif k == "mask":
+            eng.set_reject_mask(e["frame"], e["mask"], e["roles"])
+            cur_masks[e["frame"]] = (e["mask"], e["roles"]) if (e["mask"] is not None and e["roles"]) else (None, 0)
         elif k == "tie_rule":
             rule = 1 - rule
             eng.set_option("tie_rule", rule)
@@ -92,7 +100,8 @@ def run(eng, pb, events, after_search=None, after_round=None):
             if e["retry_there"]:
                 poses = Pf
         counts, weights = eng.correspond(poses, fixed, cutoff, method)
-        state.update(poses=poses, fixed=fixed.copy(), cutoff=cutoff, method=method, options=dict(options), counts=counts.copy(), weights=weights.copy())
+        state.update(poses=poses, fixed=fixed.copy(), cutoff=cutoff, method=method, options=dict(options), counts=counts.copy(), weights=weights.copy(),
+                     masks=dict(cur_masks))
         if after_search is not None:
             after_search(state)
         if k not in ("hold", "fail") and counts.sum() > 0:

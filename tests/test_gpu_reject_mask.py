@@ -7,6 +7,7 @@ the registration of the partial pair ends where tests/test_reject_mask_cpu.py sa
 import numpy as np
 import pytest
 
+import maskcases
 import matchref
 import mvicp
 import regime_seq
@@ -51,12 +52,7 @@ def lists(eng, E):
 
 def expected(pb, ref_lists, masks, roles):
     """rejectref over the maskless engine's lists: `masks` per frame (an entry may be None), in `roles` -> per edge (first, second, dist, weight)"""
-    out = []
-    for e, (f, s, d) in enumerate(ref_lists):
-        sm = masks[pb["src"][e]] if roles & S else None
-        dm = masks[pb["dst"][e]] if roles & T else None
-        out.append(rejectref.masked(f, s, d, sm, dm))
-    return out
+    return maskcases.expected_lists(pb, ref_lists, [(m, roles if m is not None else 0) for m in masks])
 
 
 def assert_equals(got_lists, counts, weights, want, tag):

@@ -64,9 +64,9 @@ def p(x1, y2=0.0):
 
 class Planner:
     """One context's worth of policy state.  frame_flags: 1 grid structures, 2 tie tree, 4 sorted normals."""
-    def __init__(self, lib, frame_flags=(5, 5, 5), exchange=0, world=1, **options):
+    def __init__(self, lib, frame_flags=(5, 5, 5), exchange=0, world=1, owned=(1, 1, 1, 1), **options):
         self.L, self.exchange, self.world = lib, exchange, world
-        src, dst, own = np.array(SRC, np.int32), np.array(DST, np.int32), np.ones(4, np.uint8)
+        src, dst, own = np.array(SRC, np.int32), np.array(DST, np.int32), np.array(owned, np.uint8)
         self.h = lib.plan_new(3, 4, src.ctypes.data, dst.ctypes.data, own.ctypes.data)
         for k in range(3):
             lib.plan_set_frame(self.h, k, NPTS[k], 1.0, CELL, frame_flags[k])
@@ -91,6 +91,8 @@ class Planner:
         rows = [tuple(int(v) for v in ints[e]) + (int(np.sign(reals[e, 0])), float(reals[e, 1]), float(reals[e, 2])) for e in range(4)]
         self.spec_arm = out.spec_arm
         self.active = [int(ints[e, 0]) for e in range(4)]
+        if self.exchange:      # the exchanged buffer holds every rank's searched edges
+            self.active = [int(not ints[e, 1]) for e in range(4)]
         return g, rows, [int(v) for v in need[:out.n_tie_need]]
 
     def finish(self, d, tie=0, far=0, armed=None, redone=0):
@@ -266,6 +268,30 @@ def test_fixed_point_with_an_exchange_configured(planner):
     assert P.finish(0.07, armed=2.0) == 1
     P.plan(p(0.106))
     assert P.finish(0.07, armed=2.0, redone=1) == 0              # the select was redone: the queued evaluation used the failed select's scales
+
+
+def test_with_an_exchange_the_bracket_waits_for_the_peers_edges(planner):
+    """Two ranks; this one owns edges 0 and 1, the peer edges 2 and 3.  The medians of all edges arrive exchanged.  This rank's edge 1 has
+    settled, the peer's edge 3 has not: no bracket here either -- the decision a single process takes, which holds all four -- so that no
+    rank arms a bracket that another rank's median then leaves.  Once edge 3 has settled the bracket is on, for the edges this rank owns."""
+    P = planner(exchange=1, world=2, owned=(1, 1, 0, 0))
+    P.plan(p(0.1)); P.finish(0.07)
+    g, r, _ = P.plan(p(0.1))
+    assert [row[0] for row in r] == [0, 1, 0, 0] and [row[1] for row in r] == [1, 0, 0, 0]      # (active: owned and searched; src_fixed)
+    P.finish([0.07, 0.07, 0.07, 0.08])
+    g, r, _ = P.plan(p(0.1))
+    m = 0.07 * 0.07
+    assert g["use_bracket"] == 0 and [row[7:] for row in r] == [(0.0, 0.0), (m * 0.994, m * 1.006), (0.0, 0.0), (0.0, 0.0)]
+    P.finish([0.07, 0.07, 0.07, 0.08])
+    g, r, _ = P.plan(p(0.1))
+    assert g["use_bracket"] == 1 and [row[7:] for row in r] == [(0.0, 0.0), (m * 0.994, m * 1.006), (0.0, 0.0), (0.0, 0.0)]
+    # and the same medians with every edge owned (a single process): the same two decisions
+    Q = planner()
+    Q.plan(p(0.1)); Q.finish(0.07)
+    Q.plan(p(0.1)); Q.finish([0.07, 0.07, 0.07, 0.08])
+    assert Q.plan(p(0.1))[0]["use_bracket"] == 0
+    Q.finish([0.07, 0.07, 0.07, 0.08])
+    assert Q.plan(p(0.1))[0]["use_bracket"] == 1
 
 
 def test_cutoff_change(planner):
