@@ -700,6 +700,44 @@ long long mvicp_fit_normals(mvicp_ctx* ctx, int frame, int max_nn, double radius
  * MVICP_ERR_STATE. */
 int mvicp_normals_fit_fetch(mvicp_ctx* ctx, long long cap_rows, unsigned char* fitted);
 
+/* ---- Jet smoothing and surface curvatures, exactly specified -----------------------------------------------------------------------------
+ * No other stage moves a point, so sensor noise along the surface normal reaches the normals, the descriptors, the objective and the fused
+ * model unchanged.  mvicp_smooth_points continues the fit of mvicp_fit_normals by one row of its back substitution, to a_0: the height of
+ * the fitted polynomial at the point, i.e. the distance from the point to the fitted surface along the PCA normal.  It moves the point there
+ * (CGAL's jet_smooth_point_set, the unweighted form of moving least squares) and reports the mean and the Gaussian curvature of the
+ * polynomial at the point, which do not depend on the choice of (u, v).  The result is a pure function of the stored bytes, bit for bit
+ * (tests/smoothref.py is the same definition in numpy and as a scalar loop).  Steps 1 to 10 of mvicp_fit_normals
+ * apply word for word, with the same arithmetic rules: fp64, every operation rounded on its own, no fma; only + - x / sqrt, comparisons and
+ * negation occur.  "Fitted" below means fitted = 1 after step 10.  Added are:
+ *   9a Height  the back substitution goes on to m = 0: s = y_0, for q = M-1 .. 1 descending s <- s - L_q0 * a_q; a_0 = s / L_00.
+ *  11 Shift    shift = a_0 * h where the row is fitted and that product is finite, else +0.0.
+ *  12 Projection  x'_b = p_b + shift * n_b for b = 0, 1, 2, with n the PCA normal of step 1 (not the fitted normal), one product and one sum
+ *              per component.  moved = 1 iff the row is fitted, a_0 * h is finite, (max_shift <= 0 or |shift| <= max_shift) and all three
+ *              x'_b are finite; then xyz = x'.  Otherwise moved = 0 and xyz holds p_i's bytes.  shift is reported either way.
+ *  13 Curvatures  where the row is fitted: E = 1.0 + a_1 * a_1, G = 1.0 + a_2 * a_2, F = a_1 * a_2, w2 = E + a_2 * a_2, w = sqrt(w2),
+ *              zxx = (a_3 + a_3) / h, zxy = a_4 / h, zyy = (a_5 + a_5) / h,
+ *              H = ((G * zxx - (F + F) * zxy) + E * zyy) / ((w2 * w) + (w2 * w)), K = (zxx * zyy - zxy * zxy) / (w2 * w2).
+ *              H is positive where the surface bends towards n: a sphere seen from outside has H = -1/R, K = 1/R^2.  If the row is not
+ *              fitted, or H or K is not finite, both are +0.0.  No NaN reaches an output.
+ * Arguments: those of mvicp_fit_normals, and max_shift: <= 0 means no limit, +inf is allowed.
+ * nrm, curvature, used and fitted are exactly mvicp_fit_normals' bytes and live in that call's slot: mvicp_normals_fetch,
+ * mvicp_normals_fit_fetch, mvicp_normals_adopt and mvicp_orient_normals(source = 1) act on them unchanged.  xyz (n x 3 doubles), shift
+ * (n doubles), moved (n bytes), H and K (n doubles each) live in a slot of their own with the same lifetime and drop rules; a later
+ * mvicp_estimate_normals or mvicp_fit_normals drops them.  The frame's stored cloud is NOT changed: smoothing repeatedly is the caller's
+ * loop (fetch xyz, and nrm if wanted, into device memory, mvicp_set_frame_device, call again).  Like the fit the call leaves its internal
+ * search as the context's last neighbour search, is otherwise HISTORY-NEUTRAL and needs NO graph; with several ranks every rank computes
+ * it locally.  Profile scopes: those of the search, "jet_smooth".
+ * RETURNS THE NUMBER OF ROWS n (>= 0) or a negative mvicp_status.
+ * Errors: those of mvicp_fit_normals, and a NaN max_shift -> MVICP_ERR_ARG; argument errors are decided before the context is touched
+ * (earlier results stay). */
+long long mvicp_smooth_points(mvicp_ctx* ctx, int frame, int max_nn, double radius, const double* viewpoint, int degree, double max_shift);
+/* Copies the last mvicp_smooth_points result: xyz (n x 3 doubles), shift (n doubles), moved (n bytes), H, K (n doubles each); each may be
+ * NULL; each may be a HOST pointer or a DEVICE pointer of the context's device, decided per pointer as mvicp_voxel_fetch decides, so xyz
+ * goes straight into mvicp_set_frame_device.  cap_rows = rows the destinations hold.
+ * Errors: NULL context, cap_rows < n -> MVICP_ERR_ARG; the context's last estimate is not a mvicp_smooth_points result, or there is none ->
+ * MVICP_ERR_STATE. */
+int mvicp_smooth_fetch(mvicp_ctx* ctx, long long cap_rows, double* xyz, double* shift, unsigned char* moved, double* H, double* K);
+
 /* ---- Consistent normal orientation without a viewpoint: propagation over a neighbour graph ----------------------------------------
  * mvicp_estimate_normals turns a normal towards a viewpoint, which is right for a range image and for nothing else.  mvicp_orient_normals
  * makes the normals of ONE cloud agree with each other without one (Hoppe et al. 1992): the sign is carried along the maximum spanning

@@ -1360,6 +1360,40 @@ int mvicp_normals_fit_fetch(mvicp_ctx* c, long long cap_rows, unsigned char* fit
   return fetch_parts(c, parts);
 } MVICP_GUARD_ABI
 
+long long mvicp_smooth_points(mvicp_ctx* c, int frame, int max_nn, double radius, const double* viewpoint, int degree, double max_shift) try {
+  // every argument error that needs no GPU first: nothing of the context has been touched when one of them is reported
+  if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
+  if (max_nn < 3 || max_nn > 64) { set_error("max_nn = %d outside [3, 64]", max_nn); return MVICP_ERR_ARG; }
+  if (degree != 2 && degree != 3) { set_error("degree = %d: 2 or 3", degree); return MVICP_ERR_ARG; }
+  if (!std::isfinite(radius)) { set_error("radius must be finite (<= 0: no radius)"); return MVICP_ERR_ARG; }
+  if (std::isnan(max_shift)) { set_error("max_shift is a NaN (<= 0: no limit)"); return MVICP_ERR_ARG; }
+  double vp[3] = {0.0, 0.0, 0.0};
+  for (int a = 0; viewpoint && a < 3; ++a) {
+    if (!std::isfinite(viewpoint[a])) { set_error("viewpoint[%d] is not finite", a); return MVICP_ERR_ARG; }
+    vp[a] = viewpoint[a];
+  }
+  if (frame < 0 || frame >= c->n_frames) { set_error("frame %d out of range [0,%d)", frame, c->n_frames); return MVICP_ERR_ARG; }
+  const FrameDev& f = c->frames[frame];
+  if (!f.pts) { set_error("frame %d was never uploaded", frame); return MVICP_ERR_STATE; }
+  MV_CHECK(bind(c));
+  MV_CHECK(finish_builds(c));
+  const long long rows = smooth_points(c, f, max_nn, radius, radius > 0.0 ? sqrt_bound(radius) : 0.0, vp, degree, max_shift);
+  if (rows >= 0) c->nrm.frame = frame;
+  if (c->profile) prof_collect_lazy(c);
+  return rows;
+} MVICP_GUARD_ABI
+
+int mvicp_smooth_fetch(mvicp_ctx* c, long long cap_rows, double* xyz, double* shift, unsigned char* moved, double* H, double* K) try {
+  if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
+  if (c->nrm.rows < 0 || !c->nrm.has_smooth) { set_error("no smoothed points: the last estimate was not mvicp_smooth_points"); return MVICP_ERR_STATE; }
+  if (cap_rows < c->nrm.rows) { set_error("cap_rows %lld < %lld rows", cap_rows, c->nrm.rows); return MVICP_ERR_ARG; }
+  if (c->nrm.rows == 0) return MVICP_OK;
+  const size_t n = (size_t)c->nrm.rows;
+  const FetchPart parts[] = {{xyz, c->nrm.xyz, 24 * n, "xyz"}, {shift, c->nrm.shift, 8 * n, "shift"}, {moved, c->nrm.moved, n, "moved"},
+                             {H, c->nrm.H, 8 * n, "H"}, {K, c->nrm.K, 8 * n, "K"}};
+  return fetch_parts(c, parts);
+} MVICP_GUARD_ABI
+
 int mvicp_normals_fetch(mvicp_ctx* c, long long cap_rows, double* nrm, double* curvature, int* used) try {
   if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
   if (c->nrm.rows < 0) { set_error("no estimated normals: call mvicp_estimate_normals first"); return MVICP_ERR_STATE; }

@@ -226,15 +226,26 @@ struct IssStage {
   long long n = -1, k = 0; int has_normals = 0;   // points of the frame (< 0: none), keypoints among them
   void release() { dev.release(); tmp.release(); pin.release(); *this = IssStage(); }
 };
-// normals_pca.hip, normals_jet.hip.  dev: [nrm n x 3 doubles | curvature n doubles | used n ints | fitted n bytes, after mvicp_fit_normals only];
+// normals_pca.hip, normals_jet.hip, smooth.hip.  dev: [nrm n x 3 doubles | curvature n doubles | used n ints | fitted n bytes, after mvicp_fit_normals only];
 // the neighbourhoods are the KnnStage result of the search the call runs.  frame: the slot the result was computed for (mvicp_normals_adopt
-// writes there); an upload to that slot drops the result.  has_fit: the result is mvicp_fit_normals' (mvicp_normals_fit_fetch serves it)
+// writes there); an upload to that slot drops the result.  has_fit: the result is mvicp_fit_normals' or mvicp_smooth_points'
+// (mvicp_normals_fit_fetch serves it).  smooth.hip adds smo: [xyz n x 3 doubles | shift | H | K n doubles each | moved n bytes], the part of
+// a mvicp_smooth_points result that mvicp_smooth_fetch serves (has_smooth); it lives and ends with the rest of the result
 struct NormalsStage {
-  DevBuf dev;
+  DevBuf dev, smo;
   double* nrm = nullptr; double* curv = nullptr; int* used = nullptr; unsigned char* fitted = nullptr;
-  long long rows = -1; int frame = -1, has_fit = 0;   // rows < 0: none
-  void drop_result() { rows = -1; frame = -1; has_fit = 0; }
-  void release() { dev.release(); *this = NormalsStage(); }
+  double* xyz = nullptr; double* shift = nullptr; double* H = nullptr; double* K = nullptr; unsigned char* moved = nullptr;
+  long long rows = -1; int frame = -1, has_fit = 0, has_smooth = 0;   // rows < 0: none
+  void drop_result() { rows = -1; frame = -1; has_fit = 0; has_smooth = 0; }
+  // the layout of dev for a result of N rows with the fitted bytes
+  int reserve_fit(size_t N) {
+    const size_t off_curv = align256(24 * N), off_used = off_curv + align256(8 * N), off_fit = off_used + align256(4 * N);
+    MV_CHECK(dev.reserve(off_fit + align256(N)));
+    nrm = reinterpret_cast<double*>(dev.p); curv = reinterpret_cast<double*>(dev.p + off_curv);
+    used = reinterpret_cast<int*>(dev.p + off_used); fitted = reinterpret_cast<unsigned char*>(dev.p + off_fit);
+    return MVICP_OK;
+  }
+  void release() { dev.release(); smo.release(); *this = NormalsStage(); }
 };
 
 // orient.hip.  dev: [nrm n x 3 doubles | comp n ints | flip n bytes | the work arrays of the Boruvka rounds], pin: the counters the host
@@ -565,6 +576,9 @@ long long iss_keypoints(mvicp_ctx* c, const FrameDev& f, double B2_salient, doub
 long long normals_estimate(mvicp_ctx* c, const FrameDev& f, int max_nn, double radius, double B2, const double* viewpoint);
 // normals_jet.hip: the same with the jet fit of `degree` (2 or 3) behind the PCA part; the result replaces c->nrm's and carries the fitted bytes.
 long long normals_fit(mvicp_ctx* c, const FrameDev& f, int max_nn, double radius, double B2, const double* viewpoint, int degree);
+// smooth.hip: the same search and fit, continued to the height a_0: the points moved onto the fitted surface along the PCA normal (max_shift
+// <= 0: no limit) and the mean and Gaussian curvature.  c->nrm holds normals_fit's bytes and, in its smo part, the smoothing result.
+long long smooth_points(mvicp_ctx* c, const FrameDev& f, int max_nn, double radius, double B2, const double* viewpoint, int degree, double max_shift);
 // normals_pca.hip: nrm (f.n rows, device memory) into f.nor and f.grid.snor (both allocated, f.n > 0, structures built).  Waits for the stream.
 int normals_adopt(mvicp_ctx* c, FrameDev& f, const double* nrm);
 // orient.hip: knn_search(c, f, null, 0, 0, k, radius, B2) and the propagation over its rows for the normals N (f.n x 3, device memory) of

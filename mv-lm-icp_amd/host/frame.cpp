@@ -632,6 +632,33 @@ std::shared_ptr<Frame> Frame::removeOutliers(int k, double std_ratio, double rad
   return out;
 }
 
+std::shared_ptr<Frame> Frame::smoothPoints(int max_nn, double radius, int degree, double max_shift, const Vector3d& viewpoint, std::vector<double>* shift,
+                                           std::vector<unsigned char>* moved) {
+  std::shared_ptr<Frame> out(new Frame());
+  out->fixed = fixed; out->pose = pose; out->poseGroundTruth = poseGroundTruth;
+  for (const OutgoingEdge& e : neighbours) out->neighbours.push_back(OutgoingEdge{e.neighbourIdx, e.weight, {}});
+  if (shift) shift->clear();
+  if (moved) moved->clear();
+  if (pts.empty()) return out;
+  int slot = 0;
+  mvicp_ctx* c = Session::get().query_context(this, &slot);
+  const long long n = mvicp_smooth_points(c, slot, max_nn, radius, viewpoint.data(), degree, max_shift);
+  if (n < 0) check((int)n);
+  out->pts.assign((size_t)n, Vector3d());
+  if (shift) shift->assign((size_t)n, 0.0);
+  if (moved) moved->assign((size_t)n, 0);
+  check(mvicp_smooth_fetch(c, n, out->pts[0].data(), shift ? shift->data() : nullptr, moved ? moved->data() : nullptr, nullptr, nullptr));
+  if (nor.size() == pts.size()) {
+    out->nor.assign((size_t)n, Vector3d());
+    check(mvicp_normals_fetch(c, n, out->nor[0].data(), nullptr, nullptr));
+    for (size_t i = 0; i < (size_t)n; ++i) {
+      Vector3d& g = out->nor[i];
+      if ((g[0] * nor[i][0] + g[1] * nor[i][1]) + g[2] * nor[i][2] < 0.0) g = Vector3d(-g[0], -g[1], -g[2]);
+    }
+  }
+  return out;
+}
+
 std::shared_ptr<Frame> Frame::removeSmallClusters(double radius, int min_pts, long long min_size, long long max_clusters, long long* clusters,
                                                   long long* kept_clusters) {
   std::shared_ptr<Frame> out(new Frame());

@@ -104,6 +104,16 @@ class Frame {
   // pose, poseGroundTruth, fixed and neighbours (index and weight; the correspondence lists start empty).  Runs in the context
   // Session::query_context finds for this frame (bin/multiview --sor_k / --sor_ratio / --ror_radius).
   std::shared_ptr<Frame> removeOutliers(int k, double std_ratio, double radius);
+  // A smoothed copy of this frame (no counterpart in the reference): mvicp_smooth_points on this cloud as it is stored -- every point moved
+  // onto the height polynomial of `degree` 2 or 3 fitted through its max_nn nearest neighbours (radius > 0: within it), along its PCA normal;
+  // a point whose fit is refused, or whose shift exceeds max_shift > 0, stays where it is.  The new Frame has the moved pts in their
+  // original order and the same pose, poseGroundTruth, fixed and neighbours (index and weight; the correspondence lists start empty).  If
+  // this frame has normals the new one has the call's fitted normals, each negated where it points against this frame's own (dot product
+  // below 0), so the frame's orientation survives; otherwise it has none.  shift / moved, if given, receive the call's signed shifts and
+  // moved bytes.  Runs in the context Session::query_context finds for this frame (bin/multiview --smooth_nn / --smooth_radius /
+  // --smooth_degree / --smooth_iters / --smooth_max_shift).
+  std::shared_ptr<Frame> smoothPoints(int max_nn, double radius, int degree, double max_shift, const Vector3d& viewpoint = Vector3d(),
+                                      std::vector<double>* shift = nullptr, std::vector<unsigned char>* moved = nullptr);
   // A copy of this frame without its small clusters (no counterpart in the reference): mvicp_cluster on this cloud as it is stored -- DBSCAN
   // with the strict radius predicate, the point itself counting towards min_pts -- and mvicp_cluster_select: the points of the clusters with
   // at least min_size members, of those only the max_clusters largest (0: all of them); noise always goes.  The new Frame has the kept

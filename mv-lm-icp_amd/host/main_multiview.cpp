@@ -62,6 +62,13 @@
 // --normals_fit D (default 0 = off; D = 2 or 3, needs --normals_nn K): Frame::fitNormals(K, R, D) in place of Frame::estimateNormals(K, R) -- the
 // same normals corrected by the slope of a height polynomial of degree D fitted over the tangent plane (mvicp_fit_normals).  Composes with
 // --normals_orient and --symmetric.
+// --smooth_nn K [--smooth_radius R] [--smooth_degree D] [--smooth_iters I] [--smooth_max_shift S] (default K = 0 = off; R = 0 = no radius, D = 2,
+// I = 1, S = 0 = no limit): with K > 0 every frame is smoothed after the cluster filter and before the normals step, I times over, by
+// Frame::smoothPoints(K, R, D, S): mvicp_smooth_points moves every point onto the height polynomial of degree D fitted through its K nearest
+// neighbours, along its PCA normal (jet smoothing), unless that moves it by more than S.  Sensor noise along the normal, which every later
+// stage otherwise receives unchanged, goes here.  A frame with normals keeps their orientation.  One line per frame, `smooth: frame i moved
+// a of b, largest |shift| s` (the last pass; %.17g; printed with --quiet too).  D outside {2, 3}, I < 1 and a --smooth_* flag without
+// --smooth_nn are refused.
 // --normals_orient mst [--orient_nn K] (default off; K = 10): consistent orientation WITHOUT a viewpoint, for clouds whose frame origin is no
 // sensor.  Per frame, after the normals step: Frame::orientNormals(K) (mvicp_orient_normals: the signs are carried along the maximum spanning
 // forest of the K-nearest-neighbour graph weighted by |n_i . n_j|); then once across the frames, at the start poses, after the graph is built
@@ -138,6 +145,21 @@ static void loadFrames(const Flags& F, std::vector<std::shared_ptr<Frame>>& fram
       f->pts.swap(kept->pts); f->nor.swap(kept->nor); ++f->version;   // (a context that holds the old cloud re-uploads)
       std::cout << "cluster filter: frame " << frames.size() << " kept " << f->pts.size() << " of " << before << ", " << stay << " of " << found << " clusters" << std::endl;
     }
+    if (F.i("smooth_nn", 0) > 0) {
+      std::vector<double> shift;
+      std::vector<unsigned char> moved;
+      for (int pass = 0; pass < F.i("smooth_iters", 1); ++pass) {
+        std::shared_ptr<Frame> smooth = f->smoothPoints(F.i("smooth_nn", 0), F.f("smooth_radius", 0.0), F.i("smooth_degree", 2), F.f("smooth_max_shift", 0.0),
+                                                        Vector3d(), &shift, &moved);
+        f->pts.swap(smooth->pts); f->nor.swap(smooth->nor); ++f->version;   // (a context that holds the old cloud re-uploads)
+      }
+      size_t count = 0;
+      double largest = 0.0;
+      for (size_t j = 0; j < moved.size(); ++j) { count += moved[j]; largest = std::max(largest, std::fabs(shift[j])); }
+      char line[160];
+      std::snprintf(line, sizeof(line), "smooth: frame %zu moved %zu of %zu, largest |shift| %.17g", frames.size(), count, f->pts.size(), largest);
+      std::cout << line << std::endl;
+    }
     if (F.i("normals_nn", 0) > 0 && F.i("normals_fit", 0)) f->fitNormals(F.i("normals_nn", 0), F.f("normals_radius", 0.0), F.i("normals_fit", 0));
     else if (F.i("normals_nn", 0) > 0) f->estimateNormals(F.i("normals_nn", 0), F.f("normals_radius", 0.0));   // (viewpoint: the view's own origin)
     else if (F.b("recomputeNormals", true)) f->recomputeNormals();  // main_multiview.cpp:49,68-70 (default on)
@@ -172,6 +194,10 @@ int main(int argc, char** argv) {
   if (!F.s("normals_orient", "").empty() && F.s("normals_orient", "") != "mst") { std::cerr << "--normals_orient must be mst" << std::endl; return 1; }
   if (F.i("normals_fit", 0) != 0 && F.i("normals_fit", 0) != 2 && F.i("normals_fit", 0) != 3) { std::cerr << "--normals_fit must be 2 or 3" << std::endl; return 1; }
   if (F.i("normals_fit", 0) != 0 && F.i("normals_nn", 0) <= 0) { std::cerr << "--normals_fit needs --normals_nn K" << std::endl; return 1; }
+  for (const char* name : {"smooth_radius", "smooth_degree", "smooth_iters", "smooth_max_shift"})
+    if (!F.s(name, "").empty() && F.i("smooth_nn", 0) <= 0) { std::cerr << "--" << name << " needs --smooth_nn K" << std::endl; return 1; }
+  if (F.i("smooth_degree", 2) != 2 && F.i("smooth_degree", 2) != 3) { std::cerr << "--smooth_degree must be 2 or 3" << std::endl; return 1; }
+  if (F.i("smooth_iters", 1) < 1) { std::cerr << "--smooth_iters must be at least 1" << std::endl; return 1; }
   const bool reject_boundary = F.b("reject_boundary", false);
   const int boundary_nn = F.i("boundary_nn", 30);
   const double boundary_radius = F.f("boundary_radius", 0.0), boundary_cos = F.f("boundary_cos", -0.5);

@@ -6,4 +6,4 @@
 `io`    : the reference's on-disk formats (.xyz clouds, 4x4 row-major pose text).
 """
 from . import lib, synth, io  # noqa: F401
-from .lib import Engine, MvicpError, load_library, graph_from_overlap, overlap_sample_indices, outlier_threshold, cluster_keep_rule, plane_from_moments, reject_by_mask, cache_allowance, match_pairs, coarse_align, poses_from_pairs, init_from_clouds, signs_from_agreement, orient_frames  # noqa: F401
+from .lib import Engine, MvicpError, load_library, graph_from_overlap, overlap_sample_indices, outlier_threshold, cluster_keep_rule, plane_from_moments, reject_by_mask, cache_allowance, match_pairs, coarse_align, poses_from_pairs, init_from_clouds, signs_from_agreement, orient_frames, principal_curvatures  # noqa: F401

@@ -28,6 +28,7 @@ SYMBOLS = [
     "mvicp_set_reject_mask", "mvicp_boundary_adopt", "mvicp_get_reject_mask",
     "mvicp_knn_search", "mvicp_knn_fetch", "mvicp_fpfh", "mvicp_fpfh_fetch", "mvicp_iss_keypoints", "mvicp_iss_fetch",
     "mvicp_estimate_normals", "mvicp_normals_fetch", "mvicp_normals_adopt", "mvicp_fit_normals", "mvicp_normals_fit_fetch",
+    "mvicp_smooth_points", "mvicp_smooth_fetch",
     "mvicp_orient_normals", "mvicp_orient_fetch", "mvicp_orient_adopt", "mvicp_normal_agreement", "mvicp_signs_from_agreement", "mvicp_negate_normals",
     "mvicp_feature_match", "mvicp_feature_match_fetch", "mvicp_match_pairs", "mvicp_consensus", "mvicp_consensus_fetch",
     "mvicp_coarse_pairs", "mvicp_coarse_pairs_fetch", "mvicp_poses_from_pairs",
@@ -200,6 +201,9 @@ def load_library(path=None):
     lib.mvicp_fit_normals.argtypes = [vp, C.c_int, C.c_int, C.c_double, dp, C.c_int]
     lib.mvicp_fit_normals.restype = C.c_longlong
     lib.mvicp_normals_fit_fetch.argtypes = [vp, C.c_longlong, vp]
+    lib.mvicp_smooth_points.argtypes = [vp, C.c_int, C.c_int, C.c_double, dp, C.c_int, C.c_double]
+    lib.mvicp_smooth_points.restype = C.c_longlong
+    lib.mvicp_smooth_fetch.argtypes = [vp, C.c_longlong, vp, vp, vp, vp, vp]
     lib.mvicp_orient_normals.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, dp]
     lib.mvicp_orient_normals.restype = C.c_longlong
     lib.mvicp_orient_fetch.argtypes = [vp, C.c_longlong, vp, vp, vp]
@@ -456,6 +460,15 @@ def poses_from_pairs(n_frames, src, dst, count, pose, min_count=0, root=0, root_
                                                 _dp(out), _ip(parent), _ip(pedge), _ip(comp)))
     return {"poses": poses_from_c(out[:K]), "parent": parent[:K].copy(), "parent_edge": pedge[:K].copy(), "component": comp[:K].copy(),
             "components": int(nc)}
+
+
+def principal_curvatures(H, K):
+    """The principal curvatures (k1 >= k2) from the mean curvature H and the Gaussian curvature K of Engine.smooth_points: D = H * H - K (a
+    negative D, which only rounding produces, counts as 0), r = sqrt(D) -> (H + r, H - r).  numpy only."""
+    H, K = np.asarray(H, dtype=np.float64), np.asarray(K, dtype=np.float64)
+    D = H * H - K
+    r = np.sqrt(np.where(D < 0, 0.0, D))
+    return H + r, H - r
 
 
 def signs_from_agreement(n_frames, src, dst, pos, neg, min_count=0):
@@ -1122,6 +1135,28 @@ class Engine:
         _check(self.lib, self.lib.mvicp_normals_fetch(self.h, n, ptr(nrm), ptr(curv), ptr(used)))
         _check(self.lib, self.lib.mvicp_normals_fit_fetch(self.h, n, ptr(fitted)))
         return {"nrm": nrm, "curvature": curv, "used": used, "fitted": fitted}
+
+    def smooth_points(self, frame, max_nn=30, radius=0.0, viewpoint=None, degree=2, max_shift=0.0, device=False):
+        """mvicp_smooth_points + mvicp_smooth_fetch + the two normals fetches on the stored cloud of `frame`: every point moved onto the
+        height polynomial of `degree` 2 or 3 fitted through its max_nn nearest neighbours, along its PCA normal (jet smoothing), and the
+        mean and Gaussian curvature of that polynomial -> dict(xyz (n,3) float64 = the moved points, shift (n,) float64 = the signed
+        distance moved along the PCA normal, moved (n,) uint8 = 0 where the row was not fitted or |shift| > max_shift > 0 (xyz is then the
+        stored point), H, K (n,) float64 (H > 0 where the surface bends towards the normal; see principal_curvatures), and nrm, curvature,
+        used, fitted exactly as fit_normals returns them).  device=True: torch tensors on the engine's GPU, ready for set_frame_device.
+        The stored cloud is untouched.  The result takes the place of the last estimate_normals / fit_normals: adopt_normals() and
+        orient_normals(source=1) act on its nrm.  Afterwards the engine's last neighbour-search result is knn_search(frame, None, max_nn,
+        radius).  Needs no graph; history-neutral."""
+        vp = None if viewpoint is None else np.ascontiguousarray(viewpoint, dtype=np.float64).reshape(3)
+        n = int(_check(self.lib, self.lib.mvicp_smooth_points(self.h, int(frame), int(max_nn), float(radius), _dp(vp) if vp is not None else None,
+                                                              int(degree), float(max_shift))))
+        mk, ptr, ready, f64, i32, i64, u8 = self._result_arrays(device)
+        nrm, curv, used, fitted = mk((n, 3), f64), mk((n,), f64), mk((n,), i32), mk((n,), u8)
+        xyz, shift, moved, H, K = mk((n, 3), f64), mk((n,), f64), mk((n,), u8), mk((n,), f64), mk((n,), f64)
+        ready()
+        _check(self.lib, self.lib.mvicp_normals_fetch(self.h, n, ptr(nrm), ptr(curv), ptr(used)))
+        _check(self.lib, self.lib.mvicp_normals_fit_fetch(self.h, n, ptr(fitted)))
+        _check(self.lib, self.lib.mvicp_smooth_fetch(self.h, n, ptr(xyz), ptr(shift), ptr(moved), ptr(H), ptr(K)))
+        return {"xyz": xyz, "nrm": nrm, "curvature": curv, "used": used, "fitted": fitted, "shift": shift, "moved": moved, "H": H, "K": K}
 
     def adopt_normals(self):
         """mvicp_normals_adopt: the frame of the last estimate_normals or fit_normals takes that result as its normals, as recompute_normals would
