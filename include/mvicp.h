@@ -213,7 +213,7 @@ int mvicp_voxel_fetch(mvicp_ctx* ctx, long long cap, double* xyz, double* nrm, i
 typedef struct mvicp_outlier_stats {
   long long n, kept;
   int q_exp;
-  int has_normals;   /* the frame has normals: mvicp_outlier_fetch gives nrm */
+  int has_normals;   /* the frame had stored normals at this call: mvicp_outlier_fetch gives nrm (the filter selects in the same call) */
   unsigned long long s1, s2_hi, s2_lo;
   double T;          /* the threshold in quantised units (compared with (double)M_i) */
   double threshold;  /* ldexp(T, -q_exp): the same in the cloud's length unit */
@@ -266,7 +266,8 @@ typedef struct mvicp_cluster_stats {
   long long n, clusters, core, border, noise;   /* core + border + noise = n */
   long long largest;                            /* size of the largest cluster (0 when there is none) */
   int largest_label;
-  int has_normals;                              /* the frame has normals: mvicp_cluster_fetch_kept gives nrm */
+  int has_normals;                              /* the frame had stored normals at this call.  What mvicp_cluster_fetch_kept gives is decided when
+                                                   mvicp_cluster_select runs: nrm iff the frame has stored normals THEN (an adopt in between counts) */
 } mvicp_cluster_stats;
 long long mvicp_cluster(mvicp_ctx* ctx, int frame, double radius, int min_pts, mvicp_cluster_stats* stats);
 /* Copies the last result: label (n ints), core (n bytes), size (C ints); each may be NULL; each may be a HOST pointer or a DEVICE pointer of
@@ -340,7 +341,8 @@ typedef struct mvicp_plane_result {
   int refit;                         /* 1: normal / point / flags are the refitted plane's */
   int count_refined;                 /* the flags set */
   int b, q;                          /* the refit's bit budget and scale exponent (0 without a refit) */
-  int has_normals;                   /* the frame has normals: mvicp_plane_fetch_kept gives nrm */
+  int has_normals;                   /* the frame had stored normals at this call.  What mvicp_plane_fetch_kept gives is decided when
+                                        mvicp_plane_select runs: nrm iff the frame has stored normals THEN (an adopt in between counts) */
   long long n;                       /* points of the frame */
   double normal[3], point[3], d;     /* the plane dot(normal, x) + d = 0 through point; d = -dot(normal, point) */
   double hyp_normal[3], hyp_point[3];/* the winning hypothesis's own m and a */

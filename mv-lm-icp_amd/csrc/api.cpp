@@ -591,6 +591,15 @@ int mvicp_set_num_frames(mvicp_ctx* c, int n_frames) try {
   return MVICP_OK;
 } MVICP_GUARD_ABI
 
+// the results that an upload to `frame` ends: every stage that remembers the frame it was computed for
+static void drop_results_of(mvicp_ctx* c, int frame) {
+  if (c->nrm.frame == frame) c->nrm.drop_result();   // (estimated normals of the cloud the upload replaces: nothing to adopt them into)
+  if (c->ori.frame == frame) c->ori.drop_result();   // (and its oriented normals)
+  if (c->clu.frame == frame) c->clu.drop_result();   // (and its clusters: a selection would read the new rows)
+  if (c->plane.frame == frame) c->plane.drop_result();   // (and its plane, for the same reason)
+  if (c->bnd.frame == frame) c->bnd.drop_result();   // (and its boundary points, for the same reason)
+}
+
 int mvicp_set_frame(mvicp_ctx* c, int frame, const double* xyz, const double* nrm, int n) try {
   MV_CHECK(bind(c));
   if (frame < 0 || frame >= c->n_frames) { set_error("frame %d out of range [0,%d)", frame, c->n_frames); return MVICP_ERR_ARG; }
@@ -604,11 +613,7 @@ int mvicp_set_frame(mvicp_ctx* c, int frame, const double* xyz, const double* nr
     max_norm = std::max(max_norm, std::sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]));
   }
   FrameDev& f = c->frames[frame];
-  if (c->nrm.frame == frame) c->nrm.drop_result();   // (estimated normals of the cloud this call replaces: nothing to adopt them into)
-  if (c->ori.frame == frame) c->ori.drop_result();   // (and its oriented normals)
-  if (c->clu.frame == frame) c->clu.drop_result();   // (and its clusters: a selection would read the new rows)
-  if (c->plane.frame == frame) c->plane.drop_result();   // (and its plane, for the same reason)
-  if (c->bnd.frame == frame) c->bnd.drop_result();   // (and its boundary points, for the same reason)
+  drop_results_of(c, frame);
   if (f.job) { try { (void)f.job->fut.get(); } catch (...) {} f.job.reset(); }   // a build of the cloud this call replaces
   dev_free(f.pts); dev_free(f.nor); free_grid(f.grid); free_tie(f);
   f.has_grid = false; f.build_error.clear();
@@ -687,11 +692,7 @@ int mvicp_set_frame_device(mvicp_ctx* c, int frame, const double* d_xyz, const d
     if (b.nonfinite) { set_error("non-finite coordinate in cloud"); return MVICP_ERR_ARG; }
   }
   FrameDev& f = c->frames[frame];
-  if (c->nrm.frame == frame) c->nrm.drop_result();   // (estimated normals of the cloud this call replaces: nothing to adopt them into)
-  if (c->ori.frame == frame) c->ori.drop_result();   // (and its oriented normals)
-  if (c->clu.frame == frame) c->clu.drop_result();   // (and its clusters: a selection would read the new rows)
-  if (c->plane.frame == frame) c->plane.drop_result();   // (and its plane, for the same reason)
-  if (c->bnd.frame == frame) c->bnd.drop_result();   // (and its boundary points, for the same reason)
+  drop_results_of(c, frame);
   if (f.job) { try { (void)f.job->fut.get(); } catch (...) {} f.job.reset(); }   // a build of the cloud this call replaces
   dev_free(f.pts); dev_free(f.nor); free_grid(f.grid); free_tie(f);
   f.has_grid = false; f.build_error.clear();
@@ -949,6 +950,45 @@ static int fetch_parts(mvicp_ctx* c, const FetchPart (&parts)[N]) {
 }
 }  // extern "C++"
 
+// The kept rows of a stage's selection (the stage's own "no result" check comes first, in the caller), and in the same fetch the stage's
+// per-point arrays of n rows each (`more`; at most three).  The texts that differ between the entry points: cap_name / what ("cap_kept", "kept
+// rows"), select_call (what makes a selection), no_normals (the whole message).
+static int fetch_kept(mvicp_ctx* c, const RowSelection& sel, long long cap, double* xyz, double* nrm, int* idx, int* label, const char* cap_name, const char* what,
+                      const char* select_call, const char* no_normals, long long cap_n = 0, long long n = 0, std::initializer_list<FetchPart> more = {}) {
+  if (sel.kept < 0) { set_error("no selection: call %s first", select_call); return MVICP_ERR_STATE; }
+  if (cap < sel.kept) { set_error("%s %lld < %lld %s", cap_name, cap, sel.kept, what); return MVICP_ERR_ARG; }
+  const size_t m = (size_t)sel.kept;
+  FetchPart parts[7] = {{xyz, sel.xyz, 24 * m, "xyz"}, {nrm, sel.nrm, 24 * m, "nrm"}, {idx, sel.idx, 4 * m, "idx"}, {label, sel.klabel, 4 * m, "label"}};
+  bool per_point = false;
+  int t = 4;
+  for (const FetchPart& p : more) { parts[t++] = p; per_point = per_point || p.dst; }
+  if (per_point && cap_n < n) { set_error("cap_n %lld < %lld points", cap_n, n); return MVICP_ERR_ARG; }
+  if (nrm && !sel.has_normals) { set_error("%s", no_normals); return MVICP_ERR_STATE; }
+  if (m == 0 && n == 0) return MVICP_OK;
+  return fetch_parts(c, parts);
+}
+
+// the frame a result of n rows was computed for is still the cloud it was computed for (an upload to it drops the result; mvicp_set_num_frames
+// can take the slot away)
+static bool frame_unchanged(const mvicp_ctx* c, int frame, long long n) {
+  return frame >= 0 && frame < c->n_frames && c->frames[frame].n == n && (n == 0 || c->frames[frame].pts);
+}
+
+// the normals a stage reads for frame f: source 0 the frame's stored ones (`missing`: what to say when it has none), 1 the last estimate of this frame
+static int normals_source(mvicp_ctx* c, int frame, const FrameDev& f, int source, const char* missing, const double** N) {
+  if (source == 0) {
+    if (f.n > 0 && !f.nor) { set_error("frame %d has no normals%s", frame, missing); return MVICP_ERR_STATE; }
+    *N = f.nor;
+  } else {
+    if (c->nrm.rows < 0 || c->nrm.frame != frame || c->nrm.rows != f.n) {
+      set_error("no estimated normals of frame %d: call mvicp_estimate_normals on it first (an upload to the frame drops the result)", frame);
+      return MVICP_ERR_STATE;
+    }
+    *N = c->nrm.nrm;
+  }
+  return MVICP_OK;
+}
+
 int mvicp_voxel_fetch(mvicp_ctx* c, long long cap, double* xyz, double* nrm, int* cnt) try {
   if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
   if (c->vox.m < 0) { set_error("no voxel grid: call mvicp_voxel_grid first"); return MVICP_ERR_STATE; }
@@ -980,14 +1020,9 @@ long long mvicp_outlier_filter(mvicp_ctx* c, int frame, int k, double std_ratio,
 int mvicp_outlier_fetch(mvicp_ctx* c, long long cap_kept, double* xyz, double* nrm, int* idx, long long cap_n, double* mdist, double* kd2) try {
   if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
   if (c->out.n < 0) { set_error("no outlier result: call mvicp_outlier_filter first"); return MVICP_ERR_STATE; }
-  if (cap_kept < c->out.kept) { set_error("cap_kept %lld < %lld kept rows", cap_kept, c->out.kept); return MVICP_ERR_ARG; }
-  if ((mdist || kd2) && cap_n < c->out.n) { set_error("cap_n %lld < %lld points", cap_n, c->out.n); return MVICP_ERR_ARG; }
-  if (nrm && !c->out.has_normals) { set_error("the filtered frame has no normals"); return MVICP_ERR_STATE; }
-  if (c->out.n == 0) return MVICP_OK;
-  const size_t m = (size_t)c->out.kept, n = (size_t)c->out.n;
-  const FetchPart parts[] = {{xyz, c->out.xyz, 24 * m, "xyz"}, {nrm, c->out.nrm, 24 * m, "nrm"}, {idx, c->out.idx, 4 * m, "idx"},
-                             {mdist, c->out.mdist, 8 * n, "mdist"}, {kd2, c->out.kd2, 8 * n, "kd2"}};
-  return fetch_parts(c, parts);
+  const size_t n = (size_t)c->out.n;
+  return fetch_kept(c, c->out.sel, cap_kept, xyz, nrm, idx, nullptr, "cap_kept", "kept rows", "mvicp_outlier_filter", "the filtered frame has no normals", cap_n, c->out.n,
+                    {{mdist, c->out.mdist, 8 * n, "mdist"}, {kd2, c->out.kd2, 8 * n, "kd2"}});
 } MVICP_GUARD_ABI
 
 long long mvicp_cluster(mvicp_ctx* c, int frame, double radius, int min_pts, mvicp_cluster_stats* stats) try {
@@ -1020,7 +1055,7 @@ long long mvicp_cluster_select(mvicp_ctx* c, long long min_size, long long max_c
   if (min_size < 0 || max_clusters < 0) { set_error("min_size and max_clusters must be >= 0"); return MVICP_ERR_ARG; }
   if (c->clu.n < 0) { set_error("no cluster result: call mvicp_cluster first"); return MVICP_ERR_STATE; }
   const int frame = c->clu.frame;
-  if (frame < 0 || frame >= c->n_frames || c->frames[frame].n != c->clu.n || (c->clu.n > 0 && !c->frames[frame].pts)) {
+  if (!frame_unchanged(c, frame, c->clu.n)) {
     set_error("the clustered frame is gone: call mvicp_cluster again");
     return MVICP_ERR_STATE;
   }
@@ -1033,13 +1068,7 @@ long long mvicp_cluster_select(mvicp_ctx* c, long long min_size, long long max_c
 int mvicp_cluster_fetch_kept(mvicp_ctx* c, long long cap, double* xyz, double* nrm, int* idx, int* label) try {
   if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
   if (c->clu.n < 0) { set_error("no cluster result: call mvicp_cluster first"); return MVICP_ERR_STATE; }
-  if (c->clu.kept < 0) { set_error("no selection: call mvicp_cluster_select first"); return MVICP_ERR_STATE; }
-  if (cap < c->clu.kept) { set_error("cap %lld < %lld kept rows", cap, c->clu.kept); return MVICP_ERR_ARG; }
-  if (nrm && !c->clu.has_normals) { set_error("the clustered frame has no normals"); return MVICP_ERR_STATE; }
-  if (c->clu.kept == 0) return MVICP_OK;
-  const size_t m = (size_t)c->clu.kept;
-  const FetchPart parts[] = {{xyz, c->clu.xyz, 24 * m, "xyz"}, {nrm, c->clu.nrm, 24 * m, "nrm"}, {idx, c->clu.idx, 4 * m, "idx"}, {label, c->clu.klabel, 4 * m, "label"}};
-  return fetch_parts(c, parts);
+  return fetch_kept(c, c->clu.sel, cap, xyz, nrm, idx, label, "cap", "kept rows", "mvicp_cluster_select", "the clustered frame has no normals");
 } MVICP_GUARD_ABI
 
 int mvicp_segment_plane(mvicp_ctx* c, int frame, long long hypotheses, unsigned long long seed, double tau, const double* axis, double cos_min, int refine,
@@ -1077,7 +1106,7 @@ long long mvicp_plane_select(mvicp_ctx* c, int inliers) try {
   if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
   if (c->plane.n < 0) { set_error("no plane result: call mvicp_segment_plane first"); return MVICP_ERR_STATE; }
   const int frame = c->plane.frame;
-  if (frame < 0 || frame >= c->n_frames || c->frames[frame].n != c->plane.n || (c->plane.n > 0 && !c->frames[frame].pts)) {
+  if (!frame_unchanged(c, frame, c->plane.n)) {
     set_error("the segmented frame is gone: call mvicp_segment_plane again");
     return MVICP_ERR_STATE;
   }
@@ -1090,13 +1119,7 @@ long long mvicp_plane_select(mvicp_ctx* c, int inliers) try {
 int mvicp_plane_fetch_kept(mvicp_ctx* c, long long cap, double* xyz, double* nrm, int* idx) try {
   if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
   if (c->plane.n < 0) { set_error("no plane result: call mvicp_segment_plane first"); return MVICP_ERR_STATE; }
-  if (c->plane.kept < 0) { set_error("no selection: call mvicp_plane_select first"); return MVICP_ERR_STATE; }
-  if (cap < c->plane.kept) { set_error("cap %lld < %lld kept rows", cap, c->plane.kept); return MVICP_ERR_ARG; }
-  if (nrm && !c->plane.has_normals) { set_error("the segmented frame has no normals"); return MVICP_ERR_STATE; }
-  if (c->plane.kept == 0) return MVICP_OK;
-  const size_t m = (size_t)c->plane.kept;
-  const FetchPart parts[] = {{xyz, c->plane.xyz, 24 * m, "xyz"}, {nrm, c->plane.nrm, 24 * m, "nrm"}, {idx, c->plane.idx, 4 * m, "idx"}};
-  return fetch_parts(c, parts);
+  return fetch_kept(c, c->plane.sel, cap, xyz, nrm, idx, nullptr, "cap", "kept rows", "mvicp_plane_select", "the segmented frame has no normals");
 } MVICP_GUARD_ABI
 
 long long mvicp_boundary(mvicp_ctx* c, int frame, int source, int max_nn, double radius, double cos_gap) try {
@@ -1110,16 +1133,7 @@ long long mvicp_boundary(mvicp_ctx* c, int frame, int source, int max_nn, double
   const FrameDev& f = c->frames[frame];
   if (!f.pts) { set_error("frame %d was never uploaded", frame); return MVICP_ERR_STATE; }
   const double* N = nullptr;
-  if (source == 0) {
-    if (f.n > 0 && !f.nor) { set_error("frame %d has no normals", frame); return MVICP_ERR_STATE; }
-    N = f.nor;
-  } else {
-    if (c->nrm.rows < 0 || c->nrm.frame != frame || c->nrm.rows != f.n) {
-      set_error("no estimated normals of frame %d: call mvicp_estimate_normals on it first (an upload to the frame drops the result)", frame);
-      return MVICP_ERR_STATE;
-    }
-    N = c->nrm.nrm;
-  }
+  MV_CHECK(normals_source(c, frame, f, source, "", &N));
   MV_CHECK(bind(c));
   MV_CHECK(finish_builds(c));
   const long long flagged = boundary_points(c, f, frame, N, max_nn, radius, radius > 0.0 ? sqrt_bound(radius) : 0.0, cos_gap);
@@ -1141,7 +1155,7 @@ long long mvicp_boundary_select(mvicp_ctx* c, int boundary) try {
   if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
   if (c->bnd.n < 0) { set_error("no boundary result: call mvicp_boundary first"); return MVICP_ERR_STATE; }
   const int frame = c->bnd.frame;
-  if (frame < 0 || frame >= c->n_frames || c->frames[frame].n != c->bnd.n || (c->bnd.n > 0 && !c->frames[frame].pts)) {
+  if (!frame_unchanged(c, frame, c->bnd.n)) {
     set_error("the frame of the boundary result is gone: call mvicp_boundary again");
     return MVICP_ERR_STATE;
   }
@@ -1154,13 +1168,7 @@ long long mvicp_boundary_select(mvicp_ctx* c, int boundary) try {
 int mvicp_boundary_fetch_kept(mvicp_ctx* c, long long cap, double* xyz, double* nrm, int* idx) try {
   if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
   if (c->bnd.n < 0) { set_error("no boundary result: call mvicp_boundary first"); return MVICP_ERR_STATE; }
-  if (c->bnd.kept < 0) { set_error("no selection: call mvicp_boundary_select first"); return MVICP_ERR_STATE; }
-  if (cap < c->bnd.kept) { set_error("cap %lld < %lld kept rows", cap, c->bnd.kept); return MVICP_ERR_ARG; }
-  if (nrm && !c->bnd.has_normals) { set_error("the frame of the boundary result has no normals"); return MVICP_ERR_STATE; }
-  if (c->bnd.kept == 0) return MVICP_OK;
-  const size_t m = (size_t)c->bnd.kept;
-  const FetchPart parts[] = {{xyz, c->bnd.xyz, 24 * m, "xyz"}, {nrm, c->bnd.nrm, 24 * m, "nrm"}, {idx, c->bnd.idx, 4 * m, "idx"}};
-  return fetch_parts(c, parts);
+  return fetch_kept(c, c->bnd.sel, cap, xyz, nrm, idx, nullptr, "cap", "kept rows", "mvicp_boundary_select", "the frame of the boundary result has no normals");
 } MVICP_GUARD_ABI
 
 // What follows a new, changed or cleared reject mask of `frame`; roles = the old and the new roles together.  Modelled on normals_changed:
@@ -1228,7 +1236,7 @@ int mvicp_boundary_adopt(mvicp_ctx* c, int roles) try {
   if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
   if (roles < 0 || roles > 3) { set_error("roles = %d outside [0, 3] (MVICP_REJECT_AS_TARGET | MVICP_REJECT_AS_SOURCE)", roles); return MVICP_ERR_ARG; }
   const int frame = c->bnd.frame;
-  if (c->bnd.n < 0 || frame < 0 || frame >= c->n_frames || c->frames[frame].n != c->bnd.n || (c->bnd.n > 0 && !c->frames[frame].pts)) {
+  if (c->bnd.n < 0 || !frame_unchanged(c, frame, c->bnd.n)) {
     set_error("no boundary result to adopt: call mvicp_boundary first (an upload to its frame drops the result)");
     return MVICP_ERR_STATE;
   }
@@ -1452,16 +1460,7 @@ long long mvicp_orient_normals(mvicp_ctx* c, int frame, int source, int k, doubl
   const FrameDev& f = c->frames[frame];
   if (!f.pts) { set_error("frame %d was never uploaded", frame); return MVICP_ERR_STATE; }
   const double* N = nullptr;
-  if (source == 0) {
-    if (f.n > 0 && !f.nor) { set_error("frame %d has no normals to orient", frame); return MVICP_ERR_STATE; }
-    N = f.nor;
-  } else {
-    if (c->nrm.rows < 0 || c->nrm.frame != frame || c->nrm.rows != f.n) {
-      set_error("no estimated normals of frame %d: call mvicp_estimate_normals on it first (an upload to the frame drops the result)", frame);
-      return MVICP_ERR_STATE;
-    }
-    N = c->nrm.nrm;
-  }
+  MV_CHECK(normals_source(c, frame, f, source, " to orient", &N));
   MV_CHECK(bind(c));
   MV_CHECK(finish_builds(c));
   const long long comps = orient_normals(c, f, N, k, radius, radius > 0.0 ? sqrt_bound(radius) : 0.0, mode, ref);
@@ -1573,14 +1572,11 @@ long long mvicp_iss_keypoints(mvicp_ctx* c, int frame, double salient_radius, do
 int mvicp_iss_fetch(mvicp_ctx* c, long long cap_keys, int* idx, double* xyz, double* nrm, long long cap_n, double* saliency, int* cnt_salient, int* cnt_nms) try {
   if (!c) { set_error("null context"); return MVICP_ERR_ARG; }
   if (c->iss.n < 0) { set_error("no keypoints: call mvicp_iss_keypoints first"); return MVICP_ERR_STATE; }
-  if ((idx || xyz || nrm) && cap_keys < c->iss.k) { set_error("cap_keys %lld < %lld keypoints", cap_keys, c->iss.k); return MVICP_ERR_ARG; }
-  if ((saliency || cnt_salient || cnt_nms) && cap_n < c->iss.n) { set_error("cap_n %lld < %lld points", cap_n, c->iss.n); return MVICP_ERR_ARG; }
-  if (nrm && !c->iss.has_normals) { set_error("the frame of the keypoints has no normals"); return MVICP_ERR_STATE; }
-  if (c->iss.n == 0) return MVICP_OK;
-  const size_t k = (size_t)c->iss.k, n = (size_t)c->iss.n;
-  const FetchPart parts[] = {{idx, c->iss.idx, 4 * k, "idx"}, {xyz, c->iss.xyz, 24 * k, "xyz"}, {nrm, c->iss.nrm, 24 * k, "nrm"},
-                             {saliency, c->iss.sal, 8 * n, "saliency"}, {cnt_salient, c->iss.cnt_s, 4 * n, "cnt_salient"}, {cnt_nms, c->iss.cnt_n, 4 * n, "cnt_nms"}};
-  return fetch_parts(c, parts);
+  const size_t n = (size_t)c->iss.n;
+  // (cap_keys counts only when a keypoint array is asked for)
+  return fetch_kept(c, c->iss.sel, (idx || xyz || nrm) ? cap_keys : c->iss.sel.kept, xyz, nrm, idx, nullptr, "cap_keys", "keypoints", "mvicp_iss_keypoints",
+                    "the frame of the keypoints has no normals", cap_n, c->iss.n,
+                    {{saliency, c->iss.sal, 8 * n, "saliency"}, {cnt_salient, c->iss.cnt_s, 4 * n, "cnt_salient"}, {cnt_nms, c->iss.cnt_n, 4 * n, "cnt_nms"}});
 } MVICP_GUARD_ABI
 
 long long mvicp_feature_match(mvicp_ctx* c, const double* a, long long m, const double* b, long long n, int dim) try {

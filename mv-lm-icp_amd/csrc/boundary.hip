@@ -15,15 +15,13 @@
 // Only comparisons, a per-lane OR and a count cross lanes, so the order the threads run in cannot show in the result.
 // Every fp64 operation is an __d*_rn intrinsic: rounded on its own, never contracted into an fma.
 //
-// mvicp_boundary_select: flag == wanted as an int, exclusive scan (rocprim), the compaction of compact_rows.h, one host wait for the number kept.
+// mvicp_boundary_select: select_rows (row_select.h) over the flag bytes, one host wait for the number kept.
 #include <algorithm>
 #include <cstring>
 
-#include <rocprim/rocprim.hpp>
-
 #include "common.h"
-#include "compact_rows.h"
 #include "normals_pca.h"
+#include "row_select.h"
 
 namespace mvicp {
 
@@ -36,7 +34,6 @@ constexpr int kCountBlocks = 1024;
 // the control block at the start of the arena; the host reads it back through the pinned copy
 struct BdCtl {
   int flagged;   // points with flag = 1 (integer atomics: exact in any order)
-  int kept;      // rows of the last selection
 };
 
 __device__ __forceinline__ double dot3(double a0, double a1, double a2, double b0, double b1, double b2) {
@@ -112,18 +109,6 @@ __global__ __launch_bounds__(kThreads) void boundary_count_kernel(const unsigned
   }
 }
 
-// the arena over n points: [control | flag bytes | open | valid | used | flag | rank | xyz | nrm | idx]
-struct Arena {
-  size_t flags, open, valid, used, flag, pos, xyz, nrm, idx, bytes;
-  explicit Arena(size_t n) {
-    size_t o = 256;
-    auto take = [&](size_t b) { const size_t at = o; o += align256(std::max<size_t>(b, 1)); return at; };
-    flags = take(n); open = take(4 * n); valid = take(4 * n); used = take(4 * n); flag = take(4 * n); pos = take(4 * n);
-    xyz = take(24 * n); nrm = take(24 * n); idx = take(4 * n);
-    bytes = o;
-  }
-};
-
 }  // namespace
 
 long long boundary_points(mvicp_ctx* c, const FrameDev& f, int frame, const double* N, int max_nn, double radius, double B2, double cos_gap) {
@@ -132,22 +117,19 @@ long long boundary_points(mvicp_ctx* c, const FrameDev& f, int frame, const doub
   const long long total = knn_search(c, f, nullptr, 0, 0, max_nn, radius, B2);
   if (total < 0) return total;
   const int n = f.n;
-  if (n == 0) { S.n = 0; S.frame = frame; S.has_normals = f.nor ? 1 : 0; return 0; }
+  if (n == 0) { S.n = 0; S.frame = frame; return 0; }
   hipStream_t st = c->stream;
   const size_t NN = (size_t)n;
-  const Arena A(NN);
-  MV_CHECK(S.dev.reserve(A.bytes));
+  // one arena: [control | flag bytes | open | valid | used]
+  const size_t o_flags = 256, o_open = o_flags + align256(NN), o_valid = o_open + align256(4 * NN), o_used = o_valid + align256(4 * NN);
+  MV_CHECK(S.dev.reserve(o_used + align256(4 * NN)));
   MV_CHECK(S.pin.reserve(256));
+  MV_CHECK(S.sel.reserve(n, false, st));   // (so that a selection allocates nothing)
   char* D = S.dev.p;
   BdCtl* d_ctl = reinterpret_cast<BdCtl*>(D);
   BdCtl* h_ctl = reinterpret_cast<BdCtl*>(S.pin.p);
-  S.flag = reinterpret_cast<unsigned char*>(D + A.flags);
-  S.open = reinterpret_cast<int*>(D + A.open); S.valid = reinterpret_cast<int*>(D + A.valid); S.used = reinterpret_cast<int*>(D + A.used);
-  {
-    size_t scan_bytes = 0;   // (mvicp_boundary_select's scan: reserved here, so that a selection allocates nothing)
-    MV_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, reinterpret_cast<int*>(D + A.flag), reinterpret_cast<int*>(D + A.pos), 0, NN, rocprim::plus<int>(), st));
-    MV_CHECK(S.tmp.reserve(std::max<size_t>(scan_bytes, 256)));
-  }
+  S.flag = reinterpret_cast<unsigned char*>(D + o_flags);
+  S.open = reinterpret_cast<int*>(D + o_open); S.valid = reinterpret_cast<int*>(D + o_valid); S.used = reinterpret_cast<int*>(D + o_used);
   MV_HIP(hipMemsetAsync(d_ctl, 0, sizeof(BdCtl), st));
   {
     // per point its position, normal, count and index row, the 13 bytes it writes; per neighbour a position (the count pass's n bytes are not counted)
@@ -162,38 +144,12 @@ long long boundary_points(mvicp_ctx* c, const FrameDev& f, int frame, const doub
   MV_HIP(hipStreamSynchronize(st));
   const int flagged = h_ctl->flagged;
   if (flagged < 0 || flagged > n) { set_error("boundary: %d flagged of %d", flagged, n); return MVICP_ERR_INTERNAL; }
-  S.n = n; S.frame = frame; S.has_normals = f.nor ? 1 : 0;
+  S.n = n; S.frame = frame;
   return flagged;
 }
 
 long long boundary_select(mvicp_ctx* c, const FrameDev& f, int boundary) {
-  BoundaryStage& S = c->bnd;
-  S.kept = -1;   // (the last selection ends here)
-  if (S.n == 0) { S.kept = 0; return 0; }
-  const int n = (int)S.n;
-  const size_t NN = (size_t)n;
-  hipStream_t st = c->stream;
-  const Arena A(NN);   // (the arena of the mvicp_boundary call this selection belongs to: same n, same offsets)
-  char* D = S.dev.p;
-  BdCtl* d_ctl = reinterpret_cast<BdCtl*>(D);
-  BdCtl* h_ctl = reinterpret_cast<BdCtl*>(S.pin.p);
-  int* flag = reinterpret_cast<int*>(D + A.flag); int* pos = reinterpret_cast<int*>(D + A.pos);
-  S.xyz = reinterpret_cast<double*>(D + A.xyz); S.nrm = f.nor ? reinterpret_cast<double*>(D + A.nrm) : nullptr;
-  S.idx = reinterpret_cast<int*>(D + A.idx);
-  {
-    ProfScope ps(c, "boundary_compact", (f.nor ? 109.0 : 61.0) * n);
-    hipLaunchKernelGGL(rows_wanted_kernel<>, dim3(grid_of(n, kCompactRowsThreads)), dim3(kCompactRowsThreads), 0, st, S.flag, n, boundary ? 1 : 0, flag);
-    size_t tb = S.tmp.cap;
-    MV_HIP(rocprim::exclusive_scan(S.tmp.p, tb, flag, pos, 0, NN, rocprim::plus<int>(), st));
-    compact_rows<false>(st, f.pts, f.nor, nullptr, flag, pos, n, S.xyz, S.nrm, S.idx, nullptr, &d_ctl->kept);
-  }
-  MV_HIP(hipGetLastError());
-  MV_HIP(hipMemcpyAsync(h_ctl, d_ctl, sizeof(BdCtl), hipMemcpyDeviceToHost, st));
-  MV_HIP(hipStreamSynchronize(st));
-  const int kept = h_ctl->kept;
-  if (kept < 0 || kept > n) { set_error("boundary select: %d kept of %d", kept, n); return MVICP_ERR_INTERNAL; }
-  S.kept = kept;
-  return kept;
+  return select_rows(c, c->bnd.sel, f, "boundary select", "boundary_compact", f.nor ? 109.0 : 61.0, c->bnd.flag, boundary ? 1 : 0);
 }
 
 }  // namespace mvicp

@@ -17,8 +17,8 @@
 //               root[i] = root[that j], or -1 (noise).  A minimum over a strict total order: the visiting order cannot matter.
 //   4  label    exclusive scan of the root flags over the original index (rocprim) = the rank of a root among the roots = the contract's
 //               numbering; label[i] = rank[root[i]]; sizes and the three counts by integer atomics, one per distinct label of a wave.
-// mvicp_cluster_select: keep byte per cluster from the host rule (mvicp_cluster_keep_rule), flag = label >= 0 and kept, scan, compact --
-// the compaction of compact_rows.h with the label as a fourth row.
+// mvicp_cluster_select: keep byte per cluster from the host rule (mvicp_cluster_keep_rule), flag = label >= 0 and kept, then select_rows
+// (row_select.h) with the label as a fourth row.
 // The radius graph is undirected because dist2 is bitwise symmetric (the differences are exact negatives, the squares drop the sign), so
 // "j < i" in the union pass loses no edge.  Every store is a plain vector store or a vector atomic; no kernel waits for another workgroup.
 #include <algorithm>
@@ -28,9 +28,9 @@
 #include <rocprim/rocprim.hpp>
 
 #include "common.h"
-#include "compact_rows.h"
 #include "knn_traverse.h"
 #include "nn_metric.h"
+#include "row_select.h"
 
 namespace mvicp {
 
@@ -39,7 +39,7 @@ namespace {
 constexpr int NT = 128;   // lanes per workgroup of the traversal kernels
 constexpr int VT = 256;   // of the streaming passes
 
-struct ClCtl { int clusters, core, border, noise, kept, pad[3]; };
+struct ClCtl { int clusters, core, border, noise; };
 
 struct ClJob {
   GridView g;
@@ -181,14 +181,13 @@ __global__ __launch_bounds__(VT) void cluster_keep_kernel(const int* __restrict_
   flag[i] = lab >= 0 && keep[lab] ? 1 : 0;
 }
 
-// the arena of a frame of n points: [control | core | parent | root | flag | rank | label | size | keep | xyz | nrm | idx | klabel]
+// the arena of a frame of n points: [control | core | parent | root | root flag | root rank | label | size | keep]
 struct Arena {
-  size_t core, parent, root, flag, pos, label, size, keep, xyz, nrm, idx, klabel, bytes;
+  size_t core, parent, root, flag, pos, label, size, keep, bytes;
   explicit Arena(size_t n) {
     size_t o = 256;
     auto take = [&](size_t b) { const size_t at = o; o += align256(std::max<size_t>(b, 1)); return at; };
     core = take(n); parent = take(4 * n); root = take(4 * n); flag = take(4 * n); pos = take(4 * n); label = take(4 * n); size = take(4 * n); keep = take(n);
-    xyz = take(24 * n); nrm = take(24 * n); idx = take(4 * n); klabel = take(4 * n);
     bytes = o;
   }
 };
@@ -215,12 +214,14 @@ long long cluster_points(mvicp_ctx* c, const FrameDev& f, int frame, double B2, 
   const Arena A(NN);
   MV_CHECK(S.dev.reserve(A.bytes));
   MV_CHECK(S.pin.reserve(256 + align256(4 * NN)));   // [control | size, later the keep bytes]
+  MV_CHECK(S.sel.reserve(n, true, st));
   char* D = S.dev.p;
   ClCtl* d_ctl = reinterpret_cast<ClCtl*>(D);
   ClCtl* h_ctl = reinterpret_cast<ClCtl*>(S.pin.p);
   int* parent = reinterpret_cast<int*>(D + A.parent); int* root = reinterpret_cast<int*>(D + A.root);
   int* flag = reinterpret_cast<int*>(D + A.flag); int* pos = reinterpret_cast<int*>(D + A.pos);
   S.core = reinterpret_cast<unsigned char*>(D + A.core); S.label = reinterpret_cast<int*>(D + A.label); S.size = reinterpret_cast<int*>(D + A.size);
+  S.keep = reinterpret_cast<unsigned char*>(D + A.keep);
   size_t scan_bytes = 0;
   MV_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, flag, pos, 0, NN, rocprim::plus<int>(), st));
   MV_CHECK(S.tmp.reserve(std::max<size_t>(scan_bytes, 256)));
@@ -274,40 +275,20 @@ long long cluster_points(mvicp_ctx* c, const FrameDev& f, int frame, double B2, 
 
 long long cluster_select(mvicp_ctx* c, const FrameDev& f, long long min_size, long long max_clusters) {
   ClusterStage& S = c->clu;
-  S.kept = -1;   // (the last selection ends here)
-  S.has_normals = f.nor ? 1 : 0;
-  if (S.n == 0) { S.kept = 0; return 0; }
+  S.sel.drop();   // (the last selection ends here, also when the keep rule fails)
   const int n = (int)S.n, C = (int)S.clusters;
-  const size_t NN = (size_t)n;
-  const bool normals = f.nor != nullptr;
-  hipStream_t st = c->stream;
-  const Arena A(NN);   // (the arena of the mvicp_cluster call this selection belongs to: same n, same offsets)
-  char* D = S.dev.p;
-  ClCtl* d_ctl = reinterpret_cast<ClCtl*>(D);
-  ClCtl* h_ctl = reinterpret_cast<ClCtl*>(S.pin.p);
-  unsigned char* h_keep = reinterpret_cast<unsigned char*>(S.pin.p + 256);
-  unsigned char* d_keep = reinterpret_cast<unsigned char*>(D + A.keep);
-  int* flag = reinterpret_cast<int*>(D + A.flag); int* pos = reinterpret_cast<int*>(D + A.pos);
-  S.xyz = reinterpret_cast<double*>(D + A.xyz); S.nrm = normals ? reinterpret_cast<double*>(D + A.nrm) : nullptr;
-  S.idx = reinterpret_cast<int*>(D + A.idx); S.klabel = reinterpret_cast<int*>(D + A.klabel);
+  const unsigned char* d_keep = S.keep;
+  const int* label = S.label;
   if (C > 0) {
+    unsigned char* h_keep = reinterpret_cast<unsigned char*>(S.pin.p + 256);
     MV_CHECK(mvicp_cluster_keep_rule(C, S.h_size.data(), min_size, max_clusters, h_keep));
-    MV_HIP(hipMemcpyAsync(d_keep, h_keep, (size_t)C, hipMemcpyHostToDevice, st));
+    MV_HIP(hipMemcpyAsync(S.keep, h_keep, (size_t)C, hipMemcpyHostToDevice, c->stream));
   }
-  {
-    ProfScope ps(c, "cluster_compact", (normals ? 112.0 : 64.0) * n);
-    hipLaunchKernelGGL(cluster_keep_kernel, dim3(grid_of(n, VT)), dim3(VT), 0, st, S.label, d_keep, n, flag);
-    size_t tb = S.tmp.cap;
-    MV_HIP(rocprim::exclusive_scan(S.tmp.p, tb, flag, pos, 0, NN, rocprim::plus<int>(), st));
-    compact_rows<true>(st, f.pts, f.nor, S.label, flag, pos, n, S.xyz, S.nrm, S.idx, S.klabel, &d_ctl->kept);
-  }
-  MV_HIP(hipGetLastError());
-  MV_HIP(hipMemcpyAsync(h_ctl, d_ctl, sizeof(ClCtl), hipMemcpyDeviceToHost, st));
-  MV_HIP(hipStreamSynchronize(st));
-  const int kept = h_ctl->kept;
-  if (kept < 0 || kept > n) { set_error("cluster select: %d kept of %d", kept, n); return MVICP_ERR_INTERNAL; }
-  S.kept = kept;
-  return kept;
+  // (the flags are this stage's to write, and the cluster_compact scope has always covered the kernel that writes them: so it is launched
+  // from inside select_rows, under the scope, and not before the call)
+  return select_rows(c, S.sel, f, "cluster select", "cluster_compact", f.nor ? 112.0 : 64.0, nullptr, 0, label, [=](hipStream_t st, int* flag) {
+    hipLaunchKernelGGL(cluster_keep_kernel, dim3(grid_of(n, VT)), dim3(VT), 0, st, label, d_keep, n, flag);
+  });
 }
 
 }  // namespace mvicp

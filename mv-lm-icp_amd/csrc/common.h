@@ -127,7 +127,9 @@ struct ProfEntry {
 // calls and grown on demand, the result arrays as views into them, and the sizes / flags, whose defaults mean "no result".  A call marks
 // its result as gone when it starts (a failed call leaves none behind) and sets it after its last wait; the result then lives until the
 // stage's next call, mvicp_set_num_frames or mvicp_destroy, and the last two release every stage through release_stages (api.cpp):
-// release() frees the buffers and assigns a default-constructed struct, so no view, size or flag can outlive them.
+// release() frees the buffers and assigns a default-constructed struct, so no view, size or flag can outlive them.  The five stages that
+// end by selecting rows of a stored cloud (outlier filter, ISS keypoints, clusters, the dominant plane, boundary points) keep those rows in
+// a RowSelection of their own, `sel`, which follows the same rules inside the stage: reserved by the stage call, dropped and released with it.
 
 inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 inline int grid_of(long long n, int threads) { return (int)((n + threads - 1) / threads); }
@@ -159,6 +161,20 @@ struct PinBuf {
   void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
 };
 
+// row_select.hip.  The rows a stage selects from a stored cloud, in ascending original index: the one owner of where they live, how they are
+// produced (select_rows, row_select.h) and when they carry normals.  dev: [kept word | flag | rank | xyz | nrm | idx | klabel, when labels were
+// asked for], tmp: rocprim storage of the scan, pin: the kept word's host copy.  A stage that selects rows holds one as `sel`; the stage call
+// reserves it (so that a selection allocates nothing), the stage's drop_result() / release() end it.  has_normals: the frame had stored normals
+// WHEN THE SELECTION RAN -- the rule for all five stages; normals that arrive later (an adopt) are in the next selection, not in this one
+struct RowSelection {
+  DevBuf dev, tmp; PinBuf pin;
+  int* flag = nullptr; int* rank = nullptr; double* xyz = nullptr; double* nrm = nullptr; int* idx = nullptr; int* klabel = nullptr;
+  long long rows = -1, kept = -1; int has_normals = 0;   // rows reserved for (< 0: none), rows of the last selection (< 0: none)
+  int reserve(long long n, bool labels, hipStream_t stream);   // row_select.hip (asks rocprim for the scan's storage); ends the last selection
+  void drop() { kept = -1; has_normals = 0; }
+  void release() { dev.release(); tmp.release(); pin.release(); *this = RowSelection(); }
+};
+
 // voxel.hip.  The result is three allocations of its own, made once the voxel count is known and freed at the start of the next call
 // (drop_result); growable are the scratch, the rocprim storage and the pinned control block
 struct VoxelStage {
@@ -172,12 +188,12 @@ struct VoxelStage {
   }
   void release() { drop_result(); scratch.release(); tmp.release(); pin.release(); *this = VoxelStage(); }
 };
-// outlier.hip.  dev: one arena [control | mdist | kd2 | flag | rank | xyz | nrm | idx], tmp: rocprim storage, pin: the control block's host copy
+// outlier.hip.  dev: one arena [control | mdist | kd2], pin: the control block's host copy, sel: the rows kept
 struct OutlierStage {
-  DevBuf dev, tmp; PinBuf pin;
-  double* xyz = nullptr; double* nrm = nullptr; double* mdist = nullptr; double* kd2 = nullptr; int* idx = nullptr;
-  long long n = -1, kept = -1; int has_normals = 0;   // n < 0: none
-  void release() { dev.release(); tmp.release(); pin.release(); *this = OutlierStage(); }
+  DevBuf dev; PinBuf pin; RowSelection sel;
+  double* mdist = nullptr; double* kd2 = nullptr;
+  long long n = -1;   // n < 0: none
+  void release() { dev.release(); pin.release(); sel.release(); *this = OutlierStage(); }
 };
 // knn.hip.  dev holds [control | cnt | off], ent the entries [idx | d2] (all mode: behind them the same in visiting order), tmp the
 // scratch (staged host queries, sort keys, rocprim storage), pin the control block's host copy
@@ -218,13 +234,13 @@ struct CoarseStage {
   int edges = -1;   // < 0: none
   void release() { dev.release(); tmp.release(); work.release(); *this = CoarseStage(); }
 };
-// iss.hip.  dev: one arena [control | saliency | cnt_salient | cnt_nms | idx | xyz | nrm | flags | ranks], tmp: rocprim storage, pin: the
-// control block's host copy
+// iss.hip.  dev: one arena [control | saliency | cnt_salient | cnt_nms], pin: the control block's host copy, sel: the keypoints' rows (sel.kept
+// = their number)
 struct IssStage {
-  DevBuf dev, tmp; PinBuf pin;
-  double* sal = nullptr; int* cnt_s = nullptr; int* cnt_n = nullptr; int* idx = nullptr; double* xyz = nullptr; double* nrm = nullptr;
-  long long n = -1, k = 0; int has_normals = 0;   // points of the frame (< 0: none), keypoints among them
-  void release() { dev.release(); tmp.release(); pin.release(); *this = IssStage(); }
+  DevBuf dev; PinBuf pin; RowSelection sel;
+  double* sal = nullptr; int* cnt_s = nullptr; int* cnt_n = nullptr;
+  long long n = -1;   // points of the frame (< 0: none)
+  void release() { dev.release(); pin.release(); sel.release(); *this = IssStage(); }
 };
 // normals_pca.hip, normals_jet.hip, smooth.hip.  dev: [nrm n x 3 doubles | curvature n doubles | used n ints | fitted n bytes, after mvicp_fit_normals only];
 // the neighbourhoods are the KnnStage result of the search the call runs.  frame: the slot the result was computed for (mvicp_normals_adopt
@@ -258,40 +274,37 @@ struct OrientStage {
   void drop_result() { rows = -1; comps = 0; frame = -1; }
   void release() { dev.release(); pin.release(); *this = OrientStage(); }
 };
-// cluster.hip.  dev: one arena [control | core | parent | root | flag | rank | label | size | keep | xyz | nrm | idx | klabel], tmp: rocprim storage,
-// pin: the host copy of [control | size, later the keep bytes]; h_size: the cluster sizes for the select rule.  frame: the slot the result was
-// computed for (mvicp_cluster_select reads its stored rows); an upload to that slot drops the result.  kept: the rows of the last
-// mvicp_cluster_select of this result (< 0: none)
+// cluster.hip.  dev: one arena [control | core | parent | root | root flag | root rank | label | size | keep], tmp: rocprim storage of the label
+// pass's scan, pin: the host copy of [control | size, later the keep bytes]; h_size: the cluster sizes for the select rule.  frame: the slot
+// the result was computed for (mvicp_cluster_select reads its stored rows); an upload to that slot drops the result.  sel: the rows of the
+// last mvicp_cluster_select of this result, with their labels
 struct ClusterStage {
-  DevBuf dev, tmp; PinBuf pin;
-  int* label = nullptr; unsigned char* core = nullptr; int* size = nullptr;
-  double* xyz = nullptr; double* nrm = nullptr; int* idx = nullptr; int* klabel = nullptr;
+  DevBuf dev, tmp; PinBuf pin; RowSelection sel;
+  int* label = nullptr; unsigned char* core = nullptr; int* size = nullptr; unsigned char* keep = nullptr;   // keep: a byte per cluster, the last select rule's
   std::vector<int> h_size;
-  long long n = -1, clusters = -1, kept = -1; int frame = -1, has_normals = 0;   // n < 0: none
-  void drop_result() { n = -1; clusters = -1; kept = -1; frame = -1; has_normals = 0; h_size.clear(); }
-  void release() { dev.release(); tmp.release(); pin.release(); *this = ClusterStage(); }
+  long long n = -1, clusters = -1; int frame = -1;   // n < 0: none
+  void drop_result() { n = -1; clusters = -1; frame = -1; h_size.clear(); sel.drop(); }
+  void release() { dev.release(); tmp.release(); pin.release(); sel.release(); *this = ClusterStage(); }
 };
-// plane.hip.  dev: one arena [control | count | accepted h | flags | flag | rank | xyz | nrm | idx], tmp: rocprim storage, pin: the host copy of
-// the control block.  frame: the slot the result was computed for (mvicp_plane_select reads its stored rows); an upload to that slot drops
-// the result.  kept: the rows of the last mvicp_plane_select of this result (< 0: none)
+// plane.hip.  dev: one arena [control | count | accepted h | flags], pin: the host copy of the control block.  frame: the slot the result was
+// computed for (mvicp_plane_select reads its stored rows); an upload to that slot drops the result.  sel: the rows of the last
+// mvicp_plane_select of this result
 struct PlaneStage {
-  DevBuf dev, tmp; PinBuf pin;
+  DevBuf dev; PinBuf pin; RowSelection sel;
   int* count = nullptr; unsigned char* flags = nullptr;
-  double* xyz = nullptr; double* nrm = nullptr; int* idx = nullptr;
-  long long n = -1, H = -1, kept = -1; int frame = -1, has_normals = 0;   // n < 0: none
-  void drop_result() { n = -1; H = -1; kept = -1; frame = -1; has_normals = 0; }
-  void release() { dev.release(); tmp.release(); pin.release(); *this = PlaneStage(); }
+  long long n = -1, H = -1; int frame = -1;   // n < 0: none
+  void drop_result() { n = -1; H = -1; frame = -1; sel.drop(); }
+  void release() { dev.release(); pin.release(); sel.release(); *this = PlaneStage(); }
 };
-// boundary.hip.  dev: one arena [control | flag bytes | open | valid | used | flag | rank | xyz | nrm | idx], tmp: rocprim storage, pin: the host
-// copy of the control block.  frame: the slot the result was computed for (mvicp_boundary_select reads its stored rows); an upload to that
-// slot drops the result.  kept: the rows of the last mvicp_boundary_select of this result (< 0: none)
+// boundary.hip.  dev: one arena [control | flag bytes | open | valid | used], pin: the host copy of the control block.  frame: the slot the
+// result was computed for (mvicp_boundary_select reads its stored rows); an upload to that slot drops the result.  sel: the rows of the
+// last mvicp_boundary_select of this result
 struct BoundaryStage {
-  DevBuf dev, tmp; PinBuf pin;
+  DevBuf dev; PinBuf pin; RowSelection sel;
   unsigned char* flag = nullptr; int* open = nullptr; int* valid = nullptr; int* used = nullptr;
-  double* xyz = nullptr; double* nrm = nullptr; int* idx = nullptr;
-  long long n = -1, kept = -1; int frame = -1, has_normals = 0;   // n < 0: none
-  void drop_result() { n = -1; kept = -1; frame = -1; has_normals = 0; }
-  void release() { dev.release(); tmp.release(); pin.release(); *this = BoundaryStage(); }
+  long long n = -1; int frame = -1;   // n < 0: none
+  void drop_result() { n = -1; frame = -1; sel.drop(); }
+  void release() { dev.release(); pin.release(); sel.release(); *this = BoundaryStage(); }
 };
 // orient.hip (mvicp_normal_agreement).  dev: [poses | per-edge pointer tables | per-edge counts | pos | neg], pin: the host copy of pos | neg
 struct AgreementStage {
@@ -523,7 +536,7 @@ long long outlier_filter(mvicp_ctx* c, const FrameDev& f, int k, double std_rati
 // overflow: MVICP_ERR_ARG, no result).  Waits for the stream once; history-neutral.
 long long cluster_points(mvicp_ctx* c, const FrameDev& f, int frame, double B2, int min_pts, mvicp_cluster_stats* stats);
 // cluster.hip: the rows of f (the frame of the last cluster_points, unchanged since: c->clu.n == f.n >= 0) whose cluster the rule
-// mvicp_cluster_keep_rule(min_size, max_clusters) keeps, compacted in ascending original index into c->clu.  Returns the rows kept or a
+// mvicp_cluster_keep_rule(min_size, max_clusters) keeps, compacted in ascending original index into c->clu.sel (select_rows).  Returns the rows kept or a
 // negative status.  Waits for the stream once; history-neutral.
 long long cluster_select(mvicp_ctx* c, const FrameDev& f, long long min_size, long long max_clusters);
 // plane.hip: the dominant plane of frame f = c->frames[frame] (valid, uploaded) over H hypotheses (1 <= H <= 2^24, finite tau > 0; axis null or
@@ -532,7 +545,7 @@ long long cluster_select(mvicp_ctx* c, const FrameDev& f, long long min_size, lo
 int plane_segment(mvicp_ctx* c, const FrameDev& f, int frame, long long H, unsigned long long seed, double tau, const double* axis, double cos_min, int refine,
                   mvicp_plane_result* out);
 // plane.hip: the rows of f (the frame of the last plane_segment, unchanged since: c->plane.n == f.n >= 0) with flag == (inliers ? 1 : 0),
-// compacted in ascending original index into c->plane.  Returns the rows kept or a negative status.  Waits for the stream once.
+// compacted in ascending original index into c->plane.sel (select_rows).  Returns the rows kept or a negative status.  Waits for the stream once.
 long long plane_select(mvicp_ctx* c, const FrameDev& f, int inliers);
 // boundary.hip: the boundary points of frame f = c->frames[frame] (valid, uploaded, structures built) by the normals N (n x 3 doubles on the
 // device: the frame's own or the last estimate's; unread when n == 0); 3 <= max_nn <= 64, B2 = sqrt_bound(radius) when radius > 0, cos_gap in
@@ -540,7 +553,7 @@ long long plane_select(mvicp_ctx* c, const FrameDev& f, int inliers);
 // number of flagged points or a negative status.  Waits for the stream; otherwise history-neutral.
 long long boundary_points(mvicp_ctx* c, const FrameDev& f, int frame, const double* N, int max_nn, double radius, double B2, double cos_gap);
 // boundary.hip: the rows of f (the frame of the last boundary_points, unchanged since: c->bnd.n == f.n >= 0) with flag == (boundary ? 1 : 0),
-// compacted in ascending original index into c->bnd.  Returns the rows kept or a negative status.  Waits for the stream once.
+// compacted in ascending original index into c->bnd.sel (select_rows).  Returns the rows kept or a negative status.  Waits for the stream once.
 long long boundary_select(mvicp_ctx* c, const FrameDev& f, int boundary);
 // knn.hip: the neighbourhoods of m queries (host or device memory, as `queries_on_device` says) or, queries == null, of the cloud's own
 // points, in frame f (valid, uploaded, structures built); 0 <= k <= 64, k == 0 needs radius > 0; B2 = sqrt_bound(radius) when radius > 0.

@@ -10,24 +10,22 @@
 //               nothing is sorted.  Then, in the same lane, D = c S - m m^T, C = D / c^2, six Jacobi sweeps and the tests; saliency and
 //               count go to the point's ORIGINAL index.
 //   2  nms      the same traversal at non_max_radius; offer reads the neighbour's saliency by its original index -> flag, count
-//   3  compact  rocprim exclusive scan of the flags; the flagged indices, ascending, and their stored rows (the fetch only copies)
+//   3  compact  select_rows (row_select.h): the flagged indices, ascending, and their stored rows (the fetch only copies)
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-
-#include <rocprim/rocprim.hpp>
 
 #include "common.h"
 #include "jacobi3.h"
 #include "knn_traverse.h"
 #include "nn_metric.h"
+#include "row_select.h"
 
 namespace mvicp {
 
 namespace {
 
 constexpr int NT = 128;          // lanes per workgroup of the two traversal passes
-constexpr int VT = 256;
 constexpr int kIssCap = 1024;    // neighbours of a salient row; more: MVICP_ERR_ARG
 constexpr int kSweeps = 6;
 constexpr unsigned int kFlagTooMany = 1u;
@@ -44,7 +42,7 @@ struct IssJob {
   int min_nb, pad;
   double* sal;            // n, original order
   int* cnt;               // n, original order: this pass's count
-  int* flag;              // n + 1, original order (pass 2; the last entry stays 0)
+  int* flag;              // n, original order (pass 2)
   IssCtl* ctl;
 };
 
@@ -116,45 +114,27 @@ __global__ __launch_bounds__(NT) void iss_nms_kernel(IssJob job) {
   job.flag[me.idx] = (mine > 0.0 && c >= job.min_nb && !beaten) ? 1 : 0;
 }
 
-// the flagged points at their rank: the original index and the stored rows
-__global__ __launch_bounds__(VT) void iss_scatter_kernel(const int* __restrict__ flag, const int* __restrict__ pos, int n, const double* __restrict__ pts,
-                                                         const double* __restrict__ nor, int* __restrict__ idx, double* __restrict__ xyz, double* __restrict__ nrm) {
-  const int i = blockIdx.x * VT + threadIdx.x;
-  if (i >= n || !flag[i]) return;
-  const size_t t = (size_t)pos[i];   // < the number of flags <= n
-  idx[t] = i;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    xyz[3 * t + a] = pts[3 * (size_t)i + a];
-    if (nor) nrm[3 * t + a] = nor[3 * (size_t)i + a];
-  }
-}
-
 }  // namespace
 
 long long iss_keypoints(mvicp_ctx* c, const FrameDev& f, double B2_salient, double B2_nms, int q, double gamma21, double gamma32, int min_neighbors) {
-  c->iss.n = -1;   // (the last result ends here; a failed call leaves none behind)
+  c->iss.n = -1; c->iss.sel.drop();   // (the last result ends here; a failed call leaves none behind)
   const int n = f.n;
   if (n > 0 && !f.has_grid) { set_error("the keypoints need the per-cloud hash structure%s%s", f.build_error.empty() ? "" : ": ", f.build_error.c_str()); return MVICP_ERR_STATE; }
-  if (n == 0) { c->iss.n = 0; c->iss.k = 0; c->iss.has_normals = 0; return 0; }
+  const auto select = [&]() { return select_rows(c, c->iss.sel, f, "iss keypoints", "iss_compact", 12.0, nullptr, 0); };
+  if (n == 0) { c->iss.n = 0; return select(); }   // (an empty selection: no launch, no wait)
   hipStream_t st = c->stream;
   const size_t N = (size_t)n;
 
-  // the result and the scratch in one arena: [control | saliency | cnt_salient | cnt_nms | idx | xyz | nrm | flag (n + 1) | rank (n + 1)]
-  const size_t o_sal = kHeadBytes, o_cs = o_sal + align256(8 * N), o_cn = o_cs + align256(4 * N), o_idx = o_cn + align256(4 * N);
-  const size_t o_xyz = o_idx + align256(4 * N), o_nrm = o_xyz + align256(24 * N), o_flag = o_nrm + align256(24 * N), o_pos = o_flag + align256(4 * (N + 1));
-  MV_CHECK(c->iss.dev.reserve(o_pos + align256(4 * (N + 1))));
-  size_t scan_bytes = 0;
-  MV_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, (int*)nullptr, (int*)nullptr, 0, N + 1, rocprim::plus<int>(), st));
-  MV_CHECK(c->iss.tmp.reserve(std::max<size_t>(scan_bytes, 256)));
+  // the per-point results in one arena: [control | saliency | cnt_salient | cnt_nms]
+  const size_t o_sal = kHeadBytes, o_cs = o_sal + align256(8 * N), o_cn = o_cs + align256(4 * N);
+  MV_CHECK(c->iss.dev.reserve(o_cn + align256(4 * N)));
   MV_CHECK(c->iss.pin.reserve(256));
+  MV_CHECK(c->iss.sel.reserve(n, false, st));
   char* D = c->iss.dev.p;
   IssCtl* d_ctl = reinterpret_cast<IssCtl*>(D);
+  IssCtl* h_ctl = reinterpret_cast<IssCtl*>(c->iss.pin.p);
   c->iss.sal = reinterpret_cast<double*>(D + o_sal); c->iss.cnt_s = reinterpret_cast<int*>(D + o_cs); c->iss.cnt_n = reinterpret_cast<int*>(D + o_cn);
-  c->iss.idx = reinterpret_cast<int*>(D + o_idx); c->iss.xyz = reinterpret_cast<double*>(D + o_xyz); c->iss.nrm = reinterpret_cast<double*>(D + o_nrm);
-  int* d_flag = reinterpret_cast<int*>(D + o_flag); int* d_pos = reinterpret_cast<int*>(D + o_pos);
   MV_HIP(hipMemsetAsync(d_ctl, 0, sizeof(IssCtl), st));
-  MV_HIP(hipMemsetAsync(d_flag + N, 0, 4, st));
 
   IssJob j;
   std::memset(&j, 0, sizeof(j));
@@ -164,7 +144,7 @@ long long iss_keypoints(mvicp_ctx* c, const FrameDev& f, double B2_salient, doub
   MV_CHECK(stage_tree_view(g, c->iss.pin.p + kTreeOffset, D + kTreeOffset, st, &j.tree));
   j.scale = std::ldexp(1.0, q); j.unscale = std::ldexp(1.0, -2 * q);
   j.g21 = gamma21; j.g32 = gamma32; j.min_nb = min_neighbors;
-  j.sal = c->iss.sal; j.flag = d_flag; j.ctl = d_ctl;
+  j.sal = c->iss.sal; j.flag = c->iss.sel.flag; j.ctl = d_ctl;
   {
     ProfScope ps(c, "iss_moments", 44.0 * n);
     j.B2 = B2_salient; j.cnt = c->iss.cnt_s;
@@ -177,24 +157,16 @@ long long iss_keypoints(mvicp_ctx* c, const FrameDev& f, double B2_salient, doub
     hipLaunchKernelGGL(iss_nms_kernel, dim3(grid_of(n, NT)), dim3(NT), 0, st, j);
     MV_HIP(hipGetLastError());
   }
-  {
-    ProfScope ps(c, "iss_compact", 12.0 * n);
-    size_t tb = scan_bytes;
-    MV_HIP(rocprim::exclusive_scan(c->iss.tmp.p, tb, d_flag, d_pos, 0, N + 1, rocprim::plus<int>(), st));
-    hipLaunchKernelGGL(iss_scatter_kernel, dim3(grid_of(n, VT)), dim3(VT), 0, st, d_flag, d_pos, n, f.pts, f.nor, c->iss.idx, c->iss.xyz, c->iss.nrm);
-    MV_HIP(hipGetLastError());
-  }
-  IssCtl* h_ctl = reinterpret_cast<IssCtl*>(c->iss.pin.p);
-  int* h_total = reinterpret_cast<int*>(c->iss.pin.p + 16);
-  MV_HIP(hipMemcpyAsync(h_ctl, d_ctl, sizeof(IssCtl), hipMemcpyDeviceToHost, st));
-  MV_HIP(hipMemcpyAsync(h_total, d_pos + N, 4, hipMemcpyDeviceToHost, st));
-  MV_HIP(hipStreamSynchronize(st));
+  MV_HIP(hipMemcpyAsync(h_ctl, d_ctl, sizeof(IssCtl), hipMemcpyDeviceToHost, st));   // (read after the selection's wait)
+  const long long keys = select();
+  if (keys < 0) return keys;
   if (h_ctl->flags & kFlagTooMany) {
+    c->iss.sel.drop();
     set_error("iss keypoints: a point has more than %d neighbours within the salient radius (smaller radius?)", kIssCap);
     return MVICP_ERR_ARG;
   }
-  c->iss.n = n; c->iss.k = *h_total; c->iss.has_normals = f.nor ? 1 : 0;
-  return c->iss.k;
+  c->iss.n = n;
+  return keys;
 }
 
 }  // namespace mvicp

@@ -12,8 +12,7 @@
 //               n < 2^31): wave reduction, then three 64-bit integer atomics per workgroup.  Integer sums: order-independent.
 //      -- host wait: the sums; T = mvicp_outlier_threshold --
 //   3  flag     keep = ((double)M <= T) and (sqrt(kd2) < radius), each rule only when it is on
-//   4  compact  exclusive scan of the flags (rocprim), then compact_rows.h: one lane per point stores its row at its rank
-//      -- host wait: the number kept --
+//   4  compact  select_rows (row_select.h): the flagged rows at their rank, one host wait for the number kept
 // What the knn kernel keeps to itself next to the other users of traverse() (this kernel is the whole feature):
 //   * the list capacity is a template parameter (9 / 17 / 33 doubles per lane, one LDS column per lane): 9 / 17 / 33 KiB per 128-lane
 //     workgroup, so k <= 8 still runs at the 32-waves-per-CU cap, k <= 16 at 18 waves and only k > 16 at 8 (160 KiB of LDS per CU);
@@ -25,12 +24,10 @@
 #include <cmath>
 #include <cstring>
 
-#include <rocprim/rocprim.hpp>
-
 #include "common.h"
-#include "compact_rows.h"
 #include "knn_traverse.h"
 #include "nn_metric.h"
+#include "row_select.h"
 
 namespace mvicp {
 
@@ -46,7 +43,7 @@ struct KnnJob {
   unsigned long long* mmax;      // bit pattern of the largest mdist
 };
 
-struct OutCtl { unsigned long long mmax, s1, s2lo, s2hi; int kept, pad; };
+struct OutCtl { unsigned long long mmax, s1, s2lo, s2hi; };
 
 template <int KCAP>
 __global__ __launch_bounds__(NT) void outlier_knn_kernel(KnnJob job) {
@@ -130,34 +127,27 @@ __global__ __launch_bounds__(VT) void outlier_flag_kernel(const double* __restri
 }  // namespace
 
 long long outlier_filter(mvicp_ctx* c, const FrameDev& f, int k, double std_ratio, double radius, mvicp_outlier_stats* stats) {
-  c->out.n = -1; c->out.kept = -1;   // (the last result ends here; a failed call leaves none behind)
+  c->out.n = -1; c->out.sel.drop();   // (the last result ends here; a failed call leaves none behind)
   mvicp_outlier_stats S;
   std::memset(&S, 0, sizeof(S));
   S.n = f.n; S.has_normals = f.nor ? 1 : 0;
-  c->out.has_normals = f.nor ? 1 : 0;
-  if (f.n == 0) { c->out.n = 0; c->out.kept = 0; if (stats) *stats = S; return 0; }
+  const auto select = [&]() { return select_rows(c, c->out.sel, f, "outlier filter", "outlier_compact", f.nor ? 108.0 : 60.0, nullptr, 0); };
+  if (f.n == 0) { c->out.n = 0; if (stats) *stats = S; return select(); }   // (an empty selection: no launch, no wait)
   if (!f.has_grid) { set_error("the outlier filter needs the per-cloud hash structure"); return MVICP_ERR_STATE; }
   const int n = f.n;
   const size_t NN = (size_t)n;
-  const bool normals = f.nor != nullptr, stat_on = std_ratio >= 0.0, rad_on = radius > 0.0;
+  const bool stat_on = std_ratio >= 0.0, rad_on = radius > 0.0;
   hipStream_t st = c->stream;
 
-  // one arena: [control | mdist | kd2 | flag | rank | xyz | nrm | idx]; the results are views into it
-  const size_t off_md = 256, off_kd = off_md + align256(8 * NN), off_fl = off_kd + align256(8 * NN), off_ps = off_fl + align256(4 * NN);
-  const size_t off_x = off_ps + align256(4 * NN), off_nr = off_x + align256(24 * NN), off_ix = off_nr + (normals ? align256(24 * NN) : 0);
-  const size_t bytes = off_ix + align256(4 * NN);
-  MV_CHECK(c->out.dev.reserve(bytes));
+  // one arena: [control | mdist | kd2]; the per-point results are views into it
+  const size_t off_md = 256, off_kd = off_md + align256(8 * NN);
+  MV_CHECK(c->out.dev.reserve(off_kd + align256(8 * NN)));
   MV_CHECK(c->out.pin.reserve(256));
+  MV_CHECK(c->out.sel.reserve(n, false, st));
   char* D = c->out.dev.p;
   OutCtl* d_ctl = reinterpret_cast<OutCtl*>(D);
   OutCtl* h_ctl = reinterpret_cast<OutCtl*>(c->out.pin.p);
   c->out.mdist = reinterpret_cast<double*>(D + off_md); c->out.kd2 = reinterpret_cast<double*>(D + off_kd);
-  int* flag = reinterpret_cast<int*>(D + off_fl); int* pos = reinterpret_cast<int*>(D + off_ps);
-  c->out.xyz = reinterpret_cast<double*>(D + off_x); c->out.nrm = normals ? reinterpret_cast<double*>(D + off_nr) : nullptr;
-  c->out.idx = reinterpret_cast<int*>(D + off_ix);
-  size_t scan_bytes = 0;
-  MV_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, flag, pos, 0, NN, rocprim::plus<int>(), st));
-  MV_CHECK(c->out.tmp.reserve(std::max<size_t>(scan_bytes, 256)));
 
   MV_HIP(hipMemsetAsync(d_ctl, 0, sizeof(OutCtl), st));
   KnnJob j;
@@ -198,23 +188,14 @@ long long outlier_filter(mvicp_ctx* c, const FrameDev& f, int k, double std_rati
   }
   {
     ProfScope ps(c, "outlier_flag", 20.0 * n);
-    hipLaunchKernelGGL(outlier_flag_kernel, dim3(grid_of(n, VT)), dim3(VT), 0, st, c->out.mdist, c->out.kd2, n, stat, q, T, rad_on ? 1 : 0, radius, flag);
+    hipLaunchKernelGGL(outlier_flag_kernel, dim3(grid_of(n, VT)), dim3(VT), 0, st, c->out.mdist, c->out.kd2, n, stat, q, T, rad_on ? 1 : 0, radius, c->out.sel.flag);
   }
   MV_HIP(hipGetLastError());
-  {
-    ProfScope ps(c, "outlier_compact", (normals ? 108.0 : 60.0) * n);
-    size_t tb = scan_bytes;
-    MV_HIP(rocprim::exclusive_scan(c->out.tmp.p, tb, flag, pos, 0, NN, rocprim::plus<int>(), st));
-    compact_rows<false>(st, f.pts, f.nor, nullptr, flag, pos, n, c->out.xyz, c->out.nrm, c->out.idx, nullptr, &d_ctl->kept);
-  }
-  MV_HIP(hipGetLastError());
-  MV_HIP(hipMemcpyAsync(h_ctl, d_ctl, sizeof(OutCtl), hipMemcpyDeviceToHost, st));
-  MV_HIP(hipStreamSynchronize(st));
-  const int kept = h_ctl->kept;
-  if (kept < 0 || kept > n) { set_error("outlier filter: %d kept of %d", kept, n); return MVICP_ERR_INTERNAL; }
+  const long long kept = select();
+  if (kept < 0) return kept;
   S.kept = kept;
   if (stats) *stats = S;
-  c->out.n = n; c->out.kept = kept;
+  c->out.n = n;
   return kept;
 }
 

@@ -23,17 +23,15 @@
 //      Passes 4 to 6 run at most kStreamBlocks workgroups whose lanes stride through the cloud: atomics on one address are served one
 //      after the other, so their number is bounded by the grid and not by the cloud.
 //      -- host wait: the number of refined inliers --
-// mvicp_plane_select: flag == wanted as an int, exclusive scan (rocprim), the compaction of compact_rows.h, one host wait for the number kept.
+// mvicp_plane_select: select_rows (row_select.h) over the flag bytes, one host wait for the number kept.
 // Every store is a plain vector store or a vector atomic; no kernel waits for another workgroup.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 
-#include <rocprim/rocprim.hpp>
-
 #include "common.h"
-#include "compact_rows.h"
 #include "cons_pose.h"
+#include "row_select.h"
 
 namespace mvicp {
 
@@ -54,7 +52,7 @@ constexpr int kStreamBlocks = 1024;
 struct PlDir { int on, pad; double ax, ay, az, rhs; };
 
 struct PlCtl {
-  int n_acc, final_count, b, q, kept, pad;
+  int n_acc, final_count, b, q, pad[2];
   unsigned long long key;    // the winner's (count + 1) << 32 | (2^32 - 1 - h); 0: nothing accepted
   unsigned long long omax;   // bit pattern of the largest |offset| over the winner's inliers
   long long mom[10];         // c, s0 s1 s2, S00 S01 S02 S11 S12 S22
@@ -234,18 +232,6 @@ __global__ __launch_bounds__(kThreads) void plane_final_kernel(const double* __r
   }
 }
 
-// the arena of H hypotheses over n points: [control | count | accepted h | flags | flag | rank | xyz | nrm | idx]
-struct Arena {
-  size_t count, hidx, flags, flag, pos, xyz, nrm, idx, bytes;
-  Arena(size_t H, size_t n) {
-    size_t o = 256;
-    auto take = [&](size_t b) { const size_t at = o; o += align256(std::max<size_t>(b, 1)); return at; };
-    count = take(4 * H); hidx = take(4 * H); flags = take(n); flag = take(4 * n); pos = take(4 * n);
-    xyz = take(24 * n); nrm = take(24 * n); idx = take(4 * n);
-    bytes = o;
-  }
-};
-
 double plane_d(const double* m, const double* g) { return -((m[0] * g[0] + m[1] * g[1]) + m[2] * g[2]); }   // (this file is built without fma contraction)
 
 }  // namespace
@@ -261,19 +247,16 @@ int plane_segment(mvicp_ctx* c, const FrameDev& f, int frame, long long H, unsig
   const size_t NN = (size_t)n, NH = (size_t)H;
   hipStream_t st = c->stream;
 
-  const Arena A(NH, NN);
-  MV_CHECK(S.dev.reserve(A.bytes));
+  // one arena: [control | count | accepted h | flags]
+  const size_t o_count = 256, o_hidx = o_count + align256(4 * NH), o_flags = o_hidx + align256(4 * NH);
+  MV_CHECK(S.dev.reserve(o_flags + align256(std::max<size_t>(NN, 1))));
   MV_CHECK(S.pin.reserve(256));
+  if (n > 0) MV_CHECK(S.sel.reserve(n, false, st));   // (so that a selection allocates nothing)
   char* D = S.dev.p;
   PlCtl* d_ctl = reinterpret_cast<PlCtl*>(D);
   PlCtl* h_ctl = reinterpret_cast<PlCtl*>(S.pin.p);
-  S.count = reinterpret_cast<int*>(D + A.count); S.flags = reinterpret_cast<unsigned char*>(D + A.flags);
-  int* hidx = reinterpret_cast<int*>(D + A.hidx);
-  if (n > 0) {
-    size_t scan_bytes = 0;   // (mvicp_plane_select's scan: reserved here, so that a selection allocates nothing)
-    MV_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, reinterpret_cast<int*>(D + A.flag), reinterpret_cast<int*>(D + A.pos), 0, NN, rocprim::plus<int>(), st));
-    MV_CHECK(S.tmp.reserve(std::max<size_t>(scan_bytes, 256)));
-  }
+  S.count = reinterpret_cast<int*>(D + o_count); S.flags = reinterpret_cast<unsigned char*>(D + o_flags);
+  int* hidx = reinterpret_cast<int*>(D + o_hidx);
 
   PlDir dir;
   std::memset(&dir, 0, sizeof(dir));
@@ -359,38 +342,12 @@ int plane_segment(mvicp_ctx* c, const FrameDev& f, int frame, long long H, unsig
     R.d = plane_d(R.normal, R.point);
   }
   if (out) *out = R;
-  S.n = n; S.H = H; S.frame = frame; S.has_normals = R.has_normals;
+  S.n = n; S.H = H; S.frame = frame;
   return MVICP_OK;
 }
 
 long long plane_select(mvicp_ctx* c, const FrameDev& f, int inliers) {
-  PlaneStage& S = c->plane;
-  S.kept = -1;   // (the last selection ends here)
-  if (S.n == 0) { S.kept = 0; return 0; }
-  const int n = (int)S.n;
-  const size_t NN = (size_t)n;
-  hipStream_t st = c->stream;
-  const Arena A((size_t)S.H, NN);   // (the arena of the mvicp_segment_plane call this selection belongs to: same H, same n, same offsets)
-  char* D = S.dev.p;
-  PlCtl* d_ctl = reinterpret_cast<PlCtl*>(D);
-  PlCtl* h_ctl = reinterpret_cast<PlCtl*>(S.pin.p);
-  int* flag = reinterpret_cast<int*>(D + A.flag); int* pos = reinterpret_cast<int*>(D + A.pos);
-  S.xyz = reinterpret_cast<double*>(D + A.xyz); S.nrm = f.nor ? reinterpret_cast<double*>(D + A.nrm) : nullptr;
-  S.idx = reinterpret_cast<int*>(D + A.idx);
-  {
-    ProfScope ps(c, "plane_compact", (f.nor ? 109.0 : 61.0) * n);
-    hipLaunchKernelGGL(rows_wanted_kernel<>, dim3(grid_of(n, kCompactRowsThreads)), dim3(kCompactRowsThreads), 0, st, S.flags, n, inliers ? 1 : 0, flag);
-    size_t tb = S.tmp.cap;
-    MV_HIP(rocprim::exclusive_scan(S.tmp.p, tb, flag, pos, 0, NN, rocprim::plus<int>(), st));
-    compact_rows<false>(st, f.pts, f.nor, nullptr, flag, pos, n, S.xyz, S.nrm, S.idx, nullptr, &d_ctl->kept);
-  }
-  MV_HIP(hipGetLastError());
-  MV_HIP(hipMemcpyAsync(h_ctl, d_ctl, sizeof(PlCtl), hipMemcpyDeviceToHost, st));
-  MV_HIP(hipStreamSynchronize(st));
-  const int kept = h_ctl->kept;
-  if (kept < 0 || kept > n) { set_error("plane select: %d kept of %d", kept, n); return MVICP_ERR_INTERNAL; }
-  S.kept = kept;
-  return kept;
+  return select_rows(c, c->plane.sel, f, "plane select", "plane_compact", f.nor ? 109.0 : 61.0, c->plane.flags, inliers ? 1 : 0);
 }
 
 }  // namespace mvicp

@@ -611,8 +611,6 @@ class Engine:
         self.n_frames = 0
         self.E = 0
         self.rank, self.world = rank, world
-        self._cluster_has_nrm = False   # the frame of the last cluster() had normals
-        self._plane_has_nrm = False     # the frame of the last segment_plane() had normals
         if world > 1:
             _check(self.lib, self.lib.mvicp_set_shard(self.h, rank, world))
 
@@ -838,6 +836,24 @@ class Engine:
                 lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None,
                 lambda: None, np.float64, np.int32, np.int64, np.uint8)
 
+    def _fetch_kept(self, fetch, kept, device, label=False):
+        """The kept rows of a selection -> dict(xyz (kept,3), nrm (kept,3) or None, idx (kept,) int32, and with label=True label (kept,)
+        int32).  fetch(xyz, nrm, idx, label) is the stage's fetch call with the row pointers in these places.  The selection carries
+        normals iff its frame had stored normals when it ran, and the C calls have no record that says so: asking for them answers it -- a
+        refusal is MVICP_ERR_STATE and writes nothing; with no rows nothing is written either way, so any non-NULL pointer asks."""
+        mk, ptr, ready, f64, i32, i64, u8 = self._result_arrays(device)
+        out = {"xyz": mk((kept, 3), f64), "nrm": mk((kept, 3), f64), "idx": mk((kept,), i32)}
+        if label:
+            out["label"] = mk((kept,), i32)
+        ready()
+        st = fetch(None, ptr(out["nrm"]) if kept else C.c_void_p(8), None, None)
+        if st == -3:   # (MVICP_ERR_STATE: no normals -- or no result at all, which the fetch below then reports)
+            out["nrm"] = None
+        else:
+            _check(self.lib, st)
+        _check(self.lib, fetch(ptr(out["xyz"]), None, ptr(out["idx"]), ptr(out.get("label"))))
+        return out
+
     def voxel_grid(self, voxel, frames=None, poses=None, device=False):
         """mvicp_voxel_grid + mvicp_voxel_fetch: the points of `frames` (a list of distinct frame indices; None = all), at `poses` ((K,4,4);
         None = as stored), reduced to one point per voxel of edge `voxel` -> dict(xyz (m,3), nrm (m,3) or None, cnt (m,) int32), rows in
@@ -870,13 +886,14 @@ class Engine:
         S = OutlierStats()
         kept = int(_check(self.lib, self.lib.mvicp_outlier_filter(self.h, int(frame), int(k), float(std_ratio), float(radius), C.byref(S))))
         n = int(S.n)
-        has_nrm = bool(S.has_normals)
         mk, ptr, ready, f64, i32, i64, u8 = self._result_arrays(device)
-        xyz, nrm, idx = mk((kept, 3), f64), (mk((kept, 3), f64) if has_nrm else None), mk((kept,), i32)
         mdist, kd2 = mk((n,), f64), mk((n,), f64)
-        ready()
-        _check(self.lib, self.lib.mvicp_outlier_fetch(self.h, kept, ptr(xyz), ptr(nrm), ptr(idx), n, ptr(mdist), ptr(kd2)))
-        return {"xyz": xyz, "nrm": nrm, "idx": idx, "mdist": mdist, "kd2": kd2, "stats": S.as_dict()}
+        # (_fetch_kept calls this twice: first with nrm alone, to learn whether normals come along, then with the rows and nrm = None.  The
+        # per-point arrays mdist / kd2 are copied once, by the second call)
+        out = self._fetch_kept(lambda xyz, nrm, idx, label: self.lib.mvicp_outlier_fetch(self.h, kept, xyz, nrm, idx, n, None if nrm else ptr(mdist),
+                                                                                          None if nrm else ptr(kd2)), kept, device)
+        out.update(mdist=mdist, kd2=kd2, stats=S.as_dict())
+        return out
 
     def cluster(self, frame, radius, min_pts=4, device=False):
         """mvicp_cluster + mvicp_cluster_fetch on the stored cloud of `frame`: DBSCAN with the strict radius predicate of knn_search, the
@@ -887,7 +904,6 @@ class Engine:
         S = ClusterStats()
         nc = int(_check(self.lib, self.lib.mvicp_cluster(self.h, int(frame), float(radius), int(min_pts), C.byref(S))))
         n = int(S.n)
-        self._cluster_has_nrm = bool(S.has_normals)
         mk, ptr, ready, f64, i32, i64, u8 = self._result_arrays(device)
         label, core, size = mk((n,), i32), mk((n,), u8), mk((nc,), i32)
         ready()
@@ -899,12 +915,9 @@ class Engine:
         keeps (noise always goes), in ascending original index -> dict(xyz (kept,3), nrm (kept,3) or None, idx (kept,) int32, label (kept,)
         int32, kept).  device=True: torch tensors on the engine's GPU (xyz / nrm ready for set_frame_device)."""
         kept = int(_check(self.lib, self.lib.mvicp_cluster_select(self.h, int(min_size), int(max_clusters))))
-        mk, ptr, ready, f64, i32, i64, u8 = self._result_arrays(device)
-        xyz, idx, label = mk((kept, 3), f64), mk((kept,), i32), mk((kept,), i32)
-        nrm = mk((kept, 3), f64) if self._cluster_has_nrm else None   # (normals cannot leave a frame without an upload, which ends the result)
-        ready()
-        _check(self.lib, self.lib.mvicp_cluster_fetch_kept(self.h, kept, ptr(xyz), ptr(nrm), ptr(idx), ptr(label)))
-        return {"xyz": xyz, "nrm": nrm, "idx": idx, "label": label, "kept": kept}
+        out = self._fetch_kept(lambda xyz, nrm, idx, label: self.lib.mvicp_cluster_fetch_kept(self.h, kept, xyz, nrm, idx, label), kept, device, label=True)
+        out["kept"] = kept
+        return out
 
     def segment_plane(self, frame, tau, hypotheses=1024, seed=0, axis=None, cos_min=0.0, refine=True, device=False):
         """mvicp_segment_plane + mvicp_plane_fetch on the stored cloud of `frame`: the plane with the most points within tau among
@@ -917,7 +930,6 @@ class Engine:
         ax = None if axis is None else np.ascontiguousarray(axis, dtype=np.float64).reshape(3)
         _check(self.lib, self.lib.mvicp_segment_plane(self.h, int(frame), int(hypotheses), int(seed) & (2 ** 64 - 1), float(tau), _dp(ax) if ax is not None else None,
                                                       float(cos_min), 1 if refine else 0, C.byref(R)))
-        self._plane_has_nrm = bool(R.has_normals)
         mk, ptr, ready, f64, i32, i64, u8 = self._result_arrays(device)
         counts, flags = mk((int(hypotheses),), i32), mk((int(R.n),), u8)
         ready()
@@ -931,12 +943,9 @@ class Engine:
         in ascending original index -> dict(xyz (kept,3), nrm (kept,3) or None, idx (kept,) int32, kept).  device=True: torch tensors on
         the engine's GPU (xyz / nrm ready for set_frame_device)."""
         kept = int(_check(self.lib, self.lib.mvicp_plane_select(self.h, 1 if inliers else 0)))
-        mk, ptr, ready, f64, i32, i64, u8 = self._result_arrays(device)
-        xyz, idx = mk((kept, 3), f64), mk((kept,), i32)
-        nrm = mk((kept, 3), f64) if self._plane_has_nrm else None   # (normals cannot leave a frame without an upload, which ends the result)
-        ready()
-        _check(self.lib, self.lib.mvicp_plane_fetch_kept(self.h, kept, ptr(xyz), ptr(nrm), ptr(idx)))
-        return {"xyz": xyz, "nrm": nrm, "idx": idx, "kept": kept}
+        out = self._fetch_kept(lambda xyz, nrm, idx, label: self.lib.mvicp_plane_fetch_kept(self.h, kept, xyz, nrm, idx), kept, device)
+        out["kept"] = kept
+        return out
 
     def boundary(self, frame, max_nn=30, radius=0.0, cos_gap=-0.5, source=0, device=False):
         """mvicp_boundary + mvicp_boundary_fetch on the stored cloud of `frame`: a point is flagged when, in its tangent plane (normals of
@@ -958,18 +967,9 @@ class Engine:
         ascending original index -> dict(xyz (kept,3), nrm (kept,3) or None, idx (kept,) int32, kept).  device=True: torch tensors on
         the engine's GPU (xyz / nrm ready for set_frame_device)."""
         kept = int(_check(self.lib, self.lib.mvicp_boundary_select(self.h, 1 if boundary else 0)))
-        mk, ptr, ready, f64, i32, i64, u8 = self._result_arrays(device)
-        xyz, nrm, idx = mk((kept, 3), f64), mk((kept, 3), f64), mk((kept,), i32)
-        ready()
-        # (the C call has no record that says whether the frame has stored normals: asking for them answers it -- a refusal is MVICP_ERR_STATE
-        # and writes nothing; with no rows nothing is written either way, so any non-NULL pointer asks)
-        st = self.lib.mvicp_boundary_fetch_kept(self.h, kept, None, ptr(nrm) if kept else C.c_void_p(8), None)
-        if st == -3:
-            nrm = None
-        else:
-            _check(self.lib, st)
-        _check(self.lib, self.lib.mvicp_boundary_fetch_kept(self.h, kept, ptr(xyz), None, ptr(idx)))
-        return {"xyz": xyz, "nrm": nrm, "idx": idx, "kept": kept}
+        out = self._fetch_kept(lambda xyz, nrm, idx, label: self.lib.mvicp_boundary_fetch_kept(self.h, kept, xyz, nrm, idx), kept, device)
+        out["kept"] = kept
+        return out
 
     def reject_correspondences(self, dst_masks, src_masks=None):
         """Drops from every list this engine owns the pairs that end on a flagged point: per owned edge e = (s, d) get_correspondences(e),

@@ -235,6 +235,16 @@ def test_small_n(eng):
         assert check(eng, two[:1], None, 0.1, m, "one point", frame=1)["stats"]["clusters"] == clusters
     for radius, m, clusters in ((0.0101, 1, 1), (0.0101, 2, 1), (0.0101, 3, 0), (0.01, 1, 2), (0.0099, 2, 0)):   # within, exactly at (strict) and beyond the radius
         assert check(eng, two, None, radius, m, "two points", frame=2)["stats"]["clusters"] == clusters
+    # one workgroup of the compaction with a lane to spare, exactly full, and one point in a second workgroup: a selection in between,
+    # then one cluster of everything kept whole (min_size 0) and dropped whole (min_size n + 1)
+    for n, kept in ((255, 238), (256, 232), (257, 235)):
+        p, nr, _ = outlierref.sheet_cloud(n, 100 + n)
+        eng.set_frames([p], [nr])
+        assert cr.select(p, nr, reference(p, 0.08, 4, True), 5, 0)["kept"] == kept
+        check(eng, p, nr, 0.08, 4, "sheet of %d" % n, rules=((5, 0),))
+        whole = reference(p, 10.0, 1, True)
+        assert whole["stats"]["clusters"] == 1 and cr.select(p, nr, whole, 0, 0)["kept"] == n and cr.select(p, nr, whole, n + 1, 0)["kept"] == 0
+        check(eng, p, nr, 10.0, 1, "sheet of %d, one cluster" % n, rules=((0, 0), (n + 1, 0)), device=(n == 256))
 
 
 def test_frames_and_memory(eng):

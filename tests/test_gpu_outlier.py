@@ -80,6 +80,17 @@ def test_size_sweep(eng, n, k):
     assert_same(eng.outlier_filter(0, k, 2.0, 0.0), want, (n, k))
 
 
+@pytest.mark.parametrize("n,kept", [(255, 237), (256, 229), (257, 239)])
+def test_one_workgroup_of_the_compaction(eng, n, kept):
+    """255 / 256 / 257 rows: one workgroup of the row compaction with a lane to spare, exactly full, and one point in a second one."""
+    p, nr, planted = sheet(n)
+    want = sheet_ref(n, 8, 1.0, 0.0)
+    assert len(want["idx"]) == kept
+    eng.set_frames([p], [nr])
+    assert_same(eng.outlier_filter(0, 8, 1.0, 0.0), want, (n, "host"))
+    assert_same(eng.outlier_filter(0, 8, 1.0, 0.0, device=True), want, (n, "device"))
+
+
 @pytest.mark.parametrize("k,std_ratio,radius", pathcases.O1_PARAMS)
 def test_far_from_the_origin(eng, k, std_ratio, radius):
     """O1: a cloud of 1 mm extent at UTM coordinates (|p| > 4e6, the spacing of the doubles there is a nanometre), one case per list

@@ -12,6 +12,7 @@ import pytest
 import clusterref
 import matchref
 import mvicp
+import outlierref
 import planeref as pr
 from mvicp import synth
 
@@ -131,6 +132,16 @@ def test_small_n(eng):
     assert three["count"] == 3 and three["refit"] == 1 and three["best"] == 0
     got = eng.segment_plane(0, 0.01, 64, device=True)
     assert got["flags"].shape == (0,) and got["counts"].shape == (64,) and eng.plane_select(False, device=True)["xyz"].shape == (0, 3)
+    one = reference(p[:1], False, 0.01, 64)
+    assert pr.select(p[:1], None, one, True)["kept"] == 0 and pr.select(p[:1], None, one, False)["kept"] == 1   # (checked above: frame 1)
+    # one workgroup of the compaction with a lane to spare, exactly full, and one point in a second workgroup; the last point is an inlier,
+    # so the number kept comes from a kept row in one selection and from a dropped row in the other
+    for n, kept in ((255, (249, 6)), (256, (250, 6)), (257, (251, 6))):
+        q, nr, _ = outlierref.sheet_cloud(n, 100 + n)
+        want = reference(q, True, 0.01, 200, seed=7 + n)
+        assert (pr.select(q, nr, want, True)["kept"], pr.select(q, nr, want, False)["kept"]) == kept and want["flags"][-1] == 1
+        eng.set_frames([q], [nr])
+        check(eng, q, nr, 0.01, 200, "sheet of %d" % n, seed=7 + n)
 
 
 def test_direction(eng):
